@@ -36,9 +36,15 @@ on another GPU -- spanning the devices, every exchange, the process group's barr
 (GLAZE_BENCH_WATCHDOG_SPAN_S, default 180 s, to span the devices; GLAZE_BENCH_WATCHDOG_S, default 90 s, per exchange or barrier) it prints `multi_gpu.diagnostics` (which call, how long, RCCL
 version, the peer-access matrix, bytes per peer, the RCCL / HSA environment) to stderr and ends the process with status 3 through os._exit.
 
-The timed region is EXACTLY K steps between barrier + synchronize pairs, MAX over ranks.  A region shorter than 0.5 s is
-repeated (five regions in all, the accumulation simply continues) and `value` comes from the MEDIAN region; every
-region's time is listed under "regions_ms".
+The timed region is EXACTLY K steps between barrier + synchronize pairs, MAX over ranks.  `--repeats R` times R such regions
+(the accumulation simply continues) and `value` comes from the MEDIAN region; every region's time is listed under "regions_ms".
+With the default R = 1 a region well under a second is one sample of the launch time: for a number to compare builds by, take K large
+enough for a region of a second or more, or --repeats 5.
+
+--dump-outputs DIR: right after the timed regions, the arrays the timed path computed by its last step are written as DIR/<name>.npy
+(float32): `hdr`, the HDR accumulator (xyz = summed radiance, w = launches; at N > 1 the frame assembled on GPU 0) and, at N = 1,
+`result`, the per-pixel result image.  The scene, seed and launch sequence are fixed by the arguments, so two builds run with the same
+arguments can be compared array for array.
 """
 import argparse
 import json
@@ -67,7 +73,9 @@ def parse_args():
     ap.add_argument("--verify", dest="verify", action="store_true", default=True,
                     help="N > 1: rank 0 re-renders the whole frame alone and compares it bit for bit (default)")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of K steps each (0 = five when a region is shorter than 0.5 s, else one)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions of K steps each (`value` and `ms_per_step` from the median one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed by its last step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the two rocprofv3 --pmc passes that measure roofline.traffic (N = 1 only)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)     # this process IS one of those passes: render only
     ap.add_argument("--scene", default=os.environ.get("GLAZE_BENCH_SCENE") or None,
@@ -79,7 +87,10 @@ def parse_args():
     ap.add_argument("--no-config5", dest="config5", action="store_false")
     ap.add_argument("--no-extras", action="store_true", help="N = 1: do not time the other BASELINE configurations and the Sponza-like atrium after the timed regions")
     ap.add_argument("--no-configs", action="store_true", help="N = 1: do not time BASELINE configs 2, 3 and 5 (extra.configs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.repeats < 1 or args.warmup < 0:
+        ap.error("--steps and --repeats must be at least 1, --warmup at least 0")
+    return args
 
 
 PMC_PASSES = (("FETCH_SIZE",), ("WRITE_SIZE",), ("SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "SQ_THREAD_CYCLES_VALU", "SQ_BUSY_CYCLES"))
@@ -267,6 +278,24 @@ def algorithmic_bytes(c):
     shadow = 48 * c["f_shadow"] + 48 * c["f_shadow"] + 64 * c["nodes_shadow"] + 36 * c["tris_shadow"]
     # k_trace traverses the closest-hit rays of a launch and the shadow rays of the launch before it in one kernel
     return {"k_trace": closest + shadow + c.get("tex_bytes_trace", 0.0), "k_shade": shade}
+
+
+DUMP_BUDGET = {"hdr": 48_000_000, "result": 12_000_000}     # bytes per array: 60 MB in all, under the 64 MB --dump-outputs allows
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every HxWx4 array as out_dir/<name>.npy in float32.  One larger than its DUMP_BUDGET share is replaced by a
+    fixed, seeded sample of its pixels (K x 4, rows in pixel order): the same pixels for the same frame size, run after run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > DUMP_BUDGET[name]:
+            px = a.reshape(-1, a.shape[-1])
+            keep = DUMP_BUDGET[name] // px[0].nbytes
+            a = px[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -510,12 +539,14 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    regions = [timed_region()]
-    # every rank sees the same (max-reduced) first time, so all of them take the same number of regions
-    n_regions = args.repeats if args.repeats > 0 else (5 if regions[0] < 0.5 else 1)
-    while len(regions) < n_regions:
-        regions.append(timed_region())
+    regions = [timed_region() for _ in range(args.repeats)]
     s1 = renderer.stats()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left, before anything below renders again; N > 1: the exchange carries the accumulator only
+        if n_gpus > 1:
+            dump_outputs(args.dump_outputs, {"hdr": frame.cpu().numpy()})
+        else:
+            dump_outputs(args.dump_outputs, {"hdr": renderer.read_hdr(), "result": renderer.read_result()})
     # the exchange alone (it is INSIDE every timed region above; this is only to show its share): nothing new was rendered,
     # so it moves the same frame again
     exchange_ms = None

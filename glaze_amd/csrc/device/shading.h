@@ -288,7 +288,8 @@ GLZ_D vec2 ggx_sample_p22(float cost, vec2 r) {   // :23-55
   float G1 = 2.0f / (1.0f + sqrtf(1.0f + 1.0f / a2));
   float A = 2.0f * r.x / G1 - 1.0f;
   float B = tant;
-  float invA2m1 = 1.0f / (A * A - 1.0f);
+  // r.x = 0 gives A = -1 and 1 / 0: clamped as the usual statement of this sampler does (float32 never reaches 1e10 otherwise)
+  float invA2m1 = A * A - 1.0f == 0.0f ? 1e10f : 1.0f / (A * A - 1.0f);
   float sq = sqrtf(gl_max(0.0f, B * B * invA2m1 * invA2m1 - (A * A - B * B) * invA2m1));
   float sx1 = B * invA2m1 - sq;
   float sx2 = B * invA2m1 + sq;
@@ -308,7 +309,8 @@ GLZ_D float ggx_d(vec3 wh, vec2 a) {   // :57-69
   float tan2t = sin2t / cos2t;
   float cos2p = wh.x * wh.x / sin2t;
   float sin2p = wh.y * wh.y / sin2t;
-  float e1 = 1.0f + ((cos2p / (a.x * a.x) + sin2p / (a.y * a.y)) * tan2t);
+  // wh on the pole (|z| rounds to 1): tan2t = 0 but the azimuth terms are x^2 / 0, and 0 * inf would be NaN; the limit is e1 = 1
+  float e1 = sin2t == 0.0f ? 1.0f : 1.0f + ((cos2p / (a.x * a.x) + sin2p / (a.y * a.y)) * tan2t);
   float d = 1.0f / (kPi * a.x * a.y * cos4t * e1 * e1);
   return isinf(tan2t) ? 0.0f : d;
 }
@@ -320,7 +322,7 @@ GLZ_D float ggx_lambda(vec3 v, vec2 a) {   // :71-82
   float sin2p = gl_max(0.0f, v.y * v.y / sin2t);
   float alpha2 = cos2p * a.x * a.x + sin2p * a.y * a.y;
   float lambda = (-1.0f + sqrtf(1.0f + tan2t * alpha2)) * 0.5f;
-  return isinf(tan2t) ? 0.0f : lambda;
+  return isinf(tan2t) || sin2t == 0.0f ? 0.0f : lambda;     // on the pole: lambda -> 0 (0 * inf would be NaN)
 }
 GLZ_D float ggx_g(vec3 wo, vec3 wi, vec2 a) { return 1.0f / (1.0f + ggx_lambda(wo, a) + ggx_lambda(wi, a)); }   // :84-87
 GLZ_D float ggx_pdf(float d, vec2 a, vec3 wo, vec3 wh) {   // :94-99, G1 of wh (Q6)
@@ -333,8 +335,9 @@ GLZ_D vec3 ggx_sample_wh(vec3 wo, vec2 r, vec2 a) {   // :102-120
   float cost = ws.z;
   vec2 slope = ggx_sample_p22(cost, r);
   float sin2t = gl_max(0.0f, 1.0f - cost * cost);
-  float cosp = sqrtf(ws.x * ws.x / sin2t);
-  float sinp = sqrtf(ws.y * ws.y / sin2t);
+  // ws on the pole: its azimuth is undefined (x^2 / 0), any rotation of the isotropic slope serves; take none
+  float cosp = sin2t == 0.0f ? 1.0f : sqrtf(ws.x * ws.x / sin2t);
+  float sinp = sin2t == 0.0f ? 0.0f : sqrtf(ws.y * ws.y / sin2t);
   float sx = cosp * slope.x - sinp * slope.y;
   float sy = sinp * slope.x + cosp * slope.y;
   return flip * normalize3(mk3(-a.x * sx, -a.y * sy, 1.0f));

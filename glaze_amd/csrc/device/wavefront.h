@@ -22,7 +22,6 @@ constexpr uint32_t kQueueShards = 8;     // shadow-ray sub-queues (see queue_slo
 constexpr uint32_t kCounterStride = 32;  // uint32 words between shard counters (128 bytes)
 constexpr uint32_t kFlagUpdate = 1u;    // update_result() is called for this pixel in this launch
 constexpr uint32_t kFlagShadow = 2u;    // the contribution is gated by a shadow ray
-constexpr uint32_t kFlagPoison = 4u;    // 0 * (|cos|/pdf) * radiance is NaN: an occluded sample still poisons the pixel
 
 // ---------------------------------------------------------------------------------------------
 // pixel <-> thread mapping
@@ -1440,7 +1439,7 @@ struct DirectState {
   __device__ __forceinline__ void ray_d(uint32_t lid, float4 v) { A.st.ray_d[lid] = v; }
   __device__ __forceinline__ void imp(int q, uint32_t lid, float4 v) { A.st.imp[q][lid] = v; }
   __device__ __forceinline__ float4 read_imp(int q, uint32_t lid) const { return A.st.imp[q][lid]; }
-  __device__ __forceinline__ void accumulate(uint32_t lid, vec3 c, bool add, bool update, float exposure) { accumulate_pixel(A, lid, c, add, update, exposure); }
+  __device__ __forceinline__ void accumulate(uint32_t lid, vec3 c, bool add, bool update, float exposure) { accumulate_pixel(A, lid, c, add && isfinite(c.x + c.y + c.z), update, exposure); }
 };
 struct StagedState {
 #ifdef GLZ_SECTION_TIMES
@@ -1468,7 +1467,7 @@ struct StagedState {
     const u32x4 v = lds_imp[q * kShadeBlockPixels];
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
   }
-  __device__ __forceinline__ void accumulate(uint32_t lid, vec3 cc, bool add, bool update, float exposure) { accumulate_pixel(*A, lid, cc, add, update, exposure); }
+  __device__ __forceinline__ void accumulate(uint32_t lid, vec3 cc, bool add, bool update, float exposure) { accumulate_pixel(*A, lid, cc, add && isfinite(cc.x + cc.y + cc.z), update, exposure); }
 };
 // Returns 0 when the pixel's next path state has been written (or, with the direct-light integrator, is not needed), 1 / 2 when the path
 // has ENDED and its reset is left to shade_pixel below: 1 = only ray_o is to be written (a miss: ray_d keeps its flag), 2 = ray_o and
@@ -1633,33 +1632,28 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
       if (bpdf > 0.0f) {
         // weight_light = (1 or 0) * |cos| / pdf; radiance = value*emission*weight*lights_no*importance
         const float w_vis = 1.0f * (fabsf(dot3(ls.wiW, ns)) / ls.pdf);
-        const float w_occ = 0.0f * (fabsf(dot3(ls.wiW, ns)) / ls.pdf);
         const float nl = (float)F.lights_no;
         const Spec emission = light_emission(ls);
         const Spec importance = load_importance();
         imp_lum = spec_luminance(importance);
         have_lum = true;
         Spec rad;
-        float poison = 0.0f;
         GLZ_BINS {
           const float rl = value.w[i] * emission.w[i];
           rad.w[i] = ((rl * w_vis) * nl) * importance.w[i];
-          poison += ((rl * w_occ) * nl) * importance.w[i];
         }
         c = spec_to_rgb(rad);
-        flags |= kFlagShadow | (poison == poison ? 0u : kFlagPoison);
+        if (!isfinite(c.x + c.y + c.z)) c = mk3(0.0f, 0.0f, 0.0f);     // a NaN / Inf sample adds nothing, occluded or not
+        flags |= kFlagShadow;
         sh_dir = ls.wiW;
         sh_tmax = ls.distance - 1e-3f;
       }
     }
     if (!(flags & kFlagShadow)) {
-      // no light sample: the reference still adds rgb(0 * lights_no * importance), which is NaN for a non-finite importance
+      // no light sample: the reference adds rgb(0 * lights_no * importance), zero or (non-finite importance) a NaN that adds nothing
       const Spec importance = load_importance();
       imp_lum = spec_luminance(importance);
       have_lum = true;
-      float probe = 0.0f;
-      GLZ_BINS probe += 0.0f * importance.w[i];
-      if (probe != probe) c = spec_to_rgb(spec_scale(importance, 0.0f * (float)F.lights_no));
     }
     // shadow-ray queue (consumed by the next launch's k_trace); pixels without a shadow ray are accumulated right here
     const bool push = (flags & kFlagShadow) != 0;
@@ -1774,14 +1768,8 @@ struct ShadowSink {
   ShadowSource& src;
   __device__ __forceinline__ void store(uint32_t, const HitRecord& h) {
     const bool occluded = h.leaf != 0xFFFFFFFFu;
-    const uint32_t flags = __float_as_uint(src.contrib.w);
-    vec3 c = mk3(src.contrib.x, src.contrib.y, src.contrib.z);
-    bool add = !occluded;
-    if (occluded && (flags & kFlagPoison)) {
-      const float nan = __uint_as_float(0x7FC00000u);
-      c = mk3(nan, nan, nan);
-      add = true;
-    }
+    const vec3 c = mk3(src.contrib.x, src.contrib.y, src.contrib.z);
+    const bool add = !occluded;
     accumulate_pixel(A, src.lid, c, add, true, A.shadow_exposure);
   }
 };

@@ -82,14 +82,8 @@ struct GroupShadowSink {
   float exposure;          // of the launch that queued the rays
   __device__ __forceinline__ void store(uint32_t, const HitRecord& h) {
     const bool occluded = h.leaf != 0xFFFFFFFFu;
-    const uint32_t flags = __float_as_uint(src.contrib.w);
-    vec3 c = mk3(src.contrib.x, src.contrib.y, src.contrib.z);
-    bool add = !occluded;
-    if (occluded && (flags & kFlagPoison)) {
-      const float nan = __uint_as_float(0x7FC00000u);
-      c = mk3(nan, nan, nan);
-      add = true;
-    }
+    const vec3 c = mk3(src.contrib.x, src.contrib.y, src.contrib.z);
+    const bool add = !occluded;
     accumulate_pixel(A, src.lid, c, add, true, exposure, src.cum);
   }
 };

@@ -1180,7 +1180,8 @@ V2 ggx_sample_p22(float cost, V2 r) {                                    // micr
   float G1 = 2.0f / (1.0f + sqrtf(1.0f + 1.0f / a2));
   float A = 2.0f * r.x / G1 - 1.0f;
   float B = tant;
-  float invA2m1 = 1.0f / (A * A - 1.0f);
+  // r.x = 0 gives A = -1 and 1 / 0: clamped as the usual statement of this sampler does (float32 never reaches 1e10 otherwise)
+  float invA2m1 = A * A - 1.0f == 0.0f ? 1e10f : 1.0f / (A * A - 1.0f);
   float sqrt_term = sqrtf(gmax(0.0f, B * B * invA2m1 * invA2m1 - (A * A - B * B) * invA2m1));
   float sx1 = B * invA2m1 - sqrt_term;
   float sx2 = B * invA2m1 + sqrt_term;
@@ -1202,7 +1203,8 @@ float ggx_d(V3 wh, V2 a) {                                               // micr
   float tan2t = sin2t / cos2t;
   float cos2p = wh.x * wh.x / sin2t;
   float sin2p = wh.y * wh.y / sin2t;
-  float eplus1 = 1.0f + ((cos2p / (a.x * a.x) + sin2p / (a.y * a.y)) * tan2t);
+  // wh on the pole (|z| rounds to 1): tan2t = 0 but the azimuth terms are x^2 / 0, and 0 * inf would be NaN; the limit is 1
+  float eplus1 = sin2t == 0.0f ? 1.0f : 1.0f + ((cos2p / (a.x * a.x) + sin2p / (a.y * a.y)) * tan2t);
   float d = 1.0f / (PI * a.x * a.y * cos4t * eplus1 * eplus1);
   return isinf(tan2t) ? 0.0f : d;
 }
@@ -1216,7 +1218,7 @@ float ggx_lambda(V3 v, V2 a) {                                           // micr
   float sin2p = gmax(0.0f, v.y * v.y / sin2t);
   float alpha2 = cos2p * a.x * a.x + sin2p * a.y * a.y;
   float lambda = (-1.0f + sqrtf(1.0f + tan2t * alpha2)) * 0.5f;
-  return isinf(tan2t) ? 0.0f : lambda;
+  return isinf(tan2t) || sin2t == 0.0f ? 0.0f : lambda;     // on the pole: lambda -> 0 (0 * inf would be NaN)
 }
 float ggx_g(V3 wo, V3 wi, V2 a) { return 1.0f / (1.0f + ggx_lambda(wo, a) + ggx_lambda(wi, a)); }   // :84-87
 float ggx_g1(V3 v, V2 a) { return 1.0f / (1.0f + ggx_lambda(v, a)); }                                // :89-92
@@ -1230,8 +1232,9 @@ V3 ggx_sample_wh(V3 wo, V2 r, V2 a) {                                    // micr
   V2 slope = ggx_sample_p22(cost, r);
   float cos2t = cost * cost;
   float sin2t = gmax(0.0f, 1.0f - cos2t);
-  float cosp = sqrtf(ws.x * ws.x / sin2t);
-  float sinp = sqrtf(ws.y * ws.y / sin2t);
+  // ws on the pole: its azimuth is undefined (x^2 / 0), any rotation of the isotropic slope serves; take none
+  float cosp = sin2t == 0.0f ? 1.0f : sqrtf(ws.x * ws.x / sin2t);
+  float sinp = sin2t == 0.0f ? 0.0f : sqrtf(ws.y * ws.y / sin2t);
   float sx = cosp * slope.x - sinp * slope.y;
   float sy = sinp * slope.x + cosp * slope.y;
   return flip * normalize(v3(-a.x * sx, -a.y * sy, 1.0f));
@@ -1860,7 +1863,7 @@ void raygen(Renderer& R, const FrameConsts& fc, uint32_t px, uint32_t py) {
   float* out = &R.out32[path_id * 4];
   auto update_result = [&](const Sp& radiance) {                         // :126-133
     V3 c = sp_rgb(radiance);
-    cum[0] += c.x; cum[1] += c.y; cum[2] += c.z;
+    if (std::isfinite(c.x + c.y + c.z)) { cum[0] += c.x; cum[1] += c.y; cum[2] += c.z; }     // a NaN / Inf sample adds nothing
     out[0] = cum[0] * R.exposure / cum[3];
     out[1] = cum[1] * R.exposure / cum[3];
     out[2] = cum[2] * R.exposure / cum[3];

@@ -5,7 +5,11 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from glaze_amd.scenes import atrium_scene
+from oracle.pyoracle import OracleRenderer, OracleScene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MATTEST = os.path.join(ROOT, "tests", "golden", "mattest.glaze")
@@ -51,3 +55,31 @@ def test_bench_on_an_obj_through_the_converter():
     out, err = run_bench("--scene", CUBE_OBJ, "--no-cpu-baseline")
     assert out["data"] == "file:cube.obj" and out["config"]["triangles"] == 12
     assert "has no lights" in err
+
+
+def test_bench_dumps_what_its_timed_steps_computed(tmp_path):
+    """--dump-outputs on the synthetic atrium: exactly --warmup + --steps launches reached every pixel (the accumulator's w), both arrays
+    are finite and are what the oracle computes for the same scene, seed and launches (the accumulator and the result image, not a
+    stale buffer), and a second run with the same arguments writes the same arrays bit for bit."""
+    dumps = []
+    for tag in ("a", "b"):
+        out, _ = run_bench("--no-cpu-baseline", "--no-extras", "--dump-outputs", str(tmp_path / tag))
+        assert out["steps"] == 8 and len(out["regions_ms"]) == 1 and out["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / tag)) == ["hdr.npy", "result.npy"]
+        dumps.append({n: np.load(tmp_path / tag / (n + ".npy")) for n in ("hdr", "result")})
+    for d in dumps:
+        assert d["hdr"].dtype == np.float32 and d["hdr"].shape == (192, 256, 4) and d["result"].shape == (192, 256, 4)
+        assert (d["hdr"][..., 3] == 2 + 8).all() and d["hdr"][..., :3].max() > 0
+        assert np.isfinite(d["hdr"]).all() and np.isfinite(d["result"]).all()
+    for n in ("hdr", "result"):
+        assert np.array_equal(dumps[0][n].view(np.uint32), dumps[1][n].view(np.uint32)), n
+    o = OracleRenderer(OracleScene(atrium_scene()), 256, 192)
+    o.set_depth(8)
+    o.set_seed(0)
+    o.restart()
+    o.step(2 + 8)
+    for n, want in (("hdr", o.read_hdr()), ("result", o.read_result())):
+        got = dumps[0][n]
+        assert np.array_equal(got[..., 3], want[..., 3]), n
+        rel = np.abs(got[..., :3] - want[..., :3]) / np.maximum(np.abs(want[..., :3]), 1e-6)
+        assert (rel.max(-1) <= 1e-4).mean() >= 0.999, n

@@ -598,10 +598,8 @@ def test_full_size_properties_atrium(instance, atrium_file):
     r.step(16)
     a = r.read_hdr()
     assert (a[..., 3] == 16.0).all()                         # update_count on every pixel, every launch
-    # a handful of pixels may legitimately go NaN (0/0 in the reference's GGX terms at exactly-normal half
-    # vectors, faithfully kept); the oracle produces the same NaN set (checked at 1080p by tools/gpu_diag.py)
-    finite = np.isfinite(a).all(-1)
-    assert finite.mean() > 0.99999 and a[finite][:, :3].mean() > 0
+    # every pixel finite: the GGX terms take their limits where the reference divides 0 by 0 (a half vector on the pole)
+    assert np.isfinite(a).all() and a[..., :3].mean() > 0
     r.restart()
     r.step(16)
     assert np.array_equal(a.view(np.uint32), r.read_hdr().view(np.uint32))   # same seed stream -> bit-identical
