@@ -51,10 +51,6 @@ struct LbvhOutputs {
 hipError_t build_lbvh(hipStream_t st, const LbvhInputs& in, LbvhOutputs& out);
 // top-of-tree table for LDS staging (types.h kBvhTopNodes): `top` receives kBvhTopNodes nodes
 hipError_t launch_top_table(hipStream_t st, const BvhNode4* nodes, uint32_t n_nodes, BvhNode4* top);
-#ifdef GLZ_NODE48
-// experiment: 64-byte nodes -> 48-byte nodes (types.h BvhNode48), n of them
-hipError_t launch_compress_nodes(hipStream_t st, const BvhNode4* nodes, uint32_t n, BvhNode48* out);
-#endif
 // 128-byte per-leaf shading records (see k_shade_records); xf_identity[t] != 0 marks an exact identity transform
 hipError_t launch_shade_records(hipStream_t st, uint32_t n, const BvhTri* tris, const RTInstance* instances, const uint32_t* indices,
                                 const float4* vertices, const float4* derivatives, const uint32_t* xf_identity, float4* out);
@@ -121,7 +117,7 @@ struct LaunchArgs {
   float shadow_exposure;     // exposure of the launch that queued the shadow rays (update_result uses it)
 };
 // The launches one k_path call runs (kernels_path.hip): what differs between launches, by value in the kernel arguments (16 bytes a
-// launch next to the 848 of LaunchArgs: 192 launches stay inside the 4 KB the arguments may take).  Long batches matter: the kernel
+// launch next to the 880 of LaunchArgs: 192 launches stay inside the 4 KB the arguments may take).  Long batches matter: the kernel
 // ends when its slowest wave does, and a wave's time per launch scatters by ~20 % -- over 16 launches the slowest of 4 096 waves is
 // 27 % above the mean, over 192 launches 8 %.
 constexpr uint32_t kPathMaxLaunches = 192;

@@ -152,7 +152,7 @@ template <bool LOD>
 __global__ void __launch_bounds__(kBlock, GLZ_PATH_WAVES) k_path(const LaunchArgs A, const PathBatch B) {
   __shared__ int s_stack[kLdsStack * kBlock];
   __shared__ alignas(1024) int s_aux[kAuxPerBlock];
-  __shared__ uint4 s_top[kLdsTop ? kBvhTopNodes * 4 : 1];
+  __shared__ uint4 s_top[kBvhTopNodes * 4];
   __shared__ float s_lut[256];
   __shared__ float4 s_hit[kBlock];
   extern __shared__ uint4 s_dyn[];   // [RTMaterial x n_materials | RTLight x n_rt_lights | TexDesc x n_textures] when B.tables_in_lds

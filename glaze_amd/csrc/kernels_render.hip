@@ -17,10 +17,7 @@ using namespace dev;
 // ---------------------------------------------------------------------------------------------
 // k_shade: path_trace.rgen:170-237 minus the two traceRayEXT calls, raytrace_hit.rchit:30-71
 // ---------------------------------------------------------------------------------------------
-#ifndef GLZ_SKY_LDS_FLOATS
-#define GLZ_SKY_LDS_FLOATS 1088
-#endif
-constexpr uint32_t kSkyLdsFloats = GLZ_SKY_LDS_FLOATS;   // (skies of up to 1 087 rows; a taller one is searched in memory)
+constexpr uint32_t kSkyLdsFloats = 1088;   // (skies of up to 1 087 rows; a taller one is searched in memory)
 constexpr uint32_t kShadeLdsTableBytes = 8192;   // k_shade's LDS copy of the material / light / texture-descriptor tables (38 materials; larger tables are read from memory)   // the sky's marginal cdf (H + 1 floats) is staged in LDS when it fits (the values and row integrals next to it are read once per sample, from memory: staging all 3 H + 1 floats was 12 of the 19 KB a block copies before it starts)
 
 // (GLZ_SHADE_WAVES = 4, device/tuning.h: 128 VGPRs, 4 of them spilled, since the light's spectrum is made after the BSDF evaluation and the
@@ -52,9 +49,7 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   uint4* s_imp = s_pool;
   float* s_sky = reinterpret_cast<float*>(s_pool + kShadeBlock * 4);
   uint4* s_tables = s_pool + kShadeBlock * 4 + kSkyLdsFloats / 4;
-#ifndef GLZ_SHADE_SLOT_TIMING
   static_assert(6u * kShadeBlock <= kShadeBlock * 4 + kSkyLdsFloats / 4 + kShadeLdsTableBytes / 16, "the staging area of the path state fits the pool");
-#endif
   // The small scene tables every hit walks through one after the other -- shading record -> RTMaterial -> texture descriptor
   // -> texels, light pick -> RTLight -- are staged in LDS when they fit: each lookup that stays on chip takes a dependent
   // memory round trip (1-2 us under load, the kernel's bound) off the hit's critical path.
@@ -163,13 +158,7 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   }
   __syncthreads();
   {
-    uint32_t pos = s_bin[(threadIdx.x >> 6) * 64u + key] + rank;   // the pixel's place in the block's order by code path
-#ifdef GLZ_SHADE_DEAL   // EXPERIMENT: the sorted sequence dealt to the four waves in chunks of GLZ_SHADE_DEAL pixels instead of 64 (balance against purity)
-    constexpr uint32_t kChunk = GLZ_SHADE_DEAL, kPerWave = 64u / kChunk;
-    const uint32_t chunk = pos / kChunk;
-    pos = (chunk % kShadeWavesPerBlock) * 64u + (chunk / kShadeWavesPerBlock) * kChunk + pos % kChunk;
-    static_assert(kPerWave * kChunk == 64u, "chunk divides a wave");
-#endif
+    const uint32_t pos = s_bin[(threadIdx.x >> 6) * 64u + key] + rank;   // the pixel's place in the block's order by code path
     s_perm[pos] = (uint16_t)threadIdx.x;
   }
   __syncthreads();
@@ -195,18 +184,6 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
 #ifdef GLZ_SECTION_TIMES
   ks_last = __builtin_amdgcn_s_memtime();
 #endif
-#ifdef GLZ_SHADE_SLOT_TIMING   // TIMING ONLY (images are wrong): every thread stores the state it made at ITS OWN index -- whole lines without the meeting at the barrier, what a slot-indexed path state would do; the pixels of a block exchange paths, the workload stays what it is
-  {
-    const LaunchArgs& A3 = A;
-    const uint32_t at = blockIdx.x * kShadeBlock + threadIdx.x;
-    if (staged.mask & 1u) A3.st.ray_o[at] = staged.ro;
-    if (staged.mask & 2u) A3.st.ray_d[at] = staged.rd;
-    if (staged.mask & 4u) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) A3.st.imp[q][at] = staged.im[q];
-    }
-  }
-#else
   {
     // The regrouped threads would store 16-byte pieces scattered over the block's 4 KB of each state array (six arrays); the L2 has
     // to assemble the lines.  Thread i stores pixel i's state instead: the values travel through LDS, which nobody needs any more
@@ -231,7 +208,6 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
       for (int q = 0; q < 4; ++q) A3.st.imp[q][at] = stage[(2u + q) * kShadeBlock + threadIdx.x];
     }
   }
-#endif
   if (COUNT) flush_tex_tallies(A.counters->shade_tex, tex_tally);   // every lane of the wave is here (the counting build returns nowhere above)
 #ifdef GLZ_SECTION_TIMES
   if (!COUNT) {
@@ -257,7 +233,7 @@ template <bool COUNT, int ALPHA>
 __global__ void __launch_bounds__(kBlock, GLZ_TRACE_WAVES) k_trace(const LaunchArgs A) {
   __shared__ int s_stack[kLdsStack * kBlock];
   __shared__ alignas(1024) int s_aux[kAuxPerBlock];
-  __shared__ uint4 s_top[kLdsTop ? kBvhTopNodes * 4 : 1];
+  __shared__ uint4 s_top[kBvhTopNodes * 4];
   static_assert(kBvhTopNodes * 4 <= kBlock, "stage_top copies one 16-byte piece per thread");
   GLZ_WAVE_STAMP(0);
   stage_top(A.scene, s_top);
@@ -272,9 +248,8 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE_WAVES) k_trace(const LaunchA
     counted_scene.tex_counter = tex_tally;
   }
   const DeviceScene& TS = COUNT ? counted_scene : A.scene;
-#if GLZ_TRACE_SPLIT
-  // Waves that specialise (device/tuning.h GLZ_TRACE_SPLIT): with more 64-ray groups than waves, a share of the waves -- GLZ_TRACE_SPLIT_NUM /
-  // _DEN of the shadow groups' share of all groups, spread evenly over the grid wave by wave -- takes only shadow groups and the others only
+  // Waves that specialise: with more 64-ray groups than waves, a share of the waves -- GLZ_TRACE_SPLIT_NUM / _DEN (device/tuning.h)
+  // of the shadow groups' share of all groups, spread evenly over the grid wave by wave -- takes only shadow groups and the others only
   // closest-hit groups: a wave then drains ONCE, at the end of the kernel, instead of once per kind, and a CU holds waves of both kinds at
   // all times.  With fewer groups than waves every group gets a wave of its own either way.  The counting kernels keep the two passes per wave.
   uint32_t split_closest = A.do_closest, split_shadow = A.do_shadow, split_wave_c = wave_index(), split_waves_c = wave_count(), split_wave_s = 0, split_waves_s = 0;
@@ -310,32 +285,6 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE_WAVES) k_trace(const LaunchA
   }
   GLZ_WAVE_STAMP(1);
   if (split_shadow) {
-    const uint32_t* counts = A.st.queue_count + (A.shade_set ^ 1u) * kQueueSetWords;
-    uint32_t start[kQueueShards + 1];
-    start[0] = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kQueueShards; ++k) start[k + 1] = start[k] + counts[k * kCounterStride];
-    TraceTally tally;
-    ShadowSource src{A, start, queue_capacity(A.map.n_local_pixels), 0u, make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
-    ShadowSink sink{A, src};
-    uint32_t n_waves = wave_count();
-    const uint32_t closest_groups = A.do_closest ? (A.map.n_local_pixels + 63u) / 64u : 0u;
-    uint32_t wave = (wave_index() + n_waves - closest_groups % n_waves) % n_waves;   // (not specialised: the shadow groups dealt behind the closest-hit ones)
-    if (split) { wave = split_wave_s; n_waves = split_waves_s; }
-    trace_wave<true, COUNT, false, GLZ_TRACE_PREFETCH != 0, false, ALPHA>(TS, src, sink, &s_stack[threadIdx.x], aux, links, (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, start[kQueueShards], wave, n_waves, tally);
-    if (COUNT) flush_counters(A.counters, true, tally);
-  }
-#else
-  if (A.do_closest) {
-    TraceTally tally;
-    ClosestSource src{A, A.frame, tally, 0u};
-    ClosestSink sink{A};
-    trace_wave<false, COUNT, false, GLZ_TRACE_PREFETCH != 0, false, ALPHA>(TS, src, sink, &s_stack[threadIdx.x], aux, links, (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, A.map.n_local_pixels, wave_index(),
-                                                         wave_count(), tally);
-    if (COUNT) flush_counters(A.counters, false, tally);
-  }
-  GLZ_WAVE_STAMP(1);
-  if (A.do_shadow) {
     // prefix sums of the eight shard counts (final: the k_shade that filled them has completed)
     const uint32_t* counts = A.st.queue_count + (A.shade_set ^ 1u) * kQueueSetWords;
     uint32_t start[kQueueShards + 1];
@@ -345,16 +294,16 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE_WAVES) k_trace(const LaunchA
     TraceTally tally;
     ShadowSource src{A, start, queue_capacity(A.map.n_local_pixels), 0u, make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
     ShadowSink sink{A, src};
-    // The shadow groups are dealt out starting at the wave after the one that received the last closest-hit group: with
-    // fewer groups than waves (a small tile share per GPU) every group of either kind gets a wave of its own, with more
-    // the per-wave totals stay level.
-    const uint32_t n_waves = wave_count();
+    // When the waves do not specialise, the shadow groups are dealt out starting at the wave after the one that received the last
+    // closest-hit group: with fewer groups than waves (a small tile share per GPU) every group of either kind gets a wave of its own,
+    // with more the per-wave totals stay level.
+    uint32_t n_waves = wave_count();
     const uint32_t closest_groups = A.do_closest ? (A.map.n_local_pixels + 63u) / 64u : 0u;
-    const uint32_t wave = (wave_index() + n_waves - closest_groups % n_waves) % n_waves;
+    uint32_t wave = (wave_index() + n_waves - closest_groups % n_waves) % n_waves;
+    if (split) { wave = split_wave_s; n_waves = split_waves_s; }
     trace_wave<true, COUNT, false, GLZ_TRACE_PREFETCH != 0, false, ALPHA>(TS, src, sink, &s_stack[threadIdx.x], aux, links, (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, start[kQueueShards], wave, n_waves, tally);
     if (COUNT) flush_counters(A.counters, true, tally);
   }
-#endif
   if (COUNT) flush_tex_tallies(A.counters->trace_tex, tex_tally);
   GLZ_WAVE_STAMP(2);
 }
@@ -517,7 +466,7 @@ __global__ void __launch_bounds__(kBlock) k_debug_closest(const DeviceScene S, c
                                                           uint32_t* overflow, uint32_t overflow_depth) {
   __shared__ int s_stack[kLdsStack * kBlock];
   __shared__ alignas(1024) int s_aux[kAuxPerBlock];
-  __shared__ uint4 s_top[kLdsTop ? kBvhTopNodes * 4 : 1];
+  __shared__ uint4 s_top[kBvhTopNodes * 4];
   __shared__ float s_top_ray[9 * kBlock];
   stage_top(S, s_top);
   TraceTally tally;
@@ -531,7 +480,7 @@ __global__ void __launch_bounds__(kBlock) k_debug_any(const DeviceScene S, const
                                                       uint32_t overflow_depth) {
   __shared__ int s_stack[kLdsStack * kBlock];
   __shared__ alignas(1024) int s_aux[kAuxPerBlock];
-  __shared__ uint4 s_top[kLdsTop ? kBvhTopNodes * 4 : 1];
+  __shared__ uint4 s_top[kBvhTopNodes * 4];
   __shared__ float s_top_ray[9 * kBlock];
   stage_top(S, s_top);
   TraceTally tally;
@@ -582,9 +531,6 @@ hipError_t launch_trace(hipStream_t st, const LaunchArgs& a, uint32_t blocks, bo
   else if (a.scene.two_level) hipLaunchKernelGGL(k_trace_tl<false>, dim3(blocks), dim3(kBlock), 0, st, a);
   else if (a.counters) hipLaunchKernelGGL((k_trace<true, kAlphaInline>), dim3(blocks), dim3(kBlock), 0, st, a);
   else if (wide8) hipLaunchKernelGGL(k_trace8, dim3(blocks), dim3(kBlock), 0, st, a);
-#ifdef GLZ_TRACE_ALPHA_INLINE   // A/B builds (tools/build_variant.sh): the alpha test where the candidate is met, whatever the scene -- rounds 1-4's kernel
-  else if (true) hipLaunchKernelGGL((k_trace<false, kAlphaInline>), dim3(blocks), dim3(kBlock), 0, st, a);
-#endif
   else if (a.scene.has_non_opaque) hipLaunchKernelGGL((k_trace<false, kAlphaPhase>), dim3(blocks), dim3(kBlock), 0, st, a);   // candidates on non-opaque geometry wait for an alpha phase
   else hipLaunchKernelGGL((k_trace<false, kAlphaNone>), dim3(blocks), dim3(kBlock), 0, st, a);   // no opacity map in the scene: no alpha code in the kernel
   return hipGetLastError();
