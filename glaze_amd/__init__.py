@@ -292,6 +292,17 @@ class RayTraceInstance:
         """'auto' (two levels when instancing multiplies the triangles more than four times), 'flat' or 'two_level' for scenes created afterwards."""
         abi.check(abi.lib().glz_instance_set_as_levels(self._h, {"auto": 0, "flat": 1, "two_level": 2}[mode]))
 
+    def debug_detmath(self, fn, x, y=None):
+        """include/glz_detmath.h run on the device: fn 'sin', 'cos', 'acos', 'atan2' (atan2(y, x)), 'log2' or 'floor'"""
+        x = np.ascontiguousarray(x, np.float32).ravel()
+        y = None if y is None else np.ascontiguousarray(y, np.float32).ravel()
+        if fn == "atan2" and (y is None or y.size != x.size):
+            raise ValueError("atan2 needs y of x's size")
+        out = np.zeros_like(x)
+        code = {"sin": 0, "cos": 1, "acos": 2, "atan2": 3, "log2": 4, "floor": 5}[fn]
+        abi.check(abi.lib().glz_debug_detmath(self._h, code, _ptr(x), None if y is None else _ptr(y), _ptr(out), x.size))
+        return out
+
     def __del__(self):
         if getattr(self, "_h", None):
             abi.lib().glz_instance_destroy(self._h)
@@ -343,6 +354,16 @@ class RayTraceScene:
         tri, inst = (np.zeros(n, np.uint32) for _ in range(2))
         abi.check(abi.lib().glz_debug_trace_closest(self._h, _ptr(o), _ptr(d), n, tmin, _ptr(t), _ptr(tri), _ptr(inst), _ptr(u), _ptr(v)))
         return t, tri, inst, u, v
+
+    def debug_sample_texture(self, texture, uv, footprint=None):
+        """the kernels' sampler on n coordinates uv (n x 2), RGBA (n x 4): level 0, or with footprint (n x 4: lod_base, du, dv, taps)
+        texture2d_lod over the mip chain (built first)"""
+        uv = np.ascontiguousarray(np.asarray(uv, np.float32).reshape(-1, 2))
+        n = uv.shape[0]
+        fp = None if footprint is None else np.ascontiguousarray(np.broadcast_to(np.asarray(footprint, np.float32), (n, 4)))
+        out = np.zeros((n, 4), np.float32)
+        abi.check(abi.lib().glz_debug_sample_texture(self._h, texture, _ptr(uv), None if fp is None else _ptr(fp), n, _ptr(out)))
+        return out
 
     def debug_trace_any(self, origins, dirs, tmax, tmin=1e-3):
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)

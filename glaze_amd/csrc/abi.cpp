@@ -671,6 +671,48 @@ int glz_debug_tonemap(glz_instance* inst, const float* rgba32f, uint64_t n, uint
   GLZ_GUARD_END(GLZ_E_IO)
 }
 
+int glz_debug_sample_texture(glz_scene* h, uint32_t texture, const float* uv2, const float* fp4, uint64_t n, float* rgba) {
+  GLZ_GUARD_BEGIN
+  if (!h || !h->s || !uv2 || !rgba) return fail(GLZ_E_ARG, "null argument");
+  Scene* s = h->s.get();
+  if (texture >= s->dev.n_textures) return fail(GLZ_E_ARG, "no such texture");
+  if (n == 0) return GLZ_OK;
+  if (n > 0x7FFFFFFFull) return fail(GLZ_E_ARG, "too many coordinates");
+  for (uint64_t i = 0; fp4 && i < n; ++i)
+    if (!(fp4[4 * i + 3] >= 1.0f && fp4[4 * i + 3] <= 16.0f)) return fail(GLZ_E_ARG, "taps out of 1..16");
+  Error e;
+  if (!hip_ok(hipSetDevice(s->instance->device), "hipSetDevice", e)) return fail(e);
+  if (fp4 && !s->ensure_mips(e)) return fail(e);
+  hipStream_t st = s->instance->stream;
+  DeviceBuffer<float> d_uv, d_fp, d_out;
+  if (!to_device(d_uv, uv2, n * 2, st, e) || (fp4 && !to_device(d_fp, fp4, n * 4, st, e))) return fail(e);
+  if (!hip_ok(d_out.alloc(n * 4), "alloc", e)) return fail(e);
+  if (!hip_ok(launch_debug_sample_texture(st, s->dev, texture, d_uv.ptr, fp4 ? d_fp.ptr : nullptr, (uint32_t)n, d_out.ptr), "k_debug_sample_texture", e))
+    return fail(e);
+  (void)hipMemcpyAsync(rgba, d_out.ptr, n * 16, hipMemcpyDeviceToHost, st);
+  if (!hip_ok(hipStreamSynchronize(st), "debug sample texture", e)) return fail(e);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_detmath(glz_instance* inst, int fn, const float* x, const float* y, float* out, uint64_t n) {
+  GLZ_GUARD_BEGIN
+  if (!inst || !x || !out || (fn == 3 && !y)) return fail(GLZ_E_ARG, "null argument");
+  if (fn < 0 || fn > 5) return fail(GLZ_E_ARG, "no such function");
+  if (n == 0) return GLZ_OK;
+  if (n > 0x7FFFFFFFull) return fail(GLZ_E_ARG, "too many values");
+  Error e;
+  if (!hip_ok(hipSetDevice(inst->i->device), "hipSetDevice", e)) return fail(e);
+  hipStream_t st = inst->i->stream;
+  DeviceBuffer<float> d_x, d_y, d_out;
+  if (!to_device(d_x, x, n, st, e) || (fn == 3 && !to_device(d_y, y, n, st, e))) return fail(e);
+  if (!hip_ok(d_out.alloc(n), "alloc", e)) return fail(e);
+  if (!hip_ok(launch_debug_detmath(st, fn, d_x.ptr, fn == 3 ? d_y.ptr : nullptr, (uint32_t)n, d_out.ptr), "k_debug_detmath", e)) return fail(e);
+  (void)hipMemcpyAsync(out, d_out.ptr, n * 4, hipMemcpyDeviceToHost, st);
+  if (!hip_ok(hipStreamSynchronize(st), "debug detmath", e)) return fail(e);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+
 int glz_renderer_device_count(glz_renderer* h) { return h ? (int)h->r->device_count() : 0; }
 int glz_renderer_device_scene_info(glz_renderer* h, int i, glz_scene_info* out) {
   if (!h || !out) return fail(GLZ_E_ARG, "null argument");

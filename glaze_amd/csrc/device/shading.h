@@ -108,8 +108,26 @@ GLZ_D int wrap_coord(int i, int n) {
   int r = i % n;
   return r < 0 ? r + n : r;
 }
+// The texel index of any integral float i (glz_floorf's result), the cold path for |i| >= 2^23: i = +-m * 2^e with a 24-bit m, the
+// low -e bits of m zero when e < 0.  Reduced exactly modulo n by binary long division, one bit of |i| at a time (r < n < 2^31, so 2r
+// does not overflow): a loop of a few registers, never an out-of-range float -> int conversion.  A non-finite i takes index 0 (its weight is NaN, the
+// sample is NaN whichever texels it blends).
+GLZ_D int wrap_coord_far(float i, int n) {
+  const uint32_t bits = __float_as_uint(i), m = (bits & 0x7FFFFFu) | 0x800000u;
+  const int e = (int)((bits >> 23) & 0xFFu) - 150;
+  if (e > 104) return 0;                        // inf, NaN
+  uint32_t r = 0;
+#pragma unroll 1
+  for (int k = 23; k >= -e; --k) {
+    r = 2u * r + (k >= 0 ? (m >> k) & 1u : 0u);
+    r = r >= (uint32_t)n ? r - (uint32_t)n : r;
+  }
+  return (int)((bits >> 31) && r != 0u ? (uint32_t)n - r : r);
+}
 GLZ_D float lerp_ab(float a, float b, float t) { return a + (b - a) * t; }
-// bilinear, REPEAT fetch from ONE level: `t` describes it, `pool` holds its texels
+// bilinear, REPEAT fetch from ONE level: `t` describes it, `pool` holds its texels.  Texel centres at (i + 0.5) / width; the texel
+// index is floor(u * width - 0.5) wrapped into [0, width).  Inside (-2^23, 2^23) it goes through int (the hot path); outside, where
+// glz_floorf returns the coordinate itself and the weight is 0, it is wrapped exactly by wrap_coord_far, never converted to int.
 GLZ_D vec4 bilinear_level(const DeviceScene& S, const TexDesc& t, const uint8_t* __restrict__ pool, float u, float v) {
   const uint32_t format = t.format & 0x7Fu;
   float fu = u * (float)t.width - 0.5f, fv = v * (float)t.height - 0.5f;
@@ -123,8 +141,9 @@ GLZ_D vec4 bilinear_level(const DeviceScene& S, const TexDesc& t, const uint8_t*
       S.tex_counter[0] += 1ull;
       S.tex_counter[1] += format == GLZ_TEX_GRAY ? 4ull : 16ull;
     }
-    const int x0 = wrap_coord((int)iu, (int)t.width), y0 = wrap_coord((int)iv, (int)t.height);
-    const int x1 = wrap_coord((int)iu + 1, (int)t.width), y1 = wrap_coord((int)iv + 1, (int)t.height);
+    const int x0 = fabsf(iu) < 8388608.0f ? wrap_coord((int)iu, (int)t.width) : wrap_coord_far(iu, (int)t.width);
+    const int y0 = fabsf(iv) < 8388608.0f ? wrap_coord((int)iv, (int)t.height) : wrap_coord_far(iv, (int)t.height);
+    const int x1 = x0 + 1 == (int)t.width ? 0 : x0 + 1, y1 = y0 + 1 == (int)t.height ? 0 : y0 + 1;
     if (format != GLZ_TEX_GRAY && x1 == x0 + 1 && (x0 & 7) != 7) {
       // the two texels of a row are neighbours inside one tile row: one 8-byte load per row
       const uint2 r0 = *reinterpret_cast<const uint2*>(pool + texel_address(t, format, (uint32_t)x0, (uint32_t)y0));

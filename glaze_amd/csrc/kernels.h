@@ -154,5 +154,8 @@ hipError_t launch_debug_closest(hipStream_t st, const DeviceScene& scene, const 
                                 float* t, uint32_t* tri, uint32_t* inst, float* u, float* v, uint32_t* overflow, uint32_t overflow_depth);
 hipError_t launch_debug_any(hipStream_t st, const DeviceScene& scene, const float* origins, const float* dirs, const float* tmax, uint32_t n,
                             float tmin, uint8_t* hit, uint32_t* overflow, uint32_t overflow_depth);
+hipError_t launch_debug_sample_texture(hipStream_t st, const DeviceScene& scene, uint32_t texture, const float* uv2, const float* footprint4,
+                                       uint32_t n, float* rgba);
+hipError_t launch_debug_detmath(hipStream_t st, int fn, const float* x, const float* y, uint32_t n, float* out);
 
 }  // namespace glz

@@ -490,6 +490,40 @@ __global__ void __launch_bounds__(kBlock) k_debug_any(const DeviceScene S, const
   else trace_wave<true, false>(S, src, sink, &s_stack[threadIdx.x], wave_aux(s_aux, threadIdx.x >> 6), wave_links(s_aux, threadIdx.x >> 6), (LdsNodePtr)s_top, overflow, overflow_depth, n, wave_index(), wave_count(), tally);
 }
 
+// the texture sampler on its own: n fetches of texture `id` at uv[i], level 0 (fp null: texture2d) or with the footprint fp[i] =
+// (lod_base, du, dv, taps) (texture2d_lod; the caller has built the mip chain)
+__global__ void __launch_bounds__(kBlock) k_debug_sample_texture(DeviceScene S, uint32_t id, const float2* __restrict__ uv, const float4* __restrict__ fp,
+                                                                 uint32_t n, float4* __restrict__ out) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  S.tex_counter = nullptr;
+  const float2 c = uv[i];
+  vec4 r;
+  if (fp) {
+    const float4 f = fp[i];
+    r = texture2d_lod(S, id, c.x, c.y, TexFootprint{f.x, f.y, f.z, (uint32_t)f.w});
+  } else {
+    r = texture2d(S, id, c.x, c.y);
+  }
+  out[i] = make_float4(r.x, r.y, r.z, r.w);
+}
+// include/glz_detmath.h on the device; fn numbered as pyoracle.DETMATH (sin, cos, acos, atan2(y, x), log2, floor)
+__global__ void __launch_bounds__(kBlock) k_debug_detmath(int fn, const float* __restrict__ x, const float* __restrict__ y, uint32_t n, float* __restrict__ out) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float a = x[i];
+  float r;
+  switch (fn) {
+    case 0: r = glz_sinf(a); break;
+    case 1: r = glz_cosf(a); break;
+    case 2: r = glz_acosf(a); break;
+    case 3: r = glz_atan2f(y[i], a); break;
+    case 4: r = glz_log2f(a); break;
+    default: r = glz_floorf(a); break;
+  }
+  out[i] = r;
+}
+
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -574,6 +608,18 @@ hipError_t launch_debug_any(hipStream_t st, const DeviceScene& scene, const floa
                             uint8_t* hit, uint32_t* overflow, uint32_t overflow_depth) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_debug_any, persistent_grid(k_debug_any, n), dim3(kBlock), 0, st, scene, o, d, tmax, n, tmin, hit, overflow, overflow_depth);
+  return hipGetLastError();
+}
+
+hipError_t launch_debug_sample_texture(hipStream_t st, const DeviceScene& scene, uint32_t id, const float* uv2, const float* fp4, uint32_t n, float* rgba) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_debug_sample_texture, grid_for(n), dim3(kBlock), 0, st, scene, id, reinterpret_cast<const float2*>(uv2),
+                     reinterpret_cast<const float4*>(fp4), n, reinterpret_cast<float4*>(rgba));
+  return hipGetLastError();
+}
+hipError_t launch_debug_detmath(hipStream_t st, int fn, const float* x, const float* y, uint32_t n, float* out) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_debug_detmath, grid_for(n), dim3(kBlock), 0, st, fn, x, y, n, out);
   return hipGetLastError();
 }
 

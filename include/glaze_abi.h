@@ -470,6 +470,12 @@ int64_t glz_debug_read_bvh8(glz_scene*, void* nodes_out, int64_t cap_nodes);
 int64_t glz_debug_read_texture_level(glz_scene*, uint32_t texture, uint32_t level, uint8_t* out, int64_t cap, uint32_t* width, uint32_t* height);
 /* k_tonemap (the out32 -> RGBA8 sRGB blit, raytracer.rs:576-584) on n host pixels of RGBA32F: upload, kernel, read back */
 int glz_debug_tonemap(glz_instance*, const float* rgba32f, uint64_t n_pixels, uint8_t* rgba8_out);
+/* The kernels' texture sampler on n coordinates uv2[2i], uv2[2i+1] of a scene texture, RGBA out: level 0 (texture2d) when
+ * footprint4 is NULL, else the level of detail of footprint4[4i..4i+3] = (lod_base, du, dv, taps in 1..16) (texture2d_lod, after
+ * building the mip chain).  The scene's own texel pool and descriptors. */
+int glz_debug_sample_texture(glz_scene*, uint32_t texture, const float* uv2, const float* footprint4_or_null, uint64_t n, float* rgba_out);
+/* include/glz_detmath.h on the device: fn 0 sin, 1 cos, 2 acos, 3 atan2(y, x), 4 log2, 5 floor of n values (y only for atan2) */
+int glz_debug_detmath(glz_instance*, int fn, const float* x, const float* y, float* out, uint64_t n);
 
 /* First contact with RCCL on this machine: a one-rank communicator on the instance's device (ncclCommInitAll), one
  * ncclReduce(sum, float) of n_floats values on the instance's stream, result compared bit for bit with the input, communicator

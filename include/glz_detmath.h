@@ -8,7 +8,16 @@
  * the GLSL built-ins of the Vulkan driver ([ext], SURVEY 8c: parity unpinned).
  *
  * Coefficients: the classic Cephes single-precision minimax polynomials (sinf/cosf/asinf/atanf/logf).
- * Accuracy: <= 2 ulp over the ranges the renderer uses (checked against numpy in tests/).
+ * Accuracy against float64, measured on dense sweeps of the domains the renderer uses (tests/test_detmath_device.py):
+ *   sin   [-2pi, 2pi]              1.6 ulp
+ *   cos   [-2pi, 2pi]              1e-7 absolute; 1.6 ulp where |cos| >= 1/8 (13.8 ulp next to the zeros, e.g. 3pi/2)
+ *   acos  [-1, 1]                  1.3 ulp (0 for x >= 1, pi for x <= -1, NaN for NaN)
+ *   atan2 finite, nonzero pairs    3.5 ulp (GLSL atan(y, x); y == 0 gives 0 or pi, x == 0 gives +-pi/2)
+ *   log2  positive normal floats   2 ulp where |log2 x| >= 2^-10, 1.5e-7 relative next to 1 (log2 1 = 0 exactly)
+ *   floor every float              exact (NaN, +-inf and |x| >= 2^23 come back unchanged; floor(-0) = +0)
+ * Outside these domains the results are only deterministic: the host and the device compute the same floats (every bit pattern
+ * at a stride, tests/test_detmath_device.py); sin and cos of large arguments, log2 of zero, negatives or denormals are not
+ * meaningful values.
  */
 #ifndef GLZ_DETMATH_H
 #define GLZ_DETMATH_H
@@ -23,8 +32,11 @@
 #include <math.h>
 #endif
 
-/* floor for |x| < 2^31 without libm dependence on the device */
+/* floor without libm dependence on the device.  Outside (-2^23, 2^23) every float is an integer already, and NaN / +-inf have
+ * no floor: x comes back unchanged.  Only values inside that range go through (int), so no conversion is ever out of range (which
+ * is undefined behaviour in C++, returns INT_MIN on x86-64 and saturates on gfx950).  floor(-0) is +0. */
 GLZ_HD float glz_floorf(float x) {
+  if (!(x > -8388608.0f && x < 8388608.0f)) return x;
   float t = (float)(int)x;
   return t > x ? t - 1.0f : t;
 }
@@ -40,7 +52,8 @@ GLZ_HD int glz_reduce_pio2(float x, float* r) {
   y = y - kf * p2;
   y = y - kf * p3;
   *r = y;
-  return ((int)kf) & 3;
+  /* k & 3 without an out-of-range conversion: from 2^25 on every float is a multiple of 4; NaN / inf take 0 */
+  return (kf > -33554432.0f && kf < 33554432.0f) ? ((int)kf) & 3 : 0;
 }
 
 GLZ_HD float glz_sin_poly(float r) {

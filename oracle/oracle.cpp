@@ -473,6 +473,22 @@ inline V4 texel(const Scene& sc, const Tex& t, int x, int y) {
   return V4{(float)p[0] / 255.0f, (float)p[1] / 255.0f, (float)p[2] / 255.0f, (float)p[3] / 255.0f};
 }
 inline int wrapi(int i, int n) { int r = i % n; return r < 0 ? r + n : r; }
+// texel index of an integral i outside (-2^23, 2^23): i = m * 2^e exactly (24-bit m, e >= 0), reduced modulo n in 64-bit integers;
+// inf / NaN take 0 (their weight is NaN).  Never an out-of-range float -> int conversion.
+inline int wrapi_far(float i, int n) {
+  uint32_t bits;
+  memcpy(&bits, &i, 4);
+  int e = (int)((bits >> 23) & 0xFFu) - 150;
+  if (e > 104) return 0;
+  uint64_t r = (uint64_t)((bits & 0x7FFFFFu) | 0x800000u) % (uint64_t)n;
+  for (; e > 0; e -= 32) r = (r << (e < 32 ? e : 32)) % (uint64_t)n;
+  return (int)((bits >> 31) && r != 0 ? (uint64_t)n - r : r);
+}
+// the two texel indices around floor(u * n - 0.5) = i, wrapped (REPEAT)
+inline void wrap_pair(float i, int n, int& a, int& b) {
+  if (fabsf(i) < 8388608.0f) { a = wrapi((int)i, n); b = wrapi((int)i + 1, n); }
+  else { a = wrapi_far(i, n); b = a + 1 == n ? 0 : a + 1; }
+}
 inline float lerp1(float a, float b, float t) { return a + (b - a) * t; }
 V4 texture_bilinear_level(const Scene& sc, const Tex& t, float u, float v);
 V4 texture_bilinear(const Scene& sc, uint32_t id, float u, float v) { return texture_bilinear_level(sc, sc.textures[id], u, v); }
@@ -480,8 +496,9 @@ V4 texture_bilinear_level(const Scene& sc, const Tex& t, float u, float v) {
   float fu = u * (float)t.w - 0.5f, fv = v * (float)t.h - 0.5f;
   float iu = glz_floorf(fu), iv = glz_floorf(fv);
   float ax = fu - iu, ay = fv - iv;
-  int x0 = wrapi((int)iu, (int)t.w), y0 = wrapi((int)iv, (int)t.h);
-  int x1 = wrapi((int)iu + 1, (int)t.w), y1 = wrapi((int)iv + 1, (int)t.h);
+  int x0, x1, y0, y1;
+  wrap_pair(iu, (int)t.w, x0, x1);
+  wrap_pair(iv, (int)t.h, y0, y1);
   V4 a = texel(sc, t, x0, y0), b = texel(sc, t, x1, y0), c = texel(sc, t, x0, y1), d = texel(sc, t, x1, y1);
   V4 r;
   r.x = lerp1(lerp1(a.x, b.x, ax), lerp1(c.x, d.x, ax), ay);
@@ -2321,9 +2338,35 @@ void orc_detmath(int fn, const float* x, const float* y, float* out, uint64_t n)
       case 1: out[i] = glz_cosf(x[i]); break;
       case 2: out[i] = glz_acosf(x[i]); break;
       case 4: out[i] = glz_log2f(x[i]); break;
+      case 5: out[i] = glz_floorf(x[i]); break;
       default: out[i] = glz_atan2f(y[i], x[i]); break;
     }
   }
+}
+// n bilinear fetches of a scene texture at (u, v) = uv2[2i..]: level 0 (footprint4 null), or texture_lod with the footprint
+// (lod_base, du, dv, taps) of each fetch (the mip chain is built first).  Returns 0, or -1 for a texture id or taps out of range.
+int orc_sample_texture(void* s, uint32_t texture, const float* uv2, const float* footprint4, uint64_t n, float* rgba) {
+  Scene* sc = (Scene*)s;
+  if (texture >= sc->textures.size()) return -1;
+  Tex& t = sc->textures[texture];
+  for (uint64_t i = 0; footprint4 && i < n; ++i)
+    if (!(footprint4[4 * i + 3] >= 1.0f && footprint4[4 * i + 3] <= 16.0f)) return -1;
+  if (footprint4 && t.mips.empty() && (t.w > 1 || t.h > 1)) build_mip_chain(t);
+  for (uint64_t i = 0; i < n; ++i) {
+    V4 r;
+    if (footprint4) {
+      TexFootprint fp;
+      fp.lod_base = footprint4[4 * i];
+      fp.du = footprint4[4 * i + 1];
+      fp.dv = footprint4[4 * i + 2];
+      fp.taps = (uint32_t)footprint4[4 * i + 3];
+      r = texture_lod(*sc, texture, uv2[2 * i], uv2[2 * i + 1], fp);
+    } else {
+      r = texture_bilinear(*sc, texture, uv2[2 * i], uv2[2 * i + 1]);
+    }
+    rgba[4 * i] = r.x; rgba[4 * i + 1] = r.y; rgba[4 * i + 2] = r.z; rgba[4 * i + 3] = r.w;
+  }
+  return 0;
 }
 uint32_t orc_pcg_hash(uint32_t x) { return pcg_hash(x); }
 // ---- shading routines on their own, for the tests that check this restatement against mathematics (tests/test_oracle_math.py) ----

@@ -63,6 +63,7 @@ def lib():
             "orc_dev_from_surface_color": (None, [_P, _P]), "orc_dev_from_illuminant_color": (None, [_P, _P]),
             "orc_dev_rgb": (None, [_P, _P]), "orc_dev_luminance": (C.c_float, [_P]),
             "orc_detmath": (None, [C.c_int, _P, _P, _P, C.c_uint64]),
+            "orc_sample_texture": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint64, _P]),
             "orc_pcg_hash": (C.c_uint32, [C.c_uint32]),
             "orc_rand_stream": (None, [C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32]),
         }
@@ -185,6 +186,17 @@ class OracleScene:
         lib().orc_texture_level(self.handle, texture, level, _ptr(out), C.byref(w), C.byref(h))
         return out.reshape(h.value, w.value) if n == w.value * h.value else out.reshape(h.value, w.value, 4)
 
+    def sample_texture(self, texture, uv, footprint=None):
+        """n bilinear fetches (n x 4 RGBA) of a texture at uv (n x 2): level 0, or with footprint (n x 4: lod_base, du, dv, taps)
+        the texture level of detail of the renderer's lod modes (builds the mip chain)"""
+        uv = np.ascontiguousarray(np.asarray(uv, np.float32).reshape(-1, 2))
+        n = uv.shape[0]
+        fp = None if footprint is None else np.ascontiguousarray(np.broadcast_to(np.asarray(footprint, np.float32), (n, 4)))
+        out = np.zeros((n, 4), np.float32)
+        if lib().orc_sample_texture(self.handle, texture, _ptr(uv), None if fp is None else _ptr(fp), n, _ptr(out)) != 0:
+            raise ValueError("texture id or taps out of range")
+        return out
+
     def sky_cond(self):
         """(conditional values H x W, conditional cdf H x (W+1)) of the sky distribution"""
         n = lib().orc_read_sky_cond(self.handle, None, None)
@@ -297,11 +309,15 @@ def launch_constants(seed, launch):
     return s.value, (off[0], off[1])
 
 
+DETMATH = {"sin": 0, "cos": 1, "acos": 2, "atan2": 3, "log2": 4, "floor": 5}   # the numbering of orc_detmath / glz_debug_detmath
+
+
 def detmath(fn, x, y=None):
+    """glz_detmath.h on the host; atan2 is atan2(y, x)"""
     x = np.ascontiguousarray(x, np.float32)
     y = np.ascontiguousarray(y if y is not None else x, np.float32)
     out = np.zeros_like(x)
-    lib().orc_detmath({"sin": 0, "cos": 1, "acos": 2, "atan2": 3, "log2": 4}[fn], _ptr(x), _ptr(y), _ptr(out), x.size)
+    lib().orc_detmath(DETMATH[fn], _ptr(x), _ptr(y), _ptr(out), x.size)
     return out
 
 
