@@ -147,6 +147,23 @@ class ParsedScene:
                                               C.cast(C.pointer(meta), C.c_void_p) if meta is not None else None))
 
 
+def _transform_array(transforms):
+    t = np.ascontiguousarray(transforms, np.float32)
+    if t.ndim != 2 or t.shape[1] != 16:
+        raise ValueError("transforms must be an (n, 16) array of column-major 4x4 matrices, got shape %s" % (t.shape,))
+    return t
+
+
+def host_instance_boxes(desc, budget=0):
+    """The top level's instance boxes by the host rule on a SceneDesc, without a device ((n, 4) float32 lo, hi; one per instance that
+    names an existing mesh).  A mesh's box is the min / max of its vertices here.  budget 0 = the library's exact-box budget."""
+    c = desc.as_c()
+    n = abi.check(abi.lib().glz_host_instance_boxes(C.byref(c), budget, None, None))
+    lo, hi = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+    abi.check(abi.lib().glz_host_instance_boxes(C.byref(c), budget, _ptr(lo), _ptr(hi)))
+    return lo, hi
+
+
 def _texture_array(textures, keep):
     texs = (abi.Texture * max(1, len(textures)))()
     for i, t in enumerate(textures):
@@ -414,6 +431,27 @@ class RayTraceScene:
         abi.check(abi.lib().glz_debug_read_bvh(self._h, _ptr(nodes), i.bvh_nodes, _ptr(tris), i.n_as_triangles))
         return nodes[:i.bvh_nodes], tris[:i.n_as_triangles]
 
+    def debug_tlas_instances(self):
+        """The 192-byte TlasInstance records of a two-level scene in the top level's leaf order (uint8; empty when flattened)."""
+        n = abi.check(abi.lib().glz_debug_read_tlas_instances(self._h, None, 0))
+        out = np.zeros(n, np.uint8)
+        abi.check(abi.lib().glz_debug_read_tlas_instances(self._h, _ptr(out), n))
+        return out
+
+    def debug_instance_boxes(self, on_device, budget=0):
+        """Instance boxes ((n, 4) float32 lo, hi) of a two-level scene under its current transforms: the host rule (on_device False)
+        or the device kernel; budget 0 = the library's exact-box budget.  None for a flattened scene."""
+        n = abi.check(abi.lib().glz_debug_instance_boxes(self._h, int(bool(on_device)), budget, None, None))
+        if n == 0:
+            return None
+        lo, hi = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+        abi.check(abi.lib().glz_debug_instance_boxes(self._h, int(bool(on_device)), budget, _ptr(lo), _ptr(hi)))
+        return lo, hi
+
+    def debug_box_kernel_ms(self):
+        """device-event time (ms) of the instance-box kernels the last time they ran for this scene; -1 if never"""
+        return float(abi.lib().glz_debug_box_kernel_ms(self._h))
+
     def debug_bvh8(self):
         """The 8-wide nodes of the same hierarchy ((n, 32) uint32; empty for two-level scenes and scenes of one leaf)."""
         n = self.info().bvh_nodes8
@@ -474,6 +512,12 @@ class RayTraceRenderer:
         t, nt = (None, 0) if textures is None else _texture_array(textures, keep)
         abi.check(abi.lib().glz_renderer_update_materials_and_lights(self._h, C.cast(m, C.c_void_p), len(materials), C.cast(l, C.c_void_p),
                                                                      len(lights), t, nt))
+
+    def update_transforms(self, transforms):
+        """Moves the instances: transforms is (n, 16) float32, column-major (as SceneDesc.transforms), n = the scene's transform count.
+        The scene's structure is rebuilt for them (every renderer sharing the scene sees the move) and accumulation restarts."""
+        t = _transform_array(transforms)
+        abi.check(abi.lib().glz_renderer_update_transforms(self._h, _ptr(t), t.shape[0]))
 
     def refresh_binded_textures(self, textures):
         """raytracer.rs:328-356: new texture array under the same materials and lights; accumulation continues."""

@@ -147,6 +147,11 @@ PROTOTYPES = {
     "glz_renderer_change_scene": (C.c_int, [_P, _P]),
     "glz_renderer_update_materials_and_lights": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
     "glz_renderer_refresh_binded_textures": (C.c_int, [_P, _P, C.c_uint32]),
+    "glz_renderer_update_transforms": (C.c_int, [_P, _P, C.c_uint32]),
+    "glz_debug_read_tlas_instances": (C.c_int64, [_P, _P, C.c_int64]),
+    "glz_debug_instance_boxes": (C.c_int64, [_P, C.c_int, C.c_uint64, _P, _P]),
+    "glz_debug_box_kernel_ms": (C.c_float, [_P]),
+    "glz_host_instance_boxes": (C.c_int64, [_P, C.c_uint64, _P, _P]),
     "glz_renderer_wait_idle": (C.c_int, [_P]),
     "glz_renderer_steps_per_sample": (C.c_uint32, [_P]),
     "glz_renderer_draw": (C.c_int, [_P, C.c_size_t, _P, _P, _P]),

@@ -364,6 +364,14 @@ int glz_renderer_update_materials_and_lights(glz_renderer* h, const glz_material
   GLZ_RET(h->r->update_materials_and_lights(m, nm, l, nl, t, nt, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_renderer_update_transforms(glz_renderer* h, const glz_transform* t, uint32_t nt) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!t) return fail(GLZ_E_ARG, "transforms is null");
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  if (nt != h->r->scene()->data.transforms.size()) return fail(GLZ_E_ARG, "update_transforms: the transform count must not change (instances index transforms)");
+  GLZ_RET(h->r->update_transforms(t, nt, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_refresh_binded_textures(glz_renderer* h, const glz_texture* t, uint32_t nt) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!t || !nt) return fail(GLZ_E_ARG, "null array");
@@ -613,6 +621,54 @@ int64_t glz_debug_read_bvh(glz_scene* h, void* nodes_out, int64_t cap_nodes, voi
   GLZ_GUARD_END(GLZ_E_IO)
 }
 
+int64_t glz_debug_read_tlas_instances(glz_scene* h, void* out, int64_t cap) {
+  GLZ_GUARD_BEGIN
+  if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");
+  Scene* s = h->s.get();
+  const int64_t n = (int64_t)s->n_tlas_records() * (int64_t)sizeof(TlasInstance);
+  if (out && cap > 0 && n > 0) {
+    Error e;
+    if (!hip_ok(hipSetDevice(s->instance->device), "hipSetDevice", e)) return fail(e);
+    if (!hip_ok(hipMemcpy(out, s->dev.tlas_instances, (size_t)std::min(n, cap), hipMemcpyDeviceToHost), "read instance records", e)) return fail(e);
+  }
+  return n;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+static int64_t write_boxes(const std::vector<float4>& lo, const std::vector<float4>& hi, float* lo4, float* hi4) {
+  if (lo4 && !lo.empty()) memcpy(lo4, lo.data(), lo.size() * sizeof(float4));
+  if (hi4 && !hi.empty()) memcpy(hi4, hi.data(), hi.size() * sizeof(float4));
+  return (int64_t)lo.size();
+}
+int64_t glz_debug_instance_boxes(glz_scene* h, int on_device, uint64_t budget, float* lo4, float* hi4) {
+  GLZ_GUARD_BEGIN
+  if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");
+  if (!lo4 && !hi4) return (int64_t)(h->s->dev.two_level ? h->s->h_instances.size() : 0);   // the count alone, nothing computed
+  std::vector<float4> lo, hi;
+  Error e;
+  if (!h->s->instance_boxes(on_device != 0, budget ? budget : kExactBoxBudget, lo, hi, e) && e.code != GLZ_OK) return fail(e);
+  return write_boxes(lo, hi, lo4, hi4);
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+float glz_debug_box_kernel_ms(glz_scene* h) { return h && h->s ? h->s->box_kernel_ms : -1.0f; }
+int64_t glz_host_instance_boxes(const glz_scene_desc* d, uint64_t budget, float* lo4, float* hi4) {
+  GLZ_GUARD_BEGIN
+  if (!d) return fail(GLZ_E_ARG, "scene description is null");
+  if ((d->n_vertices && !d->vertices) || (d->n_indices && !d->indices) || (d->n_meshes && !d->meshes) || (d->n_transforms && !d->transforms) ||
+      (d->n_instances && !d->instances))
+    return fail(GLZ_E_ARG, "null array");
+  SceneData data;
+  if (d->n_vertices) data.vertices.assign(d->vertices, d->vertices + d->n_vertices);
+  if (d->n_indices) data.indices.assign(d->indices, d->indices + d->n_indices);
+  if (d->n_meshes) data.meshes.assign(d->meshes, d->meshes + d->n_meshes);
+  if (d->n_transforms) data.transforms.assign(d->transforms, d->transforms + d->n_transforms);
+  if (d->n_instances) data.instances.assign(d->instances, d->instances + d->n_instances);
+  if (!lo4 && !hi4) return (int64_t)rt_instances(data).size();   // the count alone, nothing computed
+  std::vector<float4> lo, hi;
+  Error e;
+  if (!host_instance_boxes_of(data, budget ? budget : kExactBoxBudget, lo, hi, e)) return fail(e);
+  return write_boxes(lo, hi, lo4, hi4);
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int64_t glz_debug_read_bvh8(glz_scene* h, void* nodes_out, int64_t cap_nodes) {
   GLZ_GUARD_BEGIN
   if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");

@@ -54,6 +54,15 @@ hipError_t launch_top_table(hipStream_t st, const BvhNode4* nodes, uint32_t n_no
 // 128-byte per-leaf shading records (see k_shade_records); xf_identity[t] != 0 marks an exact identity transform
 hipError_t launch_shade_records(hipStream_t st, uint32_t n, const BvhTri* tris, const RTInstance* instances, const uint32_t* indices,
                                 const float4* vertices, const float4* derivatives, const uint32_t* xf_identity, float4* out);
+// Instance boxes of a two-level top level (kernels_tlas.hip, Scene::update_transforms): item j takes the world positions of
+// points[first .. first + count) under transform `transform`; an instance's items are item_first[i] .. item_first[i + 1] (at least one),
+// all naming the same transform and mesh.  partial: 6 doubles per item (scratch).
+struct InstanceBoxItem {
+  uint32_t transform, mesh, first, count;
+};
+hipError_t launch_instance_boxes(hipStream_t st, uint32_t n_items, const InstanceBoxItem* items, const float4* points, const TransformPair* xf,
+                                 double* partial, uint32_t n_instances, const uint32_t* item_first, const float4* mesh_lo, const float4* mesh_hi,
+                                 float4* box_lo, float4* box_hi);
 // DeviceScene::alpha_recs for `n` triangle slots (flattened scenes with an opacity map)
 hipError_t launch_alpha_records(hipStream_t st, uint32_t n, const float4* shade_tris, const RTMaterial* materials, const TexDesc* tex_desc, float4* out);
 

@@ -760,6 +760,18 @@ bool Renderer::update_materials_and_lights(const glz_material* m, uint32_t nm, c
   return forward([=](Peer& p, Error& e) { return p.r->update_materials_and_lights(m, nm, l, nl, t, nt, e); }, err);
 }
 
+// Moves the instances: the scene's structure is rebuilt for the new transforms (the scene object changes, so every renderer that
+// shares it sees the move), accumulation restarts, and every other device of set_devices updates its replica the same way.
+bool Renderer::update_transforms(const glz_transform* t, uint32_t n, Error& err) {
+  if (!wait_idle(err)) return false;
+  const uint32_t od = scene_->stack_overflow_depth;
+  const bool wide8 = scene_->dev.bvh_nodes8 != nullptr;   // what allocate() sizes from the scene and an update can change
+  if (!scene_->update_transforms(t, n, err)) return false;
+  if ((scene_->stack_overflow_depth != od || (scene_->dev.bvh_nodes8 != nullptr) != wide8) && !allocate(err)) return false;
+  request_new_frame_ = true;
+  return forward([=](Peer& p, Error& e) { return p.r->update_transforms(t, n, e); }, err);
+}
+
 // raytracer.rs:328-356.  The reference rebuilds descriptors, pipeline and SBT and leaves the accumulation alone; here the
 // kernels read the texture array through the scene struct of every launch, so re-uploading it is all there is to do.
 bool Renderer::refresh_binded_textures(const glz_texture* t, uint32_t nt, Error& err) {

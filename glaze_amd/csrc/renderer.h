@@ -22,6 +22,7 @@ class Renderer {
   bool change_scene(std::shared_ptr<Scene> scene, Error& err);
   bool update_materials_and_lights(const glz_material* m, uint32_t nm, const glz_light* l, uint32_t nl, const glz_texture* t, uint32_t nt, Error& err);
   bool refresh_binded_textures(const glz_texture* t, uint32_t nt, Error& err);
+  bool update_transforms(const glz_transform* t, uint32_t n, Error& err);   // Scene::update_transforms; restarts accumulation
   bool wait_idle(Error& err);
   uint32_t steps_per_sample() const { return integrator_ == GLZ_DIRECT ? 1u : pt_steps_; }
 

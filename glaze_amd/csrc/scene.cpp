@@ -21,6 +21,30 @@ bool hip_ok(hipError_t e, const char* what, Error& err) {
   return false;
 }
 
+// Two HIP events around work on a stream, destroyed on every way out
+struct StreamTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  StreamTimer() = default;
+  StreamTimer(const StreamTimer&) = delete;
+  StreamTimer& operator=(const StreamTimer&) = delete;
+  ~StreamTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  bool start(hipStream_t st, Error& err) {
+    if (!hip_ok(hipEventCreate(&e0), "event", err) || !hip_ok(hipEventCreate(&e1), "event", err)) return false;
+    (void)hipEventRecord(e0, st);
+    return true;
+  }
+  void stop(hipStream_t st) { (void)hipEventRecord(e1, st); }
+  float ms() {   // waits for the stop event
+    float v = 0.0f;
+    (void)hipEventSynchronize(e1);
+    (void)hipEventElapsedTime(&v, e0, e1);
+    return v;
+  }
+};
+
 Instance::~Instance() {
   if (stream) (void)hipStreamDestroy(stream);
 }
@@ -72,6 +96,41 @@ Instance* Instance::create(int hip_device, Error& err) {
     return nullptr;
   }
   return inst;
+}
+
+// load_raytrace_instances_to_gpu (scene.rs:1784-1818): meshes indexed by id (last one wins), dangling instances dropped
+std::vector<RTInstance> rt_instances(const SceneData& d) {
+  std::vector<RTInstance> out;
+  for (const glz_mesh_instance& in : d.instances) {
+    const glz_mesh* found = nullptr;
+    for (const glz_mesh& m : d.meshes)
+      if (m.id == in.mesh_id) found = &m;
+    if (!found) continue;
+    out.push_back(RTInstance{found->index_offset, found->index_count, found->material, in.transform_id});
+  }
+  return out;
+}
+
+// object -> world as given, world -> object inverted in double precision (identity when singular or not finite)
+static std::vector<TransformPair> transform_pairs(const std::vector<glz_transform>& transforms) {
+  std::vector<TransformPair> xf(transforms.size());
+  for (size_t i = 0; i < xf.size(); ++i) {
+    memcpy(xf[i].o2w, transforms[i].m, 64);
+    host::Mat4d inv;
+    if (!host::invert(host::Mat4d::from_f32(transforms[i].m), inv)) inv = host::Mat4d::identity();
+    inv.to_f32(xf[i].w2o);
+  }
+  return xf;
+}
+
+// DeviceScene::xf_identity: 1 for a transform that is bitwise the identity (-0.0 does not count)
+static std::vector<uint32_t> identity_flags(const std::vector<glz_transform>& transforms) {
+  std::vector<uint32_t> ident(transforms.size(), 0u);
+  for (size_t i = 0; i < ident.size(); ++i) {
+    static const float id[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    ident[i] = memcmp(transforms[i].m, id, 64) == 0 ? 1u : 0u;
+  }
+  return ident;
 }
 
 static uint32_t sbt_callable_index(uint8_t mtype) {   // materials/material.rs:244-258
@@ -132,7 +191,9 @@ Scene* Scene::create(Instance* inst, SceneData&& data, Error& err) {
   if (!s->upload_geometry(err)) return nullptr;
   if (!s->build_materials(err)) return nullptr;
   if (!s->build_lights_and_sky(err)) return nullptr;
+  s->build_opts_ = BuildOptions{inst->bvh_builder, inst->bvh_pair_area_ratio, inst->as_levels};
   if (!s->build_bvh(err)) return nullptr;
+  s->build_opts_.as_levels = (int)s->info.as_levels;   // the shape built: update_transforms keeps it
   if (!hip_ok(hipStreamSynchronize(inst->stream), "scene upload", err)) return nullptr;
   s->info.n_vertices = d.vertices.size();
   s->info.n_triangles = d.indices.size() / 3;
@@ -150,15 +211,7 @@ bool Scene::upload_geometry(Error& err) {
   static_assert(sizeof(glz_vertex) == 2 * sizeof(float4), "vertex = 2 x float4");
   if (!hip_ok(d_vertices_.upload(reinterpret_cast<const float4*>(d.vertices.data()), d.vertices.size() * 2, st), "upload vertices", err)) return false;
   if (!hip_ok(d_indices_.upload(d.indices.data(), d.indices.size(), st), "upload indices", err)) return false;
-  // load_raytrace_instances_to_gpu (scene.rs:1784-1818): meshes indexed by id (last one wins), dangling instances dropped
-  h_instances.clear();
-  for (const glz_mesh_instance& in : d.instances) {
-    const glz_mesh* found = nullptr;
-    for (const glz_mesh& m : d.meshes)
-      if (m.id == in.mesh_id) found = &m;
-    if (!found) continue;
-    h_instances.push_back(RTInstance{found->index_offset, found->index_count, found->material, in.transform_id});
-  }
+  h_instances = rt_instances(d);
   if (!hip_ok(d_instances_.upload(h_instances.data(), h_instances.size(), st), "upload instances", err)) return false;
   inst_base_.assign(h_instances.size(), 0);
   uint64_t total = 0;
@@ -174,13 +227,7 @@ bool Scene::upload_geometry(Error& err) {
   info.n_world_triangles = total;
   if (!hip_ok(d_inst_base_.upload(inst_base_.data(), inst_base_.size(), st), "upload instance bases", err)) return false;
   // transforms + inverses (gl_WorldToObjectEXT is supplied by the driver in the reference)
-  std::vector<TransformPair> xf(d.transforms.size());
-  for (size_t i = 0; i < xf.size(); ++i) {
-    memcpy(xf[i].o2w, d.transforms[i].m, 64);
-    host::Mat4d inv;
-    if (!host::invert(host::Mat4d::from_f32(d.transforms[i].m), inv)) inv = host::Mat4d::identity();
-    inv.to_f32(xf[i].w2o);
-  }
+  const std::vector<TransformPair> xf = transform_pairs(d.transforms);
   if (!hip_ok(d_transforms_.upload(xf.data(), xf.size(), st), "upload transforms", err)) return false;
   if (!upload_textures(err)) return false;
   float lut[256];
@@ -543,14 +590,102 @@ bool Scene::build_lights_and_sky(Error& err) {
   return true;
 }
 
+// ---- instance boxes of the top level: world AABB of the mesh's VERTICES under the instance's transform, padded.  (The eight corners
+// of the mesh's object box, which is what a top level normally takes, give a box up to sqrt(2) too wide per axis for a rotated
+// instance -- a quarter more instance entries per ray in the column forest.  The vertices cost instances x vertices; past `budget`
+// point transforms the remaining instances fall back to the corners.) ----
+std::vector<std::vector<float>> mesh_points(const SceneData& d, const std::vector<std::pair<uint32_t, uint32_t>>& ranges) {
+  std::vector<std::vector<float>> out(ranges.size());   // xyz of the vertices a mesh references, once each, in first-use order
+  std::vector<uint8_t> seen(d.vertices.size(), 0);
+  for (size_t mi = 0; mi < ranges.size(); ++mi) {
+    const uint32_t off = ranges[mi].first, count = ranges[mi].second;
+    std::vector<float>& pts = out[mi];
+    for (uint32_t k = 0; k < count; ++k) {
+      const uint32_t v = d.indices[off + k];
+      if (seen[v]) continue;
+      seen[v] = 1;
+      pts.insert(pts.end(), d.vertices[v].vv, d.vertices[v].vv + 3);
+    }
+    for (uint32_t k = 0; k < count; ++k) seen[d.indices[off + k]] = 0;
+  }
+  return out;
+}
+
+std::vector<uint8_t> exact_box_instances(const std::vector<uint32_t>& mesh_of, const std::vector<uint64_t>& mesh_point_count, uint64_t budget) {
+  std::vector<uint8_t> exact(mesh_of.size(), 0);
+  uint64_t spent = 0;
+  for (size_t i = 0; i < mesh_of.size(); ++i) {
+    const uint64_t n = mesh_point_count[mesh_of[i]];
+    if (n != 0 && spent + n <= budget) {
+      spent += n;
+      exact[i] = 1;
+    }
+  }
+  return exact;
+}
+
+void host_instance_boxes(const std::vector<uint32_t>& mesh_of, const std::vector<uint32_t>& transform_of, const std::vector<InstanceBoxMesh>& meshes,
+                         const std::vector<glz_transform>& transforms, uint64_t budget, std::vector<float4>& blo, std::vector<float4>& bhi) {
+  const size_t ni = mesh_of.size();
+  blo.assign(ni, float4{});
+  bhi.assign(ni, float4{});
+  std::vector<uint64_t> counts(meshes.size());
+  for (size_t m = 0; m < meshes.size(); ++m) counts[m] = meshes[m].points.size() / 3;
+  const std::vector<uint8_t> exact = exact_box_instances(mesh_of, counts, budget);
+  for (size_t i = 0; i < ni; ++i) {
+    const InstanceBoxMesh& m = meshes[mesh_of[i]];
+    const float* M = transforms[transform_of[i]].m;
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    auto take = [&](double x, double y, double z) {
+      for (int k = 0; k < 3; ++k) {
+        const double w = (double)M[k] * x + (double)M[4 + k] * y + (double)M[8 + k] * z + (double)M[12 + k];
+        lo[k] = std::min(lo[k], w);
+        hi[k] = std::max(hi[k], w);
+      }
+    };
+    const std::vector<float>& pts = m.points;
+    if (exact[i]) {
+      for (size_t k = 0; k + 2 < pts.size(); k += 3) take(pts[k], pts[k + 1], pts[k + 2]);
+    } else {
+      for (int c = 0; c < 8; ++c) take((c & 1) ? m.hi[0] : m.lo[0], (c & 2) ? m.hi[1] : m.lo[1], (c & 4) ? m.hi[2] : m.lo[2]);
+    }
+    float l[3], h[3];
+    for (int k = 0; k < 3; ++k) {
+      if (!(lo[k] <= hi[k])) lo[k] = hi[k] = 0.0;   // a mesh without triangles / non-finite transform: a point nobody hits
+      // the tracer's world vertices are single-precision sums of four terms: four roundings of the largest one can get
+      const double mag = std::fabs((double)M[k]) * std::max(std::fabs((double)m.lo[0]), std::fabs((double)m.hi[0])) +
+                         std::fabs((double)M[4 + k]) * std::max(std::fabs((double)m.lo[1]), std::fabs((double)m.hi[1])) +
+                         std::fabs((double)M[8 + k]) * std::max(std::fabs((double)m.lo[2]), std::fabs((double)m.hi[2])) + std::fabs((double)M[12 + k]);
+      const double pad = 1e-5 * std::max({std::fabs(lo[k]), std::fabs(hi[k]), 1e-3}) + 1e-6 * (hi[k] - lo[k]) + (std::isfinite(mag) ? 4.8e-7 * mag : 0.0);
+      l[k] = std::nextafterf((float)(lo[k] - pad), -INFINITY);
+      h[k] = std::nextafterf((float)(hi[k] + pad), INFINITY);
+    }
+    blo[i] = make_float4(l[0], l[1], l[2], 0.0f);
+    bhi[i] = make_float4(h[0], h[1], h[2], 0.0f);
+  }
+}
+
+// how far from the origin the instances reach: the diagonal of their boxes' union plus its largest coordinate (TlasInstance::slack)
+double instance_reach(const std::vector<float4>& blo, const std::vector<float4>& bhi) {
+  double wlo[3] = {1e300, 1e300, 1e300}, whi[3] = {-1e300, -1e300, -1e300};
+  for (size_t i = 0; i < blo.size(); ++i) {
+    const float l[3] = {blo[i].x, blo[i].y, blo[i].z}, h[3] = {bhi[i].x, bhi[i].y, bhi[i].z};
+    for (int k = 0; k < 3; ++k) {
+      wlo[k] = std::min(wlo[k], (double)l[k]);
+      whi[k] = std::max(whi[k], (double)h[k]);
+    }
+  }
+  return std::sqrt((whi[0] - wlo[0]) * (whi[0] - wlo[0]) + (whi[1] - wlo[1]) * (whi[1] - wlo[1]) + (whi[2] - wlo[2]) * (whi[2] - wlo[2])) +
+         std::max({std::fabs(wlo[0]), std::fabs(wlo[1]), std::fabs(wlo[2]), std::fabs(whi[0]), std::fabs(whi[1]), std::fabs(whi[2])});
+}
+
 // Two-level structure (types.h TlasInstance; acceleration.rs:319-345: a BLAS per mesh, a TLAS over the instances).  The meshes'
 // hierarchies are built by the ordinary builder over ONE pseudo-instance with the identity transform (object space = its "world"),
 // the top level by the same builder over the instances' world boxes (LbvhInputs::given_lo).  Memory is O(meshes + instances).
 bool Scene::build_two_level(Error& err) {
   hipStream_t st = instance->stream;
-  hipEvent_t e0, e1;
-  if (!hip_ok(hipEventCreate(&e0), "event", err) || !hip_ok(hipEventCreate(&e1), "event", err)) return false;
-  (void)hipEventRecord(e0, st);
+  StreamTimer timer;
+  if (!timer.start(st, err)) return false;
   h_mesh_ranges.clear();
   // ---- unique meshes (index ranges) ----
   struct MeshAs {
@@ -617,7 +752,7 @@ bool Scene::build_two_level(Error& err) {
       free_nodes();
       return false;
     }
-    LbvhInputs in{d_vertices_.ptr, d_indices_.ptr, d_pseudo.ptr, d_zero.ptr, 1u, d_ident.ptr, d_opaque.ptr, n, instance->bvh_builder, instance->bvh_pair_area_ratio};
+    LbvhInputs in{d_vertices_.ptr, d_indices_.ptr, d_pseudo.ptr, d_zero.ptr, 1u, d_ident.ptr, d_opaque.ptr, n, build_opts_.builder, build_opts_.pair_area_ratio};
     in.emit_quads = true;   // 64-byte leaf records (object space here), leaf links ~leaf number relative to the mesh
     LbvhOutputs out{};
     DeviceBuffer<BvhTri> tris;
@@ -658,64 +793,19 @@ bool Scene::build_two_level(Error& err) {
         ok = hip_ok(hipMemcpyAsync(d_quads_.ptr + m.quad_base, m.quads, sizeof(BvhQuad) * m.n_leaves, hipMemcpyDeviceToDevice, st), "copy leaf records", err);
     if (!ok) { (void)hipStreamSynchronize(st); free_nodes(); return false; }
   }
-  // ---- instance boxes: world AABB of the mesh's VERTICES under the instance's transform, padded.  (The eight corners of the
-  // mesh's object box, which is what a top level normally takes, give a box up to sqrt(2) too wide per axis for a rotated instance
-  // -- a quarter more instance entries per ray in the column forest.  The vertices cost meshes x instances x vertices on the host;
-  // past kExactBoxBudget point transforms the remaining instances fall back to the corners.) ----
+  // ---- what the top level needs of each mesh, kept for update_transforms ----
+  tl_meshes_.clear();
+  for (const MeshAs& m : meshes) {
+    TlMesh t{m.index_offset, m.index_count, m.grid, {m.lo[0], m.lo[1], m.lo[2]}, {m.hi[0], m.hi[1], m.hi[2]}};
+    tl_meshes_.push_back(t);
+  }
+  tl_mesh_of_ = mesh_of;
+  tl_points_ready_ = false;
+  tl_mesh_depth_ = max_depth;
+  // ---- instance boxes (host_instance_boxes) ----
   const size_t ni = h_instances.size();
-  std::vector<float4> blo(ni), bhi(ni);
-  double wlo[3] = {1e300, 1e300, 1e300}, whi[3] = {-1e300, -1e300, -1e300};
-  std::vector<std::vector<float>> mesh_points(meshes.size());   // xyz of the vertices a mesh references, once each
-  {
-    std::vector<uint8_t> seen(data.vertices.size(), 0);
-    for (size_t mi = 0; mi < meshes.size(); ++mi) {
-      const MeshAs& m = meshes[mi];
-      std::vector<float>& pts = mesh_points[mi];
-      for (uint32_t k = 0; k < m.index_count; ++k) {
-        const uint32_t v = data.indices[m.index_offset + k];
-        if (seen[v]) continue;
-        seen[v] = 1;
-        pts.insert(pts.end(), data.vertices[v].vv, data.vertices[v].vv + 3);
-      }
-      for (uint32_t k = 0; k < m.index_count; ++k) seen[data.indices[m.index_offset + k]] = 0;
-    }
-  }
-  constexpr uint64_t kExactBoxBudget = 50000000ull;
-  uint64_t spent = 0;
-  for (size_t i = 0; i < ni; ++i) {
-    const MeshAs& m = meshes[mesh_of[i]];
-    const float* M = data.transforms[h_instances[i].transform_id].m;
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    auto take = [&](double x, double y, double z) {
-      for (int k = 0; k < 3; ++k) {
-        const double w = (double)M[k] * x + (double)M[4 + k] * y + (double)M[8 + k] * z + (double)M[12 + k];
-        lo[k] = std::min(lo[k], w);
-        hi[k] = std::max(hi[k], w);
-      }
-    };
-    const std::vector<float>& pts = mesh_points[mesh_of[i]];
-    if (!pts.empty() && spent + pts.size() / 3 <= kExactBoxBudget) {
-      spent += pts.size() / 3;
-      for (size_t k = 0; k + 2 < pts.size(); k += 3) take(pts[k], pts[k + 1], pts[k + 2]);
-    } else {
-      for (int c = 0; c < 8; ++c) take((c & 1) ? m.hi[0] : m.lo[0], (c & 2) ? m.hi[1] : m.lo[1], (c & 4) ? m.hi[2] : m.lo[2]);
-    }
-    float l[3], h[3];
-    for (int k = 0; k < 3; ++k) {
-      if (!(lo[k] <= hi[k])) lo[k] = hi[k] = 0.0;   // a mesh without triangles / non-finite transform: a point nobody hits
-      // the tracer's world vertices are single-precision sums of four terms: four roundings of the largest one can get
-      const double mag = std::fabs((double)M[k]) * std::max(std::fabs((double)m.lo[0]), std::fabs((double)m.hi[0])) +
-                         std::fabs((double)M[4 + k]) * std::max(std::fabs((double)m.lo[1]), std::fabs((double)m.hi[1])) +
-                         std::fabs((double)M[8 + k]) * std::max(std::fabs((double)m.lo[2]), std::fabs((double)m.hi[2])) + std::fabs((double)M[12 + k]);
-      const double pad = 1e-5 * std::max({std::fabs(lo[k]), std::fabs(hi[k]), 1e-3}) + 1e-6 * (hi[k] - lo[k]) + (std::isfinite(mag) ? 4.8e-7 * mag : 0.0);
-      l[k] = std::nextafterf((float)(lo[k] - pad), -INFINITY);
-      h[k] = std::nextafterf((float)(hi[k] + pad), INFINITY);
-      wlo[k] = std::min(wlo[k], (double)l[k]);
-      whi[k] = std::max(whi[k], (double)h[k]);
-    }
-    blo[i] = make_float4(l[0], l[1], l[2], 0.0f);
-    bhi[i] = make_float4(h[0], h[1], h[2], 0.0f);
-  }
+  std::vector<float4> blo, bhi;
+  host_instance_boxes(tl_mesh_of_, instance_transforms(), box_meshes(), data.transforms, kExactBoxBudget, blo, bhi);
   DeviceBuffer<float4> d_blo, d_bhi;
   DeviceBuffer<BvhTri> top_tris;
   LbvhOutputs top{};
@@ -725,7 +815,7 @@ bool Scene::build_two_level(Error& err) {
     return false;
   }
   {
-    LbvhInputs in{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, (uint32_t)ni, instance->bvh_builder, 0.0f};
+    LbvhInputs in{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, (uint32_t)ni, build_opts_.builder, 0.0f};
     in.given_lo = d_blo.ptr;
     in.given_hi = d_bhi.ptr;
     top.tris = top_tris.ptr;
@@ -766,20 +856,28 @@ bool Scene::build_two_level(Error& err) {
   free_nodes();
   if (top.nodes) (void)hipFree(top.nodes);
   if (!ok) return false;
-  const double reach = std::sqrt((whi[0] - wlo[0]) * (whi[0] - wlo[0]) + (whi[1] - wlo[1]) * (whi[1] - wlo[1]) + (whi[2] - wlo[2]) * (whi[2] - wlo[2])) +
-                       std::max({std::fabs(wlo[0]), std::fabs(wlo[1]), std::fabs(wlo[2]), std::fabs(whi[0]), std::fabs(whi[1]), std::fabs(whi[2])});
+  tl_top_nodes_ = top.n_nodes;
+  if (!write_top_records(order, instance_reach(blo, bhi), err)) return false;
+  if (!d_top_.ptr && !hip_ok(d_top_.alloc(kBvhTopNodes), "alloc BVH top table", err)) return false;
+  if (!hip_ok(launch_top_table(st, d_nodes_.ptr, top.n_nodes, d_top_.ptr), "k_top_table", err)) return false;   // unused by the two-level tracer, kept valid
+  timer.stop(st);
+  if (!hip_ok(hipStreamSynchronize(st), "two-level build", err)) return false;
+  finish_two_level(top, timer.ms());
+  return true;
+}
+
+// The TlasInstance records in the top level's leaf order (`order`: the top level's leaves, world_id = instance), and the transform
+// flags.  `reach`: instance_reach of the instance boxes the top level was built over.
+bool Scene::write_top_records(const std::vector<BvhTri>& order, double reach, Error& err) {
+  hipStream_t st = instance->stream;
+  const size_t ni = h_instances.size();
   std::vector<TlasInstance> recs(ni);
-  std::vector<TransformPair> xf(data.transforms.size());
-  for (size_t t = 0; t < xf.size(); ++t) {
-    memcpy(xf[t].o2w, data.transforms[t].m, 64);
-    host::Mat4d inv;
-    if (!host::invert(host::Mat4d::from_f32(data.transforms[t].m), inv)) inv = host::Mat4d::identity();
-    inv.to_f32(xf[t].w2o);
-  }
+  const std::vector<TransformPair> xf = transform_pairs(data.transforms);
   for (size_t s = 0; s < ni; ++s) {
     const uint32_t i = order[s].world_id;   // the box this leaf was built from
     const RTInstance& in = h_instances[i];
-    const MeshAs& m = meshes[mesh_of[i]];
+    const TlMesh& m = tl_meshes_[tl_mesh_of_[i]];
+    const MeshRange& mr = h_mesh_ranges[tl_mesh_of_[i]];
     const TransformPair& T = xf[in.transform_id];
     TlasInstance r{};
     for (int row = 0; row < 3; ++row)
@@ -799,33 +897,27 @@ bool Scene::build_two_level(Error& err) {
     // that side needs, taken for all three, would make every box of the mesh as wide as the mesh)
     r.slack = (float)(32.0 * eps * (wnorm * reach + tr + objmax));
     r.w2o_norm = (float)wnorm;   // the tracer adds 32 eps wnorm |o|_1 per ray: origins far outside the scene's bounds
-    r.node_base = m.node_base;
-    r.tri_base = m.tri_base;
-    r.quad_base = m.quad_base;
+    r.node_base = mr.node_base;
+    r.tri_base = mr.tri_base;
+    r.quad_base = mr.quad_base;
     r.world_base = inst_base_[i];
     r.instance = i;
     r.non_opaque = h_materials[in.material_id].opacity != 0 ? 1u : 0u;
     recs[s] = r;
   }
   if (!hip_ok(d_tlas_instances_.upload(recs.data(), ni, st), "upload instance records", err)) return false;
-  std::vector<uint32_t> ident(data.transforms.size(), 0u);
-  for (size_t i = 0; i < ident.size(); ++i) {
-    static const float id[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    ident[i] = memcmp(data.transforms[i].m, id, 64) == 0 ? 1u : 0u;
-  }
+  const std::vector<uint32_t> ident = identity_flags(data.transforms);
   if (!hip_ok(d_xf_identity_.upload(ident.data(), ident.size(), st), "upload transform flags", err)) return false;
-  if (!d_top_.ptr && !hip_ok(d_top_.alloc(kBvhTopNodes), "alloc BVH top table", err)) return false;
-  if (!hip_ok(launch_top_table(st, d_nodes_.ptr, top.n_nodes, d_top_.ptr), "k_top_table", err)) return false;   // unused by the two-level tracer, kept valid
-  (void)hipEventRecord(e1, st);
-  if (!hip_ok(hipStreamSynchronize(st), "two-level build", err)) return false;
-  float ms = 0.0f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  return hip_ok(hipStreamSynchronize(st), "upload instance records", err);   // the staging vectors above must outlive the copies
+}
+
+// info, stack bound and DeviceScene of a two-level scene whose node array (top level first) and records are in place
+void Scene::finish_two_level(const LbvhOutputs& top, float build_ms) {
+  const uint32_t n_nodes = (uint32_t)d_nodes_.count, nt = (uint32_t)(d_tris_.count - 1), ni = (uint32_t)h_instances.size();
   info.bvh_nodes = n_nodes;
-  info.bvh_depth = top.depth + max_depth;
+  info.bvh_depth = top.depth + tl_mesh_depth_;
   info.bvh_sah_cost = top.sah;
-  info.build_ms = ms;
+  info.build_ms = build_ms;
   for (int k = 0; k < 3; ++k) {
     info.bounds_min[k] = top.bounds_lo[k];
     info.bounds_max[k] = top.bounds_hi[k];
@@ -833,8 +925,9 @@ bool Scene::build_two_level(Error& err) {
     info.bvh_grid_cell[k] = top.grid.cell[k];
   }
   // both levels' entries and one exit marker share the stack
-  const uint32_t stack_bound = 3u * (top.depth + max_depth) + 2u;
+  const uint32_t stack_bound = 3u * (top.depth + tl_mesh_depth_) + 2u;
   stack_overflow_depth = stack_bound > (uint32_t)kTraversalLdsStack ? stack_bound - kTraversalLdsStack + 1 : 1;
+  dev.transforms = d_transforms_.ptr;
   dev.bvh_nodes = d_nodes_.ptr;
   dev.bvh_top = d_top_.ptr;
   dev.bvh_grid = top.grid;
@@ -853,7 +946,6 @@ bool Scene::build_two_level(Error& err) {
   info.n_as_triangles = nt;
   info.as_bytes = (uint64_t)n_nodes * sizeof(BvhNode4) + (uint64_t)(nt + 1) * sizeof(BvhTri) + (uint64_t)nt * 128u + (uint64_t)ni * sizeof(TlasInstance) +
                   (uint64_t)d_quads_.count * sizeof(BvhQuad);
-  return true;
 }
 
 bool Scene::build_bvh(Error& err) {
@@ -868,7 +960,7 @@ bool Scene::build_bvh(Error& err) {
         unique += in.index_count / 3u;
       }
     }
-    const bool wanted = instance->as_levels == 2 || (instance->as_levels == 0 && unique > 0 && info.n_world_triangles > 4 * unique);
+    const bool wanted = build_opts_.as_levels == 2 || (build_opts_.as_levels == 0 && unique > 0 && info.n_world_triangles > 4 * unique);
     dev.two_level = 0u;
     dev.tlas_nodes = nullptr;
     dev.tlas_instances = nullptr;
@@ -880,23 +972,18 @@ bool Scene::build_bvh(Error& err) {
   if (!hip_ok(d_tris_.alloc((size_t)n + 1), "alloc BVH triangles", err)) return false;   // + 1: the tracer loads a leaf's partner slot unconditionally
   if (!hip_ok(hipMemsetAsync(d_tris_.ptr + n, 0, sizeof(BvhTri), st), "clear BVH triangle padding", err)) return false;
   LbvhInputs in{d_vertices_.ptr, d_indices_.ptr, d_instances_.ptr, d_inst_base_.ptr, (uint32_t)h_instances.size(), d_transforms_.ptr,
-                d_materials_.ptr, n, instance->bvh_builder, instance->bvh_pair_area_ratio};
+                d_materials_.ptr, n, build_opts_.builder, build_opts_.pair_area_ratio};
   in.emit_quads = true;   // the flattened tracer reads one 64-byte record per leaf (types.h BvhQuad); leaf links are ~leaf number
   in.emit_wide8 = true;   // ... and a small tile share the same hierarchy eight wide (types.h BvhNode8, k_trace8)
   LbvhOutputs out{};
   out.tris = d_tris_.ptr;
   d_quads_.release();
   d_nodes8_.release();
-  hipEvent_t e0, e1;
-  if (!hip_ok(hipEventCreate(&e0), "event", err) || !hip_ok(hipEventCreate(&e1), "event", err)) return false;
-  (void)hipEventRecord(e0, st);
+  StreamTimer timer;
+  if (!timer.start(st, err)) return false;
   const hipError_t be = build_lbvh(st, in, out);
-  (void)hipEventRecord(e1, st);
-  (void)hipEventSynchronize(e1);
-  float ms = 0.0f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  timer.stop(st);
+  const float ms = timer.ms();
   d_quads_.ptr = out.quads;       // ours whatever the build returned
   d_quads_.count = out.quads ? out.n_leaves : 0;
   d_nodes8_.ptr = out.nodes8;
@@ -936,11 +1023,7 @@ bool Scene::build_bvh(Error& err) {
   dev.bvh_tris = d_tris_.ptr;
   dev.bvh_quads = d_quads_.ptr;
   // per-leaf shading records (the identity flags let k_shade skip the object->world transform exactly)
-  std::vector<uint32_t> ident(data.transforms.size(), 0u);
-  for (size_t i = 0; i < ident.size(); ++i) {
-    static const float id[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    ident[i] = memcmp(data.transforms[i].m, id, 64) == 0 ? 1u : 0u;   // bitwise: -0.0 does not count
-  }
+  const std::vector<uint32_t> ident = identity_flags(data.transforms);
   if (!hip_ok(d_xf_identity_.upload(ident.data(), ident.size(), st), "upload transform flags", err)) return false;
   if (!hip_ok(d_shade_tris_.alloc((size_t)n * 8), "alloc shading records", err)) return false;
   if (!hip_ok(launch_shade_records(st, n, d_tris_.ptr, d_instances_.ptr, d_indices_.ptr, d_vertices_.ptr, d_derivatives_.ptr, d_xf_identity_.ptr,
@@ -1031,7 +1114,11 @@ bool Scene::update_materials_and_lights(const glz_material* mats, uint32_t n_mat
   data.lights.assign(lights, lights + n_lights);
   if (!build_materials(err)) return false;
   if (!build_lights_and_sky(err)) return false;
-  if (opacity_changed && !build_bvh(err)) return false;   // the non-opaque flag lives in the leaf records
+  if (opacity_changed) {   // the non-opaque flag lives in the leaf records; rebuilt with the instance's current options
+    build_opts_ = BuildOptions{instance->bvh_builder, instance->bvh_pair_area_ratio, instance->as_levels};
+    if (!build_bvh(err)) return false;
+    build_opts_.as_levels = (int)info.as_levels;
+  }
   if (!build_alpha_records(err)) return false;             // which opacity map a material names, where its texels lie
   info.n_lights = lights_no;
   info.n_rt_lights = (uint32_t)h_lights.size();
@@ -1044,6 +1131,232 @@ bool Scene::refresh_textures(const glz_texture* textures, uint32_t n, Error& err
   std::vector<glz_material> mats = data.materials;
   std::vector<glz_light> lights = data.lights;
   return update_materials_and_lights(mats.data(), (uint32_t)nm, lights.data(), (uint32_t)lights.size(), textures, n, err);
+}
+
+// ---- moving instances ------------------------------------------------------------------------------------------------------------
+std::vector<InstanceBoxMesh> Scene::box_meshes() const {
+  std::vector<std::pair<uint32_t, uint32_t>> ranges;
+  for (const TlMesh& m : tl_meshes_) ranges.emplace_back(m.index_offset, m.index_count);
+  std::vector<std::vector<float>> pts = mesh_points(data, ranges);
+  std::vector<InstanceBoxMesh> out(tl_meshes_.size());
+  for (size_t m = 0; m < out.size(); ++m) {
+    for (int k = 0; k < 3; ++k) {
+      out[m].lo[k] = tl_meshes_[m].lo[k];
+      out[m].hi[k] = tl_meshes_[m].hi[k];
+    }
+    out[m].points = std::move(pts[m]);
+  }
+  return out;
+}
+
+std::vector<uint32_t> Scene::instance_transforms() const {
+  std::vector<uint32_t> out(h_instances.size());
+  for (size_t i = 0; i < out.size(); ++i) out[i] = h_instances[i].transform_id;
+  return out;
+}
+
+bool host_instance_boxes_of(const SceneData& d, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err) {
+  for (const glz_mesh& m : d.meshes)
+    if ((uint64_t)m.index_offset + m.index_count > d.indices.size()) {
+      err.code = GLZ_E_INVALID_DATA;
+      err.msg = "mesh index range outside the index buffer";
+      return false;
+    }
+  for (uint32_t i : d.indices)
+    if (i >= d.vertices.size()) {
+      err.code = GLZ_E_INVALID_DATA;
+      err.msg = "vertex index out of range";
+      return false;
+    }
+  std::vector<glz_transform> transforms = d.transforms;
+  if (transforms.empty()) transforms.push_back(identity_transform());   // as Scene::create
+  const std::vector<RTInstance> inst = rt_instances(d);
+  std::vector<std::pair<uint32_t, uint32_t>> ranges;
+  std::vector<uint32_t> mesh_of(inst.size()), transform_of(inst.size());
+  for (size_t i = 0; i < inst.size(); ++i) {
+    if (inst[i].transform_id >= transforms.size()) {
+      err.code = GLZ_E_INVALID_DATA;
+      err.msg = "instance references a missing transform";
+      return false;
+    }
+    const std::pair<uint32_t, uint32_t> key(inst[i].index_offset, inst[i].index_count);
+    size_t m = 0;
+    while (m < ranges.size() && ranges[m] != key) ++m;
+    if (m == ranges.size()) ranges.push_back(key);
+    mesh_of[i] = (uint32_t)m;
+    transform_of[i] = inst[i].transform_id;
+  }
+  std::vector<std::vector<float>> pts = mesh_points(d, ranges);
+  std::vector<InstanceBoxMesh> meshes(ranges.size());
+  for (size_t m = 0; m < meshes.size(); ++m) {
+    InstanceBoxMesh& b = meshes[m];
+    for (int k = 0; k < 3; ++k) b.lo[k] = b.hi[k] = 0.0f;
+    for (size_t p = 0; p + 2 < pts[m].size(); p += 3)
+      for (int k = 0; k < 3; ++k) {
+        b.lo[k] = p == 0 ? pts[m][p + k] : std::min(b.lo[k], pts[m][p + k]);
+        b.hi[k] = p == 0 ? pts[m][p + k] : std::max(b.hi[k], pts[m][p + k]);
+      }
+    b.points = std::move(pts[m]);
+  }
+  host_instance_boxes(mesh_of, transform_of, meshes, transforms, budget, lo, hi);
+  return true;
+}
+
+// The device side of host_instance_boxes for the scene's current transforms (d_transforms_), into d_box_lo_ / d_box_hi_.
+bool Scene::device_instance_boxes(uint64_t budget, Error& err) {
+  hipStream_t st = instance->stream;
+  const size_t nm = tl_meshes_.size(), ni = h_instances.size();
+  if (!tl_points_ready_) {
+    const std::vector<InstanceBoxMesh> bm = box_meshes();
+    std::vector<float4> pts, mlo(nm), mhi(nm);
+    tl_point_base_.assign(nm, 0);
+    tl_point_count_.assign(nm, 0);
+    for (size_t m = 0; m < nm; ++m) {
+      tl_point_base_[m] = (uint32_t)pts.size();
+      tl_point_count_[m] = bm[m].points.size() / 3;
+      for (size_t p = 0; p + 2 < bm[m].points.size(); p += 3) pts.push_back(make_float4(bm[m].points[p], bm[m].points[p + 1], bm[m].points[p + 2], 0.0f));
+      mlo[m] = make_float4(bm[m].lo[0], bm[m].lo[1], bm[m].lo[2], 0.0f);
+      mhi[m] = make_float4(bm[m].hi[0], bm[m].hi[1], bm[m].hi[2], 0.0f);
+    }
+    for (size_t m = 0; m < nm; ++m)   // the corners, in host_instance_boxes' order, after every mesh's points
+      for (int c = 0; c < 8; ++c)
+        pts.push_back(make_float4((c & 1) ? bm[m].hi[0] : bm[m].lo[0], (c & 2) ? bm[m].hi[1] : bm[m].lo[1], (c & 4) ? bm[m].hi[2] : bm[m].lo[2], 0.0f));
+    if (pts.size() >= 0xFFFFFFFFull) {
+      err.code = GLZ_E_UNSUPPORTED;
+      err.msg = "more than 2^32 mesh vertices";
+      return false;
+    }
+    if (!hip_ok(d_tl_points_.upload(pts.data(), pts.size(), st), "upload mesh points", err) ||
+        !hip_ok(d_tl_mesh_lo_.upload(mlo.data(), nm, st), "upload mesh boxes", err) || !hip_ok(d_tl_mesh_hi_.upload(mhi.data(), nm, st), "upload mesh boxes", err) ||
+        !hip_ok(hipStreamSynchronize(st), "upload mesh points", err))
+      return false;
+    tl_points_ready_ = true;
+  }
+  // work items: an exact instance's points in chunks of one wave's share, the others' eight corners (exact_box_instances chooses, as on the host)
+  constexpr uint32_t kChunk = 64u * 32u;
+  const uint32_t corner_base = (uint32_t)(d_tl_points_.count - 8 * nm);
+  const std::vector<uint8_t> exact = exact_box_instances(tl_mesh_of_, tl_point_count_, budget);
+  std::vector<InstanceBoxItem> items;
+  std::vector<uint32_t> first(ni + 1);
+  for (size_t i = 0; i < ni; ++i) {
+    first[i] = (uint32_t)items.size();
+    const uint32_t m = tl_mesh_of_[i], t = h_instances[i].transform_id;
+    if (!exact[i]) {
+      items.push_back(InstanceBoxItem{t, m, corner_base + 8u * m, 8u});
+      continue;
+    }
+    for (uint64_t p = 0; p < tl_point_count_[m]; p += kChunk)
+      items.push_back(InstanceBoxItem{t, m, tl_point_base_[m] + (uint32_t)p, (uint32_t)std::min<uint64_t>(kChunk, tl_point_count_[m] - p)});
+  }
+  first[ni] = (uint32_t)items.size();
+  DeviceBuffer<InstanceBoxItem> d_items;
+  DeviceBuffer<uint32_t> d_first;
+  DeviceBuffer<double> d_partial;
+  if (!hip_ok(d_items.upload(items.data(), items.size(), st), "upload box items", err) || !hip_ok(d_first.upload(first.data(), first.size(), st), "upload box items", err) ||
+      !hip_ok(d_partial.alloc(6 * items.size()), "alloc box partials", err))
+    return false;
+  if (d_box_lo_.count != ni && (!hip_ok(d_box_lo_.alloc(ni), "alloc instance boxes", err) || !hip_ok(d_box_hi_.alloc(ni), "alloc instance boxes", err))) return false;
+  StreamTimer timer;
+  if (!timer.start(st, err)) return false;
+  if (!hip_ok(launch_instance_boxes(st, (uint32_t)items.size(), d_items.ptr, d_tl_points_.ptr, d_transforms_.ptr, d_partial.ptr, (uint32_t)ni, d_first.ptr,
+                                    d_tl_mesh_lo_.ptr, d_tl_mesh_hi_.ptr, d_box_lo_.ptr, d_box_hi_.ptr), "k_instance_boxes", err))
+    return false;
+  timer.stop(st);
+  if (!hip_ok(hipStreamSynchronize(st), "instance boxes", err)) return false;   // the staging vectors and scratch above must outlive the kernels
+  box_kernel_ms = timer.ms();
+  return true;
+}
+
+bool Scene::instance_boxes(bool on_device, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err) {
+  lo.clear();
+  hi.clear();
+  if (!dev.two_level) return false;
+  if (!on_device) {
+    host_instance_boxes(tl_mesh_of_, instance_transforms(), box_meshes(), data.transforms, budget, lo, hi);
+    return true;
+  }
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err) || !device_instance_boxes(budget, err)) return false;
+  lo.resize(h_instances.size());
+  hi.resize(h_instances.size());
+  return hip_ok(hipMemcpy(lo.data(), d_box_lo_.ptr, sizeof(float4) * lo.size(), hipMemcpyDeviceToHost), "read instance boxes", err) &&
+         hip_ok(hipMemcpy(hi.data(), d_box_hi_.ptr, sizeof(float4) * hi.size(), hipMemcpyDeviceToHost), "read instance boxes", err);
+}
+
+// The top level again, over the instance boxes of the current transforms; the meshes' hierarchies, leaf records and shading records
+// stay where they are (their links are relative to TlasInstance::node_base / quad_base / tri_base).
+bool Scene::rebuild_top_level(Error& err) {
+  hipStream_t st = instance->stream;
+  StreamTimer timer;
+  if (!timer.start(st, err)) return false;
+  const size_t ni = h_instances.size();
+  if (!device_instance_boxes(kExactBoxBudget, err)) return false;
+  DeviceBuffer<BvhTri> top_tris;
+  LbvhOutputs top{};
+  if (!hip_ok(top_tris.alloc(ni + 1), "alloc", err)) return false;
+  {
+    LbvhInputs in{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, (uint32_t)ni, build_opts_.builder, 0.0f};
+    in.given_lo = d_box_lo_.ptr;
+    in.given_hi = d_box_hi_.ptr;
+    top.tris = top_tris.ptr;
+    if (!hip_ok(build_lbvh(st, in, top), "instance hierarchy", err)) return false;
+  }
+  // ---- one node array: top level first, then the meshes (moved as they are when the top level's size changes) ----
+  const uint32_t old_top = tl_top_nodes_, mesh_nodes = (uint32_t)d_nodes_.count - old_top, n_nodes = top.n_nodes + mesh_nodes;
+  bool ok = true;
+  if (n_nodes >= (uint32_t)kBvhTopFlag) {
+    err.code = GLZ_E_UNSUPPORTED;
+    err.msg = "more than 2^30 BVH nodes";
+    ok = false;
+  }
+  BvhNode4* fresh = nullptr;
+  if (ok && top.n_nodes == old_top) {
+    ok = hip_ok(hipMemcpyAsync(d_nodes_.ptr, top.nodes, sizeof(BvhNode4) * top.n_nodes, hipMemcpyDeviceToDevice, st), "copy nodes", err);
+  } else if (ok) {
+    ok = hip_ok(hipMalloc(&fresh, sizeof(BvhNode4) * n_nodes), "alloc nodes", err);
+    if (ok) ok = hip_ok(hipMemcpyAsync(fresh, top.nodes, sizeof(BvhNode4) * top.n_nodes, hipMemcpyDeviceToDevice, st), "copy nodes", err);
+    if (ok) ok = hip_ok(hipMemcpyAsync(fresh + top.n_nodes, d_nodes_.ptr + old_top, sizeof(BvhNode4) * mesh_nodes, hipMemcpyDeviceToDevice, st), "move mesh nodes", err);
+  }
+  std::vector<BvhTri> order(ni);
+  std::vector<float4> blo(ni), bhi(ni);
+  if (ok) ok = hip_ok(hipMemcpyAsync(order.data(), top_tris.ptr, sizeof(BvhTri) * ni, hipMemcpyDeviceToHost, st), "read instance order", err);
+  if (ok) ok = hip_ok(hipMemcpyAsync(blo.data(), d_box_lo_.ptr, sizeof(float4) * ni, hipMemcpyDeviceToHost, st), "read instance boxes", err);
+  if (ok) ok = hip_ok(hipMemcpyAsync(bhi.data(), d_box_hi_.ptr, sizeof(float4) * ni, hipMemcpyDeviceToHost, st), "read instance boxes", err);
+  if (!hip_ok(hipStreamSynchronize(st), "top level", err)) ok = false;
+  if (top.nodes) (void)hipFree(top.nodes);
+  if (!ok) {
+    if (fresh) (void)hipFree(fresh);
+    return false;
+  }
+  if (fresh) {
+    d_nodes_.release();
+    d_nodes_.ptr = fresh;
+    d_nodes_.count = n_nodes;
+    for (MeshRange& r : h_mesh_ranges) r.node_base = r.node_base - old_top + top.n_nodes;
+  }
+  tl_top_nodes_ = top.n_nodes;
+  if (!write_top_records(order, instance_reach(blo, bhi), err)) return false;
+  if (!hip_ok(launch_top_table(st, d_nodes_.ptr, top.n_nodes, d_top_.ptr), "k_top_table", err)) return false;
+  timer.stop(st);
+  if (!hip_ok(hipStreamSynchronize(st), "top level", err)) return false;
+  finish_two_level(top, timer.ms());
+  return true;
+}
+
+bool Scene::update_transforms(const glz_transform* transforms, uint32_t n, Error& err) {
+  if (!transforms || n != data.transforms.size()) {
+    err.code = GLZ_E_ARG;
+    err.msg = "update_transforms: the transform count must not change (instances index transforms)";
+    return false;
+  }
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  data.transforms.assign(transforms, transforms + n);
+  const std::vector<TransformPair> xf = transform_pairs(data.transforms);
+  if (!hip_ok(hipMemcpyAsync(d_transforms_.ptr, xf.data(), sizeof(TransformPair) * n, hipMemcpyHostToDevice, instance->stream), "upload transforms", err) ||
+      !hip_ok(hipStreamSynchronize(instance->stream), "upload transforms", err))
+    return false;
+  // a flattened scene's world triangles depend on every transform: the whole structure again, with the options it was built with
+  if (!dev.two_level) return build_bvh(err) && hip_ok(hipStreamSynchronize(instance->stream), "update_transforms", err);
+  return rebuild_top_level(err);
 }
 
 }  // namespace glz

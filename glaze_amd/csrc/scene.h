@@ -9,6 +9,7 @@
 
 #include "device/types.h"
 #include "glaze_abi.h"
+#include "kernels.h"
 #include "parser.h"
 
 namespace glz {
@@ -33,6 +34,28 @@ struct Instance {
   ~Instance();
   static Instance* create(int hip_device, Error& err);
 };
+
+// ---- instance boxes of a two-level top level (scene.cpp) ----
+// Past this many point transforms, the remaining instances (in instance order) take the eight corners of their mesh's box.
+constexpr uint64_t kExactBoxBudget = 50000000ull;
+struct InstanceBoxMesh {
+  float lo[3], hi[3];          // the mesh's object box
+  std::vector<float> points;   // xyz of the distinct vertices the mesh references
+};
+std::vector<RTInstance> rt_instances(const SceneData& d);   // the instances the device gets (dangling ones dropped)
+// xyz of the distinct vertices each index range (offset, count) references, in first-use order
+std::vector<std::vector<float>> mesh_points(const SceneData& d, const std::vector<std::pair<uint32_t, uint32_t>>& ranges);
+// which instances take the exact box: in instance order, while the points spent stay within `budget`
+std::vector<uint8_t> exact_box_instances(const std::vector<uint32_t>& mesh_of, const std::vector<uint64_t>& mesh_point_count, uint64_t budget);
+// The host rule: instance i = mesh mesh_of[i] under transforms[transform_of[i]]; the f64 world AABB of the mesh's points (or of the
+// corners of its box), padded for the tracer's single-precision world vertices and widened by one ulp outwards.  Non-finite
+// transforms give a padded box around the origin.
+void host_instance_boxes(const std::vector<uint32_t>& mesh_of, const std::vector<uint32_t>& transform_of, const std::vector<InstanceBoxMesh>& meshes,
+                         const std::vector<glz_transform>& transforms, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi);
+double instance_reach(const std::vector<float4>& lo, const std::vector<float4>& hi);
+// The host rule on a scene description, no device: the meshes' boxes are the min / max of their vertices (a scene's own build takes
+// its mesh hierarchies' root boxes).  One box per instance that names an existing mesh.
+bool host_instance_boxes_of(const SceneData& d, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err);
 
 template <class T>
 struct DeviceBuffer {
@@ -70,6 +93,16 @@ class Scene {
   bool update_materials_and_lights(const glz_material* mats, uint32_t n_mats, const glz_light* lights, uint32_t n_lights,
                                    const glz_texture* textures, uint32_t n_textures, Error& err);
   bool refresh_textures(const glz_texture* textures, uint32_t n, Error& err);   // refresh_binded_textures, raytracer.rs:328-356
+  // New object -> world transforms, as many as the scene has (instances index them).  The structure is rebuilt with the builder, pair
+  // ratio and shape the scene was created with, and equals a scene created with these transforms: a flattened scene is built again
+  // in full (its world triangles depend on every transform); a two-level scene keeps its meshes' hierarchies and rebuilds the top
+  // level only.  Lights, sky, materials and textures are left alone.
+  bool update_transforms(const glz_transform* transforms, uint32_t n, Error& err);
+  // Instance boxes of a two-level scene under its current transforms (host rule, or the device kernel); false with an empty result
+  // for a flattened scene.  budget: kExactBoxBudget for the scene's own.
+  bool instance_boxes(bool on_device, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err);
+  size_t n_tlas_records() const { return dev.two_level ? d_tlas_instances_.count : 0; }
+  float box_kernel_ms = -1.0f;   // device-event time of the instance-box kernels the last time they ran (-1: never)
   // Mip levels 1.. of every texture on the device (mipchain.h: the file's levels when it brings all of them, else generated by
   // the LINEAR-blit rule, as load_texture_to_gpu does, scene.rs:1012-1263).  Built on first use: the reference's ray-tracing
   // stages only ever sample level 0, so a renderer without texture LOD never pays for them.
@@ -97,6 +130,35 @@ class Scene {
 
  size_t d_quads_count() const { return d_quads_.count; }   // leaf records: the flattened build's, or the meshes' concatenated (glz_debug_read_bvh)
  private:
+  // what shapes the acceleration structure, as the scene was built (Instance at creation; as_levels = the shape built, 1 or 2)
+  struct BuildOptions {
+    int builder;
+    float pair_area_ratio;
+    int as_levels;
+  };
+  BuildOptions build_opts_{};
+  // two-level scenes: what the top level needs of each mesh (node, leaf and triangle bases are in h_mesh_ranges)
+  struct TlMesh {
+    uint32_t index_offset, index_count;
+    BvhGrid grid;
+    float lo[3], hi[3];   // object box (the mesh hierarchy's root box)
+  };
+  std::vector<TlMesh> tl_meshes_;
+  std::vector<uint32_t> tl_mesh_of_;   // per RTInstance
+  uint32_t tl_top_nodes_ = 0;          // the top level's nodes at the head of d_nodes_
+  uint32_t tl_mesh_depth_ = 0;         // deepest mesh hierarchy
+  std::vector<InstanceBoxMesh> box_meshes() const;
+  std::vector<uint32_t> instance_transforms() const;
+  bool write_top_records(const std::vector<BvhTri>& order, double reach, Error& err);
+  void finish_two_level(const LbvhOutputs& top, float build_ms);
+  bool rebuild_top_level(Error& err);
+  bool device_instance_boxes(uint64_t budget, Error& err);   // -> d_box_lo_ / d_box_hi_
+  // the device side of the instance boxes, built on the first update: the meshes' distinct vertices then eight corners per mesh
+  bool tl_points_ready_ = false;
+  std::vector<uint64_t> tl_point_count_;
+  std::vector<uint32_t> tl_point_base_;
+  DeviceBuffer<float4> d_tl_points_, d_tl_mesh_lo_, d_tl_mesh_hi_, d_box_lo_, d_box_hi_;
+
   bool upload_geometry(Error& err);
   bool upload_textures(Error& err);
   bool update_textures(const glz_texture* textures, uint32_t n, Error& err);

@@ -312,6 +312,14 @@ int glz_renderer_change_scene(glz_renderer*, glz_scene* scene);          /* rayt
 int glz_renderer_update_materials_and_lights(glz_renderer*, const glz_material* mats, uint32_t n_mats,
                                              const glz_light* lights, uint32_t n_lights,
                                              const glz_texture* textures, uint32_t n_textures);
+/* Moves the instances: `transforms` replaces the scene's object -> world matrices (as many as the scene has: instances index them
+ * by a 16-bit id, and the count cannot change).  Waits for the renderer to go idle; restarts accumulation (a later step(k) / draw
+ * equals a fresh renderer's on a scene created with these transforms, same seed); reaches every device of set_devices.  The
+ * update acts on the SCENE object, so other renderers that share the scene see it too, as with materials.  The structure is
+ * rebuilt with the builder and shape the scene was created with: a flattened scene is built again in full; a two-level scene keeps
+ * its meshes' hierarchies and rebuilds only the top level.  Non-finite or singular transforms are taken as creation takes them.
+ * GLZ_E_ARG (nothing changes): null transforms, a different count. */
+int glz_renderer_update_transforms(glz_renderer*, const glz_transform* transforms, uint32_t n_transforms);
 /* raytracer.rs:328-356: the texture array changed under the same materials and lights (the reference re-binds the
  * textures it shares with the realtime viewer); accumulation is NOT restarted, like the reference. */
 int glz_renderer_refresh_binded_textures(glz_renderer*, const glz_texture* textures, uint32_t n_textures);
@@ -465,6 +473,16 @@ int64_t glz_debug_read_bvh(glz_scene*, void* nodes_out, int64_t cap_nodes, void*
  * builds only): child k's box words at [3k .. 3k+2], its link at [24 + k], leaf links name the first triangle slot as above. */
 int64_t glz_debug_read_bvh8(glz_scene*, void* nodes_out, int64_t cap_nodes);
 
+/* 192-byte TlasInstance records of a two-level scene in the top level's leaf order (returns the byte count; 0 for a flattened scene) */
+int64_t glz_debug_read_tlas_instances(glz_scene*, void* out, int64_t cap_bytes);
+/* Instance boxes of a two-level scene under its current transforms, 4 floats each (xyz, 0): on_device 0 = the host rule, 1 = the
+ * device kernel update_transforms uses.  budget: point transforms before the remaining instances take their mesh box's corners
+ * (0 = the library's own).  Returns the instance count (0 for a flattened scene); lo4 / hi4 take 4 x that many floats.  With both
+ * NULL only the count is returned and nothing runs. */
+int64_t glz_debug_instance_boxes(glz_scene*, int on_device, uint64_t budget, float* lo4, float* hi4);
+/* device-event time in ms of the instance-box kernels the last time they ran for this scene (an update, or glz_debug_instance_boxes
+ * on the device), the item upload and read-back excluded; -1 if they never ran */
+float glz_debug_box_kernel_ms(glz_scene*);
 /* one level of a scene texture's mip chain as the device holds it (level 0 = the texture; builds the chain if needed): returns the
  * byte count (0 past the last level), writes up to cap bytes and the level's dimensions */
 int64_t glz_debug_read_texture_level(glz_scene*, uint32_t texture, uint32_t level, uint8_t* out, int64_t cap, uint32_t* width, uint32_t* height);
@@ -503,6 +521,9 @@ int glz_host_srgb8_thresholds(float thresholds_out[256]);
  * byte count of that level (0 past the last), writes up to cap bytes */
 int64_t glz_host_mip_level(const glz_texture* texture, uint32_t level, uint8_t* out, int64_t cap, uint32_t* width, uint32_t* height);
 int glz_host_build_sah(uint32_t n, const float* box_lo, const float* box_hi, int32_t* children_out, int32_t* parent_out);
+/* the host rule of glz_debug_instance_boxes on a scene description (no device): a mesh's box is the min / max of its vertices here.
+ * One box per instance that names an existing mesh, in instance order; returns their count (both outputs NULL: the count alone). */
+int64_t glz_host_instance_boxes(const glz_scene_desc* desc, uint64_t budget, float* lo4, float* hi4);
 
 #ifdef __cplusplus
 }
