@@ -17,8 +17,8 @@ same accumulation (draw_frame semantics), K steps = K/depth samples per pixel.
 
 N > 1: the frame's 64x64 tiles are sharded over the GPUs (tile t -> GPU t % N); after the K steps the float HDR
 accumulator of every GPU is brought onto GPU 0 over RCCL / xGMI (inside the timed region; its share of the time is also
-printed as `exchange_ms`).  Total work is fixed -> "scaling": "strong".  GPU 0 then checks the assembled frame bit for bit
-against the frame it renders alone (--no-verify skips it).  Two ways to get there, same kernels and same partition:
+printed as `exchange_ms` with --full).  Total work is fixed -> "scaling": "strong".  With --full, GPU 0 then checks the assembled frame
+bit for bit against the frame it renders alone (--no-verify skips it).  Two ways to get there, same kernels and same partition:
   * started plainly (`python bench.py --gpus N`, no WORLD_SIZE in the environment): the product's own in-process path,
     glz_renderer_set_devices -- what `glaze-cli --devices 0,1,..` runs: one host thread, one scene replica and one RCCL
     communicator (ncclCommInitAll) per GPU, packed tiles sent to GPU 0 (ncclSend / ncclRecv in one group);
@@ -28,11 +28,16 @@ GLAZE_MULTI_EXCHANGE=reduce switches both to one ncclReduce(sum) of the zero-pad
 the packed tiles by hipMemcpyPeerAsync instead of RCCL -- also what the in-process form falls back to, saying so, when RCCL cannot be
 loaded or its communicators / first exchange fail on this machine.
 
-After the timed regions (and outside them) the same invocation also times, for at most half a second each, the other BASELINE
-configurations on one GPU (`extra.configs`: 2 = cube 512^2 depth 2, 3 = mattest.glaze 1024^2 depth 8, 5 = the atrium at 3840x2160 depth 12)
-and the atrium with the content classes real Sponza has and the stand-in lacks (`extra.atrium_sponza_like`: opacity-mapped cloth, foliage
-cards and vines, normal maps on stone, roughness maps on the Uber materials); `--no-extras` skips them.  N > 1: every step that can block
-on another GPU -- spanning the devices, every exchange, the process group's barrier -- runs under a watchdog: after its time-out
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line.
+Everything else runs after the timed regions (and outside them) only with --full; without it its fields are null (`verify`: left out):
+`roofline` (an instrumented pass over the same launches and, at N = 1, three rocprofv3 --pmc passes), `cpu_baseline` (the oracle on 16 launches),
+`grays_per_s`, and at N = 1 `extra`: the other BASELINE configurations on one GPU, timed for at most half a second each (`extra.configs`:
+2 = cube 512^2 depth 2, 3 = mattest.glaze 1024^2 depth 8, 5 = the atrium at 3840x2160 depth 12) and the atrium with the content classes
+real Sponza has and the stand-in lacks (`extra.atrium_sponza_like`: opacity-mapped cloth, foliage cards and vines, normal maps on stone,
+roughness maps on the Uber materials); at N > 1 `exchange_ms`, `config5` and `verify`.  Under --full, --no-pmc, --no-cpu-baseline,
+--no-extras, --no-configs, --no-config5 and --no-verify drop single parts; --config5 and --verify ask for theirs without --full.
+
+N > 1: every step that can block on another GPU -- spanning the devices, every exchange, the process group's barrier -- runs under a watchdog: after its time-out
 (GLAZE_BENCH_WATCHDOG_SPAN_S, default 180 s, to span the devices; GLAZE_BENCH_WATCHDOG_S, default 90 s, per exchange or barrier) it prints `multi_gpu.diagnostics` (which call, how long, RCCL
 version, the peer-access matrix, bytes per peer, the RCCL / HSA environment) to stderr and ends the process with status 3 through os._exit.
 
@@ -68,10 +73,13 @@ def parse_args():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions, also measure and check everything besides the headline: roofline (instrumented pass, PMC passes), "
+                         "cpu_baseline, extra (N = 1), exchange_ms, config5 and verify (N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-launches", type=int, default=16, help="launches of the bounded CPU-baseline sample")
-    ap.add_argument("--verify", dest="verify", action="store_true", default=True,
-                    help="N > 1: rank 0 re-renders the whole frame alone and compares it bit for bit (default)")
+    ap.add_argument("--verify", dest="verify", action="store_true", default=None,
+                    help="N > 1: rank 0 re-renders the whole frame alone and compares it bit for bit (default with --full)")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
     ap.add_argument("--repeats", type=int, default=1, help="timed regions of K steps each (`value` and `ms_per_step` from the median one)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -83,13 +91,15 @@ def parse_args():
                          "e.g. the Sponza the reference's README links (also: GLAZE_BENCH_SCENE)")
     ap.add_argument("--config5", dest="config5", action="store_true", default=None,
                     help="also time BASELINE configs[4] (3840x2160, depth 12, same scene) as a second, separately named measurement "
-                         "(default: when N > 1)")
+                         "(default: with --full when N > 1)")
     ap.add_argument("--no-config5", dest="config5", action="store_false")
     ap.add_argument("--no-extras", action="store_true", help="N = 1: do not time the other BASELINE configurations and the Sponza-like atrium after the timed regions")
     ap.add_argument("--no-configs", action="store_true", help="N = 1: do not time BASELINE configs 2, 3 and 5 (extra.configs)")
     args = ap.parse_args()
     if args.steps < 1 or args.repeats < 1 or args.warmup < 0:
         ap.error("--steps and --repeats must be at least 1, --warmup at least 0")
+    if args.verify is None:
+        args.verify = args.full
     return args
 
 
@@ -410,17 +420,18 @@ def main():
             scene_name = "Sponza-class synthetic atrium"
             data_tag = "synthetic"
         glaze_bytes = os.path.getsize(path)
-        # what the bookkeeping needs to know of the file (the sky's table height): read through the same parser, before the scene consumes it
+        # what the bookkeeping needs to know of the file (the sky's table height, --full only): read through the same parser, before the
+        # scene consumes it
         meta_parse = glaze_amd.parse(path)
         sky_ids = [int(l.resource_id) for l in meta_parse.lights() if int(l.ltype) == glaze_amd.abi.LIGHT_SKY]
-        tex = meta_parse.textures() if sky_ids else []
+        tex = meta_parse.textures() if sky_ids and args.full else []
         sky_rows = max([int(tex[i][1].shape[0]) for i in sky_ids if i < len(tex)] + [0])
         n_lights = len(meta_parse.lights())
         meta_parse.close()
         t0 = time.time()
         scene = glaze_amd.RayTraceScene.new(inst, glaze_amd.parse(path))
         setup_s = time.time() - t0
-        if desc is None and rank == 0 and not args.no_cpu_baseline and not args.pmc_child and n_gpus == 1:
+        if desc is None and rank == 0 and args.full and not args.no_cpu_baseline and not args.pmc_child and n_gpus == 1:
             from oracle.pyoracle import desc_from_file        # (the checker's own reader: only the cpu_baseline leg uses it)
             desc = desc_from_file(path)
     info = scene.info()
@@ -550,7 +561,7 @@ def main():
     # the exchange alone (it is INSIDE every timed region above; this is only to show its share): nothing new was rendered,
     # so it moves the same frame again
     exchange_ms = None
-    if n_gpus > 1:
+    if n_gpus > 1 and args.full:
         ex = []
         for _ in range(3):
             sync_all()
@@ -561,10 +572,10 @@ def main():
         exchange_ms = sorted(ex)[1]
     # what GPU 0 holds now is the frame of warmup + K * regions launches, assembled from all GPUs: kept for the check at the end
     verify_frame = frame.cpu().numpy().copy() if (n_gpus > 1 and args.verify and rank == 0) else None
-    # ---- BASELINE configs[4] next to it (N > 1 by default): the same scene at 3840x2160, depth 12, tiles over the same GPUs, the same
-    # exchange inside the timed regions -- a second, separately named measurement; `value` stays the 1080p frame.
+    # ---- BASELINE configs[4] next to it (N > 1 with --full by default): the same scene at 3840x2160, depth 12, tiles over the same GPUs,
+    # the same exchange inside the timed regions -- a second, separately named measurement; `value` stays the 1080p frame.
     config5 = None
-    if args.config5 if args.config5 is not None else n_gpus > 1:
+    if args.config5 if args.config5 is not None else (args.full and n_gpus > 1):
         W5, H5, D5 = 3840, 2160, 12
         renderer.change_resolution(W5, H5)
         renderer_size[:] = [W5, H5]
@@ -597,7 +608,8 @@ def main():
     kern_ms = {"k_trace": s1.trace_closest_ms - s0.trace_closest_ms, "k_shade": s1.shade_ms - s0.shade_ms, "k_path": s1.other_ms - s0.other_ms}
 
     out = None
-    if rank == 0:
+    roofline, counted = None, None
+    if rank == 0 and args.full:
         # counted per-sample work of the same workload: a separate, untimed pass with the instrumented kernels over the SAME
         # launch indices as the timed window (launches [warmup, warmup + K * regions) after a restart -- the mix of path ages,
         # and with it the work per sample, depends on the launch index), capped at 1024 launches
@@ -697,8 +709,9 @@ def main():
                     "counted_over_launches": [args.warmup, args.warmup + n_count],
                     "kernel_ms_per_step": {k: round(v / total_steps, 4) for k, v in kern_ms.items() if v > 0 or k != "k_path"},
                     "launch_mode": renderer.launch_mode()}
+    if rank == 0:
         cpu = None
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             # CPU baseline: the oracle (scalar C++ restatement; the reference has no CPU tracer) on a
             # bounded sample of the SAME workload: same scene/frame/depth/seed, fewer launches.
             from oracle.pyoracle import OracleRenderer, OracleScene
@@ -722,7 +735,7 @@ def main():
             cpu["single_thread"] = {"value": round(W * H / dt1 / 1e6, 3), "unit": "Msamples/s", "cores": 1,
                                     "sample": "1 launch (%.1f s)" % dt1}
         extra = None
-        if n_gpus == 1 and not args.no_extras and not args.scene:
+        if args.full and n_gpus == 1 and not args.no_extras and not args.scene:
             extra = {}
 
             def quick_time(r, w, h, budget_s=0.4, warm=16):
@@ -817,7 +830,7 @@ def main():
                 except Exception:       # noqa: BLE001
                     rccl = None
                 seen = dist.get_world_size()
-            multi = {"mode": mode, "exchange": how, "exchange_ms": round(exchange_ms, 4), "exchange_bytes_to_gpu0": int(W * H * 16 * (n_gpus - 1) / n_gpus) if exchange != "reduce" or loopback else W * H * 16,
+            multi = {"mode": mode, "exchange": how, "exchange_ms": None if exchange_ms is None else round(exchange_ms, 4), "exchange_bytes_to_gpu0": int(W * H * 16 * (n_gpus - 1) / n_gpus) if exchange != "reduce" or loopback else W * H * 16,
                      "rccl_version": rccl, "gpus_seen": seen, "measurement": not (loopback or rehearsal), "set_devices_s": None if devices_s is None else round(devices_s, 3), "rccl_fallback": rccl_fallback,
                      "first_exchange_ms": None if first_exchange_ms is None else round(first_exchange_ms, 3),
                      "exchange_bytes_per_peer": int(W * H * 16 / n_gpus) if exchange != "reduce" else W * H * 16,
@@ -840,7 +853,7 @@ def main():
                        "setup_s": round(setup_s, 3), "serialize_s": round(serialize_s, 3)},
             "roofline": roofline, "cpu_baseline": cpu, "multi_gpu": multi, "config5": config5 if multi is None else None, "extra": extra,
             "mpaths_per_s": round(value / args.depth, 2),
-            "grays_per_s": round(value * (1 + counted["f_shadow"]) / 1e3, 3),
+            "grays_per_s": None if counted is None else round(value * (1 + counted["f_shadow"]) / 1e3, 3),
         }
     failure = None
     if n_gpus > 1 and args.verify and rank == 0:

@@ -37,14 +37,14 @@ def check_line(out, name, triangles):
 
 
 def test_bench_on_a_supplied_glaze_file():
-    """mattest.glaze (the reference's own fixture) instead of the atrium: a full line -- roofline and cpu_baseline included, the oracle
+    """mattest.glaze (the reference's own fixture) instead of the atrium: a --full line -- roofline and cpu_baseline included, the oracle
     reading the same file with its own reader -- whose data / workload fields name the file; triangle count and BVH figures come from
     scene.info()."""
-    out, _ = run_bench("--scene", MATTEST)
+    out, _ = run_bench("--full", "--scene", MATTEST)
     check_line(out, "mattest.glaze", 138480)
     assert out["roofline"]["counted_per_sample"]["f_hit"] > 0.1      # the camera of the file looks at the scene
     # the environment variable does the same
-    out2, _ = run_bench("--no-cpu-baseline", env={"GLAZE_BENCH_SCENE": MATTEST})
+    out2, _ = run_bench("--full", "--no-cpu-baseline", env={"GLAZE_BENCH_SCENE": MATTEST})
     assert out2["data"] == "file:mattest.glaze" and out2["cpu_baseline"] is None
 
 
@@ -55,6 +55,17 @@ def test_bench_on_an_obj_through_the_converter():
     out, err = run_bench("--scene", CUBE_OBJ, "--no-cpu-baseline")
     assert out["data"] == "file:cube.obj" and out["config"]["triangles"] == 12
     assert "has no lights" in err
+
+
+def test_plain_bench_runs_only_its_timed_steps():
+    """Without --full the line carries the headline and the workload's description, and nothing that takes runs of its own: no instrumented
+    pass, no PMC passes, no CPU baseline, no other configurations."""
+    out, _ = run_bench()
+    assert out["data"] == "synthetic" and out["n_gpus"] == 1 and out["steps"] == 8 and out["warmup"] == 2 and len(out["regions_ms"]) == 1
+    assert out["metric"].startswith("Msamples/s") and out["unit"] == "Msamples/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["config"]["triangles"] == 262267 and out["config"]["bvh"]["nodes"] > 0
+    for k in ("roofline", "cpu_baseline", "extra", "grays_per_s", "multi_gpu", "config5"):
+        assert out[k] is None, k
 
 
 def test_bench_dumps_what_its_timed_steps_computed(tmp_path):

@@ -504,7 +504,7 @@ def instance_count():
 def test_bench_in_process_multi_gpu(tmp_path):
     """`python bench.py --gpus N` without a launcher: the in-process set_devices path (loop-back on the one GPU), verified bit for bit;
     a plain --gpus 2 on a one-GPU box fails with a clear message instead of hanging."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "2", "--width", "640", "--height", "360", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "2", "--width", "640", "--height", "360", "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run(cmd, capture_output=True, text=True, env=dict(env, **BENCH_LOOPBACK_ENV), timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -520,13 +520,28 @@ def test_bench_in_process_multi_gpu(tmp_path):
         assert p.returncode != 0 and "this machine has 1 GPU" in p.stderr
 
 
+def test_plain_bench_in_process_multi_gpu_times_only_its_steps():
+    """`python bench.py --gpus N` without --full: the exchange stays inside the timed region, and the line names the mode and the exchange,
+    but nothing else runs -- no separate exchange timing, no config5, no re-render of the whole frame to compare with."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--width", "640", "--height", "360"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    p = subprocess.run(cmd, capture_output=True, text=True, env=dict(env, **BENCH_LOOPBACK_ENV), timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    assert out["n_gpus"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0 and len(out["regions_ms"]) == 1
+    m = out["multi_gpu"]
+    assert m["gpus_seen"] == 2 and m["measurement"] is False and m["first_exchange_ms"] > 0
+    assert m["exchange_ms"] is None and m["config5"] is None and "verify" not in out
+    assert out["roofline"] is None and out["cpu_baseline"] is None
+
+
 def test_bench_falls_back_to_peer_copies_when_rccl_will_not_start(tmp_path):
     """ncclCommInitAll fails (injected into the stand-in library): bench.py says why on stderr, switches to the peer-copy exchange, still
     verifies the frame bit for bit and names the exchange and the reason in its line."""
     lib = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
     if not os.path.exists(lib):
         pytest.skip("tests/fake_rccl/libfake_rccl.so is not built (__graft_entry__.build())")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "2", "--width", "640", "--height", "360", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "2", "--width", "640", "--height", "360", "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "GLAZE_MULTI_EXCHANGE")}
     for fail in ("ncclCommInitAll", "ncclSend"):
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=900,
