@@ -1,5 +1,6 @@
 """More whole renders against closed forms (see test_analytic_render.py for why): the light callables and specular paths that the
-point-light room does not touch.  Every scene is OPEN -- a wall that fills the view, a few small quads -- so that the converged
+point-light room does not touch.  Every scene is OPEN (the closed room, with more than one diffuse bounce and the roulette, is
+test_analytic_enclosure.py) -- a wall that fills the view, a few small quads -- so that the converged
 image can be written down in float64 numpy from the reference's shaders alone:
 
   * sun light (light_sun_sample_visible.rcall): no distance falloff, pdf 1, a parallel shadow
