@@ -138,6 +138,15 @@ constexpr int kBvhEmptyChild = 0x7FFFFFFF;
 constexpr int kBvhTopNodes = 21;
 constexpr int kBvhTopFlag = 0x40000000;
 constexpr uint32_t kBvhGridMax = 32767u;   // 15-bit grid coordinates: 0x47000000 | q << 8 is the float 32768 + q (box_key)
+// the node without children (host side: a mesh without triangles; a hierarchy of one leaf puts its leaf into the first slot)
+inline BvhNode4 childless_node4() {
+  BvhNode4 nd{};
+  for (int k = 0; k < 4; ++k) {
+    nd.w[3 * k] = nd.w[3 * k + 1] = nd.w[3 * k + 2] = kBvhGridMax;
+    nd.w[12 + k] = (uint32_t)kBvhEmptyChild;
+  }
+  return nd;
+}
 struct BvhGrid {
   float lo[3];
   float cell[3];

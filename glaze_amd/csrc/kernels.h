@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "device/types.h"
+#include "device_buffer.h"
 
 namespace glz {
 
@@ -34,15 +35,15 @@ struct LbvhInputs {
 constexpr int kBvhBuilderLbvh = 0, kBvhBuilderPloc = 1, kBvhBuilderSah = 2, kBvhBuilderAuto = 3, kBvhBuilderSahHost = 4;   // = GLZ_BVH_LBVH / _PLOC / _SAH / _AUTO / _SAH_HOST
 // host side of the SAH builder (bvh_sah.cpp): binary hierarchy over n leaf boxes -> children / parent arrays
 void build_sah_host(uint32_t n, const float4* lo, const float4* hi, int2* children, int* parent);
+// nodes / nodes8 / quads are allocated by build_lbvh and owned by this struct: what the caller wants to keep it moves out, the rest is
+// freed with the struct -- also after a failed build, whatever it got to.  Their .count is the number of entries.
 struct LbvhOutputs {
-  BvhNode4* nodes;  // n_nodes entries, hipMalloc'ed by build_lbvh: the caller owns them afterwards
-  uint32_t n_nodes;
-  BvhNode8* nodes8; // emit_wide8: n_nodes8 entries, hipMalloc'ed by build_lbvh (the caller owns them), else null; a scene of one leaf has none
-  uint32_t n_nodes8, depth8;
+  DeviceBuffer<BvhNode4> nodes;    // empty for n_world = 0
+  DeviceBuffer<BvhNode8> nodes8;   // emit_wide8, else empty; a scene of one leaf has none
+  uint32_t depth8;
   BvhGrid grid;     // quantisation grid of the node boxes
-  BvhTri* tris;     // n_world + 1 entries (the tracer reads one past a leaf's first triangle), preallocated; leaf order, a leaf's triangles adjacent
-  BvhQuad* quads;   // emit_quads: n_leaves records, hipMalloc'ed by build_lbvh (the caller owns them), else null
-  uint32_t n_leaves;
+  BvhTri* tris;     // n_world + 1 entries (the tracer reads one past a leaf's first triangle), preallocated by the caller; leaf order, a leaf's triangles adjacent
+  DeviceBuffer<BvhQuad> quads;     // emit_quads: one record per leaf, else empty
   uint32_t depth;   // number of 4-wide nodes above the deepest leaf (the traversal stack holds at most 3 * depth + 1 entries)
   float sah;
   uint32_t rounds;  // PLOC merge rounds (0 for the LBVH)

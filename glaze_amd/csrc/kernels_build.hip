@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "device/math.h"
@@ -1359,149 +1360,134 @@ hipError_t build_lbvh(hipStream_t st, const LbvhInputs& in, LbvhOutputs& out) {
   out.depth = 0;
   out.sah = 0.0f;
   out.rounds = 0;
-  out.nodes = nullptr;
-  out.nodes8 = nullptr;
-  out.n_nodes8 = 0;
+  out.nodes.release();
+  out.nodes8.release();
   out.depth8 = 0;
-  out.quads = nullptr;
-  out.n_nodes = 0;
-  out.n_leaves = 0;
+  out.quads.release();
   if (nw == 0) return hipSuccess;
   const uint32_t np_max = std::max<uint32_t>(next_pow2(nw), kSortTile);
-  hipError_t e;
-  BvhTri* tris_unsorted = nullptr;
-  float4 *lo = nullptr, *hi = nullptr, *leaf_lo = nullptr, *leaf_hi = nullptr, *node_lo = nullptr, *node_hi = nullptr;
-  uint64_t* keys = nullptr;
-  uint32_t *vals = nullptr, *leaf_first = nullptr;
-  uint8_t* role = nullptr;
-  int2* children = nullptr;
-  int *parent = nullptr, *node_depth = nullptr, *scalars = nullptr, *counts = nullptr, *new_id = nullptr;
-  int *refs_a = nullptr, *refs_b = nullptr, *nearest = nullptr;
-  uint32_t *sah_idx_a = nullptr, *sah_idx_b = nullptr, *sah_counts = nullptr, *sah_total_chunks = nullptr, *sah_chunk_left = nullptr;
-  SahWideNode* sah_wide = nullptr;
-  SahTask *sah_queue_a = nullptr, *sah_queue_b = nullptr;
-  unsigned long long *flags = nullptr, *pos = nullptr, *slot = nullptr, *scan_tmp = nullptr, *scan_total = nullptr;
-  float* sah = nullptr;
-  BvhGrid* grid = nullptr;
-  auto cleanup = [&]() {
-    void* bufs[] = {tris_unsorted, lo, hi, leaf_lo, leaf_hi, leaf_first, role, node_lo, node_hi, keys, vals, children, parent, node_depth, scalars, sah,
-                    grid, counts, new_id, refs_a, refs_b, nearest, flags, pos, slot, scan_tmp, scan_total, sah_idx_a, sah_idx_b, sah_counts, sah_queue_a, sah_queue_b, sah_total_chunks, sah_chunk_left, sah_wide};
-    for (void* b : bufs)
-      if (b) (void)hipFree(b);
-  };
-#define GLZ_TRY(x) do { e = (x); if (e != hipSuccess) { cleanup(); return e; } } while (0)
-  GLZ_TRY(hipMalloc(&tris_unsorted, sizeof(BvhTri) * nw));
-  GLZ_TRY(hipMalloc(&lo, sizeof(float4) * nw));
-  GLZ_TRY(hipMalloc(&hi, sizeof(float4) * nw));
-  GLZ_TRY(hipMalloc(&leaf_lo, sizeof(float4) * nw));
-  GLZ_TRY(hipMalloc(&leaf_hi, sizeof(float4) * nw));
-  GLZ_TRY(hipMalloc(&leaf_first, sizeof(uint32_t) * nw));
-  GLZ_TRY(hipMalloc(&role, nw));
-  GLZ_TRY(hipMalloc(&node_lo, sizeof(float4) * (2 * (size_t)nw)));
-  GLZ_TRY(hipMalloc(&node_hi, sizeof(float4) * (2 * (size_t)nw)));
-  GLZ_TRY(hipMalloc(&keys, sizeof(uint64_t) * np_max));
-  GLZ_TRY(hipMalloc(&vals, sizeof(uint32_t) * np_max));
-  GLZ_TRY(hipMalloc(&children, sizeof(int2) * nw));
-  GLZ_TRY(hipMalloc(&parent, sizeof(int) * (2 * (size_t)nw)));
-  GLZ_TRY(hipMalloc(&node_depth, sizeof(int) * nw));
-  GLZ_TRY(hipMalloc(&scalars, sizeof(int) * 8));
-  GLZ_TRY(hipMalloc(&sah, sizeof(float)));
-  GLZ_TRY(hipMalloc(&grid, sizeof(BvhGrid)));
-  GLZ_TRY(hipMalloc(&counts, sizeof(int) * nw));
+  // every temporary is freed on the way out, whichever way that is (hipFree waits for work in flight)
+  DeviceBuffer<BvhTri> tris_unsorted;
+  DeviceBuffer<float4> lo, hi, leaf_lo, leaf_hi, node_lo, node_hi;
+  DeviceBuffer<uint64_t> keys;
+  DeviceBuffer<uint32_t> vals, leaf_first;
+  DeviceBuffer<uint8_t> role;
+  DeviceBuffer<int2> children;
+  DeviceBuffer<int> parent, node_depth, scalars, counts, new_id;
+  DeviceBuffer<int> refs_a, refs_b, nearest;   // PLOC only
+  DeviceBuffer<uint32_t> sah_idx_a, sah_idx_b, sah_counts, sah_total_chunks, sah_chunk_left;   // SAH only, as the three below
+  DeviceBuffer<SahWideNode> sah_wide;
+  DeviceBuffer<SahTask> sah_queue_a, sah_queue_b;
+  DeviceBuffer<unsigned long long> flags, pos, slot, scan_tmp, scan_total;
+  DeviceBuffer<float> sah;
+  DeviceBuffer<BvhGrid> grid;
+#define GLZ_TRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+  GLZ_TRY(tris_unsorted.alloc(nw));
+  GLZ_TRY(lo.alloc(nw));
+  GLZ_TRY(hi.alloc(nw));
+  GLZ_TRY(leaf_lo.alloc(nw));
+  GLZ_TRY(leaf_hi.alloc(nw));
+  GLZ_TRY(leaf_first.alloc(nw));
+  GLZ_TRY(role.alloc(nw));
+  GLZ_TRY(node_lo.alloc(2 * (size_t)nw));
+  GLZ_TRY(node_hi.alloc(2 * (size_t)nw));
+  GLZ_TRY(keys.alloc(np_max));
+  GLZ_TRY(vals.alloc(np_max));
+  GLZ_TRY(children.alloc(nw));
+  GLZ_TRY(parent.alloc(2 * (size_t)nw));
+  GLZ_TRY(node_depth.alloc(nw));
+  GLZ_TRY(scalars.alloc(8));
+  GLZ_TRY(sah.alloc(1));
+  GLZ_TRY(grid.alloc(1));
+  GLZ_TRY(counts.alloc(nw));
   {
     const size_t tiles = ((size_t)nw + kScanTile - 1) / kScanTile;
-    GLZ_TRY(hipMalloc(&flags, sizeof(unsigned long long) * nw));
-    GLZ_TRY(hipMalloc(&pos, sizeof(unsigned long long) * nw));
-    GLZ_TRY(hipMalloc(&slot, sizeof(unsigned long long) * nw));
-    GLZ_TRY(hipMalloc(&scan_tmp, sizeof(unsigned long long) * (2 * tiles + 4096)));
-    GLZ_TRY(hipMalloc(&scan_total, sizeof(unsigned long long)));
+    GLZ_TRY(flags.alloc(nw));
+    GLZ_TRY(pos.alloc(nw));
+    GLZ_TRY(slot.alloc(nw));
+    GLZ_TRY(scan_tmp.alloc(2 * tiles + 4096));
+    GLZ_TRY(scan_total.alloc(1));
   }
-  GLZ_TRY(hipMalloc(&new_id, sizeof(int) * nw));
-  GLZ_TRY(hipMemsetAsync(sah, 0, sizeof(float), st));
-  GLZ_TRY(hipMemsetAsync(role, 0, nw, st));
+  GLZ_TRY(new_id.alloc(nw));
+  GLZ_TRY(hipMemsetAsync(sah.ptr, 0, sizeof(float), st));
+  GLZ_TRY(hipMemsetAsync(role.ptr, 0, nw, st));
   {
     // ordered-int encodings of +inf / -inf, then depth counter
     const int init[8] = {0x7F800000, 0x7F800000, 0x7F800000, (int)0xFF800000 ^ 0x7FFFFFFF, (int)0xFF800000 ^ 0x7FFFFFFF,
                          (int)0xFF800000 ^ 0x7FFFFFFF, 0, 0};
-    GLZ_TRY(hipMemcpyAsync(scalars, init, sizeof(init), hipMemcpyHostToDevice, st));
+    GLZ_TRY(hipMemcpyAsync(scalars.ptr, init, sizeof(init), hipMemcpyHostToDevice, st));
   }
   const dim3 blk(256), grdw((nw + 255) / 256);
   if (in.given_lo && in.given_hi) {
-    hipLaunchKernelGGL(k_given_boxes, grdw, blk, 0, st, in.given_lo, in.given_hi, nw, tris_unsorted, lo, hi, scalars);
+    hipLaunchKernelGGL(k_given_boxes, grdw, blk, 0, st, in.given_lo, in.given_hi, nw, tris_unsorted.ptr, lo.ptr, hi.ptr, scalars.ptr);
   } else {
     hipLaunchKernelGGL(k_world_tris, grdw, blk, 0, st, in.vertices, in.indices, in.instances, in.inst_base, in.n_instances, in.transforms,
-                       in.materials, nw, tris_unsorted, lo, hi, scalars);
+                       in.materials, nw, tris_unsorted.ptr, lo.ptr, hi.ptr, scalars.ptr);
   }
   GLZ_TRY(hipGetLastError());
   // leaves: pairs of triangles where they qualify, single triangles otherwise
   if (in.pair_area_ratio > 0.0f && !in.given_lo) {
     for (uint32_t parity = 0; parity < 2; ++parity) {
-      hipLaunchKernelGGL(k_pair_triangles, grdw, blk, 0, st, nw, parity, tris_unsorted, in.indices, in.instances, lo, hi, in.pair_area_ratio, in.emit_quads ? 1u : 0u, role);
+      hipLaunchKernelGGL(k_pair_triangles, grdw, blk, 0, st, nw, parity, tris_unsorted.ptr, in.indices, in.instances, lo.ptr, hi.ptr, in.pair_area_ratio, in.emit_quads ? 1u : 0u, role.ptr);
       GLZ_TRY(hipGetLastError());
     }
   }
-  hipLaunchKernelGGL(k_leaf_flags, grdw, blk, 0, st, nw, role, flags);
+  hipLaunchKernelGGL(k_leaf_flags, grdw, blk, 0, st, nw, role.ptr, flags.ptr);
   GLZ_TRY(hipGetLastError());
-  GLZ_TRY(scan_exclusive(st, (int)nw, flags, pos, scan_tmp));
-  hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, st, (int)nw, flags, pos, scan_total);
+  GLZ_TRY(scan_exclusive(st, (int)nw, flags.ptr, pos.ptr, scan_tmp.ptr));
+  hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, st, (int)nw, flags.ptr, pos.ptr, scan_total.ptr);
   GLZ_TRY(hipGetLastError());
   unsigned long long n_leaves = 0;
-  GLZ_TRY(hipMemcpyAsync(&n_leaves, scan_total, sizeof(n_leaves), hipMemcpyDeviceToHost, st));
+  GLZ_TRY(hipMemcpyAsync(&n_leaves, scan_total.ptr, sizeof(n_leaves), hipMemcpyDeviceToHost, st));
   GLZ_TRY(hipStreamSynchronize(st));
   const uint32_t n = (uint32_t)n_leaves;
-  if (n == 0 || n > nw) { cleanup(); return hipErrorUnknown; }
-  out.n_leaves = n;
-  hipLaunchKernelGGL(k_leaf_boxes, grdw, blk, 0, st, nw, role, pos, lo, hi, leaf_first, leaf_lo, leaf_hi);
+  if (n == 0 || n > nw) return hipErrorUnknown;
+  hipLaunchKernelGGL(k_leaf_boxes, grdw, blk, 0, st, nw, role.ptr, pos.ptr, lo.ptr, hi.ptr, leaf_first.ptr, leaf_lo.ptr, leaf_hi.ptr);
   GLZ_TRY(hipGetLastError());
   const uint32_t np = std::max<uint32_t>(next_pow2(n), kSortTile);
   const dim3 grd((n + 255) / 256);
-  hipLaunchKernelGGL(k_morton, dim3((np + 255) / 256), blk, 0, st, leaf_lo, leaf_hi, scalars, n, np, keys, vals);
+  hipLaunchKernelGGL(k_morton, dim3((np + 255) / 256), blk, 0, st, leaf_lo.ptr, leaf_hi.ptr, scalars.ptr, n, np, keys.ptr, vals.ptr);
   GLZ_TRY(hipGetLastError());
   // bitonic network: stages k = 2..np; strides j = k/2..1
-  hipLaunchKernelGGL(k_bitonic_lds, dim3(np / kSortTile), dim3(1024), 0, st, keys, vals, np, 2u, kSortTile, 0u);
+  hipLaunchKernelGGL(k_bitonic_lds, dim3(np / kSortTile), dim3(1024), 0, st, keys.ptr, vals.ptr, np, 2u, kSortTile, 0u);
   GLZ_TRY(hipGetLastError());
   for (uint32_t k = kSortTile * 2; k <= np; k <<= 1) {
     for (uint32_t j = k >> 1; j >= kSortTile; j >>= 1) {
-      hipLaunchKernelGGL(k_bitonic_global, dim3((np / 2 + 255) / 256), blk, 0, st, keys, vals, np, k, j);
+      hipLaunchKernelGGL(k_bitonic_global, dim3((np / 2 + 255) / 256), blk, 0, st, keys.ptr, vals.ptr, np, k, j);
       GLZ_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_bitonic_lds, dim3(np / kSortTile), dim3(1024), 0, st, keys, vals, np, k, k, kSortTile / 2);
+    hipLaunchKernelGGL(k_bitonic_lds, dim3(np / kSortTile), dim3(1024), 0, st, keys.ptr, vals.ptr, np, k, k, kSortTile / 2);
     GLZ_TRY(hipGetLastError());
   }
   // first slot of every leaf in bvh_tris (leaf order, one or two triangles each)
-  hipLaunchKernelGGL(k_leaf_sizes, grd, blk, 0, st, n, vals, leaf_first, role, flags);
+  hipLaunchKernelGGL(k_leaf_sizes, grd, blk, 0, st, n, vals.ptr, leaf_first.ptr, role.ptr, flags.ptr);
   GLZ_TRY(hipGetLastError());
-  GLZ_TRY(scan_exclusive(st, (int)n, flags, slot, scan_tmp));
-  out.quads = nullptr;
-  if (in.emit_quads) {
-    BvhQuad* q = nullptr;
-    GLZ_TRY(hipMalloc(&q, sizeof(BvhQuad) * (size_t)n));
-    out.quads = q;   // the caller's from here on, also when a later step fails
-  }
-  hipLaunchKernelGGL(k_gather_leaves, grd, blk, 0, st, vals, n, leaf_first, role, slot, tris_unsorted, leaf_lo, leaf_hi, out.tris, node_lo, node_hi, out.quads);
+  GLZ_TRY(scan_exclusive(st, (int)n, flags.ptr, slot.ptr, scan_tmp.ptr));
+  if (in.emit_quads) GLZ_TRY(out.quads.alloc(n));
+  hipLaunchKernelGGL(k_gather_leaves, grd, blk, 0, st, vals.ptr, n, leaf_first.ptr, role.ptr, slot.ptr, tris_unsorted.ptr, leaf_lo.ptr, leaf_hi.ptr, out.tris, node_lo.ptr, node_hi.ptr, out.quads.ptr);
   GLZ_TRY(hipGetLastError());
   if (n >= 2) {
     if (builder == kBvhBuilderLbvh) {
-      hipLaunchKernelGGL(k_hierarchy, grd, blk, 0, st, keys, (int)n, children, parent);
+      hipLaunchKernelGGL(k_hierarchy, grd, blk, 0, st, keys.ptr, (int)n, children.ptr, parent.ptr);
       GLZ_TRY(hipGetLastError());
     } else if (builder == kBvhBuilderSah) {
       // binned SAH, one launch per level (k_sah_level); the leaf boxes are node_lo / node_hi slots (n-1)+j
       const size_t qcap = (size_t)n / 2 + 2;
-      GLZ_TRY(hipMalloc(&sah_idx_a, sizeof(uint32_t) * n));
-      GLZ_TRY(hipMalloc(&sah_idx_b, sizeof(uint32_t) * n));
-      GLZ_TRY(hipMalloc(&sah_queue_a, sizeof(SahTask) * qcap));
-      GLZ_TRY(hipMalloc(&sah_queue_b, sizeof(SahTask) * qcap));
-      GLZ_TRY(hipMalloc(&sah_counts, sizeof(uint32_t) * 2));
-      GLZ_TRY(hipMalloc(&sah_total_chunks, sizeof(uint32_t)));
-      GLZ_TRY(hipMalloc(&sah_wide, sizeof(SahWideNode) * ((size_t)n / kSahWideMean + 2)));
-      GLZ_TRY(hipMalloc(&sah_chunk_left, sizeof(uint32_t) * ((size_t)n / kSahWideMean + (size_t)n / kSahChunk + 4)));
-      hipLaunchKernelGGL(k_sah_init, grd, blk, 0, st, n, sah_idx_a, sah_queue_a, sah_counts, parent);
+      GLZ_TRY(sah_idx_a.alloc(n));
+      GLZ_TRY(sah_idx_b.alloc(n));
+      GLZ_TRY(sah_queue_a.alloc(qcap));
+      GLZ_TRY(sah_queue_b.alloc(qcap));
+      GLZ_TRY(sah_counts.alloc(2));
+      GLZ_TRY(sah_total_chunks.alloc(1));
+      GLZ_TRY(sah_wide.alloc((size_t)n / kSahWideMean + 2));
+      GLZ_TRY(sah_chunk_left.alloc((size_t)n / kSahWideMean + (size_t)n / kSahChunk + 4));
+      hipLaunchKernelGGL(k_sah_init, grd, blk, 0, st, n, sah_idx_a.ptr, sah_queue_a.ptr, sah_counts.ptr, parent.ptr);
       GLZ_TRY(hipGetLastError());
       uint32_t active = 1;
-      uint32_t *idx_in = sah_idx_a, *idx_out = sah_idx_b;
-      SahTask *q_in = sah_queue_a, *q_out = sah_queue_b;
+      uint32_t *idx_in = sah_idx_a.ptr, *idx_out = sah_idx_b.ptr;
+      SahTask *q_in = sah_queue_a.ptr, *q_out = sah_queue_b.ptr;
       for (int level = 0, in = 0; active > 0; ++level, in ^= 1) {
-        if (level > kSahMaxSplitLevels + 64) { cleanup(); return hipErrorUnknown; }   // cannot happen: halving ends after 32 levels
+        if (level > kSahMaxSplitLevels + 64) return hipErrorUnknown;   // cannot happen: halving ends after 32 levels
         // by the mean range of the level: several blocks per node while the ranges are long, then one block per node --
         // many threads for a long range (it is one block's loop), one wave for the wide bottom levels (its barriers cost nothing)
         // A tree this deep means input that defeats the binning level after level (a geometric progression of scales); the
@@ -1511,29 +1497,29 @@ hipError_t build_lbvh(hipStream_t st, const LbvhInputs& in, LbvhOutputs& out) {
         if (mean >= kSahWideMean && !force_halve) {
           const uint32_t max_chunks = active + n / kSahChunk + 1;
           const dim3 gc(max_chunks), gn((active + 63) / 64);
-          hipLaunchKernelGGL(k_wide_plan, dim3(1), dim3(1024), 0, st, q_in, sah_counts + in, sah_wide, sah_total_chunks);
-          hipLaunchKernelGGL(k_wide_bounds, gc, dim3(kSahWideBlock), 0, st, q_in, sah_counts + in, sah_total_chunks, sah_wide, idx_in, node_lo + (n - 1),
-                             node_hi + (n - 1));
-          hipLaunchKernelGGL(k_wide_bin, gc, dim3(kSahWideBlock), 0, st, q_in, sah_counts + in, sah_total_chunks, sah_wide, idx_in, node_lo + (n - 1),
-                             node_hi + (n - 1));
-          hipLaunchKernelGGL(k_wide_pick, gn, dim3(64), 0, st, q_in, sah_counts + in, sah_wide);
-          hipLaunchKernelGGL(k_wide_count, gc, dim3(kSahWideBlock), 0, st, q_in, sah_counts + in, sah_total_chunks, sah_wide, idx_in, node_lo + (n - 1),
-                             node_hi + (n - 1), sah_chunk_left);
-          hipLaunchKernelGGL(k_wide_scatter, gc, dim3(kSahWideBlock), 0, st, q_in, sah_counts + in, sah_total_chunks, sah_wide, sah_chunk_left, idx_in, idx_out,
-                             node_lo + (n - 1), node_hi + (n - 1));
-          hipLaunchKernelGGL(k_wide_children, gn, dim3(64), 0, st, q_in, sah_counts + in, sah_wide, idx_out, (int)n, children, parent, q_out,
-                             sah_counts + (in ^ 1));
+          hipLaunchKernelGGL(k_wide_plan, dim3(1), dim3(1024), 0, st, q_in, sah_counts.ptr + in, sah_wide.ptr, sah_total_chunks.ptr);
+          hipLaunchKernelGGL(k_wide_bounds, gc, dim3(kSahWideBlock), 0, st, q_in, sah_counts.ptr + in, sah_total_chunks.ptr, sah_wide.ptr, idx_in, node_lo.ptr + (n - 1),
+                             node_hi.ptr + (n - 1));
+          hipLaunchKernelGGL(k_wide_bin, gc, dim3(kSahWideBlock), 0, st, q_in, sah_counts.ptr + in, sah_total_chunks.ptr, sah_wide.ptr, idx_in, node_lo.ptr + (n - 1),
+                             node_hi.ptr + (n - 1));
+          hipLaunchKernelGGL(k_wide_pick, gn, dim3(64), 0, st, q_in, sah_counts.ptr + in, sah_wide.ptr);
+          hipLaunchKernelGGL(k_wide_count, gc, dim3(kSahWideBlock), 0, st, q_in, sah_counts.ptr + in, sah_total_chunks.ptr, sah_wide.ptr, idx_in, node_lo.ptr + (n - 1),
+                             node_hi.ptr + (n - 1), sah_chunk_left.ptr);
+          hipLaunchKernelGGL(k_wide_scatter, gc, dim3(kSahWideBlock), 0, st, q_in, sah_counts.ptr + in, sah_total_chunks.ptr, sah_wide.ptr, sah_chunk_left.ptr, idx_in, idx_out,
+                             node_lo.ptr + (n - 1), node_hi.ptr + (n - 1));
+          hipLaunchKernelGGL(k_wide_children, gn, dim3(64), 0, st, q_in, sah_counts.ptr + in, sah_wide.ptr, idx_out, (int)n, children.ptr, parent.ptr, q_out,
+                             sah_counts.ptr + (in ^ 1));
         } else {
-#define GLZ_SAH_LAUNCH(B) hipLaunchKernelGGL(k_sah_level<B>, dim3(active), dim3(B), 0, st, q_in, sah_counts + in, idx_in, idx_out, q_out, \
-                                             sah_counts + (in ^ 1), (int)n, node_lo + (n - 1), node_hi + (n - 1), children, parent, force_halve)
+#define GLZ_SAH_LAUNCH(B) hipLaunchKernelGGL(k_sah_level<B>, dim3(active), dim3(B), 0, st, q_in, sah_counts.ptr + in, idx_in, idx_out, q_out, \
+                                             sah_counts.ptr + (in ^ 1), (int)n, node_lo.ptr + (n - 1), node_hi.ptr + (n - 1), children.ptr, parent.ptr, force_halve)
           if (mean >= 4096) GLZ_SAH_LAUNCH(1024);
           else if (mean >= 128) GLZ_SAH_LAUNCH(256);
           else GLZ_SAH_LAUNCH(64);
 #undef GLZ_SAH_LAUNCH
         }
         GLZ_TRY(hipGetLastError());
-        GLZ_TRY(hipMemcpyAsync(&active, sah_counts + (in ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        GLZ_TRY(hipMemsetAsync(sah_counts + in, 0, sizeof(uint32_t), st));   // this level's input counter is the output counter of the level after next
+        GLZ_TRY(hipMemcpyAsync(&active, sah_counts.ptr + (in ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        GLZ_TRY(hipMemsetAsync(sah_counts.ptr + in, 0, sizeof(uint32_t), st));   // this level's input counter is the output counter of the level after next
         GLZ_TRY(hipStreamSynchronize(st));
         std::swap(idx_in, idx_out);
         std::swap(q_in, q_out);
@@ -1544,38 +1530,38 @@ hipError_t build_lbvh(hipStream_t st, const LbvhInputs& in, LbvhOutputs& out) {
       std::vector<float4> h_lo(n), h_hi(n);
       std::vector<int2> h_children(n);
       std::vector<int> h_parent(2 * (size_t)n);
-      GLZ_TRY(hipMemcpyAsync(h_lo.data(), node_lo + (n - 1), sizeof(float4) * n, hipMemcpyDeviceToHost, st));
-      GLZ_TRY(hipMemcpyAsync(h_hi.data(), node_hi + (n - 1), sizeof(float4) * n, hipMemcpyDeviceToHost, st));
+      GLZ_TRY(hipMemcpyAsync(h_lo.data(), node_lo.ptr + (n - 1), sizeof(float4) * n, hipMemcpyDeviceToHost, st));
+      GLZ_TRY(hipMemcpyAsync(h_hi.data(), node_hi.ptr + (n - 1), sizeof(float4) * n, hipMemcpyDeviceToHost, st));
       GLZ_TRY(hipStreamSynchronize(st));
       build_sah_host(n, h_lo.data(), h_hi.data(), h_children.data(), h_parent.data());
-      GLZ_TRY(hipMemcpyAsync(children, h_children.data(), sizeof(int2) * (n - 1), hipMemcpyHostToDevice, st));
-      GLZ_TRY(hipMemcpyAsync(parent, h_parent.data(), sizeof(int) * (2 * (size_t)n - 1), hipMemcpyHostToDevice, st));
+      GLZ_TRY(hipMemcpyAsync(children.ptr, h_children.data(), sizeof(int2) * (n - 1), hipMemcpyHostToDevice, st));
+      GLZ_TRY(hipMemcpyAsync(parent.ptr, h_parent.data(), sizeof(int) * (2 * (size_t)n - 1), hipMemcpyHostToDevice, st));
       GLZ_TRY(hipStreamSynchronize(st));
     } else {
-      GLZ_TRY(hipMalloc(&refs_a, sizeof(int) * n));
-      GLZ_TRY(hipMalloc(&refs_b, sizeof(int) * n));
-      GLZ_TRY(hipMalloc(&nearest, sizeof(int) * n));
-      hipLaunchKernelGGL(k_ploc_init, grd, blk, 0, st, (int)n, refs_a, parent);
+      GLZ_TRY(refs_a.alloc(n));
+      GLZ_TRY(refs_b.alloc(n));
+      GLZ_TRY(nearest.alloc(n));
+      hipLaunchKernelGGL(k_ploc_init, grd, blk, 0, st, (int)n, refs_a.ptr, parent.ptr);
       GLZ_TRY(hipGetLastError());
       int m = (int)n, next_free = (int)n - 2;
       out.rounds = 0;
       while (m > 1) {
         const dim3 gm((m + 255) / 256);
-        hipLaunchKernelGGL(k_ploc_nearest, gm, blk, 0, st, m, (int)n, refs_a, node_lo, node_hi, nearest);
+        hipLaunchKernelGGL(k_ploc_nearest, gm, blk, 0, st, m, (int)n, refs_a.ptr, node_lo.ptr, node_hi.ptr, nearest.ptr);
         GLZ_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_ploc_flags, gm, blk, 0, st, m, nearest, flags);
+        hipLaunchKernelGGL(k_ploc_flags, gm, blk, 0, st, m, nearest.ptr, flags.ptr);
         GLZ_TRY(hipGetLastError());
-        GLZ_TRY(scan_exclusive(st, m, flags, pos, scan_tmp));
-        hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, st, m, flags, pos, scan_total);
+        GLZ_TRY(scan_exclusive(st, m, flags.ptr, pos.ptr, scan_tmp.ptr));
+        hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, st, m, flags.ptr, pos.ptr, scan_total.ptr);
         GLZ_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_ploc_merge, gm, blk, 0, st, m, (int)n, next_free, refs_a, nearest, flags, pos, refs_b, children, parent, node_lo,
-                           node_hi);
+        hipLaunchKernelGGL(k_ploc_merge, gm, blk, 0, st, m, (int)n, next_free, refs_a.ptr, nearest.ptr, flags.ptr, pos.ptr, refs_b.ptr, children.ptr, parent.ptr, node_lo.ptr,
+                           node_hi.ptr);
         GLZ_TRY(hipGetLastError());
         unsigned long long total = 0;
-        GLZ_TRY(hipMemcpyAsync(&total, scan_total, sizeof(total), hipMemcpyDeviceToHost, st));
+        GLZ_TRY(hipMemcpyAsync(&total, scan_total.ptr, sizeof(total), hipMemcpyDeviceToHost, st));
         GLZ_TRY(hipStreamSynchronize(st));
         const int survivors = (int)(total & 0xFFFFFFFFull), merges = (int)(total >> 32);
-        if (merges <= 0 || survivors != m - merges) { cleanup(); return hipErrorUnknown; }   // cannot happen: the closest pair is always mutual
+        if (merges <= 0 || survivors != m - merges) return hipErrorUnknown;   // cannot happen: the closest pair is always mutual
         next_free -= merges;
         m = survivors;
         std::swap(refs_a, refs_b);
@@ -1583,93 +1569,81 @@ hipError_t build_lbvh(hipStream_t st, const LbvhInputs& in, LbvhOutputs& out) {
       }
     }
     // bottom-up, one launch per level: boxes (LBVH; PLOC made them while merging) and subtree sizes
-    hipLaunchKernelGGL(k_node_depth, dim3((2 * n + 255) / 256), blk, 0, st, (int)n, parent, node_depth, scalars + 7, scalars + 6);
+    hipLaunchKernelGGL(k_node_depth, dim3((2 * n + 255) / 256), blk, 0, st, (int)n, parent.ptr, node_depth.ptr, scalars.ptr + 7, scalars.ptr + 6);
     GLZ_TRY(hipGetLastError());
     int inner_depth = 0;
-    GLZ_TRY(hipMemcpyAsync(&inner_depth, scalars + 7, sizeof(int), hipMemcpyDeviceToHost, st));
+    GLZ_TRY(hipMemcpyAsync(&inner_depth, scalars.ptr + 7, sizeof(int), hipMemcpyDeviceToHost, st));
     GLZ_TRY(hipStreamSynchronize(st));
     for (int level = inner_depth; level >= 0; --level) {
       if (builder != kBvhBuilderPloc)
-        hipLaunchKernelGGL(k_level_up<true>, grd, blk, 0, st, (int)n, level, node_depth, children, node_lo, node_hi, counts);
+        hipLaunchKernelGGL(k_level_up<true>, grd, blk, 0, st, (int)n, level, node_depth.ptr, children.ptr, node_lo.ptr, node_hi.ptr, counts.ptr);
       else
-        hipLaunchKernelGGL(k_level_up<false>, grd, blk, 0, st, (int)n, level, node_depth, children, node_lo, node_hi, counts);
+        hipLaunchKernelGGL(k_level_up<false>, grd, blk, 0, st, (int)n, level, node_depth.ptr, children.ptr, node_lo.ptr, node_hi.ptr, counts.ptr);
       GLZ_TRY(hipGetLastError());
     }
     // depth-first layout of the finished hierarchy
-    hipLaunchKernelGGL(k_dfs_ids, grd, blk, 0, st, (int)n, children, parent, counts, new_id);
+    hipLaunchKernelGGL(k_dfs_ids, grd, blk, 0, st, (int)n, children.ptr, parent.ptr, counts.ptr, new_id.ptr);
     GLZ_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_grid_params, dim3(1), dim3(64), 0, st, node_lo, node_hi, grid);
+    hipLaunchKernelGGL(k_grid_params, dim3(1), dim3(64), 0, st, node_lo.ptr, node_hi.ptr, grid.ptr);
     GLZ_TRY(hipGetLastError());
-    // 4-wide collapse: find the heads of the BVH4 nodes top down, number them in depth-first order, then emit them
-    int* head = counts;   // k_dfs_ids was the last reader of the subtree sizes
-    GLZ_TRY(hipMemsetAsync(head, 0, sizeof(int) * n, st));
-    GLZ_TRY(hipMemsetAsync(scalars + 7, 0, sizeof(int), st));
-    for (int level = 0; level <= inner_depth; ++level) {
-      hipLaunchKernelGGL(k_mark_heads<4>, grd, blk, 0, st, (int)n, level, node_depth, children, node_lo, node_hi, head, scalars + 7);
+    // collapse, 4 wide and 8 wide alike: find the heads of the W-wide nodes top down and number them in depth-first order (flags -> pos,
+    // which the emit kernel of that width reads); gives how many W-wide nodes there are and how deep they nest
+    int* head = counts.ptr;   // k_dfs_ids was the last reader of the subtree sizes
+    auto count_heads = [&](auto width, uint32_t& n_heads, uint32_t& depth) -> hipError_t {
+      constexpr int W = decltype(width)::value;
+      GLZ_TRY(hipMemsetAsync(head, 0, sizeof(int) * n, st));
+      GLZ_TRY(hipMemsetAsync(scalars.ptr + 7, 0, sizeof(int), st));
+      for (int level = 0; level <= inner_depth; ++level) {
+        hipLaunchKernelGGL(k_mark_heads<W>, grd, blk, 0, st, (int)n, level, node_depth.ptr, children.ptr, node_lo.ptr, node_hi.ptr, head, scalars.ptr + 7);
+        GLZ_TRY(hipGetLastError());
+      }
+      hipLaunchKernelGGL(k_head_flags, grd, blk, 0, st, (int)n, head, new_id.ptr, flags.ptr);
       GLZ_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_head_flags, grd, blk, 0, st, (int)n, head, new_id, flags);
-    GLZ_TRY(hipGetLastError());
-    GLZ_TRY(scan_exclusive(st, (int)n - 1, flags, pos, scan_tmp));
-    hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, st, (int)n - 1, flags, pos, scan_total);
-    GLZ_TRY(hipGetLastError());
-    unsigned long long n4 = 0;
-    int depth4_keep = 0;
-    GLZ_TRY(hipMemcpyAsync(&n4, scan_total, sizeof(n4), hipMemcpyDeviceToHost, st));
-    GLZ_TRY(hipMemcpyAsync(&depth4_keep, scalars + 7, sizeof(int), hipMemcpyDeviceToHost, st));
-    GLZ_TRY(hipStreamSynchronize(st));
-    out.n_nodes = (uint32_t)n4;
-    GLZ_TRY(hipMalloc(&out.nodes, sizeof(BvhNode4) * (size_t)n4));
-    hipLaunchKernelGGL(k_emit_nodes4, grd, blk, 0, st, (int)n, children, node_lo, node_hi, grid, new_id, flags, pos, slot, in.emit_quads ? 1u : 0u, out.nodes, sah);
+      GLZ_TRY(scan_exclusive(st, (int)n - 1, flags.ptr, pos.ptr, scan_tmp.ptr));
+      hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, st, (int)n - 1, flags.ptr, pos.ptr, scan_total.ptr);
+      GLZ_TRY(hipGetLastError());
+      unsigned long long total = 0;
+      int deepest = 0;
+      GLZ_TRY(hipMemcpyAsync(&total, scan_total.ptr, sizeof(total), hipMemcpyDeviceToHost, st));
+      GLZ_TRY(hipMemcpyAsync(&deepest, scalars.ptr + 7, sizeof(int), hipMemcpyDeviceToHost, st));
+      GLZ_TRY(hipStreamSynchronize(st));
+      n_heads = (uint32_t)total;
+      depth = (uint32_t)deepest;
+      return hipSuccess;
+    };
+    // 4-wide collapse: heads, depth-first numbers, then emit the nodes
+    uint32_t n4 = 0, depth4_keep = 0;
+    GLZ_TRY(count_heads(std::integral_constant<int, 4>{}, n4, depth4_keep));
+    GLZ_TRY(out.nodes.alloc(n4));
+    hipLaunchKernelGGL(k_emit_nodes4, grd, blk, 0, st, (int)n, children.ptr, node_lo.ptr, node_hi.ptr, grid.ptr, new_id.ptr, flags.ptr, pos.ptr, slot.ptr, in.emit_quads ? 1u : 0u, out.nodes.ptr, sah.ptr);
     GLZ_TRY(hipGetLastError());
     if (in.emit_wide8 && in.emit_quads) {
       // the 8-wide collapse of the same binary hierarchy: heads, depth-first numbers, nodes (head / flags / pos are free again)
-      GLZ_TRY(hipMemsetAsync(head, 0, sizeof(int) * n, st));
-      GLZ_TRY(hipMemsetAsync(scalars + 7, 0, sizeof(int), st));
-      for (int level = 0; level <= inner_depth; ++level) {
-        hipLaunchKernelGGL(k_mark_heads<8>, grd, blk, 0, st, (int)n, level, node_depth, children, node_lo, node_hi, head, scalars + 7);
-        GLZ_TRY(hipGetLastError());
-      }
-      hipLaunchKernelGGL(k_head_flags, grd, blk, 0, st, (int)n, head, new_id, flags);
+      uint32_t n8 = 0;
+      GLZ_TRY(count_heads(std::integral_constant<int, 8>{}, n8, out.depth8));
+      GLZ_TRY(out.nodes8.alloc(n8));
+      hipLaunchKernelGGL(k_emit_nodes8, grd, blk, 0, st, (int)n, children.ptr, node_lo.ptr, node_hi.ptr, grid.ptr, new_id.ptr, flags.ptr, pos.ptr, out.nodes8.ptr);
       GLZ_TRY(hipGetLastError());
-      GLZ_TRY(scan_exclusive(st, (int)n - 1, flags, pos, scan_tmp));
-      hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, st, (int)n - 1, flags, pos, scan_total);
-      GLZ_TRY(hipGetLastError());
-      unsigned long long n8 = 0;
-      int depth8 = 0;
-      GLZ_TRY(hipMemcpyAsync(&n8, scan_total, sizeof(n8), hipMemcpyDeviceToHost, st));
-      GLZ_TRY(hipMemcpyAsync(&depth8, scalars + 7, sizeof(int), hipMemcpyDeviceToHost, st));
-      GLZ_TRY(hipStreamSynchronize(st));
-      out.n_nodes8 = (uint32_t)n8;
-      out.depth8 = (uint32_t)depth8;
-      GLZ_TRY(hipMalloc(&out.nodes8, sizeof(BvhNode8) * (size_t)n8));
-      hipLaunchKernelGGL(k_emit_nodes8, grd, blk, 0, st, (int)n, children, node_lo, node_hi, grid, new_id, flags, pos, out.nodes8);
-      GLZ_TRY(hipGetLastError());
-      GLZ_TRY(hipMemcpyAsync(scalars + 7, &depth4_keep, sizeof(int), hipMemcpyHostToDevice, st));   // host_scalars[7] below is the 4-wide depth
+      GLZ_TRY(hipMemcpyAsync(scalars.ptr + 7, &depth4_keep, sizeof(int), hipMemcpyHostToDevice, st));   // host_scalars[7] below is the 4-wide depth
     }
   }
   int host_scalars[8];
   float host_sah = 0.0f;
   float4 root_lo, root_hi;
-  GLZ_TRY(hipMemcpyAsync(host_scalars, scalars, sizeof(host_scalars), hipMemcpyDeviceToHost, st));
-  GLZ_TRY(hipMemcpyAsync(&host_sah, sah, sizeof(float), hipMemcpyDeviceToHost, st));
-  GLZ_TRY(hipMemcpyAsync(&root_lo, node_lo, sizeof(float4), hipMemcpyDeviceToHost, st));
-  GLZ_TRY(hipMemcpyAsync(&root_hi, node_hi, sizeof(float4), hipMemcpyDeviceToHost, st));
+  GLZ_TRY(hipMemcpyAsync(host_scalars, scalars.ptr, sizeof(host_scalars), hipMemcpyDeviceToHost, st));
+  GLZ_TRY(hipMemcpyAsync(&host_sah, sah.ptr, sizeof(float), hipMemcpyDeviceToHost, st));
+  GLZ_TRY(hipMemcpyAsync(&root_lo, node_lo.ptr, sizeof(float4), hipMemcpyDeviceToHost, st));
+  GLZ_TRY(hipMemcpyAsync(&root_hi, node_hi.ptr, sizeof(float4), hipMemcpyDeviceToHost, st));
   GLZ_TRY(hipStreamSynchronize(st));
   if (n == 1) {
     // single triangle: one node whose first child is leaf 0 with a box spanning the whole grid
-    hipLaunchKernelGGL(k_grid_params, dim3(1), dim3(64), 0, st, node_lo, node_hi, grid);   // slot (n-1)+0 = 0 is the leaf box
+    hipLaunchKernelGGL(k_grid_params, dim3(1), dim3(64), 0, st, node_lo.ptr, node_hi.ptr, grid.ptr);   // slot (n-1)+0 = 0 is the leaf box
     GLZ_TRY(hipGetLastError());
-    BvhNode4 nd{};
-    for (int k = 0; k < 4; ++k) {
-      nd.w[3 * k] = nd.w[3 * k + 1] = nd.w[3 * k + 2] = kBvhGridMax;
-      nd.w[12 + k] = (uint32_t)kBvhEmptyChild;
-    }
+    BvhNode4 nd = childless_node4();
     nd.w[0] = nd.w[1] = nd.w[2] = 0u | (kBvhGridMax << 16);   // lo 0, hi the grid's top on every axis
     nd.w[12] = ~0u;   // leaf 0
-    GLZ_TRY(hipMalloc(&out.nodes, sizeof(BvhNode4)));
-    out.n_nodes = 1;
-    GLZ_TRY(hipMemcpyAsync(out.nodes, &nd, sizeof(nd), hipMemcpyHostToDevice, st));
+    GLZ_TRY(out.nodes.alloc(1));
+    GLZ_TRY(hipMemcpyAsync(out.nodes.ptr, &nd, sizeof(nd), hipMemcpyHostToDevice, st));
     GLZ_TRY(hipStreamSynchronize(st));
     out.depth = 1;
   } else {
@@ -1678,10 +1652,9 @@ hipError_t build_lbvh(hipStream_t st, const LbvhInputs& in, LbvhOutputs& out) {
     const float ra = 2.0f * (dx * dy + dy * dz + dz * dx);
     out.sah = ra > 0.0f ? host_sah / ra : 0.0f;
   }
-  GLZ_TRY(hipMemcpy(&out.grid, grid, sizeof(BvhGrid), hipMemcpyDeviceToHost));
+  GLZ_TRY(hipMemcpy(&out.grid, grid.ptr, sizeof(BvhGrid), hipMemcpyDeviceToHost));
   out.bounds_lo[0] = root_lo.x; out.bounds_lo[1] = root_lo.y; out.bounds_lo[2] = root_lo.z;
   out.bounds_hi[0] = root_hi.x; out.bounds_hi[1] = root_hi.y; out.bounds_hi[2] = root_hi.z;
-  cleanup();
 #undef GLZ_TRY
   return hipSuccess;
 }

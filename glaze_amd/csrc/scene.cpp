@@ -98,13 +98,19 @@ Instance* Instance::create(int hip_device, Error& err) {
   return inst;
 }
 
-// load_raytrace_instances_to_gpu (scene.rs:1784-1818): meshes indexed by id (last one wins), dangling instances dropped
+// meshes are indexed by id, the last one with an id wins; null: no such mesh
+static const glz_mesh* mesh_by_id(const SceneData& d, uint32_t id) {
+  const glz_mesh* found = nullptr;
+  for (const glz_mesh& m : d.meshes)
+    if (m.id == id) found = &m;
+  return found;
+}
+
+// load_raytrace_instances_to_gpu (scene.rs:1784-1818): dangling instances dropped
 std::vector<RTInstance> rt_instances(const SceneData& d) {
   std::vector<RTInstance> out;
   for (const glz_mesh_instance& in : d.instances) {
-    const glz_mesh* found = nullptr;
-    for (const glz_mesh& m : d.meshes)
-      if (m.id == in.mesh_id) found = &m;
+    const glz_mesh* found = mesh_by_id(d, in.mesh_id);
     if (!found) continue;
     out.push_back(RTInstance{found->index_offset, found->index_count, found->material, in.transform_id});
   }
@@ -145,6 +151,36 @@ static uint32_t sbt_callable_index(uint8_t mtype) {   // materials/material.rs:2
   }
 }
 
+// The distinct index ranges (offset, count) the instances draw, in first-use order (it fixes tri_base, node_base and the order in which
+// the exact-box budget is spent), and which of them each instance uses.
+static std::vector<std::pair<uint32_t, uint32_t>> unique_meshes(const std::vector<RTInstance>& instances, std::vector<uint32_t>& mesh_of) {
+  std::vector<std::pair<uint32_t, uint32_t>> ranges;
+  mesh_of.resize(instances.size());
+  for (size_t i = 0; i < instances.size(); ++i) {
+    const std::pair<uint32_t, uint32_t> key(instances[i].index_offset, instances[i].index_count);
+    const size_t m = std::find(ranges.begin(), ranges.end(), key) - ranges.begin();
+    if (m == ranges.size()) ranges.push_back(key);
+    mesh_of[i] = (uint32_t)m;
+  }
+  return ranges;
+}
+
+// References inside the geometry, so that nothing indexes out of bounds: index ranges, vertex indices, transform ids
+static bool valid_geometry(const SceneData& d, size_t n_transforms, Error& err) {
+  auto fail = [&](const char* what) {
+    err.code = GLZ_E_INVALID_DATA;
+    err.msg = what;
+    return false;
+  };
+  for (const glz_mesh& m : d.meshes)
+    if ((uint64_t)m.index_offset + m.index_count > d.indices.size()) return fail("mesh index range outside the index buffer");
+  for (uint32_t i : d.indices)
+    if (i >= d.vertices.size()) return fail("vertex index out of range");
+  for (const glz_mesh_instance& in : d.instances)
+    if (in.transform_id >= n_transforms) return fail("instance references a missing transform");
+  return true;
+}
+
 Scene* Scene::create(Instance* inst, SceneData&& data, Error& err) {
   std::unique_ptr<Scene> s(new Scene());
   s->instance = inst;
@@ -157,8 +193,9 @@ Scene* Scene::create(Instance* inst, SceneData&& data, Error& err) {
   for (auto& t : d.textures) t.info.pixels = t.level0.data();
   if (!hip_ok(hipSetDevice(inst->device), "hipSetDevice", err)) return nullptr;
   // validate references so that no kernel can index out of bounds
+  if (!valid_geometry(d, d.transforms.size(), err)) return nullptr;
   for (const glz_mesh& m : d.meshes) {
-    if ((uint64_t)m.index_offset + m.index_count > d.indices.size() || m.index_count % 3 != 0) {
+    if (m.index_count % 3 != 0) {
       err.code = GLZ_E_INVALID_DATA;
       err.msg = "mesh index range outside the index buffer";
       return nullptr;
@@ -169,18 +206,6 @@ Scene* Scene::create(Instance* inst, SceneData&& data, Error& err) {
       return nullptr;
     }
   }
-  for (uint32_t i : d.indices)
-    if (i >= d.vertices.size()) {
-      err.code = GLZ_E_INVALID_DATA;
-      err.msg = "vertex index out of range";
-      return nullptr;
-    }
-  for (const glz_mesh_instance& in : d.instances)
-    if (in.transform_id >= d.transforms.size()) {
-      err.code = GLZ_E_INVALID_DATA;
-      err.msg = "instance references a missing transform";
-      return nullptr;
-    }
   auto tex_ok = [&](uint32_t id) { return id < d.textures.size(); };
   for (const glz_material& m : d.materials)
     if (!tex_ok(m.diffuse) || !tex_ok(m.roughness) || !tex_ok(m.metalness) || !tex_ok(m.normal) || !tex_ok(m.opacity)) {
@@ -191,9 +216,7 @@ Scene* Scene::create(Instance* inst, SceneData&& data, Error& err) {
   if (!s->upload_geometry(err)) return nullptr;
   if (!s->build_materials(err)) return nullptr;
   if (!s->build_lights_and_sky(err)) return nullptr;
-  s->build_opts_ = BuildOptions{inst->bvh_builder, inst->bvh_pair_area_ratio, inst->as_levels};
-  if (!s->build_bvh(err)) return nullptr;
-  s->build_opts_.as_levels = (int)s->info.as_levels;   // the shape built: update_transforms keeps it
+  if (!s->build_bvh_as_instance_says(err)) return nullptr;
   if (!hip_ok(hipStreamSynchronize(inst->stream), "scene upload", err)) return nullptr;
   s->info.n_vertices = d.vertices.size();
   s->info.n_triangles = d.indices.size() / 3;
@@ -252,6 +275,30 @@ bool Scene::upload_geometry(Error& err) {
   return true;
 }
 
+// 128-byte tiles: 8 x 4 RGBA texels or 16 x 8 gray texels (device/shading.h fetch_texel); ragged edges are padded
+struct Tiling {
+  uint32_t tw, th, bpp, tiles_x, tiles_y;
+  Tiling(uint32_t format, uint32_t w, uint32_t h) {
+    const bool gray = format == GLZ_TEX_GRAY;
+    tw = gray ? 16u : 8u, th = gray ? 8u : 4u, bpp = gray ? 1u : 4u;
+    tiles_x = (w + tw - 1) / tw, tiles_y = (h + th - 1) / th;
+  }
+  size_t bytes() const { return (size_t)tiles_x * tiles_y * 128u; }
+};
+// one image, tiled, appended to `pool` (whose size stays a multiple of 128)
+static TexDesc append_tiled(std::vector<uint8_t>& pool, uint32_t format, uint32_t w, uint32_t h, const uint8_t* px) {
+  const Tiling t(format, w, h);
+  pool.resize((pool.size() + 127) & ~size_t(127));
+  const size_t base = pool.size();
+  pool.resize(base + t.bytes(), 0);
+  for (uint32_t y = 0; y < h; ++y)
+    for (uint32_t x = 0; x < w; ++x) {
+      const size_t dst = base + ((size_t)(y / t.th) * t.tiles_x + x / t.tw) * 128u + ((size_t)(y % t.th) * t.tw + x % t.tw) * t.bpp;
+      memcpy(&pool[dst], &px[((size_t)y * w + x) * t.bpp], t.bpp);
+    }
+  return TexDesc{(uint32_t)base, w, h, format | (t.tiles_x << 8)};
+}
+
 // Level 0 of every texture in one byte pool (16-byte aligned starts) + a descriptor per texture; what the reference
 // keeps as one VkImage per texture behind a descriptor array (scene.rs:1264-1350).
 bool Scene::upload_textures(Error& err) {
@@ -267,13 +314,8 @@ bool Scene::upload_textures(Error& err) {
       err.msg = "texture has inconsistent dimensions";
       return false;
     }
-    // 128-byte tiles: 8 x 4 RGBA texels or 16 x 8 gray texels (device/shading.h fetch_texel); ragged edges are padded
-    const bool gray = t.info.format == GLZ_TEX_GRAY;
-    const uint32_t tw = gray ? 16u : 8u, th = gray ? 8u : 4u, bpp = gray ? 1u : 4u;
-    const uint32_t tiles_x = (t.info.width + tw - 1) / tw, tiles_y = (t.info.height + th - 1) / th;
-    const size_t tiled_bytes = (size_t)tiles_x * tiles_y * 128u;
-    pool.resize((pool.size() + 127) & ~size_t(127));
-    if (pool.size() + tiled_bytes > 0xFFFFFFFFull || tiles_x >= (1u << 24)) {
+    const Tiling tiling(t.info.format, t.info.width, t.info.height);
+    if (pool.size() + tiling.bytes() > 0xFFFFFFFFull || tiling.tiles_x >= (1u << 24)) {
       err.code = GLZ_E_UNSUPPORTED;
       err.msg = "texture pool larger than 4 GiB";
       return false;
@@ -281,18 +323,11 @@ bool Scene::upload_textures(Error& err) {
     if (t.info.width == 1 && t.info.height == 1) {
       // the texel travels in the descriptor (device/shading.h kTexInline): materials' default maps cost no texel load
       uint32_t bits = 0;
-      memcpy(&bits, t.level0.data(), bpp);
+      memcpy(&bits, t.level0.data(), tiling.bpp);
       desc[i] = TexDesc{bits, 1u, 1u, t.info.format | 0x80u | (1u << 8)};
       continue;
     }
-    desc[i] = TexDesc{(uint32_t)pool.size(), t.info.width, t.info.height, t.info.format | (tiles_x << 8)};
-    const size_t base = pool.size();
-    pool.resize(base + tiled_bytes, 0);
-    for (uint32_t y = 0; y < t.info.height; ++y)
-      for (uint32_t x = 0; x < t.info.width; ++x) {
-        const size_t dst = base + ((size_t)(y / th) * tiles_x + x / tw) * 128u + ((size_t)(y % th) * tw + x % tw) * bpp;
-        memcpy(&pool[dst], &t.level0[((size_t)y * t.info.width + x) * bpp], bpp);
-      }
+    desc[i] = append_tiled(pool, t.info.format, t.info.width, t.info.height, t.level0.data());
   }
   if (!hip_ok(d_tex_desc_.upload(desc.data(), desc.size(), st), "upload texture descriptors", err)) return false;
   if (!hip_ok(d_tex_pool_.upload(pool.data(), pool.size(), st), "upload texture pool", err)) return false;
@@ -307,22 +342,6 @@ bool Scene::upload_textures(Error& err) {
   dev.tex_mip_pool = nullptr;
   h_mips_.clear();
   return true;
-}
-
-// 128-byte tiles: 8 x 4 RGBA texels or 16 x 8 gray texels (upload_textures above), appended to `pool`
-static TexDesc append_tiled(std::vector<uint8_t>& pool, uint32_t format, uint32_t w, uint32_t h, const uint8_t* px) {
-  const bool gray = format == GLZ_TEX_GRAY;
-  const uint32_t tw = gray ? 16u : 8u, th = gray ? 8u : 4u, bpp = gray ? 1u : 4u;
-  const uint32_t tiles_x = (w + tw - 1) / tw, tiles_y = (h + th - 1) / th;
-  pool.resize((pool.size() + 127) & ~size_t(127));
-  const size_t base = pool.size();
-  pool.resize(base + (size_t)tiles_x * tiles_y * 128u, 0);
-  for (uint32_t y = 0; y < h; ++y)
-    for (uint32_t x = 0; x < w; ++x) {
-      const size_t dst = base + ((size_t)(y / th) * tiles_x + x / tw) * 128u + ((size_t)(y % th) * tw + x % tw) * bpp;
-      memcpy(&pool[dst], &px[((size_t)y * w + x) * bpp], bpp);
-    }
-  return TexDesc{(uint32_t)base, w, h, format | (tiles_x << 8)};
 }
 
 bool Scene::ensure_mips(Error& err) {
@@ -499,9 +518,7 @@ bool Scene::build_lights_and_sky(Error& err) {
       const uint16_t material_id = (uint16_t)l.resource_id;
       std::vector<uint32_t> ids;
       for (size_t i = 0; i < data.instances.size(); ++i) {
-        const glz_mesh* found = nullptr;
-        for (const glz_mesh& m : data.meshes)
-          if (m.id == data.instances[i].mesh_id) found = &m;
+        const glz_mesh* found = mesh_by_id(data, data.instances[i].mesh_id);
         if (found && found->material == material_id) ids.push_back((uint32_t)(uint16_t)i);
       }
       if (ids.empty()) ids.push_back(0);
@@ -688,41 +705,21 @@ bool Scene::build_two_level(Error& err) {
   if (!timer.start(st, err)) return false;
   h_mesh_ranges.clear();
   // ---- unique meshes (index ranges) ----
-  struct MeshAs {
-    uint32_t index_offset, index_count, tri_base, node_base, n_nodes, depth;
-    BvhGrid grid;
-    float lo[3], hi[3];
-    BvhNode4* nodes;
-    BvhQuad* quads = nullptr;   // the mesh's leaf records (object space), as build_lbvh handed them out
-    uint32_t n_leaves = 0, quad_base = 0;
-  };
-  std::vector<MeshAs> meshes;
-  std::vector<uint32_t> mesh_of(h_instances.size());
-  for (size_t i = 0; i < h_instances.size(); ++i) {
-    const RTInstance& in = h_instances[i];
-    size_t m = 0;
-    while (m < meshes.size() && !(meshes[m].index_offset == in.index_offset && meshes[m].index_count == in.index_count)) ++m;
-    if (m == meshes.size()) meshes.push_back(MeshAs{in.index_offset, in.index_count, 0, 0, 0, 0, BvhGrid{}, {0, 0, 0}, {0, 0, 0}, nullptr});
-    mesh_of[i] = (uint32_t)m;
-  }
+  std::vector<uint32_t> mesh_of;
+  std::vector<MeshBuild> meshes;
   uint64_t total_tris = 0;
-  for (MeshAs& m : meshes) {
-    m.tri_base = (uint32_t)total_tris;
-    total_tris += m.index_count / 3u;
+  for (const std::pair<uint32_t, uint32_t>& range : unique_meshes(h_instances, mesh_of)) {
+    meshes.emplace_back();
+    meshes.back().mesh.index_offset = range.first;
+    meshes.back().mesh.index_count = range.second;
+    meshes.back().range.tri_base = (uint32_t)total_tris;
+    total_tris += range.second / 3u;
   }
   if (total_tris >= 0x3FFFFFFFull) {
     err.code = GLZ_E_UNSUPPORTED;
     err.msg = "more than 2^30 mesh triangles";
     return false;
   }
-  auto free_nodes = [&]() {
-    for (MeshAs& m : meshes) {
-      if (m.nodes) (void)hipFree(m.nodes);
-      if (m.quads) (void)hipFree(m.quads);
-      m.nodes = nullptr;
-      m.quads = nullptr;
-    }
-  };
   const uint32_t nt = (uint32_t)total_tris;
   d_nodes_.release();
   if (!hip_ok(d_tris_.alloc((size_t)nt + 1), "alloc BVH triangles", err)) return false;
@@ -743,125 +740,133 @@ bool Scene::build_two_level(Error& err) {
       return false;
     if (!hip_ok(hipStreamSynchronize(st), "upload", err)) return false;
   }
-  uint32_t total_nodes = 0, max_depth = 0;
-  for (MeshAs& m : meshes) {
-    const uint32_t n = m.index_count / 3u;
+  tl_mesh_depth_ = 0;
+  for (MeshBuild& m : meshes) {
+    const uint32_t n = m.mesh.index_count / 3u;
     if (n == 0) continue;
-    const RTInstance pseudo{m.index_offset, m.index_count, 0u, 0u};
-    if (!hip_ok(hipMemcpyAsync(d_pseudo.ptr, &pseudo, sizeof(pseudo), hipMemcpyHostToDevice, st), "upload", err) || !hip_ok(hipStreamSynchronize(st), "upload", err)) {
-      free_nodes();
+    const RTInstance pseudo{m.mesh.index_offset, m.mesh.index_count, 0u, 0u};
+    if (!hip_ok(hipMemcpyAsync(d_pseudo.ptr, &pseudo, sizeof(pseudo), hipMemcpyHostToDevice, st), "upload", err) || !hip_ok(hipStreamSynchronize(st), "upload", err))
       return false;
-    }
     LbvhInputs in{d_vertices_.ptr, d_indices_.ptr, d_pseudo.ptr, d_zero.ptr, 1u, d_ident.ptr, d_opaque.ptr, n, build_opts_.builder, build_opts_.pair_area_ratio};
     in.emit_quads = true;   // 64-byte leaf records (object space here), leaf links ~leaf number relative to the mesh
     LbvhOutputs out{};
     DeviceBuffer<BvhTri> tris;
-    if (!hip_ok(tris.alloc((size_t)n + 1), "alloc mesh triangles", err)) { free_nodes(); return false; }
+    if (!hip_ok(tris.alloc((size_t)n + 1), "alloc mesh triangles", err)) return false;
     out.tris = tris.ptr;
-    const hipError_t be = build_lbvh(st, in, out);
-    m.quads = out.quads;
-    m.n_leaves = out.quads ? out.n_leaves : 0u;
-    if (!hip_ok(be, "mesh hierarchy", err)) { if (out.nodes) (void)hipFree(out.nodes); free_nodes(); return false; }
-    m.nodes = out.nodes;
-    m.n_nodes = out.n_nodes;
-    m.depth = out.depth;
-    m.grid = out.grid;
-    for (int k = 0; k < 3; ++k) { m.lo[k] = out.bounds_lo[k]; m.hi[k] = out.bounds_hi[k]; }
-    total_nodes += out.n_nodes;
-    max_depth = std::max(max_depth, out.depth);
+    if (!hip_ok(build_lbvh(st, in, out), "mesh hierarchy", err)) return false;
+    m.nodes = std::move(out.nodes);
+    m.quads = std::move(out.quads);   // the mesh's leaf records (object space)
+    m.mesh.grid = out.grid;
+    for (int k = 0; k < 3; ++k) { m.mesh.lo[k] = out.bounds_lo[k]; m.mesh.hi[k] = out.bounds_hi[k]; }
+    tl_mesh_depth_ = std::max(tl_mesh_depth_, out.depth);
     // the mesh's triangles and per-object-triangle shading records go to their place in the concatenated arrays
-    if (!hip_ok(hipMemcpyAsync(d_tris_.ptr + m.tri_base, tris.ptr, sizeof(BvhTri) * n, hipMemcpyDeviceToDevice, st), "copy mesh triangles", err) ||
+    if (!hip_ok(hipMemcpyAsync(d_tris_.ptr + m.range.tri_base, tris.ptr, sizeof(BvhTri) * n, hipMemcpyDeviceToDevice, st), "copy mesh triangles", err) ||
         !hip_ok(launch_shade_records(st, n, tris.ptr, d_pseudo.ptr, d_indices_.ptr, d_vertices_.ptr, d_derivatives_.ptr, d_one.ptr,
-                                     d_shade_tris_.ptr + 8 * (size_t)m.tri_base), "k_shade_records", err) ||
-        !hip_ok(hipStreamSynchronize(st), "mesh hierarchy", err)) {
-      free_nodes();
+                                     d_shade_tris_.ptr + 8 * (size_t)m.range.tri_base), "k_shade_records", err) ||
+        !hip_ok(hipStreamSynchronize(st), "mesh hierarchy", err))
       return false;
-    }
   }
-  // ---- the meshes' leaf records, one array (TlasInstance::quad_base) ----
-  {
-    uint32_t total_leaves = 0;
-    for (MeshAs& m : meshes) {
-      m.quad_base = total_leaves;
-      total_leaves += m.n_leaves;
-    }
-    d_quads_.release();
-    bool ok = hip_ok(d_quads_.alloc((size_t)total_leaves + 1), "alloc leaf records", err);
-    if (ok) ok = hip_ok(hipMemsetAsync(d_quads_.ptr + total_leaves, 0, sizeof(BvhQuad), st), "clear leaf record padding", err);
-    for (MeshAs& m : meshes)
-      if (ok && m.n_leaves)
-        ok = hip_ok(hipMemcpyAsync(d_quads_.ptr + m.quad_base, m.quads, sizeof(BvhQuad) * m.n_leaves, hipMemcpyDeviceToDevice, st), "copy leaf records", err);
-    if (!ok) { (void)hipStreamSynchronize(st); free_nodes(); return false; }
+  // ---- where each mesh's nodes and leaf records go: one array each (TlasInstance::node_base / quad_base); the nodes follow a top
+  // level that does not exist yet ----
+  uint32_t total_leaves = 0;
+  tl_top_nodes_ = 0;
+  uint32_t at = 0;
+  for (MeshBuild& m : meshes) {
+    m.range.node_base = at;
+    m.range.n_nodes = (uint32_t)m.nodes.count;
+    m.range.quad_base = total_leaves;
+    at += m.range.n_nodes ? m.range.n_nodes : 1u;   // a mesh without triangles gets one node without children: entering it finds nothing
+    total_leaves += (uint32_t)m.quads.count;
   }
+  d_quads_.release();
+  if (!hip_ok(d_quads_.alloc((size_t)total_leaves + 1), "alloc leaf records", err) ||
+      !hip_ok(hipMemsetAsync(d_quads_.ptr + total_leaves, 0, sizeof(BvhQuad), st), "clear leaf record padding", err))
+    return false;
+  for (const MeshBuild& m : meshes)
+    if (m.quads.count && !hip_ok(hipMemcpyAsync(d_quads_.ptr + m.range.quad_base, m.quads.ptr, sizeof(BvhQuad) * m.quads.count, hipMemcpyDeviceToDevice, st), "copy leaf records", err))
+      return false;
   // ---- what the top level needs of each mesh, kept for update_transforms ----
   tl_meshes_.clear();
-  for (const MeshAs& m : meshes) {
-    TlMesh t{m.index_offset, m.index_count, m.grid, {m.lo[0], m.lo[1], m.lo[2]}, {m.hi[0], m.hi[1], m.hi[2]}};
-    tl_meshes_.push_back(t);
+  for (const MeshBuild& m : meshes) {
+    tl_meshes_.push_back(m.mesh);
+    h_mesh_ranges.push_back(m.range);
   }
   tl_mesh_of_ = mesh_of;
   tl_points_ready_ = false;
-  tl_mesh_depth_ = max_depth;
-  // ---- instance boxes (host_instance_boxes) ----
+  // ---- instance boxes (host_instance_boxes), then the top level over them ----
   const size_t ni = h_instances.size();
   std::vector<float4> blo, bhi;
   host_instance_boxes(tl_mesh_of_, instance_transforms(), box_meshes(), data.transforms, kExactBoxBudget, blo, bhi);
   DeviceBuffer<float4> d_blo, d_bhi;
+  if (!hip_ok(d_blo.upload(blo.data(), ni, st), "upload instance boxes", err) || !hip_ok(d_bhi.upload(bhi.data(), ni, st), "upload instance boxes", err) ||
+      !hip_ok(hipStreamSynchronize(st), "upload instance boxes", err))
+    return false;
+  return assemble_top_level(d_blo.ptr, d_bhi.ptr, blo, bhi, &meshes, timer, err);
+}
+
+// Everything from "the instance boxes are on the device" onwards, for a new scene and for moved instances alike: the hierarchy over
+// the boxes, its nodes in front of the meshes' nodes in one array, the instance records in its leaf order, the top table, info.
+// h_lo / h_hi: host copies of the boxes; empty = read back here.  built: the meshes' nodes as a build has just left them (their
+// place in the array: h_mesh_ranges, behind tl_top_nodes_ = 0 top nodes), or null = they sit in d_nodes_ behind the old top level.
+// timer: started by the caller, where info.build_ms is to begin.
+bool Scene::assemble_top_level(const float4* d_lo, const float4* d_hi, std::vector<float4>& h_lo, std::vector<float4>& h_hi, const std::vector<MeshBuild>* built,
+                               StreamTimer& timer, Error& err) {
+  hipStream_t st = instance->stream;
+  const size_t ni = h_instances.size();
   DeviceBuffer<BvhTri> top_tris;
   LbvhOutputs top{};
-  if (!hip_ok(d_blo.upload(blo.data(), ni, st), "upload instance boxes", err) || !hip_ok(d_bhi.upload(bhi.data(), ni, st), "upload instance boxes", err) ||
-      !hip_ok(top_tris.alloc(ni + 1), "alloc", err) || !hip_ok(hipStreamSynchronize(st), "upload instance boxes", err)) {
-    free_nodes();
-    return false;
-  }
+  if (!hip_ok(top_tris.alloc(ni + 1), "alloc", err)) return false;
   {
     LbvhInputs in{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, (uint32_t)ni, build_opts_.builder, 0.0f};
-    in.given_lo = d_blo.ptr;
-    in.given_hi = d_bhi.ptr;
+    in.given_lo = d_lo;
+    in.given_hi = d_hi;
     top.tris = top_tris.ptr;
-    if (!hip_ok(build_lbvh(st, in, top), "instance hierarchy", err)) { free_nodes(); return false; }
+    if (!hip_ok(build_lbvh(st, in, top), "instance hierarchy", err)) return false;
   }
-  // ---- one node array: top level first, then the meshes ----
-  for (MeshAs& m : meshes)
-    if (m.n_nodes == 0) total_nodes += 1;   // a mesh without triangles gets one node without children: entering it finds nothing
-  const uint32_t n_nodes = top.n_nodes + total_nodes;
+  // ---- one node array: top level first, then the meshes (moved as they are when the top level's size changes) ----
+  const MeshRange& last = h_mesh_ranges.back();   // (a two-level scene has a mesh)
+  const uint32_t old_top = tl_top_nodes_, new_top = (uint32_t)top.nodes.count;
+  const uint32_t mesh_nodes = last.node_base + (last.n_nodes ? last.n_nodes : 1u) - old_top, n_nodes = new_top + mesh_nodes;
   if (n_nodes >= (uint32_t)kBvhTopFlag) {
-    free_nodes();
-    if (top.nodes) (void)hipFree(top.nodes);
     err.code = GLZ_E_UNSUPPORTED;
     err.msg = "more than 2^30 BVH nodes";
     return false;
   }
-  bool ok = hip_ok(d_nodes_.alloc(n_nodes), "alloc nodes", err);
-  if (ok && top.n_nodes) ok = hip_ok(hipMemcpyAsync(d_nodes_.ptr, top.nodes, sizeof(BvhNode4) * top.n_nodes, hipMemcpyDeviceToDevice, st), "copy nodes", err);
-  uint32_t at = top.n_nodes;
-  for (MeshAs& m : meshes) {
-    m.node_base = at;
-    if (ok && m.n_nodes) ok = hip_ok(hipMemcpyAsync(d_nodes_.ptr + at, m.nodes, sizeof(BvhNode4) * m.n_nodes, hipMemcpyDeviceToDevice, st), "copy nodes", err);
-    if (ok && m.n_nodes == 0) {
-      static BvhNode4 childless;
-      for (int k = 0; k < 4; ++k) {
-        childless.w[3 * k] = childless.w[3 * k + 1] = childless.w[3 * k + 2] = kBvhGridMax;
-        childless.w[12 + k] = (uint32_t)kBvhEmptyChild;
-      }
-      ok = hip_ok(hipMemcpyAsync(d_nodes_.ptr + at, &childless, sizeof(BvhNode4), hipMemcpyHostToDevice, st), "copy nodes", err);
+  DeviceBuffer<BvhNode4> fresh;
+  const bool in_place = !built && new_top == old_top;
+  if (!in_place && !hip_ok(fresh.alloc(n_nodes), "alloc nodes", err)) return false;
+  BvhNode4* nodes = in_place ? d_nodes_.ptr : fresh.ptr;
+  bool ok = !new_top || hip_ok(hipMemcpyAsync(nodes, top.nodes.ptr, sizeof(BvhNode4) * new_top, hipMemcpyDeviceToDevice, st), "copy nodes", err);
+  if (built) {
+    static const BvhNode4 childless = childless_node4();   // (static: the copy below is asynchronous)
+    for (const MeshBuild& m : *built) {
+      BvhNode4* to = nodes + new_top + m.range.node_base;
+      if (ok && m.nodes.count) ok = hip_ok(hipMemcpyAsync(to, m.nodes.ptr, sizeof(BvhNode4) * m.nodes.count, hipMemcpyDeviceToDevice, st), "copy nodes", err);
+      if (ok && !m.nodes.count) ok = hip_ok(hipMemcpyAsync(to, &childless, sizeof(BvhNode4), hipMemcpyHostToDevice, st), "copy nodes", err);
     }
-    h_mesh_ranges.push_back(MeshRange{m.node_base, m.n_nodes, m.quad_base, m.tri_base});
-    at += m.n_nodes ? m.n_nodes : 1u;
+  } else if (!in_place && ok) {
+    ok = hip_ok(hipMemcpyAsync(nodes + new_top, d_nodes_.ptr + old_top, sizeof(BvhNode4) * mesh_nodes, hipMemcpyDeviceToDevice, st), "move mesh nodes", err);
   }
   // instance records in the top level's leaf order
   std::vector<BvhTri> order(ni);
   if (ok) ok = hip_ok(hipMemcpyAsync(order.data(), top_tris.ptr, sizeof(BvhTri) * ni, hipMemcpyDeviceToHost, st), "read instance order", err);
-  if (ok) ok = hip_ok(hipStreamSynchronize(st), "two-level build", err);
-  free_nodes();
-  if (top.nodes) (void)hipFree(top.nodes);
-  if (!ok) return false;
-  tl_top_nodes_ = top.n_nodes;
-  if (!write_top_records(order, instance_reach(blo, bhi), err)) return false;
+  if (h_lo.empty()) {
+    h_lo.resize(ni);
+    h_hi.resize(ni);
+    if (ok) ok = hip_ok(hipMemcpyAsync(h_lo.data(), d_lo, sizeof(float4) * ni, hipMemcpyDeviceToHost, st), "read instance boxes", err);
+    if (ok) ok = hip_ok(hipMemcpyAsync(h_hi.data(), d_hi, sizeof(float4) * ni, hipMemcpyDeviceToHost, st), "read instance boxes", err);
+  }
+  if (!hip_ok(hipStreamSynchronize(st), "top level", err) || !ok) return false;
+  if (!in_place) {
+    d_nodes_ = std::move(fresh);
+    for (MeshRange& r : h_mesh_ranges) r.node_base = r.node_base - old_top + new_top;
+  }
+  tl_top_nodes_ = new_top;
+  if (!write_top_records(order, instance_reach(h_lo, h_hi), err)) return false;
   if (!d_top_.ptr && !hip_ok(d_top_.alloc(kBvhTopNodes), "alloc BVH top table", err)) return false;
-  if (!hip_ok(launch_top_table(st, d_nodes_.ptr, top.n_nodes, d_top_.ptr), "k_top_table", err)) return false;   // unused by the two-level tracer, kept valid
+  if (!hip_ok(launch_top_table(st, d_nodes_.ptr, new_top, d_top_.ptr), "k_top_table", err)) return false;   // unused by the two-level tracer, kept valid
   timer.stop(st);
-  if (!hip_ok(hipStreamSynchronize(st), "two-level build", err)) return false;
+  if (!hip_ok(hipStreamSynchronize(st), "top level", err)) return false;
   finish_two_level(top, timer.ms());
   return true;
 }
@@ -948,18 +953,20 @@ void Scene::finish_two_level(const LbvhOutputs& top, float build_ms) {
                   (uint64_t)d_quads_.count * sizeof(BvhQuad);
 }
 
+// The structure with the instance's current options; from then on they are the scene's own (update_transforms keeps them)
+bool Scene::build_bvh_as_instance_says(Error& err) {
+  build_opts_ = BuildOptions{instance->bvh_builder, instance->bvh_pair_area_ratio, instance->as_levels};
+  if (!build_bvh(err)) return false;
+  build_opts_.as_levels = (int)info.as_levels;   // the shape built
+  return true;
+}
+
 bool Scene::build_bvh(Error& err) {
   // instanced scenes keep one hierarchy per mesh (acceleration.rs:319-345) instead of one over every instanced triangle
   {
     uint64_t unique = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> seen;
-    for (const RTInstance& in : h_instances) {
-      const std::pair<uint32_t, uint32_t> key(in.index_offset, in.index_count);
-      if (std::find(seen.begin(), seen.end(), key) == seen.end()) {
-        seen.push_back(key);
-        unique += in.index_count / 3u;
-      }
-    }
+    std::vector<uint32_t> mesh_of;
+    for (const std::pair<uint32_t, uint32_t>& range : unique_meshes(h_instances, mesh_of)) unique += range.second / 3u;
     const bool wanted = build_opts_.as_levels == 2 || (build_opts_.as_levels == 0 && unique > 0 && info.n_world_triangles > 4 * unique);
     dev.two_level = 0u;
     dev.tlas_nodes = nullptr;
@@ -984,14 +991,12 @@ bool Scene::build_bvh(Error& err) {
   const hipError_t be = build_lbvh(st, in, out);
   timer.stop(st);
   const float ms = timer.ms();
-  d_quads_.ptr = out.quads;       // ours whatever the build returned
-  d_quads_.count = out.quads ? out.n_leaves : 0;
-  d_nodes8_.ptr = out.nodes8;
-  d_nodes8_.count = out.nodes8 ? out.n_nodes8 : 0;
   if (!hip_ok(be, "LBVH build", err)) return false;
-  d_nodes_.ptr = out.nodes;       // allocated by the build once the number of 4-wide nodes is known
-  d_nodes_.count = out.n_nodes;
-  info.bvh_nodes = out.n_nodes;
+  d_quads_ = std::move(out.quads);
+  d_nodes8_ = std::move(out.nodes8);
+  d_nodes_ = std::move(out.nodes);   // allocated by the build once the number of 4-wide nodes is known
+  const uint32_t n_nodes = (uint32_t)d_nodes_.count;
+  info.bvh_nodes = n_nodes;
   info.bvh_depth = out.depth;
   info.bvh_sah_cost = out.sah;
   info.build_ms = ms;
@@ -1004,17 +1009,17 @@ bool Scene::build_bvh(Error& err) {
   const uint32_t stack_bound = std::max(3u * out.depth, 7u * out.depth8) + 1u;   // (an 8-wide visit pushes up to seven)
   stack_overflow_depth = stack_bound > (uint32_t)kTraversalLdsStack ? stack_bound - kTraversalLdsStack + 1 : 1;
   dev.bvh_nodes = d_nodes_.ptr;
-  if (out.n_nodes >= (uint32_t)kBvhTopFlag) {
+  if (n_nodes >= (uint32_t)kBvhTopFlag) {
     err.code = GLZ_E_UNSUPPORTED;
     err.msg = "more than 2^30 BVH nodes";
     return false;
   }
   // top levels of the tree for the tracers' LDS staging
   if (!d_top_.ptr && !hip_ok(d_top_.alloc(kBvhTopNodes), "alloc BVH top table", err)) return false;
-  if (!hip_ok(launch_top_table(st, d_nodes_.ptr, out.n_nodes, d_top_.ptr), "k_top_table", err)) return false;
+  if (!hip_ok(launch_top_table(st, d_nodes_.ptr, n_nodes, d_top_.ptr), "k_top_table", err)) return false;
   dev.bvh_top = d_top_.ptr;
   dev.bvh_nodes8 = d_nodes8_.ptr;
-  info.bvh_nodes8 = d_nodes8_.ptr ? out.n_nodes8 : 0;
+  info.bvh_nodes8 = (uint32_t)d_nodes8_.count;
   dev.bvh_grid = out.grid;
   for (int k = 0; k < 3; ++k) {
     info.bvh_grid_lo[k] = out.grid.lo[k];
@@ -1037,7 +1042,7 @@ bool Scene::build_bvh(Error& err) {
   if (!build_alpha_records(err)) return false;
   info.as_levels = 1;
   info.n_as_triangles = n;
-  info.as_bytes = (uint64_t)out.n_nodes * sizeof(BvhNode4) + (uint64_t)(n + 1) * sizeof(BvhTri) + (uint64_t)n * 128u + (uint64_t)out.n_leaves * sizeof(BvhQuad) +
+  info.as_bytes = (uint64_t)n_nodes * sizeof(BvhNode4) + (uint64_t)(n + 1) * sizeof(BvhTri) + (uint64_t)n * 128u + (uint64_t)d_quads_.count * sizeof(BvhQuad) +
                   (uint64_t)info.bvh_nodes8 * sizeof(BvhNode8);
   return true;
 }
@@ -1115,9 +1120,7 @@ bool Scene::update_materials_and_lights(const glz_material* mats, uint32_t n_mat
   if (!build_materials(err)) return false;
   if (!build_lights_and_sky(err)) return false;
   if (opacity_changed) {   // the non-opaque flag lives in the leaf records; rebuilt with the instance's current options
-    build_opts_ = BuildOptions{instance->bvh_builder, instance->bvh_pair_area_ratio, instance->as_levels};
-    if (!build_bvh(err)) return false;
-    build_opts_.as_levels = (int)info.as_levels;
+    if (!build_bvh_as_instance_says(err)) return false;
   }
   if (!build_alpha_records(err)) return false;             // which opacity map a material names, where its texels lie
   info.n_lights = lights_no;
@@ -1156,36 +1159,13 @@ std::vector<uint32_t> Scene::instance_transforms() const {
 }
 
 bool host_instance_boxes_of(const SceneData& d, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err) {
-  for (const glz_mesh& m : d.meshes)
-    if ((uint64_t)m.index_offset + m.index_count > d.indices.size()) {
-      err.code = GLZ_E_INVALID_DATA;
-      err.msg = "mesh index range outside the index buffer";
-      return false;
-    }
-  for (uint32_t i : d.indices)
-    if (i >= d.vertices.size()) {
-      err.code = GLZ_E_INVALID_DATA;
-      err.msg = "vertex index out of range";
-      return false;
-    }
   std::vector<glz_transform> transforms = d.transforms;
   if (transforms.empty()) transforms.push_back(identity_transform());   // as Scene::create
+  if (!valid_geometry(d, transforms.size(), err)) return false;
   const std::vector<RTInstance> inst = rt_instances(d);
-  std::vector<std::pair<uint32_t, uint32_t>> ranges;
-  std::vector<uint32_t> mesh_of(inst.size()), transform_of(inst.size());
-  for (size_t i = 0; i < inst.size(); ++i) {
-    if (inst[i].transform_id >= transforms.size()) {
-      err.code = GLZ_E_INVALID_DATA;
-      err.msg = "instance references a missing transform";
-      return false;
-    }
-    const std::pair<uint32_t, uint32_t> key(inst[i].index_offset, inst[i].index_count);
-    size_t m = 0;
-    while (m < ranges.size() && ranges[m] != key) ++m;
-    if (m == ranges.size()) ranges.push_back(key);
-    mesh_of[i] = (uint32_t)m;
-    transform_of[i] = inst[i].transform_id;
-  }
+  std::vector<uint32_t> mesh_of, transform_of(inst.size());
+  const std::vector<std::pair<uint32_t, uint32_t>> ranges = unique_meshes(inst, mesh_of);
+  for (size_t i = 0; i < inst.size(); ++i) transform_of[i] = inst[i].transform_id;
   std::vector<std::vector<float>> pts = mesh_points(d, ranges);
   std::vector<InstanceBoxMesh> meshes(ranges.size());
   for (size_t m = 0; m < meshes.size(); ++m) {
@@ -1285,61 +1265,11 @@ bool Scene::instance_boxes(bool on_device, uint64_t budget, std::vector<float4>&
 // The top level again, over the instance boxes of the current transforms; the meshes' hierarchies, leaf records and shading records
 // stay where they are (their links are relative to TlasInstance::node_base / quad_base / tri_base).
 bool Scene::rebuild_top_level(Error& err) {
-  hipStream_t st = instance->stream;
   StreamTimer timer;
-  if (!timer.start(st, err)) return false;
-  const size_t ni = h_instances.size();
+  if (!timer.start(instance->stream, err)) return false;
   if (!device_instance_boxes(kExactBoxBudget, err)) return false;
-  DeviceBuffer<BvhTri> top_tris;
-  LbvhOutputs top{};
-  if (!hip_ok(top_tris.alloc(ni + 1), "alloc", err)) return false;
-  {
-    LbvhInputs in{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, (uint32_t)ni, build_opts_.builder, 0.0f};
-    in.given_lo = d_box_lo_.ptr;
-    in.given_hi = d_box_hi_.ptr;
-    top.tris = top_tris.ptr;
-    if (!hip_ok(build_lbvh(st, in, top), "instance hierarchy", err)) return false;
-  }
-  // ---- one node array: top level first, then the meshes (moved as they are when the top level's size changes) ----
-  const uint32_t old_top = tl_top_nodes_, mesh_nodes = (uint32_t)d_nodes_.count - old_top, n_nodes = top.n_nodes + mesh_nodes;
-  bool ok = true;
-  if (n_nodes >= (uint32_t)kBvhTopFlag) {
-    err.code = GLZ_E_UNSUPPORTED;
-    err.msg = "more than 2^30 BVH nodes";
-    ok = false;
-  }
-  BvhNode4* fresh = nullptr;
-  if (ok && top.n_nodes == old_top) {
-    ok = hip_ok(hipMemcpyAsync(d_nodes_.ptr, top.nodes, sizeof(BvhNode4) * top.n_nodes, hipMemcpyDeviceToDevice, st), "copy nodes", err);
-  } else if (ok) {
-    ok = hip_ok(hipMalloc(&fresh, sizeof(BvhNode4) * n_nodes), "alloc nodes", err);
-    if (ok) ok = hip_ok(hipMemcpyAsync(fresh, top.nodes, sizeof(BvhNode4) * top.n_nodes, hipMemcpyDeviceToDevice, st), "copy nodes", err);
-    if (ok) ok = hip_ok(hipMemcpyAsync(fresh + top.n_nodes, d_nodes_.ptr + old_top, sizeof(BvhNode4) * mesh_nodes, hipMemcpyDeviceToDevice, st), "move mesh nodes", err);
-  }
-  std::vector<BvhTri> order(ni);
-  std::vector<float4> blo(ni), bhi(ni);
-  if (ok) ok = hip_ok(hipMemcpyAsync(order.data(), top_tris.ptr, sizeof(BvhTri) * ni, hipMemcpyDeviceToHost, st), "read instance order", err);
-  if (ok) ok = hip_ok(hipMemcpyAsync(blo.data(), d_box_lo_.ptr, sizeof(float4) * ni, hipMemcpyDeviceToHost, st), "read instance boxes", err);
-  if (ok) ok = hip_ok(hipMemcpyAsync(bhi.data(), d_box_hi_.ptr, sizeof(float4) * ni, hipMemcpyDeviceToHost, st), "read instance boxes", err);
-  if (!hip_ok(hipStreamSynchronize(st), "top level", err)) ok = false;
-  if (top.nodes) (void)hipFree(top.nodes);
-  if (!ok) {
-    if (fresh) (void)hipFree(fresh);
-    return false;
-  }
-  if (fresh) {
-    d_nodes_.release();
-    d_nodes_.ptr = fresh;
-    d_nodes_.count = n_nodes;
-    for (MeshRange& r : h_mesh_ranges) r.node_base = r.node_base - old_top + top.n_nodes;
-  }
-  tl_top_nodes_ = top.n_nodes;
-  if (!write_top_records(order, instance_reach(blo, bhi), err)) return false;
-  if (!hip_ok(launch_top_table(st, d_nodes_.ptr, top.n_nodes, d_top_.ptr), "k_top_table", err)) return false;
-  timer.stop(st);
-  if (!hip_ok(hipStreamSynchronize(st), "top level", err)) return false;
-  finish_two_level(top, timer.ms());
-  return true;
+  std::vector<float4> blo, bhi;   // read back with the leaf order
+  return assemble_top_level(d_box_lo_.ptr, d_box_hi_.ptr, blo, bhi, nullptr, timer, err);
 }
 
 bool Scene::update_transforms(const glz_transform* transforms, uint32_t n, Error& err) {

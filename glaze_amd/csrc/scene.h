@@ -57,30 +57,7 @@ double instance_reach(const std::vector<float4>& lo, const std::vector<float4>& 
 // its mesh hierarchies' root boxes).  One box per instance that names an existing mesh.
 bool host_instance_boxes_of(const SceneData& d, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err);
 
-template <class T>
-struct DeviceBuffer {
-  T* ptr = nullptr;
-  size_t count = 0;
-  DeviceBuffer() = default;
-  DeviceBuffer(const DeviceBuffer&) = delete;
-  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
-  ~DeviceBuffer() { release(); }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    count = 0;
-  }
-  hipError_t alloc(size_t n) {
-    release();
-    count = n;
-    return hipMalloc(reinterpret_cast<void**>(&ptr), sizeof(T) * (n ? n : 1));
-  }
-  hipError_t upload(const T* host, size_t n, hipStream_t st) {
-    hipError_t e = alloc(n);
-    if (e != hipSuccess || n == 0) return e;
-    return hipMemcpyAsync(ptr, host, sizeof(T) * n, hipMemcpyHostToDevice, st);
-  }
-};
+struct StreamTimer;   // scene.cpp
 
 // RayTraceScene (lib/src/vulkan/scene.rs:1352-1556)
 class Scene {
@@ -144,6 +121,13 @@ class Scene {
     float lo[3], hi[3];   // object box (the mesh hierarchy's root box)
   };
   std::vector<TlMesh> tl_meshes_;
+  // a mesh as build_two_level has just built it: what is kept of it (tl_meshes_, h_mesh_ranges) and what moves into the scene's arrays
+  struct MeshBuild {
+    TlMesh mesh{};
+    MeshRange range{};
+    DeviceBuffer<BvhNode4> nodes;
+    DeviceBuffer<BvhQuad> quads;   // leaf records, object space
+  };
   std::vector<uint32_t> tl_mesh_of_;   // per RTInstance
   uint32_t tl_top_nodes_ = 0;          // the top level's nodes at the head of d_nodes_
   uint32_t tl_mesh_depth_ = 0;         // deepest mesh hierarchy
@@ -151,6 +135,8 @@ class Scene {
   std::vector<uint32_t> instance_transforms() const;
   bool write_top_records(const std::vector<BvhTri>& order, double reach, Error& err);
   void finish_two_level(const LbvhOutputs& top, float build_ms);
+  bool assemble_top_level(const float4* d_lo, const float4* d_hi, std::vector<float4>& h_lo, std::vector<float4>& h_hi, const std::vector<MeshBuild>* built,
+                          StreamTimer& timer, Error& err);
   bool rebuild_top_level(Error& err);
   bool device_instance_boxes(uint64_t budget, Error& err);   // -> d_box_lo_ / d_box_hi_
   // the device side of the instance boxes, built on the first update: the meshes' distinct vertices then eight corners per mesh
@@ -165,6 +151,7 @@ class Scene {
   bool build_materials(Error& err);
   bool build_lights_and_sky(Error& err);
   bool build_bvh(Error& err);
+  bool build_bvh_as_instance_says(Error& err);
   bool build_alpha_records(Error& err);   // DeviceScene::alpha_recs, after anything that changes materials, textures or the triangle slots
   bool build_two_level(Error& err);
 
