@@ -24,7 +24,7 @@ from .abi import GlazeError
 from .scene_desc import SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
 
 __all__ = ["parse", "converted_file", "ParsedScene", "RayTraceInstance", "RayTraceScene", "RayTraceRenderer", "Integrator",
-           "GlazeError", "SceneDesc"]
+           "GlazeError", "SceneDesc", "host_denoise"]
 
 
 def _ptr(a):
@@ -162,6 +162,27 @@ def host_instance_boxes(desc, budget=0):
     lo, hi = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
     abi.check(abi.lib().glz_host_instance_boxes(C.byref(c), budget, _ptr(lo), _ptr(hi)))
     return lo, hi
+
+
+def _denoise_frames(result, aov0, aov1):
+    r = np.ascontiguousarray(result, np.float32)
+    if r.ndim != 3 or r.shape[2] != 4:
+        raise ValueError("result must be H x W x 4")
+    a0 = np.ascontiguousarray(aov0, np.float32)
+    a1 = np.ascontiguousarray(aov1, np.float32)
+    if a0.shape != r.shape or a1.shape != r.shape:
+        raise ValueError("aov0 and aov1 must have result's shape")
+    return r, a0, a1
+
+
+def host_denoise(result, aov0, aov1, **params):
+    """glz_host_denoise: the denoiser's filter on the host (no device), the reference of the device kernels.  result, aov0 = (normal, depth),
+    aov1 = (albedo, instance bits): H x W x 4 float32; params: the fields of glz_denoise_params (defaults: the library's)."""
+    r, a0, a1 = _denoise_frames(result, aov0, aov1)
+    out = np.zeros_like(r)
+    p = abi.DenoiseParams(**params)
+    abi.check(abi.lib().glz_host_denoise(r.shape[1], r.shape[0], _ptr(r), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out)))
+    return out
 
 
 def _texture_array(textures, keep):
@@ -318,6 +339,14 @@ class RayTraceInstance:
         out = np.zeros_like(x)
         code = {"sin": 0, "cos": 1, "acos": 2, "atan2": 3, "log2": 4, "floor": 5}[fn]
         abi.check(abi.lib().glz_debug_detmath(self._h, code, _ptr(x), None if y is None else _ptr(y), _ptr(out), x.size))
+        return out
+
+    def debug_denoise(self, result, aov0, aov1, **params):
+        """the device filter on host arrays (upload, kernels, read back): bit for bit glaze_amd.host_denoise"""
+        r, a0, a1 = _denoise_frames(result, aov0, aov1)
+        out = np.zeros_like(r)
+        p = abi.DenoiseParams(**params)
+        abi.check(abi.lib().glz_debug_denoise(self._h, r.shape[1], r.shape[0], _ptr(r), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out)))
         return out
 
     def __del__(self):
@@ -606,6 +635,41 @@ class RayTraceRenderer:
         out = np.zeros((self.height, self.width, 4), np.float32)
         abi.check(abi.lib().glz_renderer_read_result(self._h, _ptr(out)))
         return out
+
+    # ---- post: first-hit feature buffers and the denoiser ----
+    def read_aov(self, name):
+        """Runs the first-hit pass (one centre ray per pixel, the whole frame) and returns one of its planes, H x W x 4 float32:
+        'normal_depth' (or 0) = (shading normal facing the camera, hit distance; +inf for a miss), 'albedo_instance' (or 1) = (albedo,
+        the bits of the instance index; view the last channel as uint32, 0xFFFFFFFF for a miss)."""
+        which = {"normal_depth": abi.AOV_NORMAL_DEPTH, "albedo_instance": abi.AOV_ALBEDO_INSTANCE}.get(name, name)
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        abi.check(abi.lib().glz_renderer_read_aov(self._h, which, _ptr(out)))
+        return out
+
+    def set_denoise(self, **params):
+        """the fields of glz_denoise_params; those left out take the library's defaults.  Accumulation goes on."""
+        p = abi.DenoiseParams(**params)
+        abi.check(abi.lib().glz_renderer_set_denoise(self._h, C.cast(C.byref(p), C.c_void_p)))
+
+    def read_denoised(self, want_rgba8=False):
+        """The result image through the denoiser: H x W x 4 float32, and with want_rgba8 also its 8-bit sRGB image (a pair)."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        img = np.zeros((self.height, self.width, 4), np.uint8) if want_rgba8 else None
+        abi.check(abi.lib().glz_renderer_read_denoised(self._h, _ptr(out), _ptr(img) if want_rgba8 else None))
+        return (out, img) if want_rgba8 else out
+
+    def debug_camera_rays(self, offset=(0.5, 0.5)):
+        """camera_ray() of every pixel at one sub-pixel offset, on the device: origins, directions (H x W x 3 float32 each)"""
+        o = np.zeros((self.height, self.width, 3), np.float32)
+        d = np.zeros((self.height, self.width, 3), np.float32)
+        abi.check(abi.lib().glz_debug_camera_rays(self._h, float(offset[0]), float(offset[1]), _ptr(o), _ptr(d)))
+        return o, d
+
+    def debug_post_timing(self):
+        """one run of the post stages between device events, ms: {'first_hit_trace', 'first_hit_attributes', 'demodulate', 'passes': [...]}"""
+        ms = np.zeros(abi.POST_TIMING_SLOTS, np.float32)
+        abi.check(abi.lib().glz_debug_post_timing(self._h, _ptr(ms)))
+        return {"first_hit_trace": float(ms[0]), "first_hit_attributes": float(ms[1]), "demodulate": float(ms[2]), "passes": [float(x) for x in ms[3:]]}
 
     def launch_constants(self, launch):
         s = C.c_uint32()

@@ -103,6 +103,23 @@ class RenderStats(C.Structure):
                 ("sky_samples", C.c_uint64)]
 
 
+class DenoiseParams(C.Structure):
+    """glz_denoise_params; the defaults are the library's (glz_renderer_set_denoise(r, NULL))"""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("normal_power_log2", C.c_uint32),
+                ("eps_albedo", C.c_float), ("eps_depth", C.c_float), ("eps_color", C.c_float)]
+    DEFAULTS = dict(iterations=5, sigma_color=4.0, sigma_depth=1.0, normal_power_log2=6, eps_albedo=1.0 / 256.0, eps_depth=1e-3, eps_color=1e-8)
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown denoise parameter(s): %s" % ", ".join(sorted(unknown)))
+        super().__init__(**dict(self.DEFAULTS, **kw))
+
+
+AOV_NORMAL_DEPTH, AOV_ALBEDO_INSTANCE = 0, 1
+DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_POWER_LOG2 = 8, 31
+POST_TIMING_SLOTS = 3 + DENOISE_MAX_ITERATIONS     # glz_debug_post_timing
+
 DRAW_CALLBACK = C.CFUNCTYPE(None, C.c_void_p)
 
 # every symbol include/glaze_abi.h declares: name -> (restype, argtypes)
@@ -204,6 +221,13 @@ PROTOTYPES = {
     "glz_renderer_device_scene_info": (C.c_int, [_P, C.c_int, _P]),
     "glz_rccl_version": (C.c_int, []),
     "glz_host_tile_owner": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P]),
+    "glz_renderer_read_aov": (C.c_int, [_P, C.c_int, _P]),
+    "glz_renderer_set_denoise": (C.c_int, [_P, _P]),
+    "glz_renderer_read_denoised": (C.c_int, [_P, _P, _P]),
+    "glz_host_denoise": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
+    "glz_debug_denoise": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
+    "glz_debug_camera_rays": (C.c_int, [_P, C.c_float, C.c_float, _P, _P]),
+    "glz_debug_post_timing": (C.c_int, [_P, _P]),
 }
 
 _LIB = None

@@ -10,6 +10,7 @@
 #include "parser.h"
 #include "serializer.h"
 #include "converter.h"
+#include "denoise.h"
 #include "codec/jpeg.h"
 #include "codec/png_enc.h"
 #include <strings.h>
@@ -406,6 +407,30 @@ int glz_renderer_read_result(glz_renderer* h, float* out) {
   GLZ_RET(h->r->read_frame(true, out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_renderer_read_aov(glz_renderer* h, int which, float* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!out) return fail(GLZ_E_ARG, "output is null");
+  GLZ_RET(h->r->read_aov(which, out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_set_denoise(glz_renderer* h, const glz_denoise_params* p) { GLZ_GUARD_BEGIN GLZ_R(h); GLZ_RET(h->r->set_denoise(p, e)); GLZ_GUARD_END(GLZ_E_IO) }
+int glz_renderer_read_denoised(glz_renderer* h, float* rgba32f, uint8_t* rgba8) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  GLZ_RET(h->r->read_denoised(rgba32f, rgba8, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_post_timing(glz_renderer* h, float ms_out[GLZ_POST_TIMING_SLOTS]) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!ms_out) return fail(GLZ_E_ARG, "output is null");
+  GLZ_RET(h->r->time_post(ms_out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_camera_rays(glz_renderer* h, float off_x, float off_y, float* origins3, float* dirs3) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!origins3 || !dirs3) return fail(GLZ_E_ARG, "output is null");
+  GLZ_RET(h->r->camera_rays(off_x, off_y, origins3, dirs3, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_launch_constants(glz_renderer* h, uint32_t launch, uint32_t* seed, float off[2]) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!seed || !off) return fail(GLZ_E_ARG, "output is null");
@@ -702,6 +727,49 @@ int64_t glz_debug_read_texture_level(glz_scene* h, uint32_t texture, uint32_t le
   if (height) *height = hh;
   if (out && cap > 0 && !px.empty()) memcpy(out, px.data(), (size_t)std::min<int64_t>(cap, (int64_t)px.size()));
   return (int64_t)px.size();
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+namespace {
+// the checks glz_host_denoise and glz_debug_denoise share; returns 0 when there is work to do, 1 for an empty frame
+int denoise_arguments(uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1, const glz_denoise_params* p, float* out,
+                      glz_denoise_params& P) {
+  if (!result || !aov0 || !aov1 || !out) return fail(GLZ_E_ARG, "null argument");
+  P = p ? *p : post::denoise_defaults();
+  if (!post::denoise_params_valid(P)) return fail(GLZ_E_ARG, post::kDenoiseParamsMessage);
+  if ((uint64_t)w * h > 0x7FFFFFFFull) return fail(GLZ_E_ARG, "frame too large");
+  return w == 0 || h == 0 ? 1 : 0;
+}
+}  // namespace
+int glz_host_denoise(uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1, const glz_denoise_params* p, float* out) {
+  GLZ_GUARD_BEGIN
+  glz_denoise_params P;
+  const int st = denoise_arguments(w, h, result, aov0, aov1, p, out, P);
+  if (st != 0) return st < 0 ? st : GLZ_OK;
+  post::host_denoise(w, h, reinterpret_cast<const float4*>(result), reinterpret_cast<const float4*>(aov0), reinterpret_cast<const float4*>(aov1), P,
+                     reinterpret_cast<float4*>(out));
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_denoise(glz_instance* inst, uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1, const glz_denoise_params* p,
+                      float* out) {
+  GLZ_GUARD_BEGIN
+  if (!inst) return fail(GLZ_E_ARG, "null argument");
+  glz_denoise_params P;
+  const int status = denoise_arguments(w, h, result, aov0, aov1, p, out, P);
+  if (status != 0) return status < 0 ? status : GLZ_OK;
+  Error e;
+  if (!hip_ok(hipSetDevice(inst->i->device), "hipSetDevice", e)) return fail(e);
+  hipStream_t st = inst->i->stream;
+  const size_t n = (size_t)w * h;
+  DeviceBuffer<float4> d_res, d_a0, d_a1, d_ping, d_pong, d_out;
+  if (!hip_ok(d_res.upload(reinterpret_cast<const float4*>(result), n, st), "upload", e) || !hip_ok(d_a0.upload(reinterpret_cast<const float4*>(aov0), n, st), "upload", e) ||
+      !hip_ok(d_a1.upload(reinterpret_cast<const float4*>(aov1), n, st), "upload", e) || !hip_ok(d_ping.alloc(n), "alloc", e) || !hip_ok(d_pong.alloc(n), "alloc", e) ||
+      !hip_ok(d_out.alloc(n), "alloc", e))
+    return fail(e);
+  if (!hip_ok(launch_denoise(st, w, h, P, d_res.ptr, d_a0.ptr, d_a1.ptr, d_ping.ptr, d_pong.ptr, d_out.ptr), "k_atrous", e)) return fail(e);
+  if (!hip_ok(hipMemcpyAsync(out, d_out.ptr, n * sizeof(float4), hipMemcpyDeviceToHost, st), "debug denoise", e)) return fail(e);
+  if (!hip_ok(hipStreamSynchronize(st), "debug denoise", e)) return fail(e);
+  return GLZ_OK;
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_debug_tonemap(glz_instance* inst, const float* rgba32f, uint64_t n, uint8_t* out) {

@@ -2,7 +2,8 @@
 // (cli/src/main.rs:24-39: `input output -r/--res WxH -s/--spp N -i/--integrator {direct,pt}`),
 // same messages and exit codes (cli/src/main.rs:41-135), driving the C ABI of libglaze_hip.so.
 // Build-defined extras: --seed, --depth, --device, --devices a,b,c (several GPUs of this process: tiles sharded, RCCL reduce),
-// --hdr-out file.pfm, --report (JSON on stdout).
+// --hdr-out file.pfm, --report (JSON on stdout), --denoise (the saved image and --hdr-out are the denoised ones), --aov-out PREFIX (the
+// first-hit feature buffers: PREFIX.normal.png, PREFIX.albedo.png, PREFIX.depth.bin).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -38,6 +39,35 @@ bool write_pfm(const std::string& path, const float* rgba, uint32_t w, uint32_t 
   return true;
 }
 
+// the first-hit feature buffers of --aov-out: two 8-bit images and the raw depth plane
+bool write_aovs(glz_renderer* renderer, const std::string& prefix, uint32_t w, uint32_t h) {
+  const size_t n = (size_t)w * h;
+  std::vector<float> nd(n * 4), ai(n * 4), depth(n);
+  if (glz_renderer_read_aov(renderer, GLZ_AOV_NORMAL_DEPTH, nd.data()) != GLZ_OK || glz_renderer_read_aov(renderer, GLZ_AOV_ALBEDO_INSTANCE, ai.data()) != GLZ_OK) return false;
+  float thr[256];
+  glz_host_srgb8_thresholds(thr);
+  std::vector<uint8_t> img(n * 4);
+  for (size_t p = 0; p < n; ++p) {
+    for (int c = 0; c < 3; ++c) img[4 * p + c] = (uint8_t)((nd[4 * p + c] * 0.5f + 0.5f) * 255.0f + 0.5f);
+    img[4 * p + 3] = 255;
+    depth[p] = nd[4 * p + 3];
+  }
+  if (glz_save_image((prefix + ".normal.png").c_str(), img.data(), w, h) != GLZ_OK) return false;
+  for (size_t p = 0; p < n; ++p)
+    for (int c = 0; c < 3; ++c) {
+      const float v = ai[4 * p + c];
+      int q = 0;
+      while (q < 255 && v >= thr[q + 1]) ++q;   // the quantiser of read_rgba8: #{k in 1..255 : v >= T_k}
+      img[4 * p + c] = (uint8_t)q;
+    }
+  if (glz_save_image((prefix + ".albedo.png").c_str(), img.data(), w, h) != GLZ_OK) return false;
+  FILE* f = fopen((prefix + ".depth.bin").c_str(), "wb");
+  if (!f) return false;
+  const bool ok = fwrite(depth.data(), sizeof(float), n, f) == n;
+  fclose(f);
+  return ok;
+}
+
 struct Progress {
   size_t done = 0, total = 0;
   std::string msg;
@@ -69,6 +99,8 @@ void usage(const char* argv0) {
           "      --devices <A,B,..>        render on several GPUs (64x64 tiles sharded over them, RCCL reduce onto the first)\n"
           "      --texture-lod <MODE>      [default: off] [possible values: off, cones, aniso] (off = level 0, what the reference's stages sample)\n"
           "      --hdr-out <FILE.pfm>      also write the float radiance image\n"
+          "      --denoise                 save the denoised image (edge-avoiding a-trous filter guided by the first-hit buffers); --hdr-out then writes the denoised floats\n"
+          "      --aov-out <PREFIX>        also write the first-hit feature buffers: PREFIX.normal.png (n / 2 + 1/2), PREFIX.albedo.png (sRGB), PREFIX.depth.bin (little-endian f32 rows, inf = miss)\n"
           "      --report                  print a JSON timing report on stdout\n",
           argv0);
 }
@@ -76,13 +108,13 @@ void usage(const char* argv0) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string input, output, resolution = "1920x1080", integrator = "pt", hdr_out, texture_lod = "off";
+  std::string input, output, resolution = "1920x1080", integrator = "pt", hdr_out, texture_lod = "off", aov_out;
   size_t spp = 256;
   uint64_t seed = 0;
   uint32_t depth = 6;
   int device = -1;
   std::vector<int> devices;
-  bool report = false;
+  bool report = false, denoise = false;
   std::vector<std::string> positional;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -114,6 +146,8 @@ int main(int argc, char** argv) {
     }
     else if (a == "--texture-lod") texture_lod = value("--texture-lod");
     else if (a == "--hdr-out") hdr_out = value("--hdr-out");
+    else if (a == "--aov-out") aov_out = value("--aov-out");
+    else if (a == "--denoise") denoise = true;
     else if (a == "--report") report = true;
     else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
     else if (!a.empty() && a[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); usage(argv[0]); return 2; }
@@ -201,6 +235,14 @@ int main(int argc, char** argv) {
   const auto r1 = std::chrono::steady_clock::now();
   const double render_ms = std::chrono::duration<double, std::milli>(r1 - r0).count();
   fprintf(stderr, "\r%sDone (%.0f ms)%60s\n", pb.msg.c_str(), render_ms, "");
+  std::vector<float> denoised;
+  if (denoise) {
+    denoised.resize((size_t)width * height * 4);
+    if (glz_renderer_read_denoised(renderer, denoised.data(), image.data()) != GLZ_OK) {
+      fprintf(stderr, "[ERROR] %s\n", glz_last_error());
+      return 1;
+    }
+  }
   int rc = 0;
   if (glz_save_image(output.c_str(), image.data(), (uint32_t)width, (uint32_t)height) != GLZ_OK) {
     fprintf(stderr, "[ERROR] Failed to save image: %s\n", output.c_str());
@@ -210,10 +252,15 @@ int main(int argc, char** argv) {
   }
   if (!hdr_out.empty()) {
     std::vector<float> hdr((size_t)width * height * 4);
-    if (glz_renderer_read_hdr(renderer, hdr.data()) != GLZ_OK || !write_pfm(hdr_out, hdr.data(), (uint32_t)width, (uint32_t)height)) {
+    if (denoise) hdr = denoised;   // .w = 1 where the pixel was ever updated: write_pfm's division leaves the values as they are
+    if ((!denoise && glz_renderer_read_hdr(renderer, hdr.data()) != GLZ_OK) || !write_pfm(hdr_out, hdr.data(), (uint32_t)width, (uint32_t)height)) {
       fprintf(stderr, "[ERROR] Failed to save the HDR image: %s\n", hdr_out.c_str());
       rc = 1;
     }
+  }
+  if (!aov_out.empty() && !write_aovs(renderer, aov_out, (uint32_t)width, (uint32_t)height)) {
+    fprintf(stderr, "[ERROR] Failed to save the feature buffers: %s\n", aov_out.c_str());
+    rc = 1;
   }
   if (report) {
     glz_render_stats st{};

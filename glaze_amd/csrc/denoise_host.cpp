@@ -1,0 +1,53 @@
+// glz_host_denoise: the filter of glz_denoise_params (denoise.h) on the host cores, no device -- the reference the device kernels are
+// compared with bit for bit.  Rows are dealt to a few threads; pixels of a pass do not interact, so the result does not depend on them.
+#include <algorithm>
+#include <thread>
+#include <vector>
+
+#include "denoise.h"
+
+namespace glz {
+namespace post {
+
+namespace {
+template <class F>
+void for_rows(uint32_t h, uint32_t w, F f) {
+  const uint32_t hw = std::thread::hardware_concurrency();
+  const uint32_t want = (uint64_t)w * h < 65536u ? 1u : std::min<uint32_t>(std::min<uint32_t>(hw ? hw : 1u, 16u), h);
+  if (want <= 1u) {
+    for (uint32_t y = 0; y < h; ++y) f(y);
+    return;
+  }
+  std::vector<std::thread> pool;
+  for (uint32_t t = 0; t < want; ++t)
+    pool.emplace_back([=] {
+      for (uint32_t y = t; y < h; y += want) f(y);
+    });
+  for (auto& th : pool) th.join();
+}
+}  // namespace
+
+void host_denoise(uint32_t w, uint32_t h, const float4* result, const float4* aov0, const float4* aov1, const glz_denoise_params& P, float4* out) {
+  const size_t n = (size_t)w * h;
+  std::vector<float4> ping(n), pong(P.iterations > 1u ? n : 0);
+  for_rows(h, w, [&](uint32_t y) {
+    for (size_t p = (size_t)y * w; p < (size_t)(y + 1) * w; ++p) ping[p] = demodulate(result[p], aov1[p], P.eps_albedo);
+  });
+  const float4* src = ping.data();
+  for (uint32_t k = 0; k < P.iterations; ++k) {
+    const bool last = k + 1 == P.iterations;
+    float4* dst = last ? out : (src == ping.data() ? pong.data() : ping.data());
+    for_rows(h, w, [&](uint32_t y) {
+      for (uint32_t x = 0; x < w; ++x) {
+        float4 v = atrous_pixel(src, aov0, w, h, x, y, k, P);
+        const size_t p = (size_t)y * w + x;
+        if (last) v = remodulate(v, aov1[p], P.eps_albedo);
+        dst[p] = v;
+      }
+    });
+    src = dst;
+  }
+}
+
+}  // namespace post
+}  // namespace glz

@@ -1231,6 +1231,25 @@ __device__ __forceinline__ void flush_tex_tallies(unsigned long long* dst, const
 __device__ __forceinline__ uint32_t wave_index() { return blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); }
 __device__ __forceinline__ uint32_t wave_count() { return gridDim.x * (kBlock / 64); }
 
+// host side of the same geometry, for every kernel built on trace_wave / trace_wave_tl (kernels_render.hip, kernels_post.hip)
+// Persistent tracers: the grid is exactly what is resident at once (CUs x blocks per CU from the occupancy query, at
+// most 8), and never more waves than there are 64-ray groups.  A block that had to wait for a slot would serialise
+// behind a whole persistent block (cdna_hip_programming.md section 1: size persistent grids by residency).
+template <class Kernel>
+static inline dim3 persistent_grid(Kernel kernel, uint32_t n_rays) {
+  int dev = 0, cus = 256, per_cu = 8;
+  if (hipGetDevice(&dev) == hipSuccess) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+  }
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+  per_cu = std::min(per_cu, 8);
+  if (const char* cap = getenv("GLAZE_TRACE_BLOCKS_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(cap)));   // tuning: leave room for another chain's k_shade
+  // (splitting the resident blocks between concurrent chains measured slower: a chain's blocks fill in as another's retire)
+  const uint32_t resident = (uint32_t)cus * (uint32_t)per_cu;
+  return dim3(std::max<uint32_t>(1u, std::min<uint32_t>((n_rays + kBlock - 1) / kBlock, resident)));
+}
+
 // ---------------------------------------------------------------------------------------------
 // closest-hit phase of k_trace: path_trace.rgen:143-169
 // ---------------------------------------------------------------------------------------------

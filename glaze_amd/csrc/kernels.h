@@ -1,9 +1,10 @@
-// Host-callable launchers of the HIP kernels (kernels_build.hip, kernels_render.hip).
+// Host-callable launchers of the HIP kernels (kernels_build.hip, kernels_render.hip, kernels_path.hip, kernels_post.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device/types.h"
+#include "glaze_abi.h"
 #include "device_buffer.h"
 
 namespace glz {
@@ -158,6 +159,22 @@ hipError_t launch_pack_tiles(hipStream_t st, uint32_t n_chain_pixels, uint32_t n
 // result (out32) -> RGBA8 sRGB, full-frame row-major (the blit of raytracer.rs:576-584)
 // thresholds: 256 floats, [k] = smallest linear value that encodes to k (host::srgb8_thresholds); [0] = 0
 hipError_t launch_tonemap(hipStream_t st, uint32_t n_pixels, const float4* result_frame, const float* thresholds, uchar4* out);
+
+// ---- post (kernels_post.hip): first-hit feature buffers and the a-trous denoiser ------------------------
+// The first-hit pass: one centre ray per pixel of the FULL frame (a.map: rank 0, world 1; a.frame: scene_size and camera_persp; a.cam;
+// a.st.overflow / overflow_depth: one spill slot per lane of `blocks` blocks, from first_hit_grid_blocks with the device current).
+// `hit` (t, u, v, leaf bits) and `inst` are private row-major buffers of width * height entries; the attribute kernel turns them into
+// aov0 = (normal.xyz, depth) and aov1 = (albedo.rgb, instance bits), row-major.
+uint32_t first_hit_grid_blocks(uint32_t n_rays);
+hipError_t launch_first_hit(hipStream_t st, const LaunchArgs& a, uint32_t blocks, float4* hit, uint32_t* inst);
+hipError_t launch_first_hit_attributes(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, float4* aov0, float4* aov1);
+// camera_ray() of every pixel at one sub-pixel offset, row-major, 3 floats each
+hipError_t launch_camera_rays(hipStream_t st, const LaunchArgs& a, float off_x, float off_y, float* origins3, float* dirs3);
+// The filter of glz_denoise_params on row-major device frames: demodulation, `iterations` a-trous passes (one launch each, ping-pong),
+// re-modulation in the last pass's store.  ping, pong and out are three different frames of w * h pixels; out may not alias an input.
+// marks (timing, may be null): 2 + iterations events recorded before the demodulation, after it and after every pass.
+hipError_t launch_denoise(hipStream_t st, uint32_t w, uint32_t h, const glz_denoise_params& params, const float4* result, const float4* aov0,
+                          const float4* aov1, float4* ping, float4* pong, float4* out, hipEvent_t* marks = nullptr);
 
 // debug / parity hooks
 hipError_t launch_debug_closest(hipStream_t st, const DeviceScene& scene, const float* origins, const float* dirs, uint32_t n, float tmin,

@@ -528,24 +528,7 @@ __global__ void __launch_bounds__(kBlock) k_debug_detmath(int fn, const float* _
 // launchers
 // ---------------------------------------------------------------------------------------------
 static inline dim3 grid_for(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
-// Persistent tracers: the grid is exactly what is resident at once (CUs x blocks per CU from the occupancy query, at
-// most 8), and never more waves than there are 64-ray groups.  A block that had to wait for a slot would serialise
-// behind a whole persistent block (cdna_hip_programming.md section 1: size persistent grids by residency).
-template <class Kernel>
-static dim3 persistent_grid(Kernel kernel, uint32_t n_rays) {
-  int dev = 0, cus = 256, per_cu = 8;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-  }
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-  per_cu = std::min(per_cu, 8);
-  if (const char* cap = getenv("GLAZE_TRACE_BLOCKS_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(cap)));   // tuning: leave room for another chain's k_shade
-  // (splitting the resident blocks between concurrent chains measured slower: a chain's blocks fill in as another's retire)
-  const uint32_t resident = (uint32_t)cus * (uint32_t)per_cu;
-  return dim3(std::max<uint32_t>(1u, std::min<uint32_t>((n_rays + kBlock - 1) / kBlock, resident)));
-}
-
+// (persistent_grid: device/wavefront.h, shared with the first-hit pass of kernels_post.hip)
 // Blocks of k_trace's persistent grid for a chain of n_local_pixels (the renderer asks once per allocation and passes the
 // answer to every launch_trace; needs the device current).  Up to one closest-hit and one shadow ray per pixel: a small
 // tile share still gets a wave per 64-ray group of either kind (fewer, longer-lived waves -- 2 to 4 groups per wave --

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <thread>
 
+#include "denoise.h"
 #include "rccl_dl.h"
 
 namespace glz {
@@ -183,6 +184,7 @@ Renderer* Renderer::create(Instance* inst, std::shared_ptr<Scene> scene, uint32_
   }
   r->w_ = w;
   r->h_ = h;
+  r->denoise_ = post::denoise_defaults();
   r->camera_ = scene->data.camera;
   r->exposure_ = scene->data.meta.exposure;
   host::push_constants(r->camera_, w, h, r->cam_.camera2world, r->cam_.screen2camera);
@@ -714,6 +716,7 @@ bool Renderer::change_resolution(uint32_t w, uint32_t h, Error& err) {
   if (!wait_idle(err)) return false;
   w_ = w;
   h_ = h;
+  release_post();
   if (!allocate(err)) return false;
   const bool want_frame = !loopback_ && exchange_ == kExchangeReduce;
   if (!forward([=](Peer& p, Error& e) {
@@ -1026,6 +1029,159 @@ bool Renderer::read_rgba8(uint8_t* out, Error& err) {
   if (!hip_ok(launch_tonemap(st, w_ * h_, frame_tmp_.ptr, oetf_thresholds_.ptr, rgba8_.ptr), "k_tonemap", err)) return false;
   if (!hip_ok(hipMemcpyAsync(out, rgba8_.ptr, (size_t)w_ * h_ * 4, hipMemcpyDeviceToHost, st), "read rgba8", err)) return false;
   return hip_ok(hipStreamSynchronize(st), "read rgba8", err);
+}
+
+// ---- post: first-hit feature buffers and the denoiser ------------------------------------------------------------------------------
+void Renderer::release_post() {
+  fh_hit_.release(); fh_inst_.release(); fh_overflow_.release();
+  aov0_.release(); aov1_.release();
+  dn_ping_.release(); dn_pong_.release(); dn_out_.release();
+}
+
+// what the post kernels read of LaunchArgs: the scene, the camera, the frame's size and projection, a FULL-frame tile map
+void Renderer::post_args(LaunchArgs& a) const {
+  memset(&a, 0, sizeof(a));
+  a.scene = scene_->dev;
+  a.cam = cam_;
+  a.frame.scene_size[0] = (float)w_;
+  a.frame.scene_size[1] = (float)h_;
+  a.frame.camera_persp = camera_.type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
+  TileMap& m = a.map;
+  m.width = w_;
+  m.height = h_;
+  m.tiles_x = (w_ + kTile - 1) / kTile;
+  m.tiles_y = (h_ + kTile - 1) / kTile;
+  m.rank = 0;
+  m.world = 1;
+  m.n_local_tiles = m.tiles_x * m.tiles_y;
+  m.n_local_pixels = m.n_local_tiles * kTile * kTile;
+}
+
+bool Renderer::first_hit_pass(Error& err, hipEvent_t* marks) {
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
+  LaunchArgs a;
+  post_args(a);
+  const size_t n = (size_t)w_ * h_;
+  if (!fh_hit_.ptr || !fh_inst_.ptr || !aov0_.ptr || !aov1_.ptr || fh_hit_.count != n) {
+    if (!hip_ok(fh_hit_.alloc(n), "alloc first-hit records", err) || !hip_ok(fh_inst_.alloc(n), "alloc first-hit records", err) ||
+        !hip_ok(aov0_.alloc(n), "alloc feature buffers", err) || !hip_ok(aov1_.alloc(n), "alloc feature buffers", err)) {
+      release_post();   // all or nothing: the next request starts over instead of meeting a buffer that is not there
+      return false;
+    }
+  }
+  const uint32_t blocks = first_hit_grid_blocks(a.map.n_local_pixels);
+  const size_t spill = (size_t)blocks * kTraceBlock * scene_->stack_overflow_depth;   // the scene may have changed since the last pass
+  if (fh_overflow_.ptr == nullptr || fh_overflow_.count != spill)
+    if (!hip_ok(fh_overflow_.alloc(spill), "alloc traversal spill", err)) {
+      fh_overflow_.release();
+      return false;
+    }
+  a.st.overflow = fh_overflow_.ptr;
+  a.st.overflow_depth = scene_->stack_overflow_depth;
+  hipStream_t st = inst_->stream;
+  // every record starts as a miss: the attribute kernel follows a record's leaf index into the scene's arrays
+  if (!hip_ok(hipMemsetAsync(fh_hit_.ptr, 0xFF, sizeof(float4) * n, st), "clear first-hit records", err)) return false;
+  if (marks) (void)hipEventRecord(marks[0], st);
+  if (!hip_ok(launch_first_hit(st, a, blocks, fh_hit_.ptr, fh_inst_.ptr), "k_first_hit", err)) return false;
+  if (marks) (void)hipEventRecord(marks[1], st);
+  if (!hip_ok(launch_first_hit_attributes(st, a, fh_hit_.ptr, fh_inst_.ptr, aov0_.ptr, aov1_.ptr), "k_first_hit_attributes", err)) return false;
+  if (marks) (void)hipEventRecord(marks[2], st);
+  return true;
+}
+
+bool Renderer::read_aov(int which, float* out, Error& err) {
+  if (which != GLZ_AOV_NORMAL_DEPTH && which != GLZ_AOV_ALBEDO_INSTANCE) {
+    err.code = GLZ_E_ARG;
+    err.msg = "unknown feature buffer (GLZ_AOV_NORMAL_DEPTH or GLZ_AOV_ALBEDO_INSTANCE)";
+    return false;
+  }
+  if (!first_hit_pass(err)) return false;
+  hipStream_t st = inst_->stream;
+  const float4* src = which == GLZ_AOV_NORMAL_DEPTH ? aov0_.ptr : aov1_.ptr;
+  if (!hip_ok(hipMemcpyAsync(out, src, sizeof(float4) * (size_t)w_ * h_, hipMemcpyDeviceToHost, st), "read feature buffer", err)) return false;
+  return hip_ok(hipStreamSynchronize(st), "read feature buffer", err);
+}
+
+bool Renderer::camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err) {
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
+  LaunchArgs a;
+  post_args(a);
+  const size_t n = (size_t)w_ * h_ * 3;
+  DeviceBuffer<float> d_o, d_d;
+  if (!hip_ok(d_o.alloc(n), "alloc", err) || !hip_ok(d_d.alloc(n), "alloc", err)) return false;
+  hipStream_t st = inst_->stream;
+  if (!hip_ok(launch_camera_rays(st, a, off_x, off_y, d_o.ptr, d_d.ptr), "k_camera_rays", err)) return false;
+  if (!hip_ok(hipMemcpyAsync(origins3, d_o.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, st), "camera rays", err)) return false;
+  if (!hip_ok(hipMemcpyAsync(dirs3, d_d.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, st), "camera rays", err)) return false;
+  return hip_ok(hipStreamSynchronize(st), "camera rays", err);
+}
+
+bool Renderer::ensure_denoise_frames(Error& err) {
+  const size_t n = (size_t)w_ * h_;
+  if (dn_ping_.ptr && dn_pong_.ptr && dn_out_.ptr && dn_out_.count == n) return true;
+  if (hip_ok(dn_ping_.alloc(n), "alloc denoiser frames", err) && hip_ok(dn_pong_.alloc(n), "alloc denoiser frames", err) &&
+      hip_ok(dn_out_.alloc(n), "alloc denoiser frames", err))
+    return true;
+  dn_ping_.release(); dn_pong_.release(); dn_out_.release();   // all or nothing
+  return false;
+}
+
+bool Renderer::time_post(float ms[GLZ_POST_TIMING_SLOTS], Error& err) {
+  if (world_ > 1 && peers_.empty()) {
+    err.code = GLZ_E_ARG;
+    err.msg = "time_post: under set_partition(world > 1) the frame is not in this process";
+    return false;
+  }
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
+  if (!gather(true, frame_tmp_.ptr, err) || !ensure_denoise_frames(err)) return false;
+  hipEvent_t ev[GLZ_POST_TIMING_SLOTS + 2] = {};   // three around the first-hit pass's kernels, 2 + iterations around the filter's
+  bool ok = true;
+  for (auto& e : ev) ok = ok && hip_ok(hipEventCreate(&e), "hipEventCreate", err);
+  hipStream_t st = chains_[0]->stream;
+  ok = ok && first_hit_pass(err, ev);
+  ok = ok && hip_ok(launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr, ev + 3), "k_atrous", err);
+  ok = ok && hip_ok(hipStreamSynchronize(st), "time_post", err);
+  if (ok) {
+    for (int i = 0; i < GLZ_POST_TIMING_SLOTS; ++i) ms[i] = 0.0f;
+    (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]);
+    (void)hipEventElapsedTime(&ms[1], ev[1], ev[2]);
+    for (uint32_t i = 0; i < 1u + denoise_.iterations; ++i) (void)hipEventElapsedTime(&ms[2 + i], ev[3 + i], ev[4 + i]);
+  }
+  for (auto& e : ev)
+    if (e) (void)hipEventDestroy(e);
+  return ok;
+}
+
+bool Renderer::set_denoise(const glz_denoise_params* p, Error& err) {
+  const glz_denoise_params v = p ? *p : post::denoise_defaults();
+  if (!post::denoise_params_valid(v)) {
+    err.code = GLZ_E_ARG;
+    err.msg = post::kDenoiseParamsMessage;
+    return false;
+  }
+  denoise_ = v;
+  return true;
+}
+
+bool Renderer::read_denoised(float* rgba32f, uint8_t* rgba8, Error& err) {
+  if (world_ > 1 && peers_.empty()) {   // (with set_devices the partition is over this process's own devices: gather() brings their tiles)
+    err.code = GLZ_E_ARG;
+    err.msg = "read_denoised: under set_partition(world > 1) the frame is not in this process";
+    return false;
+  }
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
+  if (!gather(true, frame_tmp_.ptr, err)) return false;   // flushes the pending shadow rays, brings the other devices' tiles
+  if (!first_hit_pass(err)) return false;
+  const size_t n = (size_t)w_ * h_;
+  if (!ensure_denoise_frames(err)) return false;
+  hipStream_t st = chains_[0]->stream;   // = the instance stream the first-hit pass ran on
+  if (!hip_ok(launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr), "k_atrous", err)) return false;
+  if (rgba32f && !hip_ok(hipMemcpyAsync(rgba32f, dn_out_.ptr, sizeof(float4) * n, hipMemcpyDeviceToHost, st), "read denoised", err)) return false;
+  if (rgba8) {
+    if (!hip_ok(launch_tonemap(st, w_ * h_, dn_out_.ptr, oetf_thresholds_.ptr, rgba8_.ptr), "k_tonemap", err)) return false;
+    if (!hip_ok(hipMemcpyAsync(rgba8, rgba8_.ptr, n * 4, hipMemcpyDeviceToHost, st), "read denoised", err)) return false;
+  }
+  return hip_ok(hipStreamSynchronize(st), "read denoised", err);
 }
 
 bool Renderer::set_texture_lod(int mode, Error& err) {

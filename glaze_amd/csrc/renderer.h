@@ -31,6 +31,13 @@ class Renderer {
   bool step(uint32_t n, Error& err);
   bool read_rgba8(uint8_t* out, Error& err);
   bool read_frame(bool result, float* out, Error& err);
+  // ---- post: first-hit feature buffers and the denoiser (kernels_post.hip) ----
+  bool read_aov(int which, float* out, Error& err);                   // runs the first-hit pass; GLZ_AOV_*
+  bool set_denoise(const glz_denoise_params* p, Error& err);          // null = defaults; accumulation goes on
+  bool read_denoised(float* rgba32f, uint8_t* rgba8, Error& err);     // gather + first-hit pass + filter; either output may be null
+  bool camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err);   // camera_ray() of every pixel, on the device
+  // one run of the post stages between device events: ms of {first-hit trace, attributes, demodulation, pass 0 .. iterations - 1} (unused = 0)
+  bool time_post(float ms[GLZ_POST_TIMING_SLOTS], Error& err);
 
   bool set_texture_lod(int mode, Error& err);   // 0 = level 0 (the reference), 1 = ray cones; restarts
   bool set_seed(uint64_t s);
@@ -159,6 +166,16 @@ class Renderer {
   bool configure_peer(Renderer& p, Error& err) const;
   bool reduce_peers(bool result, float4* dst, Error& err);
   bool step_local(uint32_t n, Error& err);
+
+  // The first-hit pass over the FULL frame on this device, whatever the partition: centre rays, closest hits, attributes -> aov0_ / aov1_.
+  // Recomputed on every request, never cached; its buffers are private (allocated on first use, released by change_resolution).
+  bool first_hit_pass(Error& err, hipEvent_t* marks = nullptr);   // marks: 3 events around the two kernels
+  void post_args(LaunchArgs& a) const;
+  void release_post();
+  bool ensure_denoise_frames(Error& err);
+  DeviceBuffer<float4> fh_hit_, aov0_, aov1_, dn_ping_, dn_pong_, dn_out_;
+  DeviceBuffer<uint32_t> fh_inst_, fh_overflow_;
+  glz_denoise_params denoise_;   // set in create()
 
   DeviceBuffer<float4> frame_tmp_;
   DeviceBuffer<uchar4> rgba8_;

@@ -366,6 +366,64 @@ int glz_renderer_launch_constants(glz_renderer*, uint32_t launch, uint32_t* seed
 /* camera push constants: camera2world then screen2camera, column-major (raytracer.rs:1098-1120) */
 int glz_renderer_push_constants(glz_renderer*, float out32[32]);
 
+/* ---- post: first-hit feature buffers and the edge-aware denoiser (build-defined; the reference has neither) ------------- */
+/* The first-hit pass: ONE primary ray per pixel through the pixel centre (offset 0.5, 0.5; no jitter, no seed), tmin 1e-4, for the whole
+ * frame on the renderer's own device whatever the tile partition, chains or set_devices say.  It is recomputed on every request (it
+ * costs less than one render launch) and touches neither the accumulators nor the path state.  Two row-major RGBA32F planes:
+ *   GLZ_AOV_NORMAL_DEPTH     xyz = the shading normal the shading code builds its frame from (interpolated, normal-mapped, object ->
+ *                            world), normalised and turned towards the camera; (0,0,0) for a miss or a degenerate normal.
+ *                            w = the hit distance t, +inf for a miss.
+ *   GLZ_AOV_ALBEDO_INSTANCE  rgb = texture(diffuse).rgb * diffuse_mul for Lambert and Uber materials (texture level 0 always), (1,1,1)
+ *                            for the other families and for a miss.  w = the bits of the hit's RTInstance index, 0xFFFFFFFF for a miss. */
+#define GLZ_AOV_NORMAL_DEPTH 0
+#define GLZ_AOV_ALBEDO_INSTANCE 1
+int glz_renderer_read_aov(glz_renderer*, int which, float* rgba32f_out);   /* runs the first-hit pass; W*H*4 floats, row-major */
+
+/* The denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on the albedo-demodulated result image, guided by the two
+ * planes above.  Its edge-stopping functions are rational (1 / (1 + r^2)) so that the whole filter is + - * /, comparisons and selects:
+ * host and device compute it bit for bit alike.  THE SPECIFICATION (every operation in binary32, no contraction, in this order;
+ * "finite(v)" = |v| <= FLT_MAX, false for NaN; c = result, n / z = normal / depth, a = albedo):
+ *   A(p)   = per channel a(p) > eps_albedo ? a(p) : eps_albedo
+ *   i_0(p) = c(p).rgb / A(p);  every frame's .w = c(p).w
+ *   hit(p) = finite(z(p))
+ *   g(p)   = (gx, gy), for a hit p and per axis: f = z(next) - z(p), b = z(p) - z(previous), each usable if the neighbour is inside the
+ *            image and the difference is finite; both usable: |b| < |f| ? b : f; one usable: that one; none: 0
+ *   pass k = 0 .. iterations - 1, s = 2^k, sigma_k = sigma_color * (1 / 2^k), S = sigma_k * sigma_k:
+ *     P = i_k(p) if all three channels are finite, else (0,0,0);   NP = (P.x*P.x + P.y*P.y) + P.z*P.z
+ *     taps q = p + s (dx, dy), dy = -2 .. 2 outer, dx = -2 .. 2 inner, summed in that order; a tap is DROPPED when q is outside the
+ *     image, when a channel of Q = i_k(q) is not finite, when hit(q) != hit(p), or when its weight W is not > 0:
+ *       centre tap (dx = dy = 0): W = 1
+ *       D = Q - P;  d2 = (D.x*D.x + D.y*D.y) + D.z*D.z;  NQ = (Q.x*Q.x + Q.y*Q.y) + Q.z*Q.z
+ *       cn = S * ((NP + NQ) + eps_color);  cd = cn + d2                      (the colour weight Wc = cn / cd = 1 / (1 + d2 / cn))
+ *       misses: W = cn / cd.   hits:
+ *         Wn = (n(p).x*n(q).x + n(p).y*n(q).y) + n(p).z*n(q).z, 0 unless > 0, then squared normal_power_log2 times
+ *         ax = float(s*dx) * gx;  ay = float(s*dy) * gy
+ *         a  = (z(q) - z(p)) - (ax + ay);  b = sigma_depth * ((|ax| + |ay|) + eps_depth * z(p))
+ *         zn = b*b;  zd = zn + a*a                                           (the depth weight Wz = zn / zd = 1 / (1 + (a/b)^2))
+ *         W  = (Wn * (cn * zn)) / (cd * zd)                                  (Wn Wz Wc as ONE quotient)
+ *       hw = (h[dy] * h[dx]) * W with h = (1/16, 1/4, 3/8, 1/4, 1/16);   sw += hw;   sum.c += hw * Q.c per channel
+ *     i_{k+1}(p) = sum / sw per channel if sw > 0, else i_k(p) unchanged (a non-finite pixel without a usable neighbour stays as it is)
+ *   out(p).rgb = i_K(p) * A(p)
+ * Defaults (glz_renderer_set_denoise(r, NULL)): iterations 5, sigma_color 4, sigma_depth 1, normal_power_log2 6 (cos^64), eps_albedo
+ * 1/256, eps_depth 1e-3, eps_color 1e-8.  GLZ_E_ARG: iterations outside 1 .. GLZ_DENOISE_MAX_ITERATIONS, a sigma that is not finite and
+ * positive, normal_power_log2 above GLZ_DENOISE_MAX_NORMAL_POWER_LOG2 (31: after 31 squarings every float below 1 has become 0, more
+ * would only be a longer loop in every tap).  The epsilons are taken as they are.  Beware of eps_depth = 0: where the depth plane is
+ * constant around a hit (a wall that faces the camera) b is 0, W is 0 / 0 and every tap but the centre is dropped -- the filter is the
+ * identity there.  Products of very large depths and radiances can overflow cd * zd with the same effect. */
+#define GLZ_DENOISE_MAX_ITERATIONS 8
+#define GLZ_DENOISE_MAX_NORMAL_POWER_LOG2 31
+typedef struct glz_denoise_params {
+  uint32_t iterations;
+  float sigma_color, sigma_depth;
+  uint32_t normal_power_log2;
+  float eps_albedo, eps_depth, eps_color;
+} glz_denoise_params;
+int glz_renderer_set_denoise(glz_renderer*, const glz_denoise_params*);   /* NULL = defaults; does not restart accumulation */
+/* Either output may be NULL.  Flushes pending shadow rays and gathers like glz_renderer_read_result (chains, devices of set_devices),
+ * runs the first-hit pass and the filter on the renderer's own device; rgba8_out is the filtered image through the sRGB quantiser of
+ * glz_renderer_read_rgba8.  GLZ_E_ARG under glz_renderer_set_partition(world > 1): the frame is not in this process. */
+int glz_renderer_read_denoised(glz_renderer*, float* rgba32f_out, uint8_t* rgba8_out);
+
 /* Multi-GPU (one process per GPU): this renderer owns the 64x64-pixel tiles t with
  * t % world == rank; other pixels stay zero.  The exchange of the HDR accumulator itself is done
  * by the caller (RCCL through torch.distributed or rccl directly) on the device buffers below. */
@@ -495,6 +553,17 @@ int glz_debug_sample_texture(glz_scene*, uint32_t texture, const float* uv2, con
 /* include/glz_detmath.h on the device: fn 0 sin, 1 cos, 2 acos, 3 atan2(y, x), 4 log2, 5 floor of n values (y only for atan2) */
 int glz_debug_detmath(glz_instance*, int fn, const float* x, const float* y, float* out, uint64_t n);
 
+/* The device filter of glz_denoise_params on host arrays (w*h*4 floats each, row-major): upload, kernels, read back.  params NULL = defaults. */
+int glz_debug_denoise(glz_instance*, uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1,
+                      const glz_denoise_params*, float* out);
+/* One run of the post stages of this renderer between device events (hipEvent on the instance stream), in ms: ms_out[0] the first-hit
+ * trace kernel, [1] its attribute kernel, [2] the demodulation, [3 + k] a-trous pass k (entries past the configured iterations are 0).
+ * Gathers the result image first, like glz_renderer_read_denoised; nothing is read back. */
+#define GLZ_POST_TIMING_SLOTS (3 + GLZ_DENOISE_MAX_ITERATIONS)
+int glz_debug_post_timing(glz_renderer*, float ms_out[GLZ_POST_TIMING_SLOTS]);
+/* camera_ray() of every pixel at one sub-pixel offset, on the device: W*H*3 floats each, row-major (the first-hit pass uses 0.5, 0.5) */
+int glz_debug_camera_rays(glz_renderer*, float off_x, float off_y, float* origins3, float* dirs3);
+
 /* First contact with RCCL on this machine: a one-rank communicator on the instance's device (ncclCommInitAll), one
  * ncclReduce(sum, float) of n_floats values on the instance's stream, result compared bit for bit with the input, communicator
  * destroyed.  version_out (may be NULL) receives ncclGetVersion(). */
@@ -521,6 +590,10 @@ int glz_host_srgb8_thresholds(float thresholds_out[256]);
  * byte count of that level (0 past the last), writes up to cap bytes */
 int64_t glz_host_mip_level(const glz_texture* texture, uint32_t level, uint8_t* out, int64_t cap, uint32_t* width, uint32_t* height);
 int glz_host_build_sah(uint32_t n, const float* box_lo, const float* box_hi, int32_t* children_out, int32_t* parent_out);
+/* the filter of glz_denoise_params on the host, no device: the reference the device kernels are compared with bit for bit.
+ * result / aov0 / aov1 / out: w*h*4 floats, row-major; out must not overlap an input.  params NULL = defaults. */
+int glz_host_denoise(uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1,
+                     const glz_denoise_params*, float* out);
 /* the host rule of glz_debug_instance_boxes on a scene description (no device): a mesh's box is the min / max of its vertices here.
  * One box per instance that names an existing mesh, in instance order; returns their count (both outputs NULL: the count alone). */
 int64_t glz_host_instance_boxes(const glz_scene_desc* desc, uint64_t budget, float* lo4, float* hi4);

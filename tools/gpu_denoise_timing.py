@@ -1,0 +1,50 @@
+"""Cost of the post stages on the bench atrium at 1920 x 1080: device-event medians over REPS runs of the first-hit pass (trace and
+attribute kernels), the demodulation and each a-trous pass (glz_debug_post_timing), next to one render launch of the same build in the
+same process and to a pass's byte floor (32 bytes read + 16 written per pixel at the 6.3 TB/s the microarchitecture notes give as
+achievable).  The render launch's total is a host clock around 64 launches that end in wait_idle; its k_trace / k_shade split is the
+renderer's own device-event statistics.  Run from the repository root on the GPU; writes nothing but its output."""
+import statistics
+import sys
+import time
+
+sys.path.insert(0, ".")
+import glaze_amd
+from glaze_amd.scenes import atrium_scene
+
+W, H, REPS = 1920, 1080, 64
+FLOOR_US = W * H * 48 / 6.3e12 * 1e6
+
+inst = glaze_amd.RayTraceInstance.new()
+if inst is None:
+    raise SystemExit("no gfx950 device")
+r = glaze_amd.RayTraceRenderer.new(inst, glaze_amd.RayTraceScene.from_desc(inst, atrium_scene()), W, H)
+r.set_depth(8)
+r.step(24)
+r.wait_idle()
+s0 = r.stats()
+t = time.time()
+r.step(64)
+r.wait_idle()
+launch_ms = (time.time() - t) / 64 * 1e3
+s1 = r.stats()
+print("render launch: %.3f ms (k_trace %.3f, k_shade %.3f)" % (launch_ms, (s1.trace_closest_ms - s0.trace_closest_ms) / 64, (s1.shade_ms - s0.shade_ms) / 64))
+for _ in range(8):
+    r.debug_post_timing()                     # warm-up: code objects, first-use allocations
+runs = [r.debug_post_timing() for _ in range(REPS)]
+
+
+def med(f):
+    return statistics.median(f(x) for x in runs) * 1e3
+
+
+trace, attr, demod = med(lambda x: x["first_hit_trace"]), med(lambda x: x["first_hit_attributes"]), med(lambda x: x["demodulate"])
+print("first-hit pass: trace %.1f us + attributes %.1f us = %.1f us (%.1f %% of a render launch)" % (trace, attr, trace + attr, (trace + attr) / launch_ms / 10))
+print("demodulation: %.1f us" % demod)
+passes = [med(lambda x, k=k: x["passes"][k]) for k in range(5)]
+for k, p in enumerate(passes):
+    print("a-trous pass %d (stride %2d): %.1f us = %.1f x the %.1f us byte floor" % (k, 1 << k, p, p / FLOOR_US, FLOOR_US))
+print("five passes: %.1f us (floor %.1f us); with the demodulation %.1f us" % (sum(passes), 5 * FLOOR_US, sum(passes) + demod))
+t = time.time()
+for _ in range(16):
+    r.read_denoised()
+print("read_denoised() end to end, frame read back included: %.2f ms" % ((time.time() - t) / 16 * 1e3))
