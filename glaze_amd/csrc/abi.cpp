@@ -18,6 +18,7 @@
 #include "rccl_dl.h"
 #include "renderer.h"
 #include "scene.h"
+#include "tile_map.h"
 
 using namespace glz;
 
@@ -434,7 +435,8 @@ int glz_debug_camera_rays(glz_renderer* h, float off_x, float off_y, float* orig
 int glz_renderer_launch_constants(glz_renderer* h, uint32_t launch, uint32_t* seed, float off[2]) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!seed || !off) return fail(GLZ_E_ARG, "output is null");
-  GLZ_RET(h->r->launch_constants(launch, seed, off));
+  if (!h->r->launch_constants(launch, seed, off)) return fail(GLZ_E_IO, "WorkScheduler::peek disagrees with next()");
+  return GLZ_OK;
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_push_constants(glz_renderer* h, float out[32]) {
@@ -900,20 +902,7 @@ int glz_debug_rccl_selftest(glz_instance* inst, uint64_t n, int* version_out) {
 int glz_host_launch_constants(uint64_t seed, uint32_t launch, uint32_t* seed_out, float offset[2]) {
   GLZ_GUARD_BEGIN
   if (!seed_out || !offset) return fail(GLZ_E_ARG, "output is null");
-  host::SeedStream rng(seed);
-  host::WorkScheduler ws;
-  uint32_t s = 0;
-  float o[2] = {0, 0};
-  for (uint32_t i = 0; i <= launch; ++i) {
-    s = rng.next();
-    float ahead[2] = {-1.0f, -1.0f};
-    ws.peek(ahead);   // what the launch before this one was told about it (FrameData::next_pixel_offset): must be what next() now hands out
-    ws.next(o);
-    if (memcmp(ahead, o, sizeof(o)) != 0) return fail(GLZ_E_IO, "WorkScheduler::peek disagrees with next()");
-  }
-  *seed_out = s;
-  offset[0] = o[0];
-  offset[1] = o[1];
+  if (!host::launch_constants(seed, launch, seed_out, offset)) return fail(GLZ_E_IO, "WorkScheduler::peek disagrees with next()");
   return GLZ_OK;
   GLZ_GUARD_END(GLZ_E_IO)
 }
@@ -924,20 +913,20 @@ int glz_host_push_constants(const glz_camera* camera, uint32_t width, uint32_t h
 }
 int glz_host_tile_owner(uint32_t width, uint32_t height, uint32_t world, uint16_t* owner_out) {
   if (!owner_out || world == 0 || world > 65535) return fail(GLZ_E_ARG, "bad argument");
-  const uint32_t tiles_x = (width + 63) / 64;
+  const TileMap m = make_tile_map(width, height, 0, world);
   for (uint32_t y = 0; y < height; ++y)
-    for (uint32_t x = 0; x < width; ++x) owner_out[(size_t)y * width + x] = (uint16_t)(((y / 64) * tiles_x + x / 64) % world);
+    for (uint32_t x = 0; x < width; ++x) owner_out[(size_t)y * width + x] = (uint16_t)tile_owner(tile_of_pixel(m, x, y), world);
   return GLZ_OK;
 }
 int glz_host_chain_owner(uint32_t width, uint32_t height, uint32_t rank, uint32_t world, uint32_t chains, uint16_t* owner_out) {
   if (world == 0 || rank >= world || chains > 16 || !width || !height) return fail(GLZ_E_ARG, "bad argument");
   const uint32_t S = Renderer::chains_for(width, height, rank, world, chains);
-  const uint32_t tiles_x = (width + 63) / 64;
+  const TileMap m = make_tile_map(width, height, rank, world);
   if (owner_out)
     for (uint32_t y = 0; y < height; ++y)
       for (uint32_t x = 0; x < width; ++x) {
-        const uint32_t t = (y / 64) * tiles_x + x / 64;
-        owner_out[(size_t)y * width + x] = t % world == rank ? (uint16_t)((t % (world * S)) / world) : (uint16_t)0xFFFF;
+        const uint32_t t = tile_of_pixel(m, x, y);
+        owner_out[(size_t)y * width + x] = tile_owner(t, world) == rank ? (uint16_t)tile_chain(t, world, S) : (uint16_t)0xFFFF;
       }
   return (int)S;
 }

@@ -255,6 +255,27 @@ class WorkScheduler {
   std::vector<Area> current_, next_;
 };
 
+// Seed and pixel offset of launch `launch` (0-based) of a frame that starts from `seed`: the streams replayed from their start, as
+// reset_buffers() leaves them.  False when peek() ever disagrees with the next() that follows it -- what the launch before was told
+// about this one (FrameData::next_pixel_offset) must be what next() now hands out.
+inline bool launch_constants(uint64_t seed, uint32_t launch, uint32_t* seed_out, float offset[2]) {
+  SeedStream rng(seed);
+  WorkScheduler ws;
+  uint32_t s = 0;
+  float o[2] = {0, 0};
+  for (uint32_t i = 0; i <= launch; ++i) {
+    s = rng.next();
+    float ahead[2] = {-1.0f, -1.0f};
+    ws.peek(ahead);
+    ws.next(o);
+    if (memcmp(ahead, o, sizeof(o)) != 0) return false;
+  }
+  *seed_out = s;
+  offset[0] = o[0];
+  offset[1] = o[1];
+  return true;
+}
+
 // Thresholds of the 8-bit sRGB quantiser (the R8G8B8A8_SRGB blit of raytracer.rs:576-584 [ext]): a linear value c encodes to
 // q = #{k in 1..255 : c >= thr[k]}, thr[k] = (float) EOTF((k - 0.5) / 255) -- round(255 * OETF(c)) without evaluating pow()
 // per pixel, so the device and any other implementation of this rule agree on every byte.  thr[0] = 0.

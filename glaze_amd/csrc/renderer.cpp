@@ -76,6 +76,16 @@ struct Renderer::Peer {
   DeviceBuffer<float4> frame;
   hipEvent_t sent = nullptr;   // peer-copy exchange: this device's tiles have left (recorded on its stream, awaited by device 0's)
   Worker worker;
+  size_t n_pixels() const;                    // tile slots of all its chains
+  const float4* packed(bool result) const;    // where its packed tiles travel from
+  // a copy of `src` built on this device, in the shape the root's scene HAS (builder, pair leaves, flattened or two levels), not what
+  // the environment of this thread would choose
+  std::shared_ptr<Scene> replica_of(const Scene& src, const Instance& src_inst, Error& e) {
+    inst->copy_build_options(src_inst);
+    if (src.info.as_levels) inst->as_levels = (int)src.info.as_levels;
+    SceneData copy = src.data;
+    return std::shared_ptr<Scene>(Scene::create(inst.get(), std::move(copy), e));
+  }
   ~Peer() {
     worker.stop();
     if (inst) (void)hipSetDevice(inst->device);
@@ -99,7 +109,14 @@ struct Renderer::Pending {
   }
 };
 
-// f(Peer&, Error&) -> bool on every peer's thread; f is copied into the tasks, whatever it refers to must outlive join_all()
+// The calling thread is back on this renderer's device when the scope ends, however it ends: for code that visits the peers' devices
+// on the calling thread (the exchange, set_devices).  Tasks posted to the peers run on their own threads and never move the caller.
+struct Renderer::OnOwnDevice {
+  const Renderer& r;
+  ~OnOwnDevice() { (void)hipSetDevice(r.inst_->device); }
+};
+
+// f(Peer&, size_t index, Error&) -> bool on every peer's thread; f is copied into the tasks, whatever it refers to must outlive join_all()
 template <class F>
 void Renderer::post_all(F f, Pending& p) {
   p.errs.assign(peers_.size(), Error());
@@ -111,7 +128,7 @@ void Renderer::post_all(F f, Pending& p) {
     char* ok = &p.ok[i];
     peer->worker.post([=] {
       try {
-        *ok = f(*peer, *e) ? 1 : 0;
+        *ok = f(*peer, i, *e) ? 1 : 0;
       } catch (const std::exception& ex) {
         e->code = GLZ_E_IO;
         e->msg = ex.what();
@@ -135,16 +152,28 @@ bool Renderer::join_all(Pending& p, Error& err) {
     }
   return true;
 }
-template <class F>
-bool Renderer::forward(F f, Error& err) {
-  if (peers_.empty()) return true;
+// The peers do f on their threads while this thread does g(err) -> bool; then the join.  The first error wins, this thread's before a
+// peer's.  The one place that answers for the calling thread's device: it is inst_->device afterwards, success or failure.
+template <class F, class G>
+bool Renderer::with_peers(F f, G g, Error& err) {
+  if (peers_.empty()) return g(err);
+  OnOwnDevice back{*this};
   Pending p;
   post_all(f, p);
-  return join_all(p, err);
+  bool ok = g(err);
+  Error pe;
+  if (!join_all(p, pe) && ok) {
+    err = pe;
+    ok = false;
+  }
+  return ok;
+}
+template <class F>
+bool Renderer::forward(F f, Error& err) {
+  return with_peers(f, [](Error&) { return true; }, err);
 }
 
 namespace {
-constexpr uint32_t kTile = 64;
 // Kernel boundaries are timed with HIP events on one launch of every `stride` (Renderer::event_stride), at a pseudo-random place
 // inside each group of `stride` consecutive launches, and counted `stride` times.  A fixed place would beat against the path depth:
 // launch i traces bounce i mod depth of most pixels and the bounces differ in cost.
@@ -185,9 +214,9 @@ Renderer* Renderer::create(Instance* inst, std::shared_ptr<Scene> scene, uint32_
   r->w_ = w;
   r->h_ = h;
   r->denoise_ = post::denoise_defaults();
-  r->camera_ = scene->data.camera;
-  r->exposure_ = scene->data.meta.exposure;
-  host::push_constants(r->camera_, w, h, r->cam_.camera2world, r->cam_.screen2camera);
+  r->cfg_.camera = scene->data.camera;
+  r->cfg_.exposure = scene->data.meta.exposure;
+  host::push_constants(r->cfg_.camera, w, h, r->cfg_.cam.camera2world, r->cfg_.cam.screen2camera);
   if (!r->allocate(err)) return nullptr;
   return r.release();
 }
@@ -230,15 +259,15 @@ Renderer::~Renderer() {
 // onto GPU_MAX_HW_QUEUES (4) hardware queues and the fourth chain shares one (0.154 -> 0.252 ms for a 1/8 share; with 8 queues
 // 0.19 ms, tools/gpu_chain_sweep.py) -- and no number of chains goes below one chain's own step, which lasts as long as its slowest wave.
 uint32_t Renderer::chains_for(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t wanted) {
-  const uint32_t tiles_x = (w + kTile - 1) / kTile, tiles_y = (h + kTile - 1) / kTile, tiles = tiles_x * tiles_y;
-  const uint32_t local_tiles = tiles > rank ? (tiles - rank + world - 1) / world : 0;
-  const uint64_t pixels = (uint64_t)local_tiles * kTile * kTile;
+  const TileMap m = make_tile_map(w, h, rank, world);
+  const uint32_t local_tiles = m.n_local_tiles;
+  const uint64_t pixels = m.n_local_pixels;
   uint32_t want = wanted;
   if (want == 0) want = pixels >= 1000000u ? 1u : (pixels >= 400000u ? 2u : 3u);
   if (want > local_tiles) want = local_tiles;
   return want ? want : 1u;
 }
-uint32_t Renderer::pick_chains() const { return path_mode_ ? 1u : chains_for(w_, h_, rank_, world_, chains_wanted_); }
+uint32_t Renderer::pick_chains() const { return path_mode_ ? 1u : chains_for(w_, h_, rank_, world_, cfg_.chains_wanted); }
 
 // Automatic launch mode: a device runs its launches as k_path batches only when every 64-pixel group it owns gets a resident wave of its
 // own (4 096 on an MI355X at k_path's four waves per SIMD: up to 262 144 pixels) -- with more groups than waves some waves carry two
@@ -246,10 +275,9 @@ uint32_t Renderer::pick_chains() const { return path_mode_ ? 1u : chains_for(w_,
 bool Renderer::allocate(Error& err) {
   release_chains();
   {
-    const uint32_t tiles_x = (w_ + kTile - 1) / kTile, tiles_y = (h_ + kTile - 1) / kTile, tiles = tiles_x * tiles_y;
-    const uint64_t pixels = (uint64_t)(tiles > rank_ ? (tiles - rank_ + world_ - 1) / world_ : 0) * kTile * kTile;
+    const uint64_t pixels = make_tile_map(w_, h_, rank_, world_).n_local_pixels;
     bool fits = false;
-    if (launch_mode_ == 0 && pixels > 0 && pixels <= (1u << 22) && scene_->dev.two_level == 0) {
+    if (cfg_.launch_mode == 0 && pixels > 0 && pixels <= (1u << 22) && scene_->dev.two_level == 0) {
       const uint32_t blocks = (uint32_t)((pixels / 64 + kTraceBlock / 64 - 1) / (kTraceBlock / 64));
       const uint32_t resident = path_resident_blocks(scene_->dev);
       // ... and the launch loop is what pays: where launches are short (a scene of a few thousand triangles: the 512 x 512 cube runs
@@ -258,13 +286,13 @@ bool Renderer::allocate(Error& err) {
       // kernels since round 4 (1080p / 8: 0.129 against 0.134 ms; tools/gpu_partition_timing.py, tools/gpu_batch_length.py).
       fits = resident >= blocks && (scene_->info.n_world_triangles < 4096 || (uint64_t)blocks * 5u <= (uint64_t)resident * 4u);
     }
-    path_mode_ = scene_->dev.two_level == 0 && (launch_mode_ == 2 || fits);
+    path_mode_ = scene_->dev.two_level == 0 && (cfg_.launch_mode == 2 || fits);
     // The two-kernel mode's traversal walks the hierarchy's 8-wide nodes only on request (set_node_width(8), GLAZE_NODE_WIDTH=8): built to
     // shorten a small tile share's chain of dependent node fetches (17.3 against 24.9 visits per sample), measured slower at every share --
     // a 1080p / 8 share 0.140 - 0.145 against 0.1285 ms per launch, / 16 0.098 against 0.097, the full frame 0.93 against 0.79
     // (profiles/r05_wide_nodes.txt): twice the boxes and up to seven conditional pushes make a visit 1.9 x the instructions, and one wave
     // issues them one after the other, so the shorter chain takes as long.
-    wide8_ = scene_->dev.two_level == 0 && scene_->dev.bvh_nodes8 != nullptr && node_width_ == 8;
+    wide8_ = scene_->dev.two_level == 0 && scene_->dev.bvh_nodes8 != nullptr && cfg_.node_width == 8;
   }
   const uint32_t S = pick_chains();
   const uint32_t od = scene_->stack_overflow_depth;
@@ -276,16 +304,7 @@ bool Renderer::allocate(Error& err) {
       if (!hip_ok(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate", err)) return false;
       c->own_stream = true;
     }
-    TileMap& m = c->map;
-    m.width = w_;
-    m.height = h_;
-    m.tiles_x = (w_ + kTile - 1) / kTile;
-    m.tiles_y = (h_ + kTile - 1) / kTile;
-    m.rank = rank_ + s * world_;   // chain s of S = the finer partition (rank + s * world, world * S)
-    m.world = world_ * S;
-    const uint32_t tiles = m.tiles_x * m.tiles_y;
-    m.n_local_tiles = tiles > m.rank ? (tiles - m.rank + m.world - 1) / m.world : 0;
-    m.n_local_pixels = m.n_local_tiles * kTile * kTile;
+    const TileMap& m = c->map = make_chain_map(w_, h_, rank_, world_, s, S);
     const size_t n = m.n_local_pixels;
     // shadow-ray queue: 8 shards of ceil(blocks/8)*256 entries (kernels_render.hip, queue_capacity)
     const size_t n_queue = (((n + 255) / 256 + 7) / 8) * 256 * 8;
@@ -339,7 +358,7 @@ bool Renderer::reset_buffers(Error& err) {
   if (!hip_ok(hipMemsetAsync(counters_.ptr, 0, sizeof(TraceCounters), chains_[0]->stream), "clear counters", err)) return false;
   if (chains_.size() > 1 && !hip_ok(hipStreamSynchronize(chains_[0]->stream), "clear counters", err)) return false;   // the other chains add to them too
   sched_.rewind();
-  rng_.reseed(seed_);   // build-defined: a restart replays the same seed stream (the reference keeps drawing from entropy)
+  rng_.reseed(cfg_.seed);   // build-defined: a restart replays the same seed stream (the reference keeps drawing from entropy)
   launches_ = 0;
   request_new_frame_ = false;
   return true;
@@ -363,8 +382,8 @@ void Renderer::fill_args(const Chain& c, LaunchArgs& a) const {
   a.st.overflow_depth = scene_->stack_overflow_depth;
   a.st.path_cost = c.path_cost.ptr;
   a.map = c.map;
-  a.cam = cam_;
-  a.counters = counting_ ? counters_.ptr : nullptr;
+  a.cam = cfg_.cam;
+  a.counters = cfg_.counting ? counters_.ptr : nullptr;
   a.do_closest = a.do_shadow = 0;
   a.shade_set = c.pending_set ^ 1u;
   a.shadow_exposure = c.pending_exposure;
@@ -393,7 +412,7 @@ bool Renderer::acquire_events(Chain& c, EventSet& ev, Error& err) {
   if (c.free_events.empty()) {
     if (c.pending_events.size() >= 64) {
       // resolve and recycle the pending sets (without the flush get_stats would do)
-      if (!hip_ok(hipEventSynchronize(c.pending_events.back().e[c.pending_events.back().kind ? 1 : 2]), "hipEventSynchronize", err)) return false;
+      if (!hip_ok(hipEventSynchronize(last_event(c.pending_events.back())), "hipEventSynchronize", err)) return false;
       resolve_events(c);
     }
     if (c.free_events.empty()) {
@@ -410,6 +429,31 @@ bool Renderer::acquire_events(Chain& c, EventSet& ev, Error& err) {
   return true;
 }
 
+// The events around one timed stretch of a chain's stream -- the only place the launch path records events.  begin() with on = false
+// makes the other calls no-ops.  On this thread's per-launch path: plain members, nothing allocated but a chain's first event sets.
+struct Renderer::Timed {
+  Chain& c;
+  EventSet ev{};
+  bool on = false;
+  bool begin(Renderer& r, bool timed, int kind, uint32_t weight, Error& err) {
+    on = timed;
+    if (!on) return true;
+    if (!r.acquire_events(c, ev, err)) return false;
+    ev.kind = kind;
+    ev.weight = weight;
+    (void)hipEventRecord(ev.e[0], c.stream);
+    return true;
+  }
+  void mark() {   // kind 0: between k_trace and k_shade
+    if (on) (void)hipEventRecord(ev.e[1], c.stream);
+  }
+  void end() {
+    if (!on) return;
+    (void)hipEventRecord(last_event(ev), c.stream);
+    c.pending_events.push_back(ev);
+  }
+};
+
 // Stand-alone shadow pass for the rays the last launch queued: run before anything observes the accumulators.
 bool Renderer::flush_shadows(Chain& c, Error& err) {
   if (!c.shadow_pending) return true;
@@ -417,48 +461,43 @@ bool Renderer::flush_shadows(Chain& c, Error& err) {
   fill_args(c, a);
   memset(&a.frame, 0, sizeof(a.frame));
   a.do_shadow = 1;
-  EventSet ev{};
-  if (profile_kernels_) {
-    if (!acquire_events(c, ev, err)) return false;
-    ev.kind = 1;
-    (void)hipEventRecord(ev.e[0], c.stream);
-  }
-  if (!hip_ok(launch_trace(c.stream, a, counting_ ? c.grid_counting : (wide8() ? c.grid8 : c.grid), wide8()), "k_trace (shadow pass)", err)) return false;
-  if (profile_kernels_) {
-    (void)hipEventRecord(ev.e[1], c.stream);
-    c.pending_events.push_back(ev);
-  }
+  Timed t{c};
+  if (!t.begin(*this, cfg_.profile_kernels, 1, 0, err)) return false;
+  if (!hip_ok(launch_trace(c.stream, a, trace_grid(c), wide8()), "k_trace (shadow pass)", err)) return false;
+  t.end();
   c.shadow_pending = false;
   return true;
 }
 
-// what all launches of a frame share in RTFrameData (raytracer.rs:369-613); seed, pixel offset and exposure are per launch
+// What one_launch and path_batch start with: a pending restart, then what all launches of a frame share in RTFrameData
+// (raytracer.rs:369-613); seed, pixel offset and exposure are per launch
 bool Renderer::launch_constants_common(FrameData& fd, Error& err) {
+  if (request_new_frame_ && !reset_buffers(err)) return false;
   memset(&fd, 0, sizeof(fd));
   fd.lights_no = scene_->lights_no;
   fd.scene_radius = scene_->data.meta.scene_radius;
   fd.scene_size[0] = (float)w_;
   fd.scene_size[1] = (float)h_;
   for (int k = 0; k < 3; ++k) fd.scene_centre[k] = scene_->data.meta.scene_centre[k];
-  fd.camera_persp = camera_.type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
-  fd.pt_steps = pt_steps_;
-  fd.direct_only = integrator_ == GLZ_DIRECT ? 1u : 0u;
-  fd.lod_mode = (uint32_t)lod_mode_;
-  if (lod_mode_ != 0) {
+  fd.camera_persp = cfg_.camera.type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
+  fd.pt_steps = cfg_.pt_steps;
+  fd.direct_only = cfg_.integrator == GLZ_DIRECT ? 1u : 0u;
+  fd.lod_mode = (uint32_t)cfg_.lod_mode;
+  if (cfg_.lod_mode != 0) {
     // one pixel of the image plane at unit distance (perspective: the cone's spread) or in world units (orthographic: the
     // cone's constant width), from the projection's vertical scale: screen2camera[1][1] = -tan(fovy / 2) or -scale
-    const float pixel = 2.0f * fabsf(cam_.screen2camera[5]) / (float)h_;
-    const bool persp = camera_.type == GLZ_CAMERA_PERSPECTIVE;
+    const float pixel = 2.0f * fabsf(cfg_.cam.screen2camera[5]) / (float)h_;
+    const bool persp = cfg_.camera.type == GLZ_CAMERA_PERSPECTIVE;
     fd.cone_spread = persp ? pixel : 0.0f;
     fd.cone_width0 = persp ? 0.0f : pixel;
     if (!scene_->mips_ready() && !scene_->ensure_mips(err)) return false;
   }
+  fd.pregen = fd.direct_only ? 0u : 1u;
   return true;
 }
 
 // draw_frame (raytracer.rs:369-613): one path segment per pixel
 bool Renderer::one_launch(Error& err) {
-  if (request_new_frame_ && !reset_buffers(err)) return false;
   FrameData fd;
   if (!launch_constants_common(fd, err)) return false;
   fd.seed = rng_.next();                  // rng.gen::<u32>(), raytracer.rs:487
@@ -466,8 +505,7 @@ bool Renderer::one_launch(Error& err) {
   // the launch after this one, for the paths that end in this one (shade_pixel): anything that could make the next launch differ from
   // what is assumed here -- a new camera, resolution, scene, integrator, a restart -- resets the path state before it runs (reset_buffers)
   sched_.peek(fd.next_pixel_offset);
-  fd.pregen = fd.direct_only ? 0u : 1u;
-  fd.exposure = exposure_;
+  fd.exposure = cfg_.exposure;
   ++launches_;
   if (fd.lights_no == 0) return true;   // the raygen shader returns before touching anything (path_trace.rgen:137-141)
   for (auto& cp : chains_) {
@@ -479,31 +517,21 @@ bool Renderer::one_launch(Error& err) {
     a.do_closest = 1;
     a.do_shadow = c.shadow_pending ? 1u : 0u;   // the previous launch's shadow rays ride in this launch's traversal kernel
     const uint64_t stride = event_stride();
-    const bool timed = profile_kernels_ && timed_launch(launches_, stride);
-    EventSet ev{};
-    if (timed) {
-      if (!acquire_events(c, ev, err)) return false;
-      ev.kind = 0;
-      ev.weight = (uint32_t)stride;
-      (void)hipEventRecord(ev.e[0], st);
-    }
-    if (!hip_ok(launch_trace(st, a, counting_ ? c.grid_counting : (wide8() ? c.grid8 : c.grid), wide8()), "k_trace", err)) return false;
-    if (timed) (void)hipEventRecord(ev.e[1], st);
+    Timed t{c};
+    if (!t.begin(*this, cfg_.profile_kernels && timed_launch(launches_, stride), 0, (uint32_t)stride, err)) return false;
+    if (!hip_ok(launch_trace(st, a, trace_grid(c), wide8()), "k_trace", err)) return false;
+    t.mark();
     if (!hip_ok(launch_shade(st, a), "k_shade", err)) return false;
-    if (timed) {
-      (void)hipEventRecord(ev.e[2], st);
-      c.pending_events.push_back(ev);
-    }
+    t.end();
     c.shadow_pending = true;
     c.pending_set = a.shade_set;
-    c.pending_exposure = exposure_;
+    c.pending_exposure = cfg_.exposure;
   }
   return true;
 }
 
 // n <= kPathMaxLaunches launches of draw_frame in ONE kernel (k_path): the same per-launch constants, in the same order
 bool Renderer::path_batch(uint32_t n, Error& err) {
-  if (request_new_frame_ && !reset_buffers(err)) return false;
   FrameData fd;
   if (!launch_constants_common(fd, err)) return false;
   PathBatch b;
@@ -513,10 +541,9 @@ bool Renderer::path_batch(uint32_t n, Error& err) {
   for (uint32_t i = 0; i < n; ++i) {
     b.seed[i] = rng_.next();           // rng.gen::<u32>(), raytracer.rs:487
     sched_.next(b.offset[i]);          // WorkScheduler::next(), :489
-    b.exposure[i] = exposure_;
+    b.exposure[i] = cfg_.exposure;
   }
   sched_.peek(b.offset[n]);            // the launch after the batch (FrameData::next_pixel_offset of its last launch)
-  fd.pregen = fd.direct_only ? 0u : 1u;
   launches_ += n;
   if (fd.lights_no == 0) return true;   // the raygen shader returns before touching anything (path_trace.rgen:137-141)
   Chain& c = *chains_[0];
@@ -525,19 +552,12 @@ bool Renderer::path_batch(uint32_t n, Error& err) {
   fill_args(c, a);
   a.frame = fd;
   a.counters = nullptr;
-  EventSet ev{};
-  if (profile_kernels_) {
-    if (!acquire_events(c, ev, err)) return false;
-    ev.kind = 2;
-    (void)hipEventRecord(ev.e[0], c.stream);
-  }
+  Timed t{c};
+  if (!t.begin(*this, cfg_.profile_kernels, 2, 0, err)) return false;
   // the cost accumulator this batch adds to starts empty (the kernel reads the other one, which the batch before filled)
   if (!hip_ok(hipMemsetAsync(c.path_cost.ptr + 4u * b.parity, 0, 16, c.stream), "clear path cost accumulator", err)) return false;
   if (!hip_ok(launch_path(c.stream, a, b, c.grid_path), "k_path", err)) return false;
-  if (profile_kernels_) {
-    (void)hipEventRecord(ev.e[1], c.stream);
-    c.pending_events.push_back(ev);
-  }
+  t.end();
   return true;   // nothing is pending: the kernel ends with the shadow rays of its last launch
 }
 
@@ -555,18 +575,23 @@ bool Renderer::run_launches(uint32_t n, Error& err) {
   return true;
 }
 
+// A change of something the buffers are sized by: everything enqueued drains, `apply` changes the setting, this device reallocates,
+// then every peer does the same through `on_peer`.
+template <class A, class F>
+bool Renderer::resize(A apply, F on_peer, Error& err) {
+  if (!wait_idle(err)) return false;
+  apply();
+  if (!allocate(err)) return false;
+  return forward(on_peer, err);
+}
+
 bool Renderer::set_launch_mode(int mode, Error& err) {
   if (mode < 0 || mode > 2) {
     err.code = GLZ_E_ARG;
     err.msg = "launch mode must be 0 (automatic), 1 (two kernels per launch) or 2 (per-wave launch loop)";
     return false;
   }
-  if (!wait_idle(err)) return false;
-  launch_mode_ = mode;
-  if (!allocate(err)) return false;
-  const bool ok = forward([=](Peer& p, Error& e) { return p.r->set_launch_mode(mode, e); }, err);
-  (void)hipSetDevice(inst_->device);
-  return ok;
+  return resize([&] { cfg_.launch_mode = mode; }, [=](Peer& p, size_t, Error& e) { return p.r->set_launch_mode(mode, e); }, err);
 }
 
 bool Renderer::set_node_width(int width, Error& err) {
@@ -575,12 +600,7 @@ bool Renderer::set_node_width(int width, Error& err) {
     err.msg = "node width must be 0 (automatic), 4 or 8";
     return false;
   }
-  if (!wait_idle(err)) return false;
-  node_width_ = width;
-  if (!allocate(err)) return false;
-  const bool ok = forward([=](Peer& p, Error& e) { return p.r->set_node_width(width, e); }, err);
-  (void)hipSetDevice(inst_->device);
-  return ok;
+  return resize([&] { cfg_.node_width = width; }, [=](Peer& p, size_t, Error& e) { return p.r->set_node_width(width, e); }, err);
 }
 
 bool Renderer::get_stats(glz_render_stats* out, Error& err) {
@@ -590,7 +610,7 @@ bool Renderer::get_stats(glz_render_stats* out, Error& err) {
     Chain& c = *cp;
     if (!flush_shadows(c, err)) return false;   // the counters and timings of the last launch's shadow rays belong to it
     if (!c.pending_events.empty()) {
-      if (!hip_ok(hipEventSynchronize(c.pending_events.back().e[c.pending_events.back().kind ? 1 : 2]), "hipEventSynchronize", err)) return false;
+      if (!hip_ok(hipEventSynchronize(last_event(c.pending_events.back())), "hipEventSynchronize", err)) return false;
       resolve_events(c);
     }
     trace_ms += c.trace_ms;
@@ -602,14 +622,7 @@ bool Renderer::get_stats(glz_render_stats* out, Error& err) {
   const double inv = chains_.empty() ? 0.0 : 1.0 / (double)chains_.size();
   memset(out, 0, sizeof(*out));
   out->launches = launches_;
-  uint64_t owned = 0;
-  const uint32_t tiles_x = (w_ + kTile - 1) / kTile, tiles_y = (h_ + kTile - 1) / kTile;
-  for (uint32_t t = rank_; t < tiles_x * tiles_y; t += world_) {
-    const uint32_t tx = t % tiles_x, ty = t / tiles_x;
-    const uint32_t tw = std::min(kTile, w_ - tx * kTile), th = std::min(kTile, h_ - ty * kTile);
-    owned += (uint64_t)tw * th;
-  }
-  out->samples = owned * launches_;
+  out->samples = owned_pixels(make_tile_map(w_, h_, rank_, world_)) * launches_;
   out->trace_closest_ms = trace_ms * inv;
   out->shade_ms = shade_ms * inv;
   out->trace_shadow_ms = flush_ms * inv;
@@ -637,18 +650,7 @@ bool Renderer::get_stats(glz_render_stats* out, Error& err) {
   if (!peers_.empty()) {
     std::vector<glz_render_stats> ps(peers_.size());
     glz_render_stats* base = ps.data();
-    Peer* first = peers_[0].get();
-    (void)first;
-    Pending pend;
-    std::vector<Peer*> order;
-    for (auto& p : peers_) order.push_back(p.get());
-    const std::vector<Peer*>* ord = &order;
-    post_all([=](Peer& p, Error& e) {
-      size_t i = 0;
-      while ((*ord)[i] != &p) ++i;
-      return p.r->get_stats(base + i, e);
-    }, pend);
-    if (!join_all(pend, err)) return false;
+    if (!forward([=](Peer& p, size_t i, Error& e) { return p.r->get_stats(base + i, e); }, err)) return false;
     for (const glz_render_stats& q : ps) {
       out->samples += q.samples;
       out->trace_closest_ms = std::max(out->trace_closest_ms, q.trace_closest_ms);
@@ -664,14 +666,13 @@ bool Renderer::get_stats(glz_render_stats* out, Error& err) {
       out->light_samples += q.light_samples; out->sky_samples += q.sky_samples;
     }
     out->render_ms = out->trace_closest_ms + out->shade_ms + out->trace_shadow_ms + out->other_ms;
-    (void)hipSetDevice(inst_->device);
   }
   return true;
 }
 
 void Renderer::enable_counters(int flags) {
-  counting_ = (flags & 1) != 0;
-  profile_kernels_ = (flags & 2) != 0;
+  cfg_.counting = (flags & 1) != 0;
+  cfg_.profile_kernels = (flags & 2) != 0;
   for (auto& p : peers_) p->r->enable_counters(flags);
 }
 
@@ -681,15 +682,15 @@ bool Renderer::set_integrator(int integrator, Error& err) {
     err.msg = "unknown integrator";
     return false;
   }
-  if (integrator != integrator_) {   // raytracer.rs:197
-    integrator_ = integrator;
+  if (integrator != cfg_.integrator) {   // raytracer.rs:197
+    cfg_.integrator = integrator;
     request_new_frame_ = true;
   }
-  return forward([=](Peer& p, Error& e) { return p.r->set_integrator(integrator, e); }, err);
+  return forward([=](Peer& p, size_t, Error& e) { return p.r->set_integrator(integrator, e); }, err);
 }
 
 bool Renderer::set_exposure(float e) {
-  if (e >= 0.0f) exposure_ = e;   // raytracer.rs:186-193: no restart
+  if (e >= 0.0f) cfg_.exposure = e;   // raytracer.rs:186-193: no restart
   for (auto& p : peers_) p->r->set_exposure(e);
   return true;
 }
@@ -700,11 +701,11 @@ bool Renderer::update_camera(const glz_camera& c, Error& err) {
     err.msg = "unknown camera type";
     return false;
   }
-  camera_ = c;
-  host::push_constants(camera_, w_, h_, cam_.camera2world, cam_.screen2camera);
+  cfg_.camera = c;
+  host::push_constants(cfg_.camera, w_, h_, cfg_.cam.camera2world, cfg_.cam.screen2camera);
   request_new_frame_ = true;
   const glz_camera cam = c;
-  return forward([=](Peer& p, Error& e) { return p.r->update_camera(cam, e); }, err);
+  return forward([=](Peer& p, size_t, Error& e) { return p.r->update_camera(cam, e); }, err);
 }
 
 bool Renderer::change_resolution(uint32_t w, uint32_t h, Error& err) {
@@ -713,19 +714,17 @@ bool Renderer::change_resolution(uint32_t w, uint32_t h, Error& err) {
     err.msg = "resolution must be non-zero";
     return false;
   }
-  if (!wait_idle(err)) return false;
-  w_ = w;
-  h_ = h;
-  release_post();
-  if (!allocate(err)) return false;
   const bool want_frame = !loopback_ && exchange_ == kExchangeReduce;
-  if (!forward([=](Peer& p, Error& e) {
+  if (!resize([&] {
+        w_ = w;
+        h_ = h;
+        release_post();
+      }, [=](Peer& p, size_t, Error& e) {
         if (!p.r->change_resolution(w, h, e)) return false;
         return !want_frame || hip_ok(p.frame.alloc((size_t)w * h), "alloc peer frame", e);
       }, err))
     return false;
-  (void)hipSetDevice(inst_->device);
-  return update_camera(camera_, err);   // raytracer.rs:297
+  return update_camera(cfg_.camera, err);   // raytracer.rs:297
 }
 
 bool Renderer::change_scene(std::shared_ptr<Scene> scene, Error& err) {
@@ -734,45 +733,44 @@ bool Renderer::change_scene(std::shared_ptr<Scene> scene, Error& err) {
     err.msg = "scene is null";
     return false;
   }
-  if (!wait_idle(err)) return false;
-  scene_ = scene;
-  exposure_ = scene->data.meta.exposure;
-  if (!allocate(err)) return false;
   // the other GPUs of this process get replicas of the new scene, in the shape (flattened / two levels) this device built
   const Scene* src = scene.get();
   const Instance* src_inst = scene->instance ? scene->instance : inst_;
-  if (!forward([=](Peer& p, Error& e) {
-        p.inst->copy_build_options(*src_inst);
-        if (src->info.as_levels) p.inst->as_levels = (int)src->info.as_levels;
-        SceneData copy = src->data;
-        std::shared_ptr<Scene> replica(Scene::create(p.inst.get(), std::move(copy), e));
+  if (!resize([&] {
+        scene_ = scene;
+        cfg_.exposure = scene->data.meta.exposure;
+      }, [=](Peer& p, size_t, Error& e) {
+        std::shared_ptr<Scene> replica = p.replica_of(*src, *src_inst, e);
         return replica && p.r->change_scene(replica, e);
       }, err))
     return false;
-  (void)hipSetDevice(inst_->device);
   return update_camera(scene->data.camera, err);   // raytracer.rs:246-247
+}
+
+// An update of the scene object in place, on this device: drained first; the buffers are reallocated only if the update changed what
+// allocate() sizes from the scene (the traversal spill's depth, whether there are 8-wide nodes); accumulation restarts.
+template <class U>
+bool Renderer::update_scene(U update, Error& err) {
+  if (!wait_idle(err)) return false;
+  const uint32_t od = scene_->stack_overflow_depth;
+  const bool wide8 = scene_->dev.bvh_nodes8 != nullptr;
+  if (!update()) return false;
+  if ((scene_->stack_overflow_depth != od || (scene_->dev.bvh_nodes8 != nullptr) != wide8) && !allocate(err)) return false;
+  request_new_frame_ = true;
+  return true;
 }
 
 bool Renderer::update_materials_and_lights(const glz_material* m, uint32_t nm, const glz_light* l, uint32_t nl, const glz_texture* t, uint32_t nt,
                                            Error& err) {
-  if (!wait_idle(err)) return false;
-  const uint32_t od = scene_->stack_overflow_depth;
-  if (!scene_->update_materials_and_lights(m, nm, l, nl, t, nt, err)) return false;
-  if (scene_->stack_overflow_depth != od && !allocate(err)) return false;
-  request_new_frame_ = true;   // raytracer.rs:325
-  return forward([=](Peer& p, Error& e) { return p.r->update_materials_and_lights(m, nm, l, nl, t, nt, e); }, err);
+  if (!update_scene([&] { return scene_->update_materials_and_lights(m, nm, l, nl, t, nt, err); }, err)) return false;   // raytracer.rs:325
+  return forward([=](Peer& p, size_t, Error& e) { return p.r->update_materials_and_lights(m, nm, l, nl, t, nt, e); }, err);
 }
 
 // Moves the instances: the scene's structure is rebuilt for the new transforms (the scene object changes, so every renderer that
 // shares it sees the move), accumulation restarts, and every other device of set_devices updates its replica the same way.
 bool Renderer::update_transforms(const glz_transform* t, uint32_t n, Error& err) {
-  if (!wait_idle(err)) return false;
-  const uint32_t od = scene_->stack_overflow_depth;
-  const bool wide8 = scene_->dev.bvh_nodes8 != nullptr;   // what allocate() sizes from the scene and an update can change
-  if (!scene_->update_transforms(t, n, err)) return false;
-  if ((scene_->stack_overflow_depth != od || (scene_->dev.bvh_nodes8 != nullptr) != wide8) && !allocate(err)) return false;
-  request_new_frame_ = true;
-  return forward([=](Peer& p, Error& e) { return p.r->update_transforms(t, n, e); }, err);
+  if (!update_scene([&] { return scene_->update_transforms(t, n, err); }, err)) return false;
+  return forward([=](Peer& p, size_t, Error& e) { return p.r->update_transforms(t, n, e); }, err);
 }
 
 // raytracer.rs:328-356.  The reference rebuilds descriptors, pipeline and SBT and leaves the accumulation alone; here the
@@ -780,25 +778,21 @@ bool Renderer::update_transforms(const glz_transform* t, uint32_t n, Error& err)
 bool Renderer::refresh_binded_textures(const glz_texture* t, uint32_t nt, Error& err) {
   if (!wait_idle(err)) return false;
   if (!scene_->refresh_textures(t, nt, err)) return false;
-  return forward([=](Peer& p, Error& e) { return p.r->refresh_binded_textures(t, nt, e); }, err);
+  return forward([=](Peer& p, size_t, Error& e) { return p.r->refresh_binded_textures(t, nt, e); }, err);
+}
+
+// this device's half of wait_idle: the pending shadow rays of every chain go out, then every chain's stream drains
+bool Renderer::wait_idle_local(const char* what, Error& err) {
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
+  for (auto& c : chains_)
+    if (!flush_shadows(*c, err)) return false;
+  for (auto& c : chains_)
+    if (!hip_ok(hipStreamSynchronize(c->stream), what, err)) return false;
+  return true;
 }
 
 bool Renderer::wait_idle(Error& err) {
-  Pending pend;
-  if (!peers_.empty()) post_all([](Peer& p, Error& e) { return p.r->wait_idle(e); }, pend);
-  bool ok = hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err);
-  for (auto& c : chains_)
-    if (ok && !flush_shadows(*c, err)) ok = false;
-  for (auto& c : chains_)
-    if (ok && !hip_ok(hipStreamSynchronize(c->stream), "wait_idle", err)) ok = false;
-  if (!peers_.empty()) {
-    Error pe;
-    if (!join_all(pend, pe) && ok) {
-      err = pe;
-      ok = false;
-    }
-  }
-  return ok;
+  return with_peers([](Peer& p, size_t, Error& e) { return p.r->wait_idle(e); }, [this](Error& e) { return wait_idle_local("wait_idle", e); }, err);
 }
 
 bool Renderer::restart() {
@@ -815,16 +809,7 @@ bool Renderer::step_local(uint32_t n, Error& err) {
 // Every device enqueues the same n launches (same seed stream, same jitter sequence) for its own tiles; the peers' host
 // threads work while this thread enqueues the local share.
 bool Renderer::step(uint32_t n, Error& err) {
-  if (peers_.empty()) return step_local(n, err);
-  Pending pend;
-  post_all([=](Peer& p, Error& e) { return p.r->step_local(n, e); }, pend);
-  bool ok = step_local(n, err);
-  Error pe;
-  if (!join_all(pend, pe) && ok) {
-    err = pe;
-    ok = false;
-  }
-  return ok;
+  return with_peers([=](Peer& p, size_t, Error& e) { return p.r->step_local(n, e); }, [=](Error& e) { return step_local(n, e); }, err);
 }
 
 // draw (raytracer.rs:615-687)
@@ -883,128 +868,133 @@ bool Renderer::gather(bool result, float4* dst, Error& err, bool zero_first) {
 // The tiles are disjoint, so both give the image of a one-GPU render bit for bit.  Loop-back mode (every "device" is this one;
 // tests): RCCL cannot put two ranks on one GPU, and there is nothing to move -- the peers scatter their tiles straight into `dst`.
 bool Renderer::reduce_peers(bool result, float4* dst, Error& err) {
+  if (!hip_ok(hipStreamSynchronize(chains_[0]->stream), "exchange: local frame", err)) return false;
+  OnOwnDevice back{*this};   // the exchanges visit the peers' devices on this thread
+  if (loopback_) return peers_gather(result, dst, err);
+  return exchange_ == kExchangeReduce ? exchange_reduce(result, dst, err) : exchange_packed(result, dst, err);
+}
+
+// every peer scatters its tiles into a full frame and waits for it: into `shared` (loop-back: one device, the root's frame, nothing
+// cleared) or, with shared == nullptr, into its own zero-padded p.frame
+bool Renderer::peers_gather(bool result, float4* shared, Error& err) {
+  return forward([=](Peer& p, size_t, Error& e) {
+    if (!hip_ok(hipSetDevice(p.inst->device), "hipSetDevice", e)) return false;
+    if (!p.r->gather(result, shared ? shared : p.frame.ptr, e, shared == nullptr)) return false;
+    return hip_ok(hipStreamSynchronize(p.inst->stream), "exchange: peer frame", e);
+  }, err);
+}
+
+namespace {
+bool rccl_ok(const Rccl& nc, ncclResult_t r, const char* what, Error& err) {
+  if (r == ncclSuccess) return true;
+  if (err.code == 0 || err.msg.empty()) {   // the first failure is the one reported
+    err.code = GLZ_E_DEVICE;
+    err.msg = std::string(what) + ": " + nc.GetErrorString(r);
+  }
+  return false;
+}
+}  // namespace
+const Rccl* Renderer::rccl(Error& err) const {
+  std::string why;
+  const Rccl* nc = Rccl::get(why);
+  if (nc && comms_.size() == peers_.size() + 1) return nc;
+  err.code = GLZ_E_DEVICE;
+  err.msg = nc ? "RCCL communicators are missing" : why;
+  return nullptr;
+}
+
+// the end of an RCCL exchange: the peers' streams first (their buffers are free again), the root's last -- everything has arrived when
+// it is idle.  Without the peers (peer copy): the root's stream waited for every peer's copy before it scattered.
+bool Renderer::finish_exchange(bool peers_too, Error& err) {
+  if (peers_too)
+    for (auto& p : peers_) {
+      if (!hip_ok(hipSetDevice(p->inst->device), "hipSetDevice", err)) return false;
+      if (!hip_ok(hipStreamSynchronize(p->inst->stream), "exchange (peer)", err)) return false;
+    }
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
+  return hip_ok(hipStreamSynchronize(chains_[0]->stream), "exchange (root)", err);
+}
+
+size_t Renderer::Peer::n_pixels() const {
+  size_t n = 0;
+  for (auto& c : r->chains_) n += c->map.n_local_pixels;
+  return n;
+}
+const float4* Renderer::Peer::packed(bool result) const {
+  auto& ch = r->chains_;
+  return ch.size() > 1 ? frame.ptr : (result ? ch[0]->result.ptr : ch[0]->cumulative.ptr);
+}
+
+// The gather shape over either transport: every peer's packed tiles go to recv_stage_ on device 0, peer after peer in the order of
+// the list, and are scattered from there.
+bool Renderer::exchange_packed(bool result, float4* dst, Error& err) {
   hipStream_t st = chains_[0]->stream;
-  if (!hip_ok(hipStreamSynchronize(st), "exchange: local frame", err)) return false;
-  const bool lb = loopback_;
-  const bool packed = !lb && exchange_ != kExchangeReduce;
-  if (!forward([=](Peer& p, Error& e) {
+  if (!forward([=](Peer& p, size_t, Error& e) {
         if (!hip_ok(hipSetDevice(p.inst->device), "hipSetDevice", e)) return false;
-        if (packed) {
-          // the chains' own tile-major buffers are what travels: one chain is sent from where it lies, several are laid end
-          // to end first so that every peer issues exactly ONE send (copies and send are ordered by the peer's stream)
-          if (!p.r->settle(e)) return false;
-          auto& ch = p.r->chains_;
-          if (ch.size() < 2) return true;
-          size_t total = 0, off = 0;
-          for (auto& c : ch) total += c->map.n_local_pixels;
-          if (p.frame.count < total && !hip_ok(p.frame.alloc(total), "alloc peer staging", e)) return false;
-          for (auto& c : ch) {
-            const size_t n = c->map.n_local_pixels;
-            if (n && !hip_ok(hipMemcpyAsync(p.frame.ptr + off, result ? c->result.ptr : c->cumulative.ptr, sizeof(float4) * n, hipMemcpyDeviceToDevice, p.inst->stream), "pack tiles", e))
-              return false;
-            off += n;
-          }
-          return true;
+        // the chains' own tile-major buffers are what travels: one chain is sent from where it lies, several are laid end
+        // to end first so that every peer issues exactly ONE send (copies and send are ordered by the peer's stream)
+        if (!p.r->settle(e)) return false;
+        auto& ch = p.r->chains_;
+        if (ch.size() < 2) return true;
+        const size_t total = p.n_pixels();
+        size_t off = 0;
+        if (p.frame.count < total && !hip_ok(p.frame.alloc(total), "alloc peer staging", e)) return false;
+        for (auto& c : ch) {
+          const size_t n = c->map.n_local_pixels;
+          if (n && !hip_ok(hipMemcpyAsync(p.frame.ptr + off, result ? c->result.ptr : c->cumulative.ptr, sizeof(float4) * n, hipMemcpyDeviceToDevice, p.inst->stream), "pack tiles", e))
+            return false;
+          off += n;
         }
-        if (!p.r->gather(result, lb ? dst : p.frame.ptr, e, !lb)) return false;
-        return hip_ok(hipStreamSynchronize(p.inst->stream), "exchange: peer frame", e);
+        return true;
       }, err))
     return false;
-  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  if (lb) return true;
-  if (exchange_ == kExchangePeerCopy) {
-    size_t total = 0;
-    for (auto& p : peers_)
-      for (auto& c : p->r->chains_) total += c->map.n_local_pixels;
-    if (recv_stage_.count < total && !hip_ok(recv_stage_.alloc(total), "alloc exchange staging", err)) return false;
-    size_t off = 0;
-    bool ok = true;
-    for (size_t i = 0; ok && i < peers_.size(); ++i) {
-      Peer& p = *peers_[i];
-      auto& ch = p.r->chains_;
-      size_t n = 0;
-      for (auto& c : ch) n += c->map.n_local_pixels;
-      if (!n) continue;
-      const float4* src = ch.size() > 1 ? p.frame.ptr : (result ? ch[0]->result.ptr : ch[0]->cumulative.ptr);
+  const Rccl* nc = nullptr;   // null: peer copy
+  if (exchange_ != kExchangePeerCopy && !(nc = rccl(err))) return false;
+  size_t total = 0, off = 0;
+  for (auto& p : peers_) total += p->n_pixels();
+  if (recv_stage_.count < total && !hip_ok(recv_stage_.alloc(total), "alloc exchange staging", err)) return false;
+  if (nc && !rccl_ok(*nc, nc->GroupStart(), "ncclGroupStart", err)) return false;
+  bool ok = true;
+  for (size_t i = 0; ok && i < peers_.size(); ++i) {
+    Peer& p = *peers_[i];
+    const size_t n = p.n_pixels();
+    if (!n) continue;
+    const float4* src = p.packed(result);
+    if (nc) {
+      ok = rccl_ok(*nc, nc->Send(src, n * 4, ncclFloat, 0, static_cast<ncclComm_t>(comms_[i + 1]), p.inst->stream), "ncclSend", err) &&
+           rccl_ok(*nc, nc->Recv(recv_stage_.ptr + off, n * 4, ncclFloat, (int)i + 1, static_cast<ncclComm_t>(comms_[0]), st), "ncclRecv", err);
+    } else {
       ok = hip_ok(hipSetDevice(p.inst->device), "hipSetDevice", err) && (p.sent || hip_ok(hipEventCreateWithFlags(&p.sent, hipEventDisableTiming), "event", err)) &&
            hip_ok(hipMemcpyPeerAsync(recv_stage_.ptr + off, inst_->device, src, p.inst->device, sizeof(float4) * n, p.inst->stream), "peer copy", err) &&
            hip_ok(hipEventRecord(p.sent, p.inst->stream), "peer copy", err);
-      (void)hipSetDevice(inst_->device);
+      (void)hipSetDevice(inst_->device);   // for the wait that follows, not a restore
       ok = ok && hip_ok(hipStreamWaitEvent(st, p.sent, 0), "peer copy", err);
-      off += n;
     }
-    if (!ok) return false;
-    off = 0;
-    for (auto& p : peers_)
-      for (auto& c : p->r->chains_) {
-        if (!hip_ok(launch_export(st, c->map, recv_stage_.ptr + off, dst, false), "k_export (received tiles)", err)) return false;
-        off += c->map.n_local_pixels;
-      }
-    return hip_ok(hipStreamSynchronize(st), "exchange (root)", err);   // the root waited for every peer's copy before it scattered
+    off += n;
   }
-  std::string why;
-  const Rccl* nc = Rccl::get(why);
-  if (!nc || comms_.size() != peers_.size() + 1) {
-    err.code = GLZ_E_DEVICE;
-    err.msg = nc ? "RCCL communicators are missing" : why;
-    return false;
-  }
-  auto ck = [&](ncclResult_t r, const char* what) {
-    if (r == ncclSuccess) return true;
-    if (err.code == 0 || err.msg.empty()) {
-      err.code = GLZ_E_DEVICE;
-      err.msg = std::string(what) + ": " + nc->GetErrorString(r);
+  if (nc) ok = rccl_ok(*nc, nc->GroupEnd(), "ncclGroupEnd", err) && ok;   // always closed, also after a failed call inside it
+  if (!ok) return false;
+  off = 0;
+  for (auto& p : peers_)
+    for (auto& c : p->r->chains_) {
+      if (!hip_ok(launch_export(st, c->map, recv_stage_.ptr + off, dst, false), "k_export (received tiles)", err)) return false;
+      off += c->map.n_local_pixels;
     }
-    return false;
-  };
-  bool ok = true;
-  if (packed) {
-    size_t total = 0;
-    for (auto& p : peers_)
-      for (auto& c : p->r->chains_) total += c->map.n_local_pixels;
-    if (recv_stage_.count < total && !hip_ok(recv_stage_.alloc(total), "alloc exchange staging", err)) return false;
-    if (!ck(nc->GroupStart(), "ncclGroupStart")) return false;
-    size_t off = 0;
-    for (size_t i = 0; ok && i < peers_.size(); ++i) {
-      auto& ch = peers_[i]->r->chains_;
-      size_t n = 0;
-      for (auto& c : ch) n += c->map.n_local_pixels;
-      if (!n) continue;
-      const float4* src = ch.size() > 1 ? peers_[i]->frame.ptr : (result ? ch[0]->result.ptr : ch[0]->cumulative.ptr);
-      ok = ck(nc->Send(src, n * 4, ncclFloat, 0, static_cast<ncclComm_t>(comms_[i + 1]), peers_[i]->inst->stream), "ncclSend") &&
-           ck(nc->Recv(recv_stage_.ptr + off, n * 4, ncclFloat, (int)i + 1, static_cast<ncclComm_t>(comms_[0]), st), "ncclRecv");
-      off += n;
-    }
-    const bool ended = ck(nc->GroupEnd(), "ncclGroupEnd");   // always closed, also after a failed call inside it
-    if (!ok || !ended) return false;
-    off = 0;
-    for (auto& p : peers_)
-      for (auto& c : p->r->chains_) {
-        if (!hip_ok(launch_export(st, c->map, recv_stage_.ptr + off, dst, false), "k_export (received tiles)", err)) return false;
-        off += c->map.n_local_pixels;
-      }
-  } else {
-    const size_t count = (size_t)w_ * h_ * 4;
-    if (!ck(nc->GroupStart(), "ncclGroupStart")) return false;
-    ok = ck(nc->Reduce(dst, dst, count, ncclFloat, ncclSum, 0, static_cast<ncclComm_t>(comms_[0]), st), "ncclReduce");   // in place on the root
-    for (size_t i = 0; ok && i < peers_.size(); ++i)
-      ok = ck(nc->Reduce(peers_[i]->frame.ptr, nullptr, count, ncclFloat, ncclSum, 0, static_cast<ncclComm_t>(comms_[i + 1]), peers_[i]->inst->stream), "ncclReduce");
-    const bool ended = ck(nc->GroupEnd(), "ncclGroupEnd");
-    if (!ok || !ended) return false;
-  }
-  // the peers' streams first (their buffers are free again), the root's last: everything has arrived when it is idle
-  for (auto& p : peers_) {
-    if (!hip_ok(hipSetDevice(p->inst->device), "hipSetDevice", err)) {
-      (void)hipSetDevice(inst_->device);
-      return false;
-    }
-    if (!hip_ok(hipStreamSynchronize(p->inst->stream), "exchange (peer)", err)) {
-      (void)hipSetDevice(inst_->device);
-      return false;
-    }
-  }
-  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "exchange (root)", err);
+  return finish_exchange(nc != nullptr, err);
+}
+
+// One ncclReduce per device over the zero-padded frames, in place on the root.
+bool Renderer::exchange_reduce(bool result, float4* dst, Error& err) {
+  if (!peers_gather(result, nullptr, err)) return false;
+  const Rccl* nc = rccl(err);
+  if (!nc) return false;
+  const size_t count = (size_t)w_ * h_ * 4;
+  if (!rccl_ok(*nc, nc->GroupStart(), "ncclGroupStart", err)) return false;
+  bool ok = rccl_ok(*nc, nc->Reduce(dst, dst, count, ncclFloat, ncclSum, 0, static_cast<ncclComm_t>(comms_[0]), chains_[0]->stream), "ncclReduce", err);   // in place on the root
+  for (size_t i = 0; ok && i < peers_.size(); ++i)
+    ok = rccl_ok(*nc, nc->Reduce(peers_[i]->frame.ptr, nullptr, count, ncclFloat, ncclSum, 0, static_cast<ncclComm_t>(comms_[i + 1]), peers_[i]->inst->stream), "ncclReduce", err);
+  ok = rccl_ok(*nc, nc->GroupEnd(), "ncclGroupEnd", err) && ok;
+  return ok && finish_exchange(true, err);
 }
 
 // everything this renderer has enqueued is done and its images are final (what gather() establishes before it scatters)
@@ -1013,22 +1003,31 @@ bool Renderer::settle(Error& err) {
   return wait_idle(err);
 }
 
+// The two tails of every read-out, on the first chain's stream (= the instance's): a full float4 frame to the host, or through the
+// sRGB8 quantiser (into rgba8_) to the host; both wait for the copy.  `what` names the read in an error, `what_sync` the wait's.
+bool Renderer::frame_to_host(const float4* frame, void* out, const char* what, Error& err) {
+  hipStream_t st = chains_[0]->stream;
+  if (!hip_ok(hipMemcpyAsync(out, frame, sizeof(float4) * (size_t)w_ * h_, hipMemcpyDeviceToHost, st), what, err)) return false;
+  return hip_ok(hipStreamSynchronize(st), what, err);
+}
+bool Renderer::rgba8_to_host(const float4* frame, uint8_t* out, const char* what, const char* what_sync, Error& err) {
+  hipStream_t st = chains_[0]->stream;
+  if (!hip_ok(launch_tonemap(st, w_ * h_, frame, oetf_thresholds_.ptr, rgba8_.ptr), "k_tonemap", err)) return false;
+  if (!hip_ok(hipMemcpyAsync(out, rgba8_.ptr, (size_t)w_ * h_ * 4, hipMemcpyDeviceToHost, st), what, err)) return false;
+  return hip_ok(hipStreamSynchronize(st), what_sync, err);
+}
+
 bool Renderer::read_frame(bool result, float* out, Error& err) {
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   if (!gather(result, frame_tmp_.ptr, err)) return false;
-  hipStream_t st = chains_[0]->stream;
-  if (!hip_ok(hipMemcpyAsync(out, frame_tmp_.ptr, sizeof(float4) * (size_t)w_ * h_, hipMemcpyDeviceToHost, st), "read frame", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "read frame", err);
+  return frame_to_host(frame_tmp_.ptr, out, "read frame", err);
 }
 
 // blit out32 -> out8 (R8G8B8A8_SRGB) + export (raytracer.rs:576-584, memory.rs:269-483)
 bool Renderer::read_rgba8(uint8_t* out, Error& err) {
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   if (!gather(true, frame_tmp_.ptr, err)) return false;
-  hipStream_t st = chains_[0]->stream;
-  if (!hip_ok(launch_tonemap(st, w_ * h_, frame_tmp_.ptr, oetf_thresholds_.ptr, rgba8_.ptr), "k_tonemap", err)) return false;
-  if (!hip_ok(hipMemcpyAsync(out, rgba8_.ptr, (size_t)w_ * h_ * 4, hipMemcpyDeviceToHost, st), "read rgba8", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "read rgba8", err);
+  return rgba8_to_host(frame_tmp_.ptr, out, "read rgba8", "read rgba8", err);
 }
 
 // ---- post: first-hit feature buffers and the denoiser ------------------------------------------------------------------------------
@@ -1042,19 +1041,11 @@ void Renderer::release_post() {
 void Renderer::post_args(LaunchArgs& a) const {
   memset(&a, 0, sizeof(a));
   a.scene = scene_->dev;
-  a.cam = cam_;
+  a.cam = cfg_.cam;
   a.frame.scene_size[0] = (float)w_;
   a.frame.scene_size[1] = (float)h_;
-  a.frame.camera_persp = camera_.type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
-  TileMap& m = a.map;
-  m.width = w_;
-  m.height = h_;
-  m.tiles_x = (w_ + kTile - 1) / kTile;
-  m.tiles_y = (h_ + kTile - 1) / kTile;
-  m.rank = 0;
-  m.world = 1;
-  m.n_local_tiles = m.tiles_x * m.tiles_y;
-  m.n_local_pixels = m.n_local_tiles * kTile * kTile;
+  a.frame.camera_persp = cfg_.camera.type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
+  a.map = make_tile_map(w_, h_, 0, 1);
 }
 
 bool Renderer::first_hit_pass(Error& err, hipEvent_t* marks) {
@@ -1096,10 +1087,7 @@ bool Renderer::read_aov(int which, float* out, Error& err) {
     return false;
   }
   if (!first_hit_pass(err)) return false;
-  hipStream_t st = inst_->stream;
-  const float4* src = which == GLZ_AOV_NORMAL_DEPTH ? aov0_.ptr : aov1_.ptr;
-  if (!hip_ok(hipMemcpyAsync(out, src, sizeof(float4) * (size_t)w_ * h_, hipMemcpyDeviceToHost, st), "read feature buffer", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "read feature buffer", err);
+  return frame_to_host(which == GLZ_AOV_NORMAL_DEPTH ? aov0_.ptr : aov1_.ptr, out, "read feature buffer", err);
 }
 
 bool Renderer::camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err) {
@@ -1172,16 +1160,12 @@ bool Renderer::read_denoised(float* rgba32f, uint8_t* rgba8, Error& err) {
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   if (!gather(true, frame_tmp_.ptr, err)) return false;   // flushes the pending shadow rays, brings the other devices' tiles
   if (!first_hit_pass(err)) return false;
-  const size_t n = (size_t)w_ * h_;
   if (!ensure_denoise_frames(err)) return false;
   hipStream_t st = chains_[0]->stream;   // = the instance stream the first-hit pass ran on
   if (!hip_ok(launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr), "k_atrous", err)) return false;
-  if (rgba32f && !hip_ok(hipMemcpyAsync(rgba32f, dn_out_.ptr, sizeof(float4) * n, hipMemcpyDeviceToHost, st), "read denoised", err)) return false;
-  if (rgba8) {
-    if (!hip_ok(launch_tonemap(st, w_ * h_, dn_out_.ptr, oetf_thresholds_.ptr, rgba8_.ptr), "k_tonemap", err)) return false;
-    if (!hip_ok(hipMemcpyAsync(rgba8, rgba8_.ptr, n * 4, hipMemcpyDeviceToHost, st), "read denoised", err)) return false;
-  }
-  return hip_ok(hipStreamSynchronize(st), "read denoised", err);
+  if (rgba32f && !frame_to_host(dn_out_.ptr, rgba32f, "read denoised", err)) return false;
+  if (rgba8 && !rgba8_to_host(dn_out_.ptr, rgba8, "read denoised", "read denoised", err)) return false;
+  return hip_ok(hipStreamSynchronize(st), "read denoised", err);   // with neither output the filter has still run when this returns
 }
 
 bool Renderer::set_texture_lod(int mode, Error& err) {
@@ -1190,13 +1174,13 @@ bool Renderer::set_texture_lod(int mode, Error& err) {
     err.msg = "texture LOD mode must be 0 (level 0), 1 (ray cones) or 2 (ray cones, anisotropic footprint)";
     return false;
   }
-  lod_mode_ = mode;
+  cfg_.lod_mode = mode;
   request_new_frame_ = true;
-  return forward([=](Peer& p, Error& e) { return p.r->set_texture_lod(mode, e); }, err);
+  return forward([=](Peer& p, size_t, Error& e) { return p.r->set_texture_lod(mode, e); }, err);
 }
 
 bool Renderer::set_seed(uint64_t s) {
-  seed_ = s;
+  cfg_.seed = s;
   request_new_frame_ = true;
   for (auto& p : peers_) p->r->set_seed(s);
   return true;
@@ -1208,7 +1192,7 @@ bool Renderer::set_depth(uint32_t d, Error& err) {
     err.msg = "depth (PT_STEPS) must be in 1..1024";
     return false;
   }
-  pt_steps_ = d;
+  cfg_.pt_steps = d;
   request_new_frame_ = true;
   for (auto& p : peers_)
     if (!p->r->set_depth(d, err)) return false;
@@ -1230,33 +1214,10 @@ bool Renderer::set_partition_local(uint32_t rank, uint32_t world, Error& err) {
     err.msg = "bad tile partition";
     return false;
   }
-  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  for (auto& c : chains_) {
-    if (!flush_shadows(*c, err)) return false;
-    if (!hip_ok(hipStreamSynchronize(c->stream), "set_partition", err)) return false;
-  }
+  if (!wait_idle_local("set_partition", err)) return false;
   rank_ = rank;
   world_ = world;
   return allocate(err);
-}
-
-// what a freshly created peer renderer takes over from this one
-bool Renderer::configure_peer(Renderer& p, Error& err) const {
-  p.integrator_ = integrator_;
-  p.lod_mode_ = lod_mode_;
-  p.pt_steps_ = pt_steps_;
-  p.seed_ = seed_;
-  p.exposure_ = exposure_;
-  p.camera_ = camera_;
-  p.cam_ = cam_;
-  p.chains_wanted_ = chains_wanted_;
-  p.launch_mode_ = launch_mode_;
-  p.node_width_ = node_width_;
-  p.counting_ = counting_;
-  p.profile_kernels_ = profile_kernels_;
-  p.request_new_frame_ = true;
-  (void)err;
-  return true;
 }
 
 bool Renderer::set_devices(const int* devices, int n, Error& err) {
@@ -1304,6 +1265,7 @@ bool Renderer::set_devices(const int* devices, int n, Error& err) {
     }
   }
   if (!wait_idle(err)) return false;
+  OnOwnDevice back{*this};   // peer access and ncclCommInitAll below visit the other devices on this thread
   release_peers();
   // from here on every failure leaves ONE device rendering the whole frame
   auto fail = [&]() {
@@ -1323,23 +1285,14 @@ bool Renderer::set_devices(const int* devices, int n, Error& err) {
   const Instance* src_inst = scene_->instance ? scene_->instance : inst_;
   const uint32_t w = w_, h = h_, world = (uint32_t)n;
   const bool want_frame = !loopback && exchange == kExchangeReduce;
-  std::vector<Peer*> order;
-  for (auto& p : peers_) order.push_back(p.get());
-  const std::vector<Peer*>* ord = &order;
-  const bool built = forward([=](Peer& p, Error& e) {
-    size_t i = 0;
-    while ((*ord)[i] != &p) ++i;
+  const bool built = forward([=](Peer& p, size_t i, Error& e) {
     p.inst.reset(Instance::create(devices[i + 1], e));
     if (!p.inst) return false;
-    // the replica takes the shape the root's scene HAS (builder, pair leaves, flattened or two levels), not what the
-    // environment of this thread would choose
-    p.inst->copy_build_options(*src_inst);
-    if (src->info.as_levels) p.inst->as_levels = (int)src->info.as_levels;
-    SceneData copy = src->data;
-    std::shared_ptr<Scene> replica(Scene::create(p.inst.get(), std::move(copy), e));
+    std::shared_ptr<Scene> replica = p.replica_of(*src, *src_inst, e);
     if (!replica) return false;
     p.r.reset(Renderer::create(p.inst.get(), replica, w, h, e));
-    if (!p.r || !self->configure_peer(*p.r, e)) return false;
+    if (!p.r) return false;
+    p.r->cfg_ = self->cfg_;   // (the allocate() that follows requests a new frame)
     if (!p.r->set_partition_local((uint32_t)i + 1, world, e)) return false;
     return !want_frame || hip_ok(p.frame.alloc((size_t)w * h), "alloc peer frame", e);
   }, err);
@@ -1358,12 +1311,10 @@ bool Renderer::set_devices(const int* devices, int n, Error& err) {
       }
     }
     (void)hipGetLastError();
-    (void)hipSetDevice(inst_->device);
   }
   if (use_rccl) {
     std::vector<ncclComm_t> comms((size_t)n, nullptr);
     const ncclResult_t r = nc->CommInitAll(comms.data(), n, devices);
-    (void)hipSetDevice(inst_->device);
     if (r != ncclSuccess) {
       err.code = GLZ_E_DEVICE;
       err.msg = std::string("ncclCommInitAll: ") + nc->GetErrorString(r);
@@ -1387,12 +1338,7 @@ bool Renderer::set_chains(uint32_t n, Error& err) {
     err.msg = "at most 16 chains";
     return false;
   }
-  if (!wait_idle(err)) return false;
-  chains_wanted_ = n;
-  if (!allocate(err)) return false;
-  const bool ok = forward([=](Peer& p, Error& e) { return p.r->set_chains(n, e); }, err);
-  (void)hipSetDevice(inst_->device);
-  return ok;
+  return resize([&] { cfg_.chains_wanted = n; }, [=](Peer& p, size_t, Error& e) { return p.r->set_chains(n, e); }, err);
 }
 
 bool Renderer::export_device(int which, void* dev, Error& err) {
@@ -1405,8 +1351,7 @@ bool Renderer::export_device(int which, void* dev, Error& err) {
 // order of its partition (local tile j = global tile rank + j * world), packed_count() float4s.
 size_t Renderer::packed_count(uint32_t w, uint32_t h, uint32_t rank, uint32_t world) {
   if (world == 0 || rank >= world) return 0;
-  const uint32_t tiles = ((w + kTile - 1) / kTile) * ((h + kTile - 1) / kTile);
-  return tiles > rank ? (size_t)((tiles - rank + world - 1) / world) * kTile * kTile : 0;
+  return make_tile_map(w, h, rank, world).n_local_pixels;
 }
 bool Renderer::export_packed(int which, void* dev, Error& err) {
   if (!peers_.empty()) {
@@ -1432,17 +1377,8 @@ bool Renderer::scatter_packed(uint32_t rank, uint32_t world, const void* dev_pac
     return false;
   }
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  TileMap m{};
-  m.width = w_;
-  m.height = h_;
-  m.tiles_x = (w_ + kTile - 1) / kTile;
-  m.tiles_y = (h_ + kTile - 1) / kTile;
-  m.rank = rank;
-  m.world = world;
-  m.n_local_pixels = (uint32_t)packed_count(w_, h_, rank, world);
-  m.n_local_tiles = m.n_local_pixels / (kTile * kTile);
   hipStream_t st = chains_[0]->stream;
-  if (!hip_ok(launch_export(st, m, static_cast<const float4*>(dev_packed), static_cast<float4*>(dev_frame), false), "k_export (packed tiles)", err)) return false;
+  if (!hip_ok(launch_export(st, make_tile_map(w_, h_, rank, world), static_cast<const float4*>(dev_packed), static_cast<float4*>(dev_frame), false), "k_export (packed tiles)", err)) return false;
   return hip_ok(hipStreamSynchronize(st), "scatter_packed", err);
 }
 
@@ -1455,15 +1391,7 @@ bool Renderer::scatter_packed_all(uint32_t world, const void* dev_packed, uint64
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   hipStream_t st = chains_[0]->stream;
   for (uint32_t rank = 0; rank < world; ++rank) {
-    TileMap m{};
-    m.width = w_;
-    m.height = h_;
-    m.tiles_x = (w_ + kTile - 1) / kTile;
-    m.tiles_y = (h_ + kTile - 1) / kTile;
-    m.rank = rank;
-    m.world = world;
-    m.n_local_pixels = (uint32_t)packed_count(w_, h_, rank, world);
-    m.n_local_tiles = m.n_local_pixels / (kTile * kTile);
+    const TileMap m = make_tile_map(w_, h_, rank, world);
     if (m.n_local_pixels == 0) continue;
     if (!hip_ok(launch_export(st, m, static_cast<const float4*>(dev_packed) + (size_t)rank * stride_pixels, static_cast<float4*>(dev_frame), false), "k_export (packed tiles)", err)) return false;
   }
@@ -1472,30 +1400,14 @@ bool Renderer::scatter_packed_all(uint32_t world, const void* dev_packed, uint64
 
 bool Renderer::tonemap_device(const void* dev_result, uint8_t* out, Error& err) {
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  hipStream_t st = chains_[0]->stream;
-  if (!hip_ok(launch_tonemap(st, w_ * h_, static_cast<const float4*>(dev_result), oetf_thresholds_.ptr, rgba8_.ptr), "k_tonemap", err)) return false;
-  if (!hip_ok(hipMemcpyAsync(out, rgba8_.ptr, (size_t)w_ * h_ * 4, hipMemcpyDeviceToHost, st), "read rgba8", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "tonemap_device", err);
+  return rgba8_to_host(static_cast<const float4*>(dev_result), out, "read rgba8", "tonemap_device", err);
 }
 
-bool Renderer::launch_constants(uint32_t launch, uint32_t* seed, float off[2]) {
-  host::SeedStream rng(seed_);
-  host::WorkScheduler ws;
-  uint32_t s = 0;
-  float o[2] = {0, 0};
-  for (uint32_t i = 0; i <= launch; ++i) {
-    s = rng.next();
-    ws.next(o);
-  }
-  *seed = s;
-  off[0] = o[0];
-  off[1] = o[1];
-  return true;
-}
+bool Renderer::launch_constants(uint32_t launch, uint32_t* seed, float off[2]) { return host::launch_constants(cfg_.seed, launch, seed, off); }
 
 void Renderer::push_constants(float out[32]) const {
-  memcpy(out, cam_.camera2world, 64);
-  memcpy(out + 16, cam_.screen2camera, 64);
+  memcpy(out, cfg_.cam.camera2world, 64);
+  memcpy(out + 16, cfg_.cam.screen2camera, 64);
 }
 
 }  // namespace glz

@@ -1,12 +1,14 @@
 // RayTraceRenderer on HIP (lib/src/vulkan/raytracer.rs:109-687): launch loop, per-launch frame
 // constants, accumulation buffers, tile partition for one-process-per-GPU jobs.
 #pragma once
+#include <cstdlib>
 #include <memory>
 #include <vector>
 
 #include "host_math.h"
 #include "kernels.h"
 #include "scene.h"
+#include "tile_map.h"
 
 namespace glz {
 
@@ -24,7 +26,7 @@ class Renderer {
   bool refresh_binded_textures(const glz_texture* t, uint32_t nt, Error& err);
   bool update_transforms(const glz_transform* t, uint32_t n, Error& err);   // Scene::update_transforms; restarts accumulation
   bool wait_idle(Error& err);
-  uint32_t steps_per_sample() const { return integrator_ == GLZ_DIRECT ? 1u : pt_steps_; }
+  uint32_t steps_per_sample() const { return cfg_.integrator == GLZ_DIRECT ? 1u : cfg_.pt_steps; }
 
   bool draw(size_t spp, void (*cb)(void*), void* user, uint8_t* rgba8_out, Error& err);
   bool restart();
@@ -58,7 +60,7 @@ class Renderer {
   bool path_mode() const { return path_mode_; }
   // Which nodes the two-kernel mode's traversal walks: 4 (k_trace), 8 (k_trace8: flattened scenes, counters off), 0 = by the pixels this device owns.
   bool set_node_width(int width, Error& err);
-  bool wide8() const { return wide8_ && !counting_; }
+  bool wide8() const { return wide8_ && !cfg_.counting; }
   uint32_t chains() const { return (uint32_t)chains_.size(); }
   static uint32_t chains_for(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t wanted);
   bool export_device(int which, void* dev_rgba32f, Error& err);
@@ -85,27 +87,38 @@ class Renderer {
   bool launch_constants_common(FrameData& fd, Error& err);
   bool path_batch(uint32_t n, Error& err);
   bool run_launches(uint32_t n, Error& err);
-  bool use_path() const { return path_mode_ && !counting_ && chains_.size() == 1 && chains_[0]->grid_path != 0; }
+  bool use_path() const { return path_mode_ && !cfg_.counting && chains_.size() == 1 && chains_[0]->grid_path != 0; }
   bool gather(bool result, float4* dst, Error& err, bool zero_first = true);
+  template <class A, class F> bool resize(A apply, F on_peer, Error& err);
+  template <class U> bool update_scene(U update, Error& err);
+  bool frame_to_host(const float4* frame, void* out, const char* what, Error& err);
+  bool rgba8_to_host(const float4* frame, uint8_t* out, const char* what, const char* what_sync, Error& err);
 
   Instance* inst_ = nullptr;
   std::shared_ptr<Scene> scene_;   // shared with the glz_scene handle it came from (info / debug hooks stay valid)
   uint32_t w_ = 0, h_ = 0;
-  int integrator_ = GLZ_PATH_TRACE;
-  uint32_t pt_steps_ = 6;   // PT_STEPS, raytrace_structures.rs:87
-  int lod_mode_ = 0;        // texture level of detail: 0 = level 0 always (what the reference's ray-tracing stages do), 1 = ray cones, 2 = ray cones with an anisotropic footprint
-  float exposure_ = 1.0f;
-  glz_camera camera_{};
-  CameraConsts cam_{};
-  uint64_t seed_ = 0;
+  // What every device of set_devices must agree on to render one image: a new peer takes it over by one assignment, the setters
+  // forward every change.  Deliberately not in here: the partition (rank_, world_: each device has its own), the denoiser's parameters
+  // and the post buffers (the post stage runs on this device only, on the gathered frame), and everything allocate() derives.
+  struct Settings {
+    int integrator = GLZ_PATH_TRACE;
+    uint32_t pt_steps = 6;   // PT_STEPS, raytrace_structures.rs:87
+    int lod_mode = 0;        // texture level of detail: 0 = level 0 always (what the reference's ray-tracing stages do), 1 = ray cones, 2 = ray cones with an anisotropic footprint
+    float exposure = 1.0f;
+    glz_camera camera{};
+    CameraConsts cam{};
+    uint64_t seed = 0;
+    uint32_t chains_wanted = 0;      // 0 = automatic (pick_chains)
+    int launch_mode = getenv("GLAZE_LAUNCH_MODE") ? atoi(getenv("GLAZE_LAUNCH_MODE")) : 0;   // set_launch_mode
+    int node_width = getenv("GLAZE_NODE_WIDTH") ? atoi(getenv("GLAZE_NODE_WIDTH")) : 0;   // set_node_width
+    bool counting = false;
+    bool profile_kernels = true;
+  } cfg_;
   host::SeedStream rng_;
   host::WorkScheduler sched_;
   bool request_new_frame_ = true;
   uint32_t rank_ = 0, world_ = 1;   // tile partition of this process (glz_renderer_set_partition)
-  uint32_t chains_wanted_ = 0;      // 0 = automatic (pick_chains)
-  int launch_mode_ = getenv("GLAZE_LAUNCH_MODE") ? atoi(getenv("GLAZE_LAUNCH_MODE")) : 0;   // set_launch_mode
   bool path_mode_ = false;          // decided in allocate(): this device's launches run as k_path batches
-  int node_width_ = getenv("GLAZE_NODE_WIDTH") ? atoi(getenv("GLAZE_NODE_WIDTH")) : 0;   // set_node_width
   bool wide8_ = false;              // decided in allocate(): k_trace8 (the 8-wide nodes) traces this device's rays while the counters are off
 
   // One chain = one independent sequence of launches over a subset of this rank's tiles, on its own HIP stream.
@@ -118,6 +131,8 @@ class Renderer {
     int kind;   // 0: e[0]..e[2] around k_trace, k_shade; 1: e[0]..e[1] around a stand-alone shadow pass; 2: e[0]..e[1] around k_path
     uint32_t weight;   // kind 0: the launches this timed one stands for (event_stride())
   };
+  static hipEvent_t last_event(const EventSet& s) { return s.e[s.kind ? 1 : 2]; }
+  struct Timed;   // the events around one timed stretch of a chain's stream (renderer.cpp)
   uint64_t event_stride() const;
   struct Chain {
     TileMap map{};
@@ -142,6 +157,7 @@ class Renderer {
   };
   std::vector<std::unique_ptr<Chain>> chains_;
   uint32_t pick_chains() const;
+  uint32_t trace_grid(const Chain& c) const { return cfg_.counting ? c.grid_counting : (wide8() ? c.grid8 : c.grid); }   // blocks of the traversal kernel the chain's launches run
   void release_chains();
   bool flush_shadows(Chain& c, Error& err);
   bool acquire_events(Chain& c, EventSet& ev, Error& err);
@@ -151,6 +167,7 @@ class Renderer {
   // ---- other GPUs of this process (set_devices) ----
   struct Peer;
   struct Pending;
+  struct OnOwnDevice;
   std::vector<std::unique_ptr<Peer>> peers_;
   std::vector<void*> comms_;   // ncclComm_t per device (index 0 = this renderer); empty in loop-back mode
   bool loopback_ = false;      // all "devices" are this one device (GLAZE_MULTI_LOOPBACK=1, tests on a one-GPU box): no RCCL
@@ -160,11 +177,17 @@ class Renderer {
   bool settle(Error& err);
   template <class F> void post_all(F f, Pending& p);
   bool join_all(Pending& p, Error& err);
+  template <class F, class G> bool with_peers(F f, G g, Error& err);
   template <class F> bool forward(F f, Error& err);
   void release_peers();
   bool set_partition_local(uint32_t rank, uint32_t world, Error& err);
-  bool configure_peer(Renderer& p, Error& err) const;
+  bool wait_idle_local(const char* what, Error& err);
   bool reduce_peers(bool result, float4* dst, Error& err);
+  bool peers_gather(bool result, float4* shared, Error& err);
+  bool exchange_packed(bool result, float4* dst, Error& err);
+  bool exchange_reduce(bool result, float4* dst, Error& err);
+  bool finish_exchange(bool peers_too, Error& err);
+  const struct Rccl* rccl(Error& err) const;   // the loaded library, if this renderer has its communicators
   bool step_local(uint32_t n, Error& err);
 
   // The first-hit pass over the FULL frame on this device, whatever the partition: centre rays, closest hits, attributes -> aov0_ / aov1_.
@@ -181,10 +204,7 @@ class Renderer {
   DeviceBuffer<uchar4> rgba8_;
   DeviceBuffer<float> oetf_thresholds_;   // sRGB8 quantiser thresholds (host::srgb8_thresholds), see k_tonemap
   DeviceBuffer<TraceCounters> counters_;
-  // stats
-  bool counting_ = false;
-  uint64_t launches_ = 0;
-  bool profile_kernels_ = true;
+  uint64_t launches_ = 0;   // stats
 };
 
 }  // namespace glz
