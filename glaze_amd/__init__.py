@@ -411,6 +411,44 @@ class RayTraceScene:
         abi.check(abi.lib().glz_debug_sample_texture(self._h, texture, _ptr(uv), None if fp is None else _ptr(fp), n, _ptr(out)))
         return out
 
+    # the kernels' shading routines one call at a time; arguments and results as OracleScene.bsdf_value / bsdf_sample / light_sample
+    def debug_bsdf_value(self, material_id, wo, wi, uv=(0.5, 0.5), rand=None, frame=None):
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        n = wo.shape[0]
+        rnd = np.ascontiguousarray(rand if rand is not None else np.zeros(n), np.float32)
+        uvv = np.ascontiguousarray(uv, np.float32).reshape(2)
+        fr = None if frame is None else np.ascontiguousarray(frame, np.float32).reshape(9)
+        if wi.shape[0] != n or rnd.size != n:
+            raise ValueError("wo, wi and rand differ in length")
+        value, pdf = np.zeros((n, 16), np.float32), np.zeros(n, np.float32)
+        abi.check(abi.lib().glz_debug_bsdf_value(self._h, material_id, _ptr(wo), _ptr(wi), _ptr(uvv), _ptr(rnd), None if fr is None else _ptr(fr), n,
+                                                 _ptr(value), _ptr(pdf)))
+        return value, pdf
+
+    def debug_bsdf_sample(self, material_id, wo, rand3, uv=(0.5, 0.5), frame=None):
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(rand3, np.float32).reshape(-1, 3)
+        n = wo.shape[0]
+        uvv = np.ascontiguousarray(uv, np.float32).reshape(2)
+        fr = None if frame is None else np.ascontiguousarray(frame, np.float32).reshape(9)
+        if r.shape[0] != n:
+            raise ValueError("wo and rand3 differ in length")
+        wi, value, pdf = np.zeros((n, 3), np.float32), np.zeros((n, 16), np.float32), np.zeros(n, np.float32)
+        abi.check(abi.lib().glz_debug_bsdf_sample(self._h, material_id, _ptr(wo), _ptr(uvv), _ptr(r), None if fr is None else _ptr(fr), n, _ptr(wi),
+                                                  _ptr(value), _ptr(pdf)))
+        return wi, value, pdf
+
+    def debug_light_sample(self, light_index, positions, rand3, scene_radius=1.0):
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(rand3, np.float32).reshape(-1, 3)
+        n = p.shape[0]
+        if r.shape[0] != n:
+            raise ValueError("positions and rand3 differ in length")
+        wi, dist, pdf, em = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros((n, 16), np.float32)
+        abi.check(abi.lib().glz_debug_light_sample(self._h, light_index, _ptr(p), _ptr(r), n, scene_radius, _ptr(wi), _ptr(dist), _ptr(pdf), _ptr(em)))
+        return wi, dist, pdf, em
+
     def debug_trace_any(self, origins, dirs, tmax, tmin=1e-3):
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)

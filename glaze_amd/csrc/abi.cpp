@@ -838,6 +838,85 @@ int glz_debug_detmath(glz_instance* inst, int fn, const float* x, const float* y
   return GLZ_OK;
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_debug_bsdf_value(glz_scene* h, uint32_t material_id, const float* wo3, const float* wi3, const float* uv2, const float* rand1, const float* frame9,
+                         uint64_t n, float* value16, float* pdf) {
+  GLZ_GUARD_BEGIN
+  if (!h || !h->s || !wo3 || !wi3 || !uv2 || !rand1 || !value16 || !pdf) return fail(GLZ_E_ARG, "null argument");
+  Scene* s = h->s.get();
+  if (material_id >= s->dev.n_materials) return fail(GLZ_E_ARG, "no such material");
+  if (n == 0) return GLZ_OK;
+  if (n > 0x7FFFFFFull) return fail(GLZ_E_ARG, "too many directions");
+  Error e;
+  if (!hip_ok(hipSetDevice(s->instance->device), "hipSetDevice", e)) return fail(e);
+  hipStream_t st = s->instance->stream;
+  DeviceBuffer<float> d_wo, d_wi, d_uv, d_rand, d_frame, d_value, d_pdf;
+  if (!to_device(d_wo, wo3, n * 3, st, e) || !to_device(d_wi, wi3, n * 3, st, e) || !to_device(d_uv, uv2, 2, st, e) || !to_device(d_rand, rand1, n, st, e) ||
+      (frame9 && !to_device(d_frame, frame9, 9, st, e)))
+    return fail(e);
+  if (!hip_ok(d_value.alloc(n * 16), "alloc", e) || !hip_ok(d_pdf.alloc(n), "alloc", e)) return fail(e);
+  if (!hip_ok(launch_debug_bsdf_value(st, s->dev, material_id, d_wo.ptr, d_wi.ptr, d_uv.ptr, d_rand.ptr, frame9 ? d_frame.ptr : nullptr, (uint32_t)n, d_value.ptr,
+                                      d_pdf.ptr),
+              "k_debug_bsdf_value", e))
+    return fail(e);
+  (void)hipMemcpyAsync(value16, d_value.ptr, n * 64, hipMemcpyDeviceToHost, st);
+  (void)hipMemcpyAsync(pdf, d_pdf.ptr, n * 4, hipMemcpyDeviceToHost, st);
+  if (!hip_ok(hipStreamSynchronize(st), "debug bsdf value", e)) return fail(e);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_bsdf_sample(glz_scene* h, uint32_t material_id, const float* wo3, const float* uv2, const float* rand3, const float* frame9, uint64_t n,
+                          float* wi3, float* value16, float* pdf) {
+  GLZ_GUARD_BEGIN
+  if (!h || !h->s || !wo3 || !uv2 || !rand3 || !wi3 || !value16 || !pdf) return fail(GLZ_E_ARG, "null argument");
+  Scene* s = h->s.get();
+  if (material_id >= s->dev.n_materials) return fail(GLZ_E_ARG, "no such material");
+  if (n == 0) return GLZ_OK;
+  if (n > 0x7FFFFFFull) return fail(GLZ_E_ARG, "too many directions");
+  Error e;
+  if (!hip_ok(hipSetDevice(s->instance->device), "hipSetDevice", e)) return fail(e);
+  hipStream_t st = s->instance->stream;
+  DeviceBuffer<float> d_wo, d_uv, d_rand, d_frame, d_wi, d_value, d_pdf;
+  if (!to_device(d_wo, wo3, n * 3, st, e) || !to_device(d_uv, uv2, 2, st, e) || !to_device(d_rand, rand3, n * 3, st, e) ||
+      (frame9 && !to_device(d_frame, frame9, 9, st, e)))
+    return fail(e);
+  if (!hip_ok(d_wi.alloc(n * 3), "alloc", e) || !hip_ok(d_value.alloc(n * 16), "alloc", e) || !hip_ok(d_pdf.alloc(n), "alloc", e)) return fail(e);
+  if (!hip_ok(launch_debug_bsdf_sample(st, s->dev, material_id, d_wo.ptr, d_uv.ptr, d_rand.ptr, frame9 ? d_frame.ptr : nullptr, (uint32_t)n, d_wi.ptr, d_value.ptr,
+                                       d_pdf.ptr),
+              "k_debug_bsdf_sample", e))
+    return fail(e);
+  (void)hipMemcpyAsync(wi3, d_wi.ptr, n * 12, hipMemcpyDeviceToHost, st);
+  (void)hipMemcpyAsync(value16, d_value.ptr, n * 64, hipMemcpyDeviceToHost, st);
+  (void)hipMemcpyAsync(pdf, d_pdf.ptr, n * 4, hipMemcpyDeviceToHost, st);
+  if (!hip_ok(hipStreamSynchronize(st), "debug bsdf sample", e)) return fail(e);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_light_sample(glz_scene* h, uint32_t light_index, const float* pos3, const float* rand3, uint64_t n, float scene_radius, float* wi3,
+                           float* dist, float* pdf, float* emission16) {
+  GLZ_GUARD_BEGIN
+  if (!h || !h->s || !pos3 || !rand3 || !wi3 || !dist || !pdf || !emission16) return fail(GLZ_E_ARG, "null argument");
+  Scene* s = h->s.get();
+  if (light_index >= s->dev.n_rt_lights) return fail(GLZ_E_ARG, "no such light");
+  if (n == 0) return GLZ_OK;
+  if (n > 0x7FFFFFFull) return fail(GLZ_E_ARG, "too many positions");
+  Error e;
+  if (!hip_ok(hipSetDevice(s->instance->device), "hipSetDevice", e)) return fail(e);
+  hipStream_t st = s->instance->stream;
+  DeviceBuffer<float> d_pos, d_rand, d_wi, d_dist, d_pdf, d_em;
+  if (!to_device(d_pos, pos3, n * 3, st, e) || !to_device(d_rand, rand3, n * 3, st, e)) return fail(e);
+  if (!hip_ok(d_wi.alloc(n * 3), "alloc", e) || !hip_ok(d_dist.alloc(n), "alloc", e) || !hip_ok(d_pdf.alloc(n), "alloc", e) || !hip_ok(d_em.alloc(n * 16), "alloc", e))
+    return fail(e);
+  if (!hip_ok(launch_debug_light_sample(st, s->dev, light_index, d_pos.ptr, d_rand.ptr, (uint32_t)n, scene_radius, d_wi.ptr, d_dist.ptr, d_pdf.ptr, d_em.ptr),
+              "k_debug_light_sample", e))
+    return fail(e);
+  (void)hipMemcpyAsync(wi3, d_wi.ptr, n * 12, hipMemcpyDeviceToHost, st);
+  (void)hipMemcpyAsync(dist, d_dist.ptr, n * 4, hipMemcpyDeviceToHost, st);
+  (void)hipMemcpyAsync(pdf, d_pdf.ptr, n * 4, hipMemcpyDeviceToHost, st);
+  (void)hipMemcpyAsync(emission16, d_em.ptr, n * 64, hipMemcpyDeviceToHost, st);
+  if (!hip_ok(hipStreamSynchronize(st), "debug light sample", e)) return fail(e);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 
 int glz_renderer_device_count(glz_renderer* h) { return h ? (int)h->r->device_count() : 0; }
 int glz_renderer_device_scene_info(glz_renderer* h, int i, glz_scene_info* out) {

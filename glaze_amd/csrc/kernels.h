@@ -184,5 +184,13 @@ hipError_t launch_debug_any(hipStream_t st, const DeviceScene& scene, const floa
 hipError_t launch_debug_sample_texture(hipStream_t st, const DeviceScene& scene, uint32_t texture, const float* uv2, const float* footprint4,
                                        uint32_t n, float* rgba);
 hipError_t launch_debug_detmath(hipStream_t st, int fn, const float* x, const float* y, uint32_t n, float* out);
+// bsdf_eval / bsdf_sample / sample_light + light_emission of device/shading.h, one thread per element (uv2: one pair per call; frame9: s, t, n
+// stored as given, null = x, y, z); all pointers are device memory
+hipError_t launch_debug_bsdf_value(hipStream_t st, const DeviceScene& scene, uint32_t material, const float* wo3, const float* wi3, const float* uv2,
+                                   const float* rand1, const float* frame9, uint32_t n, float* value16, float* pdf);
+hipError_t launch_debug_bsdf_sample(hipStream_t st, const DeviceScene& scene, uint32_t material, const float* wo3, const float* uv2, const float* rand3,
+                                    const float* frame9, uint32_t n, float* wi3, float* value16, float* pdf);
+hipError_t launch_debug_light_sample(hipStream_t st, const DeviceScene& scene, uint32_t light, const float* pos3, const float* rand3, uint32_t n,
+                                     float scene_radius, float* wi3, float* dist, float* pdf, float* emission16);
 
 }  // namespace glz

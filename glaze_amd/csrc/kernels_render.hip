@@ -524,6 +524,65 @@ __global__ void __launch_bounds__(kBlock) k_debug_detmath(int fn, const float* _
   out[i] = r;
 }
 
+// The shading routines of device/shading.h one call at a time: bsdf_eval, bsdf_sample, and sample_light followed by light_emission.  The
+// surface point is built the way shade_pixel builds it (woW, uv, load_material, fetch_material_textures with the level-0 footprint of a
+// renderer without texture LOD), except that the frame is stored as given -- frame9 = s, t, n; null = (x, y, z) -- and not made by
+// make_frame.  One uv pair serves the whole call.  Outputs start as zeros; what a routine leaves unwritten when it returns early stays zero.
+__device__ __forceinline__ SurfacePoint debug_surface_point(const DeviceScene& S, uint32_t material, vec3 wo, const float* __restrict__ uv2,
+                                                            const float* __restrict__ frame9) {
+  SurfacePoint P;
+  P.woW = wo;
+  P.uv = vec2{uv2[0], uv2[1]};
+  P.frame.s = frame9 ? mk3(frame9[0], frame9[1], frame9[2]) : mk3(1.0f, 0.0f, 0.0f);
+  P.frame.t = frame9 ? mk3(frame9[3], frame9[4], frame9[5]) : mk3(0.0f, 1.0f, 0.0f);
+  P.frame.n = frame9 ? mk3(frame9[6], frame9[7], frame9[8]) : mk3(0.0f, 0.0f, 1.0f);
+  P.mat = load_material(&S.materials[material]);
+  fetch_material_textures(S, P, TexFootprint{kNoLod, 0.0f, 0.0f, 1u});
+  return P;
+}
+__global__ void __launch_bounds__(kBlock) k_debug_bsdf_value(DeviceScene S, uint32_t material, const float* __restrict__ wo3, const float* __restrict__ wi3,
+                                                             const float* __restrict__ uv2, const float* __restrict__ rand1, const float* __restrict__ frame9,
+                                                             uint32_t n, float* __restrict__ value16, float* __restrict__ pdf) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  S.tex_counter = nullptr;
+  const SurfacePoint P = debug_surface_point(S, material, mk3(wo3[3 * t], wo3[3 * t + 1], wo3[3 * t + 2]), uv2, frame9);
+  Spec value = spec_set(0.0f);
+  pdf[t] = bsdf_eval(S, P, mk3(wi3[3 * t], wi3[3 * t + 1], wi3[3 * t + 2]), rand1[t], value);
+  GLZ_BINS value16[16 * t + i] = value.w[i];
+}
+__global__ void __launch_bounds__(kBlock) k_debug_bsdf_sample(DeviceScene S, uint32_t material, const float* __restrict__ wo3, const float* __restrict__ uv2,
+                                                              const float* __restrict__ rand3, const float* __restrict__ frame9, uint32_t n,
+                                                              float* __restrict__ wi3, float* __restrict__ value16, float* __restrict__ pdf) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  S.tex_counter = nullptr;
+  const SurfacePoint P = debug_surface_point(S, material, mk3(wo3[3 * t], wo3[3 * t + 1], wo3[3 * t + 2]), uv2, frame9);
+  Spec value = spec_set(0.0f);
+  vec3 wi = mk3(0.0f, 0.0f, 0.0f);
+  pdf[t] = bsdf_sample(S, P, mk3(rand3[3 * t], rand3[3 * t + 1], rand3[3 * t + 2]), value, wi);
+  wi3[3 * t] = wi.x; wi3[3 * t + 1] = wi.y; wi3[3 * t + 2] = wi.z;
+  GLZ_BINS value16[16 * t + i] = value.w[i];
+}
+// (the sky's row search reads the marginal cdf from memory here, S.sky_cdf as the host set it; k_shade's LDS copy is the render tests' to cover)
+__global__ void __launch_bounds__(kBlock) k_debug_light_sample(DeviceScene S, uint32_t light, const float* __restrict__ pos3, const float* __restrict__ rand3,
+                                                               uint32_t n, float scene_radius, float* __restrict__ wi3, float* __restrict__ dist,
+                                                               float* __restrict__ pdf, float* __restrict__ emission16) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  S.tex_counter = nullptr;
+  LightSample ls;
+  ls.wiW = mk3(0.0f, 0.0f, 0.0f);
+  ls.pdf = 0.0f;
+  ls.distance = 0.0f;
+  sample_light(S, light, mk3(pos3[3 * t], pos3[3 * t + 1], pos3[3 * t + 2]), mk3(rand3[3 * t], rand3[3 * t + 1], rand3[3 * t + 2]), scene_radius, ls);
+  const Spec e = light_emission(ls);
+  wi3[3 * t] = ls.wiW.x; wi3[3 * t + 1] = ls.wiW.y; wi3[3 * t + 2] = ls.wiW.z;
+  dist[t] = ls.distance;
+  pdf[t] = ls.pdf;
+  GLZ_BINS emission16[16 * t + i] = e.w[i];
+}
+
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -603,6 +662,24 @@ hipError_t launch_debug_sample_texture(hipStream_t st, const DeviceScene& scene,
 hipError_t launch_debug_detmath(hipStream_t st, int fn, const float* x, const float* y, uint32_t n, float* out) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_debug_detmath, grid_for(n), dim3(kBlock), 0, st, fn, x, y, n, out);
+  return hipGetLastError();
+}
+hipError_t launch_debug_bsdf_value(hipStream_t st, const DeviceScene& scene, uint32_t material, const float* wo3, const float* wi3, const float* uv2,
+                                   const float* rand1, const float* frame9, uint32_t n, float* value16, float* pdf) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_debug_bsdf_value, grid_for(n), dim3(kBlock), 0, st, scene, material, wo3, wi3, uv2, rand1, frame9, n, value16, pdf);
+  return hipGetLastError();
+}
+hipError_t launch_debug_bsdf_sample(hipStream_t st, const DeviceScene& scene, uint32_t material, const float* wo3, const float* uv2, const float* rand3,
+                                    const float* frame9, uint32_t n, float* wi3, float* value16, float* pdf) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_debug_bsdf_sample, grid_for(n), dim3(kBlock), 0, st, scene, material, wo3, uv2, rand3, frame9, n, wi3, value16, pdf);
+  return hipGetLastError();
+}
+hipError_t launch_debug_light_sample(hipStream_t st, const DeviceScene& scene, uint32_t light, const float* pos3, const float* rand3, uint32_t n,
+                                     float scene_radius, float* wi3, float* dist, float* pdf, float* emission16) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_debug_light_sample, grid_for(n), dim3(kBlock), 0, st, scene, light, pos3, rand3, n, scene_radius, wi3, dist, pdf, emission16);
   return hipGetLastError();
 }
 

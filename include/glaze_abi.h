@@ -552,6 +552,17 @@ int glz_debug_tonemap(glz_instance*, const float* rgba32f, uint64_t n_pixels, ui
 int glz_debug_sample_texture(glz_scene*, uint32_t texture, const float* uv2, const float* footprint4_or_null, uint64_t n, float* rgba_out);
 /* include/glz_detmath.h on the device: fn 0 sin, 1 cos, 2 acos, 3 atan2(y, x), 4 log2, 5 floor of n values (y only for atan2) */
 int glz_debug_detmath(glz_instance*, int fn, const float* x, const float* y, float* out, uint64_t n);
+/* The kernels' shading routines one call at a time, n elements each (device/shading.h: bsdf_eval, bsdf_sample, sample_light followed by
+ * light_emission).  The surface point is set up as the shading kernel sets it up (material scalars, the material's textures at level 0
+ * for the ONE pair uv2 of the call), except the frame: frame9 = s, t, n, stored as given, NULL = (1,0,0), (0,1,0), (0,0,1).  value16 /
+ * emission16 take 16 floats per element.  Outputs start as zeros and keep them where a routine returns early (pdf 0).  A material id or
+ * light index (RTLight records: an area light has one per instance) out of range is GLZ_E_ARG. */
+int glz_debug_bsdf_value(glz_scene*, uint32_t material_id, const float* wo3, const float* wi3, const float* uv2, const float* rand1,
+                         const float* frame9_or_null, uint64_t n, float* value16_out, float* pdf_out);
+int glz_debug_bsdf_sample(glz_scene*, uint32_t material_id, const float* wo3, const float* uv2, const float* rand3, const float* frame9_or_null,
+                          uint64_t n, float* wi3_out, float* value16_out, float* pdf_out);
+int glz_debug_light_sample(glz_scene*, uint32_t light_index, const float* pos3, const float* rand3, uint64_t n, float scene_radius,
+                           float* wi3_out, float* dist_out, float* pdf_out, float* emission16_out);
 
 /* The device filter of glz_denoise_params on host arrays (w*h*4 floats each, row-major): upload, kernels, read back.  params NULL = defaults. */
 int glz_debug_denoise(glz_instance*, uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1,

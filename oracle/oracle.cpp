@@ -2370,12 +2370,18 @@ int orc_sample_texture(void* s, uint32_t texture, const float* uv2, const float*
 }
 uint32_t orc_pcg_hash(uint32_t x) { return pcg_hash(x); }
 // ---- shading routines on their own, for the tests that check this restatement against mathematics (tests/test_oracle_math.py) ----
-// n evaluations of the material's BSDF in the canonical frame (s, t, n) = (x, y, z), so world directions ARE shading-space
-// directions: value (16 bins) and pdf of mat_*_value.rcall for (wo, wi, uv, rand)
-void orc_bsdf_value(void* s, uint32_t material_id, const float* wo3, const float* wi3, const float* uv2, const float* rand1, uint64_t n,
-                    float* value16, float* pdf) {
+// the shading frame of the calls below: frame9 = s, t, n as given (stored as they are, not orthonormalised), or null for the canonical
+// frame (s, t, n) = (x, y, z), in which world directions ARE shading-space directions
+static ShadingSpace harness_frame(const float* f) {
+  if (!f) return ShadingSpace{v3(1, 0, 0), v3(0, 1, 0), v3(0, 0, 1)};
+  return ShadingSpace{v3(f[0], f[1], f[2]), v3(f[3], f[4], f[5]), v3(f[6], f[7], f[8])};
+}
+// n evaluations of the material's BSDF: value (16 bins) and pdf of mat_*_value.rcall for (wo, wi, uv, rand)
+// (orc_bsdf_value / orc_bsdf_sample keep the argument lists they have always had, in the canonical frame; the _framed entries add frame9)
+void orc_bsdf_value_framed(void* s, uint32_t material_id, const float* wo3, const float* wi3, const float* uv2, const float* rand1, const float* frame9,
+                           uint64_t n, float* value16, float* pdf) {
   Scene* sc = (Scene*)s;
-  ShadingSpace sh{v3(1, 0, 0), v3(0, 1, 0), v3(0, 0, 1)};
+  ShadingSpace sh = harness_frame(frame9);
   for (uint64_t i = 0; i < n; ++i) {
     BsdfIn in{v3(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]), v3(wi3[3 * i], wi3[3 * i + 1], wi3[3 * i + 2]), V2{uv2[0], uv2[1]}, sh, material_id};
     Sp value = sp_uniform(0.0f);
@@ -2384,10 +2390,10 @@ void orc_bsdf_value(void* s, uint32_t material_id, const float* wo3, const float
   }
 }
 // n samples of mat_*_sample_value.rcall for (wo, uv, rand3): sampled direction, value (16 bins), pdf
-void orc_bsdf_sample(void* s, uint32_t material_id, const float* wo3, const float* uv2, const float* rand3, uint64_t n, float* wi3, float* value16,
-                     float* pdf) {
+void orc_bsdf_sample_framed(void* s, uint32_t material_id, const float* wo3, const float* uv2, const float* rand3, const float* frame9, uint64_t n,
+                            float* wi3, float* value16, float* pdf) {
   Scene* sc = (Scene*)s;
-  ShadingSpace sh{v3(1, 0, 0), v3(0, 1, 0), v3(0, 0, 1)};
+  ShadingSpace sh = harness_frame(frame9);
   for (uint64_t i = 0; i < n; ++i) {
     BsdfIn in{v3(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]), v3(0, 0, 0), V2{uv2[0], uv2[1]}, sh, material_id};
     Sp value = sp_uniform(0.0f);
@@ -2396,6 +2402,14 @@ void orc_bsdf_sample(void* s, uint32_t material_id, const float* wo3, const floa
     wi3[3 * i] = wi.x; wi3[3 * i + 1] = wi.y; wi3[3 * i + 2] = wi.z;
     memcpy(value16 + 16 * i, value.w, 64);
   }
+}
+void orc_bsdf_value(void* s, uint32_t material_id, const float* wo3, const float* wi3, const float* uv2, const float* rand1, uint64_t n,
+                    float* value16, float* pdf) {
+  orc_bsdf_value_framed(s, material_id, wo3, wi3, uv2, rand1, nullptr, n, value16, pdf);
+}
+void orc_bsdf_sample(void* s, uint32_t material_id, const float* wo3, const float* uv2, const float* rand3, uint64_t n, float* wi3, float* value16,
+                     float* pdf) {
+  orc_bsdf_sample_framed(s, material_id, wo3, uv2, rand3, nullptr, n, wi3, value16, pdf);
 }
 // n samples of light_*_sample_visible.rcall for RTLight `light_index`: direction, distance, pdf, emission (16 bins)
 void orc_light_sample(void* s, uint32_t light_index, const float* pos3, const float* rand3, uint64_t n, float scene_radius, float* wi3, float* dist,

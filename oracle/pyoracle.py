@@ -48,7 +48,9 @@ def lib():
             "orc_renderer_push_constants": (None, [_P, _P]),
             "orc_renderer_set_tiles": (None, [_P, _P, C.c_uint32]), "orc_to_srgb8": (C.c_uint8, [C.c_float]),
             "orc_bsdf_value": (None, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P, _P]),
+            "orc_bsdf_value_framed": (None, [_P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64, _P, _P]),
             "orc_bsdf_sample": (None, [_P, C.c_uint32, _P, _P, _P, C.c_uint64, _P, _P, _P]),
+            "orc_bsdf_sample_framed": (None, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P, _P, _P]),
             "orc_light_sample": (None, [_P, C.c_uint32, _P, _P, C.c_uint64, C.c_float, _P, _P, _P, _P]),
             "orc_scene_rt_light_count": (C.c_uint32, [_P]),
             "orc_renderer_set_texture_lod": (None, [_P, C.c_int]),
@@ -144,24 +146,27 @@ class OracleScene:
         lib().orc_trace_closest(self.handle, _ptr(o), _ptr(d), n, tmin, _ptr(t), _ptr(tri), _ptr(inst), _ptr(u), _ptr(v))
         return t, tri, inst, u, v
 
-    # ---- shading routines on their own (tests/test_oracle_math.py); directions are in the canonical shading frame ----
-    def bsdf_value(self, material_id, wo, wi, uv=(0.5, 0.5), rand=None):
+    # ---- shading routines on their own (tests/test_oracle_math.py); frame: 9 floats s, t, n taken as given, None = the canonical
+    # shading frame (x, y, z), in which the directions are shading-space directions ----
+    def bsdf_value(self, material_id, wo, wi, uv=(0.5, 0.5), rand=None, frame=None):
         wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
         wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
         n = wo.shape[0]
         rnd = np.ascontiguousarray(rand if rand is not None else np.zeros(n), np.float32)
         uvv = np.ascontiguousarray(uv, np.float32)
         value, pdf = np.zeros((n, 16), np.float32), np.zeros(n, np.float32)
-        lib().orc_bsdf_value(self.handle, material_id, _ptr(wo), _ptr(wi), _ptr(uvv), _ptr(rnd), n, _ptr(value), _ptr(pdf))
+        fr = None if frame is None else np.ascontiguousarray(frame, np.float32).reshape(9)
+        lib().orc_bsdf_value_framed(self.handle, material_id, _ptr(wo), _ptr(wi), _ptr(uvv), _ptr(rnd), None if fr is None else _ptr(fr), n, _ptr(value), _ptr(pdf))
         return value, pdf
 
-    def bsdf_sample(self, material_id, wo, rand3, uv=(0.5, 0.5)):
+    def bsdf_sample(self, material_id, wo, rand3, uv=(0.5, 0.5), frame=None):
         wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
         r = np.ascontiguousarray(rand3, np.float32).reshape(-1, 3)
         n = wo.shape[0]
         uvv = np.ascontiguousarray(uv, np.float32)
         wi, value, pdf = np.zeros((n, 3), np.float32), np.zeros((n, 16), np.float32), np.zeros(n, np.float32)
-        lib().orc_bsdf_sample(self.handle, material_id, _ptr(wo), _ptr(uvv), _ptr(r), n, _ptr(wi), _ptr(value), _ptr(pdf))
+        fr = None if frame is None else np.ascontiguousarray(frame, np.float32).reshape(9)
+        lib().orc_bsdf_sample_framed(self.handle, material_id, _ptr(wo), _ptr(uvv), _ptr(r), None if fr is None else _ptr(fr), n, _ptr(wi), _ptr(value), _ptr(pdf))
         return wi, value, pdf
 
     def light_sample(self, light_index, positions, rand3, scene_radius=1.0):
