@@ -178,7 +178,7 @@ struct alignas(16) TlasInstance {
 static_assert(sizeof(TlasInstance) == 192, "TlasInstance is 12 x 16 bytes");
 
 // World-space triangle in BVH leaf order, 48 bytes (36 algorithmic + ids).  The three VERTICES, not a vertex and two edges:
-// the watertight test (ray_triangle) needs the floats two triangles share to be the same floats in both records.
+// the watertight test (device/intersect.h ray_quad) needs the floats two triangles share to be the same floats in both records.
 struct alignas(16) BvhTri {
   float v0[3]; uint32_t world_id;   // instance-major id: tie-break key for equal t
   float v1[3]; uint32_t instance;

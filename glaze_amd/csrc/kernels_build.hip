@@ -1036,7 +1036,7 @@ __global__ void __launch_bounds__(256) k_dfs_ids(int n, const int2* __restrict__
 }
 
 // Quantisation grid from the root box: kBvhGridMax (32 767) cells per axis, stretched by 2^-16 so the top plane stays below it.  15 bits:
-// the tracer turns a coordinate into the float 32768 + q with one byte permute (device/wavefront.h box_key).
+// the tracer turns a coordinate into the float 32768 + q with one byte permute (device/intersect.h box_key).
 constexpr float kGridReach = 1.9073486e-6f;   // 2^-19
 __global__ void k_grid_params(const float4* __restrict__ node_lo, const float4* __restrict__ node_hi, BvhGrid* __restrict__ grid) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;

@@ -3,7 +3,10 @@
 // (v_mov 2.0, 0.5, ... and scalar literals) into the loop's preheader, where they stay live through the whole body -- 170 scratch
 // loads / 75 stores and 55 SGPR-to-lane spills in the 128-register kernel against 40 / 9 / 4 without the pass -- and the shading
 // phase of a wave took 55 us instead of 28 (tools/gpu_path_phases.py).
-#include "device/wavefront.h"
+#include "device/path_state.h"
+#include "device/shade_pixel.h"
+#include "device/trace_wave.h"
+#include "launch_geometry.h"
 
 namespace glz {
 using namespace dev;
@@ -105,10 +108,9 @@ struct GroupMixedSink {
   }
 };
 
-// The kernel's arguments, re-read: behind the empty asm the compiler no longer knows that the pointer is the one it has been loading
-// from, so what a phase of k_path needs of the arguments is loaded (scalar loads from the kernarg segment) where the phase begins and
-// dies where it ends -- instead of every pointer either phase uses staying in SGPRs through the whole launch loop (tracing and shading
-// together use more of them than there are: 233 of them went to VGPR lanes, and the VGPRs those took to scratch).
+// (reread_kernarg, device/shade_pixel.h: what a phase of k_path needs of the arguments is loaded where the phase begins and dies where
+// it ends -- instead of every pointer either phase uses staying in SGPRs through the whole launch loop (tracing and shading together
+// use more of them than there are: 233 of them went to VGPR lanes, and the VGPRs those took to scratch).)
 // RTFrameData of launch L of the batch: what all launches share (LaunchArgs::frame) with the three per-launch fields from the batch
 __device__ __forceinline__ FrameData launch_frame(const LaunchArgs& A, const PathBatch& B, uint32_t L) {
   FrameData F = A.frame;
@@ -265,14 +267,7 @@ static uint32_t path_table_bytes(const DeviceScene& sc) {
   return bytes <= kShadeTableBytes ? bytes : 0u;
 }
 uint32_t path_resident_blocks(const DeviceScene& sc) {
-  int dev = 0, cus = 256, per_cu = 4;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-  }
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_path<false>, kBlock, path_table_bytes(sc)) != hipSuccess || per_cu < 1) per_cu = 2;
-  per_cu = std::min(per_cu, 8);
-  return (uint32_t)cus * (uint32_t)per_cu;
+  return resident_blocks(k_path<false>, path_table_bytes(sc), 2);
 }
 uint32_t path_grid_blocks(uint32_t n_local_pixels, const DeviceScene& sc) {
   const uint32_t groups = (n_local_pixels + 63u) / 64u, blocks = (groups + kBlock / 64 - 1) / (kBlock / 64);

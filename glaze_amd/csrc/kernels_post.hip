@@ -2,7 +2,11 @@
 // primary ray through every pixel centre) and the edge-avoiding a-trous filter that uses them as guides (denoise.h holds the filter's
 // arithmetic, shared with the host reference).  Nothing here touches the path state or the accumulators of the render kernels.
 #include "denoise.h"
-#include "device/wavefront.h"
+#include "device/path_state.h"
+#include "device/shading.h"
+#include "device/trace_wave.h"
+#include "device/trace_wave_tl.h"
+#include "launch_geometry.h"
 
 namespace glz {
 using namespace dev;
@@ -156,7 +160,6 @@ __global__ void __launch_bounds__(kBlock) k_atrous(uint32_t w, uint32_t h, uint3
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-static inline dim3 grid_for(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
 // blocks of k_first_hit's persistent grid (the render tracers' residency rule)
 uint32_t first_hit_grid_blocks(uint32_t n_rays) { return persistent_grid(k_first_hit, n_rays).x; }
 hipError_t launch_first_hit(hipStream_t st, const LaunchArgs& a, uint32_t blocks, float4* hit, uint32_t* inst) {
@@ -168,15 +171,11 @@ hipError_t launch_first_hit(hipStream_t st, const LaunchArgs& a, uint32_t blocks
 }
 hipError_t launch_first_hit_attributes(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, float4* aov0, float4* aov1) {
   const uint32_t n = a.map.width * a.map.height;
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_first_hit_attributes, grid_for(n), dim3(kBlock), 0, st, a, hit, inst, aov0, aov1);
-  return hipGetLastError();
+  return launch_per_item(st, k_first_hit_attributes, n, a, hit, inst, aov0, aov1);
 }
 hipError_t launch_camera_rays(hipStream_t st, const LaunchArgs& a, float off_x, float off_y, float* origins3, float* dirs3) {
   const uint32_t n = a.map.width * a.map.height;
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_camera_rays, grid_for(n), dim3(kBlock), 0, st, a, off_x, off_y, origins3, dirs3);
-  return hipGetLastError();
+  return launch_per_item(st, k_camera_rays, n, a, off_x, off_y, origins3, dirs3);
 }
 hipError_t launch_denoise(hipStream_t st, uint32_t w, uint32_t h, const glz_denoise_params& P, const float4* result, const float4* aov0, const float4* aov1,
                           float4* ping, float4* pong, float4* out, hipEvent_t* marks) {

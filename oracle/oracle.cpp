@@ -1071,7 +1071,7 @@ inline uint32_t fbits(float f);
 struct ExtNode { uint32_t w[16]; };   // BvhNode4
 struct ExtTri { float v0[3]; uint32_t world_id; float v1[3]; uint32_t instance; float v2[3]; uint32_t prim_flags; };
 inline float box_entry_q(float lox, float loy, float loz, float hix, float hiy, float hiz, V3 ig, V3 cg, float tmin, float tmax) {
-  // plane distances as one correctly rounded fma each (device/wavefront.h box_key: v_pk_fma_f32).  The kernel's byte permute hands the
+  // plane distances as one correctly rounded fma each (device/intersect.h box_key: v_pk_fma_f32).  The kernel's byte permute hands the
   // fma the float 32768 + q (exact: q < 32768) and the addend carries the - 32768 ig (grid_addend): restated here operation for operation
   const float M = 32768.0f;
   const float ax = fmaf(M + lox, ig.x, cg.x), bx = fmaf(M + hix, ig.x, cg.x);
@@ -1106,7 +1106,7 @@ void ext_trace(const Scene& sc, V3 o, V3 d, float tmin, float tmax, bool any, Co
         // one word per axis: lo | hi << 16
         const float e = box_entry_q((float)(w[3 * k] & 0xFFFFu), (float)(w[3 * k + 1] & 0xFFFFu), (float)(w[3 * k + 2] & 0xFFFFu), (float)(w[3 * k] >> 16),
                                     (float)(w[3 * k + 1] >> 16), (float)(w[3 * k + 2] >> 16), ig, cg, tmin, best);
-        key[k] = (e < INF && w[12 + k] != 0x7FFFFFFFu) ? ((fbits(e) & 0xFFFFFC00u) | (k << 8)) : 0xFFFFFFFFu;   // box_key, device/wavefront.h: distance bits, child index in bits 8..9
+        key[k] = (e < INF && w[12 + k] != 0x7FFFFFFFu) ? ((fbits(e) & 0xFFFFFC00u) | (k << 8)) : 0xFFFFFFFFu;   // box_key, device/intersect.h: distance bits, child index in bits 8..9
       }
       std::sort(key, key + 4);
       if (key[0] != 0xFFFFFFFFu) {

@@ -1,6 +1,6 @@
 """Which hits the "det is rounding noise" rule may drop, pinned from OUTSIDE the oracle.
 
-oracle.cpp ray_tri = device/wavefront.h triangle_finish leave a candidate out when |U + V + W| is not above 2^-19 of
+oracle.cpp ray_tri = device/intersect.h triangle_finish leave a candidate out when |U + V + W| is not above 2^-19 of
 (|first product of U| + |of V| + |of W|): the ray lies in the triangle's plane as far as single precision can tell.  The reference's
 hits come from the driver's intersector, which has no such rule, so the rule must only ever take what no intersector in floats could
 decide anyway.  Here a float64 statement of ray / triangle intersection (plane equation + barycentrics, nothing shared with the

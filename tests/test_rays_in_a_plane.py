@@ -1,4 +1,4 @@
-"""A ray that lies in the plane of a triangle hits nothing (oracle.cpp ray_tri, device/wavefront.h triangle_finish: a candidate whose
+"""A ray that lies in the plane of a triangle hits nothing (oracle.cpp ray_tri, device/intersect.h triangle_finish: a candidate whose
 det is not above 2^-19 of its products is rounding noise, not a hit) -- stated on a designed scene: a tessellated floor with a raised
 step on it, (a) in an axis-aligned plane near coordinate 0 (translated and scaled only), (b) rotated.
   * shadow rays from a point of the floor to other points of the floor (what sampling a light that lies in the floor's plane

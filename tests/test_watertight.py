@@ -2,7 +2,7 @@
 
 The reference's hits come from traceRayEXT (lib/src/shaders/path_trace.rgen:169, :106-109) on the driver's acceleration
 structure (lib/src/vulkan/acceleration.rs:319-345), and the Vulkan specification requires that intersector to be watertight.
-The build's intersector (oracle.cpp ray_tri = kernels_render.hip ray_triangle) gets there by construction -- the edge function
+The build's intersector (oracle.cpp ray_tri = device/intersect.h ray_quad) gets there by construction -- the edge function
 of a shared edge is the same number with the opposite sign in the two triangles -- and these tests look for the leak that
 Moeller-Trumbore, which rounds 1-2 ran, shows: rays aimed at vertices, at points of edges and along the diagonals of
 pixel-aligned quads.  Oracle on the CPU; the HIP path on the GPU must give the same hits bit for bit.

@@ -1,6 +1,6 @@
 """Why does the HIP tracer not find a triangle?  For one ray of a fuzz scene: every triangle of the flattened structure through a numpy
 restatement of the triangle test, then the boxes on the way from the root to the leaf that holds the accepted one through a numpy
-restatement of the slab test (device/wavefront.h box_key).
+restatement of the slab test (device/intersect.h box_key).
     python tools/gpu_fuzz_walk.py SEED ox oy oz dx dy dz tmax [tmin]
 """
 import sys

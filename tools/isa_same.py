@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""Compares the gfx950 code of two builds, symbol by symbol:  tools/isa_same.py OLD_DIR NEW_DIR
+
+OLD_DIR / NEW_DIR hold the kernels_*.o of a build (glaze_amd/csrc/build of two checkouts, each built with `make`).  For every kernel and
+device function in OLD's objects the same symbol is looked up in NEW -- in the object of the same name first, then in whichever object
+holds it (code that moved to another file) -- and the two disassemblies are compared; the line says `same`, `differs` or `missing`,
+followed, for a kernel, by the code object's figures in both builds (as tools/isa_meta.sh prints them): VGPRs, VGPR spills, scratch
+bytes, LDS bytes.  What does not count as a difference is what moves with the position of the code and not with the code: the address /
+encoding comments, the literals of the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64 (the pc-relative distance to a function that is
+called, not inlined), and the padding behind a symbol's last s_endpgm.  Exit status 1 when a symbol differs or is missing.
+(The .o is a fat binary: llvm-objdump --offloading extracts the device ELF first, as in tools/isa_dump.sh.)
+"""
+import glob
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'lib/llvm/bin')
+FIGURES = [('vgpr', '.vgpr_count'), ('vgpr_spill', '.vgpr_spill_count'), ('scratch', '.private_segment_fixed_size'), ('lds', '.group_segment_fixed_size')]
+
+
+def run(*cmd, cwd=None):
+    return subprocess.run(cmd, cwd=cwd, check=True, capture_output=True, text=True).stdout
+
+
+def normalise(lines):
+    """The instructions of one symbol without what depends on where the code sits."""
+    out, pcrel = [], 0
+    for line in lines:
+        ins = line.split('//')[0].strip()
+        if not ins or ins == '...':
+            continue
+        if ins.startswith('s_getpc_b64'):
+            pcrel = 2
+        elif pcrel and re.match(r's_addc?_u32 ', ins):
+            ins = ins.rsplit(',', 1)[0] + ', <pc-relative>'
+            pcrel -= 1
+        out.append(ins)
+    last = max((i for i, ins in enumerate(out) if ins.startswith('s_endpgm')), default=None)
+    if last is not None and all(ins.startswith('s_nop') for ins in out[last + 1:]):
+        del out[last + 1:]
+    return out
+
+
+def load(directory):
+    """{object name: {symbol: (instructions, figures or None)}} of the kernels_*.o in `directory` (or in its build/)."""
+    objects = sorted(glob.glob(os.path.join(directory, 'kernels_*.o'))) or sorted(glob.glob(os.path.join(directory, 'build', 'kernels_*.o')))
+    if not objects:
+        sys.exit('no kernels_*.o in %s' % directory)
+    build = {}
+    for obj in objects:
+        tmp = tempfile.mkdtemp()
+        try:
+            shutil.copy(obj, os.path.join(tmp, 'in.o'))
+            run(os.path.join(LLVM, 'llvm-objdump'), '--offloading', 'in.o', cwd=tmp)
+            elf = glob.glob(os.path.join(tmp, 'in.o.*gfx950*'))[0]
+            figures, name = {}, None
+            for line in run(os.path.join(LLVM, 'llvm-readelf'), '--notes', elf).splitlines():
+                m = re.match(r'\s+(?:- )?(\.[a-z_]+):\s+(\S+)\s*$', line)
+                if not m:
+                    continue
+                if line.startswith('  - '):   # a new entry of amdhsa.kernels
+                    name, pending = None, {}
+                if m.group(1) == '.name' and not line.startswith('      '):
+                    name = m.group(2)
+                    figures[name] = pending
+                elif not line.startswith('      '):   # (six spaces: a field of one of the kernel's arguments)
+                    (figures[name] if name else pending)[m.group(1)] = m.group(2)
+            symbols, current = {}, None
+            for line in run(os.path.join(LLVM, 'llvm-objdump'), '-d', '--mcpu=gfx950', elf).splitlines():
+                m = re.match(r'[0-9a-f]+ <(.+)>:$', line)
+                if m:
+                    current = symbols.setdefault(m.group(1), [])
+                elif current is not None and line.startswith('\t'):
+                    current.append(line)
+            build[os.path.basename(obj)] = {s: (normalise(l), figures.get(s)) for s, l in symbols.items()}
+        finally:
+            shutil.rmtree(tmp)
+    return build
+
+
+def main():
+    if len(sys.argv) != 3:
+        sys.exit(__doc__)
+    old, new = load(sys.argv[1]), load(sys.argv[2])
+    names = [s for syms in old.values() for s in syms]
+    filt = shutil.which('llvm-cxxfilt', path=LLVM) or shutil.which('c++filt')   # readable names where a demangler is at hand
+    plain = dict(zip(names, run(filt, *names).splitlines() if filt and names else names))
+    bad = 0
+    for obj, syms in old.items():
+        for sym, (code, fig) in syms.items():
+            where = obj if sym in new.get(obj, {}) else next((o for o in new if sym in new[o]), None)
+            if where is None:
+                verdict, fig2 = 'missing', None
+            else:
+                code2, fig2 = new[where][sym]
+                verdict = 'same' if code == code2 else 'differs'
+            bad += verdict != 'same'
+            text = '%-8s%s  [%s -> %s]' % (verdict, re.sub(r'\(.*', '', plain[sym]), obj, where or '-')
+            if fig is not None:
+                text += '  ' + '  '.join('%s %s/%s' % (label, fig.get(key, '-'), (fig2 or {}).get(key, '-')) for label, key in FIGURES)
+                if fig2 is not None and any(fig.get(key) != fig2.get(key) for _, key in FIGURES):
+                    text += '  FIGURES DIFFER'
+                    bad += 1
+            print(text)
+    print('%d symbols of %s compared with %s: %s' % (len(names), sys.argv[1], sys.argv[2], 'all same' if not bad else '%d not the same' % bad))
+    return 1 if bad else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
