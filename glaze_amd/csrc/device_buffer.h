@@ -44,4 +44,12 @@ struct DeviceBuffer {
   }
 };
 
+// buffers of n entries each; the first error ends it
+template <class... Buffers>
+inline hipError_t alloc_each(size_t n, Buffers&... buffers) {
+  hipError_t e = hipSuccess;
+  ((e = e == hipSuccess ? buffers.alloc(n) : e), ...);
+  return e;
+}
+
 }  // namespace glz

@@ -1,4 +1,4 @@
-// Host-callable launchers of the HIP kernels (kernels_build.hip, kernels_render.hip, kernels_path.hip, kernels_post.hip).
+// Host-callable launchers of the HIP kernels (kernels_records.hip, kernels_build.hip, kernels_render.hip, kernels_path.hip, kernels_post.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,7 +12,7 @@ namespace glz {
 // ---- scene build --------------------------------------------------------------------------------
 hipError_t launch_derivatives(hipStream_t st, const float4* vertices, const uint32_t* indices, uint32_t n_tris, float4* out);
 
-struct LbvhInputs {
+struct HierarchyInputs {
   const float4* vertices;
   const uint32_t* indices;
   const RTInstance* instances;
@@ -30,15 +30,15 @@ struct LbvhInputs {
   // The flattened world build: also emit the 64-byte per-leaf records (BvhQuad) and make leaf links ~leaf number instead of
   // ~first triangle slot (the record names the slot).  Pairs are only formed in the two vertex orders a quad record can hold.
   bool emit_quads = false;
-  // ... and the same hierarchy collapsed eight wide (types.h BvhNode8; needs emit_quads): LbvhOutputs::nodes8
+  // ... and the same hierarchy collapsed eight wide (types.h BvhNode8; needs emit_quads): HierarchyOutputs::nodes8
   bool emit_wide8 = false;
 };
 constexpr int kBvhBuilderLbvh = 0, kBvhBuilderPloc = 1, kBvhBuilderSah = 2, kBvhBuilderAuto = 3, kBvhBuilderSahHost = 4;   // = GLZ_BVH_LBVH / _PLOC / _SAH / _AUTO / _SAH_HOST
 // host side of the SAH builder (bvh_sah.cpp): binary hierarchy over n leaf boxes -> children / parent arrays
 void build_sah_host(uint32_t n, const float4* lo, const float4* hi, int2* children, int* parent);
-// nodes / nodes8 / quads are allocated by build_lbvh and owned by this struct: what the caller wants to keep it moves out, the rest is
+// nodes / nodes8 / quads are allocated by build_hierarchy and owned by this struct: what the caller wants to keep it moves out, the rest is
 // freed with the struct -- also after a failed build, whatever it got to.  Their .count is the number of entries.
-struct LbvhOutputs {
+struct HierarchyOutputs {
   DeviceBuffer<BvhNode4> nodes;    // empty for n_world = 0
   DeviceBuffer<BvhNode8> nodes8;   // emit_wide8, else empty; a scene of one leaf has none
   uint32_t depth8;
@@ -47,10 +47,9 @@ struct LbvhOutputs {
   DeviceBuffer<BvhQuad> quads;     // emit_quads: one record per leaf, else empty
   uint32_t depth;   // number of 4-wide nodes above the deepest leaf (the traversal stack holds at most 3 * depth + 1 entries)
   float sah;
-  uint32_t rounds;  // PLOC merge rounds (0 for the LBVH)
   float bounds_lo[3], bounds_hi[3];
 };
-hipError_t build_lbvh(hipStream_t st, const LbvhInputs& in, LbvhOutputs& out);
+hipError_t build_hierarchy(hipStream_t st, const HierarchyInputs& in, HierarchyOutputs& out);
 // top-of-tree table for LDS staging (types.h kBvhTopNodes): `top` receives kBvhTopNodes nodes
 hipError_t launch_top_table(hipStream_t st, const BvhNode4* nodes, uint32_t n_nodes, BvhNode4* top);
 // 128-byte per-leaf shading records (see k_shade_records); xf_identity[t] != 0 marks an exact identity transform

@@ -698,7 +698,7 @@ double instance_reach(const std::vector<float4>& blo, const std::vector<float4>&
 
 // Two-level structure (types.h TlasInstance; acceleration.rs:319-345: a BLAS per mesh, a TLAS over the instances).  The meshes'
 // hierarchies are built by the ordinary builder over ONE pseudo-instance with the identity transform (object space = its "world"),
-// the top level by the same builder over the instances' world boxes (LbvhInputs::given_lo).  Memory is O(meshes + instances).
+// the top level by the same builder over the instances' world boxes (HierarchyInputs::given_lo).  Memory is O(meshes + instances).
 bool Scene::build_two_level(Error& err) {
   hipStream_t st = instance->stream;
   StreamTimer timer;
@@ -747,13 +747,13 @@ bool Scene::build_two_level(Error& err) {
     const RTInstance pseudo{m.mesh.index_offset, m.mesh.index_count, 0u, 0u};
     if (!hip_ok(hipMemcpyAsync(d_pseudo.ptr, &pseudo, sizeof(pseudo), hipMemcpyHostToDevice, st), "upload", err) || !hip_ok(hipStreamSynchronize(st), "upload", err))
       return false;
-    LbvhInputs in{d_vertices_.ptr, d_indices_.ptr, d_pseudo.ptr, d_zero.ptr, 1u, d_ident.ptr, d_opaque.ptr, n, build_opts_.builder, build_opts_.pair_area_ratio};
+    HierarchyInputs in{d_vertices_.ptr, d_indices_.ptr, d_pseudo.ptr, d_zero.ptr, 1u, d_ident.ptr, d_opaque.ptr, n, build_opts_.builder, build_opts_.pair_area_ratio};
     in.emit_quads = true;   // 64-byte leaf records (object space here), leaf links ~leaf number relative to the mesh
-    LbvhOutputs out{};
+    HierarchyOutputs out{};
     DeviceBuffer<BvhTri> tris;
     if (!hip_ok(tris.alloc((size_t)n + 1), "alloc mesh triangles", err)) return false;
     out.tris = tris.ptr;
-    if (!hip_ok(build_lbvh(st, in, out), "mesh hierarchy", err)) return false;
+    if (!hip_ok(build_hierarchy(st, in, out), "mesh hierarchy", err)) return false;
     m.nodes = std::move(out.nodes);
     m.quads = std::move(out.quads);   // the mesh's leaf records (object space)
     m.mesh.grid = out.grid;
@@ -814,14 +814,14 @@ bool Scene::assemble_top_level(const float4* d_lo, const float4* d_hi, std::vect
   hipStream_t st = instance->stream;
   const size_t ni = h_instances.size();
   DeviceBuffer<BvhTri> top_tris;
-  LbvhOutputs top{};
+  HierarchyOutputs top{};
   if (!hip_ok(top_tris.alloc(ni + 1), "alloc", err)) return false;
   {
-    LbvhInputs in{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, (uint32_t)ni, build_opts_.builder, 0.0f};
+    HierarchyInputs in{nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, (uint32_t)ni, build_opts_.builder, 0.0f};
     in.given_lo = d_lo;
     in.given_hi = d_hi;
     top.tris = top_tris.ptr;
-    if (!hip_ok(build_lbvh(st, in, top), "instance hierarchy", err)) return false;
+    if (!hip_ok(build_hierarchy(st, in, top), "instance hierarchy", err)) return false;
   }
   // ---- one node array: top level first, then the meshes (moved as they are when the top level's size changes) ----
   const MeshRange& last = h_mesh_ranges.back();   // (a two-level scene has a mesh)
@@ -917,7 +917,7 @@ bool Scene::write_top_records(const std::vector<BvhTri>& order, double reach, Er
 }
 
 // info, stack bound and DeviceScene of a two-level scene whose node array (top level first) and records are in place
-void Scene::finish_two_level(const LbvhOutputs& top, float build_ms) {
+void Scene::finish_two_level(const HierarchyOutputs& top, float build_ms) {
   const uint32_t n_nodes = (uint32_t)d_nodes_.count, nt = (uint32_t)(d_tris_.count - 1), ni = (uint32_t)h_instances.size();
   info.bvh_nodes = n_nodes;
   info.bvh_depth = top.depth + tl_mesh_depth_;
@@ -978,20 +978,20 @@ bool Scene::build_bvh(Error& err) {
   d_nodes_.release();
   if (!hip_ok(d_tris_.alloc((size_t)n + 1), "alloc BVH triangles", err)) return false;   // + 1: the tracer loads a leaf's partner slot unconditionally
   if (!hip_ok(hipMemsetAsync(d_tris_.ptr + n, 0, sizeof(BvhTri), st), "clear BVH triangle padding", err)) return false;
-  LbvhInputs in{d_vertices_.ptr, d_indices_.ptr, d_instances_.ptr, d_inst_base_.ptr, (uint32_t)h_instances.size(), d_transforms_.ptr,
+  HierarchyInputs in{d_vertices_.ptr, d_indices_.ptr, d_instances_.ptr, d_inst_base_.ptr, (uint32_t)h_instances.size(), d_transforms_.ptr,
                 d_materials_.ptr, n, build_opts_.builder, build_opts_.pair_area_ratio};
   in.emit_quads = true;   // the flattened tracer reads one 64-byte record per leaf (types.h BvhQuad); leaf links are ~leaf number
   in.emit_wide8 = true;   // ... and a small tile share the same hierarchy eight wide (types.h BvhNode8, k_trace8)
-  LbvhOutputs out{};
+  HierarchyOutputs out{};
   out.tris = d_tris_.ptr;
   d_quads_.release();
   d_nodes8_.release();
   StreamTimer timer;
   if (!timer.start(st, err)) return false;
-  const hipError_t be = build_lbvh(st, in, out);
+  const hipError_t be = build_hierarchy(st, in, out);
   timer.stop(st);
   const float ms = timer.ms();
-  if (!hip_ok(be, "LBVH build", err)) return false;
+  if (!hip_ok(be, "hierarchy build", err)) return false;
   d_quads_ = std::move(out.quads);
   d_nodes8_ = std::move(out.nodes8);
   d_nodes_ = std::move(out.nodes);   // allocated by the build once the number of 4-wide nodes is known

@@ -1,4 +1,4 @@
-// RayTraceInstance / RayTraceScene equivalents: device selection, scene upload, LBVH build.
+// RayTraceInstance / RayTraceScene equivalents: device selection, scene upload, hierarchy build.
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime.h>
@@ -134,7 +134,7 @@ class Scene {
   std::vector<InstanceBoxMesh> box_meshes() const;
   std::vector<uint32_t> instance_transforms() const;
   bool write_top_records(const std::vector<BvhTri>& order, double reach, Error& err);
-  void finish_two_level(const LbvhOutputs& top, float build_ms);
+  void finish_two_level(const HierarchyOutputs& top, float build_ms);
   bool assemble_top_level(const float4* d_lo, const float4* d_hi, std::vector<float4>& h_lo, std::vector<float4>& h_hi, const std::vector<MeshBuild>* built,
                           StreamTimer& timer, Error& err);
   bool rebuild_top_level(Error& err);
@@ -169,7 +169,7 @@ class Scene {
   DeviceBuffer<float> d_srgb_lut_, d_sky_marginal_, d_sky_cond_values_, d_sky_cond_cdf_;
   DeviceBuffer<BvhNode4> d_nodes_, d_top_;
   DeviceBuffer<BvhTri> d_tris_;
-  DeviceBuffer<BvhQuad> d_quads_;   // flattened build: per-leaf records of the tracer (built by build_lbvh)
+  DeviceBuffer<BvhQuad> d_quads_;   // flattened build: per-leaf records of the tracer (built by build_hierarchy)
   DeviceBuffer<BvhNode8> d_nodes8_;   // flattened build: the hierarchy eight wide (k_trace8)
   DeviceBuffer<float4> d_shade_tris_;
   DeviceBuffer<float4> d_alpha_recs_;   // DeviceScene::alpha_recs

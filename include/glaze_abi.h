@@ -279,7 +279,7 @@ typedef struct glz_scene_info {
   uint32_t n_instances, n_materials, n_lights /* lights_no, scene.rs:1549 */, n_rt_lights, n_textures;
   uint32_t bvh_nodes, bvh_depth;
   float bvh_sah_cost;
-  float build_ms;                            /* LBVH build time on the device */
+  float build_ms;                            /* hierarchy build time on the device (whichever builder) */
   float bounds_min[3], bounds_max[3];
   float bvh_grid_lo[3], bvh_grid_cell[3];    /* quantisation grid of the BVH node boxes: world = lo + q * cell */
   uint32_t as_levels;                        /* 1 = one hierarchy over all instanced triangles, 2 = TLAS over per-mesh BLAS */

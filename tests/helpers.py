@@ -12,6 +12,17 @@ def desc_from_oracle_parse(path):
     return desc_from_file(path)
 
 
+def host_sah_tree(lo, hi):
+    """children (n - 1, 2) / parent (2 n - 1) of the host SAH builder (bvh_sah.cpp) over the n boxes lo, hi ((n, 3) float32)"""
+    n = lo.shape[0]
+    lo4 = np.zeros((n, 4), np.float32); lo4[:, :3] = lo
+    hi4 = np.zeros((n, 4), np.float32); hi4[:, :3] = hi
+    children = np.full((n - 1, 2), 0x7FFFFFF0, np.int32)
+    parent = np.full(2 * n - 1, 0x7FFFFFF0, np.int32)
+    abi.check(abi.lib().glz_host_build_sah(n, lo4.ctypes.data, hi4.ctypes.data, children.ctypes.data, parent.ctypes.data))
+    return children, parent
+
+
 def camera_rays(push, width, height, offset=(0.5, 0.5)):
     """Perspective camera rays as the raygen stage builds them (numpy float32, not bit-exact; for hit tests only)."""
     c2w = push[:16].reshape(4, 4).T.astype(np.float64)

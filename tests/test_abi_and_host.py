@@ -11,6 +11,8 @@ from glaze_amd import abi
 from glaze_amd.scene_desc import make_camera
 from oracle import pyoracle
 
+from helpers import host_sah_tree
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -142,17 +144,6 @@ def test_launch_chains_partition_a_ranks_tiles():
     assert n == 2 and (own[tile_owner(200, 136, 3) == 1] != 0xFFFF).all()
 
 
-def _sah_tree(lo, hi):
-    import ctypes as C
-    n = lo.shape[0]
-    lo4 = np.zeros((n, 4), np.float32); lo4[:, :3] = lo
-    hi4 = np.zeros((n, 4), np.float32); hi4[:, :3] = hi
-    children = np.full((n - 1, 2), 0x7FFFFFF0, np.int32)
-    parent = np.full(2 * n - 1, 0x7FFFFFF0, np.int32)
-    abi.check(abi.lib().glz_host_build_sah(n, lo4.ctypes.data, hi4.ctypes.data, children.ctypes.data, parent.ctypes.data))
-    return children, parent
-
-
 def _check_tree(children, parent, n):
     """every leaf and every inner node but the root has exactly one parent, links and parents agree, ids are the pre-order"""
     assert parent[0] == -1
@@ -174,9 +165,9 @@ def test_host_sah_builder_structure_and_determinism():
     n = 70000                                                      # above the threshold where the top ranges are binned in parallel
     c = np.concatenate([rng.random((n // 2, 3)) * 10, rng.normal(size=(n - n // 2, 3)) * 0.01 + [50, -20, 5]]).astype(np.float32)
     ext = (rng.random((n, 3)) * 0.05).astype(np.float32)
-    ch, pa = _sah_tree(c - ext, c + ext)
+    ch, pa = host_sah_tree(c - ext, c + ext)
     _check_tree(ch, pa, n)
-    ch2, pa2 = _sah_tree(c - ext, c + ext)
+    ch2, pa2 = host_sah_tree(c - ext, c + ext)
     assert np.array_equal(ch, ch2) and np.array_equal(pa, pa2)     # threads do not change the tree
     # the split of the root separates the two clusters
     def leaves_under(link):
@@ -190,12 +181,12 @@ def test_host_sah_builder_structure_and_determinism():
     first, second = (a, b) if a.min() < n // 2 else (b, a)
     assert len(a) + len(b) == n and (first < n // 2).all() and (second >= n // 2).all()
     same = np.tile(np.array([[1.0, 2.0, 3.0]], np.float32), (257, 1))
-    ch, pa = _sah_tree(same, same + 1)
+    ch, pa = host_sah_tree(same, same + 1)
     _check_tree(ch, pa, 257)
-    ch, pa = _sah_tree(np.zeros((2, 3), np.float32), np.ones((2, 3), np.float32))
+    ch, pa = host_sah_tree(np.zeros((2, 3), np.float32), np.ones((2, 3), np.float32))
     assert sorted((~ch[0]).tolist()) == [0, 1] and pa.tolist() == [-1, 0, 0]
     nan = c[:1000].copy(); nan[::7] = np.nan                      # degenerate input must still give a tree
-    ch, pa = _sah_tree(nan, nan)
+    ch, pa = host_sah_tree(nan, nan)
     _check_tree(ch, pa, 1000)
 
 

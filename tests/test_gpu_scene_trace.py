@@ -12,7 +12,7 @@ from glaze_amd.scenes import atrium_scene, cube_scene
 from oracle.pyoracle import OracleRenderer, OracleScene
 
 from conftest import MATTEST
-from helpers import camera_rays, desc_from_oracle_parse
+from helpers import camera_rays, desc_from_oracle_parse, host_sah_tree
 
 pytestmark = pytest.mark.gpu
 
@@ -249,11 +249,13 @@ def test_sah_build_is_deterministic_and_default(mattest, mattest_by_builder):
     assert mattest_by_builder["sah"].info().bvh_sah_cost < mattest_by_builder["lbvh"].info().bvh_sah_cost
 
 
-@pytest.mark.parametrize("case", ["atrium", "equal centroids", "tiny"])
+@pytest.mark.parametrize("case", ["atrium", "equal centroids", "tiny", "wide level, two leaves"])
 def test_gpu_sah_builder_equals_its_host_reference(case):
     """k_sah_level restates bvh_sah.cpp statement for statement (bins, candidate order, tie-breaks, stable partition): the two
-    builders must emit identical node and triangle arrays -- also where binning finds no split and ranges are halved."""
+    builders must emit identical node and triangle arrays -- also where binning finds no split and ranges are halved, and
+    where a level of several blocks per node (k_wide_*) holds a node of two leaves next to one whose last chunk is partial."""
     from glaze_amd.scene_desc import MESH_DTYPE, VERTEX_DTYPE, SceneDesc
+    n_leaf_links = None
     if case == "atrium":
         from glaze_amd.scenes import atrium_scene
         descs = [atrium_scene(detail=0.2, texture_size=16, sky_size=(64, 32))]
@@ -268,6 +270,30 @@ def test_gpu_sah_builder_equals_its_host_reference(case):
         base = cube_scene()
         descs = [SceneDesc(verts.view(VERTEX_DTYPE).reshape(-1), np.arange(n * 3, dtype=np.uint32), np.array([(0, 1, 0, n * 3)], MESH_DTYPE), None,
                            base.instances, base.materials, base.lights, base.textures, base.camera, base.meta)]
+    elif case == "wide level, two leaves":
+        # 32 866 small triangles in the unit cube and two at x = 1000: on x the cluster is bin 0 and the pair bin 15, so the root splits
+        # (32 866 | 2) and level 1 has a mean range of 16 434 >= kSahWideMean: the wide path, with a node of two leaves (the
+        # cnt <= 2 exits, the unchanged-range copy, the halving) and a node of 8 x kSahChunk + 98 elements (a partial ninth chunk).
+        # Three private vertices per triangle: nothing pairs, leaves = triangles.
+        rng = np.random.default_rng(11)
+        n = 32868
+        centre = rng.random((n, 1, 3)).astype(np.float32)
+        centre[-2:, 0, 0] = [1000.0, 999.5]
+        centre[-2:, 0, 1:] = [[0.5, 0.5], [0.52, 0.48]]
+        tri = centre + ((rng.random((n, 3, 3)) - 0.5) * 0.01).astype(np.float32)
+        verts = np.zeros((n * 3, 8), np.float32)
+        verts[:, :3] = tri.reshape(-1, 3)
+        verts[:, 3:6] = [0, 0, 1]
+        base = cube_scene()
+        descs = [SceneDesc(verts.view(VERTEX_DTYPE).reshape(-1), np.arange(n * 3, dtype=np.uint32), np.array([(0, 1, 0, n * 3)], MESH_DTYPE), None,
+                           base.instances, base.materials, base.lights, base.textures, base.camera, base.meta)]
+        n_leaf_links = n
+        # the case must hit its target: on the triangles' boxes (padded as k_world_tris pads them) the host builder cuts the pair off the root
+        lo, hi = tri.min(1), tri.max(1)
+        pad = np.float32(1e-5) * np.maximum(np.maximum(np.abs(lo), np.abs(hi)), np.float32(1e-3))
+        ch, _ = host_sah_tree(lo - pad, hi + pad)
+        small = [int(c) for c in ch[0] if c >= 0 and (ch[c] < 0).all()]
+        assert len(small) == 1 and sorted((~ch[small[0]]).tolist()) == [n - 2, n - 1]
     else:
         descs = []
         for ntri in (1, 2, 3, 5, 12):
@@ -282,6 +308,9 @@ def test_gpu_sah_builder_equals_its_host_reference(case):
             inst.set_bvh_builder(b)
             out.append(glaze_amd.RayTraceScene.from_desc(inst, desc).debug_bvh())
         assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1].view(np.uint32), out[1][1].view(np.uint32))
+        if n_leaf_links is not None:                               # nothing paired: every triangle is a leaf of its own
+            links = out[0][0][:, 12:16].view(np.int32)
+            assert int(((links < 0)).sum()) == n_leaf_links
 
 
 def test_non_finite_vertices_do_not_break_the_builders():
