@@ -696,6 +696,29 @@ class RayTraceRenderer:
         abi.check(abi.lib().glz_renderer_read_denoised(self._h, _ptr(out), _ptr(img) if want_rgba8 else None))
         return (out, img) if want_rgba8 else out
 
+    _GUIDE_MODES = {"first_hit": abi.GUIDE_FIRST_HIT, "through_specular": abi.GUIDE_THROUGH_SPECULAR}
+
+    def set_guide_mode(self, mode, max_bounces=4):
+        """Which surface read_aov and read_denoised take their planes from: 'first_hit' (the default) or 'through_specular', which follows
+        the path's own ray through Mirror and Glass to the first vertex that is not specular, at most max_bounces (1 .. 8) bounces
+        (include/glaze_abi.h holds the specification).  Accumulation goes on."""
+        abi.check(abi.lib().glz_renderer_set_guide_mode(self._h, self._GUIDE_MODES.get(mode, mode), int(max_bounces)))
+
+    def guide_mode(self):
+        """(mode name, max_bounces) in force; max_bounces means nothing in 'first_hit'"""
+        b = C.c_uint32()
+        mode = abi.check(abi.lib().glz_renderer_guide_mode(self._h, C.byref(b)))
+        return {v: k for k, v in self._GUIDE_MODES.items()}[mode], b.value
+
+    def debug_guide_chain(self, segment):
+        """the rays of segment `segment` of every pixel's guide chain under the mode in force (0 = the camera rays): origins, directions
+        (H x W x 3 float32, zero where the chain has no such segment) and alive (H x W bool)"""
+        o = np.zeros((self.height, self.width, 3), np.float32)
+        d = np.zeros((self.height, self.width, 3), np.float32)
+        alive = np.zeros((self.height, self.width), np.uint8)
+        abi.check(abi.lib().glz_debug_guide_chain(self._h, int(segment), _ptr(o), _ptr(d), _ptr(alive)))
+        return o, d, alive.astype(bool)
+
     def debug_camera_rays(self, offset=(0.5, 0.5)):
         """camera_ray() of every pixel at one sub-pixel offset, on the device: origins, directions (H x W x 3 float32 each)"""
         o = np.zeros((self.height, self.width, 3), np.float32)

@@ -117,6 +117,7 @@ class DenoiseParams(C.Structure):
 
 
 AOV_NORMAL_DEPTH, AOV_ALBEDO_INSTANCE = 0, 1
+GUIDE_FIRST_HIT, GUIDE_THROUGH_SPECULAR, GUIDE_MAX_BOUNCES = 0, 1, 8
 DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_POWER_LOG2 = 8, 31
 POST_TIMING_SLOTS = 3 + DENOISE_MAX_ITERATIONS     # glz_debug_post_timing
 
@@ -231,6 +232,9 @@ PROTOTYPES = {
     "glz_debug_denoise": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
     "glz_debug_camera_rays": (C.c_int, [_P, C.c_float, C.c_float, _P, _P]),
     "glz_debug_post_timing": (C.c_int, [_P, _P]),
+    "glz_renderer_set_guide_mode": (C.c_int, [_P, C.c_int, C.c_uint32]),
+    "glz_renderer_guide_mode": (C.c_int, [_P, _P]),
+    "glz_debug_guide_chain": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
 }
 
 _LIB = None

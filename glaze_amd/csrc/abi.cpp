@@ -380,6 +380,16 @@ int glz_renderer_read_aov(glz_renderer* h, int which, float* out) {
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_set_denoise(glz_renderer* h, const glz_denoise_params* p) { GLZ_GUARD_BEGIN GLZ_R(h); GLZ_RET(h->r->set_denoise(p, e)); GLZ_GUARD_END(GLZ_E_IO) }
+int glz_renderer_set_guide_mode(glz_renderer* h, int mode, uint32_t max_bounces) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  GLZ_RET(h->r->set_guide_mode(mode, max_bounces, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_guide_mode(glz_renderer* h, uint32_t* max_bounces_out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  return h->r->guide_mode(max_bounces_out);
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_read_denoised(glz_renderer* h, float* rgba32f, uint8_t* rgba8) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   GLZ_RET(h->r->read_denoised(rgba32f, rgba8, e));

@@ -96,6 +96,12 @@ int glz_debug_camera_rays(glz_renderer* h, float off_x, float off_y, float* orig
   GLZ_RET(h->r->camera_rays(off_x, off_y, origins3, dirs3, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_debug_guide_chain(glz_renderer* h, uint32_t segment, float* origins3, float* dirs3, uint8_t* alive) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!origins3 || !dirs3 || !alive) return fail(GLZ_E_ARG, "output is null");
+  GLZ_RET(h->r->guide_chain(segment, origins3, dirs3, alive, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 
 int glz_debug_trace_closest(glz_scene* h, const float* o, const float* d, uint64_t n, float tmin, float* t, uint32_t* tri, uint32_t* inst, float* u,
                             float* v) {

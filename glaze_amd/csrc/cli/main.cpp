@@ -39,7 +39,7 @@ bool write_pfm(const std::string& path, const float* rgba, uint32_t w, uint32_t 
   return true;
 }
 
-// the first-hit feature buffers of --aov-out: two 8-bit images and the raw depth plane
+// the feature buffers of --aov-out (of the guide mode in force): two 8-bit images and the raw depth plane
 bool write_aovs(glz_renderer* renderer, const std::string& prefix, uint32_t w, uint32_t h) {
   const size_t n = (size_t)w * h;
   std::vector<float> nd(n * 4), ai(n * 4), depth(n);
@@ -101,6 +101,7 @@ void usage(const char* argv0) {
           "      --hdr-out <FILE.pfm>      also write the float radiance image\n"
           "      --denoise                 save the denoised image (edge-avoiding a-trous filter guided by the first-hit buffers); --hdr-out then writes the denoised floats\n"
           "      --aov-out <PREFIX>        also write the first-hit feature buffers: PREFIX.normal.png (n / 2 + 1/2), PREFIX.albedo.png (sRGB), PREFIX.depth.bin (little-endian f32 rows, inf = miss)\n"
+          "      --guides <MODE>           what --denoise and --aov-out take their feature buffers from [default: first-hit] [possible values: first-hit, through-specular[:N]] (through-specular: follow mirrors and glass to the first diffuse hit, at most N bounces, 1 .. 8 [default: 4])\n"
           "      --report                  print a JSON timing report on stdout\n",
           argv0);
 }
@@ -108,7 +109,7 @@ void usage(const char* argv0) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string input, output, resolution = "1920x1080", integrator = "pt", hdr_out, texture_lod = "off", aov_out;
+  std::string input, output, resolution = "1920x1080", integrator = "pt", hdr_out, texture_lod = "off", aov_out, guides = "first-hit";
   size_t spp = 256;
   uint64_t seed = 0;
   uint32_t depth = 6;
@@ -148,6 +149,7 @@ int main(int argc, char** argv) {
     else if (a == "--hdr-out") hdr_out = value("--hdr-out");
     else if (a == "--aov-out") aov_out = value("--aov-out");
     else if (a == "--denoise") denoise = true;
+    else if (a == "--guides") guides = value("--guides");
     else if (a == "--report") report = true;
     else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
     else if (!a.empty() && a[0] == '-') { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); usage(argv[0]); return 2; }
@@ -163,6 +165,19 @@ int main(int argc, char** argv) {
   if (texture_lod != "off" && texture_lod != "cones" && texture_lod != "aniso") {
     fprintf(stderr, "error: invalid value '%s' for '--texture-lod' [possible values: off, cones, aniso]\n", texture_lod.c_str());
     return 2;
+  }
+  int guide_mode = GLZ_GUIDE_FIRST_HIT;
+  uint32_t guide_bounces = 4;
+  if (guides != "first-hit") {
+    const std::string name = "through-specular";
+    char* e = nullptr;
+    const unsigned long n = guides.size() > name.size() + 1 && guides[name.size()] == ':' ? strtoul(guides.c_str() + name.size() + 1, &e, 10) : 4;
+    if (guides.compare(0, name.size(), name) != 0 || (guides.size() > name.size() && (!e || *e)) || n < 1 || n > GLZ_GUIDE_MAX_BOUNCES) {
+      fprintf(stderr, "error: invalid value '%s' for '--guides' [possible values: first-hit, through-specular[:N] with N = 1 .. %d]\n", guides.c_str(), GLZ_GUIDE_MAX_BOUNCES);
+      return 2;
+    }
+    guide_mode = GLZ_GUIDE_THROUGH_SPECULAR;
+    guide_bounces = (uint32_t)n;
   }
   // check output (cli/src/main.rs:46-55)
   if (!(ends_with(output, "jpg") || ends_with(output, "png"))) {
@@ -215,6 +230,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   glz_renderer_set_seed(renderer, seed);
+  if (glz_renderer_set_guide_mode(renderer, guide_mode, guide_bounces) != GLZ_OK) { fprintf(stderr, "\n[ERROR] %s\n", glz_last_error()); return 1; }
   if (devices.size() > 1 && glz_renderer_set_devices(renderer, devices.data(), (int)devices.size()) != GLZ_OK) {
     fprintf(stderr, "\n[ERROR] %s\n", glz_last_error());
     return 1;

@@ -167,6 +167,24 @@ hipError_t launch_tonemap(hipStream_t st, uint32_t n_pixels, const float4* resul
 uint32_t first_hit_grid_blocks(uint32_t n_rays);
 hipError_t launch_first_hit(hipStream_t st, const LaunchArgs& a, uint32_t blocks, float4* hit, uint32_t* inst);
 hipError_t launch_first_hit_attributes(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, float4* aov0, float4* aov1);
+// Through-specular guides (GLZ_GUIDE_THROUGH_SPECULAR), after launch_first_hit on the same stream and with the same `a`: vertex 0 of every
+// pixel, then per bounce k = 1 .. max_bounces the closest hits of list k and vertex k of its rays.  List k (segment k of the chains that have
+// one) is compacted: o = (origin, depth so far), d = (direction, pixel bits), in buffers [k & 1] of width * height entries each, its length
+// in count[k]; `hit` / `inst` are reused, indexed by list slot.  Nothing is read back: a kernel whose list is empty returns at once.
+// blocks: guide_grid_blocks (the device must be current).  last_list: stop once list `last_list` has been written (the planes are then
+// those of the vertices so far); GLZ_GUIDE_MAX_BOUNCES + 1 or more runs the whole chain.
+constexpr uint32_t kGuideCountWords = GLZ_GUIDE_MAX_BOUNCES + 2;
+struct GuideLists {
+  float4* o[2];
+  float4* d[2];
+  uint32_t* count;   // kGuideCountWords words
+};
+uint32_t guide_grid_blocks(uint32_t n_rays, uint32_t first_hit_blocks);
+hipError_t launch_guide_chain(hipStream_t st, const LaunchArgs& a, uint32_t blocks, uint32_t max_bounces, uint32_t last_list, float4* hit, uint32_t* inst,
+                              const GuideLists& lists, float4* aov0, float4* aov1);
+// list `list` (1 .. GLZ_GUIDE_MAX_BOUNCES) back to its pixels: 3 floats each, row-major, alive = 1; pixels without a ray in it are left as they are
+hipError_t launch_guide_scatter(hipStream_t st, uint32_t blocks, const GuideLists& lists, uint32_t list, uint32_t n_pixels, float* origins3, float* dirs3,
+                                uint8_t* alive);
 // camera_ray() of every pixel at one sub-pixel offset, row-major, 3 floats each
 hipError_t launch_camera_rays(hipStream_t st, const LaunchArgs& a, float off_x, float off_y, float* origins3, float* dirs3);
 // The filter of glz_denoise_params on row-major device frames: demodulation, `iterations` a-trous passes (one launch each, ping-pong),

@@ -55,30 +55,19 @@ __global__ void __launch_bounds__(kBlock) k_first_hit(const LaunchArgs A, float4
 }
 
 // ---------------------------------------------------------------------------------------------
-// First-hit pass, part 2: the attributes, one thread per pixel (row-major).  The first lines of shade_pixel_body up to
-// fetch_material_textures restated -- same operations, same order -- with texture level 0 always (kNoLod).
-//   aov0 = (normal.xyz, depth)   aov1 = (albedo.rgb, instance bits)
+// One vertex of a guide chain: the first lines of shade_pixel_body up to fetch_material_textures restated -- same operations, same
+// order -- with texture level 0 always (kNoLod).  Gives the vertex's planes' values (the normal turned against `direction`, the albedo)
+// and, with CHAIN, the ray the path would go on with through a specular material: `point` and `wiW` as shade_pixel_body forms them
+// (bsdf_sample with xi = (0, 0, 1 - 2^-24): Mirror ignores it, Glass takes the transmitted branch unless its Fresnel term is 1).
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kBlock) k_first_hit_attributes(const LaunchArgs A, const float4* __restrict__ hit, const uint32_t* __restrict__ inst,
-                                                                 float4* __restrict__ aov0, float4* __restrict__ aov1) {
-  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  if (p >= A.map.width * A.map.height) return;
-  const float4 hr = hit[p];
+struct GuideVertex {
+  vec3 n, albedo;
+  bool go_on;        // CHAIN: the material is specular and bsdf_sample gave a direction to follow
+  vec3 point, wiW;   // CHAIN, go_on: the next segment
+};
+template <bool CHAIN>
+__device__ __forceinline__ GuideVertex guide_vertex(const DeviceScene& S, float4 hr, uint32_t hit_inst, vec3 direction) {
   const uint32_t leaf = __float_as_uint(hr.w);
-  if (leaf == 0xFFFFFFFFu) {
-    aov0[p] = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
-    aov1[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(0xFFFFFFFFu));
-    return;
-  }
-  DeviceScene S = A.scene;
-  S.tex_counter = nullptr;
-  PixelId px;
-  px.x = p % A.map.width;
-  px.y = p / A.map.width;
-  px.active = true;
-  vec3 origin, direction;
-  camera_ray(A, A.frame, px, 0.5f, 0.5f, origin, direction);   // the ray k_first_hit traced, bit for bit
-  const uint32_t hit_inst = inst[p];
   const float4* rec = S.shade_tris + 8u * (size_t)leaf;
   const float4 va0 = rec[0], va1 = rec[1], vb0 = rec[2], vb1 = rec[3], vc0 = rec[4], vc1 = rec[5], dn = rec[6], du = rec[7];
   uint32_t material_id = __float_as_uint(dn.w), xf_bits = __float_as_uint(du.w);
@@ -88,6 +77,8 @@ __global__ void __launch_bounds__(kBlock) k_first_hit_attributes(const LaunchArg
     xf_bits = in.transform_id | (S.xf_identity[in.transform_id] ? 0x80000000u : 0u);
   }
   const float b0 = 1.0f - hr.y - hr.z, b1 = hr.y, b2 = hr.z;
+  vec3 point = mk3(0.0f, 0.0f, 0.0f);
+  if (CHAIN) point = (mk3(va0.x, va0.y, va0.z) * b0 + mk3(vb0.x, vb0.y, vb0.z) * b1) + mk3(vc0.x, vc0.y, vc0.z) * b2;
   const vec2 uv = vec2{(va1.z * b0 + vb1.z * b1) + vc1.z * b2, (va1.w * b0 + vb1.w * b1) + vc1.w * b2};
   vec3 ng = mk3(dn.x, dn.y, dn.z), dpdu = mk3(du.x, du.y, du.z);
   vec3 ns = (mk3(va0.w, va1.x, va1.y) * b0 + mk3(vb0.w, vb1.x, vb1.y) * b1) + mk3(vc0.w, vc1.x, vc1.y) * b2;
@@ -106,18 +97,215 @@ __global__ void __launch_bounds__(kBlock) k_first_hit_attributes(const LaunchArg
     const float4* xq = reinterpret_cast<const float4*>(&S.transforms[xf_bits & 0x7FFFFFFFu]);
     const float4 w0 = xq[4], w1 = xq[5], w2 = xq[6];
     const float w2o[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
+    if (CHAIN) {
+      const float4 m0 = xq[0], m1 = xq[1], m2 = xq[2], m3 = xq[3];
+      const float o2w[16] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w, m3.x, m3.y, m3.z, m3.w};
+      point = xform_point(o2w, point);
+      dpdu = xform_point(o2w, dpdu);   // transformed as a point, as shade_pixel_body does (Q8)
+    }
     ns = xform_tdir(w2o, ns);
   }
-  vec3 n = normalize3(ns);
-  if (dot3(n, direction) > 0.0f) n = -n;
-  if (!(post::finite1(n.x) && post::finite1(n.y) && post::finite1(n.z))) n = mk3(0.0f, 0.0f, 0.0f);   // a zero-length ns normalises to NaN
-  vec3 albedo = mk3(1.0f, 1.0f, 1.0f);
+  GuideVertex v;
+  v.n = normalize3(ns);
+  if (dot3(v.n, direction) > 0.0f) v.n = -v.n;
+  if (!(post::finite1(v.n.x) && post::finite1(v.n.y) && post::finite1(v.n.z))) v.n = mk3(0.0f, 0.0f, 0.0f);   // a zero-length ns normalises to NaN
+  v.albedo = mk3(1.0f, 1.0f, 1.0f);
   if (mat.bsdf_index == kBsdfLambert || mat.bsdf_index == kBsdfUber) {
     const vec4 tx = texture2d_lod(S, mat.diffuse, uv.x, uv.y, fp);
-    albedo = mk3(tx.x, tx.y, tx.z) * mk3(mat.diffuse_mul[0], mat.diffuse_mul[1], mat.diffuse_mul[2]);
+    v.albedo = mk3(tx.x, tx.y, tx.z) * mk3(mat.diffuse_mul[0], mat.diffuse_mul[1], mat.diffuse_mul[2]);
   }
-  aov0[p] = make_float4(n.x, n.y, n.z, hr.x);
-  aov1[p] = make_float4(albedo.x, albedo.y, albedo.z, __uint_as_float(hit_inst));
+  v.go_on = false;
+  v.point = point;
+  v.wiW = mk3(0.0f, 0.0f, 0.0f);
+  if (CHAIN && mat.is_specular != 0) {
+    SurfacePoint P;
+    P.woW = -direction;
+    P.uv = uv;
+    P.frame = make_frame(dpdu, ns);
+    P.mat = mat;
+    fetch_material_textures(S, P, fp);
+    Spec value = spec_set(0.0f);
+    const float pdf = bsdf_sample(S, P, mk3(0.0f, 0.0f, 0x1.fffffep-1f), value, v.wiW);
+    v.go_on = pdf != 0.0f && post::finite1(v.wiW.x) && post::finite1(v.wiW.y) && post::finite1(v.wiW.z);
+  }
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------
+// First-hit pass, part 2: the attributes of the first vertex, one thread per pixel (row-major).
+//   aov0 = (normal.xyz, depth)   aov1 = (albedo.rgb, instance bits)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void store_miss_planes(float4* __restrict__ aov0, float4* __restrict__ aov1, uint32_t p) {
+  aov0[p] = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
+  aov1[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(0xFFFFFFFFu));
+}
+__device__ __forceinline__ vec3 centre_ray_direction(const LaunchArgs& A, uint32_t p) {
+  PixelId px;
+  px.x = p % A.map.width;
+  px.y = p / A.map.width;
+  px.active = true;
+  vec3 origin, direction;
+  camera_ray(A, A.frame, px, 0.5f, 0.5f, origin, direction);   // the ray k_first_hit traced, bit for bit
+  return direction;
+}
+__global__ void __launch_bounds__(kBlock) k_first_hit_attributes(const LaunchArgs A, const float4* __restrict__ hit, const uint32_t* __restrict__ inst,
+                                                                 float4* __restrict__ aov0, float4* __restrict__ aov1) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= A.map.width * A.map.height) return;
+  const float4 hr = hit[p];
+  if (__float_as_uint(hr.w) == 0xFFFFFFFFu) {
+    store_miss_planes(aov0, aov1, p);
+    return;
+  }
+  DeviceScene S = A.scene;
+  S.tex_counter = nullptr;
+  const uint32_t hit_inst = inst[p];
+  const GuideVertex v = guide_vertex<false>(S, hr, hit_inst, centre_ray_direction(A, p));
+  aov0[p] = make_float4(v.n.x, v.n.y, v.n.z, hr.x);
+  aov1[p] = make_float4(v.albedo.x, v.albedo.y, v.albedo.z, __uint_as_float(hit_inst));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Through-specular guides (GLZ_GUIDE_THROUGH_SPECULAR): the chain of segments the path itself would follow through Mirror and Glass.
+// Segment 0 is the centre ray (k_first_hit above); segment k >= 1 lives in a COMPACTED list of rays -- o = (origin, depth so far),
+// d = (direction, pixel bits) -- with its length in device memory, so that a bounce costs what its live rays cost and the host never
+// reads a count back: a kernel whose list is empty returns at once.
+//   k_guide_continue<FIRST>  vertex k of every live ray: writes the vertex's planes at the ray's pixel (a later vertex overwrites them;
+//                            a later segment that misses leaves them, which makes the last vertex hit the reporting one) and, where the
+//                            chain goes on, appends segment k + 1 to the next list (ballot + popcount, one atomic per wave).
+//   k_guide_trace            the closest hits of a list, stored at the rays' slots.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t list_slot(uint32_t* count, bool push) {
+  const unsigned long long m = __ballot(push);
+  uint32_t slot = 0;
+  if (push) {
+    const int lane = threadIdx.x & 63;
+    const int leader = __ffsll((long long)m) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
+    base = __shfl(base, leader);
+    slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  }
+  return slot;
+}
+// vertex k of ray `i` (FIRST: of pixel i); all lanes of a wave call it together
+template <bool FIRST>
+__device__ __forceinline__ void guide_continue_ray(const LaunchArgs& A, const DeviceScene& S, uint32_t i, bool live, bool may_push, const float4* __restrict__ hit,
+                                                   const uint32_t* __restrict__ inst, const float4* __restrict__ in_o, const float4* __restrict__ in_d,
+                                                   float4* __restrict__ out_o, float4* __restrict__ out_d, uint32_t* out_count, float4* __restrict__ aov0,
+                                                   float4* __restrict__ aov1) {
+  bool push = false;
+  uint32_t p = 0;
+  float depth = 0.0f;
+  vec3 point = mk3(0.0f, 0.0f, 0.0f), wiW = mk3(0.0f, 0.0f, 0.0f);
+  if (live) {
+    const float4 hr = hit[i];
+    vec3 direction;
+    float before = 0.0f;
+    if (FIRST) {
+      p = i;
+      direction = centre_ray_direction(A, p);
+    } else {
+      const float4 ro = in_o[i], rd = in_d[i];
+      p = __float_as_uint(rd.w);
+      direction = mk3(rd.x, rd.y, rd.z);
+      before = ro.w;
+    }
+    if (__float_as_uint(hr.w) == 0xFFFFFFFFu) {
+      if (FIRST) store_miss_planes(aov0, aov1, p);   // (a later segment that misses: the planes of the vertex before stay)
+    } else {
+      const uint32_t hit_inst = inst[i];
+      const GuideVertex v = guide_vertex<true>(S, hr, hit_inst, direction);
+      depth = FIRST ? hr.x : before + hr.x;
+      aov0[p] = make_float4(v.n.x, v.n.y, v.n.z, depth);
+      aov1[p] = make_float4(v.albedo.x, v.albedo.y, v.albedo.z, __uint_as_float(hit_inst));
+      push = may_push && v.go_on;
+      point = v.point;
+      wiW = v.wiW;
+    }
+  }
+  const uint32_t slot = list_slot(out_count, push);
+  if (push) {
+    out_o[slot] = make_float4(point.x, point.y, point.z, depth);
+    out_d[slot] = make_float4(wiW.x, wiW.y, wiW.z, __uint_as_float(p));
+  }
+}
+// the length of a list: the same in every lane, and the compiler has to know it (trace_wave)
+__device__ __forceinline__ uint32_t list_length(const uint32_t* count) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)*count); }
+
+// vertex 0: one thread per pixel (row-major), in place of k_first_hit_attributes
+__global__ void __launch_bounds__(kBlock) k_guide_first(const LaunchArgs A, const float4* __restrict__ hit, const uint32_t* __restrict__ inst, float4* __restrict__ out_o,
+                                                        float4* __restrict__ out_d, uint32_t* out_count, float4* __restrict__ aov0, float4* __restrict__ aov1) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  DeviceScene S = A.scene;
+  S.tex_counter = nullptr;
+  guide_continue_ray<true>(A, S, p, p < A.map.width * A.map.height, true, hit, inst, nullptr, nullptr, out_o, out_d, out_count, aov0, aov1);
+}
+// vertex k >= 1: a persistent grid strides over the list, a block on kBlock consecutive rays at a time
+__global__ void __launch_bounds__(kBlock) k_guide_continue(const LaunchArgs A, uint32_t may_push, const float4* __restrict__ hit, const uint32_t* __restrict__ inst,
+                                                           const float4* __restrict__ in_o, const float4* __restrict__ in_d, const uint32_t* in_count,
+                                                           float4* __restrict__ out_o, float4* __restrict__ out_d, uint32_t* out_count, float4* __restrict__ aov0,
+                                                           float4* __restrict__ aov1) {
+  const uint32_t n = list_length(in_count);
+  DeviceScene S = A.scene;
+  S.tex_counter = nullptr;
+  for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
+    const uint32_t i = base + threadIdx.x;
+    guide_continue_ray<false>(A, S, i, i < n, may_push != 0u, hit, inst, in_o, in_d, out_o, out_d, out_count, aov0, aov1);
+  }
+}
+
+struct ListSource {
+  const float4* o;
+  const float4* d;
+  uint32_t n;
+  __device__ __forceinline__ bool load(uint32_t i, vec3& origin, vec3& direction, float& tmin, float& tmax) {
+    if (i >= n) return false;
+    const float4 ro = o[i], rd = d[i];
+    origin = mk3(ro.x, ro.y, ro.z);
+    direction = mk3(rd.x, rd.y, rd.z);
+    tmin = 0.0001f;   // as CentreSource
+    tmax = INFINITY;
+    return true;
+  }
+};
+struct ListSink {
+  const LaunchArgs& A;
+  float4* hit;       // by slot: t, u, v, leaf (bits)
+  uint32_t* inst;    // by slot: RTInstance of the hit
+  __device__ __forceinline__ void store(uint32_t i, const HitRecord& h) {
+    const bool is_hit = h.leaf != 0xFFFFFFFFu;
+    hit[i] = make_float4(is_hit ? h.t : INFINITY, h.u, h.v, __uint_as_float(h.leaf));
+    inst[i] = is_hit ? (A.scene.two_level ? h.inst : A.scene.bvh_tris[h.leaf].instance) : 0xFFFFFFFFu;
+  }
+};
+__global__ void __launch_bounds__(kBlock) k_guide_trace(const LaunchArgs A, const float4* __restrict__ in_o, const float4* __restrict__ in_d, const uint32_t* in_count,
+                                                        float4* hit, uint32_t* inst) {
+  __shared__ int s_stack[kLdsStack * kBlock];
+  __shared__ alignas(1024) int s_aux[kAuxPerBlock];
+  __shared__ uint4 s_top[kBvhTopNodes * 4];
+  __shared__ float s_top_ray[9 * kBlock];
+  const uint32_t n = list_length(in_count);
+  if (n == 0) return;   // (the whole grid: nothing has been staged, no barrier is waiting)
+  stage_top(A.scene, s_top);
+  TraceTally tally;
+  ListSource src{in_o, in_d, n};
+  ListSink sink{A, hit, inst};
+  if (A.scene.two_level) trace_wave_tl<false, false>(A.scene, src, sink, &s_stack[threadIdx.x], wave_aux(s_aux, threadIdx.x >> 6), wave_links(s_aux, threadIdx.x >> 6), &s_top_ray[threadIdx.x], (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, n, wave_index(), wave_count(), tally);
+  else trace_wave<false, false>(A.scene, src, sink, &s_stack[threadIdx.x], wave_aux(s_aux, threadIdx.x >> 6), wave_links(s_aux, threadIdx.x >> 6), (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, n, wave_index(), wave_count(), tally);
+}
+// a list back to the pixels it belongs to (glz_debug_guide_chain): 3 floats each, row-major, and alive = 1; the rest is left as it is
+__global__ void __launch_bounds__(kBlock) k_guide_scatter(const float4* __restrict__ in_o, const float4* __restrict__ in_d, const uint32_t* in_count, uint32_t n_pixels,
+                                                          float* __restrict__ o3, float* __restrict__ d3, uint8_t* __restrict__ alive) {
+  const uint32_t n = list_length(in_count);
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const float4 ro = in_o[i], rd = in_d[i];
+    const uint32_t p = __float_as_uint(rd.w);
+    if (p >= n_pixels) continue;
+    o3[3 * (size_t)p] = ro.x; o3[3 * (size_t)p + 1] = ro.y; o3[3 * (size_t)p + 2] = ro.z;
+    d3[3 * (size_t)p] = rd.x; d3[3 * (size_t)p + 1] = rd.y; d3[3 * (size_t)p + 2] = rd.z;
+    alive[p] = 1;
+  }
 }
 
 // camera_ray() of every pixel at one sub-pixel offset (row-major, 3 floats each): the parity hook behind glz_debug_camera_rays
@@ -172,6 +360,31 @@ hipError_t launch_first_hit(hipStream_t st, const LaunchArgs& a, uint32_t blocks
 hipError_t launch_first_hit_attributes(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, float4* aov0, float4* aov1) {
   const uint32_t n = a.map.width * a.map.height;
   return launch_per_item(st, k_first_hit_attributes, n, a, hit, inst, aov0, aov1);
+}
+// blocks of k_guide_trace's persistent grid: the tracers' residency rule, and never more than the first-hit pass's, whose spill area it uses
+uint32_t guide_grid_blocks(uint32_t n_rays, uint32_t first_hit_blocks) { return std::min(persistent_grid(k_guide_trace, n_rays).x, first_hit_blocks); }
+hipError_t launch_guide_chain(hipStream_t st, const LaunchArgs& a, uint32_t blocks, uint32_t max_bounces, uint32_t last_list, float4* hit, uint32_t* inst,
+                              const GuideLists& lists, float4* aov0, float4* aov1) {
+  const uint32_t n = a.map.width * a.map.height;
+  if (n == 0) return hipSuccess;
+  if (a.map.rank != 0 || a.map.world != 1 || max_bounces < 1 || max_bounces > GLZ_GUIDE_MAX_BOUNCES || last_list < 1) return hipErrorInvalidValue;
+  if (blocks == 0 || (uint64_t)blocks * kBlock > (uint64_t)a.map.n_local_pixels + kBlock) return hipErrorInvalidValue;   // the spill area, as launch_first_hit
+  hipError_t status = hipMemsetAsync(lists.count, 0, sizeof(uint32_t) * kGuideCountWords, st);
+  if (status != hipSuccess) return status;
+  hipLaunchKernelGGL(k_guide_first, grid_for(n), dim3(kBlock), 0, st, a, hit, inst, lists.o[1], lists.d[1], lists.count + 1, aov0, aov1);
+  for (uint32_t k = 1; k <= max_bounces && k < last_list; ++k) {   // list k -> hits -> vertex k -> list k + 1 (none behind vertex max_bounces)
+    const uint32_t in = k & 1u, out = in ^ 1u;
+    hipLaunchKernelGGL(k_guide_trace, dim3(blocks), dim3(kBlock), 0, st, a, lists.o[in], lists.d[in], lists.count + k, hit, inst);
+    hipLaunchKernelGGL(k_guide_continue, dim3(blocks), dim3(kBlock), 0, st, a, k < max_bounces ? 1u : 0u, hit, inst, lists.o[in], lists.d[in], lists.count + k, lists.o[out],
+                       lists.d[out], lists.count + k + 1, aov0, aov1);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_guide_scatter(hipStream_t st, uint32_t blocks, const GuideLists& lists, uint32_t list, uint32_t n_pixels, float* origins3, float* dirs3, uint8_t* alive) {
+  if (n_pixels == 0) return hipSuccess;
+  if (blocks == 0 || list < 1 || list > GLZ_GUIDE_MAX_BOUNCES) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_guide_scatter, dim3(blocks), dim3(kBlock), 0, st, lists.o[list & 1u], lists.d[list & 1u], lists.count + list, n_pixels, origins3, dirs3, alive);
+  return hipGetLastError();
 }
 hipError_t launch_camera_rays(hipStream_t st, const LaunchArgs& a, float off_x, float off_y, float* origins3, float* dirs3) {
   const uint32_t n = a.map.width * a.map.height;

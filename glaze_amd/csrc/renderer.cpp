@@ -1035,6 +1035,8 @@ void Renderer::release_post() {
   fh_hit_.release(); fh_inst_.release(); fh_overflow_.release();
   aov0_.release(); aov1_.release();
   dn_ping_.release(); dn_pong_.release(); dn_out_.release();
+  for (int i = 0; i < 2; ++i) { guide_o_[i].release(); guide_d_[i].release(); }
+  guide_count_.release();
 }
 
 // what the post kernels read of LaunchArgs: the scene, the camera, the frame's size and projection, a FULL-frame tile map
@@ -1048,7 +1050,7 @@ void Renderer::post_args(LaunchArgs& a) const {
   a.map = make_tile_map(w_, h_, 0, 1);
 }
 
-bool Renderer::first_hit_pass(Error& err, hipEvent_t* marks) {
+bool Renderer::first_hit_pass(Error& err, hipEvent_t* marks, uint32_t last_list) {
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   LaunchArgs a;
   post_args(a);
@@ -1067,6 +1069,14 @@ bool Renderer::first_hit_pass(Error& err, hipEvent_t* marks) {
       fh_overflow_.release();
       return false;
     }
+  const bool chain = guide_mode_ == GLZ_GUIDE_THROUGH_SPECULAR;
+  if (chain && (!guide_o_[0].ptr || !guide_o_[1].ptr || !guide_d_[0].ptr || !guide_d_[1].ptr || !guide_count_.ptr || guide_o_[0].count != n)) {
+    if (!hip_ok(alloc_each(n, guide_o_[0], guide_o_[1], guide_d_[0], guide_d_[1]), "alloc guide ray lists", err) ||
+        !hip_ok(guide_count_.alloc(kGuideCountWords), "alloc guide ray lists", err)) {
+      release_post();
+      return false;
+    }
+  }
   a.st.overflow = fh_overflow_.ptr;
   a.st.overflow_depth = scene_->stack_overflow_depth;
   hipStream_t st = inst_->stream;
@@ -1075,9 +1085,60 @@ bool Renderer::first_hit_pass(Error& err, hipEvent_t* marks) {
   if (marks) (void)hipEventRecord(marks[0], st);
   if (!hip_ok(launch_first_hit(st, a, blocks, fh_hit_.ptr, fh_inst_.ptr), "k_first_hit", err)) return false;
   if (marks) (void)hipEventRecord(marks[1], st);
-  if (!hip_ok(launch_first_hit_attributes(st, a, fh_hit_.ptr, fh_inst_.ptr, aov0_.ptr, aov1_.ptr), "k_first_hit_attributes", err)) return false;
+  if (chain) {
+    guide_blocks_ = guide_grid_blocks(a.map.n_local_pixels, blocks);
+    if (!hip_ok(launch_guide_chain(st, a, guide_blocks_, guide_bounces_, last_list, fh_hit_.ptr, fh_inst_.ptr, guide_lists(), aov0_.ptr, aov1_.ptr), "k_guide_continue", err))
+      return false;
+  } else if (!hip_ok(launch_first_hit_attributes(st, a, fh_hit_.ptr, fh_inst_.ptr, aov0_.ptr, aov1_.ptr), "k_first_hit_attributes", err)) {
+    return false;
+  }
   if (marks) (void)hipEventRecord(marks[2], st);
   return true;
+}
+
+bool Renderer::set_guide_mode(int mode, uint32_t max_bounces, Error& err) {
+  if (mode != GLZ_GUIDE_FIRST_HIT && mode != GLZ_GUIDE_THROUGH_SPECULAR) {
+    err.code = GLZ_E_ARG;
+    err.msg = "unknown guide mode (GLZ_GUIDE_FIRST_HIT or GLZ_GUIDE_THROUGH_SPECULAR)";
+    return false;
+  }
+  if (mode == GLZ_GUIDE_THROUGH_SPECULAR && (max_bounces < 1 || max_bounces > GLZ_GUIDE_MAX_BOUNCES)) {
+    err.code = GLZ_E_ARG;
+    err.msg = "guide mode: max_bounces must be 1 .. GLZ_GUIDE_MAX_BOUNCES";
+    return false;
+  }
+  guide_mode_ = mode;
+  if (mode == GLZ_GUIDE_THROUGH_SPECULAR) guide_bounces_ = max_bounces;
+  return true;
+}
+int Renderer::guide_mode(uint32_t* max_bounces_out) const {
+  if (max_bounces_out) *max_bounces_out = guide_bounces_;
+  return guide_mode_;
+}
+
+bool Renderer::guide_chain(uint32_t segment, float* origins3, float* dirs3, uint8_t* alive, Error& err) {
+  const size_t n = (size_t)w_ * h_;
+  if (segment == 0) {   // the camera rays: every pixel has them
+    memset(alive, 1, n);
+    return camera_rays(0.5f, 0.5f, origins3, dirs3, err);
+  }
+  memset(origins3, 0, sizeof(float) * 3 * n);
+  memset(dirs3, 0, sizeof(float) * 3 * n);
+  memset(alive, 0, n);
+  if (guide_mode_ != GLZ_GUIDE_THROUGH_SPECULAR || segment > guide_bounces_ || n == 0) return true;
+  if (!first_hit_pass(err, nullptr, segment)) return false;   // up to the list of this segment
+  DeviceBuffer<float> d_o, d_d;
+  DeviceBuffer<uint8_t> d_alive;
+  if (!hip_ok(d_o.alloc(3 * n), "alloc", err) || !hip_ok(d_d.alloc(3 * n), "alloc", err) || !hip_ok(d_alive.alloc(n), "alloc", err)) return false;
+  hipStream_t st = inst_->stream;
+  if (!hip_ok(hipMemsetAsync(d_o.ptr, 0, sizeof(float) * 3 * n, st), "guide chain", err) || !hip_ok(hipMemsetAsync(d_d.ptr, 0, sizeof(float) * 3 * n, st), "guide chain", err) ||
+      !hip_ok(hipMemsetAsync(d_alive.ptr, 0, n, st), "guide chain", err))
+    return false;
+  if (!hip_ok(launch_guide_scatter(st, guide_blocks_, guide_lists(), segment, (uint32_t)n, d_o.ptr, d_d.ptr, d_alive.ptr), "k_guide_scatter", err)) return false;
+  if (!hip_ok(hipMemcpyAsync(origins3, d_o.ptr, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, st), "guide chain", err)) return false;
+  if (!hip_ok(hipMemcpyAsync(dirs3, d_d.ptr, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, st), "guide chain", err)) return false;
+  if (!hip_ok(hipMemcpyAsync(alive, d_alive.ptr, n, hipMemcpyDeviceToHost, st), "guide chain", err)) return false;
+  return hip_ok(hipStreamSynchronize(st), "guide chain", err);
 }
 
 bool Renderer::read_aov(int which, float* out, Error& err) {

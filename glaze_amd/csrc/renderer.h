@@ -38,6 +38,11 @@ class Renderer {
   bool set_denoise(const glz_denoise_params* p, Error& err);          // null = defaults; accumulation goes on
   bool read_denoised(float* rgba32f, uint8_t* rgba8, Error& err);     // gather + first-hit pass + filter; either output may be null
   bool camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err);   // camera_ray() of every pixel, on the device
+  // which surface the feature buffers describe (GLZ_GUIDE_*, glaze_abi.h holds the specification); accumulation goes on
+  bool set_guide_mode(int mode, uint32_t max_bounces, Error& err);
+  int guide_mode(uint32_t* max_bounces_out) const;
+  // the rays of one segment of every pixel's guide chain under the mode and cap in force (glz_debug_guide_chain)
+  bool guide_chain(uint32_t segment, float* origins3, float* dirs3, uint8_t* alive, Error& err);
   // one run of the post stages between device events: ms of {first-hit trace, attributes, demodulation, pass 0 .. iterations - 1} (unused = 0)
   bool time_post(float ms[GLZ_POST_TIMING_SLOTS], Error& err);
 
@@ -192,13 +197,20 @@ class Renderer {
 
   // The first-hit pass over the FULL frame on this device, whatever the partition: centre rays, closest hits, attributes -> aov0_ / aov1_.
   // Recomputed on every request, never cached; its buffers are private (allocated on first use, released by change_resolution).
-  bool first_hit_pass(Error& err, hipEvent_t* marks = nullptr);   // marks: 3 events around the two kernels
+  // In GLZ_GUIDE_THROUGH_SPECULAR the chain's kernels take the attribute kernel's place (launch_guide_chain; last_list as there).
+  bool first_hit_pass(Error& err, hipEvent_t* marks = nullptr, uint32_t last_list = GLZ_GUIDE_MAX_BOUNCES + 1);   // marks: 3 events around the trace and what follows it
   void post_args(LaunchArgs& a) const;
   void release_post();
   bool ensure_denoise_frames(Error& err);
   DeviceBuffer<float4> fh_hit_, aov0_, aov1_, dn_ping_, dn_pong_, dn_out_;
   DeviceBuffer<uint32_t> fh_inst_, fh_overflow_;
   glz_denoise_params denoise_;   // set in create()
+  int guide_mode_ = GLZ_GUIDE_FIRST_HIT;
+  uint32_t guide_bounces_ = 4;
+  DeviceBuffer<float4> guide_o_[2], guide_d_[2];   // the chain's ray lists (GuideLists), allocated on first use in GLZ_GUIDE_THROUGH_SPECULAR
+  DeviceBuffer<uint32_t> guide_count_;
+  uint32_t guide_blocks_ = 0;                      // the chain's grid in the last pass
+  GuideLists guide_lists() const { return GuideLists{{guide_o_[0].ptr, guide_o_[1].ptr}, {guide_d_[0].ptr, guide_d_[1].ptr}, guide_count_.ptr}; }
 
   DeviceBuffer<float4> frame_tmp_;
   DeviceBuffer<uchar4> rgba8_;

@@ -432,3 +432,69 @@ def forest_scene(n, seed=3):
     camera = make_camera(position=(-18, 2.0, -18), target=(10, 1.0, 10), up=(0, 1, 0), fovx=np.float32(np.radians(np.float32(70.0))), near=1e-2, far=200.0)
     meta = make_meta(centre=(0, 2, 0), radius=30.0, exposure=1.0)
     return SceneDesc(vertices, indices, meshes, transforms, instances, materials, lights, textures, camera, meta)
+
+
+# ------------------------------------------------------------------------------------------------
+# a room with mirrors and glass
+# ------------------------------------------------------------------------------------------------
+MIRROR_ROOM_PLANE_Z = 5.0          # the large mirror lies in the plane z = 5 and faces -z
+
+
+def mirror_room_scene(mirror=True, view="room"):
+    """A room (8 x 4 x 10 m, textured Lambert floor, ceiling and three walls) whose fourth side, the plane z = 5, is ONE planar Mirror quad
+    of two triangles; three textured boxes and a Glass slab stand in it as instances of a cube under rotations, scales and translations,
+    and a pair of parallel mirrors face each other 1 m apart, one on the left wall and one on a free-standing panel.  What the denoiser's through-specular guides are
+    for: texture and geometry edges seen in a mirror and through glass.  The large mirror is the LAST instance: mirror=False leaves it out
+    (the room is then open on that side) and changes no other instance's index.  view: 'room' looks at the large mirror, 'facing' from
+    between the facing mirrors into one of them."""
+    B = _Builder()
+    B.grid((-4, 0, -5), (0, 0, 10), (8, 0, 0), 4, 4, 1, uv_scale=5.0)          # floor (+y)
+    B.grid((-4, 4, -5), (8, 0, 0), (0, 0, 10), 4, 4, 2, uv_scale=4.0)          # ceiling (-y)
+    B.grid((-4, 0, -5), (0, 4, 0), (0, 0, 10), 2, 4, 3, uv_scale=3.0)          # left wall (+x)
+    B.grid((4, 0, -5), (0, 0, 10), (0, 4, 0), 4, 2, 3, uv_scale=3.0)           # right wall (-x)
+    B.grid((-4, 0, -5), (8, 0, 0), (0, 4, 0), 4, 2, 2, uv_scale=2.0)           # front wall (+z), behind the 'room' camera
+    cube = cube_scene()
+    # mesh 5: the boxes' cube; mesh 6: the glass slab, thin in OBJECT space.  Every transform below is a similarity (rotation, ONE scale,
+    # translation): the shading frame's normal is not renormalised after the inverse-transpose (as in the reference), so a squashed
+    # instance multiplies the path's weight by the squash at every bounce -- a slab made by scaling the cube to 4 % floods the room with
+    # fireflies of 1e5 times its median radiance
+    B.add(cube.vertices["vv"], cube.vertices["vn"], cube.vertices["vt"], cube.indices, 4)
+    B.add(cube.vertices["vv"] * np.array([0.9, 1.3, 0.04], np.float32), cube.vertices["vn"], cube.vertices["vt"], cube.indices, 5)
+    B.grid((-3.9, 0.5, -4.5), (0, 3, 0), (0, 0, 3), 1, 1, 6)                   # facing mirrors: on the left wall (+x) ...
+    B.grid((-2.9, 0.5, -4.5), (0, 0, 3), (0, 3, 0), 1, 1, 6)                   # ... and a free-standing panel 1 m in front of it (-x)
+    B.grid((-4, 0, MIRROR_ROOM_PLANE_Z), (0, 4, 0), (8, 0, 0), 1, 1, 6)        # the large mirror (-z)
+    vertices, indices, meshes = B.finish()
+
+    def placed(scale, angle_deg, axis, position):
+        a = np.radians(angle_deg)
+        c, s = np.cos(a), np.sin(a)
+        rot = {"y": [[c, 0, s], [0, 1, 0], [-s, 0, c]], "x": [[1, 0, 0], [0, c, -s], [0, s, c]]}[axis]
+        m = np.eye(4)
+        m[:3, :3] = np.array(rot) @ np.diag(scale)
+        m[:3, 3] = position
+        return m
+
+    mats = [np.eye(4), placed((0.6, 0.6, 0.6), 30.0, "y", (1.9, 0.6, 2.4)), placed((0.45, 0.45, 0.45), -20.0, "y", (2.9, 0.45, 0.6)),
+            placed((0.35, 0.35, 0.35), 12.0, "x", (-0.4, 0.43, 3.2)), placed((1.0, 1.0, 1.0), 25.0, "y", (-2.0, 1.3, 1.6))]
+    transforms = np.stack([np.asarray(m, np.float32).T.reshape(16) for m in mats])
+    instances = [(0, 0), (1, 0), (2, 0), (3, 0), (4, 0), (5, 1), (5, 2), (5, 3), (6, 4), (7, 0), (8, 0)] + ([(9, 0)] if mirror else [])
+    # Albedos of moderate contrast and few texels: the guides sample the albedo at the pixel centre while the path's samples are
+    # jittered over the pixel, so a demodulated pixel on a texture edge is wrong by the edge's contrast, whatever the guide mode
+    stripes = checker_texture(32, 4, 140, 240)
+    stripes[..., 0] = stripes[:, ::-1, 0] - 40                                 # a second, coloured pattern
+    stripes[..., 2] = np.roll(stripes[..., 2], 4, axis=0)
+    materials = [make_material("default"), make_material("floor", diffuse=1, diffuse_mul=(220, 200, 170)),
+                 make_material("plaster", diffuse=2, diffuse_mul=(235, 235, 235)), make_material("wall", diffuse=1, diffuse_mul=(150, 190, 215)),
+                 make_material("box", diffuse=2, diffuse_mul=(240, 170, 120)), make_material("slab", mtype=abi.MAT_GLASS, ior=1.5),
+                 make_material("mirror", mtype=abi.MAT_MIRROR)]
+    textures = [(abi.TEX_RGBA_SRGB, np.full((1, 1, 4), 255, np.uint8), "default"), (abi.TEX_RGBA_SRGB, checker_texture(32, 8, 150, 235), "checker"),
+                (abi.TEX_RGBA_SRGB, stripes, "stripes")]
+    lights = [make_light(abi.LIGHT_OMNI, "lamp", position=(0.5, 3.5, 1.0), intensity=12.0),
+              make_light(abi.LIGHT_OMNI, "front lamp", position=(-1.0, 3.2, -3.0), intensity=6.0)]
+    fov = np.float32(np.radians(np.float32(70.0)))
+    if view == "facing":
+        camera = make_camera(position=(-3.0, 2.0, -3.0), target=(-3.9, 1.9, -2.9), up=(0, 1, 0), fovx=fov, near=1e-2, far=100.0)
+    else:
+        camera = make_camera(position=(0.8, 2.0, -2.5), target=(0.0, 1.8, MIRROR_ROOM_PLANE_Z), up=(0, 1, 0), fovx=fov, near=1e-2, far=100.0)
+    meta = make_meta(centre=(0, 2, 0), radius=8.0, exposure=1.0)
+    return SceneDesc(vertices, indices, meshes, transforms, np.array(instances, INSTANCE_DTYPE), materials, lights, textures, camera, meta)

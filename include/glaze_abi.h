@@ -379,6 +379,34 @@ int glz_renderer_push_constants(glz_renderer*, float out32[32]);
 #define GLZ_AOV_ALBEDO_INSTANCE 1
 int glz_renderer_read_aov(glz_renderer*, int which, float* rgba32f_out);   /* runs the first-hit pass; W*H*4 floats, row-major */
 
+/* Which surface the two planes describe (glz_renderer_read_aov, glz_renderer_read_denoised; glaze-cli --guides).  The default is the first
+ * hit, as above.  GLZ_GUIDE_THROUGH_SPECULAR follows the ray the path itself would follow through the materials it flags specular (Mirror
+ * and Glass, RTMaterial::is_specular) to the first vertex that is not: inside a planar mirror and behind a window the filter then sees
+ * the reflected / refracted geometry and texture instead of one featureless surface.  THE SPECIFICATION (B = max_bounces,
+ * 1 <= B <= GLZ_GUIDE_MAX_BOUNCES):
+ *   THE CHAIN.  Segment 0 is the centre ray of the first-hit pass: camera_ray at (1/2, 1/2), tmin 1e-4, tmax inf.  Vertex k is the closest
+ *     hit of segment k (the render kernels' tracer, alpha tests inline).  If vertex k's material has is_specular != 0 and k < B, segment
+ *     k + 1 has origin = point and direction = wiW, tmin 1e-4, tmax inf, with point and wiW formed as the shading kernel forms them for the
+ *     path: barycentric point, object -> world; normal map, make_frame(dpdu, ns), woW = -direction of segment k; bsdf_sample at texture
+ *     level 0 -- the same operations in the same order, hence the same bits -- with xi = (0, 0, 1 - 2^-24): Mirror ignores xi, Glass takes
+ *     the transmitted branch unless its Fresnel term is 1 (total internal reflection), with the refraction as the renderer computes it
+ *     (Q7): the guide follows what the renderer shows.  The chain ends at vertex k when bsdf_sample returns pdf 0 or a direction that is not
+ *     finite.
+ *   THE REPORTING VERTEX r is the first vertex whose material is not specular.  If a segment j >= 1 misses, if the cap is reached (vertex B
+ *     is specular) or if the chain ends as above, r is the last vertex that was hit.  If segment 0 misses the pixel is a miss as above.
+ *   THE PLANES.  GLZ_AOV_NORMAL_DEPTH: xyz = the normal rule above at vertex r, turned against the direction of segment r;
+ *     w = ((t_0 + t_1) + ...) + t_r in binary32, in that order: the distance along the unfolded path, continuous across a planar mirror.
+ *     GLZ_AOV_ALBEDO_INSTANCE: rgb = the albedo rule above at vertex r ((1,1,1) when r is itself specular), w = the instance of vertex r.
+ *     A pixel whose first hit is not specular has the same bits in both modes.
+ * The setting is held by the root renderer only (like the denoiser's parameters: the post stage runs on its device), and changing it does
+ * not restart accumulation.  max_bounces is ignored with GLZ_GUIDE_FIRST_HIT.  GLZ_E_ARG, with nothing changed: a null renderer, an
+ * unknown mode, max_bounces outside 1 .. GLZ_GUIDE_MAX_BOUNCES with GLZ_GUIDE_THROUGH_SPECULAR. */
+#define GLZ_GUIDE_FIRST_HIT 0
+#define GLZ_GUIDE_THROUGH_SPECULAR 1
+#define GLZ_GUIDE_MAX_BOUNCES 8
+int glz_renderer_set_guide_mode(glz_renderer*, int mode, uint32_t max_bounces);
+int glz_renderer_guide_mode(glz_renderer*, uint32_t* max_bounces_out);   /* returns the mode (or a negative status); max_bounces_out may be NULL */
+
 /* The denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on the albedo-demodulated result image, guided by the two
  * planes above.  Its edge-stopping functions are rational (1 / (1 + r^2)) so that the whole filter is + - * /, comparisons and selects:
  * host and device compute it bit for bit alike.  THE SPECIFICATION (every operation in binary32, no contraction, in this order;
@@ -574,6 +602,12 @@ int glz_debug_denoise(glz_instance*, uint32_t w, uint32_t h, const float* result
 int glz_debug_post_timing(glz_renderer*, float ms_out[GLZ_POST_TIMING_SLOTS]);
 /* camera_ray() of every pixel at one sub-pixel offset, on the device: W*H*3 floats each, row-major (the first-hit pass uses 0.5, 0.5) */
 int glz_debug_camera_rays(glz_renderer*, float off_x, float off_y, float* origins3, float* dirs3);
+
+/* The rays of segment `segment` of every pixel's guide chain under the mode and cap in force (0 = the camera rays of the first-hit pass):
+ * W*H*3 floats each and W*H bytes, row-major.  alive[p] = 1 where pixel p's chain has that segment -- every pixel for segment 0; for
+ * segment k >= 1 the pixels whose vertices 0 .. k - 1 were all hit and specular and went on, with k <= max_bounces in
+ * GLZ_GUIDE_THROUGH_SPECULAR, none in GLZ_GUIDE_FIRST_HIT -- and its origin and direction are 0 where it has not. */
+int glz_debug_guide_chain(glz_renderer*, uint32_t segment, float* origins3, float* dirs3, uint8_t* alive);
 
 /* First contact with RCCL on this machine: a one-rank communicator on the instance's device (ncclCommInitAll), one
  * ncclReduce(sum, float) of n_floats values on the instance's stream, result compared bit for bit with the input, communicator

@@ -2,7 +2,11 @@
 attribute kernels), the demodulation and each a-trous pass (glz_debug_post_timing), next to one render launch of the same build in the
 same process and to a pass's byte floor (32 bytes read + 16 written per pixel at the 6.3 TB/s the microarchitecture notes give as
 achievable).  The render launch's total is a host clock around 64 launches that end in wait_idle; its k_trace / k_shade split is the
-renderer's own device-event statistics.  Run from the repository root on the GPU; writes nothing but its output."""
+renderer's own device-event statistics.  Then the guide modes: the first-hit pass with the attribute kernel (first_hit) against the
+chain of through_specular at caps 1 .. 8 on the atrium, which has no specular material -- every list is empty, so the slope over the cap
+is the cost of two empty launches -- and on tests/golden/mattest.glaze at 1024 x 1024, where half the frame is Glass: the time every
+bounce adds next to the number of rays alive in it.  Run from the repository root on the GPU; writes nothing but its output."""
+import os
 import statistics
 import sys
 import time
@@ -48,3 +52,42 @@ t = time.time()
 for _ in range(16):
     r.read_denoised()
 print("read_denoised() end to end, frame read back included: %.2f ms" % ((time.time() - t) / 16 * 1e3))
+
+
+# ---- guide modes: what follows k_first_hit (slot 'first_hit_attributes' of the timing hook) ----
+def after_trace(ren, reps=REPS):
+    for _ in range(4):
+        ren.debug_post_timing()
+    got = [ren.debug_post_timing() for _ in range(reps)]
+    return statistics.median(x["first_hit_trace"] for x in got) * 1e3, statistics.median(x["first_hit_attributes"] for x in got) * 1e3
+
+
+def guide_rows(name, ren, caps, counts):
+    ren.set_guide_mode("first_hit")
+    trace0, attr0 = after_trace(ren)
+    print("%s, first_hit: trace %.1f us + attributes %.1f us = %.1f us" % (name, trace0, attr0, trace0 + attr0))
+    before, rows = None, []
+    for cap in caps:
+        ren.set_guide_mode("through_specular", cap)
+        trace, chain = after_trace(ren)
+        alive = int(ren.debug_guide_chain(cap)[2].sum()) if counts else 0
+        rows.append((cap, chain))
+        print("%s, through_specular cap %d: trace %.1f us + chain %.1f us = %.1f us (+%.1f us on first_hit)%s" % (
+            name, cap, trace, chain, trace + chain, trace + chain - trace0 - attr0,
+            "" if before is None else "; bounce %d adds %.1f us%s" % (cap, chain - before, " for %d live rays" % alive if counts else "")))
+        if before is None and counts:
+            print("%s:   bounce 1 (in the cap-1 figure above) has %d live rays" % (name, alive))
+        before = chain
+    ren.set_guide_mode("first_hit")
+    return attr0, rows
+
+
+attr0, rows = guide_rows("atrium %d x %d" % (W, H), r, range(1, 9), False)
+slope = (rows[-1][1] - rows[0][1]) / (rows[-1][0] - rows[0][0])
+print("atrium: a bounce whose list is empty (k_guide_trace + k_guide_continue) costs %.1f us, one empty launch %.1f us; vertex 0 through k_guide_first "
+      "%.1f us against %.1f us through k_first_hit_attributes" % (slope, slope / 2, rows[0][1] - slope, attr0))
+mattest = os.path.join("tests", "golden", "mattest.glaze")
+m = glaze_amd.RayTraceRenderer.new(inst, glaze_amd.RayTraceScene.new(inst, glaze_amd.parse(mattest)), 1024, 1024)
+m.step(2)
+m.wait_idle()
+guide_rows("mattest 1024 x 1024", m, range(1, 5), True)
