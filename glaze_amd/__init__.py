@@ -24,7 +24,7 @@ from .abi import GlazeError
 from .scene_desc import SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
 
 __all__ = ["parse", "converted_file", "ParsedScene", "RayTraceInstance", "RayTraceScene", "RayTraceRenderer", "Integrator",
-           "GlazeError", "SceneDesc", "host_denoise"]
+           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle"]
 
 
 def _ptr(a):
@@ -182,6 +182,19 @@ def host_denoise(result, aov0, aov1, **params):
     out = np.zeros_like(r)
     p = abi.DenoiseParams(**params)
     abi.check(abi.lib().glz_host_denoise(r.shape[1], r.shape[0], _ptr(r), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out)))
+    return out
+
+
+def host_despeckle(result, aov0, aov1, with_filter=False, denoise=None, **params):
+    """glz_host_despeckle: the firefly rejection on the host (no device), the reference of k_despeckle.  Frames as host_denoise; params: the
+    fields of glz_despeckle_params (defaults: the library's); denoise: a dict of glz_denoise_params fields (only eps_albedo matters without
+    the filter).  with_filter: the filter's passes run on the rejection's output -- what read_denoised returns with the rejection enabled;
+    otherwise the re-modulated rejection output -- what read_despeckled returns."""
+    r, a0, a1 = _denoise_frames(result, aov0, aov1)
+    out = np.zeros_like(r)
+    d, p = abi.DespeckleParams(**params), abi.DenoiseParams(**(denoise or {}))
+    abi.check(abi.lib().glz_host_despeckle(r.shape[1], r.shape[0], _ptr(r), _ptr(a0), _ptr(a1), C.cast(C.byref(d), C.c_void_p), C.cast(C.byref(p), C.c_void_p),
+                                           1 if with_filter else 0, _ptr(out)))
     return out
 
 
@@ -348,6 +361,17 @@ class RayTraceInstance:
         p = abi.DenoiseParams(**params)
         abi.check(abi.lib().glz_debug_denoise(self._h, r.shape[1], r.shape[0], _ptr(r), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out)))
         return out
+
+    def debug_despeckle(self, result, aov0, aov1, with_filter=False, denoise=None, want_ms=False, **params):
+        """the device side of glaze_amd.host_despeckle on host arrays (upload, kernels, read back), bit for bit alike; with want_ms also the
+        device-event time of k_despeckle alone in milliseconds (a pair)"""
+        r, a0, a1 = _denoise_frames(result, aov0, aov1)
+        out = np.zeros_like(r)
+        d, p = abi.DespeckleParams(**params), abi.DenoiseParams(**(denoise or {}))
+        ms = C.c_float(0.0)
+        abi.check(abi.lib().glz_debug_despeckle(self._h, r.shape[1], r.shape[0], _ptr(r), _ptr(a0), _ptr(a1), C.cast(C.byref(d), C.c_void_p),
+                                                C.cast(C.byref(p), C.c_void_p), 1 if with_filter else 0, _ptr(out), C.cast(C.byref(ms), C.c_void_p)))
+        return (out, ms.value) if want_ms else out
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -694,6 +718,26 @@ class RayTraceRenderer:
         out = np.zeros((self.height, self.width, 4), np.float32)
         img = np.zeros((self.height, self.width, 4), np.uint8) if want_rgba8 else None
         abi.check(abi.lib().glz_renderer_read_denoised(self._h, _ptr(out), _ptr(img) if want_rgba8 else None))
+        return (out, img) if want_rgba8 else out
+
+    def set_despeckle(self, enabled=True, **params):
+        """Firefly rejection (glz_despeckle_params: radius, trim, ratio; those left out take the library's defaults).  enabled: read_denoised
+        runs it ahead of the filter; read_despeckled applies it whatever the flag says.  Accumulation goes on."""
+        p = abi.DespeckleParams(**params)
+        abi.check(abi.lib().glz_renderer_set_despeckle(self._h, 1 if enabled else 0, C.cast(C.byref(p), C.c_void_p)))
+
+    def despeckle(self):
+        """(enabled, dict of the parameters in force)"""
+        p = abi.DespeckleParams()
+        on = abi.check(abi.lib().glz_renderer_despeckle(self._h, C.cast(C.byref(p), C.c_void_p)))
+        return bool(on), dict(radius=p.radius, trim=p.trim, ratio=p.ratio)
+
+    def read_despeckled(self, want_rgba8=False):
+        """The result image through the firefly rejection alone (no filter pass): H x W x 4 float32, and with want_rgba8 also its 8-bit
+        sRGB image (a pair)."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        img = np.zeros((self.height, self.width, 4), np.uint8) if want_rgba8 else None
+        abi.check(abi.lib().glz_renderer_read_despeckled(self._h, _ptr(out), _ptr(img) if want_rgba8 else None))
         return (out, img) if want_rgba8 else out
 
     _GUIDE_MODES = {"first_hit": abi.GUIDE_FIRST_HIT, "through_specular": abi.GUIDE_THROUGH_SPECULAR}

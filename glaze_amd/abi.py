@@ -116,6 +116,18 @@ class DenoiseParams(C.Structure):
         super().__init__(**dict(self.DEFAULTS, **kw))
 
 
+class DespeckleParams(C.Structure):
+    """glz_despeckle_params; the defaults are the library's (glz_renderer_set_despeckle(r, enabled, NULL))"""
+    _fields_ = [("radius", C.c_uint32), ("trim", C.c_uint32), ("ratio", C.c_float)]
+    DEFAULTS = dict(radius=2, trim=2, ratio=8.0)
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown despeckle parameter(s): %s" % ", ".join(sorted(unknown)))
+        super().__init__(**dict(self.DEFAULTS, **kw))
+
+
 AOV_NORMAL_DEPTH, AOV_ALBEDO_INSTANCE = 0, 1
 GUIDE_FIRST_HIT, GUIDE_THROUGH_SPECULAR, GUIDE_MAX_BOUNCES = 0, 1, 8
 DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_POWER_LOG2 = 8, 31
@@ -228,6 +240,11 @@ PROTOTYPES = {
     "glz_renderer_read_aov": (C.c_int, [_P, C.c_int, _P]),
     "glz_renderer_set_denoise": (C.c_int, [_P, _P]),
     "glz_renderer_read_denoised": (C.c_int, [_P, _P, _P]),
+    "glz_renderer_set_despeckle": (C.c_int, [_P, C.c_int, _P]),
+    "glz_renderer_despeckle": (C.c_int, [_P, _P]),
+    "glz_renderer_read_despeckled": (C.c_int, [_P, _P, _P]),
+    "glz_host_despeckle": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "glz_debug_despeckle": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     "glz_host_denoise": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
     "glz_debug_denoise": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
     "glz_debug_camera_rays": (C.c_int, [_P, C.c_float, C.c_float, _P, _P]),

@@ -395,6 +395,21 @@ int glz_renderer_read_denoised(glz_renderer* h, float* rgba32f, uint8_t* rgba8) 
   GLZ_RET(h->r->read_denoised(rgba32f, rgba8, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_renderer_set_despeckle(glz_renderer* h, int enabled, const glz_despeckle_params* p) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  GLZ_RET(h->r->set_despeckle(enabled != 0, p, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_despeckle(glz_renderer* h, glz_despeckle_params* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  return h->r->despeckle(out);
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_read_despeckled(glz_renderer* h, float* rgba32f, uint8_t* rgba8) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  GLZ_RET(h->r->read_despeckled(rgba32f, rgba8, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_launch_constants(glz_renderer* h, uint32_t launch, uint32_t* seed, float off[2]) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!seed || !off) return fail(GLZ_E_ARG, "output is null");

@@ -294,6 +294,65 @@ int glz_debug_denoise(glz_instance* inst, uint32_t w, uint32_t h, const float* r
   });
   GLZ_GUARD_END(GLZ_E_IO)
 }
+namespace {
+// the checks glz_host_despeckle and glz_debug_despeckle share, as denoise_arguments.  Without the filter only eps_albedo of `p` is used, so
+// only that is taken from it: the rest of P is the defaults, and a caller's unused fields cannot fail the call
+int despeckle_arguments(uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1, const glz_despeckle_params* d,
+                        const glz_denoise_params* p, bool with_filter, float* out, glz_despeckle_params& D, glz_denoise_params& P) {
+  glz_denoise_params used = post::denoise_defaults();
+  if (p && with_filter) used = *p;
+  else if (p) used.eps_albedo = p->eps_albedo;
+  const int st = denoise_arguments(w, h, result, aov0, aov1, &used, out, P);
+  if (st < 0) return st;
+  D = d ? *d : post::despeckle_defaults();
+  if (!post::despeckle_params_valid(D)) return fail(GLZ_E_ARG, post::kDespeckleParamsMessage);
+  return st;
+}
+}  // namespace
+int glz_host_despeckle(uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1, const glz_despeckle_params* d, const glz_denoise_params* p,
+                       int with_filter, float* out) {
+  GLZ_GUARD_BEGIN
+  glz_denoise_params P;
+  glz_despeckle_params D;
+  const int st = despeckle_arguments(w, h, result, aov0, aov1, d, p, with_filter != 0, out, D, P);
+  if (st != 0) return st < 0 ? st : GLZ_OK;
+  post::host_despeckle(w, h, reinterpret_cast<const float4*>(result), reinterpret_cast<const float4*>(aov0), reinterpret_cast<const float4*>(aov1), D, P,
+                       with_filter != 0, reinterpret_cast<float4*>(out));
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_despeckle(glz_instance* inst, uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1, const glz_despeckle_params* d,
+                        const glz_denoise_params* p, int with_filter, float* out, float* kernel_ms_out) {
+  GLZ_GUARD_BEGIN
+  if (!inst) return fail(GLZ_E_ARG, "null argument");
+  glz_denoise_params P;
+  glz_despeckle_params D;
+  const int status = despeckle_arguments(w, h, result, aov0, aov1, d, p, with_filter != 0, out, D, P);
+  if (status < 0) return status;
+  if (kernel_ms_out) *kernel_ms_out = 0.0f;
+  if (status != 0) return GLZ_OK;
+  const size_t n = (size_t)w * h;
+  Error e;
+  if (!hip_ok(hipSetDevice(inst->i->device), "hipSetDevice", e)) return fail(e);
+  hipEvent_t ev[2] = {};
+  for (auto& v : ev)
+    if (!hip_ok(hipEventCreate(&v), "hipEventCreate", e)) {
+      if (ev[0]) (void)hipEventDestroy(ev[0]);
+      return fail(e);
+    }
+  const int rc = debug_call(inst->i.get(), "debug despeckle", "k_despeckle", [&](DebugCall& c) {
+    const float4* r = c.in(reinterpret_cast<const float4*>(result), n);
+    const float4* a0 = c.in(reinterpret_cast<const float4*>(aov0), n);
+    const float4* a1 = c.in(reinterpret_cast<const float4*>(aov1), n);
+    float4* ping = c.out<float4>(nullptr, n);
+    if (with_filter) return launch_denoise(c.st, w, h, P, r, a0, a1, ping, c.out<float4>(nullptr, n), c.out(reinterpret_cast<float4*>(out), n), nullptr, &D, ev);
+    return launch_despeckle(c.st, w, h, D, P.eps_albedo, r, a0, a1, ping, c.out(reinterpret_cast<float4*>(out), n), ev);
+  });
+  if (rc == GLZ_OK && kernel_ms_out) (void)hipEventElapsedTime(kernel_ms_out, ev[0], ev[1]);   // debug_call has synchronised the stream
+  for (auto& v : ev) (void)hipEventDestroy(v);
+  return rc;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_debug_tonemap(glz_instance* inst, const float* rgba32f, uint64_t n, uint8_t* out) {
   GLZ_GUARD_BEGIN
   if (!inst || !rgba32f || !out) return fail(GLZ_E_ARG, "null argument");

@@ -2,7 +2,8 @@
 // (cli/src/main.rs:24-39: `input output -r/--res WxH -s/--spp N -i/--integrator {direct,pt}`),
 // same messages and exit codes (cli/src/main.rs:41-135), driving the C ABI of libglaze_hip.so.
 // Build-defined extras: --seed, --depth, --device, --devices a,b,c (several GPUs of this process: tiles sharded, RCCL reduce),
-// --hdr-out file.pfm, --report (JSON on stdout), --denoise (the saved image and --hdr-out are the denoised ones), --aov-out PREFIX (the
+// --hdr-out file.pfm, --report (JSON on stdout), --denoise (the saved image and --hdr-out are the denoised ones), --despeckle / --despeckle-ratio R
+// (firefly rejection: ahead of the filter with --denoise, else the saved image and --hdr-out are the despeckled ones), --aov-out PREFIX (the
 // first-hit feature buffers: PREFIX.normal.png, PREFIX.albedo.png, PREFIX.depth.bin).
 #include <algorithm>
 #include <chrono>
@@ -100,6 +101,8 @@ void usage(const char* argv0) {
           "      --texture-lod <MODE>      [default: off] [possible values: off, cones, aniso] (off = level 0, what the reference's stages sample)\n"
           "      --hdr-out <FILE.pfm>      also write the float radiance image\n"
           "      --denoise                 save the denoised image (edge-avoiding a-trous filter guided by the first-hit buffers); --hdr-out then writes the denoised floats\n"
+          "      --despeckle               reject fireflies: clamp a hit pixel that stands above 8 x a robust mean of its 5 x 5 neighbourhood (albedo-demodulated); with --denoise ahead of the filter, else the saved image and --hdr-out are the despeckled ones\n"
+          "      --despeckle-ratio <R>     the rejection's threshold ratio, finite and at least 1 [default: 8]; implies --despeckle\n"
           "      --aov-out <PREFIX>        also write the first-hit feature buffers: PREFIX.normal.png (n / 2 + 1/2), PREFIX.albedo.png (sRGB), PREFIX.depth.bin (little-endian f32 rows, inf = miss)\n"
           "      --guides <MODE>           what --denoise and --aov-out take their feature buffers from [default: first-hit] [possible values: first-hit, through-specular[:N]] (through-specular: follow mirrors and glass to the first diffuse hit, at most N bounces, 1 .. 8 [default: 4])\n"
           "      --report                  print a JSON timing report on stdout\n",
@@ -115,7 +118,8 @@ int main(int argc, char** argv) {
   uint32_t depth = 6;
   int device = -1;
   std::vector<int> devices;
-  bool report = false, denoise = false;
+  bool report = false, denoise = false, despeckle = false;
+  const char* despeckle_ratio = nullptr;   // as given; null = not given
   std::vector<std::string> positional;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -149,6 +153,8 @@ int main(int argc, char** argv) {
     else if (a == "--hdr-out") hdr_out = value("--hdr-out");
     else if (a == "--aov-out") aov_out = value("--aov-out");
     else if (a == "--denoise") denoise = true;
+    else if (a == "--despeckle") despeckle = true;
+    else if (a == "--despeckle-ratio") { despeckle_ratio = value("--despeckle-ratio"); despeckle = true; }
     else if (a == "--guides") guides = value("--guides");
     else if (a == "--report") report = true;
     else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
@@ -165,6 +171,15 @@ int main(int argc, char** argv) {
   if (texture_lod != "off" && texture_lod != "cones" && texture_lod != "aniso") {
     fprintf(stderr, "error: invalid value '%s' for '--texture-lod' [possible values: off, cones, aniso]\n", texture_lod.c_str());
     return 2;
+  }
+  float despeckle_ratio_value = 0.0f;
+  if (despeckle_ratio) {
+    char* e = nullptr;
+    despeckle_ratio_value = strtof(despeckle_ratio, &e);
+    if (!*despeckle_ratio || *e || !(despeckle_ratio_value >= 1.0f && despeckle_ratio_value <= 3.4e38f)) {
+      fprintf(stderr, "error: invalid value '%s' for '--despeckle-ratio' (a finite number, at least 1)\n", despeckle_ratio);
+      return 2;
+    }
   }
   int guide_mode = GLZ_GUIDE_FIRST_HIT;
   uint32_t guide_bounces = 4;
@@ -231,6 +246,13 @@ int main(int argc, char** argv) {
   }
   glz_renderer_set_seed(renderer, seed);
   if (glz_renderer_set_guide_mode(renderer, guide_mode, guide_bounces) != GLZ_OK) { fprintf(stderr, "\n[ERROR] %s\n", glz_last_error()); return 1; }
+  if (despeckle) {
+    glz_despeckle_params p{};
+    bool ok = glz_renderer_despeckle(renderer, &p) >= 0;   // the library's defaults; only the ratio is the command line's
+    if (despeckle_ratio) p.ratio = despeckle_ratio_value;
+    ok = ok && glz_renderer_set_despeckle(renderer, 1, &p) == GLZ_OK;
+    if (!ok) { fprintf(stderr, "\n[ERROR] %s\n", glz_last_error()); return 1; }
+  }
   if (devices.size() > 1 && glz_renderer_set_devices(renderer, devices.data(), (int)devices.size()) != GLZ_OK) {
     fprintf(stderr, "\n[ERROR] %s\n", glz_last_error());
     return 1;
@@ -251,10 +273,11 @@ int main(int argc, char** argv) {
   const auto r1 = std::chrono::steady_clock::now();
   const double render_ms = std::chrono::duration<double, std::milli>(r1 - r0).count();
   fprintf(stderr, "\r%sDone (%.0f ms)%60s\n", pb.msg.c_str(), render_ms, "");
-  std::vector<float> denoised;
-  if (denoise) {
+  std::vector<float> denoised;   // the post stage's image: the filter's (with the rejection ahead of it if enabled), or the rejection's alone
+  const bool post = denoise || despeckle;
+  if (post) {
     denoised.resize((size_t)width * height * 4);
-    if (glz_renderer_read_denoised(renderer, denoised.data(), image.data()) != GLZ_OK) {
+    if ((denoise ? glz_renderer_read_denoised(renderer, denoised.data(), image.data()) : glz_renderer_read_despeckled(renderer, denoised.data(), image.data())) != GLZ_OK) {
       fprintf(stderr, "[ERROR] %s\n", glz_last_error());
       return 1;
     }
@@ -268,8 +291,8 @@ int main(int argc, char** argv) {
   }
   if (!hdr_out.empty()) {
     std::vector<float> hdr((size_t)width * height * 4);
-    if (denoise) hdr = denoised;   // .w = 1 where the pixel was ever updated: write_pfm's division leaves the values as they are
-    if ((!denoise && glz_renderer_read_hdr(renderer, hdr.data()) != GLZ_OK) || !write_pfm(hdr_out, hdr.data(), (uint32_t)width, (uint32_t)height)) {
+    if (post) hdr = denoised;   // .w = 1 where the pixel was ever updated: write_pfm's division leaves the values as they are
+    if ((!post && glz_renderer_read_hdr(renderer, hdr.data()) != GLZ_OK) || !write_pfm(hdr_out, hdr.data(), (uint32_t)width, (uint32_t)height)) {
       fprintf(stderr, "[ERROR] Failed to save the HDR image: %s\n", hdr_out.c_str());
       rc = 1;
     }

@@ -1,4 +1,5 @@
-// The edge-avoiding a-trous filter of glz_denoise_params (include/glaze_abi.h holds the specification), one pixel of one pass, in the
+// The edge-avoiding a-trous filter of glz_denoise_params and the firefly rejection of glz_despeckle_params (include/glaze_abi.h holds the
+// specifications), one pixel of one pass, in the
 // ONE form both the host reference (glz_host_denoise, g++) and the device kernels (kernels_post.hip, hipcc) compile: the same operations
 // in the same order, -ffp-contract=off and correctly rounded divisions on both sides, so the two agree bit for bit.  Only + - * /,
 // comparisons and selects; no library function.
@@ -133,8 +134,92 @@ GLZ_POST_FN float4 remodulate(float4 i, float4 albedo, float eps) {
   return make_float4(i.x * a.x, i.y * a.y, i.z * a.z, i.w);
 }
 
+// ---- firefly rejection (glz_despeckle_params; include/glaze_abi.h holds the specification) ----------------------------------------
+inline glz_despeckle_params despeckle_defaults() { return glz_despeckle_params{2u, 2u, 8.0f}; }
+// radius 1 or 2 (the window unrolls: a template parameter of the kernel), trim 0 .. 3 (the sorted top-4), ratio finite and >= 1
+inline bool despeckle_params_valid(const glz_despeckle_params& p) {
+  return (p.radius == 1u || p.radius == 2u) && p.trim <= GLZ_DESPECKLE_MAX_TRIM && p.ratio >= 1.0f && p.ratio <= 3.4e38f;
+}
+constexpr const char* kDespeckleParamsMessage = "despeckle: radius must be 1 or 2, trim 0 .. 3, ratio finite and at least 1";
+
+// i_0'(p) of pixel (x, y): `in` = i_0, aov0 = (normal.xyz, depth), both w * h row-major.  The window row by row (dy outer, dx inner); its
+// L values stay in `l` (-inf where q is not usable: such an entry can never displace one of the m > trim real ones from the top
+// trim + 1, and `use` keeps it out of the sum).  M comes from a sorted top-4 kept by compare and select.
+template <int RADIUS>
+GLZ_POST_FN float4 despeckle_pixel(const float4* __restrict__ in, const float4* __restrict__ aov0, uint32_t w, uint32_t h, uint32_t x, uint32_t y, uint32_t trim,
+                                   float ratio) {
+  constexpr int kSide = 2 * RADIUS + 1;
+  constexpr float kLowest = -__builtin_huge_valf();
+  const size_t ip = (size_t)y * w + x;
+  const float4 cp = in[ip];
+  if (!(finite1(aov0[ip].w) && finite3(cp))) return cp;   // not a candidate
+  float l[kSide * kSide];
+  bool use[kSide * kSide];
+  float t0 = kLowest, t1 = kLowest, t2 = kLowest, t3 = kLowest;   // the four largest, t0 >= t1 >= t2 >= t3
+  uint32_t m = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int dy = -RADIUS; dy <= RADIUS; ++dy) {
+    const int qy = (int)y + dy;
+    const bool row_in = qy >= 0 && qy < (int)h;
+    const size_t row = (size_t)(row_in ? qy : (int)y) * w;   // (a row outside the image reads the pixel's own and is dropped below)
+    // the row's values of both planes are requested before any of them is used (an x outside the image reads the clamped column)
+    float4 cqs[kSide];
+    float zqs[kSide];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int dx = -RADIUS; dx <= RADIUS; ++dx) {
+      const int qx = (int)x + dx;
+      const size_t iq = row + (size_t)(qx < 0 ? 0 : (qx >= (int)w ? (int)w - 1 : qx));
+      cqs[dx + RADIUS] = in[iq];
+      zqs[dx + RADIUS] = aov0[iq].w;
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int dx = -RADIUS; dx <= RADIUS; ++dx) {
+      const int qx = (int)x + dx;
+      const float4 cq = cqs[dx + RADIUS];
+      const bool ok = row_in && qx >= 0 && qx < (int)w && (dx != 0 || dy != 0) && finite1(zqs[dx + RADIUS]) && finite3(cq);
+      float v = ok ? (cq.x + cq.y) + cq.z : kLowest;
+      const int i = (dy + RADIUS) * kSide + (dx + RADIUS);
+      l[i] = v;
+      use[i] = ok;
+      m += ok ? 1u : 0u;
+      // insert v into the sorted four: at each place the larger stays, the smaller moves on
+      float hi;
+      hi = v > t0 ? v : t0; v = v > t0 ? t0 : v; t0 = hi;
+      hi = v > t1 ? v : t1; v = v > t1 ? t1 : v; t1 = hi;
+      hi = v > t2 ? v : t2; v = v > t2 ? t2 : v; t2 = hi;
+      t3 = v > t3 ? v : t3;
+    }
+  }
+  if (m <= trim) return cp;
+  const float M = trim == 0u ? t0 : (trim == 1u ? t1 : (trim == 2u ? t2 : t3));
+  float sum = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int i = 0; i < kSide * kSide; ++i) {
+    const float v = l[i] < M ? l[i] : M;
+    sum = use[i] ? sum + v : sum;
+  }
+  const float mu = sum / (float)m;
+  const float T = ratio * mu;
+  const float lp = (cp.x + cp.y) + cp.z;
+  if (!(T >= 0.0f && lp > T)) return cp;
+  const float f = T / lp;
+  return make_float4(cp.x * f, cp.y * f, cp.z * f, cp.w);
+}
+
 // the whole filter on host arrays (denoise_host.cpp); P must be valid, out must not overlap an input
 void host_denoise(uint32_t w, uint32_t h, const float4* result, const float4* aov0, const float4* aov1, const glz_denoise_params& P, float4* out);
+// the rejection of D on the demodulated image, then either out = i_0' * A (with_filter false: only P.eps_albedo is used) or the filter's
+// passes on i_0' -- the composition read_denoised runs when the rejection is enabled.  D and P must be valid, out must not overlap an input
+void host_despeckle(uint32_t w, uint32_t h, const float4* result, const float4* aov0, const float4* aov1, const glz_despeckle_params& D,
+                    const glz_denoise_params& P, bool with_filter, float4* out);
 
 }  // namespace post
 }  // namespace glz

@@ -1,5 +1,5 @@
-// glz_host_denoise: the filter of glz_denoise_params (denoise.h) on the host cores, no device -- the reference the device kernels are
-// compared with bit for bit.  Rows are dealt to a few threads; pixels of a pass do not interact, so the result does not depend on them.
+// glz_host_denoise and glz_host_despeckle: the filter of glz_denoise_params and the firefly rejection of glz_despeckle_params (denoise.h)
+// on the host cores, no device -- the reference the device kernels are compared with bit for bit.  Rows are dealt to a few threads; pixels of a pass do not interact, so the result does not depend on them.
 #include <algorithm>
 #include <thread>
 #include <vector>
@@ -25,18 +25,13 @@ void for_rows(uint32_t h, uint32_t w, F f) {
     });
   for (auto& th : pool) th.join();
 }
-}  // namespace
 
-void host_denoise(uint32_t w, uint32_t h, const float4* result, const float4* aov0, const float4* aov1, const glz_denoise_params& P, float4* out) {
-  const size_t n = (size_t)w * h;
-  std::vector<float4> ping(n), pong(P.iterations > 1u ? n : 0);
-  for_rows(h, w, [&](uint32_t y) {
-    for (size_t p = (size_t)y * w; p < (size_t)(y + 1) * w; ++p) ping[p] = demodulate(result[p], aov1[p], P.eps_albedo);
-  });
-  const float4* src = ping.data();
+// the filter's passes on i_0 = src, which is `ping` or `pong`; the last one re-modulates into out
+void filter_passes(uint32_t w, uint32_t h, const float4* src, float4* ping, float4* pong, const float4* aov0, const float4* aov1, const glz_denoise_params& P,
+                   float4* out) {
   for (uint32_t k = 0; k < P.iterations; ++k) {
     const bool last = k + 1 == P.iterations;
-    float4* dst = last ? out : (src == ping.data() ? pong.data() : ping.data());
+    float4* dst = last ? out : (src == ping ? pong : ping);
     for_rows(h, w, [&](uint32_t y) {
       for (uint32_t x = 0; x < w; ++x) {
         float4 v = atrous_pixel(src, aov0, w, h, x, y, k, P);
@@ -47,6 +42,35 @@ void host_denoise(uint32_t w, uint32_t h, const float4* result, const float4* ao
     });
     src = dst;
   }
+}
+void demodulate_frame(uint32_t w, uint32_t h, const float4* result, const float4* aov1, float eps_albedo, float4* out) {
+  for_rows(h, w, [&](uint32_t y) {
+    for (size_t p = (size_t)y * w; p < (size_t)(y + 1) * w; ++p) out[p] = demodulate(result[p], aov1[p], eps_albedo);
+  });
+}
+}  // namespace
+
+void host_denoise(uint32_t w, uint32_t h, const float4* result, const float4* aov0, const float4* aov1, const glz_denoise_params& P, float4* out) {
+  const size_t n = (size_t)w * h;
+  std::vector<float4> ping(n), pong(P.iterations > 1u ? n : 0);
+  demodulate_frame(w, h, result, aov1, P.eps_albedo, ping.data());
+  filter_passes(w, h, ping.data(), ping.data(), pong.data(), aov0, aov1, P, out);
+}
+
+void host_despeckle(uint32_t w, uint32_t h, const float4* result, const float4* aov0, const float4* aov1, const glz_despeckle_params& D,
+                    const glz_denoise_params& P, bool with_filter, float4* out) {
+  const size_t n = (size_t)w * h;
+  std::vector<float4> ping(n), pong(with_filter ? n : 0);
+  demodulate_frame(w, h, result, aov1, P.eps_albedo, ping.data());
+  float4* dst = with_filter ? pong.data() : out;
+  for_rows(h, w, [&](uint32_t y) {
+    for (uint32_t x = 0; x < w; ++x) {
+      const float4 v = D.radius == 1u ? despeckle_pixel<1>(ping.data(), aov0, w, h, x, y, D.trim, D.ratio) : despeckle_pixel<2>(ping.data(), aov0, w, h, x, y, D.trim, D.ratio);
+      const size_t p = (size_t)y * w + x;
+      dst[p] = with_filter ? v : remodulate(v, aov1[p], P.eps_albedo);
+    }
+  });
+  if (with_filter) filter_passes(w, h, pong.data(), ping.data(), pong.data(), aov0, aov1, P, out);
 }
 
 }  // namespace post

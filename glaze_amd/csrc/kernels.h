@@ -190,8 +190,14 @@ hipError_t launch_camera_rays(hipStream_t st, const LaunchArgs& a, float off_x, 
 // The filter of glz_denoise_params on row-major device frames: demodulation, `iterations` a-trous passes (one launch each, ping-pong),
 // re-modulation in the last pass's store.  ping, pong and out are three different frames of w * h pixels; out may not alias an input.
 // marks (timing, may be null): 2 + iterations events recorded before the demodulation, after it and after every pass.
+// despeckle (may be null = exactly the launches above): the firefly rejection of glz_despeckle_params between the demodulation and the first
+// pass, ping -> pong, the passes then start from pong.  despeckle_marks (may be null): two events recorded around k_despeckle alone.
 hipError_t launch_denoise(hipStream_t st, uint32_t w, uint32_t h, const glz_denoise_params& params, const float4* result, const float4* aov0,
-                          const float4* aov1, float4* ping, float4* pong, float4* out, hipEvent_t* marks = nullptr);
+                          const float4* aov1, float4* ping, float4* pong, float4* out, hipEvent_t* marks = nullptr,
+                          const glz_despeckle_params* despeckle = nullptr, hipEvent_t* despeckle_marks = nullptr);
+// The rejection alone: demodulation into ping, then out = i_0' * max(albedo, eps_albedo) in k_despeckle's store.  No a-trous pass.
+hipError_t launch_despeckle(hipStream_t st, uint32_t w, uint32_t h, const glz_despeckle_params& params, float eps_albedo, const float4* result,
+                            const float4* aov0, const float4* aov1, float4* ping, float4* out, hipEvent_t* despeckle_marks = nullptr);
 
 // debug / parity hooks
 hipError_t launch_debug_closest(hipStream_t st, const DeviceScene& scene, const float* origins, const float* dirs, uint32_t n, float tmin,

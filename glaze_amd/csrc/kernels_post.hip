@@ -346,6 +346,25 @@ __global__ void __launch_bounds__(kBlock) k_atrous(uint32_t w, uint32_t h, uint3
 }
 
 // ---------------------------------------------------------------------------------------------
+// Firefly rejection (glz_despeckle_params; post::despeckle_pixel holds the arithmetic).  k_atrous's layout: every window row a wave reads is
+// one coalesced line per plane (the colours as 16-byte lanes, the depths as the .w dwords of theirs), requested together before the first
+// value is used; columns outside the image read the clamped column and are dropped.  The window's L values stay in registers (RADIUS is a
+// template parameter: both loops unroll), M comes from a sorted top-4 kept by compare and select: no loop with a data-dependent trip count,
+// no LDS, no scratch.  Two correctly rounded divisions per pixel that is clamped, one per candidate that is not.
+// REMODULATE: out = i_0' * max(albedo, eps_a), the stand-alone read; otherwise out = i_0', what the filter's first pass reads.
+// ---------------------------------------------------------------------------------------------
+template <int RADIUS, bool REMODULATE>
+__global__ void __launch_bounds__(kBlock) k_despeckle(uint32_t w, uint32_t h, uint32_t trim, float ratio, float eps_albedo, const float4* __restrict__ in,
+                                                      const float4* __restrict__ aov0, const float4* __restrict__ aov1, float4* __restrict__ out) {
+  const uint32_t x = blockIdx.x * kPostTileW + (threadIdx.x & 63u), y = blockIdx.y * kPostTileH + (threadIdx.x >> 6);
+  if (x >= w || y >= h) return;
+  float4 v = post::despeckle_pixel<RADIUS>(in, aov0, w, h, x, y, trim, ratio);
+  const size_t p = (size_t)y * w + x;
+  if (REMODULATE) v = post::remodulate(v, aov1[p], eps_albedo);
+  out[p] = v;
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 // blocks of k_first_hit's persistent grid (the render tracers' residency rule)
@@ -390,16 +409,30 @@ hipError_t launch_camera_rays(hipStream_t st, const LaunchArgs& a, float off_x, 
   const uint32_t n = a.map.width * a.map.height;
   return launch_per_item(st, k_camera_rays, n, a, off_x, off_y, origins3, dirs3);
 }
+static dim3 post_tile_grid(uint32_t w, uint32_t h) { return dim3((w + kPostTileW - 1) / kPostTileW, (h + kPostTileH - 1) / kPostTileH); }
+template <bool REMODULATE>
+static void launch_despeckle_kernel(hipStream_t st, uint32_t w, uint32_t h, const glz_despeckle_params& D, float eps_albedo, const float4* in, const float4* aov0,
+                                    const float4* aov1, float4* out, hipEvent_t* marks) {
+  if (marks) (void)hipEventRecord(marks[0], st);
+  if (D.radius == 1u) hipLaunchKernelGGL((k_despeckle<1, REMODULATE>), post_tile_grid(w, h), dim3(kBlock), 0, st, w, h, D.trim, D.ratio, eps_albedo, in, aov0, aov1, out);
+  else hipLaunchKernelGGL((k_despeckle<2, REMODULATE>), post_tile_grid(w, h), dim3(kBlock), 0, st, w, h, D.trim, D.ratio, eps_albedo, in, aov0, aov1, out);
+  if (marks) (void)hipEventRecord(marks[1], st);
+}
 hipError_t launch_denoise(hipStream_t st, uint32_t w, uint32_t h, const glz_denoise_params& P, const float4* result, const float4* aov0, const float4* aov1,
-                          float4* ping, float4* pong, float4* out, hipEvent_t* marks) {
+                          float4* ping, float4* pong, float4* out, hipEvent_t* marks, const glz_despeckle_params* despeckle, hipEvent_t* despeckle_marks) {
   if (w == 0 || h == 0) return hipSuccess;
   if (!post::denoise_params_valid(P) || (uint64_t)w * h > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  if (despeckle && !post::despeckle_params_valid(*despeckle)) return hipErrorInvalidValue;
   const uint32_t n = w * h;
   if (marks) (void)hipEventRecord(marks[0], st);
   hipLaunchKernelGGL(k_demodulate, grid_for(n), dim3(kBlock), 0, st, n, result, aov1, P.eps_albedo, ping);
   if (marks) (void)hipEventRecord(marks[1], st);
-  const dim3 grid((w + kPostTileW - 1) / kPostTileW, (h + kPostTileH - 1) / kPostTileH);
   const float4* src = ping;
+  if (despeckle) {   // ping -> pong, and the passes start from pong: no pixel sees a clamped neighbour, no further frame is needed
+    launch_despeckle_kernel<false>(st, w, h, *despeckle, P.eps_albedo, ping, aov0, aov1, pong, despeckle_marks);
+    src = pong;
+  }
+  const dim3 grid = post_tile_grid(w, h);
   for (uint32_t k = 0; k < P.iterations; ++k) {
     const bool last = k + 1 == P.iterations;
     float4* dst = last ? out : (src == ping ? pong : ping);
@@ -408,6 +441,15 @@ hipError_t launch_denoise(hipStream_t st, uint32_t w, uint32_t h, const glz_deno
     if (marks) (void)hipEventRecord(marks[2 + k], st);
     src = dst;
   }
+  return hipGetLastError();
+}
+hipError_t launch_despeckle(hipStream_t st, uint32_t w, uint32_t h, const glz_despeckle_params& D, float eps_albedo, const float4* result, const float4* aov0,
+                            const float4* aov1, float4* ping, float4* out, hipEvent_t* despeckle_marks) {
+  if (w == 0 || h == 0) return hipSuccess;
+  if (!post::despeckle_params_valid(D) || (uint64_t)w * h > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  const uint32_t n = w * h;
+  hipLaunchKernelGGL(k_demodulate, grid_for(n), dim3(kBlock), 0, st, n, result, aov1, eps_albedo, ping);
+  launch_despeckle_kernel<true>(st, w, h, D, eps_albedo, ping, aov0, aov1, out, despeckle_marks);
   return hipGetLastError();
 }
 

@@ -214,6 +214,7 @@ Renderer* Renderer::create(Instance* inst, std::shared_ptr<Scene> scene, uint32_
   r->w_ = w;
   r->h_ = h;
   r->denoise_ = post::denoise_defaults();
+  r->despeckle_ = post::despeckle_defaults();
   r->cfg_.camera = scene->data.camera;
   r->cfg_.exposure = scene->data.meta.exposure;
   host::push_constants(r->cfg_.camera, w, h, r->cfg_.cam.camera2world, r->cfg_.cam.screen2camera);
@@ -1223,10 +1224,45 @@ bool Renderer::read_denoised(float* rgba32f, uint8_t* rgba8, Error& err) {
   if (!first_hit_pass(err)) return false;
   if (!ensure_denoise_frames(err)) return false;
   hipStream_t st = chains_[0]->stream;   // = the instance stream the first-hit pass ran on
-  if (!hip_ok(launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr), "k_atrous", err)) return false;
+  if (!hip_ok(launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr, nullptr, despeckle_on_ ? &despeckle_ : nullptr),
+              "k_atrous", err))
+    return false;
   if (rgba32f && !frame_to_host(dn_out_.ptr, rgba32f, "read denoised", err)) return false;
   if (rgba8 && !rgba8_to_host(dn_out_.ptr, rgba8, "read denoised", "read denoised", err)) return false;
   return hip_ok(hipStreamSynchronize(st), "read denoised", err);   // with neither output the filter has still run when this returns
+}
+
+bool Renderer::set_despeckle(bool enabled, const glz_despeckle_params* p, Error& err) {
+  const glz_despeckle_params v = p ? *p : post::despeckle_defaults();
+  if (!post::despeckle_params_valid(v)) {
+    err.code = GLZ_E_ARG;
+    err.msg = post::kDespeckleParamsMessage;
+    return false;
+  }
+  despeckle_ = v;
+  despeckle_on_ = enabled;
+  return true;
+}
+int Renderer::despeckle(glz_despeckle_params* out) const {
+  if (out) *out = despeckle_;
+  return despeckle_on_ ? 1 : 0;
+}
+
+bool Renderer::read_despeckled(float* rgba32f, uint8_t* rgba8, Error& err) {
+  if (world_ > 1 && peers_.empty()) {   // as read_denoised
+    err.code = GLZ_E_ARG;
+    err.msg = "read_despeckled: under set_partition(world > 1) the frame is not in this process";
+    return false;
+  }
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
+  if (!gather(true, frame_tmp_.ptr, err)) return false;
+  if (!first_hit_pass(err)) return false;
+  if (!ensure_denoise_frames(err)) return false;
+  hipStream_t st = chains_[0]->stream;
+  if (!hip_ok(launch_despeckle(st, w_, h_, despeckle_, denoise_.eps_albedo, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_out_.ptr), "k_despeckle", err)) return false;
+  if (rgba32f && !frame_to_host(dn_out_.ptr, rgba32f, "read despeckled", err)) return false;
+  if (rgba8 && !rgba8_to_host(dn_out_.ptr, rgba8, "read despeckled", "read despeckled", err)) return false;
+  return hip_ok(hipStreamSynchronize(st), "read despeckled", err);
 }
 
 bool Renderer::set_texture_lod(int mode, Error& err) {

@@ -37,6 +37,10 @@ class Renderer {
   bool read_aov(int which, float* out, Error& err);                   // runs the first-hit pass; GLZ_AOV_*
   bool set_denoise(const glz_denoise_params* p, Error& err);          // null = defaults; accumulation goes on
   bool read_denoised(float* rgba32f, uint8_t* rgba8, Error& err);     // gather + first-hit pass + filter; either output may be null
+  // firefly rejection (glz_despeckle_params): enabled = ahead of the filter in read_denoised; null = defaults; accumulation goes on
+  bool set_despeckle(bool enabled, const glz_despeckle_params* p, Error& err);
+  int despeckle(glz_despeckle_params* out) const;                      // the enabled flag
+  bool read_despeckled(float* rgba32f, uint8_t* rgba8, Error& err);    // gather + first-hit pass + demodulation + rejection; no filter pass
   bool camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err);   // camera_ray() of every pixel, on the device
   // which surface the feature buffers describe (GLZ_GUIDE_*, glaze_abi.h holds the specification); accumulation goes on
   bool set_guide_mode(int mode, uint32_t max_bounces, Error& err);
@@ -103,8 +107,8 @@ class Renderer {
   std::shared_ptr<Scene> scene_;   // shared with the glz_scene handle it came from (info / debug hooks stay valid)
   uint32_t w_ = 0, h_ = 0;
   // What every device of set_devices must agree on to render one image: a new peer takes it over by one assignment, the setters
-  // forward every change.  Deliberately not in here: the partition (rank_, world_: each device has its own), the denoiser's parameters
-  // and the post buffers (the post stage runs on this device only, on the gathered frame), and everything allocate() derives.
+  // forward every change.  Deliberately not in here: the partition (rank_, world_: each device has its own), the denoiser's and the
+  // rejection's parameters and the post buffers (the post stage runs on this device only, on the gathered frame), and everything allocate() derives.
   struct Settings {
     int integrator = GLZ_PATH_TRACE;
     uint32_t pt_steps = 6;   // PT_STEPS, raytrace_structures.rs:87
@@ -205,6 +209,8 @@ class Renderer {
   DeviceBuffer<float4> fh_hit_, aov0_, aov1_, dn_ping_, dn_pong_, dn_out_;
   DeviceBuffer<uint32_t> fh_inst_, fh_overflow_;
   glz_denoise_params denoise_;   // set in create()
+  glz_despeckle_params despeckle_;   // set in create()
+  bool despeckle_on_ = false;
   int guide_mode_ = GLZ_GUIDE_FIRST_HIT;
   uint32_t guide_bounces_ = 4;
   DeviceBuffer<float4> guide_o_[2], guide_d_[2];   // the chain's ray lists (GuideLists), allocated on first use in GLZ_GUIDE_THROUGH_SPECULAR

@@ -452,6 +452,49 @@ int glz_renderer_set_denoise(glz_renderer*, const glz_denoise_params*);   /* NUL
  * glz_renderer_read_rgba8.  GLZ_E_ARG under glz_renderer_set_partition(world > 1): the frame is not in this process. */
 int glz_renderer_read_denoised(glz_renderer*, float* rgba32f_out, uint8_t* rgba8_out);
 
+/* Firefly rejection: an opt-in stage of the post stage that clamps a hit pixel whose demodulated brightness stands far above a robust mean
+ * of its neighbours'.  The a-trous filter above cannot do this: its colour weight is relative (Wc >= 16/18 in pass 0 at the default
+ * sigma_color however bright the neighbour is), so a firefly enters every pixel within reach at almost full weight.  The rule edits no
+ * render kernel and is, like the filter, + - * /, comparisons and selects: host and device compute it bit for bit alike.
+ * THE SPECIFICATION (every operation in binary32, no contraction, in this order; finite, A, i_0 and hit as the filter defines them, with
+ * the eps_albedo of the denoise parameters in force):
+ *   L(p)      = (i_0(p).x + i_0(p).y) + i_0(p).z
+ *   usable(q) = q inside the image, hit(q), all three channels of i_0(q) finite
+ *   p is a CANDIDATE iff usable(p).  Every other pixel (misses, non-finite pixels) passes through unchanged and is nobody's neighbour.
+ *   window: q = p + (dx, dy), dy = -radius .. radius outer, dx = -radius .. radius inner, q != p, usable(q);  m = their number
+ *   if m <= trim: unchanged
+ *   M  = the (trim + 1)-th largest L(q) of the window, counted with multiplicity
+ *   mu = (sum over the window, in window order, of (L(q) < M ? L(q) : M)) / float(m)      (a winsorised mean: no cancellation, ties are
+ *                                                                                          harmless)
+ *   T  = ratio * mu
+ *   if T >= 0 and L(p) > T:  f = T / L(p);  i_0'(p).rgb = (i_0(p).x * f, i_0(p).y * f, i_0(p).z * f)    else i_0'(p) = i_0(p)
+ *   .w passes through
+ * All reads come from i_0 and all writes go to another frame: no pixel sees a neighbour that has already been clamped.  Misses (the sky,
+ * the sun seen directly) are noise-free in this renderer and are never touched.
+ * With the rejection enabled glz_renderer_read_denoised runs the filter's passes on i_0' instead of i_0; glz_renderer_read_despeckled
+ * returns i_0' * A with no filter pass at all.
+ * Defaults (params NULL): radius 2, trim 2, ratio 8.  GLZ_E_ARG, before anything is launched and with nothing changed: radius other than 1
+ * or 2, trim above GLZ_DESPECKLE_MAX_TRIM (3), a ratio that is not finite or below 1.
+ * KNOWN COSTS.  It is a biased estimator: it removes energy.  A lit pixel whose window holds at most `trim` lit neighbours goes black
+ * (M = 0, hence T = 0).  An isolated one-pixel emitter is treated as a firefly.  A cluster of more than `trim` adjacent fireflies
+ * survives -- counted as the rule counts, q != p: a firefly with more than `trim` fireflies among its window's neighbours, for then M is a
+ * firefly's L (T is at least (trim + 1) * ratio / m of it).  With up to `trim` of them around it, it is brought down like a lone one. */
+#define GLZ_DESPECKLE_MAX_TRIM 3
+typedef struct glz_despeckle_params {
+  uint32_t radius, trim;
+  float ratio;
+} glz_despeckle_params;
+/* params NULL = defaults; enabled != 0 puts the rejection ahead of the filter in glz_renderer_read_denoised.  The default state is
+ * disabled.  Held by the root renderer only, like the denoiser's parameters; does not restart accumulation and touches neither the path
+ * state nor the accumulators. */
+int glz_renderer_set_despeckle(glz_renderer*, int enabled, const glz_despeckle_params*);
+int glz_renderer_despeckle(glz_renderer*, glz_despeckle_params* out);   /* returns the enabled flag (or a negative status); out may be NULL */
+/* The result image through the rejection alone, with the parameters in force whatever the enabled flag says: gathers and runs the
+ * first-hit pass (or the guide chain of the mode in force) like glz_renderer_read_denoised, then i_0' * A; no filter pass runs.  Either
+ * output may be NULL; rgba8_out goes through the sRGB quantiser of glz_renderer_read_rgba8.  GLZ_E_ARG under
+ * glz_renderer_set_partition(world > 1). */
+int glz_renderer_read_despeckled(glz_renderer*, float* rgba32f_out, uint8_t* rgba8_out);
+
 /* Multi-GPU (one process per GPU): this renderer owns the 64x64-pixel tiles t with
  * t % world == rank; other pixels stay zero.  The exchange of the HDR accumulator itself is done
  * by the caller (RCCL through torch.distributed or rccl directly) on the device buffers below. */
@@ -595,6 +638,10 @@ int glz_debug_light_sample(glz_scene*, uint32_t light_index, const float* pos3, 
 /* The device filter of glz_denoise_params on host arrays (w*h*4 floats each, row-major): upload, kernels, read back.  params NULL = defaults. */
 int glz_debug_denoise(glz_instance*, uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1,
                       const glz_denoise_params*, float* out);
+/* The device side of glz_host_despeckle on host arrays: upload, k_demodulate, k_despeckle (and the filter's passes with with_filter), read
+ * back.  kernel_ms_out (may be NULL) receives the device-event time of k_despeckle alone, in milliseconds. */
+int glz_debug_despeckle(glz_instance*, uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1,
+                        const glz_despeckle_params*, const glz_denoise_params*, int with_filter, float* out, float* kernel_ms_out);
 /* One run of the post stages of this renderer between device events (hipEvent on the instance stream), in ms: ms_out[0] the first-hit
  * trace kernel, [1] its attribute kernel, [2] the demodulation, [3 + k] a-trous pass k (entries past the configured iterations are 0).
  * Gathers the result image first, like glz_renderer_read_denoised; nothing is read back. */
@@ -639,6 +686,12 @@ int glz_host_build_sah(uint32_t n, const float* box_lo, const float* box_hi, int
  * result / aov0 / aov1 / out: w*h*4 floats, row-major; out must not overlap an input.  params NULL = defaults. */
 int glz_host_denoise(uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1,
                      const glz_denoise_params*, float* out);
+/* the firefly rejection of glz_despeckle_params on the host, no device (either params NULL = defaults).  with_filter = 0: out = i_0' * A,
+ * and only eps_albedo of the denoise parameters is used (the other fields are not read, and not checked).  with_filter != 0: all of them
+ * must be valid, and the filter's passes run on i_0' -- the composition
+ * glz_renderer_read_denoised equals bit for bit when the rejection is enabled. */
+int glz_host_despeckle(uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1,
+                       const glz_despeckle_params*, const glz_denoise_params*, int with_filter, float* out);
 /* the host rule of glz_debug_instance_boxes on a scene description (no device): a mesh's box is the min / max of its vertices here.
  * One box per instance that names an existing mesh, in instance order; returns their count (both outputs NULL: the count alone). */
 int64_t glz_host_instance_boxes(const glz_scene_desc* desc, uint64_t budget, float* lo4, float* hi4);

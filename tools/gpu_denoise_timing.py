@@ -1,7 +1,7 @@
 """Cost of the post stages on the bench atrium at 1920 x 1080: device-event medians over REPS runs of the first-hit pass (trace and
 attribute kernels), the demodulation and each a-trous pass (glz_debug_post_timing), next to one render launch of the same build in the
 same process and to a pass's byte floor (32 bytes read + 16 written per pixel at the 6.3 TB/s the microarchitecture notes give as
-achievable).  The render launch's total is a host clock around 64 launches that end in wait_idle; its k_trace / k_shade split is the
+achievable), and k_despeckle alone at radius 1 and 2 on the same frame (glz_debug_despeckle's device events; same byte floor).  The render launch's total is a host clock around 64 launches that end in wait_idle; its k_trace / k_shade split is the
 renderer's own device-event statistics.  Then the guide modes: the first-hit pass with the attribute kernel (first_hit) against the
 chain of through_specular at caps 1 .. 8 on the atrium, which has no specular material -- every list is empty, so the slope over the cap
 is the cost of two empty launches -- and on tests/golden/mattest.glaze at 1024 x 1024, where half the frame is Glass: the time every
@@ -48,10 +48,31 @@ passes = [med(lambda x, k=k: x["passes"][k]) for k in range(5)]
 for k, p in enumerate(passes):
     print("a-trous pass %d (stride %2d): %.1f us = %.1f x the %.1f us byte floor" % (k, 1 << k, p, p / FLOOR_US, FLOOR_US))
 print("five passes: %.1f us (floor %.1f us); with the demodulation %.1f us" % (sum(passes), 5 * FLOOR_US, sum(passes) + demod))
+# ---- firefly rejection: k_despeckle alone between device events (glz_debug_despeckle), on this renderer's own frame and planes ----
+frame, plane0, plane1 = r.read_result(), r.read_aov(0), r.read_aov(1)
+for radius in (1, 2):
+    for _ in range(4):
+        inst.debug_despeckle(frame, plane0, plane1, want_ms=True, radius=radius)
+    remod = statistics.median(inst.debug_despeckle(frame, plane0, plane1, want_ms=True, radius=radius)[1] for _ in range(REPS)) * 1e3
+    ahead = statistics.median(inst.debug_despeckle(frame, plane0, plane1, want_ms=True, with_filter=True, radius=radius)[1] for _ in range(REPS)) * 1e3
+    # the floor is the kernel's ahead of the filter (i_0 and aov0 read, one frame written); the re-modulating one reads aov1 too: 48 B + 16 B
+    print("despeckle radius %d (%2d neighbours): %.1f us ahead of the filter = %.1f x the %.1f us byte floor, %.2f x a-trous pass 0; "
+          "%.1f us with the re-modulating store (which also reads the albedo plane: floor %.1f us)" % (
+              radius, (2 * radius + 1) ** 2 - 1, ahead, ahead / FLOOR_US, FLOOR_US, ahead / passes[0], remod, FLOOR_US * 64 / 48))
 t = time.time()
 for _ in range(16):
     r.read_denoised()
 print("read_denoised() end to end, frame read back included: %.2f ms" % ((time.time() - t) / 16 * 1e3))
+r.set_despeckle(True)
+t = time.time()
+for _ in range(16):
+    r.read_denoised()
+print("read_denoised() with the rejection enabled: %.2f ms" % ((time.time() - t) / 16 * 1e3))
+t = time.time()
+for _ in range(16):
+    r.read_despeckled()
+print("read_despeckled() end to end, frame read back included: %.2f ms" % ((time.time() - t) / 16 * 1e3))
+r.set_despeckle(False)
 
 
 # ---- guide modes: what follows k_first_hit (slot 'first_hit_attributes' of the timing hook) ----
