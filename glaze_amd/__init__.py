@@ -354,6 +354,13 @@ class RayTraceInstance:
         abi.check(abi.lib().glz_debug_detmath(self._h, code, _ptr(x), None if y is None else _ptr(y), _ptr(out), x.size))
         return out
 
+    def debug_color_to_spec(self, rgb, illuminant=False):
+        """the kernels' from_surface_color (or from_illuminant_color) of an (n, 3) array of colours: (n, 16) float32"""
+        rgb = np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+        out = np.zeros((rgb.shape[0], 16), np.float32)
+        abi.check(abi.lib().glz_debug_color_to_spec(self._h, int(bool(illuminant)), _ptr(rgb), rgb.shape[0], _ptr(out)))
+        return out
+
     def debug_denoise(self, result, aov0, aov1, **params):
         """the device filter on host arrays (upload, kernels, read back): bit for bit glaze_amd.host_denoise"""
         r, a0, a1 = _denoise_frames(result, aov0, aov1)

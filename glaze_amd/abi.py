@@ -220,6 +220,7 @@ PROTOTYPES = {
     "glz_debug_tonemap": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "glz_debug_sample_texture": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint64, _P]),
     "glz_debug_detmath": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_uint64]),
+    "glz_debug_color_to_spec": (C.c_int, [_P, C.c_int, _P, C.c_uint64, _P]),
     "glz_debug_bsdf_value": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64, _P, _P]),
     "glz_debug_bsdf_sample": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P, _P, _P]),
     "glz_debug_light_sample": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint64, C.c_float, _P, _P, _P, _P]),

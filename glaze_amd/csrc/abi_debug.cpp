@@ -393,6 +393,16 @@ int glz_debug_detmath(glz_instance* inst, int fn, const float* x, const float* y
   });
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_debug_color_to_spec(glz_instance* inst, int illuminant, const float* rgb3, uint64_t n, float* out16) {
+  GLZ_GUARD_BEGIN
+  if (!inst || !rgb3 || !out16) return fail(GLZ_E_ARG, "null argument");
+  if (n == 0) return GLZ_OK;
+  if (n > 0x7FFFFFFull) return fail(GLZ_E_ARG, "too many colours");
+  return debug_call(inst->i.get(), "debug color to spectrum", "k_debug_color_to_spec", [&](DebugCall& c) {
+    return launch_debug_color_to_spec(c.st, illuminant != 0, c.in(rgb3, n * 3), (uint32_t)n, c.out(out16, n * 16));
+  });
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_debug_bsdf_value(glz_scene* h, uint32_t material_id, const float* wo3, const float* wi3, const float* uv2, const float* rand1, const float* frame9,
                          uint64_t n, float* value16, float* pdf) {
   GLZ_GUARD_BEGIN

@@ -139,7 +139,12 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
   TexFootprint fp{kNoLod, 0.0f, 0.0f, 1u};
   float cone_w = 0.0f;
   if constexpr (LOD) {
-    cone_w = (fresh ? F.cone_width0 : A.st.cone[lid]) + F.cone_spread * hr.x;
+    // (the argument's value behind an empty asm: the compiler otherwise merges the two reads into one load from a chosen address, an argument's or
+    // the state array's, which is generic and makes the load FLAT)
+    float cone_in = F.cone_width0;
+    asm volatile("" : "+v"(cone_in));
+    if (!fresh) cone_in = A.st.cone[lid];
+    cone_w = cone_in + F.cone_spread * hr.x;
     vec3 e1 = mk3(vb0.x, vb0.y, vb0.z) - mk3(va0.x, va0.y, va0.z), e2 = mk3(vc0.x, vc0.y, vc0.z) - mk3(va0.x, va0.y, va0.z);
     vec3 n = mk3(dn.x, dn.y, dn.z);
     if (!(xf_bits >> 31)) {

@@ -207,6 +207,8 @@ hipError_t launch_debug_any(hipStream_t st, const DeviceScene& scene, const floa
 hipError_t launch_debug_sample_texture(hipStream_t st, const DeviceScene& scene, uint32_t texture, const float* uv2, const float* footprint4,
                                        uint32_t n, float* rgba);
 hipError_t launch_debug_detmath(hipStream_t st, int fn, const float* x, const float* y, uint32_t n, float* out);
+// from_surface_color (illuminant 0) / from_illuminant_color (1) of device/shading.h on n colours, 16 bins out per colour
+hipError_t launch_debug_color_to_spec(hipStream_t st, int illuminant, const float* rgb3, uint32_t n, float* out16);
 // bsdf_eval / bsdf_sample / sample_light + light_emission of device/shading.h, one thread per element (uv2: one pair per call; frame9: s, t, n
 // stored as given, null = x, y, z); all pointers are device memory
 hipError_t launch_debug_bsdf_value(hipStream_t st, const DeviceScene& scene, uint32_t material, const float* wo3, const float* wi3, const float* uv2,

@@ -101,6 +101,14 @@ __global__ void __launch_bounds__(kBlock) k_debug_detmath(int fn, const float* _
   }
   out[i] = r;
 }
+// from_surface_color (illuminant 0) / from_illuminant_color (1) of n colours rgb3[3 i ..]: 16 bins each
+__global__ void __launch_bounds__(kBlock) k_debug_color_to_spec(int illuminant, const float* __restrict__ rgb3, uint32_t n, float* __restrict__ out16) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const vec3 c = mk3(rgb3[3 * t], rgb3[3 * t + 1], rgb3[3 * t + 2]);
+  const Spec s = illuminant ? from_illuminant_color(c) : from_surface_color(c);
+  GLZ_BINS out16[16 * t + i] = s.w[i];
+}
 
 // The shading routines of device/shading.h one call at a time: bsdf_eval, bsdf_sample, and sample_light followed by light_emission.  The
 // surface point is built the way shade_pixel builds it (woW, uv, load_material, fetch_material_textures with the level-0 footprint of a
@@ -180,6 +188,9 @@ hipError_t launch_debug_sample_texture(hipStream_t st, const DeviceScene& scene,
 }
 hipError_t launch_debug_detmath(hipStream_t st, int fn, const float* x, const float* y, uint32_t n, float* out) {
   return launch_per_item(st, k_debug_detmath, n, fn, x, y, n, out);
+}
+hipError_t launch_debug_color_to_spec(hipStream_t st, int illuminant, const float* rgb3, uint32_t n, float* out16) {
+  return launch_per_item(st, k_debug_color_to_spec, n, illuminant, rgb3, n, out16);
 }
 hipError_t launch_debug_bsdf_value(hipStream_t st, const DeviceScene& scene, uint32_t material, const float* wo3, const float* wi3, const float* uv2,
                                    const float* rand1, const float* frame9, uint32_t n, float* value16, float* pdf) {

@@ -34,7 +34,19 @@ constexpr uint32_t kShadeBlock = 256, kShadeWavesPerBlock = kShadeBlock / 64;   
 #ifdef GLZ_SECTION_TIMES
 static __device__ unsigned long long g_shade_sections[16 * 4096];   // per wave (the first 4 096 of the grid): clocks {prologue, key, sort, [shade_pixel's six], epilogue}, [15] = launches
 #endif
-template <bool COUNT, bool LOD>
+// TABLES, SKY: whether the scene tables / the sky's marginal cdf fit their LDS areas (shade_tables_fit, shade_sky_fits: the same over the
+// whole grid, so launch_shade picks the instantiation).  The address space of every table pointer is then fixed when the kernel is
+// compiled -- LDS copies are read with ds_read, tables left in memory with global_load.  Chosen at run time the pointers were generic and
+// every lookup a FLAT access, which goes down the vector-memory path as well and waits on both counters: what the copies are there to avoid.
+__host__ __device__ inline uint32_t shade_table_quads(const DeviceScene& s) {   // [RTMaterial x n_materials | RTLight x n_rt_lights | TexDesc x n_textures] in 16-byte pieces
+  return s.n_materials * (uint32_t)(sizeof(RTMaterial) / 16) + s.n_rt_lights * (uint32_t)(sizeof(RTLight) / 16) + s.n_textures * (uint32_t)(sizeof(TexDesc) / 16);
+}
+__host__ __device__ inline bool shade_tables_fit(const DeviceScene& s) { return shade_table_quads(s) * 16u <= kShadeLdsTableBytes; }
+__host__ __device__ inline bool shade_sky_fits(const DeviceScene& s) { return s.sky_header.marginal_cdf_count > 1u && s.sky_header.marginal_cdf_count <= kSkyLdsFloats; }
+// a pointer into device memory, said to be one: loads through it (and through what is derived from it) are global_load
+template <class T>
+__device__ __forceinline__ const T* in_memory(const T* p) { return (const T*)(const __attribute__((address_space(1))) T*)p; }
+template <bool COUNT, bool LOD, bool TABLES, bool SKY>
 __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const LaunchArgs A) {
 #ifdef GLZ_SECTION_TIMES
   unsigned long long ks[4] = {0, 0, 0, 0}, ks_last = __builtin_amdgcn_s_memtime();
@@ -61,16 +73,13 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   __shared__ uint16_t s_perm[kShadeBlock];
   __shared__ float4 s_hit[kShadeBlock];   // hit records read by the regrouping prologue, handed to the thread that shades the pixel
   const uint32_t n_sky = A.scene.sky_header.marginal_cdf_count;
-  const bool sky_in_lds = A.scene.sky_header.marginal_cdf_count > 1u && n_sky <= kSkyLdsFloats;
   if (threadIdx.x < 256u) s_lut[threadIdx.x] = A.scene.srgb_lut[threadIdx.x];
-  if (sky_in_lds)
+  if (SKY)
     for (uint32_t i = threadIdx.x; i < n_sky; i += kShadeBlock) s_sky[i] = A.scene.sky_marginal[i];
   s_bin[threadIdx.x] = 0;
-  // [RTMaterial x n_materials | RTLight x n_rt_lights | TexDesc x n_textures] in 16-byte pieces
   const uint32_t qm = A.scene.n_materials * (uint32_t)(sizeof(RTMaterial) / 16), ql = A.scene.n_rt_lights * (uint32_t)(sizeof(RTLight) / 16),
                  qt = A.scene.n_textures * (uint32_t)(sizeof(TexDesc) / 16);
-  const bool tables_in_lds = (qm + ql + qt) * 16u <= kShadeLdsTableBytes;   // uniform over the grid
-  if (tables_in_lds) {
+  if (TABLES) {
     const uint4* gm = reinterpret_cast<const uint4*>(A.scene.materials);
     const uint4* gl = reinterpret_cast<const uint4*>(A.scene.lights);
     const uint4* gt = reinterpret_cast<const uint4*>(A.scene.tex_desc);
@@ -82,11 +91,15 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   unsigned long long tex_tally[4] = {0ull, 0ull, 0ull, 0ull};
   S.tex_counter = COUNT ? tex_tally : nullptr;
   S.srgb_lut = s_lut;
-  if (sky_in_lds) S.sky_cdf = s_sky;
-  if (tables_in_lds) {
+  S.sky_cdf = SKY ? s_sky : in_memory(S.sky_cdf);
+  if (TABLES) {
     S.materials = reinterpret_cast<const RTMaterial*>(s_tables);
     S.lights = reinterpret_cast<const RTLight*>(s_tables + qm);
     S.tex_desc = reinterpret_cast<const TexDesc*>(s_tables + qm + ql);
+  } else {
+    S.materials = in_memory(S.materials);
+    S.lights = in_memory(S.lights);
+    S.tex_desc = in_memory(S.tex_desc);
   }
   const FrameData& F = A.frame;
   // Block-local regrouping: the 256 pixels of the block are bucketed by the code path they are going to take -- miss,
@@ -475,11 +488,13 @@ hipError_t launch_trace(hipStream_t st, const LaunchArgs& a, uint32_t blocks, bo
 hipError_t launch_shade(hipStream_t st, const LaunchArgs& a) {
   if (a.map.n_local_pixels == 0) return hipSuccess;
   const dim3 grid((a.map.n_local_pixels + kShadeBlock - 1) / kShadeBlock), block(kShadeBlock);
-  const bool lod = a.frame.lod_mode != 0u;
-  if (a.counters && lod) hipLaunchKernelGGL((k_shade<true, true>), grid, block, 0, st, a);
-  else if (a.counters) hipLaunchKernelGGL((k_shade<true, false>), grid, block, 0, st, a);
-  else if (lod) hipLaunchKernelGGL((k_shade<false, true>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_shade<false, false>), grid, block, 0, st, a);
+  const int which = (a.counters ? 8 : 0) | (a.frame.lod_mode != 0u ? 4 : 0) | (shade_tables_fit(a.scene) ? 2 : 0) | (shade_sky_fits(a.scene) ? 1 : 0);
+  switch (which) {
+#define GLZ_SHADE_CASE(k) case k: hipLaunchKernelGGL((k_shade<((k) & 8) != 0, ((k) & 4) != 0, ((k) & 2) != 0, ((k) & 1) != 0>), grid, block, 0, st, a); break;
+    GLZ_SHADE_CASE(0) GLZ_SHADE_CASE(1) GLZ_SHADE_CASE(2) GLZ_SHADE_CASE(3) GLZ_SHADE_CASE(4) GLZ_SHADE_CASE(5) GLZ_SHADE_CASE(6) GLZ_SHADE_CASE(7)
+    GLZ_SHADE_CASE(8) GLZ_SHADE_CASE(9) GLZ_SHADE_CASE(10) GLZ_SHADE_CASE(11) GLZ_SHADE_CASE(12) GLZ_SHADE_CASE(13) GLZ_SHADE_CASE(14) GLZ_SHADE_CASE(15)
+#undef GLZ_SHADE_CASE
+  }
   return hipGetLastError();
 }
 hipError_t launch_export(hipStream_t st, const TileMap& map, const float4* tiled, float4* frame, bool zero_first) {

@@ -623,6 +623,9 @@ int glz_debug_tonemap(glz_instance*, const float* rgba32f, uint64_t n_pixels, ui
 int glz_debug_sample_texture(glz_scene*, uint32_t texture, const float* uv2, const float* footprint4_or_null, uint64_t n, float* rgba_out);
 /* include/glz_detmath.h on the device: fn 0 sin, 1 cos, 2 acos, 3 atan2(y, x), 4 log2, 5 floor of n values (y only for atan2) */
 int glz_debug_detmath(glz_instance*, int fn, const float* x, const float* y, float* out, uint64_t n);
+/* The kernels' colour-to-spectrum conversion (device/shading.h: from_surface_color, or from_illuminant_color when illuminant != 0)
+ * of n colours rgb3[3i..3i+2]; out16 takes 16 floats per colour */
+int glz_debug_color_to_spec(glz_instance*, int illuminant, const float* rgb3, uint64_t n, float* out16);
 /* The kernels' shading routines one call at a time, n elements each (device/shading.h: bsdf_eval, bsdf_sample, sample_light followed by
  * light_emission).  The surface point is set up as the shading kernel sets it up (material scalars, the material's textures at level 0
  * for the ONE pair uv2 of the call), except the frame: frame9 = s, t, n, stored as given, NULL = (1,0,0), (0,1,0), (0,0,1).  value16 /
