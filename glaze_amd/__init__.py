@@ -24,7 +24,8 @@ from .abi import GlazeError
 from .scene_desc import SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
 
 __all__ = ["parse", "converted_file", "ParsedScene", "RayTraceInstance", "RayTraceScene", "RayTraceRenderer", "Integrator",
-           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle"]
+           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points",
+           "host_project_constants"]
 
 
 def _ptr(a):
@@ -195,6 +196,41 @@ def host_despeckle(result, aov0, aov1, with_filter=False, denoise=None, **params
     d, p = abi.DespeckleParams(**params), abi.DenoiseParams(**(denoise or {}))
     abi.check(abi.lib().glz_host_despeckle(r.shape[1], r.shape[0], _ptr(r), _ptr(a0), _ptr(a1), C.cast(C.byref(d), C.c_void_p), C.cast(C.byref(p), C.c_void_p),
                                            1 if with_filter else 0, _ptr(out)))
+    return out
+
+
+def _reproject_frames(motion, prev_color, prev_aov0, prev_aov1):
+    frames = [np.ascontiguousarray(f, np.float32) for f in (motion, prev_color, prev_aov0, prev_aov1)]
+    if frames[0].ndim != 3 or frames[0].shape[2] != 4 or any(f.shape != frames[0].shape for f in frames):
+        raise ValueError("motion, prev_color, prev_aov0 and prev_aov1 must all be H x W x 4")
+    return frames
+
+
+def host_project_constants(camera, width, height):
+    """glz_host_project_constants: (world2camera, camera2screen with m[5] negated), each 16 float32, column-major -- the two matrices
+    whose inverses glz_host_push_constants hands the kernels, formed in float64 and rounded once."""
+    out = np.zeros(32, np.float32)
+    abi.check(abi.lib().glz_host_project_constants(C.cast(C.byref(camera), C.c_void_p), width, height, _ptr(out)))
+    return out[:16].copy(), out[16:].copy()
+
+
+def host_project_points(camera, width, height, points):
+    """glz_host_project_points: project_point of include/glaze_abi.h on an (n, 3) array of world points, on the host (no device):
+    (n, 3) float32 (fx, fy, z), (0, 0, +inf) where the projection is invalid."""
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    out = np.zeros_like(pts)
+    abi.check(abi.lib().glz_host_project_points(C.cast(C.byref(camera), C.c_void_p), width, height, _ptr(pts), pts.shape[0], _ptr(out)))
+    return out
+
+
+def host_reproject(motion, prev_color, prev_aov0, prev_aov1, **params):
+    """glz_host_reproject: the reprojection rule on the host (no device), the reference of k_reproject.  motion: the plane read_motion
+    returns; prev_color, prev_aov0 = (normal, depth), prev_aov1 = (albedo, instance bits): the previous frames; all H x W x 4 float32.
+    params: the fields of glz_reproject_params (default: the library's).  Returns (reprojected rgb, confidence), H x W x 4."""
+    m, c, a0, a1 = _reproject_frames(motion, prev_color, prev_aov0, prev_aov1)
+    out = np.zeros_like(m)
+    p = abi.ReprojectParams(**params)
+    abi.check(abi.lib().glz_host_reproject(m.shape[1], m.shape[0], _ptr(m), _ptr(c), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out)))
     return out
 
 
@@ -378,6 +414,24 @@ class RayTraceInstance:
         ms = C.c_float(0.0)
         abi.check(abi.lib().glz_debug_despeckle(self._h, r.shape[1], r.shape[0], _ptr(r), _ptr(a0), _ptr(a1), C.cast(C.byref(d), C.c_void_p),
                                                 C.cast(C.byref(p), C.c_void_p), 1 if with_filter else 0, _ptr(out), C.cast(C.byref(ms), C.c_void_p)))
+        return (out, ms.value) if want_ms else out
+
+    def debug_project_points(self, camera, width, height, points):
+        """the device side of glaze_amd.host_project_points on a host array (upload, kernel, read back), bit for bit alike"""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        out = np.zeros_like(pts)
+        abi.check(abi.lib().glz_debug_project_points(self._h, C.cast(C.byref(camera), C.c_void_p), width, height, _ptr(pts), pts.shape[0], _ptr(out)))
+        return out
+
+    def debug_reproject(self, motion, prev_color, prev_aov0, prev_aov1, want_ms=False, **params):
+        """the device side of glaze_amd.host_reproject on host arrays (upload, kernel, read back), bit for bit alike; with want_ms also the
+        device-event time of k_reproject in milliseconds (a pair)"""
+        m, c, a0, a1 = _reproject_frames(motion, prev_color, prev_aov0, prev_aov1)
+        out = np.zeros_like(m)
+        p = abi.ReprojectParams(**params)
+        ms = C.c_float(0.0)
+        abi.check(abi.lib().glz_debug_reproject(self._h, m.shape[1], m.shape[0], _ptr(m), _ptr(c), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out),
+                                                C.cast(C.byref(ms), C.c_void_p)))
         return (out, ms.value) if want_ms else out
 
     def __del__(self):
@@ -746,6 +800,40 @@ class RayTraceRenderer:
         img = np.zeros((self.height, self.width, 4), np.uint8) if want_rgba8 else None
         abi.check(abi.lib().glz_renderer_read_despeckled(self._h, _ptr(out), _ptr(img) if want_rgba8 else None))
         return (out, img) if want_rgba8 else out
+
+    def read_motion(self, prev_camera, prev_transforms=None):
+        """The motion plane (include/glaze_abi.h holds the specification): H x W x 4 float32, per pixel (where the first hit of the centre
+        ray was on screen under prev_camera and prev_transforms, minus the pixel's own centre; its distance from the previous eye; the
+        hit's instance bits).  prev_transforms: (n, 16) float32 as update_transforms takes them, None = the instances did not move.
+        Accumulation goes on."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        t = None if prev_transforms is None else _transform_array(prev_transforms)
+        abi.check(abi.lib().glz_renderer_read_motion(self._h, C.cast(C.byref(prev_camera), C.c_void_p), None if t is None else _ptr(t), 0 if t is None else t.shape[0],
+                                                     _ptr(out)))
+        return out
+
+    def debug_motion_timing(self, prev_camera, prev_transforms=None):
+        """read_motion's pass without the read-back: the device-event time of k_motion alone, in milliseconds"""
+        t = None if prev_transforms is None else _transform_array(prev_transforms)
+        ms = C.c_float(0.0)
+        abi.check(abi.lib().glz_debug_motion_timing(self._h, C.cast(C.byref(prev_camera), C.c_void_p), None if t is None else _ptr(t), 0 if t is None else t.shape[0],
+                                                    C.cast(C.byref(ms), C.c_void_p)))
+        return ms.value
+
+    def reproject(self, prev_camera, prev_color, prev_aov0, prev_aov1, prev_transforms=None, **params):
+        """The previous frame's colour carried to this frame's pixels with disocclusion rejection: H x W x 4 float32 (rgb, confidence
+        0 .. 1).  prev_color: any H x W x 4 image of the previous frame; prev_aov0 / prev_aov1: read_aov(0) / read_aov(1) of the previous
+        state in first-hit mode; params: glz_reproject_params (depth_tolerance).  Accumulation goes on."""
+        shape = (self.height, self.width, 4)
+        c, a0, a1 = (np.ascontiguousarray(f, np.float32) for f in (prev_color, prev_aov0, prev_aov1))
+        if c.shape != shape or a0.shape != shape or a1.shape != shape:
+            raise ValueError("prev_color, prev_aov0 and prev_aov1 must be H x W x 4 of the renderer's size")
+        out = np.zeros(shape, np.float32)
+        t = None if prev_transforms is None else _transform_array(prev_transforms)
+        p = abi.ReprojectParams(**params)
+        abi.check(abi.lib().glz_renderer_reproject(self._h, C.cast(C.byref(prev_camera), C.c_void_p), None if t is None else _ptr(t), 0 if t is None else t.shape[0],
+                                                   _ptr(c), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out)))
+        return out
 
     _GUIDE_MODES = {"first_hit": abi.GUIDE_FIRST_HIT, "through_specular": abi.GUIDE_THROUGH_SPECULAR}
 

@@ -128,6 +128,18 @@ class DespeckleParams(C.Structure):
         super().__init__(**dict(self.DEFAULTS, **kw))
 
 
+class ReprojectParams(C.Structure):
+    """glz_reproject_params; the default is the library's (params NULL)"""
+    _fields_ = [("depth_tolerance", C.c_float)]
+    DEFAULTS = dict(depth_tolerance=1.0 / 64.0)
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError("unknown reproject parameter(s): %s" % ", ".join(sorted(unknown)))
+        super().__init__(**dict(self.DEFAULTS, **kw))
+
+
 AOV_NORMAL_DEPTH, AOV_ALBEDO_INSTANCE = 0, 1
 GUIDE_FIRST_HIT, GUIDE_THROUGH_SPECULAR, GUIDE_MAX_BOUNCES = 0, 1, 8
 DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_POWER_LOG2 = 8, 31
@@ -244,6 +256,14 @@ PROTOTYPES = {
     "glz_renderer_set_despeckle": (C.c_int, [_P, C.c_int, _P]),
     "glz_renderer_despeckle": (C.c_int, [_P, _P]),
     "glz_renderer_read_despeckled": (C.c_int, [_P, _P, _P]),
+    "glz_renderer_read_motion": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    "glz_renderer_reproject": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "glz_host_project_constants": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "glz_host_project_points": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P]),
+    "glz_host_reproject": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "glz_debug_project_points": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P]),
+    "glz_debug_motion_timing": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    "glz_debug_reproject": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     "glz_host_despeckle": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.c_int, _P]),
     "glz_debug_despeckle": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     "glz_host_denoise": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),

@@ -7,6 +7,7 @@
 
 #include "abi_internal.h"
 #include "denoise.h"
+#include "reproject.h"
 #include "mipchain.h"
 #include "rccl_dl.h"
 #include "tile_map.h"
@@ -94,6 +95,13 @@ int glz_debug_camera_rays(glz_renderer* h, float off_x, float off_y, float* orig
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!origins3 || !dirs3) return fail(GLZ_E_ARG, "output is null");
   GLZ_RET(h->r->camera_rays(off_x, off_y, origins3, dirs3, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_motion_timing(glz_renderer* h, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms, float* kernel_ms_out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!prev_camera || !kernel_ms_out || prev_camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "bad argument");
+  *kernel_ms_out = 0.0f;
+  GLZ_RET(h->r->time_motion(prev_camera, prev_transforms, n_prev_transforms, kernel_ms_out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_debug_guide_chain(glz_renderer* h, uint32_t segment, float* origins3, float* dirs3, uint8_t* alive) {
@@ -347,6 +355,88 @@ int glz_debug_despeckle(glz_instance* inst, uint32_t w, uint32_t h, const float*
     float4* ping = c.out<float4>(nullptr, n);
     if (with_filter) return launch_denoise(c.st, w, h, P, r, a0, a1, ping, c.out<float4>(nullptr, n), c.out(reinterpret_cast<float4*>(out), n), nullptr, &D, ev);
     return launch_despeckle(c.st, w, h, D, P.eps_albedo, r, a0, a1, ping, c.out(reinterpret_cast<float4*>(out), n), ev);
+  });
+  if (rc == GLZ_OK && kernel_ms_out) (void)hipEventElapsedTime(kernel_ms_out, ev[0], ev[1]);   // debug_call has synchronised the stream
+  for (auto& v : ev) (void)hipEventDestroy(v);
+  return rc;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+namespace {
+// the checks the four projection / reprojection hooks share; 0 = work to do, 1 = nothing to do, negative = a status
+int project_arguments(const glz_camera* camera, uint32_t w, uint32_t h, const float* points3, uint64_t n, float* out3, post::ProjectConstants& C) {
+  if (!camera || !points3 || !out3 || w == 0 || h == 0 || camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "bad argument");
+  if (n > 0x7FFFFFFFull) return fail(GLZ_E_ARG, "too many points");
+  host::project_constants(*camera, w, h, C.world2camera, C.camera2screen);
+  C.persp = camera->type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
+  return n == 0 ? 1 : 0;
+}
+int reproject_arguments(uint32_t w, uint32_t h, const float* motion, const float* color, const float* aov0, const float* aov1, const glz_reproject_params* p, float* out,
+                        glz_reproject_params& P) {
+  if (!motion || !color || !aov0 || !aov1 || !out) return fail(GLZ_E_ARG, "null argument");
+  P = p ? *p : post::reproject_defaults();
+  if (!post::reproject_params_valid(P)) return fail(GLZ_E_ARG, post::kReprojectParamsMessage);
+  if ((uint64_t)w * h > 0x7FFFFFFFull) return fail(GLZ_E_ARG, "frame too large");
+  return w == 0 || h == 0 ? 1 : 0;
+}
+}  // namespace
+int glz_host_project_constants(const glz_camera* camera, uint32_t width, uint32_t height, float out32[32]) {
+  if (!camera || !out32 || width == 0 || height == 0 || camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "bad argument");
+  host::project_constants(*camera, width, height, out32, out32 + 16);
+  return GLZ_OK;
+}
+int glz_host_project_points(const glz_camera* camera, uint32_t w, uint32_t h, const float* points3, uint64_t n, float* out3) {
+  GLZ_GUARD_BEGIN
+  post::ProjectConstants C;
+  const int st = project_arguments(camera, w, h, points3, n, out3, C);
+  if (st != 0) return st < 0 ? st : GLZ_OK;
+  post::host_project_points(C, w, h, points3, (size_t)n, out3);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_project_points(glz_instance* inst, const glz_camera* camera, uint32_t w, uint32_t h, const float* points3, uint64_t n, float* out3) {
+  GLZ_GUARD_BEGIN
+  if (!inst) return fail(GLZ_E_ARG, "null argument");
+  post::ProjectConstants C;
+  const int st = project_arguments(camera, w, h, points3, n, out3, C);
+  if (st != 0) return st < 0 ? st : GLZ_OK;
+  return debug_call(inst->i.get(), "debug project points", "k_project_points",
+                    [&](DebugCall& c) { return launch_project_points(c.st, C, w, h, c.in(points3, n * 3), (uint32_t)n, c.out(out3, n * 3)); });
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_host_reproject(uint32_t w, uint32_t h, const float* motion, const float* color, const float* aov0, const float* aov1, const glz_reproject_params* p, float* out) {
+  GLZ_GUARD_BEGIN
+  glz_reproject_params P;
+  const int st = reproject_arguments(w, h, motion, color, aov0, aov1, p, out, P);
+  if (st != 0) return st < 0 ? st : GLZ_OK;
+  post::host_reproject(w, h, reinterpret_cast<const float4*>(motion), reinterpret_cast<const float4*>(color), reinterpret_cast<const float4*>(aov0),
+                       reinterpret_cast<const float4*>(aov1), P, reinterpret_cast<float4*>(out));
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_reproject(glz_instance* inst, uint32_t w, uint32_t h, const float* motion, const float* color, const float* aov0, const float* aov1,
+                        const glz_reproject_params* p, float* out, float* kernel_ms_out) {
+  GLZ_GUARD_BEGIN
+  if (!inst) return fail(GLZ_E_ARG, "null argument");
+  glz_reproject_params P;
+  const int status = reproject_arguments(w, h, motion, color, aov0, aov1, p, out, P);
+  if (status < 0) return status;
+  if (kernel_ms_out) *kernel_ms_out = 0.0f;
+  if (status != 0) return GLZ_OK;
+  const size_t n = (size_t)w * h;
+  Error e;
+  if (!hip_ok(hipSetDevice(inst->i->device), "hipSetDevice", e)) return fail(e);
+  hipEvent_t ev[2] = {};
+  for (auto& v : ev)
+    if (!hip_ok(hipEventCreate(&v), "hipEventCreate", e)) {
+      if (ev[0]) (void)hipEventDestroy(ev[0]);
+      return fail(e);
+    }
+  const int rc = debug_call(inst->i.get(), "debug reproject", "k_reproject", [&](DebugCall& c) {
+    const float4* m = c.in(reinterpret_cast<const float4*>(motion), n);
+    const float4* cc = c.in(reinterpret_cast<const float4*>(color), n);
+    const float4* a0 = c.in(reinterpret_cast<const float4*>(aov0), n);
+    const float4* a1 = c.in(reinterpret_cast<const float4*>(aov1), n);
+    return launch_reproject(c.st, w, h, P, m, cc, a0, a1, c.out(reinterpret_cast<float4*>(out), n), ev);
   });
   if (rc == GLZ_OK && kernel_ms_out) (void)hipEventElapsedTime(kernel_ms_out, ev[0], ev[1]);   // debug_call has synchronised the stream
   for (auto& v : ev) (void)hipEventDestroy(v);

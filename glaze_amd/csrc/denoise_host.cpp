@@ -1,10 +1,11 @@
-// glz_host_denoise and glz_host_despeckle: the filter of glz_denoise_params and the firefly rejection of glz_despeckle_params (denoise.h)
+// glz_host_denoise, glz_host_despeckle, glz_host_project_points and glz_host_reproject: the filter of glz_denoise_params and the firefly rejection of glz_despeckle_params (denoise.h)
 // on the host cores, no device -- the reference the device kernels are compared with bit for bit.  Rows are dealt to a few threads; pixels of a pass do not interact, so the result does not depend on them.
 #include <algorithm>
 #include <thread>
 #include <vector>
 
 #include "denoise.h"
+#include "reproject.h"
 
 namespace glz {
 namespace post {
@@ -71,6 +72,23 @@ void host_despeckle(uint32_t w, uint32_t h, const float4* result, const float4* 
     }
   });
   if (with_filter) filter_passes(w, h, pong.data(), ping.data(), pong.data(), aov0, aov1, P, out);
+}
+
+// ---- motion and reprojection (reproject.h) ----
+void host_project_points(const ProjectConstants& C, uint32_t w, uint32_t h, const float* points3, size_t n, float* out3) {
+  for (size_t i = 0; i < n; ++i) {
+    const Projected r = project_point(C, (float)w, (float)h, points3[3 * i], points3[3 * i + 1], points3[3 * i + 2]);
+    out3[3 * i] = r.fx;
+    out3[3 * i + 1] = r.fy;
+    out3[3 * i + 2] = r.z;
+  }
+}
+
+void host_reproject(uint32_t w, uint32_t h, const float4* motion, const float4* color, const float4* aov0, const float4* aov1, const glz_reproject_params& P,
+                    float4* out) {
+  for_rows(h, w, [&](uint32_t y) {
+    for (uint32_t x = 0; x < w; ++x) out[(size_t)y * w + x] = reproject_pixel(motion, color, aov0, aov1, w, h, x, y, P.depth_tolerance);
+  });
 }
 
 }  // namespace post

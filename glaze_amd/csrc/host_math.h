@@ -128,6 +128,14 @@ inline void push_constants(const glz_camera& c, uint32_t width, uint32_t height,
   proj_inv.to_f32(screen2camera);
 }
 
+// The forward twin of push_constants: the two matrices it inverts, formed in f64 and rounded once; nothing is inverted
+inline void project_constants(const glz_camera& c, uint32_t width, uint32_t height, float world2camera[16], float camera2screen[16]) {
+  look_at_rh(c).to_f32(world2camera);
+  Mat4d proj = projection(c, width, height);
+  proj.m[5] *= -1.0;
+  proj.to_f32(camera2screen);
+}
+
 // Light::rotation_matrix (geometry/light.rs:195-199): from_angle_y(yaw) * from_angle_z(pitch) * from_angle_x(roll)
 inline Mat4d sky_rotation(float yaw_deg, float pitch_deg, float roll_deg) {
   const double k = 3.14159265358979323846 / 180.0;

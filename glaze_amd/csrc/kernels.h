@@ -6,6 +6,7 @@
 #include "device/types.h"
 #include "glaze_abi.h"
 #include "device_buffer.h"
+#include "reproject.h"
 
 namespace glz {
 
@@ -198,6 +199,15 @@ hipError_t launch_denoise(hipStream_t st, uint32_t w, uint32_t h, const glz_deno
 // The rejection alone: demodulation into ping, then out = i_0' * max(albedo, eps_albedo) in k_despeckle's store.  No a-trous pass.
 hipError_t launch_despeckle(hipStream_t st, uint32_t w, uint32_t h, const glz_despeckle_params& params, float eps_albedo, const float4* result,
                             const float4* aov0, const float4* aov1, float4* ping, float4* out, hipEvent_t* despeckle_marks = nullptr);
+// Motion and reprojection (reproject.h).  launch_motion: after launch_first_hit on the same stream and with the same `a`, BEFORE the
+// attribute kernel or the guide chain (the chain reuses `hit` / `inst`); prev_o2w: one column-major 4x4 per transform of the scene, 64 B
+// apart, or null = the scene's own; motion: width * height float4.  launch_reproject: all frames are device memory, w * h float4 each, out
+// may not alias an input; marks (may be null): two events around the kernel.
+hipError_t launch_motion(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, const float4* prev_o2w, const post::ProjectConstants& prev,
+                         float4* motion);
+hipError_t launch_reproject(hipStream_t st, uint32_t w, uint32_t h, const glz_reproject_params& params, const float4* motion, const float4* prev_color,
+                            const float4* prev_aov0, const float4* prev_aov1, float4* out, hipEvent_t* marks = nullptr);
+hipError_t launch_project_points(hipStream_t st, const post::ProjectConstants& C, uint32_t w, uint32_t h, const float* points3, uint32_t n, float* out3);
 
 // debug / parity hooks
 hipError_t launch_debug_closest(hipStream_t st, const DeviceScene& scene, const float* origins, const float* dirs, uint32_t n, float tmin,

@@ -7,6 +7,7 @@
 #include "device/trace_wave.h"
 #include "device/trace_wave_tl.h"
 #include "launch_geometry.h"
+#include "reproject.h"
 
 namespace glz {
 using namespace dev;
@@ -365,6 +366,55 @@ __global__ void __launch_bounds__(kBlock) k_despeckle(uint32_t w, uint32_t h, ui
 }
 
 // ---------------------------------------------------------------------------------------------
+// Motion and reprojection (glz_renderer_read_motion, glz_renderer_reproject; post::project_point and post::reproject_pixel hold the
+// arithmetic, shared with the host references).
+//   k_motion     one thread per pixel (row-major), after k_first_hit and before anything reuses the hit buffers: the hit record and the
+//                instance, the three position float4s and the transform word of the shading record (rec[0], rec[2], rec[4], rec[7]: one
+//                128-byte line), 64 B of the previous object -> world matrix (the caller's, 64 B apart, or the scene's own, the first half
+//                of its 128-byte TransformPair), one float4 out.  The object-space point is guide_vertex's `point`; nothing is skipped for
+//                a transform flagged identity: the previous one need not be.
+//   k_reproject  k_atrous's layout.  A wave's taps sit at p + motion with nearly equal motion, so they fall in a few lines; every load is
+//                requested before the first is used.  No LDS, no scratch, no loop with a data-dependent trip count.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) k_motion(const DeviceScene S, uint32_t w, uint32_t h, const float4* __restrict__ hit, const uint32_t* __restrict__ inst,
+                                                   const float4* __restrict__ prev_o2w, const post::ProjectConstants C, float4* __restrict__ out) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= w * h) return;
+  const float4 hr = hit[p];
+  const uint32_t leaf = __float_as_uint(hr.w);
+  if (leaf == 0xFFFFFFFFu) {
+    out[p] = make_float4(0.0f, 0.0f, INFINITY, __uint_as_float(0xFFFFFFFFu));
+    return;
+  }
+  const uint32_t hit_inst = inst[p];
+  const float4* rec = S.shade_tris + 8u * (size_t)leaf;
+  const float4 va0 = rec[0], vb0 = rec[2], vc0 = rec[4], du = rec[7];
+  uint32_t xf = __float_as_uint(du.w) & 0x7FFFFFFFu;
+  if (S.two_level) xf = S.instances[hit_inst].transform_id;
+  const float b0 = 1.0f - hr.y - hr.z, b1 = hr.y, b2 = hr.z;
+  const vec3 point = (mk3(va0.x, va0.y, va0.z) * b0 + mk3(vb0.x, vb0.y, vb0.z) * b1) + mk3(vc0.x, vc0.y, vc0.z) * b2;
+  const float4* xq = prev_o2w ? prev_o2w + 4u * (size_t)xf : reinterpret_cast<const float4*>(&S.transforms[xf]);
+  const float4 m0 = xq[0], m1 = xq[1], m2 = xq[2], m3 = xq[3];
+  const float o2w[16] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w, m3.x, m3.y, m3.z, m3.w};
+  const vec3 prev = xform_point(o2w, point);
+  out[p] = post::motion_value(C, w, h, p % w, p / w, prev.x, prev.y, prev.z, __uint_as_float(hit_inst));
+}
+__global__ void __launch_bounds__(kBlock) k_reproject(uint32_t w, uint32_t h, float tolerance, const float4* __restrict__ motion, const float4* __restrict__ color,
+                                                      const float4* __restrict__ aov0, const float4* __restrict__ aov1, float4* __restrict__ out) {
+  const uint32_t x = blockIdx.x * kPostTileW + (threadIdx.x & 63u), y = blockIdx.y * kPostTileH + (threadIdx.x >> 6);
+  if (x >= w || y >= h) return;
+  out[(size_t)y * w + x] = post::reproject_pixel(motion, color, aov0, aov1, w, h, x, y, tolerance);
+}
+// post::project_point of n points (3 floats each): the parity hook behind glz_debug_project_points
+__global__ void __launch_bounds__(kBlock) k_project_points(const post::ProjectConstants C, float w, float h, const float* __restrict__ points3, uint32_t n,
+                                                           float* __restrict__ out3) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const post::Projected r = post::project_point(C, w, h, points3[3 * (size_t)i], points3[3 * (size_t)i + 1], points3[3 * (size_t)i + 2]);
+  out3[3 * (size_t)i] = r.fx; out3[3 * (size_t)i + 1] = r.fy; out3[3 * (size_t)i + 2] = r.z;
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 // blocks of k_first_hit's persistent grid (the render tracers' residency rule)
@@ -451,6 +501,23 @@ hipError_t launch_despeckle(hipStream_t st, uint32_t w, uint32_t h, const glz_de
   hipLaunchKernelGGL(k_demodulate, grid_for(n), dim3(kBlock), 0, st, n, result, aov1, eps_albedo, ping);
   launch_despeckle_kernel<true>(st, w, h, D, eps_albedo, ping, aov0, aov1, out, despeckle_marks);
   return hipGetLastError();
+}
+hipError_t launch_motion(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, const float4* prev_o2w, const post::ProjectConstants& prev,
+                         float4* motion) {
+  const uint32_t n = a.map.width * a.map.height;
+  return launch_per_item(st, k_motion, n, a.scene, a.map.width, a.map.height, hit, inst, prev_o2w, prev, motion);
+}
+hipError_t launch_reproject(hipStream_t st, uint32_t w, uint32_t h, const glz_reproject_params& P, const float4* motion, const float4* prev_color,
+                            const float4* prev_aov0, const float4* prev_aov1, float4* out, hipEvent_t* marks) {
+  if (w == 0 || h == 0) return hipSuccess;
+  if (!post::reproject_params_valid(P) || (uint64_t)w * h > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  if (marks) (void)hipEventRecord(marks[0], st);
+  hipLaunchKernelGGL(k_reproject, post_tile_grid(w, h), dim3(kBlock), 0, st, w, h, P.depth_tolerance, motion, prev_color, prev_aov0, prev_aov1, out);
+  if (marks) (void)hipEventRecord(marks[1], st);
+  return hipGetLastError();
+}
+hipError_t launch_project_points(hipStream_t st, const post::ProjectConstants& C, uint32_t w, uint32_t h, const float* points3, uint32_t n, float* out3) {
+  return launch_per_item(st, k_project_points, n, C, (float)w, (float)h, points3, n, out3);
 }
 
 }  // namespace glz

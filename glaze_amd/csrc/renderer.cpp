@@ -1086,6 +1086,12 @@ bool Renderer::first_hit_pass(Error& err, hipEvent_t* marks, uint32_t last_list)
   if (marks) (void)hipEventRecord(marks[0], st);
   if (!hip_ok(launch_first_hit(st, a, blocks, fh_hit_.ptr, fh_inst_.ptr), "k_first_hit", err)) return false;
   if (marks) (void)hipEventRecord(marks[1], st);
+  if (motion_request_) {
+    const MotionRequest& m = *motion_request_;
+    if (m.marks) (void)hipEventRecord(m.marks[0], st);
+    if (!hip_ok(launch_motion(st, a, fh_hit_.ptr, fh_inst_.ptr, m.prev_o2w, m.prev, m.out), "k_motion", err)) return false;
+    if (m.marks) (void)hipEventRecord(m.marks[1], st);
+  }
   if (chain) {
     guide_blocks_ = guide_grid_blocks(a.map.n_local_pixels, blocks);
     if (!hip_ok(launch_guide_chain(st, a, guide_blocks_, guide_bounces_, last_list, fh_hit_.ptr, fh_inst_.ptr, guide_lists(), aov0_.ptr, aov1_.ptr), "k_guide_continue", err))
@@ -1263,6 +1269,79 @@ bool Renderer::read_despeckled(float* rgba32f, uint8_t* rgba8, Error& err) {
   if (rgba32f && !frame_to_host(dn_out_.ptr, rgba32f, "read despeckled", err)) return false;
   if (rgba8 && !rgba8_to_host(dn_out_.ptr, rgba8, "read despeckled", "read despeckled", err)) return false;
   return hip_ok(hipStreamSynchronize(st), "read despeckled", err);
+}
+
+// the checks of read_motion and reproject, the upload of the caller's matrices, then the first-hit pass with k_motion in it
+bool Renderer::motion_pass(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, DeviceBuffer<float4>& prev_o2w,
+                           DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks) {
+  if (!prev_camera) {
+    err.code = GLZ_E_ARG;
+    err.msg = "motion: the previous camera is null";
+    return false;
+  }
+  if (prev_transforms && n_prev != scene_->data.transforms.size()) {
+    err.code = GLZ_E_ARG;
+    err.msg = "motion: the previous transforms must be as many as the scene's (instances index transforms)";
+    return false;
+  }
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
+  hipStream_t st = inst_->stream;
+  MotionRequest req;
+  host::project_constants(*prev_camera, w_, h_, req.prev.world2camera, req.prev.camera2screen);
+  req.prev.persp = prev_camera->type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
+  req.prev_o2w = nullptr;
+  if (prev_transforms && n_prev > 0) {
+    static_assert(sizeof(glz_transform) == 4 * sizeof(float4), "one previous matrix is four float4");
+    if (!hip_ok(prev_o2w.upload(reinterpret_cast<const float4*>(prev_transforms), 4 * (size_t)n_prev, st), "upload previous transforms", err)) return false;
+    req.prev_o2w = prev_o2w.ptr;
+  }
+  if (!hip_ok(motion.alloc((size_t)w_ * h_), "alloc motion plane", err)) return false;
+  req.out = motion.ptr;
+  req.marks = marks;
+  motion_request_ = &req;
+  const bool ok = first_hit_pass(err);
+  motion_request_ = nullptr;
+  return ok;
+}
+
+bool Renderer::read_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* out, Error& err) {
+  DeviceBuffer<float4> prev_o2w, motion;
+  if (!motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err)) return false;
+  return frame_to_host(motion.ptr, out, "read motion", err);
+}
+
+bool Renderer::time_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* kernel_ms, Error& err) {
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
+  hipEvent_t ev[2] = {};
+  bool ok = true;
+  for (auto& e : ev) ok = ok && hip_ok(hipEventCreate(&e), "hipEventCreate", err);
+  DeviceBuffer<float4> prev_o2w, motion;
+  ok = ok && motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err, ev);
+  ok = ok && hip_ok(hipStreamSynchronize(inst_->stream), "time_motion", err);
+  if (ok) (void)hipEventElapsedTime(kernel_ms, ev[0], ev[1]);
+  for (auto& e : ev)
+    if (e) (void)hipEventDestroy(e);
+  return ok;
+}
+
+bool Renderer::reproject(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, const float* prev_color, const float* prev_aov0,
+                         const float* prev_aov1, const glz_reproject_params* params, float* out, Error& err) {
+  const glz_reproject_params P = params ? *params : post::reproject_defaults();
+  if (!post::reproject_params_valid(P)) {
+    err.code = GLZ_E_ARG;
+    err.msg = post::kReprojectParamsMessage;
+    return false;
+  }
+  DeviceBuffer<float4> prev_o2w, motion, color, plane0, plane1, result;
+  if (!motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err)) return false;
+  const size_t n = (size_t)w_ * h_;
+  hipStream_t st = inst_->stream;
+  if (!hip_ok(color.upload(reinterpret_cast<const float4*>(prev_color), n, st), "upload previous frame", err) ||
+      !hip_ok(plane0.upload(reinterpret_cast<const float4*>(prev_aov0), n, st), "upload previous frame", err) ||
+      !hip_ok(plane1.upload(reinterpret_cast<const float4*>(prev_aov1), n, st), "upload previous frame", err) || !hip_ok(result.alloc(n), "alloc reprojected frame", err))
+    return false;
+  if (!hip_ok(launch_reproject(st, w_, h_, P, motion.ptr, color.ptr, plane0.ptr, plane1.ptr, result.ptr), "k_reproject", err)) return false;
+  return frame_to_host(result.ptr, out, "reproject", err);
 }
 
 bool Renderer::set_texture_lod(int mode, Error& err) {

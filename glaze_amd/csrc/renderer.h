@@ -41,6 +41,12 @@ class Renderer {
   bool set_despeckle(bool enabled, const glz_despeckle_params* p, Error& err);
   int despeckle(glz_despeckle_params* out) const;                      // the enabled flag
   bool read_despeckled(float* rgba32f, uint8_t* rgba8, Error& err);    // gather + first-hit pass + demodulation + rejection; no filter pass
+  // motion vectors and history reprojection (glz_reproject_params; reproject.h): the first-hit trace and k_motion against the caller's
+  // previous camera and transforms (null = the scene's own), then, for reproject, k_reproject on the three uploaded previous frames
+  bool read_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* out, Error& err);
+  bool time_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* kernel_ms, Error& err);   // k_motion alone, device events
+  bool reproject(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, const float* prev_color, const float* prev_aov0,
+                 const float* prev_aov1, const glz_reproject_params* params, float* out, Error& err);
   bool camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err);   // camera_ray() of every pixel, on the device
   // which surface the feature buffers describe (GLZ_GUIDE_*, glaze_abi.h holds the specification); accumulation goes on
   bool set_guide_mode(int mode, uint32_t max_bounces, Error& err);
@@ -204,6 +210,16 @@ class Renderer {
   // In GLZ_GUIDE_THROUGH_SPECULAR the chain's kernels take the attribute kernel's place (launch_guide_chain; last_list as there).
   bool first_hit_pass(Error& err, hipEvent_t* marks = nullptr, uint32_t last_list = GLZ_GUIDE_MAX_BOUNCES + 1);   // marks: 3 events around the trace and what follows it
   void post_args(LaunchArgs& a) const;
+  // what first_hit_pass launches k_motion with, between the trace and whatever reuses the hit buffers
+  struct MotionRequest {
+    post::ProjectConstants prev;
+    const float4* prev_o2w;   // device, or null = the scene's own
+    float4* out;              // device
+    hipEvent_t* marks;        // null, or two events recorded around k_motion
+  };
+  const MotionRequest* motion_request_ = nullptr;   // set by motion_pass() around its first_hit_pass()
+  bool motion_pass(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, DeviceBuffer<float4>& prev_o2w, DeviceBuffer<float4>& motion,
+                   Error& err, hipEvent_t* marks = nullptr);
   void release_post();
   bool ensure_denoise_frames(Error& err);
   DeviceBuffer<float4> fh_hit_, aov0_, aov1_, dn_ping_, dn_pong_, dn_out_;

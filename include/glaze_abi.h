@@ -495,6 +495,62 @@ int glz_renderer_despeckle(glz_renderer*, glz_despeckle_params* out);   /* retur
  * glz_renderer_set_partition(world > 1). */
 int glz_renderer_read_despeckled(glz_renderer*, float* rgba32f_out, uint8_t* rgba8_out);
 
+/* Motion vectors and history reprojection: the geometric half of a temporal filter.  Where was the surface point a pixel shows on screen in
+ * the previous frame, and does the previous pixel there still show the same surface?  Stateless: the caller keeps the previous camera, the
+ * previous transforms and the previous frames; nothing here blends, keeps a history, restarts accumulation or touches the path state or
+ * the accumulators.  Everything runs on the renderer's own device over the whole frame, as glz_renderer_read_aov does (so it also works
+ * under glz_renderer_set_partition and glz_renderer_set_devices).  THE SPECIFICATION (every operation in binary32, no contraction, in this
+ * order; finite as the filter defines it; sqrt correctly rounded; floor exact):
+ *   PROJECTION CONSTANTS (glz_host_project_constants, the forward twin of glz_host_push_constants): out32[0..16) = world2camera =
+ *     look_at_rh(camera), out32[16..32) = camera2screen = projection(camera, w, h) with m[5] negated -- the two matrices whose inverses
+ *     the push constants are -- column-major, formed in binary64 and rounded to binary32 once.  Nothing is inverted.
+ *   project_point(M = world2camera, S = camera2screen, camera type, w, h, P) -> (fx, fy, z):
+ *     Pc.r = ((M[r]*P.x + M[4+r]*P.y) + M[8+r]*P.z) + M[12+r]                                             r = 0, 1, 2
+ *     perspective:  d = -Pc.z;  ndc.r = (((S[r]*Pc.x + S[4+r]*Pc.y) + S[8+r]*Pc.z) + S[12+r]) / d  (r = 0, 1);
+ *                   z = sqrt((Pc.x*Pc.x + Pc.y*Pc.y) + Pc.z*Pc.z)
+ *     orthographic: ndc = (Pc.x, Pc.y);  z = -Pc.z;  d counts as positive     (camera_ray's orthographic branch: the ray starts at
+ *                   camera2world * (ndc.x, ndc.y, 0, 1) and runs along the view axis -- the projection's scale is not applied, Q18 kept)
+ *     fx = ((ndc.x + 1) * 0.5) * w;   fy = ((ndc.y + 1) * 0.5) * h
+ *     (fx, fy) is the continuous pixel position (pixel centres at + 1/2, row-major, y down), the inverse of camera_ray's
+ *     ndc = -1 + 2 (pixel / size); z is the distance at which camera_ray of that camera through (fx, fy) reaches P.
+ *     INVALID -- the result is (0, 0, +inf) -- unless d > 0, finite(z), z > 0, finite(fx) and finite(fy).  (An intermediate beyond
+ *     FLT_MAX is an infinity in binary32 and makes the point invalid: coordinates of 1e30 overflow Pc.x*Pc.x.)
+ *   THE MOTION PLANE (glz_renderer_read_motion): one row-major float4 per pixel p = (px, py), describing the first hit of the centre ray
+ *     (segment 0 of the first-hit pass, whatever glz_renderer_set_guide_mode says):
+ *     b0 = 1 - u - v;  P_obj = (v0*b0 + v1*u) + v2*v per component, from the hit triangle's object-space positions
+ *     P' = prev_o2w[transform id] applied to P_obj: per row r, m[r]*x + m[4+r]*y + m[8+r]*z + m[12+r] summed left to right.  The transform
+ *       id is the hit instance's.  prev_transforms == NULL means "the instances did not move": the scene's own object -> world matrices.
+ *       Nothing is skipped for an identity transform.
+ *     (fx, fy, z') = project_point(previous camera, P')
+ *     plane = (fx - (float(px) + 0.5), fy - (float(py) + 0.5), z', the first hit's instance bits)
+ *     a miss: (0, 0, +inf, 0xFFFFFFFF);   an invalid projection: (0, 0, +inf, instance bits)
+ *   THE REPROJECTION RULE (glz_renderer_reproject, glz_host_reproject), per pixel p, from the motion plane m and three PREVIOUS frames:
+ *     the colour c (any RGBA32F image), aov0 = (normal, depth) and aov1 = (albedo, instance bits), both from GLZ_GUIDE_FIRST_HIT:
+ *     z' = m.z not finite: out = (0, 0, 0, 0).  Otherwise
+ *     q = p + (m.x, m.y) -- the pixel centre moved by the motion, in pixel-corner coordinates ((px + 1/2) + m.x - 1/2) -- taken apart exactly:
+ *     x0 = px + floor(m.x), y0 = py + floor(m.y) (integers), a = (m.x - floor(m.x), m.y - floor(m.y)) (exact in binary32): no rounding
+ *     of q's hundreds of pixels reaches the weights
+ *     four taps t = (x0 + dx, y0 + dy), dy = 0, 1 outer, dx = 0, 1 inner, with W = (dx ? a.x : 1 - a.x) * (dy ? a.y : 1 - a.y)
+ *     a tap is ACCEPTED iff it lies inside the frame (a motion that is not finite has no tap inside), the bits of aov1(t).w equal the bits
+ *     of m.w, the three colour channels of c(t) are finite, and |zh - z'| <= depth_tolerance * z' (false when a side is NaN), where
+ *       zh = z(t) + (gx * (a.x - float(dx)) + gy * (a.y - float(dy)))                    (a - d = q - t)
+ *     is the tap's depth carried to q by the filter's own first-order model: (gx, gy) = g(t) of the filter's specification above, taken
+ *     on the previous depth plane at the tap.
+ *     sw = sum of W, sum.c = sum of W * c(t).c over the accepted taps, in tap order, each starting from 0
+ *     out = (sum.x / sw, sum.y / sw, sum.z / sw, sw) if sw > 0, else (0, 0, 0, 0).   out.w is a confidence in 0 .. 1.
+ *     There is no normal test: carrying a normal into the previous frame needs the previous transform's inverse.
+ * Default (params NULL): depth_tolerance 1/64.  GLZ_E_ARG, before anything is launched and with nothing changed: a null renderer, camera,
+ * frame or output; a non-NULL prev_transforms whose count is not the scene's (with NULL the count is ignored); a depth_tolerance that is
+ * not finite and positive. */
+typedef struct glz_reproject_params {
+  float depth_tolerance;
+} glz_reproject_params;
+/* All frames are row-major W*H*4 floats in host memory. */
+int glz_renderer_read_motion(glz_renderer*, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms, float* out);
+/* The first-hit trace, the motion plane, then the rule on the three uploaded frames. */
+int glz_renderer_reproject(glz_renderer*, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms,
+                           const float* prev_color, const float* prev_aov0, const float* prev_aov1, const glz_reproject_params* params_or_null, float* out);
+
 /* Multi-GPU (one process per GPU): this renderer owns the 64x64-pixel tiles t with
  * t % world == rank; other pixels stay zero.  The exchange of the HDR accumulator itself is done
  * by the caller (RCCL through torch.distributed or rccl directly) on the device buffers below. */
@@ -616,6 +672,13 @@ float glz_debug_box_kernel_ms(glz_scene*);
  * byte count (0 past the last level), writes up to cap bytes and the level's dimensions */
 int64_t glz_debug_read_texture_level(glz_scene*, uint32_t texture, uint32_t level, uint8_t* out, int64_t cap, uint32_t* width, uint32_t* height);
 /* k_tonemap (the out32 -> RGBA8 sRGB blit, raytracer.rs:576-584) on n host pixels of RGBA32F: upload, kernel, read back */
+/* the two references above on the device, on arrays the caller supplies: the parity hooks (kernel_ms_out, may be NULL: k_reproject alone
+ * between device events) */
+int glz_debug_project_points(glz_instance*, const glz_camera* camera, uint32_t width, uint32_t height, const float* points3, uint64_t n, float* out3);
+int glz_debug_reproject(glz_instance*, uint32_t w, uint32_t h, const float* motion, const float* prev_color, const float* prev_aov0, const float* prev_aov1,
+                        const glz_reproject_params* params_or_null, float* out, float* kernel_ms_out);
+/* glz_renderer_read_motion's pass without the read-back: the device-event time of k_motion alone, in milliseconds */
+int glz_debug_motion_timing(glz_renderer*, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms, float* kernel_ms_out);
 int glz_debug_tonemap(glz_instance*, const float* rgba32f, uint64_t n_pixels, uint8_t* rgba8_out);
 /* The kernels' texture sampler on n coordinates uv2[2i], uv2[2i+1] of a scene texture, RGBA out: level 0 (texture2d) when
  * footprint4 is NULL, else the level of detail of footprint4[4i..4i+3] = (lod_base, du, dv, taps in 1..16) (texture2d_lod, after
@@ -697,6 +760,12 @@ int glz_host_despeckle(uint32_t w, uint32_t h, const float* result, const float*
                        const glz_despeckle_params*, const glz_denoise_params*, int with_filter, float* out);
 /* the host rule of glz_debug_instance_boxes on a scene description (no device): a mesh's box is the min / max of its vertices here.
  * One box per instance that names an existing mesh, in instance order; returns their count (both outputs NULL: the count alone). */
+/* The references of the motion / reprojection specification above, no device.  project_constants: out32 as specified.  project_points:
+ * n points (3 floats each) -> (fx, fy, z) each.  reproject: the rule on host arrays (params NULL = defaults). */
+int glz_host_project_constants(const glz_camera* camera, uint32_t width, uint32_t height, float out32[32]);
+int glz_host_project_points(const glz_camera* camera, uint32_t width, uint32_t height, const float* points3, uint64_t n, float* out3);
+int glz_host_reproject(uint32_t w, uint32_t h, const float* motion, const float* prev_color, const float* prev_aov0, const float* prev_aov1,
+                       const glz_reproject_params* params_or_null, float* out);
 int64_t glz_host_instance_boxes(const glz_scene_desc* desc, uint64_t budget, float* lo4, float* hi4);
 
 #ifdef __cplusplus

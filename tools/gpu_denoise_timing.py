@@ -5,7 +5,8 @@ achievable), and k_despeckle alone at radius 1 and 2 on the same frame (glz_debu
 renderer's own device-event statistics.  Then the guide modes: the first-hit pass with the attribute kernel (first_hit) against the
 chain of through_specular at caps 1 .. 8 on the atrium, which has no specular material -- every list is empty, so the slope over the cap
 is the cost of two empty launches -- and on tests/golden/mattest.glaze at 1024 x 1024, where half the frame is Glass: the time every
-bounce adds next to the number of rays alive in it.  Run from the repository root on the GPU; writes nothing but its output."""
+bounce adds next to the number of rays alive in it.  Last, k_motion and k_reproject alone (glz_debug_motion_timing, glz_debug_reproject's
+device events) for a camera that moved about 0.6 m and turned, next to their byte floors.  Run from the repository root on the GPU; writes nothing but its output."""
 import os
 import statistics
 import sys
@@ -112,3 +113,42 @@ m = glaze_amd.RayTraceRenderer.new(inst, glaze_amd.RayTraceScene.new(inst, glaze
 m.step(2)
 m.wait_idle()
 guide_rows("mattest 1024 x 1024", m, range(1, 5), True)
+
+
+# ---- motion and reprojection: k_motion and k_reproject alone between device events, the atrium's camera moved and turned ----
+from glaze_amd.scene_desc import _clone
+
+desc = atrium_scene()
+prev_cam = _clone(desc.camera)
+prev_cam.position[:] = [a + b for a, b in zip(desc.camera.position[:], (0.45, 0.1, -0.4))]
+prev_cam.target[:] = [a + b for a, b in zip(desc.camera.target[:], (0.6, -0.2, 0.5))]
+motion = r.read_motion(prev_cam)
+hits = float((motion[..., 2] < float("inf")).mean())
+for _ in range(8):
+    r.debug_motion_timing(prev_cam)
+k_motion = statistics.median(r.debug_motion_timing(prev_cam) for _ in range(REPS)) * 1e3
+# per pixel: hit record 16 B + instance 4 B read, 16 B written.  The four float4 of a hit's 128-byte shading record are shared by every pixel
+# that shows the triangle (the atrium's walls are a few hundred pixels per triangle): at most one line per triangle of the scene moves;
+# the 64 B of a transform are shared by a wave and come from cache
+n_tris = r.scene.info().n_as_triangles
+lo, hi = W * H * 36 / 6.3e12 * 1e6, (W * H * 36 + n_tris * 128) / 6.3e12 * 1e6
+print("k_motion: %.1f us (%.1f %% of the pixels hit) = %.1f x the %.1f us floor of its per-pixel streams (36 B), %.1f x the %.1f us with every one of the "
+      "scene's %d shading records read once" % (k_motion, 100 * hits, k_motion / lo, lo, k_motion / hi, hi, n_tris))
+r.update_camera(prev_cam)
+prev0, prev1 = r.read_aov(0), r.read_aov(1)
+r.update_camera(desc.camera)
+for _ in range(4):
+    inst.debug_reproject(motion, frame, prev0, prev1, want_ms=True)
+out, _ = inst.debug_reproject(motion, frame, prev0, prev1, want_ms=True)
+k_reproject = statistics.median(inst.debug_reproject(motion, frame, prev0, prev1, want_ms=True)[1] for _ in range(REPS)) * 1e3
+floor = W * H * 80 / 6.3e12 * 1e6   # four planes read once each (a wave's taps share their lines), one written
+print("k_reproject: %.1f us = %.1f x the %.1f us byte floor (80 B per pixel), %.2f x a-trous pass 0; %.1f %% of the hit pixels receive history" % (
+    k_reproject, k_reproject / floor, floor, k_reproject / passes[0], 100 * float((out[..., 3] > 0).mean()) / max(hits, 1e-9)))
+t = time.time()
+for _ in range(16):
+    r.read_motion(prev_cam)
+print("read_motion() end to end, frame read back included: %.2f ms" % ((time.time() - t) / 16 * 1e3))
+t = time.time()
+for _ in range(16):
+    r.reproject(prev_cam, frame, prev0, prev1)
+print("reproject() end to end, three frames uploaded and one read back: %.2f ms" % ((time.time() - t) / 16 * 1e3))
