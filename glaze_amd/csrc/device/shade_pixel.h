@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "device/hit_vertex.h"
 #include "device/math.h"
 #include "device/path_state.h"
 #include "device/shading.h"
@@ -113,20 +114,8 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
     return F.direct_only ? 0 : 1;   // RESET_PATH
   }
   // ---- closest-hit shader (raytrace_hit.rchit:30-71), inputs from the 128-byte per-leaf shading record ----
-  const float4* rec = S.shade_tris + 8u * (size_t)leaf;
-  const float4 va0 = rec[0], va1 = rec[1], vb0 = rec[2], vb1 = rec[3], vc0 = rec[4], vc1 = rec[5], dn = rec[6], du = rec[7];
-  uint32_t material_id = __float_as_uint(dn.w), xf_bits = __float_as_uint(du.w);
-  if (S.two_level) {   // the record is per OBJECT triangle: material and transform are the instance's
-    const RTInstance in = S.instances[A.st.hit_inst[lid]];
-    material_id = in.material_id;
-    xf_bits = in.transform_id | (S.xf_identity[in.transform_id] ? 0x80000000u : 0u);
-  }
-  const float b0 = 1.0f - hr.y - hr.z, b1 = hr.y, b2 = hr.z;
-  vec3 point = (mk3(va0.x, va0.y, va0.z) * b0 + mk3(vb0.x, vb0.y, vb0.z) * b1) + mk3(vc0.x, vc0.y, vc0.z) * b2;
-  const vec2 uv = vec2{(va1.z * b0 + vb1.z * b1) + vc1.z * b2, (va1.w * b0 + vb1.w * b1) + vc1.w * b2};
-  vec3 ng = mk3(dn.x, dn.y, dn.z), dpdu = mk3(du.x, du.y, du.z);   // dpdv is transformed by the reference but never read afterwards
-  vec3 ns = (mk3(va0.w, va1.x, va1.y) * b0 + mk3(vb0.w, vb1.x, vb1.y) * b1) + mk3(vc0.w, vc1.x, vc1.y) * b2;
-  const MatScalars mat = load_material(&S.materials[material_id]);
+  HitVertex hv = load_hit_vertex(S, hr, [&]() { return A.st.hit_inst[lid]; });
+  const MatScalars mat = hv.mat;
   GLZ_SHADE_STAMP(0);   // hit record -> shading record -> material scalars
   // ---- texture level of detail by ray cones (build-defined, off by default: the reference's stages sample level 0) ----
   // The cone of a camera path starts cone_width0 wide and widens by cone_spread per unit of distance along the whole path;
@@ -139,6 +128,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
   TexFootprint fp{kNoLod, 0.0f, 0.0f, 1u};
   float cone_w = 0.0f;
   if constexpr (LOD) {
+    const auto& [va0, va1, vb0, vb1, vc0, vc1, dn, du_rec] = hv.rec;   // the triangle in object space
     // (the argument's value behind an empty asm: the compiler otherwise merges the two reads into one load from a chosen address, an argument's or
     // the state array's, which is generic and makes the load FLAT)
     float cone_in = F.cone_width0;
@@ -147,8 +137,8 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
     cone_w = cone_in + F.cone_spread * hr.x;
     vec3 e1 = mk3(vb0.x, vb0.y, vb0.z) - mk3(va0.x, va0.y, va0.z), e2 = mk3(vc0.x, vc0.y, vc0.z) - mk3(va0.x, va0.y, va0.z);
     vec3 n = mk3(dn.x, dn.y, dn.z);
-    if (!(xf_bits >> 31)) {
-      const TransformPair* xf = &S.transforms[xf_bits & 0x7FFFFFFFu];
+    if (!(hv.xf_bits >> 31)) {
+      const TransformPair* xf = &S.transforms[hv.xf_bits & 0x7FFFFFFFu];
       e1 = xform_dir(xf->o2w, e1);
       e2 = xform_dir(xf->o2w, e2);
       n = xform_tdir(xf->w2o, n);
@@ -184,36 +174,11 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
       }
     }
   }
-  if (mat.normal != 0) {
-    const vec4 tx = texture2d_lod(S, mat.normal, uv.x, uv.y, fp);
-    Frame old;
-    old.s = normalize3(dpdu);
-    old.n = ns;
-    old.t = normalize3(cross3(old.n, old.s));
-    ns = normalize3(to_world(mk3(tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f), old));
-    ns = ns * gl_sign(dot3(ng, ns));
-  }
-  if (!(xf_bits >> 31)) {
-    // object -> world.  Skipped for an exact identity transform: m*x with m = I reproduces x bit for bit
-    // (x*1 + y*0 + z*0 + 0 for finite coordinates), so the result is unchanged and ~25 scalar loads are saved.
-    const float4* xq = reinterpret_cast<const float4*>(&S.transforms[xf_bits & 0x7FFFFFFFu]);
-    const float4 m0 = xq[0], m1 = xq[1], m2 = xq[2], m3 = xq[3], w0 = xq[4], w1 = xq[5], w2 = xq[6];
-    const float o2w[16] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w, m3.x, m3.y, m3.z, m3.w};
-    const float w2o[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
-    point = xform_point(o2w, point);
-    dpdu = xform_point(o2w, dpdu);   // transformed as a point, w = 1 (Q8)
-    ng = xform_tdir(w2o, ng);
-    ns = xform_tdir(w2o, ns);
-  }
-  (void)ng;
+  finish_hit_vertex<true>(S, hv, fp);
+  const vec3 point = hv.point, ns = hv.ns;
   // ---- raygen continues (path_trace.rgen:180-237) ----
   uint32_t rng = pcg(__float_as_uint((float)F.seed) ^ pcg(__float_as_uint((float)px.x) ^ pcg(__float_as_uint((float)px.y))));   // :143, Q11
-  SurfacePoint P;
-  P.woW = -direction;
-  P.uv = uv;
-  P.frame = make_frame(dpdu, ns);
-  P.mat = mat;
-  fetch_material_textures(S, P, fp);
+  const SurfacePoint P = hit_surface_point(S, hv, direction, fp);
   GLZ_SHADE_STAMP(1);   // normal map, transform, frame, the material's textures
   float spec_flag;
   float imp_lum = 0.0f;      // luminance of the importance, taken when the light-sampling block reads it: the roulette needs nothing else of it

@@ -2,6 +2,7 @@
 // primary ray through every pixel centre) and the edge-avoiding a-trous filter that uses them as guides (denoise.h holds the filter's
 // arithmetic, shared with the host reference).  Nothing here touches the path state or the accumulators of the render kernels.
 #include "denoise.h"
+#include "device/hit_vertex.h"
 #include "device/path_state.h"
 #include "device/shading.h"
 #include "device/trace_wave.h"
@@ -29,13 +30,16 @@ struct CentreSource {
     return true;
   }
 };
-struct FirstHitSink {
+// What the post tracers store per ray: hit = (t (inf = miss), u, v, leaf bits), inst = the RTInstance of the hit (0xFFFFFFFF = miss).
+// BY_PIXEL: at the ray's pixel, row-major (k_first_hit); otherwise at the ray's slot in its list (k_guide_trace).
+template <bool BY_PIXEL>
+struct HitSink {
   const LaunchArgs& A;
-  float4* hit;       // row-major: t (inf = miss), u, v, leaf (bits)
-  uint32_t* inst;    // row-major: RTInstance of the hit, 0xFFFFFFFF = miss
+  float4* hit;
+  uint32_t* inst;
   __device__ __forceinline__ void store(uint32_t i, const HitRecord& h) {
-    const PixelId px = pixel_of(A.map, i);   // only rays CentreSource handed out arrive here: inside the image
-    const size_t p = (size_t)px.y * A.map.width + px.x;
+    const PixelId px = pixel_of(A.map, i);   // (BY_PIXEL) only rays CentreSource handed out arrive here: inside the image
+    const size_t p = BY_PIXEL ? (size_t)px.y * A.map.width + px.x : i;
     const bool is_hit = h.leaf != 0xFFFFFFFFu;
     hit[p] = make_float4(is_hit ? h.t : INFINITY, h.u, h.v, __uint_as_float(h.leaf));
     inst[p] = is_hit ? (A.scene.two_level ? h.inst : A.scene.bvh_tris[h.leaf].instance) : 0xFFFFFFFFu;
@@ -49,17 +53,17 @@ __global__ void __launch_bounds__(kBlock) k_first_hit(const LaunchArgs A, float4
   stage_top(A.scene, s_top);
   TraceTally tally;
   CentreSource src{A};
-  FirstHitSink sink{A, hit, inst};
+  HitSink<true> sink{A, hit, inst};
   const uint32_t n = A.map.n_local_pixels;
   if (A.scene.two_level) trace_wave_tl<false, false>(A.scene, src, sink, &s_stack[threadIdx.x], wave_aux(s_aux, threadIdx.x >> 6), wave_links(s_aux, threadIdx.x >> 6), &s_top_ray[threadIdx.x], (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, n, wave_index(), wave_count(), tally);
   else trace_wave<false, false>(A.scene, src, sink, &s_stack[threadIdx.x], wave_aux(s_aux, threadIdx.x >> 6), wave_links(s_aux, threadIdx.x >> 6), (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, n, wave_index(), wave_count(), tally);
 }
 
 // ---------------------------------------------------------------------------------------------
-// One vertex of a guide chain: the first lines of shade_pixel_body up to fetch_material_textures restated -- same operations, same
-// order -- with texture level 0 always (kNoLod).  Gives the vertex's planes' values (the normal turned against `direction`, the albedo)
-// and, with CHAIN, the ray the path would go on with through a specular material: `point` and `wiW` as shade_pixel_body forms them
-// (bsdf_sample with xi = (0, 0, 1 - 2^-24): Mirror ignores it, Glass takes the transmitted branch unless its Fresnel term is 1).
+// One vertex of a guide chain: the hit vertex of shade_pixel_body (device/hit_vertex.h) with texture level 0 always (kNoLod).  Gives the
+// vertex's planes' values (the normal turned against `direction`, the albedo) and, with CHAIN, the ray the path would go on with through
+// a specular material: `point` and `wiW` as shade_pixel_body forms them (bsdf_sample with xi = (0, 0, 1 - 2^-24): Mirror ignores it,
+// Glass takes the transmitted branch unless its Fresnel term is 1).
 // ---------------------------------------------------------------------------------------------
 struct GuideVertex {
   vec3 n, albedo;
@@ -68,63 +72,24 @@ struct GuideVertex {
 };
 template <bool CHAIN>
 __device__ __forceinline__ GuideVertex guide_vertex(const DeviceScene& S, float4 hr, uint32_t hit_inst, vec3 direction) {
-  const uint32_t leaf = __float_as_uint(hr.w);
-  const float4* rec = S.shade_tris + 8u * (size_t)leaf;
-  const float4 va0 = rec[0], va1 = rec[1], vb0 = rec[2], vb1 = rec[3], vc0 = rec[4], vc1 = rec[5], dn = rec[6], du = rec[7];
-  uint32_t material_id = __float_as_uint(dn.w), xf_bits = __float_as_uint(du.w);
-  if (S.two_level) {
-    const RTInstance in = S.instances[hit_inst];
-    material_id = in.material_id;
-    xf_bits = in.transform_id | (S.xf_identity[in.transform_id] ? 0x80000000u : 0u);
-  }
-  const float b0 = 1.0f - hr.y - hr.z, b1 = hr.y, b2 = hr.z;
-  vec3 point = mk3(0.0f, 0.0f, 0.0f);
-  if (CHAIN) point = (mk3(va0.x, va0.y, va0.z) * b0 + mk3(vb0.x, vb0.y, vb0.z) * b1) + mk3(vc0.x, vc0.y, vc0.z) * b2;
-  const vec2 uv = vec2{(va1.z * b0 + vb1.z * b1) + vc1.z * b2, (va1.w * b0 + vb1.w * b1) + vc1.w * b2};
-  vec3 ng = mk3(dn.x, dn.y, dn.z), dpdu = mk3(du.x, du.y, du.z);
-  vec3 ns = (mk3(va0.w, va1.x, va1.y) * b0 + mk3(vb0.w, vb1.x, vb1.y) * b1) + mk3(vc0.w, vc1.x, vc1.y) * b2;
-  const MatScalars mat = load_material(&S.materials[material_id]);
   const TexFootprint fp{kNoLod, 0.0f, 0.0f, 1u};
-  if (mat.normal != 0) {
-    const vec4 tx = texture2d_lod(S, mat.normal, uv.x, uv.y, fp);
-    Frame old;
-    old.s = normalize3(dpdu);
-    old.n = ns;
-    old.t = normalize3(cross3(old.n, old.s));
-    ns = normalize3(to_world(mk3(tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f), old));
-    ns = ns * gl_sign(dot3(ng, ns));
-  }
-  if (!(xf_bits >> 31)) {
-    const float4* xq = reinterpret_cast<const float4*>(&S.transforms[xf_bits & 0x7FFFFFFFu]);
-    const float4 w0 = xq[4], w1 = xq[5], w2 = xq[6];
-    const float w2o[12] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
-    if (CHAIN) {
-      const float4 m0 = xq[0], m1 = xq[1], m2 = xq[2], m3 = xq[3];
-      const float o2w[16] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w, m3.x, m3.y, m3.z, m3.w};
-      point = xform_point(o2w, point);
-      dpdu = xform_point(o2w, dpdu);   // transformed as a point, as shade_pixel_body does (Q8)
-    }
-    ns = xform_tdir(w2o, ns);
-  }
+  HitVertex hv = load_hit_vertex(S, hr, [&]() { return hit_inst; });
+  finish_hit_vertex<CHAIN>(S, hv, fp);
+  const MatScalars& mat = hv.mat;
   GuideVertex v;
-  v.n = normalize3(ns);
+  v.n = normalize3(hv.ns);
   if (dot3(v.n, direction) > 0.0f) v.n = -v.n;
   if (!(post::finite1(v.n.x) && post::finite1(v.n.y) && post::finite1(v.n.z))) v.n = mk3(0.0f, 0.0f, 0.0f);   // a zero-length ns normalises to NaN
   v.albedo = mk3(1.0f, 1.0f, 1.0f);
   if (mat.bsdf_index == kBsdfLambert || mat.bsdf_index == kBsdfUber) {
-    const vec4 tx = texture2d_lod(S, mat.diffuse, uv.x, uv.y, fp);
+    const vec4 tx = texture2d_lod(S, mat.diffuse, hv.uv.x, hv.uv.y, fp);
     v.albedo = mk3(tx.x, tx.y, tx.z) * mk3(mat.diffuse_mul[0], mat.diffuse_mul[1], mat.diffuse_mul[2]);
   }
   v.go_on = false;
-  v.point = point;
+  v.point = hv.point;
   v.wiW = mk3(0.0f, 0.0f, 0.0f);
   if (CHAIN && mat.is_specular != 0) {
-    SurfacePoint P;
-    P.woW = -direction;
-    P.uv = uv;
-    P.frame = make_frame(dpdu, ns);
-    P.mat = mat;
-    fetch_material_textures(S, P, fp);
+    const SurfacePoint P = hit_surface_point(S, hv, direction, fp);
     Spec value = spec_set(0.0f);
     const float pdf = bsdf_sample(S, P, mk3(0.0f, 0.0f, 0x1.fffffep-1f), value, v.wiW);
     v.go_on = pdf != 0.0f && post::finite1(v.wiW.x) && post::finite1(v.wiW.y) && post::finite1(v.wiW.z);
@@ -270,16 +235,6 @@ struct ListSource {
     return true;
   }
 };
-struct ListSink {
-  const LaunchArgs& A;
-  float4* hit;       // by slot: t, u, v, leaf (bits)
-  uint32_t* inst;    // by slot: RTInstance of the hit
-  __device__ __forceinline__ void store(uint32_t i, const HitRecord& h) {
-    const bool is_hit = h.leaf != 0xFFFFFFFFu;
-    hit[i] = make_float4(is_hit ? h.t : INFINITY, h.u, h.v, __uint_as_float(h.leaf));
-    inst[i] = is_hit ? (A.scene.two_level ? h.inst : A.scene.bvh_tris[h.leaf].instance) : 0xFFFFFFFFu;
-  }
-};
 __global__ void __launch_bounds__(kBlock) k_guide_trace(const LaunchArgs A, const float4* __restrict__ in_o, const float4* __restrict__ in_d, const uint32_t* in_count,
                                                         float4* hit, uint32_t* inst) {
   __shared__ int s_stack[kLdsStack * kBlock];
@@ -291,7 +246,7 @@ __global__ void __launch_bounds__(kBlock) k_guide_trace(const LaunchArgs A, cons
   stage_top(A.scene, s_top);
   TraceTally tally;
   ListSource src{in_o, in_d, n};
-  ListSink sink{A, hit, inst};
+  HitSink<false> sink{A, hit, inst};
   if (A.scene.two_level) trace_wave_tl<false, false>(A.scene, src, sink, &s_stack[threadIdx.x], wave_aux(s_aux, threadIdx.x >> 6), wave_links(s_aux, threadIdx.x >> 6), &s_top_ray[threadIdx.x], (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, n, wave_index(), wave_count(), tally);
   else trace_wave<false, false>(A.scene, src, sink, &s_stack[threadIdx.x], wave_aux(s_aux, threadIdx.x >> 6), wave_links(s_aux, threadIdx.x >> 6), (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, n, wave_index(), wave_count(), tally);
 }
@@ -371,8 +326,8 @@ __global__ void __launch_bounds__(kBlock) k_despeckle(uint32_t w, uint32_t h, ui
 //   k_motion     one thread per pixel (row-major), after k_first_hit and before anything reuses the hit buffers: the hit record and the
 //                instance, the three position float4s and the transform word of the shading record (rec[0], rec[2], rec[4], rec[7]: one
 //                128-byte line), 64 B of the previous object -> world matrix (the caller's, 64 B apart, or the scene's own, the first half
-//                of its 128-byte TransformPair), one float4 out.  The object-space point is guide_vertex's `point`; nothing is skipped for
-//                a transform flagged identity: the previous one need not be.
+//                of its 128-byte TransformPair), one float4 out.  Record, point and transform index are hit_vertex.h's; nothing is skipped
+//                for a transform flagged identity: the previous one need not be.
 //   k_reproject  k_atrous's layout.  A wave's taps sit at p + motion with nearly equal motion, so they fall in a few lines; every load is
 //                requested before the first is used.  No LDS, no scratch, no loop with a data-dependent trip count.
 // ---------------------------------------------------------------------------------------------
@@ -387,12 +342,9 @@ __global__ void __launch_bounds__(kBlock) k_motion(const DeviceScene S, uint32_t
     return;
   }
   const uint32_t hit_inst = inst[p];
-  const float4* rec = S.shade_tris + 8u * (size_t)leaf;
-  const float4 va0 = rec[0], vb0 = rec[2], vc0 = rec[4], du = rec[7];
-  uint32_t xf = __float_as_uint(du.w) & 0x7FFFFFFFu;
-  if (S.two_level) xf = S.instances[hit_inst].transform_id;
-  const float b0 = 1.0f - hr.y - hr.z, b1 = hr.y, b2 = hr.z;
-  const vec3 point = (mk3(va0.x, va0.y, va0.z) * b0 + mk3(vb0.x, vb0.y, vb0.z) * b1) + mk3(vc0.x, vc0.y, vc0.z) * b2;
+  const ShadeRecord rec = load_shade_record(S, leaf);
+  const uint32_t xf = hit_ids<false>(S, rec, [&]() { return hit_inst; }).xf;
+  const vec3 point = hit_point(rec, hr);
   const float4* xq = prev_o2w ? prev_o2w + 4u * (size_t)xf : reinterpret_cast<const float4*>(&S.transforms[xf]);
   const float4 m0 = xq[0], m1 = xq[1], m2 = xq[2], m3 = xq[3];
   const float o2w[16] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w, m3.x, m3.y, m3.z, m3.w};
@@ -427,8 +379,7 @@ hipError_t launch_first_hit(hipStream_t st, const LaunchArgs& a, uint32_t blocks
   return hipGetLastError();
 }
 hipError_t launch_first_hit_attributes(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, float4* aov0, float4* aov1) {
-  const uint32_t n = a.map.width * a.map.height;
-  return launch_per_item(st, k_first_hit_attributes, n, a, hit, inst, aov0, aov1);
+  return launch_per_item(st, k_first_hit_attributes, a.map.width * a.map.height, a, hit, inst, aov0, aov1);
 }
 // blocks of k_guide_trace's persistent grid: the tracers' residency rule, and never more than the first-hit pass's, whose spill area it uses
 uint32_t guide_grid_blocks(uint32_t n_rays, uint32_t first_hit_blocks) { return std::min(persistent_grid(k_guide_trace, n_rays).x, first_hit_blocks); }
@@ -456,8 +407,7 @@ hipError_t launch_guide_scatter(hipStream_t st, uint32_t blocks, const GuideList
   return hipGetLastError();
 }
 hipError_t launch_camera_rays(hipStream_t st, const LaunchArgs& a, float off_x, float off_y, float* origins3, float* dirs3) {
-  const uint32_t n = a.map.width * a.map.height;
-  return launch_per_item(st, k_camera_rays, n, a, off_x, off_y, origins3, dirs3);
+  return launch_per_item(st, k_camera_rays, a.map.width * a.map.height, a, off_x, off_y, origins3, dirs3);
 }
 static dim3 post_tile_grid(uint32_t w, uint32_t h) { return dim3((w + kPostTileW - 1) / kPostTileW, (h + kPostTileH - 1) / kPostTileH); }
 template <bool REMODULATE>
@@ -504,8 +454,7 @@ hipError_t launch_despeckle(hipStream_t st, uint32_t w, uint32_t h, const glz_de
 }
 hipError_t launch_motion(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, const float4* prev_o2w, const post::ProjectConstants& prev,
                          float4* motion) {
-  const uint32_t n = a.map.width * a.map.height;
-  return launch_per_item(st, k_motion, n, a.scene, a.map.width, a.map.height, hit, inst, prev_o2w, prev, motion);
+  return launch_per_item(st, k_motion, a.map.width * a.map.height, a.scene, a.map.width, a.map.height, hit, inst, prev_o2w, prev, motion);
 }
 hipError_t launch_reproject(hipStream_t st, uint32_t w, uint32_t h, const glz_reproject_params& P, const float4* motion, const float4* prev_color,
                             const float4* prev_aov0, const float4* prev_aov1, float4* out, hipEvent_t* marks) {

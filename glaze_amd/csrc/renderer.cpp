@@ -1051,7 +1051,8 @@ void Renderer::post_args(LaunchArgs& a) const {
   a.map = make_tile_map(w_, h_, 0, 1);
 }
 
-bool Renderer::first_hit_pass(Error& err, hipEvent_t* marks, uint32_t last_list) {
+bool Renderer::first_hit_pass(const FirstHitRequest& req, Error& err) {
+  hipEvent_t* const marks = req.marks;
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   LaunchArgs a;
   post_args(a);
@@ -1086,15 +1087,15 @@ bool Renderer::first_hit_pass(Error& err, hipEvent_t* marks, uint32_t last_list)
   if (marks) (void)hipEventRecord(marks[0], st);
   if (!hip_ok(launch_first_hit(st, a, blocks, fh_hit_.ptr, fh_inst_.ptr), "k_first_hit", err)) return false;
   if (marks) (void)hipEventRecord(marks[1], st);
-  if (motion_request_) {
-    const MotionRequest& m = *motion_request_;
+  if (req.motion) {
+    const MotionStep& m = *req.motion;
     if (m.marks) (void)hipEventRecord(m.marks[0], st);
     if (!hip_ok(launch_motion(st, a, fh_hit_.ptr, fh_inst_.ptr, m.prev_o2w, m.prev, m.out), "k_motion", err)) return false;
     if (m.marks) (void)hipEventRecord(m.marks[1], st);
   }
   if (chain) {
     guide_blocks_ = guide_grid_blocks(a.map.n_local_pixels, blocks);
-    if (!hip_ok(launch_guide_chain(st, a, guide_blocks_, guide_bounces_, last_list, fh_hit_.ptr, fh_inst_.ptr, guide_lists(), aov0_.ptr, aov1_.ptr), "k_guide_continue", err))
+    if (!hip_ok(launch_guide_chain(st, a, guide_blocks_, guide_bounces_, req.last_list, fh_hit_.ptr, fh_inst_.ptr, guide_lists(), aov0_.ptr, aov1_.ptr), "k_guide_continue", err))
       return false;
   } else if (!hip_ok(launch_first_hit_attributes(st, a, fh_hit_.ptr, fh_inst_.ptr, aov0_.ptr, aov1_.ptr), "k_first_hit_attributes", err)) {
     return false;
@@ -1133,7 +1134,7 @@ bool Renderer::guide_chain(uint32_t segment, float* origins3, float* dirs3, uint
   memset(dirs3, 0, sizeof(float) * 3 * n);
   memset(alive, 0, n);
   if (guide_mode_ != GLZ_GUIDE_THROUGH_SPECULAR || segment > guide_bounces_ || n == 0) return true;
-  if (!first_hit_pass(err, nullptr, segment)) return false;   // up to the list of this segment
+  if (!first_hit_pass({nullptr, segment}, err)) return false;   // up to the list of this segment
   DeviceBuffer<float> d_o, d_d;
   DeviceBuffer<uint8_t> d_alive;
   if (!hip_ok(d_o.alloc(3 * n), "alloc", err) || !hip_ok(d_d.alloc(3 * n), "alloc", err) || !hip_ok(d_alive.alloc(n), "alloc", err)) return false;
@@ -1154,7 +1155,7 @@ bool Renderer::read_aov(int which, float* out, Error& err) {
     err.msg = "unknown feature buffer (GLZ_AOV_NORMAL_DEPTH or GLZ_AOV_ALBEDO_INSTANCE)";
     return false;
   }
-  if (!first_hit_pass(err)) return false;
+  if (!first_hit_pass({}, err)) return false;
   return frame_to_host(which == GLZ_AOV_NORMAL_DEPTH ? aov0_.ptr : aov1_.ptr, out, "read feature buffer", err);
 }
 
@@ -1182,30 +1183,47 @@ bool Renderer::ensure_denoise_frames(Error& err) {
   return false;
 }
 
-bool Renderer::time_post(float ms[GLZ_POST_TIMING_SLOTS], Error& err) {
-  if (world_ > 1 && peers_.empty()) {
-    err.code = GLZ_E_ARG;
-    err.msg = "time_post: under set_partition(world > 1) the frame is not in this process";
-    return false;
+// the readers of the whole frame: under set_partition(world > 1) it is not in this process (with set_devices the partition is over this
+// process's own devices: gather() brings their tiles)
+bool Renderer::frame_is_here(const char* who, Error& err) const {
+  if (world_ <= 1 || !peers_.empty()) return true;
+  err.code = GLZ_E_ARG;
+  err.msg = std::string(who) + ": under set_partition(world > 1) the frame is not in this process";
+  return false;
+}
+
+namespace {
+// N device events for one timed run: created together, destroyed with the holder
+template <int N>
+struct Events {
+  hipEvent_t ev[N] = {};
+  bool create(Error& err) {
+    for (auto& e : ev)
+      if (!hip_ok(hipEventCreate(&e), "hipEventCreate", err)) return false;
+    return true;
   }
+  ~Events() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+}  // namespace
+
+bool Renderer::time_post(float ms[GLZ_POST_TIMING_SLOTS], Error& err) {
+  if (!frame_is_here("time_post", err)) return false;
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   if (!gather(true, frame_tmp_.ptr, err) || !ensure_denoise_frames(err)) return false;
-  hipEvent_t ev[GLZ_POST_TIMING_SLOTS + 2] = {};   // three around the first-hit pass's kernels, 2 + iterations around the filter's
-  bool ok = true;
-  for (auto& e : ev) ok = ok && hip_ok(hipEventCreate(&e), "hipEventCreate", err);
+  Events<GLZ_POST_TIMING_SLOTS + 2> t;   // three around the first-hit pass's kernels, 2 + iterations around the filter's
+  hipEvent_t* const ev = t.ev;
   hipStream_t st = chains_[0]->stream;
-  ok = ok && first_hit_pass(err, ev);
-  ok = ok && hip_ok(launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr, ev + 3), "k_atrous", err);
-  ok = ok && hip_ok(hipStreamSynchronize(st), "time_post", err);
-  if (ok) {
-    for (int i = 0; i < GLZ_POST_TIMING_SLOTS; ++i) ms[i] = 0.0f;
-    (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]);
-    (void)hipEventElapsedTime(&ms[1], ev[1], ev[2]);
-    for (uint32_t i = 0; i < 1u + denoise_.iterations; ++i) (void)hipEventElapsedTime(&ms[2 + i], ev[3 + i], ev[4 + i]);
-  }
-  for (auto& e : ev)
-    if (e) (void)hipEventDestroy(e);
-  return ok;
+  if (!t.create(err) || !first_hit_pass({ev}, err)) return false;
+  if (!hip_ok(launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr, ev + 3), "k_atrous", err)) return false;
+  if (!hip_ok(hipStreamSynchronize(st), "time_post", err)) return false;
+  for (int i = 0; i < GLZ_POST_TIMING_SLOTS; ++i) ms[i] = 0.0f;
+  (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]);
+  (void)hipEventElapsedTime(&ms[1], ev[1], ev[2]);
+  for (uint32_t i = 0; i < 1u + denoise_.iterations; ++i) (void)hipEventElapsedTime(&ms[2 + i], ev[3 + i], ev[4 + i]);
+  return true;
 }
 
 bool Renderer::set_denoise(const glz_denoise_params* p, Error& err) {
@@ -1219,23 +1237,22 @@ bool Renderer::set_denoise(const glz_denoise_params* p, Error& err) {
   return true;
 }
 
-bool Renderer::read_denoised(float* rgba32f, uint8_t* rgba8, Error& err) {
-  if (world_ > 1 && peers_.empty()) {   // (with set_devices the partition is over this process's own devices: gather() brings their tiles)
-    err.code = GLZ_E_ARG;
-    err.msg = "read_denoised: under set_partition(world > 1) the frame is not in this process";
-    return false;
-  }
+// read_denoised (filter: the a-trous passes, with the rejection ahead of them when it is enabled) and read_despeckled (the rejection alone)
+bool Renderer::read_post(bool filter, float* rgba32f, uint8_t* rgba8, Error& err) {
+  const char* what = filter ? "read denoised" : "read despeckled";
+  if (!frame_is_here(filter ? "read_denoised" : "read_despeckled", err)) return false;
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   if (!gather(true, frame_tmp_.ptr, err)) return false;   // flushes the pending shadow rays, brings the other devices' tiles
-  if (!first_hit_pass(err)) return false;
+  if (!first_hit_pass({}, err)) return false;
   if (!ensure_denoise_frames(err)) return false;
   hipStream_t st = chains_[0]->stream;   // = the instance stream the first-hit pass ran on
-  if (!hip_ok(launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr, nullptr, despeckle_on_ ? &despeckle_ : nullptr),
-              "k_atrous", err))
-    return false;
-  if (rgba32f && !frame_to_host(dn_out_.ptr, rgba32f, "read denoised", err)) return false;
-  if (rgba8 && !rgba8_to_host(dn_out_.ptr, rgba8, "read denoised", "read denoised", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "read denoised", err);   // with neither output the filter has still run when this returns
+  const hipError_t launched =
+      filter ? launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr, nullptr, despeckle_on_ ? &despeckle_ : nullptr)
+             : launch_despeckle(st, w_, h_, despeckle_, denoise_.eps_albedo, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_out_.ptr);
+  if (!hip_ok(launched, filter ? "k_atrous" : "k_despeckle", err)) return false;
+  if (rgba32f && !frame_to_host(dn_out_.ptr, rgba32f, what, err)) return false;
+  if (rgba8 && !rgba8_to_host(dn_out_.ptr, rgba8, what, what, err)) return false;
+  return hip_ok(hipStreamSynchronize(st), what, err);   // with neither output the filter has still run when this returns
 }
 
 bool Renderer::set_despeckle(bool enabled, const glz_despeckle_params* p, Error& err) {
@@ -1254,23 +1271,6 @@ int Renderer::despeckle(glz_despeckle_params* out) const {
   return despeckle_on_ ? 1 : 0;
 }
 
-bool Renderer::read_despeckled(float* rgba32f, uint8_t* rgba8, Error& err) {
-  if (world_ > 1 && peers_.empty()) {   // as read_denoised
-    err.code = GLZ_E_ARG;
-    err.msg = "read_despeckled: under set_partition(world > 1) the frame is not in this process";
-    return false;
-  }
-  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  if (!gather(true, frame_tmp_.ptr, err)) return false;
-  if (!first_hit_pass(err)) return false;
-  if (!ensure_denoise_frames(err)) return false;
-  hipStream_t st = chains_[0]->stream;
-  if (!hip_ok(launch_despeckle(st, w_, h_, despeckle_, denoise_.eps_albedo, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_out_.ptr), "k_despeckle", err)) return false;
-  if (rgba32f && !frame_to_host(dn_out_.ptr, rgba32f, "read despeckled", err)) return false;
-  if (rgba8 && !rgba8_to_host(dn_out_.ptr, rgba8, "read despeckled", "read despeckled", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "read despeckled", err);
-}
-
 // the checks of read_motion and reproject, the upload of the caller's matrices, then the first-hit pass with k_motion in it
 bool Renderer::motion_pass(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, DeviceBuffer<float4>& prev_o2w,
                            DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks) {
@@ -1286,22 +1286,21 @@ bool Renderer::motion_pass(const glz_camera* prev_camera, const glz_transform* p
   }
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   hipStream_t st = inst_->stream;
-  MotionRequest req;
-  host::project_constants(*prev_camera, w_, h_, req.prev.world2camera, req.prev.camera2screen);
-  req.prev.persp = prev_camera->type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
-  req.prev_o2w = nullptr;
+  MotionStep step;
+  host::project_constants(*prev_camera, w_, h_, step.prev.world2camera, step.prev.camera2screen);
+  step.prev.persp = prev_camera->type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
+  step.prev_o2w = nullptr;
   if (prev_transforms && n_prev > 0) {
     static_assert(sizeof(glz_transform) == 4 * sizeof(float4), "one previous matrix is four float4");
     if (!hip_ok(prev_o2w.upload(reinterpret_cast<const float4*>(prev_transforms), 4 * (size_t)n_prev, st), "upload previous transforms", err)) return false;
-    req.prev_o2w = prev_o2w.ptr;
+    step.prev_o2w = prev_o2w.ptr;
   }
   if (!hip_ok(motion.alloc((size_t)w_ * h_), "alloc motion plane", err)) return false;
-  req.out = motion.ptr;
-  req.marks = marks;
-  motion_request_ = &req;
-  const bool ok = first_hit_pass(err);
-  motion_request_ = nullptr;
-  return ok;
+  step.out = motion.ptr;
+  step.marks = marks;
+  FirstHitRequest pass;
+  pass.motion = &step;
+  return first_hit_pass(pass, err);
 }
 
 bool Renderer::read_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* out, Error& err) {
@@ -1312,16 +1311,12 @@ bool Renderer::read_motion(const glz_camera* prev_camera, const glz_transform* p
 
 bool Renderer::time_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* kernel_ms, Error& err) {
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  hipEvent_t ev[2] = {};
-  bool ok = true;
-  for (auto& e : ev) ok = ok && hip_ok(hipEventCreate(&e), "hipEventCreate", err);
+  Events<2> t;
   DeviceBuffer<float4> prev_o2w, motion;
-  ok = ok && motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err, ev);
-  ok = ok && hip_ok(hipStreamSynchronize(inst_->stream), "time_motion", err);
-  if (ok) (void)hipEventElapsedTime(kernel_ms, ev[0], ev[1]);
-  for (auto& e : ev)
-    if (e) (void)hipEventDestroy(e);
-  return ok;
+  if (!t.create(err) || !motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err, t.ev)) return false;
+  if (!hip_ok(hipStreamSynchronize(inst_->stream), "time_motion", err)) return false;
+  (void)hipEventElapsedTime(kernel_ms, t.ev[0], t.ev[1]);
+  return true;
 }
 
 bool Renderer::reproject(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, const float* prev_color, const float* prev_aov0,

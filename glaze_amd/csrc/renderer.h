@@ -36,11 +36,11 @@ class Renderer {
   // ---- post: first-hit feature buffers and the denoiser (kernels_post.hip) ----
   bool read_aov(int which, float* out, Error& err);                   // runs the first-hit pass; GLZ_AOV_*
   bool set_denoise(const glz_denoise_params* p, Error& err);          // null = defaults; accumulation goes on
-  bool read_denoised(float* rgba32f, uint8_t* rgba8, Error& err);     // gather + first-hit pass + filter; either output may be null
+  bool read_denoised(float* rgba32f, uint8_t* rgba8, Error& err) { return read_post(true, rgba32f, rgba8, err); }     // gather + first-hit pass + filter; either output may be null
   // firefly rejection (glz_despeckle_params): enabled = ahead of the filter in read_denoised; null = defaults; accumulation goes on
   bool set_despeckle(bool enabled, const glz_despeckle_params* p, Error& err);
   int despeckle(glz_despeckle_params* out) const;                      // the enabled flag
-  bool read_despeckled(float* rgba32f, uint8_t* rgba8, Error& err);    // gather + first-hit pass + demodulation + rejection; no filter pass
+  bool read_despeckled(float* rgba32f, uint8_t* rgba8, Error& err) { return read_post(false, rgba32f, rgba8, err); }    // gather + first-hit pass + demodulation + rejection; no filter pass
   // motion vectors and history reprojection (glz_reproject_params; reproject.h): the first-hit trace and k_motion against the caller's
   // previous camera and transforms (null = the scene's own), then, for reproject, k_reproject on the three uploaded previous frames
   bool read_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* out, Error& err);
@@ -205,19 +205,25 @@ class Renderer {
   const struct Rccl* rccl(Error& err) const;   // the loaded library, if this renderer has its communicators
   bool step_local(uint32_t n, Error& err);
 
-  // The first-hit pass over the FULL frame on this device, whatever the partition: centre rays, closest hits, attributes -> aov0_ / aov1_.
-  // Recomputed on every request, never cached; its buffers are private (allocated on first use, released by change_resolution).
-  // In GLZ_GUIDE_THROUGH_SPECULAR the chain's kernels take the attribute kernel's place (launch_guide_chain; last_list as there).
-  bool first_hit_pass(Error& err, hipEvent_t* marks = nullptr, uint32_t last_list = GLZ_GUIDE_MAX_BOUNCES + 1);   // marks: 3 events around the trace and what follows it
-  void post_args(LaunchArgs& a) const;
-  // what first_hit_pass launches k_motion with, between the trace and whatever reuses the hit buffers
-  struct MotionRequest {
+  // what the first-hit pass launches k_motion with, between the trace and whatever reuses the hit buffers
+  struct MotionStep {
     post::ProjectConstants prev;
     const float4* prev_o2w;   // device, or null = the scene's own
     float4* out;              // device
     hipEvent_t* marks;        // null, or two events recorded around k_motion
   };
-  const MotionRequest* motion_request_ = nullptr;   // set by motion_pass() around its first_hit_pass()
+  struct FirstHitRequest {
+    hipEvent_t* marks = nullptr;                      // null, or 3 events around the trace and what follows it
+    uint32_t last_list = GLZ_GUIDE_MAX_BOUNCES + 1;   // launch_guide_chain's: the chain stops once this list is written
+    const MotionStep* motion = nullptr;               // null, or motion_pass()'s k_motion
+  };
+  // The first-hit pass over the FULL frame on this device, whatever the partition: centre rays, closest hits, attributes -> aov0_ / aov1_.
+  // Recomputed on every request, never cached; its buffers are private (allocated on first use, released by change_resolution).
+  // In GLZ_GUIDE_THROUGH_SPECULAR the chain's kernels take the attribute kernel's place (launch_guide_chain).
+  bool first_hit_pass(const FirstHitRequest& req, Error& err);
+  void post_args(LaunchArgs& a) const;
+  bool frame_is_here(const char* who, Error& err) const;                     // false, with the error set, for one rank of a process partition
+  bool read_post(bool filter, float* rgba32f, uint8_t* rgba8, Error& err);   // read_denoised (filter) / read_despeckled
   bool motion_pass(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, DeviceBuffer<float4>& prev_o2w, DeviceBuffer<float4>& motion,
                    Error& err, hipEvent_t* marks = nullptr);
   void release_post();
