@@ -376,18 +376,18 @@ int glz_renderer_read_result(glz_renderer* h, float* out) {
 int glz_renderer_read_aov(glz_renderer* h, int which, float* out) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!out) return fail(GLZ_E_ARG, "output is null");
-  GLZ_RET(h->r->read_aov(which, out, e));
+  GLZ_RET(h->r->post().read_aov(which, out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
-int glz_renderer_set_denoise(glz_renderer* h, const glz_denoise_params* p) { GLZ_GUARD_BEGIN GLZ_R(h); GLZ_RET(h->r->set_denoise(p, e)); GLZ_GUARD_END(GLZ_E_IO) }
+int glz_renderer_set_denoise(glz_renderer* h, const glz_denoise_params* p) { GLZ_GUARD_BEGIN GLZ_R(h); GLZ_RET(h->r->post().set_denoise(p, e)); GLZ_GUARD_END(GLZ_E_IO) }
 int glz_renderer_set_guide_mode(glz_renderer* h, int mode, uint32_t max_bounces) {
   GLZ_GUARD_BEGIN GLZ_R(h);
-  GLZ_RET(h->r->set_guide_mode(mode, max_bounces, e));
+  GLZ_RET(h->r->post().set_guide_mode(mode, max_bounces, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_guide_mode(glz_renderer* h, uint32_t* max_bounces_out) {
   GLZ_GUARD_BEGIN GLZ_R(h);
-  return h->r->guide_mode(max_bounces_out);
+  return h->r->post().guide_mode(max_bounces_out);
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_read_denoised(glz_renderer* h, float* rgba32f, uint8_t* rgba8) {
@@ -397,12 +397,12 @@ int glz_renderer_read_denoised(glz_renderer* h, float* rgba32f, uint8_t* rgba8) 
 }
 int glz_renderer_set_despeckle(glz_renderer* h, int enabled, const glz_despeckle_params* p) {
   GLZ_GUARD_BEGIN GLZ_R(h);
-  GLZ_RET(h->r->set_despeckle(enabled != 0, p, e));
+  GLZ_RET(h->r->post().set_despeckle(enabled != 0, p, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_despeckle(glz_renderer* h, glz_despeckle_params* out) {
   GLZ_GUARD_BEGIN GLZ_R(h);
-  return h->r->despeckle(out);
+  return h->r->post().despeckle(out);
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_read_despeckled(glz_renderer* h, float* rgba32f, uint8_t* rgba8) {
@@ -414,7 +414,7 @@ int glz_renderer_read_motion(glz_renderer* h, const glz_camera* prev_camera, con
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!prev_camera || !out) return fail(GLZ_E_ARG, "the previous camera or the output is null");
   if (prev_camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
-  GLZ_RET(h->r->read_motion(prev_camera, prev_transforms, n_prev_transforms, out, e));
+  GLZ_RET(h->r->post().read_motion(prev_camera, prev_transforms, n_prev_transforms, out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_reproject(glz_renderer* h, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms, const float* prev_color,
@@ -422,7 +422,7 @@ int glz_renderer_reproject(glz_renderer* h, const glz_camera* prev_camera, const
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!prev_camera || !prev_color || !prev_aov0 || !prev_aov1 || !out) return fail(GLZ_E_ARG, "the previous camera, a previous frame or the output is null");
   if (prev_camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
-  GLZ_RET(h->r->reproject(prev_camera, prev_transforms, n_prev_transforms, prev_color, prev_aov0, prev_aov1, params, out, e));
+  GLZ_RET(h->r->post().reproject(prev_camera, prev_transforms, n_prev_transforms, prev_color, prev_aov0, prev_aov1, params, out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_launch_constants(glz_renderer* h, uint32_t launch, uint32_t* seed, float off[2]) {

@@ -94,20 +94,20 @@ int glz_debug_post_timing(glz_renderer* h, float ms_out[GLZ_POST_TIMING_SLOTS]) 
 int glz_debug_camera_rays(glz_renderer* h, float off_x, float off_y, float* origins3, float* dirs3) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!origins3 || !dirs3) return fail(GLZ_E_ARG, "output is null");
-  GLZ_RET(h->r->camera_rays(off_x, off_y, origins3, dirs3, e));
+  GLZ_RET(h->r->post().camera_rays(off_x, off_y, origins3, dirs3, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_debug_motion_timing(glz_renderer* h, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms, float* kernel_ms_out) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!prev_camera || !kernel_ms_out || prev_camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "bad argument");
   *kernel_ms_out = 0.0f;
-  GLZ_RET(h->r->time_motion(prev_camera, prev_transforms, n_prev_transforms, kernel_ms_out, e));
+  GLZ_RET(h->r->post().time_motion(prev_camera, prev_transforms, n_prev_transforms, kernel_ms_out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_debug_guide_chain(glz_renderer* h, uint32_t segment, float* origins3, float* dirs3, uint8_t* alive) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!origins3 || !dirs3 || !alive) return fail(GLZ_E_ARG, "output is null");
-  GLZ_RET(h->r->guide_chain(segment, origins3, dirs3, alive, e));
+  GLZ_RET(h->r->post().guide_chain(segment, origins3, dirs3, alive, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 

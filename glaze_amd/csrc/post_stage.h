@@ -1,0 +1,93 @@
+// The post stage of a renderer (kernels_post.hip): the first-hit pass with its feature buffers, the guide chain, the a-trous filter, the
+// firefly rejection, motion and reprojection.  It runs on the renderer's own device only, over the FULL frame whatever the partition, on
+// the instance's stream.  Its buffers and settings are its own; device, stream, scene, frame size and camera are the renderer's, read on
+// every call -- a new scene, camera or set of transforms needs no word to the stage, a new resolution only release().
+#pragma once
+#include "kernels.h"
+#include "scene.h"
+
+namespace glz {
+
+class Renderer;
+
+// N device events for one timed run: created together, destroyed with the holder
+template <int N>
+struct Events {
+  hipEvent_t ev[N] = {};
+  bool create(Error& err) {
+    for (auto& e : ev)
+      if (!hip_ok(hipEventCreate(&e), "hipEventCreate", err)) return false;
+    return true;
+  }
+  ~Events() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+class PostStage {
+ public:
+  explicit PostStage(const Renderer& r) : r_(r) {}
+  void release();   // every buffer; each comes back on first use
+
+  // ---- first-hit feature buffers and the denoiser ----
+  bool read_aov(int which, float* out, Error& err);                   // runs the first-hit pass; GLZ_AOV_*
+  bool set_denoise(const glz_denoise_params* p, Error& err);          // null = defaults; accumulation goes on
+  const glz_denoise_params& denoise() const { return denoise_; }
+  // firefly rejection (glz_despeckle_params): enabled = ahead of the filter in read_denoised; null = defaults; accumulation goes on
+  bool set_despeckle(bool enabled, const glz_despeckle_params* p, Error& err);
+  int despeckle(glz_despeckle_params* out) const;                      // the enabled flag
+  // The first-hit pass, then on `frame` (device; the renderer's gathered result) the a-trous passes, with the rejection ahead of them when
+  // it is enabled (filter), or demodulation + rejection with no filter pass (!filter).  Returns the device frame that holds the outcome
+  // once the stream has drained, null on failure.  marks: null, or GLZ_POST_TIMING_SLOTS + 2 events -- three around the first-hit pass's
+  // kernels, 2 + iterations around the filter's; such a timed run never includes the rejection.
+  const float4* filtered(const float4* frame, bool filter, hipEvent_t* marks, Error& err);
+  // motion vectors and history reprojection (glz_reproject_params; reproject.h): the first-hit trace and k_motion against the caller's
+  // previous camera and transforms (null = the scene's own), then, for reproject, k_reproject on the three uploaded previous frames
+  bool read_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* out, Error& err);
+  bool time_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* kernel_ms, Error& err);   // k_motion alone, device events
+  bool reproject(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, const float* prev_color, const float* prev_aov0,
+                 const float* prev_aov1, const glz_reproject_params* params, float* out, Error& err);
+  bool camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err);   // camera_ray() of every pixel, on the device
+  // which surface the feature buffers describe (GLZ_GUIDE_*, glaze_abi.h holds the specification); accumulation goes on
+  bool set_guide_mode(int mode, uint32_t max_bounces, Error& err);
+  int guide_mode(uint32_t* max_bounces_out) const;
+  // the rays of one segment of every pixel's guide chain under the mode and cap in force (glz_debug_guide_chain)
+  bool guide_chain(uint32_t segment, float* origins3, float* dirs3, uint8_t* alive, Error& err);
+
+ private:
+  // what the first-hit pass launches k_motion with, between the trace and whatever reuses the hit buffers
+  struct MotionStep {
+    post::ProjectConstants prev;
+    const float4* prev_o2w;   // device, or null = the scene's own
+    float4* out;              // device
+    hipEvent_t* marks;        // null, or two events recorded around k_motion
+  };
+  struct FirstHitRequest {
+    hipEvent_t* marks = nullptr;                      // null, or 3 events around the trace and what follows it
+    uint32_t last_list = GLZ_GUIDE_MAX_BOUNCES + 1;   // launch_guide_chain's: the chain stops once this list is written
+    const MotionStep* motion = nullptr;               // null, or motion_pass()'s k_motion
+  };
+  // The first-hit pass over the FULL frame on this device, whatever the partition: centre rays, closest hits, attributes -> aov0_ / aov1_.
+  // Recomputed on every request, never cached; its buffers are private (allocated on first use, released by release()).
+  // In GLZ_GUIDE_THROUGH_SPECULAR the chain's kernels take the attribute kernel's place (launch_guide_chain).
+  bool first_hit_pass(const FirstHitRequest& req, Error& err);
+  void post_args(LaunchArgs& a) const;
+  bool motion_pass(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, DeviceBuffer<float4>& prev_o2w, DeviceBuffer<float4>& motion,
+                   Error& err, hipEvent_t* marks = nullptr);
+  GuideLists guide_lists() const { return GuideLists{{guide_o_[0].ptr, guide_o_[1].ptr}, {guide_d_[0].ptr, guide_d_[1].ptr}, guide_count_.ptr}; }
+
+  const Renderer& r_;
+  DeviceBuffer<float4> fh_hit_, aov0_, aov1_, dn_ping_, dn_pong_, dn_out_;
+  DeviceBuffer<uint32_t> fh_inst_, fh_overflow_;
+  glz_denoise_params denoise_ = post::denoise_defaults();
+  glz_despeckle_params despeckle_ = post::despeckle_defaults();
+  bool despeckle_on_ = false;
+  int guide_mode_ = GLZ_GUIDE_FIRST_HIT;
+  uint32_t guide_bounces_ = 4;
+  DeviceBuffer<float4> guide_o_[2], guide_d_[2];   // the chain's ray lists (GuideLists), allocated on first use in GLZ_GUIDE_THROUGH_SPECULAR
+  DeviceBuffer<uint32_t> guide_count_;
+  uint32_t guide_blocks_ = 0;                      // the chain's grid in the last pass
+};
+
+}  // namespace glz

@@ -11,7 +11,6 @@
 #include <mutex>
 #include <thread>
 
-#include "denoise.h"
 #include "rccl_dl.h"
 
 namespace glz {
@@ -213,8 +212,6 @@ Renderer* Renderer::create(Instance* inst, std::shared_ptr<Scene> scene, uint32_
   }
   r->w_ = w;
   r->h_ = h;
-  r->denoise_ = post::denoise_defaults();
-  r->despeckle_ = post::despeckle_defaults();
   r->cfg_.camera = scene->data.camera;
   r->cfg_.exposure = scene->data.meta.exposure;
   host::push_constants(r->cfg_.camera, w, h, r->cfg_.cam.camera2world, r->cfg_.cam.screen2camera);
@@ -719,7 +716,7 @@ bool Renderer::change_resolution(uint32_t w, uint32_t h, Error& err) {
   if (!resize([&] {
         w_ = w;
         h_ = h;
-        release_post();
+        post_.release();
       }, [=](Peer& p, size_t, Error& e) {
         if (!p.r->change_resolution(w, h, e)) return false;
         return !want_frame || hip_ok(p.frame.alloc((size_t)w * h), "alloc peer frame", e);
@@ -1004,11 +1001,12 @@ bool Renderer::settle(Error& err) {
   return wait_idle(err);
 }
 
-// The two tails of every read-out, on the first chain's stream (= the instance's): a full float4 frame to the host, or through the
-// sRGB8 quantiser (into rgba8_) to the host; both wait for the copy.  `what` names the read in an error, `what_sync` the wait's.
-bool Renderer::frame_to_host(const float4* frame, void* out, const char* what, Error& err) {
-  hipStream_t st = chains_[0]->stream;
-  if (!hip_ok(hipMemcpyAsync(out, frame, sizeof(float4) * (size_t)w_ * h_, hipMemcpyDeviceToHost, st), what, err)) return false;
+// The tails of every read-out, on the instance's stream (the first chain's): device arrays to the host, or a float4 frame through the sRGB8
+// quantiser (into rgba8_) to the host; both wait for the copy.  `what` names the read in an error, `what_sync` the wait's.
+bool Renderer::to_host(std::initializer_list<HostCopy> copies, const char* what, Error& err) const {
+  hipStream_t st = inst_->stream;
+  for (const HostCopy& c : copies)
+    if (!hip_ok(hipMemcpyAsync(c.out, c.dev, c.bytes, hipMemcpyDeviceToHost, st), what, err)) return false;
   return hip_ok(hipStreamSynchronize(st), what, err);
 }
 bool Renderer::rgba8_to_host(const float4* frame, uint8_t* out, const char* what, const char* what_sync, Error& err) {
@@ -1031,158 +1029,7 @@ bool Renderer::read_rgba8(uint8_t* out, Error& err) {
   return rgba8_to_host(frame_tmp_.ptr, out, "read rgba8", "read rgba8", err);
 }
 
-// ---- post: first-hit feature buffers and the denoiser ------------------------------------------------------------------------------
-void Renderer::release_post() {
-  fh_hit_.release(); fh_inst_.release(); fh_overflow_.release();
-  aov0_.release(); aov1_.release();
-  dn_ping_.release(); dn_pong_.release(); dn_out_.release();
-  for (int i = 0; i < 2; ++i) { guide_o_[i].release(); guide_d_[i].release(); }
-  guide_count_.release();
-}
-
-// what the post kernels read of LaunchArgs: the scene, the camera, the frame's size and projection, a FULL-frame tile map
-void Renderer::post_args(LaunchArgs& a) const {
-  memset(&a, 0, sizeof(a));
-  a.scene = scene_->dev;
-  a.cam = cfg_.cam;
-  a.frame.scene_size[0] = (float)w_;
-  a.frame.scene_size[1] = (float)h_;
-  a.frame.camera_persp = cfg_.camera.type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
-  a.map = make_tile_map(w_, h_, 0, 1);
-}
-
-bool Renderer::first_hit_pass(const FirstHitRequest& req, Error& err) {
-  hipEvent_t* const marks = req.marks;
-  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  LaunchArgs a;
-  post_args(a);
-  const size_t n = (size_t)w_ * h_;
-  if (!fh_hit_.ptr || !fh_inst_.ptr || !aov0_.ptr || !aov1_.ptr || fh_hit_.count != n) {
-    if (!hip_ok(fh_hit_.alloc(n), "alloc first-hit records", err) || !hip_ok(fh_inst_.alloc(n), "alloc first-hit records", err) ||
-        !hip_ok(aov0_.alloc(n), "alloc feature buffers", err) || !hip_ok(aov1_.alloc(n), "alloc feature buffers", err)) {
-      release_post();   // all or nothing: the next request starts over instead of meeting a buffer that is not there
-      return false;
-    }
-  }
-  const uint32_t blocks = first_hit_grid_blocks(a.map.n_local_pixels);
-  const size_t spill = (size_t)blocks * kTraceBlock * scene_->stack_overflow_depth;   // the scene may have changed since the last pass
-  if (fh_overflow_.ptr == nullptr || fh_overflow_.count != spill)
-    if (!hip_ok(fh_overflow_.alloc(spill), "alloc traversal spill", err)) {
-      fh_overflow_.release();
-      return false;
-    }
-  const bool chain = guide_mode_ == GLZ_GUIDE_THROUGH_SPECULAR;
-  if (chain && (!guide_o_[0].ptr || !guide_o_[1].ptr || !guide_d_[0].ptr || !guide_d_[1].ptr || !guide_count_.ptr || guide_o_[0].count != n)) {
-    if (!hip_ok(alloc_each(n, guide_o_[0], guide_o_[1], guide_d_[0], guide_d_[1]), "alloc guide ray lists", err) ||
-        !hip_ok(guide_count_.alloc(kGuideCountWords), "alloc guide ray lists", err)) {
-      release_post();
-      return false;
-    }
-  }
-  a.st.overflow = fh_overflow_.ptr;
-  a.st.overflow_depth = scene_->stack_overflow_depth;
-  hipStream_t st = inst_->stream;
-  // every record starts as a miss: the attribute kernel follows a record's leaf index into the scene's arrays
-  if (!hip_ok(hipMemsetAsync(fh_hit_.ptr, 0xFF, sizeof(float4) * n, st), "clear first-hit records", err)) return false;
-  if (marks) (void)hipEventRecord(marks[0], st);
-  if (!hip_ok(launch_first_hit(st, a, blocks, fh_hit_.ptr, fh_inst_.ptr), "k_first_hit", err)) return false;
-  if (marks) (void)hipEventRecord(marks[1], st);
-  if (req.motion) {
-    const MotionStep& m = *req.motion;
-    if (m.marks) (void)hipEventRecord(m.marks[0], st);
-    if (!hip_ok(launch_motion(st, a, fh_hit_.ptr, fh_inst_.ptr, m.prev_o2w, m.prev, m.out), "k_motion", err)) return false;
-    if (m.marks) (void)hipEventRecord(m.marks[1], st);
-  }
-  if (chain) {
-    guide_blocks_ = guide_grid_blocks(a.map.n_local_pixels, blocks);
-    if (!hip_ok(launch_guide_chain(st, a, guide_blocks_, guide_bounces_, req.last_list, fh_hit_.ptr, fh_inst_.ptr, guide_lists(), aov0_.ptr, aov1_.ptr), "k_guide_continue", err))
-      return false;
-  } else if (!hip_ok(launch_first_hit_attributes(st, a, fh_hit_.ptr, fh_inst_.ptr, aov0_.ptr, aov1_.ptr), "k_first_hit_attributes", err)) {
-    return false;
-  }
-  if (marks) (void)hipEventRecord(marks[2], st);
-  return true;
-}
-
-bool Renderer::set_guide_mode(int mode, uint32_t max_bounces, Error& err) {
-  if (mode != GLZ_GUIDE_FIRST_HIT && mode != GLZ_GUIDE_THROUGH_SPECULAR) {
-    err.code = GLZ_E_ARG;
-    err.msg = "unknown guide mode (GLZ_GUIDE_FIRST_HIT or GLZ_GUIDE_THROUGH_SPECULAR)";
-    return false;
-  }
-  if (mode == GLZ_GUIDE_THROUGH_SPECULAR && (max_bounces < 1 || max_bounces > GLZ_GUIDE_MAX_BOUNCES)) {
-    err.code = GLZ_E_ARG;
-    err.msg = "guide mode: max_bounces must be 1 .. GLZ_GUIDE_MAX_BOUNCES";
-    return false;
-  }
-  guide_mode_ = mode;
-  if (mode == GLZ_GUIDE_THROUGH_SPECULAR) guide_bounces_ = max_bounces;
-  return true;
-}
-int Renderer::guide_mode(uint32_t* max_bounces_out) const {
-  if (max_bounces_out) *max_bounces_out = guide_bounces_;
-  return guide_mode_;
-}
-
-bool Renderer::guide_chain(uint32_t segment, float* origins3, float* dirs3, uint8_t* alive, Error& err) {
-  const size_t n = (size_t)w_ * h_;
-  if (segment == 0) {   // the camera rays: every pixel has them
-    memset(alive, 1, n);
-    return camera_rays(0.5f, 0.5f, origins3, dirs3, err);
-  }
-  memset(origins3, 0, sizeof(float) * 3 * n);
-  memset(dirs3, 0, sizeof(float) * 3 * n);
-  memset(alive, 0, n);
-  if (guide_mode_ != GLZ_GUIDE_THROUGH_SPECULAR || segment > guide_bounces_ || n == 0) return true;
-  if (!first_hit_pass({nullptr, segment}, err)) return false;   // up to the list of this segment
-  DeviceBuffer<float> d_o, d_d;
-  DeviceBuffer<uint8_t> d_alive;
-  if (!hip_ok(d_o.alloc(3 * n), "alloc", err) || !hip_ok(d_d.alloc(3 * n), "alloc", err) || !hip_ok(d_alive.alloc(n), "alloc", err)) return false;
-  hipStream_t st = inst_->stream;
-  if (!hip_ok(hipMemsetAsync(d_o.ptr, 0, sizeof(float) * 3 * n, st), "guide chain", err) || !hip_ok(hipMemsetAsync(d_d.ptr, 0, sizeof(float) * 3 * n, st), "guide chain", err) ||
-      !hip_ok(hipMemsetAsync(d_alive.ptr, 0, n, st), "guide chain", err))
-    return false;
-  if (!hip_ok(launch_guide_scatter(st, guide_blocks_, guide_lists(), segment, (uint32_t)n, d_o.ptr, d_d.ptr, d_alive.ptr), "k_guide_scatter", err)) return false;
-  if (!hip_ok(hipMemcpyAsync(origins3, d_o.ptr, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, st), "guide chain", err)) return false;
-  if (!hip_ok(hipMemcpyAsync(dirs3, d_d.ptr, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, st), "guide chain", err)) return false;
-  if (!hip_ok(hipMemcpyAsync(alive, d_alive.ptr, n, hipMemcpyDeviceToHost, st), "guide chain", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "guide chain", err);
-}
-
-bool Renderer::read_aov(int which, float* out, Error& err) {
-  if (which != GLZ_AOV_NORMAL_DEPTH && which != GLZ_AOV_ALBEDO_INSTANCE) {
-    err.code = GLZ_E_ARG;
-    err.msg = "unknown feature buffer (GLZ_AOV_NORMAL_DEPTH or GLZ_AOV_ALBEDO_INSTANCE)";
-    return false;
-  }
-  if (!first_hit_pass({}, err)) return false;
-  return frame_to_host(which == GLZ_AOV_NORMAL_DEPTH ? aov0_.ptr : aov1_.ptr, out, "read feature buffer", err);
-}
-
-bool Renderer::camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err) {
-  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  LaunchArgs a;
-  post_args(a);
-  const size_t n = (size_t)w_ * h_ * 3;
-  DeviceBuffer<float> d_o, d_d;
-  if (!hip_ok(d_o.alloc(n), "alloc", err) || !hip_ok(d_d.alloc(n), "alloc", err)) return false;
-  hipStream_t st = inst_->stream;
-  if (!hip_ok(launch_camera_rays(st, a, off_x, off_y, d_o.ptr, d_d.ptr), "k_camera_rays", err)) return false;
-  if (!hip_ok(hipMemcpyAsync(origins3, d_o.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, st), "camera rays", err)) return false;
-  if (!hip_ok(hipMemcpyAsync(dirs3, d_d.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, st), "camera rays", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "camera rays", err);
-}
-
-bool Renderer::ensure_denoise_frames(Error& err) {
-  const size_t n = (size_t)w_ * h_;
-  if (dn_ping_.ptr && dn_pong_.ptr && dn_out_.ptr && dn_out_.count == n) return true;
-  if (hip_ok(dn_ping_.alloc(n), "alloc denoiser frames", err) && hip_ok(dn_pong_.alloc(n), "alloc denoiser frames", err) &&
-      hip_ok(dn_out_.alloc(n), "alloc denoiser frames", err))
-    return true;
-  dn_ping_.release(); dn_pong_.release(); dn_out_.release();   // all or nothing
-  return false;
-}
-
+// ---- post: the reads that need the accumulated frame (everything else is PostStage's own) ------------------------------------------------
 // the readers of the whole frame: under set_partition(world > 1) it is not in this process (with set_devices the partition is over this
 // process's own devices: gather() brings their tiles)
 bool Renderer::frame_is_here(const char* who, Error& err) const {
@@ -1192,151 +1039,30 @@ bool Renderer::frame_is_here(const char* who, Error& err) const {
   return false;
 }
 
-namespace {
-// N device events for one timed run: created together, destroyed with the holder
-template <int N>
-struct Events {
-  hipEvent_t ev[N] = {};
-  bool create(Error& err) {
-    for (auto& e : ev)
-      if (!hip_ok(hipEventCreate(&e), "hipEventCreate", err)) return false;
-    return true;
-  }
-  ~Events() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-}  // namespace
-
 bool Renderer::time_post(float ms[GLZ_POST_TIMING_SLOTS], Error& err) {
-  if (!frame_is_here("time_post", err)) return false;
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  if (!gather(true, frame_tmp_.ptr, err) || !ensure_denoise_frames(err)) return false;
   Events<GLZ_POST_TIMING_SLOTS + 2> t;   // three around the first-hit pass's kernels, 2 + iterations around the filter's
   hipEvent_t* const ev = t.ev;
-  hipStream_t st = chains_[0]->stream;
-  if (!t.create(err) || !first_hit_pass({ev}, err)) return false;
-  if (!hip_ok(launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr, ev + 3), "k_atrous", err)) return false;
-  if (!hip_ok(hipStreamSynchronize(st), "time_post", err)) return false;
+  if (!t.create(err) || !read_post(true, nullptr, nullptr, err, ev)) return false;
   for (int i = 0; i < GLZ_POST_TIMING_SLOTS; ++i) ms[i] = 0.0f;
   (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]);
   (void)hipEventElapsedTime(&ms[1], ev[1], ev[2]);
-  for (uint32_t i = 0; i < 1u + denoise_.iterations; ++i) (void)hipEventElapsedTime(&ms[2 + i], ev[3 + i], ev[4 + i]);
+  for (uint32_t i = 0; i < 1u + post_.denoise().iterations; ++i) (void)hipEventElapsedTime(&ms[2 + i], ev[3 + i], ev[4 + i]);
   return true;
 }
 
-bool Renderer::set_denoise(const glz_denoise_params* p, Error& err) {
-  const glz_denoise_params v = p ? *p : post::denoise_defaults();
-  if (!post::denoise_params_valid(v)) {
-    err.code = GLZ_E_ARG;
-    err.msg = post::kDenoiseParamsMessage;
-    return false;
-  }
-  denoise_ = v;
-  return true;
-}
-
-// read_denoised (filter: the a-trous passes, with the rejection ahead of them when it is enabled) and read_despeckled (the rejection alone)
-bool Renderer::read_post(bool filter, float* rgba32f, uint8_t* rgba8, Error& err) {
-  const char* what = filter ? "read denoised" : "read despeckled";
-  if (!frame_is_here(filter ? "read_denoised" : "read_despeckled", err)) return false;
+// read_denoised (filter: the a-trous passes, with the rejection ahead of them when it is enabled), read_despeckled (the rejection alone) and,
+// with marks, time_post: the one place where the accumulated frame meets the stage
+bool Renderer::read_post(bool filter, float* rgba32f, uint8_t* rgba8, Error& err, hipEvent_t* marks) {
+  const char* what = marks ? "time_post" : filter ? "read denoised" : "read despeckled";
+  if (!frame_is_here(marks ? "time_post" : filter ? "read_denoised" : "read_despeckled", err)) return false;
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   if (!gather(true, frame_tmp_.ptr, err)) return false;   // flushes the pending shadow rays, brings the other devices' tiles
-  if (!first_hit_pass({}, err)) return false;
-  if (!ensure_denoise_frames(err)) return false;
-  hipStream_t st = chains_[0]->stream;   // = the instance stream the first-hit pass ran on
-  const hipError_t launched =
-      filter ? launch_denoise(st, w_, h_, denoise_, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_pong_.ptr, dn_out_.ptr, nullptr, despeckle_on_ ? &despeckle_ : nullptr)
-             : launch_despeckle(st, w_, h_, despeckle_, denoise_.eps_albedo, frame_tmp_.ptr, aov0_.ptr, aov1_.ptr, dn_ping_.ptr, dn_out_.ptr);
-  if (!hip_ok(launched, filter ? "k_atrous" : "k_despeckle", err)) return false;
-  if (rgba32f && !frame_to_host(dn_out_.ptr, rgba32f, what, err)) return false;
-  if (rgba8 && !rgba8_to_host(dn_out_.ptr, rgba8, what, what, err)) return false;
-  return hip_ok(hipStreamSynchronize(st), what, err);   // with neither output the filter has still run when this returns
-}
-
-bool Renderer::set_despeckle(bool enabled, const glz_despeckle_params* p, Error& err) {
-  const glz_despeckle_params v = p ? *p : post::despeckle_defaults();
-  if (!post::despeckle_params_valid(v)) {
-    err.code = GLZ_E_ARG;
-    err.msg = post::kDespeckleParamsMessage;
-    return false;
-  }
-  despeckle_ = v;
-  despeckle_on_ = enabled;
-  return true;
-}
-int Renderer::despeckle(glz_despeckle_params* out) const {
-  if (out) *out = despeckle_;
-  return despeckle_on_ ? 1 : 0;
-}
-
-// the checks of read_motion and reproject, the upload of the caller's matrices, then the first-hit pass with k_motion in it
-bool Renderer::motion_pass(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, DeviceBuffer<float4>& prev_o2w,
-                           DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks) {
-  if (!prev_camera) {
-    err.code = GLZ_E_ARG;
-    err.msg = "motion: the previous camera is null";
-    return false;
-  }
-  if (prev_transforms && n_prev != scene_->data.transforms.size()) {
-    err.code = GLZ_E_ARG;
-    err.msg = "motion: the previous transforms must be as many as the scene's (instances index transforms)";
-    return false;
-  }
-  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  hipStream_t st = inst_->stream;
-  MotionStep step;
-  host::project_constants(*prev_camera, w_, h_, step.prev.world2camera, step.prev.camera2screen);
-  step.prev.persp = prev_camera->type == GLZ_CAMERA_PERSPECTIVE ? 1u : 0u;
-  step.prev_o2w = nullptr;
-  if (prev_transforms && n_prev > 0) {
-    static_assert(sizeof(glz_transform) == 4 * sizeof(float4), "one previous matrix is four float4");
-    if (!hip_ok(prev_o2w.upload(reinterpret_cast<const float4*>(prev_transforms), 4 * (size_t)n_prev, st), "upload previous transforms", err)) return false;
-    step.prev_o2w = prev_o2w.ptr;
-  }
-  if (!hip_ok(motion.alloc((size_t)w_ * h_), "alloc motion plane", err)) return false;
-  step.out = motion.ptr;
-  step.marks = marks;
-  FirstHitRequest pass;
-  pass.motion = &step;
-  return first_hit_pass(pass, err);
-}
-
-bool Renderer::read_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* out, Error& err) {
-  DeviceBuffer<float4> prev_o2w, motion;
-  if (!motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err)) return false;
-  return frame_to_host(motion.ptr, out, "read motion", err);
-}
-
-bool Renderer::time_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* kernel_ms, Error& err) {
-  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  Events<2> t;
-  DeviceBuffer<float4> prev_o2w, motion;
-  if (!t.create(err) || !motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err, t.ev)) return false;
-  if (!hip_ok(hipStreamSynchronize(inst_->stream), "time_motion", err)) return false;
-  (void)hipEventElapsedTime(kernel_ms, t.ev[0], t.ev[1]);
-  return true;
-}
-
-bool Renderer::reproject(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, const float* prev_color, const float* prev_aov0,
-                         const float* prev_aov1, const glz_reproject_params* params, float* out, Error& err) {
-  const glz_reproject_params P = params ? *params : post::reproject_defaults();
-  if (!post::reproject_params_valid(P)) {
-    err.code = GLZ_E_ARG;
-    err.msg = post::kReprojectParamsMessage;
-    return false;
-  }
-  DeviceBuffer<float4> prev_o2w, motion, color, plane0, plane1, result;
-  if (!motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err)) return false;
-  const size_t n = (size_t)w_ * h_;
-  hipStream_t st = inst_->stream;
-  if (!hip_ok(color.upload(reinterpret_cast<const float4*>(prev_color), n, st), "upload previous frame", err) ||
-      !hip_ok(plane0.upload(reinterpret_cast<const float4*>(prev_aov0), n, st), "upload previous frame", err) ||
-      !hip_ok(plane1.upload(reinterpret_cast<const float4*>(prev_aov1), n, st), "upload previous frame", err) || !hip_ok(result.alloc(n), "alloc reprojected frame", err))
-    return false;
-  if (!hip_ok(launch_reproject(st, w_, h_, P, motion.ptr, color.ptr, plane0.ptr, plane1.ptr, result.ptr), "k_reproject", err)) return false;
-  return frame_to_host(result.ptr, out, "reproject", err);
+  const float4* out = post_.filtered(frame_tmp_.ptr, filter, marks, err);
+  if (!out) return false;
+  if (rgba32f && !frame_to_host(out, rgba32f, what, err)) return false;
+  if (rgba8 && !rgba8_to_host(out, rgba8, what, what, err)) return false;
+  return hip_ok(hipStreamSynchronize(inst_->stream), what, err);   // with neither output the filter has still run when this returns
 }
 
 bool Renderer::set_texture_lod(int mode, Error& err) {

@@ -2,11 +2,13 @@
 // constants, accumulation buffers, tile partition for one-process-per-GPU jobs.
 #pragma once
 #include <cstdlib>
+#include <initializer_list>
 #include <memory>
 #include <vector>
 
 #include "host_math.h"
 #include "kernels.h"
+#include "post_stage.h"
 #include "scene.h"
 #include "tile_map.h"
 
@@ -33,26 +35,10 @@ class Renderer {
   bool step(uint32_t n, Error& err);
   bool read_rgba8(uint8_t* out, Error& err);
   bool read_frame(bool result, float* out, Error& err);
-  // ---- post: first-hit feature buffers and the denoiser (kernels_post.hip) ----
-  bool read_aov(int which, float* out, Error& err);                   // runs the first-hit pass; GLZ_AOV_*
-  bool set_denoise(const glz_denoise_params* p, Error& err);          // null = defaults; accumulation goes on
+  // ---- post (post_stage.h): everything that needs no accumulated frame is called on post() itself; these gather the result first ----
+  PostStage& post() { return post_; }
   bool read_denoised(float* rgba32f, uint8_t* rgba8, Error& err) { return read_post(true, rgba32f, rgba8, err); }     // gather + first-hit pass + filter; either output may be null
-  // firefly rejection (glz_despeckle_params): enabled = ahead of the filter in read_denoised; null = defaults; accumulation goes on
-  bool set_despeckle(bool enabled, const glz_despeckle_params* p, Error& err);
-  int despeckle(glz_despeckle_params* out) const;                      // the enabled flag
   bool read_despeckled(float* rgba32f, uint8_t* rgba8, Error& err) { return read_post(false, rgba32f, rgba8, err); }    // gather + first-hit pass + demodulation + rejection; no filter pass
-  // motion vectors and history reprojection (glz_reproject_params; reproject.h): the first-hit trace and k_motion against the caller's
-  // previous camera and transforms (null = the scene's own), then, for reproject, k_reproject on the three uploaded previous frames
-  bool read_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* out, Error& err);
-  bool time_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* kernel_ms, Error& err);   // k_motion alone, device events
-  bool reproject(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, const float* prev_color, const float* prev_aov0,
-                 const float* prev_aov1, const glz_reproject_params* params, float* out, Error& err);
-  bool camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err);   // camera_ray() of every pixel, on the device
-  // which surface the feature buffers describe (GLZ_GUIDE_*, glaze_abi.h holds the specification); accumulation goes on
-  bool set_guide_mode(int mode, uint32_t max_bounces, Error& err);
-  int guide_mode(uint32_t* max_bounces_out) const;
-  // the rays of one segment of every pixel's guide chain under the mode and cap in force (glz_debug_guide_chain)
-  bool guide_chain(uint32_t segment, float* origins3, float* dirs3, uint8_t* alive, Error& err);
   // one run of the post stages between device events: ms of {first-hit trace, attributes, demodulation, pass 0 .. iterations - 1} (unused = 0)
   bool time_post(float ms[GLZ_POST_TIMING_SLOTS], Error& err);
 
@@ -93,6 +79,16 @@ class Renderer {
   Scene* scene() const { return scene_.get(); }
   uint32_t width() const { return w_; }
   uint32_t height() const { return h_; }
+  const CameraConsts& camera_consts() const { return cfg_.cam; }
+  bool perspective() const { return cfg_.camera.type == GLZ_CAMERA_PERSPECTIVE; }
+  // The tail of every read-out: device arrays to the host on the instance's stream, then the wait for them.  `what` names the read in an error.
+  struct HostCopy {
+    void* out;
+    const void* dev;
+    size_t bytes;
+  };
+  bool to_host(std::initializer_list<HostCopy> copies, const char* what, Error& err) const;
+  bool frame_to_host(const float4* frame, void* out, const char* what, Error& err) const { return to_host({{out, frame, sizeof(float4) * (size_t)w_ * h_}}, what, err); }
 
  private:
   Renderer() = default;
@@ -106,15 +102,14 @@ class Renderer {
   bool gather(bool result, float4* dst, Error& err, bool zero_first = true);
   template <class A, class F> bool resize(A apply, F on_peer, Error& err);
   template <class U> bool update_scene(U update, Error& err);
-  bool frame_to_host(const float4* frame, void* out, const char* what, Error& err);
   bool rgba8_to_host(const float4* frame, uint8_t* out, const char* what, const char* what_sync, Error& err);
 
   Instance* inst_ = nullptr;
   std::shared_ptr<Scene> scene_;   // shared with the glz_scene handle it came from (info / debug hooks stay valid)
   uint32_t w_ = 0, h_ = 0;
   // What every device of set_devices must agree on to render one image: a new peer takes it over by one assignment, the setters
-  // forward every change.  Deliberately not in here: the partition (rank_, world_: each device has its own), the denoiser's and the
-  // rejection's parameters and the post buffers (the post stage runs on this device only, on the gathered frame), and everything allocate() derives.
+  // forward every change.  Deliberately not in here: the partition (rank_, world_: each device has its own), the post stage's
+  // parameters and buffers (PostStage: it runs on this device only, on the gathered frame), and everything allocate() derives.
   struct Settings {
     int integrator = GLZ_PATH_TRACE;
     uint32_t pt_steps = 6;   // PT_STEPS, raytrace_structures.rs:87
@@ -205,40 +200,10 @@ class Renderer {
   const struct Rccl* rccl(Error& err) const;   // the loaded library, if this renderer has its communicators
   bool step_local(uint32_t n, Error& err);
 
-  // what the first-hit pass launches k_motion with, between the trace and whatever reuses the hit buffers
-  struct MotionStep {
-    post::ProjectConstants prev;
-    const float4* prev_o2w;   // device, or null = the scene's own
-    float4* out;              // device
-    hipEvent_t* marks;        // null, or two events recorded around k_motion
-  };
-  struct FirstHitRequest {
-    hipEvent_t* marks = nullptr;                      // null, or 3 events around the trace and what follows it
-    uint32_t last_list = GLZ_GUIDE_MAX_BOUNCES + 1;   // launch_guide_chain's: the chain stops once this list is written
-    const MotionStep* motion = nullptr;               // null, or motion_pass()'s k_motion
-  };
-  // The first-hit pass over the FULL frame on this device, whatever the partition: centre rays, closest hits, attributes -> aov0_ / aov1_.
-  // Recomputed on every request, never cached; its buffers are private (allocated on first use, released by change_resolution).
-  // In GLZ_GUIDE_THROUGH_SPECULAR the chain's kernels take the attribute kernel's place (launch_guide_chain).
-  bool first_hit_pass(const FirstHitRequest& req, Error& err);
-  void post_args(LaunchArgs& a) const;
   bool frame_is_here(const char* who, Error& err) const;                     // false, with the error set, for one rank of a process partition
-  bool read_post(bool filter, float* rgba32f, uint8_t* rgba8, Error& err);   // read_denoised (filter) / read_despeckled
-  bool motion_pass(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, DeviceBuffer<float4>& prev_o2w, DeviceBuffer<float4>& motion,
-                   Error& err, hipEvent_t* marks = nullptr);
-  void release_post();
-  bool ensure_denoise_frames(Error& err);
-  DeviceBuffer<float4> fh_hit_, aov0_, aov1_, dn_ping_, dn_pong_, dn_out_;
-  DeviceBuffer<uint32_t> fh_inst_, fh_overflow_;
-  glz_denoise_params denoise_;   // set in create()
-  glz_despeckle_params despeckle_;   // set in create()
-  bool despeckle_on_ = false;
-  int guide_mode_ = GLZ_GUIDE_FIRST_HIT;
-  uint32_t guide_bounces_ = 4;
-  DeviceBuffer<float4> guide_o_[2], guide_d_[2];   // the chain's ray lists (GuideLists), allocated on first use in GLZ_GUIDE_THROUGH_SPECULAR
-  DeviceBuffer<uint32_t> guide_count_;
-  uint32_t guide_blocks_ = 0;                      // the chain's grid in the last pass
-  GuideLists guide_lists() const { return GuideLists{{guide_o_[0].ptr, guide_o_[1].ptr}, {guide_d_[0].ptr, guide_d_[1].ptr}, guide_count_.ptr}; }
+  // read_denoised (filter) / read_despeckled / time_post (filter, marks: PostStage::filtered's events)
+  bool read_post(bool filter, float* rgba32f, uint8_t* rgba8, Error& err, hipEvent_t* marks = nullptr);
+  PostStage post_{*this};
 
   DeviceBuffer<float4> frame_tmp_;
   DeviceBuffer<uchar4> rgba8_;

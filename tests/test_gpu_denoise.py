@@ -13,7 +13,8 @@ from PIL import Image
 
 import glaze_amd
 from glaze_amd import abi
-from glaze_amd.scenes import atrium_scene, cube_scene, forest_scene
+from glaze_amd.scene_desc import _clone
+from glaze_amd.scenes import atrium_scene, cube_scene, forest_scene, mirror_room_scene
 from oracle.pyoracle import OracleScene
 
 from conftest import MATTEST
@@ -213,6 +214,64 @@ def test_first_hit_pass_does_not_depend_on_the_render_state(instance, monkeypatc
     nd, ai = empty.read_aov(0), empty.read_aov(1)
     assert np.isposinf(nd[..., 3]).all() and (nd[..., :3] == 0).all() and (ai[..., :3] == 1).all()
     assert (bits(ai[..., 3]) == 0xFFFFFFFF).all()
+
+
+def test_post_buffers_follow_scene_resolution_guide_mode_and_devices(instance, monkeypatch):
+    """The lifetime of the post stage's buffers: ONE renderer driven through new scenes, resolutions, guide modes and device counts must
+    read, in every state, the bits a fresh renderer created directly in that state reads."""
+    monkeypatch.setenv("GLAZE_MULTI_LOOPBACK", "1")
+    descs = {"cube": cube_scene(), "room": mirror_room_scene(), "atrium": small_atrium()}
+
+    def scene(name):                                                            # a renderer takes its scene over: one per use
+        return glaze_amd.RayTraceScene.from_desc(instance, descs[name])
+
+    # the traversal spill of the first-hit pass is sized by the scene (stack_overflow_depth: 3 * depth + 2 against the 17 entries kept in
+    # LDS), not only by the frame: the cube needs the minimum, the atrium more
+    assert scene("cube").info().bvh_depth <= 5 and scene("atrium").info().bvh_depth >= 6
+
+    def sideways(cam):
+        c = _clone(cam)
+        c.position[:] = [a + b for a, b in zip(cam.position[:], (0.3, 0.0, 0.0))]
+        c.target[:] = [a + b for a, b in zip(cam.target[:], (0.3, 0.0, 0.0))]
+        return c
+
+    reads = {"aov0": lambda r, desc: (r.read_aov(0),), "aov1": lambda r, desc: (r.read_aov(1),),
+             "denoised": lambda r, desc: (r.read_denoised(),), "despeckled": lambda r, desc: (r.read_despeckled(),),
+             "motion": lambda r, desc: (r.read_motion(sideways(desc.camera)),), "chain": lambda r, desc: r.debug_guide_chain(1)}
+
+    def fresh(name, w, h, guide):
+        r = glaze_amd.RayTraceRenderer.new(instance, scene(name), w, h)
+        r.set_guide_mode(*guide)
+        return r
+
+    def check(state, ren, ref, name, names):
+        for r in (ren, ref):
+            r.set_seed(17)
+            r.set_depth(3)
+            r.step(2)
+        for read in names:
+            got, want = reads[read](ren, descs[name]), reads[read](ref, descs[name])
+            assert len(got) == len(want)
+            for a, b in zip(got, want):
+                assert a.shape == b.shape and np.array_equal(bits(a), bits(b)), (state, read)
+
+    first_hit, through = ("first_hit",), ("through_specular", 2)
+    planes = ("aov0", "aov1")
+    ren = glaze_amd.RayTraceRenderer.new(instance, scene("cube"), 70, 40)
+    check(1, ren, fresh("cube", 70, 40, first_hit), "cube", planes)
+    ren.set_guide_mode(*through)
+    ren.change_scene(scene("room"))
+    check(2, ren, fresh("room", 70, 40, through), "room", planes + ("denoised",))
+    ren.change_resolution(33, 17)                                               # every buffer shrinks; neither side is a multiple of 8
+    check(3, ren, fresh("room", 33, 17, through), "room", planes + ("denoised", "despeckled", "motion", "chain"))
+    assert ren.debug_guide_chain(1)[2].any()                                    # the mirror is in view: the chain's lists are in use
+    ren.change_resolution(130, 70)                                              # more than one 64-pixel tile each way
+    ren.set_guide_mode(*first_hit)
+    ren.change_scene(scene("atrium"))
+    one_device = fresh("atrium", 130, 70, first_hit)
+    check(4, ren, one_device, "atrium", planes + ("denoised", "motion"))
+    ren.set_devices([instance.device] * 2)                                      # the stage runs on device 0 after the exchange
+    check(5, ren, one_device, "atrium", ("denoised",))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
