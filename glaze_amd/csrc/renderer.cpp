@@ -3,174 +3,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
-#include <functional>
-#include <mutex>
-#include <thread>
-
-#include "rccl_dl.h"
 
 namespace glz {
-
-namespace {
-// One host thread per additional GPU: it enqueues that device's launches while the caller's thread enqueues its own (two
-// kernels per launch and device; at 1/8 of a 1080p frame per GPU a launch lasts ~0.17 ms, so eight devices fed from one
-// thread would be bound by the host).  One task at a time: post(), then wait().
-class Worker {
- public:
-  Worker() : th_([this] { loop(); }) {}
-  ~Worker() { stop(); }
-  void post(std::function<void()> f) {
-    std::lock_guard<std::mutex> l(m_);
-    task_ = std::move(f);
-    has_ = true;
-    done_ = false;
-    cv_.notify_all();
-  }
-  void wait() {
-    std::unique_lock<std::mutex> l(m_);
-    cv_.wait(l, [&] { return done_; });
-  }
-  void stop() {
-    {
-      std::lock_guard<std::mutex> l(m_);
-      if (quit_) return;
-      quit_ = true;
-      cv_.notify_all();
-    }
-    th_.join();
-  }
-
- private:
-  void loop() {
-    std::unique_lock<std::mutex> l(m_);
-    for (;;) {
-      cv_.wait(l, [&] { return has_ || quit_; });
-      if (!has_) return;
-      std::function<void()> f = std::move(task_);
-      has_ = false;
-      l.unlock();
-      f();
-      l.lock();
-      done_ = true;
-      cv_.notify_all();
-    }
-  }
-  std::mutex m_;
-  std::condition_variable cv_;
-  std::function<void()> task_;
-  bool has_ = false, done_ = true, quit_ = false;
-  std::thread th_;   // last member: the thread starts once everything above exists
-};
-}  // namespace
-
-// Another GPU of this process: its own instance (device + stream), a replica of the scene, a renderer for the tiles
-// t % n == rank, the frame it contributes to the reduce, and the host thread that drives it.
-struct Renderer::Peer {
-  std::unique_ptr<Instance> inst;
-  std::unique_ptr<Renderer> r;
-  DeviceBuffer<float4> frame;
-  hipEvent_t sent = nullptr;   // peer-copy exchange: this device's tiles have left (recorded on its stream, awaited by device 0's)
-  Worker worker;
-  size_t n_pixels() const;                    // tile slots of all its chains
-  const float4* packed(bool result) const;    // where its packed tiles travel from
-  // a copy of `src` built on this device, in the shape the root's scene HAS (builder, pair leaves, flattened or two levels), not what
-  // the environment of this thread would choose
-  std::shared_ptr<Scene> replica_of(const Scene& src, const Instance& src_inst, Error& e) {
-    inst->copy_build_options(src_inst);
-    if (src.info.as_levels) inst->as_levels = (int)src.info.as_levels;
-    SceneData copy = src.data;
-    return std::shared_ptr<Scene>(Scene::create(inst.get(), std::move(copy), e));
-  }
-  ~Peer() {
-    worker.stop();
-    if (inst) (void)hipSetDevice(inst->device);
-    if (sent) (void)hipEventDestroy(sent);
-    r.reset();
-    frame.release();
-  }
-};
-// What the peers' tasks write their outcome into.  The tasks hold pointers into it, so it must not go away while one of them
-// runs: if the poster leaves early (an exception out of its local share of the work), the destructor waits for the workers.
-struct Renderer::Pending {
-  std::vector<Error> errs;
-  std::vector<char> ok;
-  Renderer* posted_on = nullptr;
-  Pending() = default;
-  Pending(const Pending&) = delete;
-  Pending& operator=(const Pending&) = delete;
-  ~Pending() {
-    if (posted_on)
-      for (auto& peer : posted_on->peers_) peer->worker.wait();
-  }
-};
-
-// The calling thread is back on this renderer's device when the scope ends, however it ends: for code that visits the peers' devices
-// on the calling thread (the exchange, set_devices).  Tasks posted to the peers run on their own threads and never move the caller.
-struct Renderer::OnOwnDevice {
-  const Renderer& r;
-  ~OnOwnDevice() { (void)hipSetDevice(r.inst_->device); }
-};
-
-// f(Peer&, size_t index, Error&) -> bool on every peer's thread; f is copied into the tasks, whatever it refers to must outlive join_all()
-template <class F>
-void Renderer::post_all(F f, Pending& p) {
-  p.errs.assign(peers_.size(), Error());
-  p.ok.assign(peers_.size(), 1);
-  p.posted_on = this;
-  for (size_t i = 0; i < peers_.size(); ++i) {
-    Peer* peer = peers_[i].get();
-    Error* e = &p.errs[i];
-    char* ok = &p.ok[i];
-    peer->worker.post([=] {
-      try {
-        *ok = f(*peer, i, *e) ? 1 : 0;
-      } catch (const std::exception& ex) {
-        e->code = GLZ_E_IO;
-        e->msg = ex.what();
-        *ok = 0;
-      } catch (...) {   // nothing may leave a peer's thread: that would be std::terminate
-        e->code = GLZ_E_IO;
-        e->msg = "unknown exception on a device thread";
-        *ok = 0;
-      }
-    });
-  }
-}
-bool Renderer::join_all(Pending& p, Error& err) {
-  for (auto& peer : peers_) peer->worker.wait();
-  p.posted_on = nullptr;
-  for (size_t i = 0; i < p.ok.size(); ++i)
-    if (!p.ok[i]) {
-      err = p.errs[i];
-      err.msg = "device " + std::to_string(peers_[i]->inst->device) + ": " + err.msg;
-      return false;
-    }
-  return true;
-}
-// The peers do f on their threads while this thread does g(err) -> bool; then the join.  The first error wins, this thread's before a
-// peer's.  The one place that answers for the calling thread's device: it is inst_->device afterwards, success or failure.
-template <class F, class G>
-bool Renderer::with_peers(F f, G g, Error& err) {
-  if (peers_.empty()) return g(err);
-  OnOwnDevice back{*this};
-  Pending p;
-  post_all(f, p);
-  bool ok = g(err);
-  Error pe;
-  if (!join_all(p, pe) && ok) {
-    err = pe;
-    ok = false;
-  }
-  return ok;
-}
-template <class F>
-bool Renderer::forward(F f, Error& err) {
-  return with_peers(f, [](Error&) { return true; }, err);
-}
 
 namespace {
 // Kernel boundaries are timed with HIP events on one launch of every `stride` (Renderer::event_stride), at a pseudo-random place
@@ -231,21 +67,8 @@ void Renderer::release_chains() {
   chains_.clear();
 }
 
-void Renderer::release_peers() {
-  if (!comms_.empty()) {
-    std::string why;
-    if (const Rccl* nc = Rccl::get(why))
-      for (void* c : comms_)
-        if (c) (void)nc->CommDestroy(static_cast<ncclComm_t>(c));
-    comms_.clear();
-  }
-  peers_.clear();
-  loopback_ = false;
-  if (inst_) (void)hipSetDevice(inst_->device);
-}
-
 Renderer::~Renderer() {
-  release_peers();
+  group_.release();   // the peers first, each on its own device
   if (inst_) (void)hipSetDevice(inst_->device);
   release_chains();
 }
@@ -573,14 +396,13 @@ bool Renderer::run_launches(uint32_t n, Error& err) {
   return true;
 }
 
-// A change of something the buffers are sized by: everything enqueued drains, `apply` changes the setting, this device reallocates,
-// then every peer does the same through `on_peer`.
-template <class A, class F>
-bool Renderer::resize(A apply, F on_peer, Error& err) {
+// A change of something the buffers are sized by: everything enqueued drains, `apply` changes the setting, this device reallocates;
+// the caller then has every peer do the same.
+template <class A>
+bool Renderer::resize(A apply, Error& err) {
   if (!wait_idle(err)) return false;
   apply();
-  if (!allocate(err)) return false;
-  return forward(on_peer, err);
+  return allocate(err);
 }
 
 bool Renderer::set_launch_mode(int mode, Error& err) {
@@ -589,7 +411,7 @@ bool Renderer::set_launch_mode(int mode, Error& err) {
     err.msg = "launch mode must be 0 (automatic), 1 (two kernels per launch) or 2 (per-wave launch loop)";
     return false;
   }
-  return resize([&] { cfg_.launch_mode = mode; }, [=](Peer& p, size_t, Error& e) { return p.r->set_launch_mode(mode, e); }, err);
+  return resize([&] { cfg_.launch_mode = mode; }, err) && group_.forward([=](Renderer& p, Error& e) { return p.set_launch_mode(mode, e); }, err);
 }
 
 bool Renderer::set_node_width(int width, Error& err) {
@@ -598,7 +420,7 @@ bool Renderer::set_node_width(int width, Error& err) {
     err.msg = "node width must be 0 (automatic), 4 or 8";
     return false;
   }
-  return resize([&] { cfg_.node_width = width; }, [=](Peer& p, size_t, Error& e) { return p.r->set_node_width(width, e); }, err);
+  return resize([&] { cfg_.node_width = width; }, err) && group_.forward([=](Renderer& p, Error& e) { return p.set_node_width(width, e); }, err);
 }
 
 bool Renderer::get_stats(glz_render_stats* out, Error& err) {
@@ -644,34 +466,13 @@ bool Renderer::get_stats(glz_render_stats* out, Error& err) {
   out->alpha_tex_bytes = c.trace_tex[1];
   out->light_samples = c.shade_tex[2];
   out->sky_samples = c.shade_tex[3];
-  // other GPUs of this process: work counters add up, kernel times overlap (the slowest device is what the job waits for)
-  if (!peers_.empty()) {
-    std::vector<glz_render_stats> ps(peers_.size());
-    glz_render_stats* base = ps.data();
-    if (!forward([=](Peer& p, size_t i, Error& e) { return p.r->get_stats(base + i, e); }, err)) return false;
-    for (const glz_render_stats& q : ps) {
-      out->samples += q.samples;
-      out->trace_closest_ms = std::max(out->trace_closest_ms, q.trace_closest_ms);
-      out->shade_ms = std::max(out->shade_ms, q.shade_ms);
-      out->trace_shadow_ms = std::max(out->trace_shadow_ms, q.trace_shadow_ms);
-      out->other_ms = std::max(out->other_ms, q.other_ms);
-      out->closest_rays += q.closest_rays; out->shadow_rays += q.shadow_rays;
-      out->closest_nodes += q.closest_nodes; out->closest_tris += q.closest_tris;
-      out->shadow_nodes += q.shadow_nodes; out->shadow_tris += q.shadow_tris;
-      out->hits += q.hits; out->fresh_paths += q.fresh_paths;
-      for (int i = 0; i < 12; ++i) out->phase[i] += q.phase[i];
-      out->tex_fetches += q.tex_fetches; out->tex_bytes += q.tex_bytes; out->alpha_tex_bytes += q.alpha_tex_bytes;
-      out->light_samples += q.light_samples; out->sky_samples += q.sky_samples;
-    }
-    out->render_ms = out->trace_closest_ms + out->shade_ms + out->trace_shadow_ms + out->other_ms;
-  }
-  return true;
+  return group_.add_stats(out, err);
 }
 
 void Renderer::enable_counters(int flags) {
   cfg_.counting = (flags & 1) != 0;
   cfg_.profile_kernels = (flags & 2) != 0;
-  for (auto& p : peers_) p->r->enable_counters(flags);
+  group_.each([=](Renderer& p) { p.enable_counters(flags); });
 }
 
 bool Renderer::set_integrator(int integrator, Error& err) {
@@ -684,12 +485,12 @@ bool Renderer::set_integrator(int integrator, Error& err) {
     cfg_.integrator = integrator;
     request_new_frame_ = true;
   }
-  return forward([=](Peer& p, size_t, Error& e) { return p.r->set_integrator(integrator, e); }, err);
+  return group_.forward([=](Renderer& p, Error& e) { return p.set_integrator(integrator, e); }, err);
 }
 
 bool Renderer::set_exposure(float e) {
   if (e >= 0.0f) cfg_.exposure = e;   // raytracer.rs:186-193: no restart
-  for (auto& p : peers_) p->r->set_exposure(e);
+  group_.each([=](Renderer& p) { p.set_exposure(e); });
   return true;
 }
 
@@ -703,7 +504,7 @@ bool Renderer::update_camera(const glz_camera& c, Error& err) {
   host::push_constants(cfg_.camera, w_, h_, cfg_.cam.camera2world, cfg_.cam.screen2camera);
   request_new_frame_ = true;
   const glz_camera cam = c;
-  return forward([=](Peer& p, size_t, Error& e) { return p.r->update_camera(cam, e); }, err);
+  return group_.forward([=](Renderer& p, Error& e) { return p.update_camera(cam, e); }, err);
 }
 
 bool Renderer::change_resolution(uint32_t w, uint32_t h, Error& err) {
@@ -712,15 +513,11 @@ bool Renderer::change_resolution(uint32_t w, uint32_t h, Error& err) {
     err.msg = "resolution must be non-zero";
     return false;
   }
-  const bool want_frame = !loopback_ && exchange_ == kExchangeReduce;
   if (!resize([&] {
         w_ = w;
         h_ = h;
         post_.release();
-      }, [=](Peer& p, size_t, Error& e) {
-        if (!p.r->change_resolution(w, h, e)) return false;
-        return !want_frame || hip_ok(p.frame.alloc((size_t)w * h), "alloc peer frame", e);
-      }, err))
+      }, err) || !group_.change_resolution(w, h, err))
     return false;
   return update_camera(cfg_.camera, err);   // raytracer.rs:297
 }
@@ -732,15 +529,10 @@ bool Renderer::change_scene(std::shared_ptr<Scene> scene, Error& err) {
     return false;
   }
   // the other GPUs of this process get replicas of the new scene, in the shape (flattened / two levels) this device built
-  const Scene* src = scene.get();
-  const Instance* src_inst = scene->instance ? scene->instance : inst_;
   if (!resize([&] {
         scene_ = scene;
         cfg_.exposure = scene->data.meta.exposure;
-      }, [=](Peer& p, size_t, Error& e) {
-        std::shared_ptr<Scene> replica = p.replica_of(*src, *src_inst, e);
-        return replica && p.r->change_scene(replica, e);
-      }, err))
+      }, err) || !group_.change_scene(*scene, scene->instance ? *scene->instance : *inst_, err))
     return false;
   return update_camera(scene->data.camera, err);   // raytracer.rs:246-247
 }
@@ -761,14 +553,14 @@ bool Renderer::update_scene(U update, Error& err) {
 bool Renderer::update_materials_and_lights(const glz_material* m, uint32_t nm, const glz_light* l, uint32_t nl, const glz_texture* t, uint32_t nt,
                                            Error& err) {
   if (!update_scene([&] { return scene_->update_materials_and_lights(m, nm, l, nl, t, nt, err); }, err)) return false;   // raytracer.rs:325
-  return forward([=](Peer& p, size_t, Error& e) { return p.r->update_materials_and_lights(m, nm, l, nl, t, nt, e); }, err);
+  return group_.forward([=](Renderer& p, Error& e) { return p.update_materials_and_lights(m, nm, l, nl, t, nt, e); }, err);
 }
 
 // Moves the instances: the scene's structure is rebuilt for the new transforms (the scene object changes, so every renderer that
 // shares it sees the move), accumulation restarts, and every other device of set_devices updates its replica the same way.
 bool Renderer::update_transforms(const glz_transform* t, uint32_t n, Error& err) {
   if (!update_scene([&] { return scene_->update_transforms(t, n, err); }, err)) return false;
-  return forward([=](Peer& p, size_t, Error& e) { return p.r->update_transforms(t, n, e); }, err);
+  return group_.forward([=](Renderer& p, Error& e) { return p.update_transforms(t, n, e); }, err);
 }
 
 // raytracer.rs:328-356.  The reference rebuilds descriptors, pipeline and SBT and leaves the accumulation alone; here the
@@ -776,7 +568,7 @@ bool Renderer::update_transforms(const glz_transform* t, uint32_t n, Error& err)
 bool Renderer::refresh_binded_textures(const glz_texture* t, uint32_t nt, Error& err) {
   if (!wait_idle(err)) return false;
   if (!scene_->refresh_textures(t, nt, err)) return false;
-  return forward([=](Peer& p, size_t, Error& e) { return p.r->refresh_binded_textures(t, nt, e); }, err);
+  return group_.forward([=](Renderer& p, Error& e) { return p.refresh_binded_textures(t, nt, e); }, err);
 }
 
 // this device's half of wait_idle: the pending shadow rays of every chain go out, then every chain's stream drains
@@ -790,12 +582,12 @@ bool Renderer::wait_idle_local(const char* what, Error& err) {
 }
 
 bool Renderer::wait_idle(Error& err) {
-  return with_peers([](Peer& p, size_t, Error& e) { return p.r->wait_idle(e); }, [this](Error& e) { return wait_idle_local("wait_idle", e); }, err);
+  return group_.with_peers([](Renderer& p, Error& e) { return p.wait_idle(e); }, [this](Error& e) { return wait_idle_local("wait_idle", e); }, err);
 }
 
 bool Renderer::restart() {
   request_new_frame_ = true;
-  for (auto& p : peers_) p->r->restart();
+  group_.each([](Renderer& p) { p.restart(); });
   return true;
 }
 
@@ -807,7 +599,7 @@ bool Renderer::step_local(uint32_t n, Error& err) {
 // Every device enqueues the same n launches (same seed stream, same jitter sequence) for its own tiles; the peers' host
 // threads work while this thread enqueues the local share.
 bool Renderer::step(uint32_t n, Error& err) {
-  return with_peers([=](Peer& p, size_t, Error& e) { return p.r->step_local(n, e); }, [=](Error& e) { return step_local(n, e); }, err);
+  return group_.with_peers([=](Renderer& p, Error& e) { return p.step_local(n, e); }, [=](Error& e) { return step_local(n, e); }, err);
 }
 
 // draw (raytracer.rs:615-687)
@@ -824,11 +616,11 @@ bool Renderer::draw(size_t spp, void (*cb)(void*), void* user, uint8_t* rgba8_ou
     // any device in the per-wave launch loop wants long batches (a root over the residency limit must not hold its peers to one
     // sample per call); with a callback -- a progress bar, a cancel hook -- at most four samples go out between two calls of it
     bool any_path = use_path();
-    for (const auto& p : peers_) any_path = any_path || p->r->use_path();
+    group_.each([&](Renderer& p) { any_path = any_path || p.use_path(); });
     size_t chunk = any_path ? (size_t)kPathMaxLaunches : steps;
     if (cb && chunk > 4 * steps) chunk = 4 * steps;
     const uint32_t m = (uint32_t)std::min(chunk, substep - done);
-    if (!(peers_.empty() ? run_launches(m, err) : step(m, err))) return false;
+    if (!(group_.empty() ? run_launches(m, err) : step(m, err))) return false;
     done += m;
     for (; fired < (done + steps - 1) / steps; ++fired)
       if (cb) cb(user);
@@ -849,150 +641,7 @@ bool Renderer::gather(bool result, float4* dst, Error& err, bool zero_first) {
     if (!hip_ok(launch_export(st, c->map, result ? c->result.ptr : c->cumulative.ptr, dst, first), "k_export", err)) return false;
     first = false;
   }
-  if (!peers_.empty() && !reduce_peers(result, dst, err)) return false;
-  return true;
-}
-
-// The tiles of the other GPUs meet this device's in `dst` (RCCL over xGMI; one communicator per device, every call of one
-// exchange inside ONE ncclGroup issued from this thread).  Two shapes:
-//  * gather (default): every peer chain SENDS its packed tile-major buffer (its share of the frame, 1/n of the bytes) straight to
-//    device 0, which receives into a staging area and scatters with k_export.  xGMI is point to point: the n - 1 transfers use
-//    n - 1 different links at the same time, each carrying 1/n of the frame (4 MB of a 1080p frame at n = 8).
-//  * reduce (GLAZE_MULTI_EXCHANGE=reduce): one ncclReduce(sum, float) of the zero-padded W*H*4 frame per device, in place on the
-//    root -- what SURVEY 8(e) names first; a ring moves the whole frame over every link (33 MB at 1080p).
-//  * peer (GLAZE_MULTI_EXCHANGE=peer): the gather shape without RCCL -- one hipMemcpyPeerAsync per peer on that peer's stream into
-//    the same staging area, an event per peer that device 0's stream waits for.  For machines whose RCCL cannot be loaded or will not
-//    initialise (bench.py falls back to it and says so); never chosen silently.
-// The tiles are disjoint, so both give the image of a one-GPU render bit for bit.  Loop-back mode (every "device" is this one;
-// tests): RCCL cannot put two ranks on one GPU, and there is nothing to move -- the peers scatter their tiles straight into `dst`.
-bool Renderer::reduce_peers(bool result, float4* dst, Error& err) {
-  if (!hip_ok(hipStreamSynchronize(chains_[0]->stream), "exchange: local frame", err)) return false;
-  OnOwnDevice back{*this};   // the exchanges visit the peers' devices on this thread
-  if (loopback_) return peers_gather(result, dst, err);
-  return exchange_ == kExchangeReduce ? exchange_reduce(result, dst, err) : exchange_packed(result, dst, err);
-}
-
-// every peer scatters its tiles into a full frame and waits for it: into `shared` (loop-back: one device, the root's frame, nothing
-// cleared) or, with shared == nullptr, into its own zero-padded p.frame
-bool Renderer::peers_gather(bool result, float4* shared, Error& err) {
-  return forward([=](Peer& p, size_t, Error& e) {
-    if (!hip_ok(hipSetDevice(p.inst->device), "hipSetDevice", e)) return false;
-    if (!p.r->gather(result, shared ? shared : p.frame.ptr, e, shared == nullptr)) return false;
-    return hip_ok(hipStreamSynchronize(p.inst->stream), "exchange: peer frame", e);
-  }, err);
-}
-
-namespace {
-bool rccl_ok(const Rccl& nc, ncclResult_t r, const char* what, Error& err) {
-  if (r == ncclSuccess) return true;
-  if (err.code == 0 || err.msg.empty()) {   // the first failure is the one reported
-    err.code = GLZ_E_DEVICE;
-    err.msg = std::string(what) + ": " + nc.GetErrorString(r);
-  }
-  return false;
-}
-}  // namespace
-const Rccl* Renderer::rccl(Error& err) const {
-  std::string why;
-  const Rccl* nc = Rccl::get(why);
-  if (nc && comms_.size() == peers_.size() + 1) return nc;
-  err.code = GLZ_E_DEVICE;
-  err.msg = nc ? "RCCL communicators are missing" : why;
-  return nullptr;
-}
-
-// the end of an RCCL exchange: the peers' streams first (their buffers are free again), the root's last -- everything has arrived when
-// it is idle.  Without the peers (peer copy): the root's stream waited for every peer's copy before it scattered.
-bool Renderer::finish_exchange(bool peers_too, Error& err) {
-  if (peers_too)
-    for (auto& p : peers_) {
-      if (!hip_ok(hipSetDevice(p->inst->device), "hipSetDevice", err)) return false;
-      if (!hip_ok(hipStreamSynchronize(p->inst->stream), "exchange (peer)", err)) return false;
-    }
-  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
-  return hip_ok(hipStreamSynchronize(chains_[0]->stream), "exchange (root)", err);
-}
-
-size_t Renderer::Peer::n_pixels() const {
-  size_t n = 0;
-  for (auto& c : r->chains_) n += c->map.n_local_pixels;
-  return n;
-}
-const float4* Renderer::Peer::packed(bool result) const {
-  auto& ch = r->chains_;
-  return ch.size() > 1 ? frame.ptr : (result ? ch[0]->result.ptr : ch[0]->cumulative.ptr);
-}
-
-// The gather shape over either transport: every peer's packed tiles go to recv_stage_ on device 0, peer after peer in the order of
-// the list, and are scattered from there.
-bool Renderer::exchange_packed(bool result, float4* dst, Error& err) {
-  hipStream_t st = chains_[0]->stream;
-  if (!forward([=](Peer& p, size_t, Error& e) {
-        if (!hip_ok(hipSetDevice(p.inst->device), "hipSetDevice", e)) return false;
-        // the chains' own tile-major buffers are what travels: one chain is sent from where it lies, several are laid end
-        // to end first so that every peer issues exactly ONE send (copies and send are ordered by the peer's stream)
-        if (!p.r->settle(e)) return false;
-        auto& ch = p.r->chains_;
-        if (ch.size() < 2) return true;
-        const size_t total = p.n_pixels();
-        size_t off = 0;
-        if (p.frame.count < total && !hip_ok(p.frame.alloc(total), "alloc peer staging", e)) return false;
-        for (auto& c : ch) {
-          const size_t n = c->map.n_local_pixels;
-          if (n && !hip_ok(hipMemcpyAsync(p.frame.ptr + off, result ? c->result.ptr : c->cumulative.ptr, sizeof(float4) * n, hipMemcpyDeviceToDevice, p.inst->stream), "pack tiles", e))
-            return false;
-          off += n;
-        }
-        return true;
-      }, err))
-    return false;
-  const Rccl* nc = nullptr;   // null: peer copy
-  if (exchange_ != kExchangePeerCopy && !(nc = rccl(err))) return false;
-  size_t total = 0, off = 0;
-  for (auto& p : peers_) total += p->n_pixels();
-  if (recv_stage_.count < total && !hip_ok(recv_stage_.alloc(total), "alloc exchange staging", err)) return false;
-  if (nc && !rccl_ok(*nc, nc->GroupStart(), "ncclGroupStart", err)) return false;
-  bool ok = true;
-  for (size_t i = 0; ok && i < peers_.size(); ++i) {
-    Peer& p = *peers_[i];
-    const size_t n = p.n_pixels();
-    if (!n) continue;
-    const float4* src = p.packed(result);
-    if (nc) {
-      ok = rccl_ok(*nc, nc->Send(src, n * 4, ncclFloat, 0, static_cast<ncclComm_t>(comms_[i + 1]), p.inst->stream), "ncclSend", err) &&
-           rccl_ok(*nc, nc->Recv(recv_stage_.ptr + off, n * 4, ncclFloat, (int)i + 1, static_cast<ncclComm_t>(comms_[0]), st), "ncclRecv", err);
-    } else {
-      ok = hip_ok(hipSetDevice(p.inst->device), "hipSetDevice", err) && (p.sent || hip_ok(hipEventCreateWithFlags(&p.sent, hipEventDisableTiming), "event", err)) &&
-           hip_ok(hipMemcpyPeerAsync(recv_stage_.ptr + off, inst_->device, src, p.inst->device, sizeof(float4) * n, p.inst->stream), "peer copy", err) &&
-           hip_ok(hipEventRecord(p.sent, p.inst->stream), "peer copy", err);
-      (void)hipSetDevice(inst_->device);   // for the wait that follows, not a restore
-      ok = ok && hip_ok(hipStreamWaitEvent(st, p.sent, 0), "peer copy", err);
-    }
-    off += n;
-  }
-  if (nc) ok = rccl_ok(*nc, nc->GroupEnd(), "ncclGroupEnd", err) && ok;   // always closed, also after a failed call inside it
-  if (!ok) return false;
-  off = 0;
-  for (auto& p : peers_)
-    for (auto& c : p->r->chains_) {
-      if (!hip_ok(launch_export(st, c->map, recv_stage_.ptr + off, dst, false), "k_export (received tiles)", err)) return false;
-      off += c->map.n_local_pixels;
-    }
-  return finish_exchange(nc != nullptr, err);
-}
-
-// One ncclReduce per device over the zero-padded frames, in place on the root.
-bool Renderer::exchange_reduce(bool result, float4* dst, Error& err) {
-  if (!peers_gather(result, nullptr, err)) return false;
-  const Rccl* nc = rccl(err);
-  if (!nc) return false;
-  const size_t count = (size_t)w_ * h_ * 4;
-  if (!rccl_ok(*nc, nc->GroupStart(), "ncclGroupStart", err)) return false;
-  bool ok = rccl_ok(*nc, nc->Reduce(dst, dst, count, ncclFloat, ncclSum, 0, static_cast<ncclComm_t>(comms_[0]), chains_[0]->stream), "ncclReduce", err);   // in place on the root
-  for (size_t i = 0; ok && i < peers_.size(); ++i)
-    ok = rccl_ok(*nc, nc->Reduce(peers_[i]->frame.ptr, nullptr, count, ncclFloat, ncclSum, 0, static_cast<ncclComm_t>(comms_[i + 1]), peers_[i]->inst->stream), "ncclReduce", err);
-  ok = rccl_ok(*nc, nc->GroupEnd(), "ncclGroupEnd", err) && ok;
-  return ok && finish_exchange(true, err);
+  return group_.empty() || group_.bring_tiles(result, dst, err);   // the other devices' tiles (device_group.h)
 }
 
 // everything this renderer has enqueued is done and its images are final (what gather() establishes before it scatters)
@@ -1033,7 +682,7 @@ bool Renderer::read_rgba8(uint8_t* out, Error& err) {
 // the readers of the whole frame: under set_partition(world > 1) it is not in this process (with set_devices the partition is over this
 // process's own devices: gather() brings their tiles)
 bool Renderer::frame_is_here(const char* who, Error& err) const {
-  if (world_ <= 1 || !peers_.empty()) return true;
+  if (world_ <= 1 || !group_.empty()) return true;
   err.code = GLZ_E_ARG;
   err.msg = std::string(who) + ": under set_partition(world > 1) the frame is not in this process";
   return false;
@@ -1073,13 +722,13 @@ bool Renderer::set_texture_lod(int mode, Error& err) {
   }
   cfg_.lod_mode = mode;
   request_new_frame_ = true;
-  return forward([=](Peer& p, size_t, Error& e) { return p.r->set_texture_lod(mode, e); }, err);
+  return group_.forward([=](Renderer& p, Error& e) { return p.set_texture_lod(mode, e); }, err);
 }
 
 bool Renderer::set_seed(uint64_t s) {
   cfg_.seed = s;
   request_new_frame_ = true;
-  for (auto& p : peers_) p->r->set_seed(s);
+  group_.each([=](Renderer& p) { p.set_seed(s); });
   return true;
 }
 
@@ -1091,13 +740,13 @@ bool Renderer::set_depth(uint32_t d, Error& err) {
   }
   cfg_.pt_steps = d;
   request_new_frame_ = true;
-  for (auto& p : peers_)
-    if (!p->r->set_depth(d, err)) return false;
-  return true;
+  bool ok = true;
+  group_.each([&](Renderer& p) { ok = ok && p.set_depth(d, err); });
+  return ok;
 }
 
 bool Renderer::set_partition(uint32_t rank, uint32_t world, Error& err) {
-  if (!peers_.empty()) {
+  if (!group_.empty()) {
     err.code = GLZ_E_ARG;
     err.msg = "a renderer that spans several devices (set_devices) cannot also be one rank of a process partition";
     return false;
@@ -1117,116 +766,24 @@ bool Renderer::set_partition_local(uint32_t rank, uint32_t world, Error& err) {
   return allocate(err);
 }
 
+// The group checks the list, the environment and RCCL before anything is touched; from the release of the old peers on every failure
+// leaves ONE device rendering the whole frame, with a new frame requested.
 bool Renderer::set_devices(const int* devices, int n, Error& err) {
-  auto bad = [&](const char* m) {
+  if (world_ != 1 && group_.empty()) {
     err.code = GLZ_E_ARG;
-    err.msg = m;
+    err.msg = "set_devices: this renderer is one rank of a process partition (set_partition)";
     return false;
-  };
-  if (!devices || n < 1 || n > 64) return bad("set_devices: between 1 and 64 devices");
-  if (devices[0] != inst_->device) return bad("set_devices: the first device must be the renderer's own (glz_instance_device)");
-  if (world_ != 1 && peers_.empty()) return bad("set_devices: this renderer is one rank of a process partition (set_partition)");
-  bool all_same = true, any_same = false;
-  for (int i = 0; i < n; ++i) {
-    if (devices[i] != devices[0]) all_same = false;
-    for (int j = 0; j < i; ++j) any_same |= devices[i] == devices[j];
   }
-  // GLAZE_MULTI_LOOPBACK: the list may name ONE device n times (tests on a one-GPU box).  Any value but `rccl`: the tiles meet
-  // without RCCL (which cannot put two ranks on one GPU).  `rccl`: the exchange still goes through the RCCL entry points -- for
-  // a stand-in library named by GLAZE_RCCL_LIBRARY (tests/fake_rccl), so that the n >= 2 group construction itself runs.
-  const char* lbenv = getenv("GLAZE_MULTI_LOOPBACK");
-  const bool dup_ok = n > 1 && all_same && lbenv != nullptr;
-  const bool loopback = dup_ok && strcmp(lbenv, "rccl") != 0 && strcmp(lbenv, "peer") != 0;   // `peer`: the peer-copy exchange with n "devices" on one GPU
-  if (any_same && !dup_ok) return bad("set_devices: a device is listed twice (GLAZE_MULTI_LOOPBACK=1 allows n copies of ONE device, for tests)");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess) count = 0;
-  for (int i = 0; i < n; ++i)
-    if (devices[i] < 0 || devices[i] >= count) return bad("set_devices: HIP device ordinal out of range");
-  int exchange = kExchangeGather;
-  if (const char* x = getenv("GLAZE_MULTI_EXCHANGE")) {
-    if (!strcmp(x, "reduce")) exchange = kExchangeReduce;
-    else if (!strcmp(x, "peer")) exchange = kExchangePeerCopy;
-    else if (strcmp(x, "gather")) return bad("GLAZE_MULTI_EXCHANGE must be `gather`, `reduce` or `peer`");
-  }
-  if (dup_ok && !strcmp(lbenv, "peer")) exchange = kExchangePeerCopy;
-  const bool use_rccl = n > 1 && !loopback && exchange != kExchangePeerCopy;
-  // RCCL first: without it nothing is touched (a renderer that already spans devices keeps them)
-  const Rccl* nc = nullptr;
-  if (use_rccl) {
-    std::string why;
-    nc = Rccl::get(why);
-    if (!nc) {
-      err.code = GLZ_E_DEVICE;
-      err.msg = why;
-      return false;
-    }
-  }
+  DeviceGroup::Plan plan;
+  if (!group_.check(devices, n, plan, err)) return false;
   if (!wait_idle(err)) return false;
-  OnOwnDevice back{*this};   // peer access and ncclCommInitAll below visit the other devices on this thread
-  release_peers();
-  // from here on every failure leaves ONE device rendering the whole frame
-  auto fail = [&]() {
-    release_peers();
-    Error ignored;
-    (void)set_partition_local(0, 1, ignored);
-    request_new_frame_ = true;
-    return false;
-  };
-  if (n == 1) return set_partition_local(0, 1, err) ? true : fail();
-  for (int i = 1; i < n; ++i) peers_.emplace_back(new Peer());
-  loopback_ = loopback;
-  exchange_ = exchange;
-  // instance + scene replica (upload, BVH build) + renderer for the tiles t % n == i, on every peer's own thread
-  const Renderer* self = this;
-  const Scene* src = scene_.get();
-  const Instance* src_inst = scene_->instance ? scene_->instance : inst_;
-  const uint32_t w = w_, h = h_, world = (uint32_t)n;
-  const bool want_frame = !loopback && exchange == kExchangeReduce;
-  const bool built = forward([=](Peer& p, size_t i, Error& e) {
-    p.inst.reset(Instance::create(devices[i + 1], e));
-    if (!p.inst) return false;
-    std::shared_ptr<Scene> replica = p.replica_of(*src, *src_inst, e);
-    if (!replica) return false;
-    p.r.reset(Renderer::create(p.inst.get(), replica, w, h, e));
-    if (!p.r) return false;
-    p.r->cfg_ = self->cfg_;   // (the allocate() that follows requests a new frame)
-    if (!p.r->set_partition_local((uint32_t)i + 1, world, e)) return false;
-    return !want_frame || hip_ok(p.frame.alloc((size_t)w * h), "alloc peer frame", e);
-  }, err);
-  if (!built) return fail();
-  if (!set_partition_local(0, world, err)) return fail();
-  if (!loopback && !use_rccl) {
-    // direct access between device 0 and every peer (without it the copies are staged through the host); "already enabled" is fine
-    for (int i = 1; i < n; ++i) {
-      if (devices[i] == devices[0]) continue;
-      int can = 0;
-      if (hipDeviceCanAccessPeer(&can, devices[0], devices[i]) == hipSuccess && can) {
-        (void)hipSetDevice(devices[0]);
-        (void)hipDeviceEnablePeerAccess(devices[i], 0);
-        (void)hipSetDevice(devices[i]);
-        (void)hipDeviceEnablePeerAccess(devices[0], 0);
-      }
-    }
-    (void)hipGetLastError();
-  }
-  if (use_rccl) {
-    std::vector<ncclComm_t> comms((size_t)n, nullptr);
-    const ncclResult_t r = nc->CommInitAll(comms.data(), n, devices);
-    if (r != ncclSuccess) {
-      err.code = GLZ_E_DEVICE;
-      err.msg = std::string("ncclCommInitAll: ") + nc->GetErrorString(r);
-      return fail();
-    }
-    for (ncclComm_t c : comms) comms_.push_back(c);
-  }
+  group_.release();
   request_new_frame_ = true;
-  return true;
-}
-
-const Scene* Renderer::device_scene(int i) const {
-  if (i == 0) return scene_.get();
-  if (i < 0 || (size_t)i > peers_.size() || !peers_[(size_t)i - 1]->r) return nullptr;
-  return peers_[(size_t)i - 1]->r->scene_.get();
+  if (set_partition_local(0, (uint32_t)n, err) && (n == 1 || group_.build(plan, err))) return true;
+  group_.release();
+  Error ignored;
+  (void)set_partition_local(0, 1, ignored);
+  return false;
 }
 
 bool Renderer::set_chains(uint32_t n, Error& err) {
@@ -1235,7 +792,7 @@ bool Renderer::set_chains(uint32_t n, Error& err) {
     err.msg = "at most 16 chains";
     return false;
   }
-  return resize([&] { cfg_.chains_wanted = n; }, [=](Peer& p, size_t, Error& e) { return p.r->set_chains(n, e); }, err);
+  return resize([&] { cfg_.chains_wanted = n; }, err) && group_.forward([=](Renderer& p, Error& e) { return p.set_chains(n, e); }, err);
 }
 
 bool Renderer::export_device(int which, void* dev, Error& err) {
@@ -1251,7 +808,7 @@ size_t Renderer::packed_count(uint32_t w, uint32_t h, uint32_t rank, uint32_t wo
   return make_tile_map(w, h, rank, world).n_local_pixels;
 }
 bool Renderer::export_packed(int which, void* dev, Error& err) {
-  if (!peers_.empty()) {
+  if (!group_.empty()) {
     err.code = GLZ_E_ARG;
     err.msg = "export_packed is for one rank of a process partition (a renderer that spans devices exchanges by itself)";
     return false;

@@ -6,6 +6,7 @@
 #include <memory>
 #include <vector>
 
+#include "device_group.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "post_stage.h"
@@ -46,13 +47,11 @@ class Renderer {
   bool set_seed(uint64_t s);
   bool set_depth(uint32_t d, Error& err);
   bool set_partition(uint32_t rank, uint32_t world, Error& err);
-  // Several GPUs inside ONE process: devices[0] must be this renderer's own device; every further entry
-  // gets its own stream, a replica of the scene, a renderer for the tiles t % n == i and a host thread that enqueues its
-  // launches.  Reads sum the zero-padded RGBA32F frames onto devices[0] with one ncclReduce (RCCL over xGMI; one
-  // communicator per device from ncclCommInitAll).  n == 1 returns to a single device.
+  // Several GPUs inside ONE process: devices[0] must be this renderer's own device, every further entry renders the
+  // tiles t % n == i and every read-out brings them here (device_group.h).  n == 1 returns to a single device.
   bool set_devices(const int* devices, int n, Error& err);
-  uint32_t device_count() const { return 1u + (uint32_t)peers_.size(); }
-  const Scene* device_scene(int i) const;    // the scene (replica) device i of set_devices renders; null when out of range
+  uint32_t device_count() const { return 1u + (uint32_t)group_.size(); }
+  const Scene* device_scene(int i) const { return i == 0 ? scene_.get() : group_.scene(i); }   // the scene (replica) device i of set_devices renders; null when out of range
   bool set_chains(uint32_t n, Error& err);   // 0 = automatic
   // How a launch reaches the device: 1 = two kernels per launch (k_trace, k_shade: throughput, the full frame), 2 = the per-wave
   // launch loop k_path (one kernel per batch of launches: latency, a small tile share per GPU), 0 = by the pixels this device
@@ -90,6 +89,17 @@ class Renderer {
   bool to_host(std::initializer_list<HostCopy> copies, const char* what, Error& err) const;
   bool frame_to_host(const float4* frame, void* out, const char* what, Error& err) const { return to_host({{out, frame, sizeof(float4) * (size_t)w_ * h_}}, what, err); }
 
+  // ---- what a DeviceGroup asks of the renderers it drives, beyond the calls above; nothing else uses these ----
+  void take_settings(const Renderer& root) { cfg_ = root.cfg_; }                 // a new peer: everything the devices must agree on
+  bool set_partition_local(uint32_t rank, uint32_t world, Error& err);           // the tiles t % world == rank, no questions asked
+  bool settle(Error& err);                                                       // everything enqueued is done, the images are final
+  bool gather(bool result, float4* dst, Error& err, bool zero_first = true);     // every chain's tiles into the full frame `dst`
+  struct PackedTiles {
+    const TileMap& map;
+    const float4* data;   // map.n_local_pixels float4s, tile-major
+  };
+  PackedTiles packed_tiles(uint32_t chain, bool result) const { return {chains_[chain]->map, result ? chains_[chain]->result.ptr : chains_[chain]->cumulative.ptr}; }
+
  private:
   Renderer() = default;
   bool allocate(Error& err);
@@ -99,8 +109,7 @@ class Renderer {
   bool path_batch(uint32_t n, Error& err);
   bool run_launches(uint32_t n, Error& err);
   bool use_path() const { return path_mode_ && !cfg_.counting && chains_.size() == 1 && chains_[0]->grid_path != 0; }
-  bool gather(bool result, float4* dst, Error& err, bool zero_first = true);
-  template <class A, class F> bool resize(A apply, F on_peer, Error& err);
+  template <class A> bool resize(A apply, Error& err);
   template <class U> bool update_scene(U update, Error& err);
   bool rgba8_to_host(const float4* frame, uint8_t* out, const char* what, const char* what_sync, Error& err);
 
@@ -174,30 +183,8 @@ class Renderer {
   void resolve_events(Chain& c);
   void fill_args(const Chain& c, LaunchArgs& a) const;
 
-  // ---- other GPUs of this process (set_devices) ----
-  struct Peer;
-  struct Pending;
-  struct OnOwnDevice;
-  std::vector<std::unique_ptr<Peer>> peers_;
-  std::vector<void*> comms_;   // ncclComm_t per device (index 0 = this renderer); empty in loop-back mode
-  bool loopback_ = false;      // all "devices" are this one device (GLAZE_MULTI_LOOPBACK=1, tests on a one-GPU box): no RCCL
-  enum { kExchangeGather = 0, kExchangeReduce = 1, kExchangePeerCopy = 2 };
-  int exchange_ = kExchangeGather;      // how the peers' tiles reach device 0 (reduce_peers); GLAZE_MULTI_EXCHANGE at set_devices
-  DeviceBuffer<float4> recv_stage_;     // device 0: the packed tiles received from the peers (gather shape)
-  bool settle(Error& err);
-  template <class F> void post_all(F f, Pending& p);
-  bool join_all(Pending& p, Error& err);
-  template <class F, class G> bool with_peers(F f, G g, Error& err);
-  template <class F> bool forward(F f, Error& err);
-  void release_peers();
-  bool set_partition_local(uint32_t rank, uint32_t world, Error& err);
+  DeviceGroup group_{*this};   // the other GPUs of this process (set_devices)
   bool wait_idle_local(const char* what, Error& err);
-  bool reduce_peers(bool result, float4* dst, Error& err);
-  bool peers_gather(bool result, float4* shared, Error& err);
-  bool exchange_packed(bool result, float4* dst, Error& err);
-  bool exchange_reduce(bool result, float4* dst, Error& err);
-  bool finish_exchange(bool peers_too, Error& err);
-  const struct Rccl* rccl(Error& err) const;   // the loaded library, if this renderer has its communicators
   bool step_local(uint32_t n, Error& err);
 
   bool frame_is_here(const char* who, Error& err) const;                     // false, with the error set, for one rank of a process partition

@@ -165,6 +165,77 @@ def test_loopback_devices_follow_every_update(instance, loopback):
         r.set_partition(0, 2)                                                                  # not while it spans several devices
 
 
+WORK_COUNTERS = ("launches", "samples", "closest_rays", "shadow_rays", "closest_nodes", "closest_tris", "shadow_nodes", "shadow_tris", "hits", "fresh_paths")
+
+
+def test_one_live_renderer_through_regroups_and_updates(instance, monkeypatch):
+    """ONE renderer goes 3 devices -> 2 (a regroup while spanning: the old peers are released with work behind them) -> update_transforms ->
+    set_texture_lod -> change_resolution -> set_node_width(8) and back under two kernels per launch -> 1 device; after every step all three
+    read-outs are those of a one-device renderer that received the same calls, bit for bit, and so are the work counters once they are on.
+    Then 3 -> 2 -> change_resolution again over the peer-copy exchange, whose staging area has to grow and shrink with the group."""
+    d = instance.device
+    desc = cube_scene(material_type=abi.MAT_UBER)
+
+    def pair():
+        rs = [glaze_amd.RayTraceRenderer.new(instance, glaze_amd.RayTraceScene.from_desc(instance, desc), 136, 200) for _ in range(2)]
+        for x in rs:
+            x.set_depth(4)
+            x.set_seed(21)
+        return rs
+
+    def same(tag, launches, counters=False):
+        r.step(launches); one.step(launches)
+        assert np.array_equal(bits(r.read_hdr()), bits(one.read_hdr())), tag
+        assert np.array_equal(bits(r.read_result()), bits(one.read_result())), tag
+        assert np.array_equal(r.read_rgba8(), one.read_rgba8()), tag
+        if counters:
+            s, s1 = r.stats(), one.stats()
+            for f in WORK_COUNTERS:
+                assert getattr(s, f) == getattr(s1, f), (tag, f)
+
+    def regroup(n, tag, launches, **kw):
+        r.set_devices([d] * n)                                                                 # starts a new frame on every device
+        one.restart()
+        assert r.device_count() == n
+        same(tag, launches, **kw)
+
+    monkeypatch.setenv("GLAZE_MULTI_LOOPBACK", "1")
+    r, one = pair()
+    regroup(3, "three devices", 5)
+    regroup(2, "three devices -> two", 6)
+    moved = desc.transforms.copy()
+    moved[0, 12] += 0.25                                                                       # column-major: the translation's x
+    for x in (r, one):
+        x.update_transforms(moved)
+    same("update_transforms", 4)
+    for x in (r, one):
+        x.set_texture_lod(1)
+    same("set_texture_lod", 4)
+    for x in (r, one):
+        x.change_resolution(150, 70)
+    same("change_resolution", 5)
+    for x in (r, one):
+        x.set_launch_mode("two_kernels")
+        x.set_node_width(8)
+    same("8-wide nodes", 3)
+    for x in (r, one):
+        x.set_node_width(0)
+    same("node width back to automatic", 3)
+    for x in (r, one):
+        x.enable_counters(True, True)
+        x.restart()
+    same("counters on, two devices", 4, counters=True)
+    regroup(1, "back to one device", 4, counters=True)
+
+    monkeypatch.setenv("GLAZE_MULTI_LOOPBACK", "peer")
+    r, one = pair()
+    regroup(3, "peer copies: three devices", 5)
+    regroup(2, "peer copies: three devices -> two", 4)
+    for x in (r, one):
+        x.change_resolution(150, 70)
+    same("peer copies: change_resolution", 3)
+
+
 def test_cli_devices_flag(tmp_path, instance):
     """glaze-cli --devices: one device = the default path; a loop-back list of three = the same image."""
     cli = os.path.join(ROOT, "glaze_amd", "csrc", "glaze-cli")
