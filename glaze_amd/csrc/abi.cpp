@@ -309,7 +309,7 @@ void glz_renderer_destroy(glz_renderer* h) { delete h; }
 
 
 int glz_renderer_set_integrator(glz_renderer* h, int i) { GLZ_GUARD_BEGIN GLZ_R(h); GLZ_RET(h->r->set_integrator(i, e)); GLZ_GUARD_END(GLZ_E_IO) }
-int glz_renderer_set_exposure(glz_renderer* h, float x) { GLZ_GUARD_BEGIN GLZ_R(h); GLZ_RET(h->r->set_exposure(x)); GLZ_GUARD_END(GLZ_E_IO) }
+int glz_renderer_set_exposure(glz_renderer* h, float x) { GLZ_GUARD_BEGIN GLZ_R(h); GLZ_RET(h->r->set_exposure(x, e)); GLZ_GUARD_END(GLZ_E_IO) }
 int glz_renderer_update_camera(glz_renderer* h, const glz_camera* c) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!c) return fail(GLZ_E_ARG, "camera is null");

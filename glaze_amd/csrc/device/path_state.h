@@ -106,17 +106,25 @@ struct ClosestSink {
   }
 };
 
-// update_count() + update_result() of path_trace.rgen:119-133 for one pixel; `cum` = cumulative[lid] as read before
-__device__ __forceinline__ void accumulate_pixel(const LaunchArgs& A, uint32_t lid, vec3 c, bool add, bool update, float exposure, float4 cum) {
-  cum.w += 1.0f;
-  if (update) {
-    if (add) { cum.x += c.x; cum.y += c.y; cum.z += c.z; }
-    A.st.result[lid] = make_float4(cum.x * exposure / cum.w, cum.y * exposure / cum.w, cum.z * exposure / cum.w, 1.0f);
-  }
-  A.st.cumulative[lid] = cum;
+// update_count() + update_result() of path_trace.rgen:119-133 for one pixel, with the result left to k_finalize.  update_count runs once
+// per active pixel and accumulating launch -- a miss, a specular hit, a hit without a light sample, a shadow ray retired either way -- so
+// the count of every active pixel is the same number, which the host knows, and a pixel that does not update touches no memory.  What is
+// per pixel is the launch of its last update_result: `mark`, -(float)min(u, 2^24) for the u-th accumulating launch since the reset, goes
+// to cumulative.w.  The sign says "updated since the last resolve", the magnitude is what update_result divided by (the eager
+// w += 1.0f sticks at 2^24 too); k_finalize (kernels_render.hip) makes result and the count from it whenever somebody looks.
+// accumulate_retired: a shadow ray's end (k_trace, k_path).  An occluded ray has nothing to add: four bytes say that the pixel updated, the
+// accumulator is not read.  `cum` = cumulative[lid] as read by the caller (only its xyz are used, and only by an unoccluded ray).
+// accumulate_shaded: the shading code's update.  What it adds is finite but for a rare sample, so one path for both (the sum is re-stored
+// unchanged): a branch here is a branch in shade_pixel.
+__device__ __forceinline__ float update_mark(uint32_t ordinal) { return -(float)(ordinal < (1u << 24) ? ordinal : (1u << 24)); }
+__device__ __forceinline__ void accumulate_retired(const LaunchArgs& A, uint32_t lid, vec3 c, bool add, float mark, float4 cum) {
+  if (add) A.st.cumulative[lid] = make_float4(cum.x + c.x, cum.y + c.y, cum.z + c.z, mark);
+  else A.st.cumulative[lid].w = mark;
 }
-__device__ __forceinline__ void accumulate_pixel(const LaunchArgs& A, uint32_t lid, vec3 c, bool add, bool update, float exposure) {
-  accumulate_pixel(A, lid, c, add, update, exposure, A.st.cumulative[lid]);
+__device__ __forceinline__ void accumulate_shaded(const LaunchArgs& A, uint32_t lid, vec3 c, bool add, bool update, float mark) {
+  if (!update) return;
+  const float4 cum = A.st.cumulative[lid];
+  A.st.cumulative[lid] = make_float4(add ? cum.x + c.x : cum.x, add ? cum.y + c.y : cum.y, add ? cum.z + c.z : cum.z, mark);
 }
 
 // Shadow-ray queue: 8 sub-queues ("shards"), shard = blockIdx % 8.  Blocks b and b+8 are observed to land on
@@ -146,7 +154,7 @@ __device__ __forceinline__ uint32_t queue_slot(uint32_t* counters, uint32_t n_lo
 
 // ---------------------------------------------------------------------------------------------
 // Shadow rays: the shadow traceRayEXT (path_trace.rgen:106-110) for the compacted queue written by k_shade,
-// followed by update_count / update_result (:119-133) of the owning pixel (source / sink of k_trace's second phase).
+// followed by update_count / update_result (:119-133, accumulate_retired) of the owning pixel (source / sink of k_trace's second phase).
 // ---------------------------------------------------------------------------------------------
 struct ShadowSource {
   const LaunchArgs& A;
@@ -175,8 +183,8 @@ struct ShadowSink {
   __device__ __forceinline__ void store(uint32_t, const HitRecord& h) {
     const bool occluded = h.leaf != 0xFFFFFFFFu;
     const vec3 c = mk3(src.contrib.x, src.contrib.y, src.contrib.z);
-    const bool add = !occluded;
-    accumulate_pixel(A, src.lid, c, add, true, A.shadow_exposure);
+    if (occluded) A.st.cumulative[src.lid].w = A.shadow_mark;   // no read: the sum stays
+    else accumulate_retired(A, src.lid, c, true, A.shadow_mark, A.st.cumulative[src.lid]);
   }
 };
 }  // namespace glz

@@ -41,7 +41,7 @@ struct DirectState {
   __device__ __forceinline__ void ray_d(uint32_t lid, float4 v) { A.st.ray_d[lid] = v; }
   __device__ __forceinline__ void imp(int q, uint32_t lid, float4 v) { A.st.imp[q][lid] = v; }
   __device__ __forceinline__ float4 read_imp(int q, uint32_t lid) const { return A.st.imp[q][lid]; }
-  __device__ __forceinline__ void accumulate(uint32_t lid, vec3 c, bool add, bool update, float exposure) { accumulate_pixel(A, lid, c, add && isfinite(c.x + c.y + c.z), update, exposure); }
+  __device__ __forceinline__ void accumulate(uint32_t lid, vec3 c, bool add, bool update, float mark) { accumulate_shaded(A, lid, c, add && isfinite(c.x + c.y + c.z), update, mark); }
 };
 struct StagedState {
 #ifdef GLZ_SECTION_TIMES
@@ -69,7 +69,7 @@ struct StagedState {
     const u32x4 v = lds_imp[q * kShadeBlockPixels];
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
   }
-  __device__ __forceinline__ void accumulate(uint32_t lid, vec3 cc, bool add, bool update, float exposure) { accumulate_pixel(*A, lid, cc, add && isfinite(cc.x + cc.y + cc.z), update, exposure); }
+  __device__ __forceinline__ void accumulate(uint32_t lid, vec3 cc, bool add, bool update, float mark) { accumulate_shaded(*A, lid, cc, add && isfinite(cc.x + cc.y + cc.z), update, mark); }
 };
 // Returns 0 when the pixel's next path state has been written (or, with the direct-light integrator, is not needed), 1 / 2 when the path
 // has ENDED and its reset is left to shade_pixel below: 1 = only ray_o is to be written (a miss: ray_d keeps its flag), 2 = ray_o and
@@ -109,7 +109,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
       c = spec_to_rgb(spec_mul(load_importance(), from_illuminant_color(texel)));
       flags = kFlagUpdate;
     }
-    out.accumulate(lid, c, true, flags != 0, F.exposure);
+    if (flags != 0) out.accumulate(lid, c, true, true, F.update_mark);   // (a miss behind a diffuse bounce only counts: nothing to write)
     end_w = rd.w;
     return F.direct_only ? 0 : 1;   // RESET_PATH
   }
@@ -235,12 +235,11 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
       A.st.sh_d[slot] = make_float4(sh_dir.x, sh_dir.y, sh_dir.z, __uint_as_float(lid));
       A.st.contrib[slot] = make_float4(c.x, c.y, c.z, __uint_as_float(flags));
     } else {
-      out.accumulate(lid, c, true, true, F.exposure);
+      out.accumulate(lid, c, true, true, F.update_mark);
     }
     spec_flag = 0.0f;
   } else {
-    out.accumulate(lid, mk3(0.0f, 0.0f, 0.0f), false, false, F.exposure);
-    spec_flag = 1.0f;
+    spec_flag = 1.0f;   // a specular bounce only counts (update_count without update_result): nothing to write
   }
   if (F.direct_only) return 0;
   GLZ_SHADE_STAMP(4);   // queue entry / accumulator update

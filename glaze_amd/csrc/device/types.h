@@ -17,7 +17,10 @@ struct FrameData {
   uint32_t lights_no;
   float pixel_offset[2];
   float scene_radius;
-  float exposure;
+  // (RTFrameData::exposure's place: k_finalize applies the exposure when the result is resolved.)  What a pixel that calls update_result in
+  // this launch leaves in cumulative.w: -(float)min(u, 2^24), u = this launch's 1-based place among the accumulating launches since the
+  // reset (accumulate_retired / accumulate_shaded, device/path_state.h)
+  float update_mark;
   float scene_size[2];
   float scene_centre[4];
   uint32_t camera_persp;

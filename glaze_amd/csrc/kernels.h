@@ -87,8 +87,8 @@ struct PathState {
   float4* sh_d;      //   direction.xyz, owning pixel lid (bits)
   float4* contrib;   //   rgb radiance to add if unoccluded, flags (bits)
   uint32_t* queue_count;
-  float4* cumulative;// accumulate_image (xyz = sum rgb, w = launches)
-  float4* result;    // result_image (out32)
+  float4* cumulative;// accumulate_image (xyz = sum rgb, w = launches; between two resolves w < 0 marks the launch of the last update: device/path_state.h)
+  float4* result;    // result_image (out32), written by k_finalize
   uint32_t* overflow;// traversal stack spill, `overflow_depth` words per lane slot of the k_trace grid
   uint32_t overflow_depth;
   uint32_t* path_cost;// k_path: [0..7] two accumulators {sum of per-launch ticks (u64), groups (u32), pad}, then one word per 64-pixel group: its ticks per launch in the last batch
@@ -125,9 +125,9 @@ struct LaunchArgs {
   // k_shade queued (they only gate an accumulation, so nothing of the current launch depends on them)
   uint32_t do_closest, do_shadow;
   uint32_t shade_set;        // which of the two shadow-queue counter sets this launch's k_shade fills (the other one is drained)
-  float shadow_exposure;     // exposure of the launch that queued the shadow rays (update_result uses it)
+  float shadow_mark;         // FrameData::update_mark of the launch that queued the shadow rays
 };
-// The launches one k_path call runs (kernels_path.hip): what differs between launches, by value in the kernel arguments (16 bytes a
+// The launches one k_path call runs (kernels_path.hip): what differs between launches, by value in the kernel arguments (12 bytes a
 // launch next to the 880 of LaunchArgs: 192 launches stay inside the 4 KB the arguments may take).  Long batches matter: the kernel
 // ends when its slowest wave does, and a wave's time per launch scatters by ~20 % -- over 16 launches the slowest of 4 096 waves is
 // 27 % above the mean, over 192 launches 8 %.
@@ -138,7 +138,7 @@ struct PathBatch {
   uint32_t parity;                         // which of the two cost accumulators this batch adds to (it reads the other one)
   uint32_t seed[kPathMaxLaunches];         // FrameData::seed of each launch (the rest of FrameData is LaunchArgs::frame)
   float offset[kPathMaxLaunches + 1][2];   // FrameData::pixel_offset; entry n: of the launch after the batch (FrameData::next_pixel_offset)
-  float exposure[kPathMaxLaunches];        // FrameData::exposure
+  uint32_t base_ordinal;                   // accumulating launches since the reset before this batch: launch L of it is number base_ordinal + L + 1 (FrameData::update_mark)
 };
 constexpr uint32_t kTraceBlock = 256;          // threads per block of the render kernels (4 waves)
 constexpr uint32_t kQueueSetWords = 8 * 32;   // 8 shard counters, 128 bytes apart
@@ -152,6 +152,9 @@ hipError_t launch_shade(hipStream_t st, const LaunchArgs& a);
 uint32_t path_grid_blocks(uint32_t n_local_pixels, const DeviceScene& scene);
 uint32_t path_resident_blocks(const DeviceScene& scene);   // blocks of k_path the chip holds at once
 hipError_t launch_path(hipStream_t st, const LaunchArgs& a, const PathBatch& batch, uint32_t blocks);
+// The resolve (Renderer::settle): for every pixel of the chain that updated since the last one (cumulative.w < 0) result = xyz * exposure / -w,
+// then cumulative.w = launches for every active pixel: what update_count / update_result would have left had they run in every launch
+hipError_t launch_finalize(hipStream_t st, const TileMap& map, float4* cumulative, float4* result, float exposure, float launches);
 // scatter the tile-major cumulative / result images into full-frame row-major RGBA32F buffers
 hipError_t launch_export(hipStream_t st, const TileMap& map, const float4* tiled, float4* frame, bool zero_first);
 // chain `chain` of `n_chains` -> the rank's packed tile order (local tile j = jl * n_chains + chain), see Renderer::export_packed

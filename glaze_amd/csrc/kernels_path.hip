@@ -18,7 +18,7 @@ using namespace dev;
 // pays that maximum again, twice (k_trace, k_shade).  Pixels are independent (path_trace.rgen:143-168: state, RNG and accumulator are
 // per pixel), so nothing forces a wave to wait for the others: here every wave carries ITS 64 pixels through
 //     closest hits of launch L -> shadow rays queued by launch L-1 (+ update_count / update_result) -> shade of launch L
-// for all launches of the batch (up to 192: only seed, jitter offset and exposure differ between launches, 16 bytes each in the kernel
+// for all launches of the batch (up to 192: only seed and jitter offset differ between launches, 12 bytes each in the kernel
 // arguments), with no grid-wide boundary in between.  A step then costs the slowest wave's SUM over the launches instead of the
 // sum over launches of the slowest wave.  (Measured: DESIGN.md section 6.)  Per pixel the operations and their order are those of k_trace / k_shade
 // (same sources, same shade_pixel, shadow rays of a launch resolved before the next launch's shading), so the image is bit-identical
@@ -30,7 +30,7 @@ using namespace dev;
 // ---------------------------------------------------------------------------------------------
 // THE ORDERING CONTRACT of k_path.  Lanes of one wave hand data to each other through GLOBAL memory: the shading lane of a pixel
 // writes a shadow-queue entry (sh_o / sh_d / contrib) that whichever lane picks the ray up in the next traversal pass reads; the lane
-// that finishes a shadow ray read-modify-writes cumulative / result of the OWNING pixel, which that pixel's own lane reads and writes
+// that finishes a shadow ray read-modify-writes cumulative of the OWNING pixel, which that pixel's own lane reads and writes
 // again in the next shading phase.  (The two-kernel mode has a kernel boundary in each of these places.)  What makes this defined is a
 // release / acquire pair at WAVEFRONT scope at every phase boundary: all lanes of a wave go through one vector-memory pipeline and one
 // L1, which performs a wave's accesses to an address in program order, so at this scope the fence needs no cache action and no
@@ -63,7 +63,7 @@ struct GroupShadowSource {
   float4 contrib;
   // The owning pixel's accumulator, read when the ray STARTS: nobody else touches it while the ray is in flight (one shadow ray per pixel
   // and launch, the pixel's own lane only shades after this pass), and it was last written a launch ago -- read at the ray's end, where
-  // update_count / update_result need it, the lane (and with it the wave's round) waited for it to come from HBM
+  // an unoccluded ray adds to it, the lane (and with it the wave's round) waited for it to come from HBM
   // (tools/gpu_sections.py: merge + retire was a fifth of a wave's tracing time).
   float4 cum;
   __device__ __forceinline__ bool load(uint32_t i, vec3& o, vec3& d, float& tmin, float& tmax) {
@@ -82,12 +82,12 @@ struct GroupShadowSource {
 struct GroupShadowSink {
   const LaunchArgs& A;
   GroupShadowSource& src;
-  float exposure;          // of the launch that queued the rays
+  float mark;              // FrameData::update_mark of the launch that queued the rays
   __device__ __forceinline__ void store(uint32_t, const HitRecord& h) {
     const bool occluded = h.leaf != 0xFFFFFFFFu;
     const vec3 c = mk3(src.contrib.x, src.contrib.y, src.contrib.z);
     const bool add = !occluded;
-    accumulate_pixel(A, src.lid, c, add, true, exposure, src.cum);
+    accumulate_retired(A, src.lid, c, add, mark, src.cum);
   }
 };
 
@@ -111,7 +111,7 @@ struct GroupMixedSink {
 // (reread_kernarg, device/shade_pixel.h: what a phase of k_path needs of the arguments is loaded where the phase begins and dies where
 // it ends -- instead of every pointer either phase uses staying in SGPRs through the whole launch loop (tracing and shading together
 // use more of them than there are: 233 of them went to VGPR lanes, and the VGPRs those took to scratch).)
-// RTFrameData of launch L of the batch: what all launches share (LaunchArgs::frame) with the three per-launch fields from the batch
+// RTFrameData of launch L of the batch: what all launches share (LaunchArgs::frame) with the per-launch fields from the batch
 __device__ __forceinline__ FrameData launch_frame(const LaunchArgs& A, const PathBatch& B, uint32_t L) {
   FrameData F = A.frame;
   F.seed = B.seed[L];
@@ -119,7 +119,7 @@ __device__ __forceinline__ FrameData launch_frame(const LaunchArgs& A, const Pat
   F.pixel_offset[1] = B.offset[L][1];
   F.next_pixel_offset[0] = B.offset[L + 1][0];
   F.next_pixel_offset[1] = B.offset[L + 1][1];
-  F.exposure = B.exposure[L];
+  F.update_mark = update_mark(B.base_ordinal + L + 1u);
   return F;
 }
 constexpr uint32_t kPathBatchOffset = (uint32_t)(((sizeof(LaunchArgs) + alignof(PathBatch) - 1) / alignof(PathBatch)) * alignof(PathBatch));   // PathBatch in k_path's kernarg segment
@@ -206,7 +206,7 @@ __global__ void __launch_bounds__(kBlock, GLZ_PATH_WAVES) k_path(const LaunchArg
       if (prio == 3) __builtin_amdgcn_s_setprio(3); else if (prio == 2) __builtin_amdgcn_s_setprio(2); else if (prio == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
     }
     uint32_t n_shadow = 0;      // wave-uniform: shadow rays the group's last shading queued
-    float queued_exposure = 0.0f;
+    float queued_mark = 0.0f;
     for (uint32_t L = 0;; ++L) {
       const LaunchArgs& A = *(const LaunchArgs*)reread_kernarg();   // the tracing phase's view of the arguments (shadows the parameter)
       const PathBatch& B = *(const PathBatch*)(reread_kernarg() + kPathBatchOffset);
@@ -223,12 +223,12 @@ __global__ void __launch_bounds__(kBlock, GLZ_PATH_WAVES) k_path(const LaunchArg
         const FrameData F = launch_frame(A, B, L);
         // ONE traversal pass: the 64 closest-hit rays of launch L, then -- in the lanes those leave idle -- the shadow rays launch L-1 queued
         GroupMixedSource src{ClosestSource{A, F, tally, lid0}, GroupShadowSource{A, lid0, 0u, make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_float4(0.0f, 0.0f, 0.0f, 0.0f)}, false};
-        GroupMixedSink sink{GroupHitSink{hit}, GroupShadowSink{A, src.shadow, queued_exposure}};
+        GroupMixedSink sink{GroupHitSink{hit}, GroupShadowSink{A, src.shadow, queued_mark}};
         trace_wave<false, false, true, GLZ_PATH_PREFETCH != 0>(A.scene, src, sink, &s_stack[threadIdx.x], aux, links, (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, 64u + n_shadow, 0u, 1u, tally);
         n_shadow = 0u;
       } else {
         GroupShadowSource src{A, lid0, 0u, make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
-        GroupShadowSink sink{A, src, queued_exposure};
+        GroupShadowSink sink{A, src, queued_mark};
         trace_wave<true, false, false, GLZ_PATH_PREFETCH != 0>(A.scene, src, sink, &s_stack[threadIdx.x], aux, links, (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, n_shadow, 0u, 1u, tally);
         n_shadow = 0u;
       }
@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(kBlock, GLZ_PATH_WAVES) k_path(const LaunchArg
       wave_handover_fence();   // tracing -> shading: the accumulators the shadow rays' lanes updated
       if (L >= B.n) break;
       n_shadow = path_shade<LOD>(g, n_groups, lane, L, S, hit);
-      queued_exposure = B.exposure[L];
+      queued_mark = update_mark(B.base_ordinal + L + 1u);
 #ifdef GLZ_PATH_TIMES
       pt_shade += wall_clock64() - pt1;
 #endif

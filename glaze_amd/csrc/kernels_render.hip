@@ -3,9 +3,10 @@
 // two kernels over the SoA path state in HBM:
 //
 //   k_trace   (persistent) ray generation / resume + closest-hit BVH4 traversal -> hit record; then the any-hit
-//             traversal of the shadow rays the previous launch queued + update_count / update_result
+//             traversal of the shadow rays the previous launch queued + the accumulator update (accumulate_retired)
 //   k_shade   hit attributes, light sample, BSDF eval, Russian roulette, BSDF sample, state update
 //             -> next ray + queued shadow ray with its contribution
+//   k_finalize makes the result image and the launch count of the accumulator, once, when somebody reads the images
 //
 // A wave owns one 8x8 pixel block of a 64x64 tile, so primary rays of a wave are coherent and all
 // per-pixel arrays are read and written as one contiguous 1 KiB (float4) line per wave.
@@ -416,6 +417,20 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE_TL_WAVES) k_trace_tl(const L
 // ---------------------------------------------------------------------------------------------
 // image plumbing
 // ---------------------------------------------------------------------------------------------
+// The resolve of a chain's images, in place (Renderer::settle; accumulate_retired / accumulate_shaded, device/path_state.h): a pixel that updated since the last
+// resolve carries -(the launch of its last update) in cumulative.w, and its result is update_result's own expression with that divisor;
+// the count of every active pixel is `launches`.  A pixel that never updated keeps result 0, a pixel outside the image is left alone.
+__global__ void __launch_bounds__(kBlock) k_finalize(const TileMap map, float4* __restrict__ cumulative, float4* __restrict__ result, float exposure, float launches) {
+  const uint32_t lid = blockIdx.x * kBlock + threadIdx.x;
+  if (!pixel_of(map, lid).active) return;
+  const float4 cum = cumulative[lid];
+  if (cum.w < 0.0f) {
+    const float w = -cum.w;
+    result[lid] = make_float4(cum.x * exposure / w, cum.y * exposure / w, cum.z * exposure / w, 1.0f);
+  }
+  if (cum.w != launches) cumulative[lid].w = launches;
+}
+
 __global__ void __launch_bounds__(kBlock) k_export(const TileMap map, const float4* __restrict__ tiled, float4* __restrict__ frame) {
   const uint32_t lid = blockIdx.x * kBlock + threadIdx.x;
   const PixelId px = pixel_of(map, lid);
@@ -496,6 +511,9 @@ hipError_t launch_shade(hipStream_t st, const LaunchArgs& a) {
 #undef GLZ_SHADE_CASE
   }
   return hipGetLastError();
+}
+hipError_t launch_finalize(hipStream_t st, const TileMap& map, float4* cumulative, float4* result, float exposure, float launches) {
+  return launch_per_item(st, k_finalize, map.n_local_pixels, map, cumulative, result, exposure, launches);
 }
 hipError_t launch_export(hipStream_t st, const TileMap& map, const float4* tiled, float4* frame, bool zero_first) {
   if (zero_first) {

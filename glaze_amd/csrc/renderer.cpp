@@ -181,6 +181,8 @@ bool Renderer::reset_buffers(Error& err) {
   sched_.rewind();
   rng_.reseed(cfg_.seed);   // build-defined: a restart replays the same seed stream (the reference keeps drawing from entropy)
   launches_ = 0;
+  accum_launches_ = 0;
+  resolve_pending_ = false;   // what the launches of the abandoned frame left is gone with it
   request_new_frame_ = false;
   return true;
 }
@@ -207,7 +209,7 @@ void Renderer::fill_args(const Chain& c, LaunchArgs& a) const {
   a.counters = cfg_.counting ? counters_.ptr : nullptr;
   a.do_closest = a.do_shadow = 0;
   a.shade_set = c.pending_set ^ 1u;
-  a.shadow_exposure = c.pending_exposure;
+  a.shadow_mark = c.pending_mark;
 }
 
 void Renderer::resolve_events(Chain& c) {
@@ -290,8 +292,19 @@ bool Renderer::flush_shadows(Chain& c, Error& err) {
   return true;
 }
 
+bool Renderer::resolve(Error& err) {
+  if (!resolve_pending_) return true;
+  for (auto& cp : chains_) {
+    Chain& c = *cp;
+    if (!flush_shadows(c, err)) return false;
+    if (!hip_ok(launch_finalize(c.stream, c.map, c.cumulative.ptr, c.result.ptr, cfg_.exposure, -update_mark()), "k_finalize", err)) return false;
+  }
+  resolve_pending_ = false;
+  return true;
+}
+
 // What one_launch and path_batch start with: a pending restart, then what all launches of a frame share in RTFrameData
-// (raytracer.rs:369-613); seed, pixel offset and exposure are per launch
+// (raytracer.rs:369-613); seed, pixel offset and update mark are per launch
 bool Renderer::launch_constants_common(FrameData& fd, Error& err) {
   if (request_new_frame_ && !reset_buffers(err)) return false;
   memset(&fd, 0, sizeof(fd));
@@ -326,9 +339,11 @@ bool Renderer::one_launch(Error& err) {
   // the launch after this one, for the paths that end in this one (shade_pixel): anything that could make the next launch differ from
   // what is assumed here -- a new camera, resolution, scene, integrator, a restart -- resets the path state before it runs (reset_buffers)
   sched_.peek(fd.next_pixel_offset);
-  fd.exposure = cfg_.exposure;
   ++launches_;
   if (fd.lights_no == 0) return true;   // the raygen shader returns before touching anything (path_trace.rgen:137-141)
+  ++accum_launches_;
+  resolve_pending_ = true;
+  fd.update_mark = update_mark();
   for (auto& cp : chains_) {
     Chain& c = *cp;
     hipStream_t st = c.stream;
@@ -346,7 +361,7 @@ bool Renderer::one_launch(Error& err) {
     t.end();
     c.shadow_pending = true;
     c.pending_set = a.shade_set;
-    c.pending_exposure = cfg_.exposure;
+    c.pending_mark = fd.update_mark;
   }
   return true;
 }
@@ -362,11 +377,13 @@ bool Renderer::path_batch(uint32_t n, Error& err) {
   for (uint32_t i = 0; i < n; ++i) {
     b.seed[i] = rng_.next();           // rng.gen::<u32>(), raytracer.rs:487
     sched_.next(b.offset[i]);          // WorkScheduler::next(), :489
-    b.exposure[i] = cfg_.exposure;
   }
   sched_.peek(b.offset[n]);            // the launch after the batch (FrameData::next_pixel_offset of its last launch)
   launches_ += n;
   if (fd.lights_no == 0) return true;   // the raygen shader returns before touching anything (path_trace.rgen:137-141)
+  b.base_ordinal = (uint32_t)std::min<uint64_t>(accum_launches_, 1u << 24);   // (update_mark sticks there)
+  accum_launches_ += n;
+  resolve_pending_ = true;
   Chain& c = *chains_[0];
   if (!flush_shadows(c, err)) return false;   // left by launches that ran as two kernels (work counters had been on)
   LaunchArgs a;
@@ -488,10 +505,15 @@ bool Renderer::set_integrator(int integrator, Error& err) {
   return group_.forward([=](Renderer& p, Error& e) { return p.set_integrator(integrator, e); }, err);
 }
 
-bool Renderer::set_exposure(float e) {
-  if (e >= 0.0f) cfg_.exposure = e;   // raytracer.rs:186-193: no restart
-  group_.each([=](Renderer& p) { p.set_exposure(e); });
-  return true;
+// raytracer.rs:186-193: no restart.  update_result applies the exposure of the launch that updates the pixel, and a resolve applies one
+// exposure to everything it resolves: what is pending is resolved with the old value before the new one holds (stream-ordered, no wait;
+// the queued shadow rays belong to launches under the old value and go first).  A frame about to be reset has nothing to keep.
+bool Renderer::set_exposure(float e, Error& err) {
+  if (e >= 0.0f && e != cfg_.exposure) {
+    if (resolve_pending_ && !request_new_frame_ && !(hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err) && resolve(err))) return false;
+    cfg_.exposure = e;
+  }
+  return group_.forward([=](Renderer& p, Error& pe) { return p.set_exposure(e, pe); }, err);   // (it may enqueue: on the peers' own threads)
 }
 
 bool Renderer::update_camera(const glz_camera& c, Error& err) {
@@ -644,9 +666,11 @@ bool Renderer::gather(bool result, float4* dst, Error& err, bool zero_first) {
   return group_.empty() || group_.bring_tiles(result, dst, err);   // the other devices' tiles (device_group.h)
 }
 
-// everything this renderer has enqueued is done and its images are final (what gather() establishes before it scatters)
+// everything this renderer has enqueued is done and its images are final (what gather() establishes before it scatters): cumulative and
+// result are resolved here, on this device; every other device of set_devices settles for itself when its tiles are asked for
 bool Renderer::settle(Error& err) {
   if (request_new_frame_ && !reset_buffers(err)) return false;
+  if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err) || !resolve(err)) return false;
   return wait_idle(err);
 }
 

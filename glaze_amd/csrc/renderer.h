@@ -1,6 +1,7 @@
 // RayTraceRenderer on HIP (lib/src/vulkan/raytracer.rs:109-687): launch loop, per-launch frame
 // constants, accumulation buffers, tile partition for one-process-per-GPU jobs.
 #pragma once
+#include <algorithm>
 #include <cstdlib>
 #include <initializer_list>
 #include <memory>
@@ -21,7 +22,7 @@ class Renderer {
   ~Renderer();
 
   bool set_integrator(int integrator, Error& err);
-  bool set_exposure(float e);
+  bool set_exposure(float e, Error& err);   // resolves what is pending with the old value first (resolve())
   bool update_camera(const glz_camera& c, Error& err);
   bool change_resolution(uint32_t w, uint32_t h, Error& err);
   bool change_scene(std::shared_ptr<Scene> scene, Error& err);
@@ -169,7 +170,7 @@ class Renderer {
     // a stand-alone pass as soon as anything looks at the images: flush_shadows)
     bool shadow_pending = false;
     uint32_t pending_set = 0;
-    float pending_exposure = 1.0f;
+    float pending_mark = 0.0f;   // FrameData::update_mark of the launch that queued them
     std::vector<EventSet> pending_events;   // per-launch kernel boundaries, resolved lazily in get_stats
     std::vector<EventSet> free_events;
     double trace_ms = 0, shade_ms = 0, flush_ms = 0, path_ms = 0;
@@ -179,6 +180,11 @@ class Renderer {
   uint32_t trace_grid(const Chain& c) const { return cfg_.counting ? c.grid_counting : (wide8() ? c.grid8 : c.grid); }   // blocks of the traversal kernel the chain's launches run
   void release_chains();
   bool flush_shadows(Chain& c, Error& err);
+  // The launches write no result and count nothing (accumulate_retired / accumulate_shaded, device/path_state.h); settle() -- every read-out -- and a change of
+  // the exposure resolve what they left: the pending shadow rays, then k_finalize on every chain's stream, with the exposure in force
+  // for everything it resolves.  The device must be current; nothing waits.
+  bool resolve(Error& err);
+  float update_mark() const { return -(float)std::min<uint64_t>(accum_launches_, 1u << 24); }   // of the launch counted last
   bool acquire_events(Chain& c, EventSet& ev, Error& err);
   void resolve_events(Chain& c);
   void fill_args(const Chain& c, LaunchArgs& a) const;
@@ -197,6 +203,8 @@ class Renderer {
   DeviceBuffer<float> oetf_thresholds_;   // sRGB8 quantiser thresholds (host::srgb8_thresholds), see k_tonemap
   DeviceBuffer<TraceCounters> counters_;
   uint64_t launches_ = 0;   // stats
+  uint64_t accum_launches_ = 0;   // launches since the reset that touched the accumulator (none does in a scene without lights)
+  bool resolve_pending_ = false;  // launches have run since the last resolve
 };
 
 }  // namespace glz
