@@ -99,11 +99,11 @@ struct ClosestSource {
     return true;
   }
 };
+// the closest-hit record as it is stored: (t (inf = miss), u, v, leaf bits)
+__device__ __forceinline__ float4 pack_hit(const HitRecord& h) { return make_float4(h.leaf == 0xFFFFFFFFu ? INFINITY : h.t, h.u, h.v, __uint_as_float(h.leaf)); }
 struct ClosestSink {
   const LaunchArgs& A;
-  __device__ __forceinline__ void store(uint32_t lid, const HitRecord& h) {
-    A.st.hit[lid] = make_float4(h.leaf == 0xFFFFFFFFu ? INFINITY : h.t, h.u, h.v, __uint_as_float(h.leaf));
-  }
+  __device__ __forceinline__ void store(uint32_t lid, const HitRecord& h) { A.st.hit[lid] = pack_hit(h); }
 };
 
 // update_count() + update_result() of path_trace.rgen:119-133 for one pixel, with the result left to k_finalize.  update_count runs once
@@ -187,4 +187,8 @@ struct ShadowSink {
     else accumulate_retired(A, src.lid, c, true, A.shadow_mark, A.st.cumulative[src.lid]);
   }
 };
+// every tracing kernel clears the counters of the queue set the k_shade that follows fills (shade_set)
+__device__ __forceinline__ void clear_next_queue_set(const LaunchArgs& A) {
+  if (blockIdx.x == 0 && threadIdx.x < kQueueShards) A.st.queue_count[A.shade_set * kQueueSetWords + threadIdx.x * kCounterStride] = 0;
+}
 }  // namespace glz

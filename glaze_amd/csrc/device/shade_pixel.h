@@ -303,7 +303,32 @@ __device__ __forceinline__ void shade_pixel(const LaunchArgs& A, const DeviceSce
   }
 }
 
-constexpr uint32_t kShadeTableBytes = 16384;   // LDS copy of the material / light / texture-descriptor tables (78 materials alone would fill it)
+// The scene tables every hit walks through -- [RTMaterial x n_materials | RTLight x n_rt_lights | TexDesc x n_textures] -- as k_shade and
+// k_path stage them in LDS when they fit.  The two capacities differ: k_shade's pool also holds the pixels' importance and the sky's
+// marginal cdf, so its table area is the smaller; k_path takes its copy from dynamic LDS, which it asks for only when the tables fit,
+// so a scene with small tables buys residency.
+constexpr uint32_t kShadeLdsTableBytes = 8192;   // k_shade (38 materials; larger tables are read from memory)
+constexpr uint32_t kPathTableBytes = 16384;      // k_path (78 materials alone would fill it)
+static_assert(sizeof(RTMaterial) % 16 == 0 && sizeof(RTLight) % 16 == 0 && sizeof(TexDesc) % 16 == 0, "the tables are copied in 16-byte pieces");
+struct SceneTables {
+  uint32_t qm, ql, qt;   // the three tables' sizes in 16-byte pieces
+  __host__ __device__ explicit SceneTables(const DeviceScene& s)
+      : qm(s.n_materials * (uint32_t)(sizeof(RTMaterial) / 16)), ql(s.n_rt_lights * (uint32_t)(sizeof(RTLight) / 16)), qt(s.n_textures * (uint32_t)(sizeof(TexDesc) / 16)) {}
+  __host__ __device__ uint32_t bytes() const { return (qm + ql + qt) * 16u; }
+  // the cooperative copy by a block of `block` threads (the caller's barrier ends it) ...
+  __device__ __forceinline__ void stage(const DeviceScene& s, uint4* dst, uint32_t block) const {
+    const uint4* gm = reinterpret_cast<const uint4*>(s.materials);
+    const uint4* gl = reinterpret_cast<const uint4*>(s.lights);
+    const uint4* gt = reinterpret_cast<const uint4*>(s.tex_desc);
+    for (uint32_t i = threadIdx.x; i < qm + ql + qt; i += block) dst[i] = i < qm ? gm[i] : (i < qm + ql ? gl[i - qm] : gt[i - qm - ql]);
+  }
+  // ... and the three table pointers of S onto the copy
+  __device__ __forceinline__ void use(DeviceScene& S, const uint4* copy) const {
+    S.materials = reinterpret_cast<const RTMaterial*>(copy);
+    S.lights = reinterpret_cast<const RTLight*>(copy + qm);
+    S.tex_desc = reinterpret_cast<const TexDesc*>(copy + qm + ql);
+  }
+};
 
 // The kernel's arguments, re-read: behind the empty asm the compiler no longer knows that the pointer is the one it has been loading
 // from, so what follows loads the arguments it needs where it needs them (scalar loads from the kernarg segment) instead of keeping

@@ -7,6 +7,7 @@
 #include "device/shade_pixel.h"
 #include "device/trace_wave.h"
 #include "launch_geometry.h"
+#include "symbol_readers.h"
 
 namespace glz {
 using namespace dev;
@@ -43,9 +44,7 @@ __device__ __forceinline__ void wave_handover_fence() {
 
 struct GroupHitSink {   // closest-hit record of ray i of the group -> the wave's LDS slots
   float4* hit;
-  __device__ __forceinline__ void store(uint32_t i, const HitRecord& h) {
-    hit[i] = make_float4(h.leaf == 0xFFFFFFFFu ? INFINITY : h.t, h.u, h.v, __uint_as_float(h.leaf));
-  }
+  __device__ __forceinline__ void store(uint32_t i, const HitRecord& h) { hit[i] = pack_hit(h); }
 };
 struct GroupQueue {     // shade_pixel's shadow-queue policy: entry k of the wave's own 64 (the lanes that push, in lane order)
   uint32_t base;
@@ -157,25 +156,15 @@ __global__ void __launch_bounds__(kBlock, GLZ_PATH_WAVES) k_path(const LaunchArg
   __shared__ uint4 s_top[kBvhTopNodes * 4];
   __shared__ float s_lut[256];
   __shared__ float4 s_hit[kBlock];
-  extern __shared__ uint4 s_dyn[];   // [RTMaterial x n_materials | RTLight x n_rt_lights | TexDesc x n_textures] when B.tables_in_lds
+  extern __shared__ uint4 s_dyn[];   // the scene tables (device/shade_pixel.h) when B.tables_in_lds
   stage_top(A.scene, s_top);
   s_lut[threadIdx.x] = A.scene.srgb_lut[threadIdx.x];
-  const uint32_t qm = A.scene.n_materials * (uint32_t)(sizeof(RTMaterial) / 16), ql = A.scene.n_rt_lights * (uint32_t)(sizeof(RTLight) / 16),
-                 qt = A.scene.n_textures * (uint32_t)(sizeof(TexDesc) / 16);
-  if (B.tables_in_lds) {
-    const uint4* gm = reinterpret_cast<const uint4*>(A.scene.materials);
-    const uint4* gl = reinterpret_cast<const uint4*>(A.scene.lights);
-    const uint4* gt = reinterpret_cast<const uint4*>(A.scene.tex_desc);
-    for (uint32_t i = threadIdx.x; i < qm + ql + qt; i += kBlock) s_dyn[i] = i < qm ? gm[i] : (i < qm + ql ? gl[i - qm] : gt[i - qm - ql]);
-  }
+  const SceneTables tables(A.scene);
+  if (B.tables_in_lds) tables.stage(A.scene, s_dyn, kBlock);
   __syncthreads();   // the only block-wide barrier: from here on the four waves of the block never wait for each other
   DeviceScene S = A.scene;
   S.srgb_lut = s_lut;
-  if (B.tables_in_lds) {
-    S.materials = reinterpret_cast<const RTMaterial*>(s_dyn);
-    S.lights = reinterpret_cast<const RTLight*>(s_dyn + qm);
-    S.tex_desc = reinterpret_cast<const TexDesc*>(s_dyn + qm + ql);
-  }
+  if (B.tables_in_lds) tables.use(S, s_dyn);
   // wave-uniform values in scalar registers: the compiler cannot see that threadIdx.x >> 6 is the same in all lanes of a wave
   const uint32_t wave_in_block = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t my_wave = blockIdx.x * (kBlock / 64) + wave_in_block;
@@ -261,10 +250,10 @@ __global__ void __launch_bounds__(kBlock, GLZ_PATH_WAVES) k_path(const LaunchArg
 #endif
 }
 
-// dynamic LDS of k_path: the scene's material / light / texture-descriptor tables when they fit kShadeTableBytes, else nothing
+// dynamic LDS of k_path: the scene's material / light / texture-descriptor tables when they fit kPathTableBytes, else nothing
 static uint32_t path_table_bytes(const DeviceScene& sc) {
-  const uint32_t bytes = sc.n_materials * (uint32_t)sizeof(RTMaterial) + sc.n_rt_lights * (uint32_t)sizeof(RTLight) + sc.n_textures * (uint32_t)sizeof(TexDesc);
-  return bytes <= kShadeTableBytes ? bytes : 0u;
+  const uint32_t bytes = SceneTables(sc).bytes();
+  return bytes <= kPathTableBytes ? bytes : 0u;
 }
 uint32_t path_resident_blocks(const DeviceScene& sc) {
   return resident_blocks(k_path<false>, path_table_bytes(sc), 2);
@@ -287,18 +276,11 @@ hipError_t launch_path(hipStream_t st, const LaunchArgs& a, const PathBatch& bat
 }  // namespace glz
 
 #ifdef GLZ_SECTION_TIMES
-extern "C" int glz_debug_sections_path(unsigned long long* out, int reset) {
-  int e = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(glz::g_sections), sizeof(unsigned long long) * 16 * 8192);
-  if (reset) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(glz::g_sections)) == hipSuccess) e = (int)hipMemset(p, 0, sizeof(unsigned long long) * 16 * 8192);
-  }
-  return e;
-}
+extern "C" int glz_debug_sections_path(unsigned long long* out, int reset) { return glz::read_device_symbol(out, glz::g_sections, sizeof(glz::g_sections), reset); }
 #endif
 #ifdef GLZ_PATH_TIMES
 extern "C" int glz_debug_path_times(unsigned long long* out, int n_waves) {
   if (n_waves > 8192) n_waves = 8192;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(glz::g_path_times), sizeof(unsigned long long) * 3 * (size_t)n_waves);
+  return glz::read_device_symbol(out, glz::g_path_times, sizeof(unsigned long long) * 3 * (size_t)n_waves, 0);
 }
 #endif

@@ -41,7 +41,7 @@ struct HitSink {
     const PixelId px = pixel_of(A.map, i);   // (BY_PIXEL) only rays CentreSource handed out arrive here: inside the image
     const size_t p = BY_PIXEL ? (size_t)px.y * A.map.width + px.x : i;
     const bool is_hit = h.leaf != 0xFFFFFFFFu;
-    hit[p] = make_float4(is_hit ? h.t : INFINITY, h.u, h.v, __uint_as_float(h.leaf));
+    hit[p] = pack_hit(h);
     inst[p] = is_hit ? (A.scene.two_level ? h.inst : A.scene.bvh_tris[h.leaf].instance) : 0xFFFFFFFFu;
   }
 };

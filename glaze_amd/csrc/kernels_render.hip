@@ -15,6 +15,7 @@
 #include "device/trace_wave.h"
 #include "device/trace_wave_tl.h"
 #include "launch_geometry.h"
+#include "symbol_readers.h"
 
 namespace glz {
 using namespace dev;
@@ -22,8 +23,8 @@ using namespace dev;
 // ---------------------------------------------------------------------------------------------
 // k_shade: path_trace.rgen:170-237 minus the two traceRayEXT calls, raytrace_hit.rchit:30-71
 // ---------------------------------------------------------------------------------------------
+// the sky's marginal cdf (H + 1 floats) is staged in LDS when it fits (the values and row integrals next to it are read once per sample, from memory: staging all 3 H + 1 floats was 12 of the 19 KB a block copies before it starts)
 constexpr uint32_t kSkyLdsFloats = 1088;   // (skies of up to 1 087 rows; a taller one is searched in memory)
-constexpr uint32_t kShadeLdsTableBytes = 8192;   // k_shade's LDS copy of the material / light / texture-descriptor tables (38 materials; larger tables are read from memory)   // the sky's marginal cdf (H + 1 floats) is staged in LDS when it fits (the values and row integrals next to it are read once per sample, from memory: staging all 3 H + 1 floats was 12 of the 19 KB a block copies before it starts)
 
 // (GLZ_SHADE_WAVES = 4, device/tuning.h: 128 VGPRs, 4 of them spilled, since the light's spectrum is made after the BSDF evaluation and the
 // importance is read where it is used (natural demand 152 -> 132): 0.357 -> 0.348 ms; at three waves the same code takes 0.363 ms.)
@@ -39,10 +40,7 @@ static __device__ unsigned long long g_shade_sections[16 * 4096];   // per wave 
 // whole grid, so launch_shade picks the instantiation).  The address space of every table pointer is then fixed when the kernel is
 // compiled -- LDS copies are read with ds_read, tables left in memory with global_load.  Chosen at run time the pointers were generic and
 // every lookup a FLAT access, which goes down the vector-memory path as well and waits on both counters: what the copies are there to avoid.
-__host__ __device__ inline uint32_t shade_table_quads(const DeviceScene& s) {   // [RTMaterial x n_materials | RTLight x n_rt_lights | TexDesc x n_textures] in 16-byte pieces
-  return s.n_materials * (uint32_t)(sizeof(RTMaterial) / 16) + s.n_rt_lights * (uint32_t)(sizeof(RTLight) / 16) + s.n_textures * (uint32_t)(sizeof(TexDesc) / 16);
-}
-__host__ __device__ inline bool shade_tables_fit(const DeviceScene& s) { return shade_table_quads(s) * 16u <= kShadeLdsTableBytes; }
+__host__ __device__ inline bool shade_tables_fit(const DeviceScene& s) { return SceneTables(s).bytes() <= kShadeLdsTableBytes; }
 __host__ __device__ inline bool shade_sky_fits(const DeviceScene& s) { return s.sky_header.marginal_cdf_count > 1u && s.sky_header.marginal_cdf_count <= kSkyLdsFloats; }
 // a pointer into device memory, said to be one: loads through it (and through what is derived from it) are global_load
 template <class T>
@@ -78,14 +76,8 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   if (SKY)
     for (uint32_t i = threadIdx.x; i < n_sky; i += kShadeBlock) s_sky[i] = A.scene.sky_marginal[i];
   s_bin[threadIdx.x] = 0;
-  const uint32_t qm = A.scene.n_materials * (uint32_t)(sizeof(RTMaterial) / 16), ql = A.scene.n_rt_lights * (uint32_t)(sizeof(RTLight) / 16),
-                 qt = A.scene.n_textures * (uint32_t)(sizeof(TexDesc) / 16);
-  if (TABLES) {
-    const uint4* gm = reinterpret_cast<const uint4*>(A.scene.materials);
-    const uint4* gl = reinterpret_cast<const uint4*>(A.scene.lights);
-    const uint4* gt = reinterpret_cast<const uint4*>(A.scene.tex_desc);
-    for (uint32_t i = threadIdx.x; i < qm + ql + qt; i += kShadeBlock) s_tables[i] = i < qm ? gm[i] : (i < qm + ql ? gl[i - qm] : gt[i - qm - ql]);
-  }
+  const SceneTables tables(A.scene);
+  if (TABLES) tables.stage(A.scene, s_tables, kShadeBlock);
   __syncthreads();
   GLZ_KS(0);   // tables staged
   DeviceScene S = A.scene;
@@ -94,9 +86,7 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   S.srgb_lut = s_lut;
   S.sky_cdf = SKY ? s_sky : in_memory(S.sky_cdf);
   if (TABLES) {
-    S.materials = reinterpret_cast<const RTMaterial*>(s_tables);
-    S.lights = reinterpret_cast<const RTLight*>(s_tables + qm);
-    S.tex_desc = reinterpret_cast<const TexDesc*>(s_tables + qm + ql);
+    tables.use(S, s_tables);
   } else {
     S.materials = in_memory(S.materials);
     S.lights = in_memory(S.lights);
@@ -269,7 +259,7 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE_WAVES) k_trace(const LaunchA
   stage_top(A.scene, s_top);
   int* aux = wave_aux(s_aux, threadIdx.x >> 6);
   int* links = wave_links(s_aux, threadIdx.x >> 6);
-  if (blockIdx.x == 0 && threadIdx.x < kQueueShards) A.st.queue_count[A.shade_set * kQueueSetWords + threadIdx.x * kCounterStride] = 0;
+  clear_next_queue_set(A);
   // counting build: the alpha tests' texture fetches are tallied through a copy of the scene that points at this thread's registers
   unsigned long long tex_tally[4] = {0ull, 0ull, 0ull, 0ull};
   DeviceScene counted_scene;
@@ -346,7 +336,7 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE8_WAVES) k_trace8(const Launc
   __shared__ alignas(1024) int s_aux[kAuxPerBlock];
   int* aux = wave_aux(s_aux, threadIdx.x >> 6);
   int* links = wave_links(s_aux, threadIdx.x >> 6);
-  if (blockIdx.x == 0 && threadIdx.x < kQueueShards) A.st.queue_count[A.shade_set * kQueueSetWords + threadIdx.x * kCounterStride] = 0;
+  clear_next_queue_set(A);
   if (A.do_closest) {
     TraceTally tally;
     ClosestSource src{A, A.frame, tally, 0u};
@@ -375,7 +365,7 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE8_WAVES) k_trace8(const Launc
 struct ClosestSinkTl {
   const LaunchArgs& A;
   __device__ __forceinline__ void store(uint32_t lid, const HitRecord& h) {
-    A.st.hit[lid] = make_float4(h.leaf == 0xFFFFFFFFu ? INFINITY : h.t, h.u, h.v, __uint_as_float(h.leaf));
+    A.st.hit[lid] = pack_hit(h);
     A.st.hit_inst[lid] = h.inst;
   }
 };
@@ -389,7 +379,7 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE_TL_WAVES) k_trace_tl(const L
   if (kTlLdsTop) stage_top(A.scene, s_top);
   int* aux = wave_aux(s_aux, threadIdx.x >> 6);
   int* links = wave_links(s_aux, threadIdx.x >> 6);
-  if (blockIdx.x == 0 && threadIdx.x < kQueueShards) A.st.queue_count[A.shade_set * kQueueSetWords + threadIdx.x * kCounterStride] = 0;
+  clear_next_queue_set(A);
   if (A.do_closest) {
     TraceTally tally;
     ClosestSource src{A, A.frame, tally, 0u};
@@ -534,28 +524,14 @@ hipError_t launch_tonemap(hipStream_t st, uint32_t n, const float4* result_frame
 }  // namespace glz
 
 #ifdef GLZ_SECTION_TIMES
-extern "C" int glz_debug_shade_sections(unsigned long long* out, int reset) {
-  int e = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(glz::g_shade_sections), sizeof(unsigned long long) * 16 * 4096);
-  if (reset) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(glz::g_shade_sections)) == hipSuccess) e = (int)hipMemset(p, 0, sizeof(unsigned long long) * 16 * 4096);
-  }
-  return e;
-}
+extern "C" int glz_debug_shade_sections(unsigned long long* out, int reset) { return glz::read_device_symbol(out, glz::g_shade_sections, sizeof(glz::g_shade_sections), reset); }
 // kernels_render.hip and kernels_path.hip each hold their own copy of g_sections (a __device__ array per translation unit): `which` 0 = k_trace's, see kernels_path.hip for k_path's
-extern "C" int glz_debug_sections_trace(unsigned long long* out, int reset) {
-  int e = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(glz::g_sections), sizeof(unsigned long long) * 16 * 8192);
-  if (reset) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(glz::g_sections)) == hipSuccess) e = (int)hipMemset(p, 0, sizeof(unsigned long long) * 16 * 8192);
-  }
-  return e;
-}
+extern "C" int glz_debug_sections_trace(unsigned long long* out, int reset) { return glz::read_device_symbol(out, glz::g_sections, sizeof(glz::g_sections), reset); }
 #endif
 #ifdef GLZ_WAVE_TIMES
 extern "C" int glz_debug_wave_times(unsigned long long* out, int n_waves) {
   if (n_waves > 8192) n_waves = 8192;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(glz::g_wave_times), sizeof(unsigned long long) * 3 * (size_t)n_waves);
+  return glz::read_device_symbol(out, glz::g_wave_times, sizeof(unsigned long long) * 3 * (size_t)n_waves, 0);
 }
 extern "C" int glz_debug_tl_stats(unsigned long long* out, int reset) {
   int e = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(glz::g_tl_stats), sizeof(unsigned long long) * 8);
@@ -567,6 +543,6 @@ extern "C" int glz_debug_tl_stats(unsigned long long* out, int reset) {
 }
 extern "C" int glz_debug_wave_stats(unsigned int* out, int n_waves) {
   if (n_waves > 8192) n_waves = 8192;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(glz::g_wave_stats), sizeof(unsigned int) * 8 * (size_t)n_waves);
+  return glz::read_device_symbol(out, glz::g_wave_stats, sizeof(unsigned int) * 8 * (size_t)n_waves, 0);
 }
 #endif
