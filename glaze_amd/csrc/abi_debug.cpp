@@ -69,7 +69,7 @@ int64_t read_array(const Scene& s, const void* dev, size_t bytes, void* out, int
 // triangle slot), and so do the meshes of a two-level scene, by leaf number within the mesh; what the read hooks hand out is the
 // structure as its readers walk it -- nodes whose leaf links are ~(first slot in the triangle array) -- so the links are translated.
 bool read_quads(const Scene* s, std::vector<BvhQuad>& quads, Error& e) {
-  quads.resize(s->d_quads_count());
+  quads.resize(s->accel().n_leaf_records());
   return quads.empty() || hip_ok(hipMemcpy(quads.data(), s->dev.bvh_quads, quads.size() * sizeof(BvhQuad), hipMemcpyDeviceToHost), "read leaf records", e);
 }
 // nodes [first, last) of an array of `width`-wide nodes whose links start at word `link_offset`; their leaves' records start at quad_base
@@ -120,7 +120,7 @@ int glz_debug_trace_closest(glz_scene* h, const float* o, const float* d, uint64
   Scene* s = h->s.get();
   return debug_call(s->instance, "debug trace", "k_debug_closest", [&](DebugCall& c) {
     return launch_debug_closest(c.st, s->dev, c.in(o, n * 3), c.in(d, n * 3), (uint32_t)n, tmin, c.out(t, n), c.out(tri, n), c.out(inst, n), c.out(u, n), c.out(v, n),
-                                c.out<uint32_t>(nullptr, (n + 512) * s->stack_overflow_depth), s->stack_overflow_depth);
+                                c.out<uint32_t>(nullptr, (n + 512) * s->accel().stack_overflow_depth), s->accel().stack_overflow_depth);
   });
   GLZ_GUARD_END(GLZ_E_IO)
 }
@@ -133,7 +133,7 @@ int glz_debug_trace_any(glz_scene* h, const float* o, const float* d, const floa
   Scene* s = h->s.get();
   return debug_call(s->instance, "debug trace", "k_debug_any", [&](DebugCall& c) {
     return launch_debug_any(c.st, s->dev, c.in(o, n * 3), c.in(d, n * 3), c.in(tmax, n), (uint32_t)n, tmin, c.out(out, n),
-                            c.out<uint32_t>(nullptr, (n + 512) * s->stack_overflow_depth), s->stack_overflow_depth);
+                            c.out<uint32_t>(nullptr, (n + 512) * s->accel().stack_overflow_depth), s->accel().stack_overflow_depth);
   });
   GLZ_GUARD_END(GLZ_E_IO)
 }
@@ -150,23 +150,23 @@ int64_t glz_debug_read_derivatives(glz_scene* h, float* out, int64_t cap_tris) {
 }
 int64_t glz_debug_read_rt_materials(glz_scene* h, void* out, int64_t cap) {
   if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");
-  return read_array(*h->s, h->s->dev.materials, h->s->h_materials.size() * sizeof(RTMaterial), out, cap, "read materials");
+  return read_array(*h->s, h->s->dev.materials, h->s->tables().h_materials.size() * sizeof(RTMaterial), out, cap, "read materials");
 }
 int64_t glz_debug_read_rt_lights(glz_scene* h, void* out, int64_t cap) {
   if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");
-  return read_array(*h->s, h->s->dev.lights, h->s->h_lights.size() * sizeof(RTLight), out, cap, "read lights");
+  return read_array(*h->s, h->s->dev.lights, h->s->tables().h_lights.size() * sizeof(RTLight), out, cap, "read lights");
 }
 int64_t glz_debug_read_sky(glz_scene* h, float* out, int64_t cap) {
   GLZ_GUARD_BEGIN
   if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");
   Scene* s = h->s.get();
-  std::vector<float> buf(36 + 4 + s->h_sky_marginal.size());
-  memcpy(buf.data(), &s->h_sky, 144);
-  memcpy(buf.data() + 36, &s->h_sky_header, 16);
-  if (!s->h_sky_marginal.empty()) {
+  std::vector<float> buf(36 + 4 + s->tables().h_sky_marginal.size());
+  memcpy(buf.data(), &s->tables().h_sky, 144);
+  memcpy(buf.data() + 36, &s->tables().h_sky_header, 16);
+  if (!s->tables().h_sky_marginal.empty()) {
     Error e;
     if (!hip_ok(hipSetDevice(s->instance->device), "hipSetDevice", e)) return fail(e);
-    if (!hip_ok(hipMemcpy(buf.data() + 40, s->dev.sky_marginal, s->h_sky_marginal.size() * 4, hipMemcpyDeviceToHost), "read sky", e)) return fail(e);
+    if (!hip_ok(hipMemcpy(buf.data() + 40, s->dev.sky_marginal, s->tables().h_sky_marginal.size() * 4, hipMemcpyDeviceToHost), "read sky", e)) return fail(e);
   }
   if (out && cap > 0) memcpy(out, buf.data(), (size_t)std::min<int64_t>(cap, (int64_t)buf.size()) * 4);
   return (int64_t)buf.size();
@@ -189,7 +189,7 @@ int64_t glz_debug_read_bvh(glz_scene* h, void* nodes_out, int64_t cap_nodes, voi
     const int64_t end = std::min(cap_nodes, nn);
     if (!s->dev.two_level) translate_leaf_links(nd, 4, 12, 0, end, 0, quads);
     else   // the meshes of a two-level scene: leaf number within the mesh -> ~(first slot within the mesh's triangles)
-      for (const Scene::MeshRange& m : s->h_mesh_ranges) translate_leaf_links(nd, 4, 12, m.node_base, std::min<int64_t>(end, (int64_t)m.node_base + m.n_nodes), m.quad_base, quads);
+      for (const Accel::MeshRange& m : s->accel().h_mesh_ranges) translate_leaf_links(nd, 4, 12, m.node_base, std::min<int64_t>(end, (int64_t)m.node_base + m.n_nodes), m.quad_base, quads);
   }
   if (tris_out && cap_tris > 0 && nt > 0 &&
       !hip_ok(hipMemcpy(tris_out, s->dev.bvh_tris, (size_t)std::min(cap_tris, nt) * sizeof(BvhTri), hipMemcpyDeviceToHost), "read tris", e))
@@ -200,7 +200,7 @@ int64_t glz_debug_read_bvh(glz_scene* h, void* nodes_out, int64_t cap_nodes, voi
 
 int64_t glz_debug_read_tlas_instances(glz_scene* h, void* out, int64_t cap) {
   if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");
-  return read_array(*h->s, h->s->dev.tlas_instances, h->s->n_tlas_records() * sizeof(TlasInstance), out, cap, "read instance records");
+  return read_array(*h->s, h->s->dev.tlas_instances, h->s->accel().n_tlas_records() * sizeof(TlasInstance), out, cap, "read instance records");
 }
 static int64_t write_boxes(const std::vector<float4>& lo, const std::vector<float4>& hi, float* lo4, float* hi4) {
   if (lo4 && !lo.empty()) memcpy(lo4, lo.data(), lo.size() * sizeof(float4));
@@ -210,14 +210,14 @@ static int64_t write_boxes(const std::vector<float4>& lo, const std::vector<floa
 int64_t glz_debug_instance_boxes(glz_scene* h, int on_device, uint64_t budget, float* lo4, float* hi4) {
   GLZ_GUARD_BEGIN
   if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");
-  if (!lo4 && !hi4) return (int64_t)(h->s->dev.two_level ? h->s->h_instances.size() : 0);   // the count alone, nothing computed
+  if (!lo4 && !hi4) return (int64_t)(h->s->dev.two_level ? h->s->info.n_instances : 0);   // the count alone, nothing computed
   std::vector<float4> lo, hi;
   Error e;
   if (!h->s->instance_boxes(on_device != 0, budget ? budget : kExactBoxBudget, lo, hi, e) && e.code != GLZ_OK) return fail(e);
   return write_boxes(lo, hi, lo4, hi4);
   GLZ_GUARD_END(GLZ_E_IO)
 }
-float glz_debug_box_kernel_ms(glz_scene* h) { return h && h->s ? h->s->box_kernel_ms : -1.0f; }
+float glz_debug_box_kernel_ms(glz_scene* h) { return h && h->s ? h->s->accel().box_kernel_ms : -1.0f; }
 int64_t glz_host_instance_boxes(const glz_scene_desc* d, uint64_t budget, float* lo4, float* hi4) {
   GLZ_GUARD_BEGIN
   if (!d) return fail(GLZ_E_ARG, "scene description is null");
@@ -342,12 +342,9 @@ int glz_debug_despeckle(glz_instance* inst, uint32_t w, uint32_t h, const float*
   const size_t n = (size_t)w * h;
   Error e;
   if (!hip_ok(hipSetDevice(inst->i->device), "hipSetDevice", e)) return fail(e);
-  hipEvent_t ev[2] = {};
-  for (auto& v : ev)
-    if (!hip_ok(hipEventCreate(&v), "hipEventCreate", e)) {
-      if (ev[0]) (void)hipEventDestroy(ev[0]);
-      return fail(e);
-    }
+  Events<2> events;
+  if (!events.create(e)) return fail(e);
+  hipEvent_t* ev = events.ev;
   const int rc = debug_call(inst->i.get(), "debug despeckle", "k_despeckle", [&](DebugCall& c) {
     const float4* r = c.in(reinterpret_cast<const float4*>(result), n);
     const float4* a0 = c.in(reinterpret_cast<const float4*>(aov0), n);
@@ -357,7 +354,6 @@ int glz_debug_despeckle(glz_instance* inst, uint32_t w, uint32_t h, const float*
     return launch_despeckle(c.st, w, h, D, P.eps_albedo, r, a0, a1, ping, c.out(reinterpret_cast<float4*>(out), n), ev);
   });
   if (rc == GLZ_OK && kernel_ms_out) (void)hipEventElapsedTime(kernel_ms_out, ev[0], ev[1]);   // debug_call has synchronised the stream
-  for (auto& v : ev) (void)hipEventDestroy(v);
   return rc;
   GLZ_GUARD_END(GLZ_E_IO)
 }
@@ -425,12 +421,9 @@ int glz_debug_reproject(glz_instance* inst, uint32_t w, uint32_t h, const float*
   const size_t n = (size_t)w * h;
   Error e;
   if (!hip_ok(hipSetDevice(inst->i->device), "hipSetDevice", e)) return fail(e);
-  hipEvent_t ev[2] = {};
-  for (auto& v : ev)
-    if (!hip_ok(hipEventCreate(&v), "hipEventCreate", e)) {
-      if (ev[0]) (void)hipEventDestroy(ev[0]);
-      return fail(e);
-    }
+  Events<2> events;
+  if (!events.create(e)) return fail(e);
+  hipEvent_t* ev = events.ev;
   const int rc = debug_call(inst->i.get(), "debug reproject", "k_reproject", [&](DebugCall& c) {
     const float4* m = c.in(reinterpret_cast<const float4*>(motion), n);
     const float4* cc = c.in(reinterpret_cast<const float4*>(color), n);
@@ -439,7 +432,6 @@ int glz_debug_reproject(glz_instance* inst, uint32_t w, uint32_t h, const float*
     return launch_reproject(c.st, w, h, P, m, cc, a0, a1, c.out(reinterpret_cast<float4*>(out), n), ev);
   });
   if (rc == GLZ_OK && kernel_ms_out) (void)hipEventElapsedTime(kernel_ms_out, ev[0], ev[1]);   // debug_call has synchronised the stream
-  for (auto& v : ev) (void)hipEventDestroy(v);
   return rc;
   GLZ_GUARD_END(GLZ_E_IO)
 }

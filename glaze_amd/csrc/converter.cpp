@@ -97,7 +97,7 @@ void set_name(char* dst, size_t cap, const std::string& s) {
 }  // namespace
 
 bool convert_obj(const std::string& input, const std::string& output, bool gen_mipmaps, ConvertReport* report, Error& err) {
-  auto fail = [&](int code, const std::string& m) { err.code = code; err.msg = m; return false; };
+  auto fail = [&](int code, const std::string& m) { return err.fail(code, m); };
   std::vector<uint8_t> bytes;
   if (!read_file(input, bytes)) return fail(GLZ_E_IO, "cannot open " + input);
   const std::string base = dir_of(input);

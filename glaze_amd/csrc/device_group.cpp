@@ -72,10 +72,7 @@ struct BackOnDevice {
 
 bool rccl_ok(const Rccl& nc, ncclResult_t r, const char* what, Error& err) {
   if (r == ncclSuccess) return true;
-  if (err.code == 0 || err.msg.empty()) {   // the first failure is the one reported
-    err.code = GLZ_E_DEVICE;
-    err.msg = std::string(what) + ": " + nc.GetErrorString(r);
-  }
+  if (err.code == 0 || err.msg.empty()) err.fail(GLZ_E_DEVICE, std::string(what) + ": " + nc.GetErrorString(r));   // the first failure is the one reported
   return false;
 }
 }  // namespace
@@ -252,9 +249,7 @@ bool DeviceGroup::add_stats(glz_render_stats* out, Error& err) {
 
 bool DeviceGroup::check(const int* devices, int n, Plan& plan, Error& err) const {
   auto bad = [&](const char* m) {
-    err.code = GLZ_E_ARG;
-    err.msg = m;
-    return false;
+    return err.fail(GLZ_E_ARG, m);
   };
   if (!devices || n < 1 || n > 64) return bad("set_devices: between 1 and 64 devices");
   if (devices[0] != root_.instance()->device) return bad("set_devices: the first device must be the renderer's own (glz_instance_device)");
@@ -288,11 +283,7 @@ bool DeviceGroup::check(const int* devices, int n, Plan& plan, Error& err) const
   if (n > 1 && !plan.loopback && plan.exchange != kExchangePeerCopy) {
     std::string why;
     plan.rccl = Rccl::get(why);
-    if (!plan.rccl) {
-      err.code = GLZ_E_DEVICE;
-      err.msg = why;
-      return false;
-    }
+    if (!plan.rccl) return err.fail(GLZ_E_DEVICE, why);
   }
   return true;
 }
@@ -340,11 +331,7 @@ bool DeviceGroup::build(const Plan& plan, Error& err) {
   if (nc) {
     std::vector<ncclComm_t> comms((size_t)n, nullptr);
     const ncclResult_t r = nc->CommInitAll(comms.data(), n, devices);
-    if (r != ncclSuccess) {
-      err.code = GLZ_E_DEVICE;
-      err.msg = std::string("ncclCommInitAll: ") + nc->GetErrorString(r);
-      return false;
-    }
+    if (r != ncclSuccess) return err.fail(GLZ_E_DEVICE, std::string("ncclCommInitAll: ") + nc->GetErrorString(r));
     for (ncclComm_t c : comms) comms_.push_back(c);
   }
   return true;
@@ -371,8 +358,7 @@ const Rccl* DeviceGroup::rccl(Error& err) const {
   std::string why;
   const Rccl* nc = Rccl::get(why);
   if (nc && comms_.size() == peers_.size() + 1) return nc;
-  err.code = GLZ_E_DEVICE;
-  err.msg = nc ? "RCCL communicators are missing" : why;
+  err.fail(GLZ_E_DEVICE, nc ? "RCCL communicators are missing" : why);
   return nullptr;
 }
 

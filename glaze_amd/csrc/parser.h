@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "glaze_abi.h"
@@ -13,6 +14,11 @@ namespace glz {
 struct Error {
   int code = GLZ_OK;
   std::string msg;
+  bool fail(int c, std::string m) {   // `return err.fail(code, "why");`
+    code = c;
+    msg = std::move(m);
+    return false;
+  }
 };
 
 struct TextureData {

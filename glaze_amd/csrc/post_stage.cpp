@@ -19,9 +19,7 @@ bool present(size_t n, const char* what, Error& err, Buffers&... buffers) {
   return false;
 }
 bool bad_argument(Error& err, const char* message) {
-  err.code = GLZ_E_ARG;
-  err.msg = message;
-  return false;
+  return err.fail(GLZ_E_ARG, message);
 }
 }  // namespace
 
@@ -52,7 +50,7 @@ bool PostStage::first_hit_pass(const FirstHitRequest& req, Error& err) {
   const size_t n = (size_t)r_.width() * r_.height();
   if (!present(n, "alloc first-hit records", err, fh_hit_, fh_inst_) || !present(n, "alloc feature buffers", err, aov0_, aov1_)) return false;
   const uint32_t blocks = first_hit_grid_blocks(a.map.n_local_pixels);
-  const uint32_t od = r_.scene()->stack_overflow_depth;
+  const uint32_t od = r_.scene()->accel().stack_overflow_depth;
   const size_t spill = (size_t)blocks * kTraceBlock * od;   // the scene may have changed since the last pass
   if (fh_overflow_.ptr == nullptr || fh_overflow_.count != spill)
     if (!hip_ok(fh_overflow_.alloc(spill), "alloc traversal spill", err)) {

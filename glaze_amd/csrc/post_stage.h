@@ -3,27 +3,13 @@
 // the instance's stream.  Its buffers and settings are its own; device, stream, scene, frame size and camera are the renderer's, read on
 // every call -- a new scene, camera or set of transforms needs no word to the stage, a new resolution only release().
 #pragma once
+#include "hip_util.h"
 #include "kernels.h"
 #include "scene.h"
 
 namespace glz {
 
 class Renderer;
-
-// N device events for one timed run: created together, destroyed with the holder
-template <int N>
-struct Events {
-  hipEvent_t ev[N] = {};
-  bool create(Error& err) {
-    for (auto& e : ev)
-      if (!hip_ok(hipEventCreate(&e), "hipEventCreate", err)) return false;
-    return true;
-  }
-  ~Events() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
 
 class PostStage {
  public:

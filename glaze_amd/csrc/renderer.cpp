@@ -42,8 +42,7 @@ Renderer* Renderer::create(Instance* inst, std::shared_ptr<Scene> scene, uint32_
   }
   r->scene_ = scene;
   if (w == 0 || h == 0) {
-    err.code = GLZ_E_ARG;
-    err.msg = "resolution must be non-zero";
+    err.fail(GLZ_E_ARG, "resolution must be non-zero");
     return nullptr;
   }
   r->w_ = w;
@@ -116,7 +115,7 @@ bool Renderer::allocate(Error& err) {
     wide8_ = scene_->dev.two_level == 0 && scene_->dev.bvh_nodes8 != nullptr && cfg_.node_width == 8;
   }
   const uint32_t S = pick_chains();
-  const uint32_t od = scene_->stack_overflow_depth;
+  const uint32_t od = scene_->accel().stack_overflow_depth;
   for (uint32_t s = 0; s < S; ++s) {
     std::unique_ptr<Chain> c(new Chain());
     if (s == 0) {
@@ -202,7 +201,7 @@ void Renderer::fill_args(const Chain& c, LaunchArgs& a) const {
   a.st.cumulative = c.cumulative.ptr;
   a.st.result = c.result.ptr;
   a.st.overflow = c.overflow.ptr;
-  a.st.overflow_depth = scene_->stack_overflow_depth;
+  a.st.overflow_depth = scene_->accel().stack_overflow_depth;
   a.st.path_cost = c.path_cost.ptr;
   a.map = c.map;
   a.cam = cfg_.cam;
@@ -308,7 +307,7 @@ bool Renderer::resolve(Error& err) {
 bool Renderer::launch_constants_common(FrameData& fd, Error& err) {
   if (request_new_frame_ && !reset_buffers(err)) return false;
   memset(&fd, 0, sizeof(fd));
-  fd.lights_no = scene_->lights_no;
+  fd.lights_no = scene_->tables().lights_no;
   fd.scene_radius = scene_->data.meta.scene_radius;
   fd.scene_size[0] = (float)w_;
   fd.scene_size[1] = (float)h_;
@@ -423,20 +422,12 @@ bool Renderer::resize(A apply, Error& err) {
 }
 
 bool Renderer::set_launch_mode(int mode, Error& err) {
-  if (mode < 0 || mode > 2) {
-    err.code = GLZ_E_ARG;
-    err.msg = "launch mode must be 0 (automatic), 1 (two kernels per launch) or 2 (per-wave launch loop)";
-    return false;
-  }
+  if (mode < 0 || mode > 2) return err.fail(GLZ_E_ARG, "launch mode must be 0 (automatic), 1 (two kernels per launch) or 2 (per-wave launch loop)");
   return resize([&] { cfg_.launch_mode = mode; }, err) && group_.forward([=](Renderer& p, Error& e) { return p.set_launch_mode(mode, e); }, err);
 }
 
 bool Renderer::set_node_width(int width, Error& err) {
-  if (width != 0 && width != 4 && width != 8) {
-    err.code = GLZ_E_ARG;
-    err.msg = "node width must be 0 (automatic), 4 or 8";
-    return false;
-  }
+  if (width != 0 && width != 4 && width != 8) return err.fail(GLZ_E_ARG, "node width must be 0 (automatic), 4 or 8");
   return resize([&] { cfg_.node_width = width; }, err) && group_.forward([=](Renderer& p, Error& e) { return p.set_node_width(width, e); }, err);
 }
 
@@ -493,11 +484,7 @@ void Renderer::enable_counters(int flags) {
 }
 
 bool Renderer::set_integrator(int integrator, Error& err) {
-  if (integrator != GLZ_DIRECT && integrator != GLZ_PATH_TRACE) {
-    err.code = GLZ_E_ARG;
-    err.msg = "unknown integrator";
-    return false;
-  }
+  if (integrator != GLZ_DIRECT && integrator != GLZ_PATH_TRACE) return err.fail(GLZ_E_ARG, "unknown integrator");
   if (integrator != cfg_.integrator) {   // raytracer.rs:197
     cfg_.integrator = integrator;
     request_new_frame_ = true;
@@ -517,11 +504,7 @@ bool Renderer::set_exposure(float e, Error& err) {
 }
 
 bool Renderer::update_camera(const glz_camera& c, Error& err) {
-  if (c.type > GLZ_CAMERA_ORTHOGRAPHIC) {
-    err.code = GLZ_E_ARG;
-    err.msg = "unknown camera type";
-    return false;
-  }
+  if (c.type > GLZ_CAMERA_ORTHOGRAPHIC) return err.fail(GLZ_E_ARG, "unknown camera type");
   cfg_.camera = c;
   host::push_constants(cfg_.camera, w_, h_, cfg_.cam.camera2world, cfg_.cam.screen2camera);
   request_new_frame_ = true;
@@ -530,11 +513,7 @@ bool Renderer::update_camera(const glz_camera& c, Error& err) {
 }
 
 bool Renderer::change_resolution(uint32_t w, uint32_t h, Error& err) {
-  if (w == 0 || h == 0) {
-    err.code = GLZ_E_ARG;
-    err.msg = "resolution must be non-zero";
-    return false;
-  }
+  if (w == 0 || h == 0) return err.fail(GLZ_E_ARG, "resolution must be non-zero");
   if (!resize([&] {
         w_ = w;
         h_ = h;
@@ -545,11 +524,7 @@ bool Renderer::change_resolution(uint32_t w, uint32_t h, Error& err) {
 }
 
 bool Renderer::change_scene(std::shared_ptr<Scene> scene, Error& err) {
-  if (!scene) {
-    err.code = GLZ_E_ARG;
-    err.msg = "scene is null";
-    return false;
-  }
+  if (!scene) return err.fail(GLZ_E_ARG, "scene is null");
   // the other GPUs of this process get replicas of the new scene, in the shape (flattened / two levels) this device built
   if (!resize([&] {
         scene_ = scene;
@@ -564,10 +539,10 @@ bool Renderer::change_scene(std::shared_ptr<Scene> scene, Error& err) {
 template <class U>
 bool Renderer::update_scene(U update, Error& err) {
   if (!wait_idle(err)) return false;
-  const uint32_t od = scene_->stack_overflow_depth;
+  const uint32_t od = scene_->accel().stack_overflow_depth;
   const bool wide8 = scene_->dev.bvh_nodes8 != nullptr;
   if (!update()) return false;
-  if ((scene_->stack_overflow_depth != od || (scene_->dev.bvh_nodes8 != nullptr) != wide8) && !allocate(err)) return false;
+  if ((scene_->accel().stack_overflow_depth != od || (scene_->dev.bvh_nodes8 != nullptr) != wide8) && !allocate(err)) return false;
   request_new_frame_ = true;
   return true;
 }
@@ -707,9 +682,7 @@ bool Renderer::read_rgba8(uint8_t* out, Error& err) {
 // process's own devices: gather() brings their tiles)
 bool Renderer::frame_is_here(const char* who, Error& err) const {
   if (world_ <= 1 || !group_.empty()) return true;
-  err.code = GLZ_E_ARG;
-  err.msg = std::string(who) + ": under set_partition(world > 1) the frame is not in this process";
-  return false;
+  return err.fail(GLZ_E_ARG, std::string(who) + ": under set_partition(world > 1) the frame is not in this process");
 }
 
 bool Renderer::time_post(float ms[GLZ_POST_TIMING_SLOTS], Error& err) {
@@ -739,11 +712,7 @@ bool Renderer::read_post(bool filter, float* rgba32f, uint8_t* rgba8, Error& err
 }
 
 bool Renderer::set_texture_lod(int mode, Error& err) {
-  if (mode != 0 && mode != 1 && mode != 2) {
-    err.code = GLZ_E_ARG;
-    err.msg = "texture LOD mode must be 0 (level 0), 1 (ray cones) or 2 (ray cones, anisotropic footprint)";
-    return false;
-  }
+  if (mode != 0 && mode != 1 && mode != 2) return err.fail(GLZ_E_ARG, "texture LOD mode must be 0 (level 0), 1 (ray cones) or 2 (ray cones, anisotropic footprint)");
   cfg_.lod_mode = mode;
   request_new_frame_ = true;
   return group_.forward([=](Renderer& p, Error& e) { return p.set_texture_lod(mode, e); }, err);
@@ -757,11 +726,7 @@ bool Renderer::set_seed(uint64_t s) {
 }
 
 bool Renderer::set_depth(uint32_t d, Error& err) {
-  if (d == 0 || d > 1024) {
-    err.code = GLZ_E_ARG;
-    err.msg = "depth (PT_STEPS) must be in 1..1024";
-    return false;
-  }
+  if (d == 0 || d > 1024) return err.fail(GLZ_E_ARG, "depth (PT_STEPS) must be in 1..1024");
   cfg_.pt_steps = d;
   request_new_frame_ = true;
   bool ok = true;
@@ -770,20 +735,12 @@ bool Renderer::set_depth(uint32_t d, Error& err) {
 }
 
 bool Renderer::set_partition(uint32_t rank, uint32_t world, Error& err) {
-  if (!group_.empty()) {
-    err.code = GLZ_E_ARG;
-    err.msg = "a renderer that spans several devices (set_devices) cannot also be one rank of a process partition";
-    return false;
-  }
+  if (!group_.empty()) return err.fail(GLZ_E_ARG, "a renderer that spans several devices (set_devices) cannot also be one rank of a process partition");
   return set_partition_local(rank, world, err);
 }
 
 bool Renderer::set_partition_local(uint32_t rank, uint32_t world, Error& err) {
-  if (world == 0 || rank >= world) {
-    err.code = GLZ_E_ARG;
-    err.msg = "bad tile partition";
-    return false;
-  }
+  if (world == 0 || rank >= world) return err.fail(GLZ_E_ARG, "bad tile partition");
   if (!wait_idle_local("set_partition", err)) return false;
   rank_ = rank;
   world_ = world;
@@ -793,11 +750,7 @@ bool Renderer::set_partition_local(uint32_t rank, uint32_t world, Error& err) {
 // The group checks the list, the environment and RCCL before anything is touched; from the release of the old peers on every failure
 // leaves ONE device rendering the whole frame, with a new frame requested.
 bool Renderer::set_devices(const int* devices, int n, Error& err) {
-  if (world_ != 1 && group_.empty()) {
-    err.code = GLZ_E_ARG;
-    err.msg = "set_devices: this renderer is one rank of a process partition (set_partition)";
-    return false;
-  }
+  if (world_ != 1 && group_.empty()) return err.fail(GLZ_E_ARG, "set_devices: this renderer is one rank of a process partition (set_partition)");
   DeviceGroup::Plan plan;
   if (!group_.check(devices, n, plan, err)) return false;
   if (!wait_idle(err)) return false;
@@ -811,11 +764,7 @@ bool Renderer::set_devices(const int* devices, int n, Error& err) {
 }
 
 bool Renderer::set_chains(uint32_t n, Error& err) {
-  if (n > 16) {
-    err.code = GLZ_E_ARG;
-    err.msg = "at most 16 chains";
-    return false;
-  }
+  if (n > 16) return err.fail(GLZ_E_ARG, "at most 16 chains");
   return resize([&] { cfg_.chains_wanted = n; }, err) && group_.forward([=](Renderer& p, Error& e) { return p.set_chains(n, e); }, err);
 }
 
@@ -832,11 +781,7 @@ size_t Renderer::packed_count(uint32_t w, uint32_t h, uint32_t rank, uint32_t wo
   return make_tile_map(w, h, rank, world).n_local_pixels;
 }
 bool Renderer::export_packed(int which, void* dev, Error& err) {
-  if (!group_.empty()) {
-    err.code = GLZ_E_ARG;
-    err.msg = "export_packed is for one rank of a process partition (a renderer that spans devices exchanges by itself)";
-    return false;
-  }
+  if (!group_.empty()) return err.fail(GLZ_E_ARG, "export_packed is for one rank of a process partition (a renderer that spans devices exchanges by itself)");
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   if (!settle(err)) return false;
   hipStream_t st = chains_[0]->stream;
@@ -849,11 +794,7 @@ bool Renderer::export_packed(int which, void* dev, Error& err) {
 }
 // rank 0 of such a job: the packed tiles of partition (rank, world) go to their place in a full frame (nothing else is touched)
 bool Renderer::scatter_packed(uint32_t rank, uint32_t world, const void* dev_packed, void* dev_frame, Error& err) {
-  if (world == 0 || rank >= world) {
-    err.code = GLZ_E_ARG;
-    err.msg = "bad tile partition";
-    return false;
-  }
+  if (world == 0 || rank >= world) return err.fail(GLZ_E_ARG, "bad tile partition");
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   hipStream_t st = chains_[0]->stream;
   if (!hip_ok(launch_export(st, make_tile_map(w_, h_, rank, world), static_cast<const float4*>(dev_packed), static_cast<float4*>(dev_frame), false), "k_export (packed tiles)", err)) return false;
@@ -861,11 +802,7 @@ bool Renderer::scatter_packed(uint32_t rank, uint32_t world, const void* dev_pac
 }
 
 bool Renderer::scatter_packed_all(uint32_t world, const void* dev_packed, uint64_t stride_pixels, void* dev_frame, Error& err) {
-  if (world == 0 || stride_pixels < packed_count(w_, h_, 0, world)) {
-    err.code = GLZ_E_ARG;
-    err.msg = "scatter_packed_all: the parts must lie at least packed_pixels(0, world) pixels apart";
-    return false;
-  }
+  if (world == 0 || stride_pixels < packed_count(w_, h_, 0, world)) return err.fail(GLZ_E_ARG, "scatter_packed_all: the parts must lie at least packed_pixels(0, world) pixels apart");
   if (!hip_ok(hipSetDevice(inst_->device), "hipSetDevice", err)) return false;
   hipStream_t st = chains_[0]->stream;
   for (uint32_t rank = 0; rank < world; ++rank) {

@@ -58,8 +58,7 @@ ChunkBytes encode_meshes(const glz_mesh* m, uint64_t n, const uint32_t* indices,
   Dynamic d(n);
   for (uint64_t i = 0; i < n; ++i) {   // mesh_to_bytes, v1.rs:669-681: id u16, index count u32, material u16, indices
     if ((uint64_t)m[i].index_offset + m[i].index_count > n_indices) {
-      err.code = GLZ_E_INVALID_INPUT;
-      err.msg = "mesh index range outside the index array";
+      err.fail(GLZ_E_INVALID_INPUT, "mesh index range outside the index array");
       return {};
     }
     std::vector<uint8_t> rec;
@@ -177,8 +176,7 @@ ChunkBytes encode_textures(const glz_texture* t, uint64_t n, Error& err) {
     const glz_texture& tx = t[i];
     const int channels = tx.format == GLZ_TEX_GRAY ? 1 : 4;
     if (tx.format < 1 || tx.format > 3 || !tx.pixels || !tx.width || !tx.height) {
-      err.code = GLZ_E_INVALID_INPUT;
-      err.msg = "texture without pixels or with an unknown format";
+      err.fail(GLZ_E_INVALID_INPUT, "texture without pixels or with an unknown format");
       return {};
     }
     std::vector<uint8_t> rec;
@@ -193,8 +191,7 @@ ChunkBytes encode_textures(const glz_texture* t, uint64_t n, Error& err) {
     for (size_t lvl = 0; lvl <= mips.size(); ++lvl) {
       std::vector<uint8_t> png;
       if (!png_encode(lvl == 0 ? tx.pixels : mips[lvl - 1].data(), w, h, channels, png)) {
-        err.code = GLZ_E_INVALID_INPUT;
-        err.msg = "Failed to encode texture";
+        err.fail(GLZ_E_INVALID_INPUT, "Failed to encode texture");
         return {};
       }
       put32(rec, (uint32_t)png.size());
@@ -279,19 +276,11 @@ bool write_glaze_file(const std::string& path, const std::vector<std::pair<int, 
   put64(head, xxh64(table.data(), table.size(), kHasherSeed));
   head.insert(head.end(), table.begin(), table.end());
   FILE* f = fopen(path.c_str(), "wb");
-  if (!f) {
-    err.code = GLZ_E_IO;
-    err.msg = "cannot create " + path;
-    return false;
-  }
+  if (!f) return err.fail(GLZ_E_IO, "cannot create " + path);
   bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
   for (const auto* c : live) ok = ok && fwrite(c->second.data(), 1, c->second.size(), f) == c->second.size();
   ok = (fclose(f) == 0) && ok;
-  if (!ok) {
-    err.code = GLZ_E_IO;
-    err.msg = "short write on " + path;
-  }
-  return ok;
+  return ok || err.fail(GLZ_E_IO, "short write on " + path);
 }
 
 bool serialize_scene(const std::string& path, const SerializeInput& in, Error& err) {

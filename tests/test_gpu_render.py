@@ -405,7 +405,9 @@ def test_update_textures_through_update_materials_and_lights(instance):
         r.update_materials_and_lights(mats, desc.lights, more[:2])
     with pytest.raises(abi.GlazeError):
         r.update_materials_and_lights(desc.materials, desc.lights, more[:1])
-    r.step(1)                                                                                     # failed updates left the scene usable
+    r.restart()                                                                                   # failed updates left the scene usable, and as it was
+    r.step(6)
+    assert_parity(r, o, "after rejected updates")
 
 
 def test_refresh_binded_textures_keeps_accumulating(instance):

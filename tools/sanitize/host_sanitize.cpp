@@ -1,5 +1,6 @@
 // AddressSanitizer / UBSan run of the host-only parts of libglaze_hip (the GPU parts cannot run under sanitizers on
-// this pool): .glaze reader and writer with their own xz / PNG / JPEG codecs, the OBJ converter and the host SAH builder.
+// this pool): .glaze reader and writer with their own xz / PNG / JPEG codecs, the OBJ converter, the host SAH builder and the host
+// rule of the instance boxes.
 // Built and run by tools/sanitize/run.sh; exits non-zero on the first failure (the sanitizers abort on their findings).
 #include <cmath>
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include "codec/png_dec.h"
 #include "codec/png_enc.h"
 #include "converter.h"
+#include "instance_boxes.h"
 #include "kernels.h"
 #include "parser.h"
 #include "serializer.h"
@@ -165,6 +167,89 @@ int main(int argc, char** argv) {
         for (int link : {children[i].x, children[i].y}) seen[link >= 0 ? link : (int)(n - 1) + ~link]++;
       for (size_t s = 1; s < seen.size(); ++s) REQUIRE(seen[s] == 1);
     }
+  }
+  // 7. the host rule of the instance boxes (instance_boxes.cpp) on the fixture and on degenerate descriptions: every box ordered and finite
+  {
+    auto quad_scene = [] {   // one mesh of two triangles over four vertices, instanced three times
+      SceneData d;
+      const float corners[4][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 2}};
+      for (const auto& c : corners) {
+        glz_vertex v{};
+        for (int k = 0; k < 3; ++k) v.vv[k] = c[k];
+        d.vertices.push_back(v);
+      }
+      d.indices = {0, 1, 2, 0, 2, 3};
+      glz_mesh m{};
+      m.id = 7;
+      m.index_offset = 0;
+      m.index_count = 6;
+      d.meshes.push_back(m);
+      for (uint32_t i = 0; i < 3; ++i) {
+        glz_transform t = identity_transform();
+        t.m[12] = 3.0f * (float)i;
+        d.transforms.push_back(t);
+        glz_mesh_instance in{};
+        in.mesh_id = 7;
+        in.transform_id = i;
+        d.instances.push_back(in);
+      }
+      return d;
+    };
+    std::vector<SceneData> cases;
+    std::vector<size_t> boxes_expected;
+    cases.push_back(sd);   // the fixture
+    boxes_expected.push_back(rt_instances(sd).size());
+    cases.push_back(quad_scene());
+    boxes_expected.push_back(3);
+    {
+      SceneData d = quad_scene();   // no instances
+      d.instances.clear();
+      cases.push_back(d);
+      boxes_expected.push_back(0);
+    }
+    {
+      SceneData d = quad_scene();   // an instance naming a missing mesh: dropped
+      d.instances[1].mesh_id = 99;
+      cases.push_back(d);
+      boxes_expected.push_back(2);
+    }
+    {
+      SceneData d = quad_scene();   // a mesh of zero triangles
+      d.meshes[0].index_count = 0;
+      cases.push_back(d);
+      boxes_expected.push_back(3);
+    }
+    {
+      SceneData d = quad_scene();   // a transform with a NaN and one with an infinity
+      d.transforms[0].m[5] = NAN;
+      d.transforms[2].m[13] = INFINITY;
+      cases.push_back(d);
+      boxes_expected.push_back(3);
+    }
+    for (size_t c = 0; c < cases.size(); ++c)
+      for (uint64_t budget : {(uint64_t)1, (uint64_t)7, kExactBoxBudget}) {
+        std::vector<float4> lo, hi;
+        REQUIRE(host_instance_boxes_of(cases[c], budget, lo, hi, err));
+        REQUIRE(lo.size() == boxes_expected[c] && hi.size() == lo.size());
+        const std::vector<RTInstance> inst = rt_instances(cases[c]);
+        for (size_t i = 0; i < lo.size(); ++i) {
+          const float l[3] = {lo[i].x, lo[i].y, lo[i].z}, h[3] = {hi[i].x, hi[i].y, hi[i].z};
+          const float* M = cases[c].transforms[inst[i].transform_id].m;
+          for (int k = 0; k < 3; ++k) {
+            // an infinity in the transform's row k puts every point of that axis at infinity: the rule answers with the whole axis
+            // (tests/test_instance_boxes.py asserts it); everything else, a NaN included, gives an ordered finite box
+            const bool whole_axis = std::isinf(M[k]) || std::isinf(M[4 + k]) || std::isinf(M[8 + k]) || std::isinf(M[12 + k]);
+            if (whole_axis) REQUIRE(l[k] == -INFINITY && h[k] == INFINITY);
+            else REQUIRE(std::isfinite(l[k]) && std::isfinite(h[k]) && l[k] <= h[k]);
+          }
+        }
+        (void)instance_reach(lo, hi);
+      }
+    SceneData bad = quad_scene();   // an index past the vertices is reported, not followed
+    bad.indices[4] = 4;
+    std::vector<float4> lo, hi;
+    Error e2;
+    REQUIRE(!host_instance_boxes_of(bad, kExactBoxBudget, lo, hi, e2) && e2.code == GLZ_E_INVALID_DATA);
   }
   printf("host sanitize: ok\n");
   return 0;
