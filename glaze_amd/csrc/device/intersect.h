@@ -44,9 +44,20 @@ __device__ __forceinline__ uint32_t slab_sel(float ig) { return ig < 0.0f ? kSla
 // far plane picked by the ray's sign such a box has t_near > t_far on every axis whatever the ray (the planes are 32 767 cells the
 // wrong way round; distances are never NaN) -- four compares fewer per node visit.  The two-level tracer widens boxes by a per-ray
 // pad that may exceed that in extreme cases and keeps the check.
-template <bool CHECK_LINK = true>
+// ORDER: which child a sorted key sequence names first.  Any-hit rays (GLZ_ANY_FAR_FIRST, trace_wave) want the child entered LAST:
+//   kKeysNearFirst  the key above; the caller sorts ascending.
+//   kKeysFarFirst   every ray of the pass is an any-hit ray: the same key with bit 0 set, 0 for a miss, and the caller sorts DESCENDING --
+//                   no instruction more than nearest first.  Bit 0 keeps the key of child 0 at t0 == 0 (tmin is the caller's in the debug
+//                   kernels) apart from the miss marker; it lies below the child bits and no one reads it.
+//   kKeysPerLane    rays of both kinds in one pass (k_path's MIXED pass): `flip` = kKeyDistanceMask in an any-hit lane, 0 in a closest-hit
+//                   lane -- the distance bits complemented, so that the ascending sort puts the farthest first; one v_xor_b32 per child.
+//                   The largest such key is 0xFFFFFC00 | k, never the miss marker.
+constexpr int kKeysNearFirst = 0, kKeysFarFirst = 1, kKeysPerLane = 2;
+template <int ORDER>
+constexpr uint32_t kKeyMiss = ORDER == kKeysFarFirst ? 0u : 0xFFFFFFFFu;
+template <bool CHECK_LINK = true, int ORDER = kKeysNearFirst>
 __device__ __forceinline__ uint32_t box_key(uint32_t wx, uint32_t wy, uint32_t wz, uint32_t link, uint32_t k, SlabSel sel, vec3 ig, vec3 cgn, vec3 cgf,
-                                            float tmin, float tmax) {
+                                            float tmin, float tmax, uint32_t flip = 0u) {
   // v_perm_b32: bytes 0..3 of the selector index the second operand, 4..7 the first (the node word), 0x0C is a zero byte
   const float nx = __uint_as_float(__builtin_amdgcn_perm(wx, kSlabMagic, sel.x)), fx = __uint_as_float(__builtin_amdgcn_perm(wx, kSlabMagic, sel.x ^ kSlabSelFlip));
   const float ny = __uint_as_float(__builtin_amdgcn_perm(wy, kSlabMagic, sel.y)), fy = __uint_as_float(__builtin_amdgcn_perm(wy, kSlabMagic, sel.y ^ kSlabSelFlip));
@@ -56,10 +67,13 @@ __device__ __forceinline__ uint32_t box_key(uint32_t wx, uint32_t wy, uint32_t w
   const f32x2 tz = __builtin_elementwise_fma(f32x2{nz, fz}, f32x2{ig.z, ig.z}, f32x2{cgn.z, cgf.z});
   const float t0 = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, tmin));
   const float t1 = fminf(fminf(tx.y, ty.y), fminf(tz.y, tmax));
-  return (t0 <= t1 && (!CHECK_LINK || link != (uint32_t)kBvhEmptyChild)) ? ((__float_as_uint(t0) & kKeyDistanceMask) | k) : 0xFFFFFFFFu;
+  const uint32_t bits = ORDER == kKeysPerLane ? __float_as_uint(t0) ^ flip : __float_as_uint(t0);
+  return (t0 <= t1 && (!CHECK_LINK || link != (uint32_t)kBvhEmptyChild)) ? ((bits & kKeyDistanceMask) | k | (ORDER == kKeysFarFirst ? 1u : 0u)) : kKeyMiss<ORDER>;
 }
 // The same test for a child of an 8-wide node (types.h BvhNode8): the child index takes three bits of the key (8..10)
+// FAR (a pass of any-hit rays): bit 0 set and 0 for a miss, as kKeysFarFirst above -- the caller picks the LARGEST key
 constexpr uint32_t kKey8DistanceMask = 0xFFFFF800u, kKey8ChildMask = 0x700u;
+template <bool FAR = false>
 __device__ __forceinline__ uint32_t box_key8(uint32_t wx, uint32_t wy, uint32_t wz, uint32_t k, SlabSel sel, vec3 ig, vec3 cg, float tmin, float tmax) {
   const float nx = __uint_as_float(__builtin_amdgcn_perm(wx, kSlabMagic, sel.x)), fx = __uint_as_float(__builtin_amdgcn_perm(wx, kSlabMagic, sel.x ^ kSlabSelFlip));
   const float ny = __uint_as_float(__builtin_amdgcn_perm(wy, kSlabMagic, sel.y)), fy = __uint_as_float(__builtin_amdgcn_perm(wy, kSlabMagic, sel.y ^ kSlabSelFlip));
@@ -69,7 +83,7 @@ __device__ __forceinline__ uint32_t box_key8(uint32_t wx, uint32_t wy, uint32_t 
   const f32x2 tz = __builtin_elementwise_fma(f32x2{nz, fz}, f32x2{ig.z, ig.z}, f32x2{cg.z, cg.z});
   const float t0 = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, tmin));
   const float t1 = fminf(fminf(tx.y, ty.y), fminf(tz.y, tmax));
-  return t0 <= t1 ? ((__float_as_uint(t0) & kKey8DistanceMask) | k) : 0xFFFFFFFFu;   // (an unused slot's box is inverted: no ray enters it)
+  return t0 <= t1 ? ((__float_as_uint(t0) & kKey8DistanceMask) | k | (FAR ? 1u : 0u)) : (FAR ? 0u : 0xFFFFFFFFu);   // (an unused slot's box is inverted: no ray enters it)
 }
 // the addend of a plane distance: plane q (a float 32768 + q out of box_key) is crossed at t = (32768 + q) ig + grid_addend = q ig - og ig
 __device__ __forceinline__ float grid_addend(float og, float ig) { return fmaf(-32768.0f, ig, -(og * ig)); }

@@ -76,6 +76,11 @@ struct TraceTally {
 //   * inner-node phase: lanes sitting on an inner node test its four child boxes, descend into the nearest
 //     hit child and push the others farthest first; lanes that reached a leaf wait.  The phase ends when no lane is on an
 //     inner node, or when at least kLeafQuorum lanes are waiting on a leaf.
+//     A lane with an ANY-HIT ray does the opposite (GLZ_ANY_FAR_FIRST): it descends into the hit child with the LARGEST entry distance and
+//     pushes the others nearest first, so that the next-farthest is popped next.  Nearest first is the order for finding the nearest hit; a
+//     shadow ray only has to find one, and what occludes it in a scene with walls and a roof stands at its far end -- the small boxes
+//     around the surface it leaves almost never do (tools/bvh_lab anyorder=: 15.6 -> 10.6 node visits, 2.02 -> 1.13 leaf visits per shadow
+//     ray of the bench scene).  The counting kernels walk both kinds nearest first: their counts are defined by the oracle's walk.
 //   * leaf phase: every lane on a leaf runs the exact ray/triangle test once, then pops its stack.
 //   * share / merge (only once the wave's sequence is exhausted, i.e. in the tail): an idle lane takes the OLDEST
 //     pending subtree off the LDS stack of a busy lane (the stacks are LDS columns, so any lane can reach them),
@@ -127,10 +132,11 @@ __device__ __forceinline__ void rotate_priority(uint32_t turn) {
 __device__ __forceinline__ int sorted_link(uint32_t base, uint32_t key) {
   return *(LdsIntPtr)(uintptr_t)((key & kKeyChildMask) | base);
 }
+template <bool DESCENDING = false>   // (DESCENDING: a pass of any-hit rays, box_key<kKeysFarFirst>)
 __device__ __forceinline__ void sort2(uint32_t& a, uint32_t& b) {
   const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-  a = lo;
-  b = hi;
+  a = DESCENDING ? hi : lo;
+  b = DESCENDING ? lo : hi;
 }
 
 // The staged nodes are read through a pointer that keeps its LDS address space: with a generic pointer the compiler
@@ -178,7 +184,7 @@ __device__ unsigned long long g_tl_stats[8];      // two-level tracer, summed ov
 // one 64-ray group per resident wave is bound by the LATENCY of a ray's chain of dependent node fetches (1 800 - 2 100 clocks per node
 // iteration whatever the load), and eight-wide that chain is 31 % shorter (17.3 against 24.9 visits per sample on the bench scene,
 // tools/bvh_lab); the full frame is bound by VALU issue and by the address units, where twice the boxes per visit cost more than the
-// visits saved (it keeps the 4-wide nodes).  The nearest child is entered, the others are pushed in slot order -- no sort: ordering the
+// visits saved (it keeps the 4-wide nodes).  The nearest child is entered (the farthest in its pass of any-hit rays), the others are pushed in slot order -- no sort: ordering the
 // rest by distance as well saves 0.7 % of the visits (tools/bvh_lab order=nearest) for 38 instructions a visit; the child links are
 // picked in registers (a select tree on the key's child bits) rather than through LDS, one round trip less on the chain.  Hits do not
 // depend on the visit order, so the images are those of the 4-wide walk bit for bit.  No staged top (the root is node 0), a deeper LDS
@@ -193,6 +199,11 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
   constexpr bool SHARE = !COUNT;
   constexpr bool TOP = !WIDE8;   // the top kBvhTopNodes nodes of the tree come from a per-block LDS copy ("LDS-staged node packets", stage_top)
   constexpr int kLevels = WIDE8 ? kLdsStack8 : kLdsStack;
+  // the order of a node's children (box_key): any-hit rays farthest first, per pass where the pass has one kind of ray, per lane in a MIXED pass
+  constexpr bool FAR = GLZ_ANY_FAR_FIRST != 0 && (!COUNT || GLZ_COUNT_ANY_FAR_FIRST != 0);
+  constexpr int ORDER = !FAR ? kKeysNearFirst : (ANY ? kKeysFarFirst : (MIXED ? kKeysPerLane : kKeysNearFirst));
+  static_assert(!(WIDE8 && MIXED), "the 8-wide walk picks its first child per pass");
+  constexpr uint32_t kMiss = kKeyMiss<ORDER>;
   const BvhNode8* __restrict__ nodes8 = S.bvh_nodes8;
   constexpr uint32_t kNone = 0xFFFFFFFFu;
   // The wave's place in the deal is the same in all of its lanes, and the compiler has to KNOW that: everything that steers the rounds below
@@ -435,14 +446,16 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
         float bound = best.t;
         if (SHARE && !ANY && exhausted) bound = fminf(bound, __uint_as_float(aux_t[helper ? (int)ray : lane]));
         uint32_t key[8];
-        key[0] = box_key8(w0.x, w0.y, w0.z, 0u << 8, sel, ig, cg, tmin, bound); key[1] = box_key8(w0.w, w1.x, w1.y, 1u << 8, sel, ig, cg, tmin, bound);
-        key[2] = box_key8(w1.z, w1.w, w2.x, 2u << 8, sel, ig, cg, tmin, bound); key[3] = box_key8(w2.y, w2.z, w2.w, 3u << 8, sel, ig, cg, tmin, bound);
-        key[4] = box_key8(w3.x, w3.y, w3.z, 4u << 8, sel, ig, cg, tmin, bound); key[5] = box_key8(w3.w, w4.x, w4.y, 5u << 8, sel, ig, cg, tmin, bound);
-        key[6] = box_key8(w4.z, w4.w, w5.x, 6u << 8, sel, ig, cg, tmin, bound); key[7] = box_key8(w5.y, w5.z, w5.w, 7u << 8, sel, ig, cg, tmin, bound);
-        const uint32_t ka = key[0] < key[1] ? key[0] : key[1], kb = key[2] < key[3] ? key[2] : key[3], kc = key[4] < key[5] ? key[4] : key[5], kd = key[6] < key[7] ? key[6] : key[7];
-        const uint32_t kab = ka < kb ? ka : kb, kcd = kc < kd ? kc : kd;
-        const uint32_t kmin = kab < kcd ? kab : kcd;
-        if (kmin == 0xFFFFFFFFu) {
+        constexpr bool FAR8 = ORDER == kKeysFarFirst;   // a pass of any-hit rays: the child entered is the farthest (a max tree, misses are 0), the rest keep slot order
+        key[0] = box_key8<FAR8>(w0.x, w0.y, w0.z, 0u << 8, sel, ig, cg, tmin, bound); key[1] = box_key8<FAR8>(w0.w, w1.x, w1.y, 1u << 8, sel, ig, cg, tmin, bound);
+        key[2] = box_key8<FAR8>(w1.z, w1.w, w2.x, 2u << 8, sel, ig, cg, tmin, bound); key[3] = box_key8<FAR8>(w2.y, w2.z, w2.w, 3u << 8, sel, ig, cg, tmin, bound);
+        key[4] = box_key8<FAR8>(w3.x, w3.y, w3.z, 4u << 8, sel, ig, cg, tmin, bound); key[5] = box_key8<FAR8>(w3.w, w4.x, w4.y, 5u << 8, sel, ig, cg, tmin, bound);
+        key[6] = box_key8<FAR8>(w4.z, w4.w, w5.x, 6u << 8, sel, ig, cg, tmin, bound); key[7] = box_key8<FAR8>(w5.y, w5.z, w5.w, 7u << 8, sel, ig, cg, tmin, bound);
+        auto first_of = [](uint32_t a, uint32_t b) { return (FAR8 ? a > b : a < b) ? a : b; };
+        const uint32_t ka = first_of(key[0], key[1]), kb = first_of(key[2], key[3]), kc = first_of(key[4], key[5]), kd = first_of(key[6], key[7]);
+        const uint32_t kab = first_of(ka, kb), kcd = first_of(kc, kd);
+        const uint32_t kmin = first_of(kab, kcd);   // the key of the child to enter
+        if (kmin == kMiss) {
           cur = SHARE ? st.pop_live() : (st.sp ? st.pop() : kRayDone);
           prefetch_node();
         } else {
@@ -450,24 +463,24 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
           const bool b0 = (kmin & 0x100u) != 0u, b1 = (kmin & 0x200u) != 0u, b2 = (kmin & 0x400u) != 0u;
           const int s01 = b0 ? link[1] : link[0], s23 = b0 ? link[3] : link[2], s45 = b0 ? link[5] : link[4], s67 = b0 ? link[7] : link[6];
           const int t03 = b1 ? s23 : s01, t47 = b1 ? s67 : s45;
-          const int nearest = b2 ? t47 : t03;
+          const int entered = b2 ? t47 : t03;
           if (__ballot(st.sp + 7 > kLevels) == 0ull) {   // wave-uniform: every lane stays inside the LDS part of its stack
 #pragma unroll
             for (int k = 7; k >= 0; --k)
-              if (key[k] != 0xFFFFFFFFu && key[k] != kmin) { st.lds[st.sp * kBlock] = link[k]; ++st.sp; }
+              if (key[k] != kMiss && key[k] != kmin) { st.lds[st.sp * kBlock] = link[k]; ++st.sp; }
           } else {
 #pragma unroll
             for (int k = 7; k >= 0; --k)
-              if (key[k] != 0xFFFFFFFFu && key[k] != kmin) st.push(link[k]);
+              if (key[k] != kMiss && key[k] != kmin) st.push(link[k]);
           }
-          cur = nearest;
+          cur = entered;
           prefetch_node();
         }
        }
       } else
       if (at_node) {
         // 64-byte node = 4 x dwordx4: four child boxes in 16-bit grid coordinates (the ray was mapped into grid units at
-        // refill) and four links.  Children are entered nearest first; the others are pushed farthest first.
+        // refill) and four links.  Children are entered nearest first; the others are pushed farthest first (any-hit rays: the reverse).
         // Nodes of the top levels come out of the block's LDS copy (their `cur` carries kBvhTopFlag | slot); lanes that read the
         // same staged node broadcast.
         u32x4 w0, w1, w2, w3;
@@ -490,9 +503,13 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
 #endif
         float bound = best.t;
         if (SHARE && !ANY && exhausted) bound = fminf(bound, __uint_as_float(aux_t[helper ? (int)ray : lane]));   // positive floats order like their bits
-        uint32_t k0 = box_key<false>(w0.x, w0.y, w0.z, w3.x, 0u, sel, ig, cg, cg, tmin, bound), k1 = box_key<false>(w0.w, w1.x, w1.y, w3.y, kKeyChild, sel, ig, cg, cg, tmin, bound);
-        uint32_t k2 = box_key<false>(w1.z, w1.w, w2.x, w3.z, 2u * kKeyChild, sel, ig, cg, cg, tmin, bound), k3 = box_key<false>(w2.y, w2.z, w2.w, w3.w, 3u * kKeyChild, sel, ig, cg, cg, tmin, bound);
-        sort2(k0, k1); sort2(k2, k3); sort2(k0, k2); sort2(k1, k3); sort2(k1, k2);
+        // (k0 .. k3 sorted: the child to enter, then the others in the order they are to be popped -- by distance from the near end, for any-hit
+        // rays from the far end: box_key's ORDER)
+        const uint32_t flip = (ORDER == kKeysPerLane && any_lane) ? kKeyDistanceMask : 0u;
+        uint32_t k0 = box_key<false, ORDER>(w0.x, w0.y, w0.z, w3.x, 0u, sel, ig, cg, cg, tmin, bound, flip), k1 = box_key<false, ORDER>(w0.w, w1.x, w1.y, w3.y, kKeyChild, sel, ig, cg, cg, tmin, bound, flip);
+        uint32_t k2 = box_key<false, ORDER>(w1.z, w1.w, w2.x, w3.z, 2u * kKeyChild, sel, ig, cg, cg, tmin, bound, flip), k3 = box_key<false, ORDER>(w2.y, w2.z, w2.w, w3.w, 3u * kKeyChild, sel, ig, cg, cg, tmin, bound, flip);
+        constexpr bool DESC = ORDER == kKeysFarFirst;
+        sort2<DESC>(k0, k1); sort2<DESC>(k2, k3); sort2<DESC>(k0, k2); sort2<DESC>(k1, k3); sort2<DESC>(k1, k2);
         // The links go through LDS: picking one of four registers by a per-lane index costs 6 VALU instructions (the
         // kernel's bottleneck), an LDS read at a computed address 2 (k_trace 0.714 -> 0.691 ms).  The scratch is laid out
         // [child][lane] so that every access of a wave instruction has bank = lane % 32 (the [lane][child] layout with one
@@ -514,18 +531,18 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         GLZ_SEC_STAMP(sec_f2);   // links through LDS
 #endif
-        if (k0 == 0xFFFFFFFFu) {
+        if (k0 == kMiss) {
           cur = SHARE ? st.pop_live() : (st.sp ? st.pop() : kRayDone);
           prefetch_node();
         } else {
           if (__ballot(st.sp + 3 > kLdsStack) == 0ull) {   // wave-uniform: every lane stays inside the LDS part of its stack (no spill branches)
-            if (k3 != 0xFFFFFFFFu) { st.lds[st.sp * kBlock] = l3; ++st.sp; }
-            if (k2 != 0xFFFFFFFFu) { st.lds[st.sp * kBlock] = l2; ++st.sp; }
-            if (k1 != 0xFFFFFFFFu) { st.lds[st.sp * kBlock] = l1; ++st.sp; }
+            if (k3 != kMiss) { st.lds[st.sp * kBlock] = l3; ++st.sp; }
+            if (k2 != kMiss) { st.lds[st.sp * kBlock] = l2; ++st.sp; }
+            if (k1 != kMiss) { st.lds[st.sp * kBlock] = l1; ++st.sp; }
           } else {
-            if (k3 != 0xFFFFFFFFu) st.push(l3);
-            if (k2 != 0xFFFFFFFFu) st.push(l2);
-            if (k1 != 0xFFFFFFFFu) st.push(l1);
+            if (k3 != kMiss) st.push(l3);
+            if (k2 != kMiss) st.push(l2);
+            if (k1 != kMiss) st.push(l1);
           }
           cur = l0;
           prefetch_node();

@@ -6,7 +6,11 @@
 //   switch                 default  what
 //   ---------------------  -------  ----------------------------------------------------------------------------------------------
 //   GLZ_TRACE_WAVES           6     waves per SIMD k_trace is compiled for (80 VGPRs)
-//   GLZ_TRACE_SPLIT_NUM / _DEN  9 / 10  k_trace: with more groups than waves, waves take groups of ONE kind (closest-hit or shadow); the shadow waves' share relative to the shadow groups' share
+//   GLZ_TRACE_SPLIT_NUM / _DEN  8 / 10  k_trace: with more groups than waves, waves take groups of ONE kind (closest-hit or shadow); the shadow waves' share relative to the shadow groups' share
+//                                   (9 / 10 while shadow rays walked nearest first.  Far first, 5 / 6 / 7 / 8 / 9 over 10: the atrium 0.700 / 0.675 / 0.677 / 0.688 / 0.696 ms per launch, but
+//                                   mattest.glaze, whose shadow rays are mostly unoccluded and no cheaper than before, 0.401 at 7 against 0.389 / 0.388 at 8 / 9: 8 is the smallest value that costs it nothing)
+//   GLZ_ANY_FAR_FIRST         1     any-hit (shadow) rays enter the child with the LARGEST entry distance and keep the nearest for last (trace_wave); 0: nearest first, as closest-hit rays
+//   GLZ_COUNT_ANY_FAR_FIRST   0     tools only: the counting kernels walk any-hit rays in the product's order too (tools/gpu_diag.py); off, their counts are the oracle's walk
 //   GLZ_TRACE_PREFETCH        0     k_trace: the next node's loads issued as soon as the node is known (as k_path does; wants 16 more registers)
 //   GLZ_TRACE_TL_WAVES        4     ... the two-level tracer (128 VGPRs)
 //   GLZ_SHADE_WAVES           4     ... k_shade (128 VGPRs)
@@ -17,7 +21,7 @@
 //   GLZ_REFILL               10     idle lanes at which a wave takes new rays (16 until the camera rays left the refill: round 5)
 //   GLZ_TL_REFILL            16     the same for the two-level tracer (8: 0.834 against 0.827 ms, round 3)
 //   GLZ_LEAF_QUORUM          24     lanes waiting on a leaf at which the inner-node phase ends
-//   GLZ_LEAF_QUORUM_ANY      30     ... in a pass of shadow rays only (18 / 24 / 30 / 36 / 42: 0.444 / 0.432 / 0.429 / 0.431 / 0.434 ms per k_trace); GLZ_REFILL_ANY: = GLZ_REFILL (6 / 16: no difference)
+//   GLZ_LEAF_QUORUM_ANY      30     ... in a pass of shadow rays only (18 / 24 / 30 / 36 / 42: 0.444 / 0.432 / 0.429 / 0.431 / 0.434 ms per k_trace); GLZ_REFILL_ANY: = GLZ_REFILL (6 / 16: no difference); both swept again with far first: inside the spread
 //   GLZ_TL_LEAF_QUORUM       32     the same for the two-level tracer (a leaf visit there is an instance entry: dearer)
 //   GLZ_ALPHA_QUORUM         12     lanes waiting with a candidate on non-opaque geometry at which the alpha phase runs
 //   GLZ_PATH_PREFETCH         1     k_path: the next node's loads issued as soon as the node is known (trace_wave<PREFETCH>)
@@ -29,10 +33,16 @@
 #define GLZ_TRACE_WAVES 6
 #endif
 #ifndef GLZ_TRACE_SPLIT_NUM
-#define GLZ_TRACE_SPLIT_NUM 9
+#define GLZ_TRACE_SPLIT_NUM 8
 #endif
 #ifndef GLZ_TRACE_SPLIT_DEN
 #define GLZ_TRACE_SPLIT_DEN 10
+#endif
+#ifndef GLZ_ANY_FAR_FIRST
+#define GLZ_ANY_FAR_FIRST 1
+#endif
+#ifndef GLZ_COUNT_ANY_FAR_FIRST
+#define GLZ_COUNT_ANY_FAR_FIRST 0
 #endif
 #ifndef GLZ_TRACE_PREFETCH
 #define GLZ_TRACE_PREFETCH 0

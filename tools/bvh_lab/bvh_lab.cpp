@@ -5,7 +5,11 @@
 // over a ray population shaped like a path tracer's: camera rays, cosine-distributed bounces, shadow rays towards the sun and the sky.
 //
 //   g++ -O2 -std=c++17 -fopenmp tools/bvh_lab/bvh_lab.cpp -o /tmp/bvh_lab && /tmp/bvh_lab /tmp/atrium.bin [options]
-//   options: builder=binned|sweep|sbvh  bins=16  alpha=1e-5  width=4|8  collapse=area|sah  order=full|nearest  leafmax=1  presplit=0|N  rays=WxH  bounces=8
+//   options: builder=binned|sweep|sbvh  bins=16  alpha=1e-5  width=4|8  collapse=area|sah  order=full|nearest  anyorder=nearest|farthest|exit|interval|area|slot  leafmax=1  presplit=0|N  rays=WxH  bounces=8
+//
+// anyorder: the sort key of ANY-HIT rays only (closest-hit rays keep `order`): nearest entry first (what closest-hit rays do), farthest
+// entry first (what the tracers do: device/trace_wave.h, GLZ_ANY_FAR_FIRST), farthest exit first, longest interval inside the box first,
+// largest box area first, or the node's slot order.
 //
 // Boxes are kept in floats (no 15-bit grid): the numbers are for comparing variants with each other, not with the GPU counters.
 #include <algorithm>
@@ -88,7 +92,7 @@ static std::vector<BNode> bnodes;
 static std::vector<Ref> leaf_refs;   // refs in leaf order
 
 struct Opt {
-  std::string builder = "binned", collapse = "area", order = "full";
+  std::string builder = "binned", collapse = "area", order = "full", anyorder = "nearest";
   int bins = 16, width = 4, leafmax = 1, presplit = 0, rw = 480, rh = 270, bounces = 8, sbins = 32;
   float alpha = 1e-5f, ct = 1.2f, ci = 1.0f;
 } opt;
@@ -353,10 +357,15 @@ static bool trace(V3 o, V3 d, float tmin, float tmax, bool any, Count& c, float&
         const float ax = (b.lo.x - o.x) * inv.x, bx = (b.hi.x - o.x) * inv.x; t0 = std::max(t0, std::min(ax, bx)); t1 = std::min(t1, std::max(ax, bx));
         const float ay = (b.lo.y - o.y) * inv.y, by = (b.hi.y - o.y) * inv.y; t0 = std::max(t0, std::min(ay, by)); t1 = std::min(t1, std::max(ay, by));
         const float az = (b.lo.z - o.z) * inv.z, bz = (b.hi.z - o.z) * inv.z; t0 = std::max(t0, std::min(az, bz)); t1 = std::min(t1, std::max(az, bz));
-        if (t0 <= t1) key[nk++] = {t0, k};
+        if (t0 <= t1) {
+          float sort_key = t0;
+          if (any && opt.anyorder != "nearest")
+            sort_key = opt.anyorder == "farthest" ? -t0 : opt.anyorder == "exit" ? -t1 : opt.anyorder == "interval" ? -(t1 - t0) : opt.anyorder == "area" ? -b.area() : (float)k;
+          key[nk++] = {sort_key, k};
+        }
       }
       if (nk == 0) c.empty_visits += 1;
-      if (opt.order == "full") std::sort(key, key + nk);
+      if (opt.order == "full" || (any && opt.anyorder != "nearest")) std::sort(key, key + nk);
       else if (nk > 1) {   // "nearest": the nearest child first, the others in slot order
         int m = 0;
         for (int k = 1; k < nk; ++k) if (key[k] < key[m]) m = k;
@@ -397,7 +406,7 @@ int main(int argc, char** argv) {
     std::string a = argv[i]; const size_t eq = a.find('=');
     if (eq == std::string::npos) continue;
     const std::string k = a.substr(0, eq), v = a.substr(eq + 1);
-    if (k == "builder") opt.builder = v; else if (k == "order") opt.order = v; else if (k == "collapse") opt.collapse = v; else if (k == "bins") opt.bins = std::atoi(v.c_str());
+    if (k == "builder") opt.builder = v; else if (k == "order") opt.order = v; else if (k == "anyorder") opt.anyorder = v; else if (k == "collapse") opt.collapse = v; else if (k == "bins") opt.bins = std::atoi(v.c_str());
     else if (k == "sbins") opt.sbins = std::atoi(v.c_str()); else if (k == "width") opt.width = std::atoi(v.c_str()); else if (k == "leafmax") opt.leafmax = std::atoi(v.c_str());
     else if (k == "presplit") opt.presplit = std::atoi(v.c_str()); else if (k == "alpha") opt.alpha = (float)std::atof(v.c_str()); else if (k == "bounces") opt.bounces = std::atoi(v.c_str());
     else if (k == "ct") opt.ct = (float)std::atof(v.c_str());

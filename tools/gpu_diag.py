@@ -1,4 +1,8 @@
-"""Ad-hoc GPU diagnostics (not part of the test-suite): full-size parity + first timings."""
+"""Ad-hoc GPU diagnostics (not part of the test-suite): full-size parity + first timings.
+
+The per-sample counts and phase occupancies come from the counting kernels, which walk every ray nearest child first (the oracle's order).
+For the shadow pass as the product walks it -- farthest first -- run this under a library built with -DGLZ_COUNT_ANY_FAR_FIRST=1:
+tools/build_variant.sh countfar -DGLZ_COUNT_ANY_FAR_FIRST=1 && GLAZE_HIP_LIB=variants/libglaze_hip_countfar.so python tools/gpu_diag.py"""
 import sys, time
 import numpy as np
 sys.path.insert(0, ".")
