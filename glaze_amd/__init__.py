@@ -21,7 +21,7 @@ import numpy as np
 
 from . import abi
 from .abi import GlazeError
-from .scene_desc import SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
+from .scene_desc import VERTEX_DTYPE, SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
 
 __all__ = ["parse", "converted_file", "ParsedScene", "RayTraceInstance", "RayTraceScene", "RayTraceRenderer", "Integrator",
            "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points",
@@ -583,6 +583,13 @@ class RayTraceScene:
         abi.check(abi.lib().glz_debug_read_bvh(self._h, _ptr(nodes), i.bvh_nodes, _ptr(tris), i.n_as_triangles))
         return nodes[:i.bvh_nodes], tris[:i.n_as_triangles]
 
+    def debug_leaf_records(self):
+        """The 64-byte per-leaf records the tracers read ((n, 16) uint32; a two-level scene's are its meshes' concatenated)."""
+        n = abi.check(abi.lib().glz_debug_read_leaf_records(self._h, None, 0))
+        out = np.zeros((max(1, n), 16), np.uint32)
+        abi.check(abi.lib().glz_debug_read_leaf_records(self._h, _ptr(out), n))
+        return out[:n]
+
     def debug_tlas_instances(self):
         """The 192-byte TlasInstance records of a two-level scene in the top level's leaf order (uint8; empty when flattened)."""
         n = abi.check(abi.lib().glz_debug_read_tlas_instances(self._h, None, 0))
@@ -670,6 +677,30 @@ class RayTraceRenderer:
         The scene's structure is rebuilt for them (every renderer sharing the scene sees the move) and accumulation restarts."""
         t = _transform_array(transforms)
         abi.check(abi.lib().glz_renderer_update_transforms(self._h, _ptr(t), t.shape[0]))
+
+    _GEOMETRY_MODES = {"refit": abi.GEOMETRY_REFIT, "rebuild": abi.GEOMETRY_REBUILD}
+
+    def update_vertices(self, vertices, first=0, mode="refit"):
+        """Deforms the meshes: vertices is an (n, 8) float32 array (position, normal, texture coordinate, as SceneDesc.vertices) or an
+        abi.Vertex array, written over the scene's vertices [first, first + n).  mode 'refit' keeps the hierarchy's topology and refits
+        it on the device, 'rebuild' runs the builder again; either way the scene then equals one created with the new vertices (every
+        renderer sharing it sees the change) and accumulation restarts."""
+        if isinstance(vertices, C.Array) and vertices._type_ is abi.Vertex:
+            v = np.frombuffer(vertices, np.float32).reshape(-1, 8)
+        elif getattr(vertices, "dtype", None) == VERTEX_DTYPE:      # SceneDesc.vertices as it is
+            v = np.ascontiguousarray(vertices).view(np.float32).reshape(-1, 8)
+        else:
+            v = np.ascontiguousarray(vertices, np.float32)
+        if v.ndim != 2 or v.shape[1] != 8:
+            raise ValueError("vertices must be an (n, 8) array (position, normal, texture coordinate), got shape %s" % (v.shape,))
+        abi.check(abi.lib().glz_renderer_update_vertices(self._h, _ptr(v), int(first), v.shape[0], self._GEOMETRY_MODES.get(mode, mode)))
+
+    def geometry_update_info(self):
+        """glz_geometry_update_info of the scene's last update_vertices: mode, meshes_touched, update_ms and the box-area figures whose
+        ratio box_area / box_area_built says how far a refitted tree has degraded.  Raises GlazeError before any update."""
+        i = abi.GeometryUpdateInfo()
+        abi.check(abi.lib().glz_renderer_geometry_update_info(self._h, C.byref(i)))
+        return i
 
     def refresh_binded_textures(self, textures):
         """raytracer.rs:328-356: new texture array under the same materials and lights; accumulation continues."""

@@ -93,6 +93,15 @@ class SceneInfo(C.Structure):
                 ("bvh_nodes8", C.c_uint32), ("_reserved", C.c_uint32)]
 
 
+GEOMETRY_REFIT, GEOMETRY_REBUILD = 0, 1
+
+
+class GeometryUpdateInfo(C.Structure):
+    """glz_geometry_update_info"""
+    _fields_ = [("mode", C.c_uint32), ("meshes_touched", C.c_uint32), ("update_ms", C.c_float), ("box_area", C.c_float),
+                ("box_area_built", C.c_float)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [("launches", C.c_uint64), ("samples", C.c_uint64), ("render_ms", C.c_double),
                 ("trace_closest_ms", C.c_double), ("shade_ms", C.c_double), ("trace_shadow_ms", C.c_double), ("other_ms", C.c_double),
@@ -190,6 +199,9 @@ PROTOTYPES = {
     "glz_renderer_update_materials_and_lights": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
     "glz_renderer_refresh_binded_textures": (C.c_int, [_P, _P, C.c_uint32]),
     "glz_renderer_update_transforms": (C.c_int, [_P, _P, C.c_uint32]),
+    "glz_renderer_update_vertices": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int]),
+    "glz_renderer_geometry_update_info": (C.c_int, [_P, _P]),
+    "glz_debug_read_leaf_records": (C.c_int64, [_P, _P, C.c_int64]),
     "glz_debug_read_tlas_instances": (C.c_int64, [_P, _P, C.c_int64]),
     "glz_debug_instance_boxes": (C.c_int64, [_P, C.c_int, C.c_uint64, _P, _P]),
     "glz_debug_box_kernel_ms": (C.c_float, [_P]),

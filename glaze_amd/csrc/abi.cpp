@@ -339,6 +339,21 @@ int glz_renderer_update_transforms(glz_renderer* h, const glz_transform* t, uint
   GLZ_RET(h->r->update_transforms(t, nt, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_renderer_update_vertices(glz_renderer* h, const glz_vertex* v, uint32_t first, uint32_t n, int mode) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!v || !n) return fail(GLZ_E_ARG, "update_vertices: vertices is null or empty");
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  if ((uint64_t)first + n > h->r->scene()->data.vertices.size()) return fail(GLZ_E_ARG, "update_vertices: the range reaches past the scene's vertex count");
+  if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return fail(GLZ_E_ARG, "update_vertices: unknown mode");
+  GLZ_RET(h->r->update_vertices(v, first, n, mode, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_geometry_update_info(glz_renderer* h, glz_geometry_update_info* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!out) return fail(GLZ_E_ARG, "output is null");
+  GLZ_RET(h->r->geometry_update_info(*out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_refresh_binded_textures(glz_renderer* h, const glz_texture* t, uint32_t nt) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!t || !nt) return fail(GLZ_E_ARG, "null array");

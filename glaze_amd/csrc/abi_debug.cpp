@@ -254,6 +254,13 @@ int64_t glz_debug_read_bvh8(glz_scene* h, void* nodes_out, int64_t cap_nodes) {
   GLZ_GUARD_END(GLZ_E_IO)
 }
 
+int64_t glz_debug_read_leaf_records(glz_scene* h, void* out, int64_t cap) {
+  if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");
+  const size_t n = h->s->accel().n_leaf_records() - (h->s->dev.two_level && h->s->accel().n_leaf_records() ? 1 : 0);   // (two levels: less the padding record)
+  const int64_t bytes = read_array(*h->s, h->s->dev.bvh_quads, n * sizeof(BvhQuad), cap > 0 ? out : nullptr, cap * (int64_t)sizeof(BvhQuad), "read leaf records");
+  return bytes < 0 ? bytes : (int64_t)n;
+}
+
 int64_t glz_debug_read_texture_level(glz_scene* h, uint32_t texture, uint32_t level, uint8_t* out, int64_t cap, uint32_t* width, uint32_t* height) {
   GLZ_GUARD_BEGIN
   if (!h || !h->s) return fail(GLZ_E_ARG, "scene is null");

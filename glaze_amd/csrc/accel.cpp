@@ -81,6 +81,7 @@ bool Accel::build_two_level(const Sources& s, Error& err) {
   StreamTimer timer;
   if (!timer.start(st, err)) return false;
   h_mesh_ranges.clear();
+  plans_.clear();   // (the meshes' hierarchies are new)
   // ---- unique meshes (index ranges) ----
   std::vector<uint32_t> mesh_of;
   std::vector<MeshBuild> meshes;
@@ -322,6 +323,7 @@ bool Accel::build_bvh(const Sources& s, Error& err) {
   const Geometry& g = s.geometry;
   two_level_ = false;
   alpha_ready_ = false;
+  plans_.clear();   // a refit plan belongs to the structure it was made for
   n_world_tris_ = (uint32_t)g.n_world_triangles;
   // instanced scenes keep one hierarchy per mesh (acceleration.rs:319-345) instead of one over every instanced triangle
   {
@@ -507,6 +509,201 @@ bool Accel::rebuild(const Sources& s, Error& err) {
   if (!device_instance_boxes(s, kExactBoxBudget, err)) return false;
   std::vector<float4> blo, bhi;   // read back with the leaf order
   return assemble_top_level(s, d_box_lo_.ptr, d_box_hi_.ptr, blo, bhi, nullptr, timer, err);
+}
+
+// ---- deforming meshes ------------------------------------------------------------------------------------------------------------
+// The nodes of one width grouped by height above the leaves: order (nodes of height 0 first) and the offsets of the levels in it.
+// Depth-first numbering puts every parent before its children, so one pass from the last node to the first knows the children's heights.
+static bool level_lists(const uint32_t* words, uint32_t n_nodes, uint32_t n_leaves, int width, std::vector<uint32_t>& order, std::vector<uint32_t>& first) {
+  std::vector<uint32_t> height(n_nodes, 0u);
+  uint32_t top = 0;
+  for (uint32_t i = n_nodes; i-- > 0;) {
+    const uint32_t* link = words + (size_t)i * 4 * width + 3 * width;
+    for (int k = 0; k < width; ++k) {
+      const int l = (int)link[k];
+      if (l == kBvhEmptyChild) continue;
+      if (l < 0 ? (uint32_t)~l >= n_leaves : ((uint32_t)l <= i || (uint32_t)l >= n_nodes)) return false;   // (what the kernels index with)
+      if (l < 0) continue;
+      height[i] = std::max(height[i], height[l] + 1u);
+    }
+    top = std::max(top, height[i]);
+  }
+  first.assign(top + 2, 0u);
+  for (uint32_t i = 0; i < n_nodes; ++i) ++first[height[i] + 1];
+  for (uint32_t h = 0; h <= top; ++h) first[h + 1] += first[h];
+  order.resize(n_nodes);
+  std::vector<uint32_t> at(first.begin(), first.end() - 1);
+  for (uint32_t i = 0; i < n_nodes; ++i) order[at[height[i]]++] = i;
+  return true;
+}
+
+bool Accel::make_plan(hipStream_t st, const RefitTarget& t, uint32_t n_leaves, RefitPlan& p, Error& err) {
+  p.n_leaves = n_leaves;
+  if (!hip_ok(alloc_each(n_leaves, p.leaf_lo, p.leaf_hi), "alloc refit leaf boxes", err)) return false;
+  if (n_leaves < 2) return true;   // one leaf: one node that spans the grid whatever the leaf's box is; nothing to fit
+  std::vector<uint32_t> order;
+  std::vector<BvhNode4> h4(t.n_nodes);
+  if (!hip_ok(hipMemcpy(h4.data(), t.nodes, sizeof(BvhNode4) * t.n_nodes, hipMemcpyDeviceToHost), "read nodes", err)) return false;
+  if (!level_lists(h4[0].w, t.n_nodes, n_leaves, 4, order, p.first4)) return err.fail(GLZ_E_UNSUPPORTED, "refit: the nodes are not as the builder numbers them");
+  if (!hip_ok(p.order4.upload(order.data(), order.size(), st), "upload refit plan", err) || !hip_ok(alloc_each(t.n_nodes, p.lo4, p.hi4), "alloc refit node boxes", err) ||
+      !hip_ok(hipStreamSynchronize(st), "upload refit plan", err))
+    return false;
+  if (!t.n_nodes8) return true;
+  std::vector<BvhNode8> h8(t.n_nodes8);
+  if (!hip_ok(hipMemcpy(h8.data(), t.nodes8, sizeof(BvhNode8) * t.n_nodes8, hipMemcpyDeviceToHost), "read 8-wide nodes", err)) return false;
+  if (!level_lists(h8[0].w, t.n_nodes8, n_leaves, 8, order, p.first8)) return err.fail(GLZ_E_UNSUPPORTED, "refit: the 8-wide nodes are not as the builder numbers them");
+  return hip_ok(p.order8.upload(order.data(), order.size(), st), "upload refit plan", err) && hip_ok(alloc_each(t.n_nodes8, p.lo8, p.hi8), "alloc refit node boxes", err) &&
+         hip_ok(hipStreamSynchronize(st), "upload refit plan", err);
+}
+
+Accel::RefitTarget Accel::refit_target(const Sources& s, size_t plan) const {
+  if (!two_level_)
+    return RefitTarget{d_nodes_.ptr, (uint32_t)d_nodes_.count, d_nodes8_.ptr, (uint32_t)d_nodes8_.count, d_quads_.ptr, d_tris_.ptr, s.geometry.instances.ptr,
+                       s.geometry.transforms.ptr};
+  const MeshRange& r = h_mesh_ranges[plan];
+  return RefitTarget{d_nodes_.ptr + r.node_base, r.n_nodes, nullptr, 0u, d_quads_.ptr + r.quad_base, d_tris_.ptr + r.tri_base, d_tl_pseudo_.ptr + plan, d_tl_ident_.ptr};
+}
+
+// One hierarchy under the vertices as they are on the device: leaves, fit, (write) grid and quantisation, the box-area sum into p.area.
+bool Accel::refit(hipStream_t st, const Sources& s, const RefitTarget& t, RefitPlan& p, bool write, RefitResult& out, Error& err) {
+  const Geometry& g = s.geometry;
+  if (!hip_ok(launch_refit_leaves(st, g.vertices.ptr, g.indices.ptr, t.instances, t.transforms, p.n_leaves, t.quads, t.tris, p.leaf_lo.ptr, p.leaf_hi.ptr), "k_refit_leaves", err))
+    return false;
+  const bool fit = p.n_leaves >= 2;
+  const RefitNodes n4{4, t.nodes, t.n_nodes, p.order4.ptr, p.first4, p.leaf_lo.ptr, p.leaf_hi.ptr, p.lo4.ptr, p.hi4.ptr};
+  const RefitNodes n8{8, t.nodes8, t.n_nodes8, p.order8.ptr, p.first8, p.leaf_lo.ptr, p.leaf_hi.ptr, p.lo8.ptr, p.hi8.ptr};
+  const float4 *root_lo = fit ? p.lo4.ptr : p.leaf_lo.ptr, *root_hi = fit ? p.hi4.ptr : p.leaf_hi.ptr;   // (node 0, or the only leaf)
+  float area = 0.0f;
+  if (fit && !hip_ok(launch_refit_fit(st, n4), "k_refit_fit", err)) return false;
+  if (write && !hip_ok(launch_refit_grid(st, root_lo, root_hi, d_refit_grid_.ptr), "k_grid_params", err)) return false;
+  if (fit) {
+    if (!hip_ok(hipMemsetAsync(d_refit_area_.ptr, 0, sizeof(float), st), "clear", err) ||
+        !hip_ok(launch_refit_quantise(st, n4, d_refit_grid_.ptr, write, d_refit_area_.ptr), "k_refit_quantise", err))
+      return false;
+    if (t.n_nodes8 && write && (!hip_ok(launch_refit_fit(st, n8), "k_refit_fit", err) || !hip_ok(launch_refit_quantise(st, n8, d_refit_grid_.ptr, true, nullptr), "k_refit_quantise", err)))
+      return false;
+    if (!hip_ok(hipMemcpyAsync(&area, d_refit_area_.ptr, sizeof(float), hipMemcpyDeviceToHost, st), "read box area", err)) return false;
+  }
+  out.grid = BvhGrid{};
+  if ((write && !hip_ok(hipMemcpyAsync(&out.grid, d_refit_grid_.ptr, sizeof(BvhGrid), hipMemcpyDeviceToHost, st), "read grid", err)) ||
+      !hip_ok(hipMemcpyAsync(&out.lo, root_lo, sizeof(float4), hipMemcpyDeviceToHost, st), "read root box", err) ||
+      !hip_ok(hipMemcpyAsync(&out.hi, root_hi, sizeof(float4), hipMemcpyDeviceToHost, st), "read root box", err) || !hip_ok(hipStreamSynchronize(st), "refit", err))
+    return false;
+  p.area = fit ? area : 2.0f * ((out.hi.x - out.lo.x) * (out.hi.y - out.lo.y) + (out.hi.y - out.lo.y) * (out.hi.z - out.lo.z) + (out.hi.z - out.lo.z) * (out.hi.x - out.lo.x));
+  return true;
+}
+
+bool Accel::prepare_refit(const Sources& s, Error& err) {
+  if (!plans_.empty()) return true;
+  hipStream_t st = s.stream;
+  if (!d_refit_grid_.ptr && (!hip_ok(d_refit_grid_.alloc(1), "alloc", err) || !hip_ok(d_refit_area_.alloc(1), "alloc", err))) return false;
+  std::vector<RefitPlan> plans(two_level_ ? tl_meshes_.size() : 1);
+  if (two_level_) {
+    // what the meshes' builds had: a pseudo-instance each, the identity transform, its flag
+    std::vector<RTInstance> pseudo;
+    tl_vertex_span_.clear();
+    for (const TlMesh& m : tl_meshes_) {
+      pseudo.push_back(RTInstance{m.index_offset, m.index_count, 0u, 0u});
+      std::pair<uint32_t, uint32_t> span(0xFFFFFFFFu, 0u);
+      for (uint32_t k = 0; k < m.index_count; ++k) {
+        const uint32_t v = s.data.indices[m.index_offset + k];
+        span.first = std::min(span.first, v);
+        span.second = std::max(span.second, v);
+      }
+      tl_vertex_span_.push_back(span);
+    }
+    TransformPair ident{};
+    for (int k = 0; k < 4; ++k) ident.o2w[5 * k] = ident.w2o[5 * k] = 1.0f;
+    const uint32_t one = 1u;
+    if (!hip_ok(d_tl_pseudo_.upload(pseudo.data(), pseudo.size(), st), "upload", err) || !hip_ok(d_tl_ident_.upload(&ident, 1, st), "upload", err) ||
+        !hip_ok(d_tl_one_.upload(&one, 1, st), "upload", err) || !hip_ok(hipStreamSynchronize(st), "upload", err))
+      return false;
+  }
+  for (size_t m = 0; m < plans.size(); ++m) {
+    const RefitTarget t = refit_target(s, m);
+    const size_t quads_end = !two_level_ ? d_quads_.count : (m + 1 < plans.size() ? h_mesh_ranges[m + 1].quad_base : d_quads_.count - 1);
+    const uint32_t n_leaves = (uint32_t)(quads_end - (two_level_ ? h_mesh_ranges[m].quad_base : 0u));
+    if (!make_plan(st, t, n_leaves, plans[m], err)) return false;
+    // the figure of the structure as the builder left it: the same passes over the vertices it was built from, nothing written but what is there
+    RefitResult r;
+    if (n_leaves && !refit(st, s, t, plans[m], false, r, err)) return false;
+    plans[m].area_built = plans[m].area;
+  }
+  plans_ = std::move(plans);
+  return true;
+}
+
+bool Accel::update_geometry(const Sources& s, int mode, uint32_t first, uint32_t count, StreamTimer& timer, Error& err) {
+  hipStream_t st = s.stream;
+  const Geometry& g = s.geometry;
+  uint32_t touched = 0;
+  if (mode == GLZ_GEOMETRY_REBUILD) {
+    if (!(two_level_ ? build_two_level(s, err) : build_bvh(s, err)) || !hip_ok(hipStreamSynchronize(st), "update_vertices", err)) return false;
+    timer.stop(st);
+    for (const TlMesh& m : tl_meshes_) touched += m.index_count >= 3u ? 1u : 0u;
+    if (!two_level_) touched = 1;
+  } else {
+    if (!prepare_refit(s, err)) return false;   // (Scene::update_vertices has called it before the vertices changed: nothing left to do)
+    if (!two_level_ && plans_[0].n_leaves == 0) {   // a scene without triangles has nothing to refit
+      timer.stop(st);
+    } else if (!two_level_) {
+      RefitResult r;
+      if (!refit(st, s, refit_target(s, 0), plans_[0], true, r, err)) return false;
+      grid_ = r.grid;
+      for (int k = 0; k < 3; ++k) {
+        info_.bounds_min[k] = (&r.lo.x)[k];
+        info_.bounds_max[k] = (&r.hi.x)[k];
+        info_.bvh_grid_lo[k] = r.grid.lo[k];
+        info_.bvh_grid_cell[k] = r.grid.cell[k];
+      }
+      // what the build derives from the nodes and the triangle records, again and unchanged
+      if (!hip_ok(launch_top_table(st, d_nodes_.ptr, (uint32_t)d_nodes_.count, d_top_.ptr), "k_top_table", err) ||
+          !hip_ok(launch_shade_records(st, n_shade_slots_, d_tris_.ptr, g.instances.ptr, g.indices.ptr, g.vertices.ptr, g.derivatives.ptr, d_xf_identity_.ptr,
+                                       d_shade_tris_.ptr), "k_shade_records", err) ||
+          !hip_ok(hipStreamSynchronize(st), "shading records", err) || !build_alpha_records(s, err))
+        return false;
+      timer.stop(st);
+      touched = 1;
+    } else {
+      for (size_t m = 0; m < plans_.size(); ++m) {
+        const uint32_t n = tl_meshes_[m].index_count / 3u;
+        const std::pair<uint32_t, uint32_t>& span = tl_vertex_span_[m];
+        if (n == 0 || span.second < first || span.first >= (uint64_t)first + count) continue;   // (conservative: a mesh may skip vertices inside its span)
+        RefitResult r;
+        if (!refit(st, s, refit_target(s, m), plans_[m], true, r, err)) return false;
+        tl_meshes_[m].grid = r.grid;
+        for (int k = 0; k < 3; ++k) {
+          tl_meshes_[m].lo[k] = (&r.lo.x)[k];
+          tl_meshes_[m].hi[k] = (&r.hi.x)[k];
+        }
+        const uint32_t tri_base = h_mesh_ranges[m].tri_base;
+        if (!hip_ok(launch_shade_records(st, n, d_tris_.ptr + tri_base, d_tl_pseudo_.ptr + m, g.indices.ptr, g.vertices.ptr, g.derivatives.ptr, d_tl_one_.ptr,
+                                         d_shade_tris_.ptr + 8 * (size_t)tri_base), "k_shade_records", err))
+          return false;
+        ++touched;
+      }
+      tl_points_ready_ = false;   // the cached mesh points and boxes are those of the old vertices
+      if (!rebuild(s, err)) return false;   // the top level over the instance boxes of the new meshes
+      timer.stop(st);
+    }
+  }
+  update_.mode = (uint32_t)mode;
+  update_.meshes_touched = touched;
+  update_.update_ms = info_.build_ms = timer.ms();
+  update_valid_ = true;
+  return true;
+}
+
+bool Accel::geometry_update(const Sources& s, glz_geometry_update_info& out, Error& err) {
+  if (!update_valid_) return err.fail(GLZ_E_ARG, "geometry_update_info: no update_vertices on this scene yet");
+  if (!prepare_refit(s, err)) return false;   // (after a rebuild: the figures of the new structure, and the plan the next refit needs)
+  out = update_;
+  out.box_area = out.box_area_built = 0.0f;
+  for (const RefitPlan& p : plans_) {
+    out.box_area += p.area;
+    out.box_area_built += p.area_built;
+  }
+  return true;
 }
 
 }  // namespace glz

@@ -48,6 +48,19 @@ class Accel {
   // After new transforms: a flattened scene is built again in full (its world triangles depend on every transform), a two-level scene
   // keeps its meshes' hierarchies, leaf records and shading records and gets a new top level.
   bool rebuild(const Sources& s, Error& err);
+  // New vertices in [first, first + count) of the vertex buffer, already on the device with their derivatives (Scene::update_vertices).
+  // GLZ_GEOMETRY_REBUILD runs the builder again with the options and the shape the scene has.  GLZ_GEOMETRY_REFIT keeps the topology:
+  // leaf records and leaf boxes again from the vertices, the wide nodes' boxes fitted level by level, the grid re-derived from the root
+  // box and every child box quantised on it (kernels_refit.hip) -- for a flattened scene over the whole structure, for a two-level
+  // scene per mesh whose indices reach into the range, each in its object space, and then the top level as rebuild() makes it.
+  // timer: started by the caller where glz_geometry_update_info::update_ms (and info.build_ms) is to begin.
+  bool update_geometry(const Sources& s, int mode, uint32_t first, uint32_t count, StreamTimer& timer, Error& err);
+  // What a refit needs of the structure as it stands, made on the first refit after a build and kept until the next build: the refit plan
+  // (RefitPlan) and the box-area figure of the structure as built -- so it runs BEFORE the new vertices go in.  Nothing when it is there.
+  bool prepare_refit(const Sources& s, Error& err);
+  // What the last update_geometry did; GLZ_E_ARG before any.  The box-area figures come from the refit plans: after a rebuild there is
+  // none yet, and it is made here, on request, so that a caller who rebuilds every frame and never asks does not pay for it.
+  bool geometry_update(const Sources& s, glz_geometry_update_info& out, Error& err);
   // What the alpha test of a candidate reads (DeviceScene::alpha_recs): texture coordinates and the opacity map's descriptor per triangle
   // slot.  Flattened scenes only (the two-level tracer takes the material from the instance, alpha_test_instance); nothing without an
   // opacity map.  Called by the flattened build and again after everything that changes a material's opacity map or moves texels.
@@ -81,6 +94,34 @@ class Accel {
     DeviceBuffer<BvhNode4> nodes;
     DeviceBuffer<BvhQuad> quads;   // leaf records, object space
   };
+  // The refit plan of one hierarchy (the flattened scene's, or one mesh's): its wide nodes grouped by height above the leaves for the
+  // level launches, and a float box per leaf and per node.  Links are relative to the hierarchy's first node and first leaf record, so a
+  // mesh's plan outlives a new top level.  Not counted in as_bytes: 32 bytes per leaf, 36 per 4-wide and per 8-wide node.
+  struct RefitPlan {
+    uint32_t n_leaves = 0;
+    DeviceBuffer<uint32_t> order4, order8;
+    std::vector<uint32_t> first4, first8;   // level offsets into order4 / order8 (height 0 first)
+    DeviceBuffer<float4> leaf_lo, leaf_hi, lo4, hi4, lo8, hi8;
+    float area_built = 0.0f, area = 0.0f;   // glz_geometry_update_info::box_area_built / box_area, this hierarchy's share
+  };
+  // where a plan's hierarchy lies and what its leaves are made from
+  struct RefitTarget {
+    BvhNode4* nodes;
+    uint32_t n_nodes;
+    BvhNode8* nodes8;
+    uint32_t n_nodes8;
+    BvhQuad* quads;
+    BvhTri* tris;
+    const RTInstance* instances;
+    const TransformPair* transforms;
+  };
+  struct RefitResult {
+    BvhGrid grid;
+    float4 lo, hi;   // the root box
+  };
+  RefitTarget refit_target(const Sources& s, size_t plan) const;
+  bool make_plan(hipStream_t st, const RefitTarget& t, uint32_t n_leaves, RefitPlan& p, Error& err);
+  bool refit(hipStream_t st, const Sources& s, const RefitTarget& t, RefitPlan& p, bool write, RefitResult& out, Error& err);
   bool build_bvh(const Sources& s, Error& err);
   bool build_two_level(const Sources& s, Error& err);
   bool assemble_top_level(const Sources& s, const float4* d_lo, const float4* d_hi, std::vector<float4>& h_lo, std::vector<float4>& h_hi,
@@ -106,6 +147,18 @@ class Accel {
   std::vector<uint64_t> tl_point_count_;
   std::vector<uint32_t> tl_point_base_;
   DeviceBuffer<float4> d_tl_points_, d_tl_mesh_lo_, d_tl_mesh_hi_, d_box_lo_, d_box_hi_;
+
+  // refit: one plan (flattened) or one per mesh; empty = none for the structure as it is.  Two levels: the meshes' pseudo-instances,
+  // the identity transform and its flag as their builds had them, and the lowest / highest vertex index each mesh references.
+  std::vector<RefitPlan> plans_;
+  DeviceBuffer<RTInstance> d_tl_pseudo_;
+  DeviceBuffer<TransformPair> d_tl_ident_;
+  DeviceBuffer<uint32_t> d_tl_one_;
+  std::vector<std::pair<uint32_t, uint32_t>> tl_vertex_span_;
+  DeviceBuffer<BvhGrid> d_refit_grid_;
+  DeviceBuffer<float> d_refit_area_;
+  glz_geometry_update_info update_{};
+  bool update_valid_ = false;
 
   DeviceBuffer<BvhNode4> d_nodes_, d_top_;
   DeviceBuffer<BvhTri> d_tris_;

@@ -1,7 +1,9 @@
-// Host-callable launchers of the HIP kernels (kernels_records.hip, kernels_build.hip, kernels_render.hip, kernels_path.hip, kernels_post.hip).
+// Host-callable launchers of the HIP kernels (kernels_records.hip, kernels_build.hip, kernels_refit.hip, kernels_render.hip, kernels_path.hip, kernels_post.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <vector>
 
 #include "device/types.h"
 #include "glaze_abi.h"
@@ -67,6 +69,28 @@ hipError_t launch_instance_boxes(hipStream_t st, uint32_t n_items, const Instanc
                                  float4* box_lo, float4* box_hi);
 // DeviceScene::alpha_recs for `n` triangle slots (flattened scenes with an opacity map)
 hipError_t launch_alpha_records(hipStream_t st, uint32_t n, const float4* shade_tris, const RTMaterial* materials, const TexDesc* tex_desc, float4* out);
+
+// ---- refit (kernels_refit.hip, Accel::update_geometry): new vertices under a hierarchy that keeps its topology ----
+// The leaf records `quads` (each names its instance, first primitive and first triangle slot) written again from the vertices, with
+// their triangles in `tris` and their float boxes in leaf_lo / leaf_hi, all by the build's rules.
+hipError_t launch_refit_leaves(hipStream_t st, const float4* vertices, const uint32_t* indices, const RTInstance* instances, const TransformPair* transforms,
+                               uint32_t n_leaves, BvhQuad* quads, BvhTri* tris, float4* leaf_lo, float4* leaf_hi);
+// One width of a structure's wide nodes with what the level launches need (the refit plan): the nodes grouped by height above the
+// leaves -- order[level_first[h] .. level_first[h + 1]) are those of height h -- and a float box per node and per leaf.
+struct RefitNodes {
+  int width;        // 4 (BvhNode4) or 8 (BvhNode8)
+  void* nodes;
+  uint32_t n_nodes;
+  const uint32_t* order;   // device
+  const std::vector<uint32_t>& level_first;
+  const float4 *leaf_lo, *leaf_hi;
+  float4 *node_lo, *node_hi;
+};
+// node boxes from the leaf boxes up, one launch per level; then the grid from a root box; then every child box on that grid again
+// (write = false leaves the nodes alone) and, with `area`, the sum of the child boxes' surface areas added to *area
+hipError_t launch_refit_fit(hipStream_t st, const RefitNodes& n);
+hipError_t launch_refit_grid(hipStream_t st, const float4* root_lo, const float4* root_hi, BvhGrid* grid);
+hipError_t launch_refit_quantise(hipStream_t st, const RefitNodes& n, const BvhGrid* grid, bool write, float* area);
 
 // Traversal stack entries each lane keeps in LDS (a near-first 4-wide traversal holds at most three entries per
 // level of the tree; what does not fit spills to a per-lane HBM area).

@@ -40,28 +40,17 @@ __global__ void __launch_bounds__(256) k_world_tris(const float4* __restrict__ v
     const uint32_t* ix = indices + in.index_offset + 3 * prim;
     const float* M = transforms[in.transform_id].o2w;
     vec3 v[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float4 p = vertices[2 * ix[k]];
-      v[k] = xform_point(M, mk3(p.x, p.y, p.z));
-    }
+    world_triangle(vertices, ix, M, v);
     BvhTri t;
-    t.v0[0] = v[0].x; t.v0[1] = v[0].y; t.v0[2] = v[0].z; t.world_id = w;
-    t.v1[0] = v[1].x; t.v1[1] = v[1].y; t.v1[2] = v[1].z; t.instance = inst;
-    t.v2[0] = v[2].x; t.v2[1] = v[2].y; t.v2[2] = v[2].z;
+    set_tri_vertices(t, v);
+    t.world_id = w;
+    t.instance = inst;
     t.prim_flags = prim | (materials[in.material_id].opacity != 0 ? kTriNonOpaque : 0u);   // acceleration.rs:136-141
     tris[w] = t;
-    const float* A = &v[0].x; const float* B = &v[1].x; const float* C = &v[2].x;
     float l[3], h[3];
+    padded_tri_box(v, l, h);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      l[k] = fminf(A[k], fminf(B[k], C[k]));
-      h[k] = fmaxf(A[k], fmaxf(B[k], C[k]));
-      // conservative pad: the ray/triangle test may accept points a few ulps outside the exact box
-      const float pad = 1e-5f * fmaxf(fmaxf(fabsf(l[k]), fabsf(h[k])), 1e-3f);
-      l[k] -= pad; h[k] += pad;
-      clo[k] = chi[k] = 0.5f * (l[k] + h[k]);
-    }
+    for (int k = 0; k < 3; ++k) clo[k] = chi[k] = 0.5f * (l[k] + h[k]);
     box_lo[w] = make_float4(l[0], l[1], l[2], 0.0f);
     box_hi[w] = make_float4(h[0], h[1], h[2], 0.0f);
   }
@@ -238,9 +227,8 @@ __global__ void __launch_bounds__(256) k_leaf_boxes(uint32_t n_world, const uint
   const uint32_t l = (uint32_t)pos[w];
   float4 lo = box_lo[w], hi = box_hi[w];
   if (role[w] & 1) {
-    const float4 l2 = box_lo[w + 1], h2 = box_hi[w + 1];
-    lo = make_float4(fminf(lo.x, l2.x), fminf(lo.y, l2.y), fminf(lo.z, l2.z), 0.0f);
-    hi = make_float4(fmaxf(hi.x, h2.x), fmaxf(hi.y, h2.y), fmaxf(hi.z, h2.z), 0.0f);
+    lo = union_lo(lo, box_lo[w + 1]);
+    hi = union_hi(hi, box_hi[w + 1]);
   }
   leaf_first[l] = w;
   leaf_lo[l] = lo;
@@ -276,18 +264,7 @@ __global__ void __launch_bounds__(256) k_gather_leaves(const uint32_t* __restric
     q.instance = t.instance;
     q.prim_flags = t.prim_flags;
     q.slot = s;
-    const float* c[4] = {t.v0, t.v1, t.v2, t.v2};   // a single triangle: q3 repeats q2 (never looked at)
-    if (role[first] == 1) {            // second triangle = (p0, p2, d)
-      c[3] = tris_in[first + 1].v2;
-    } else if (role[first] == 5) {     // second triangle = (p0, d, p1): it is A, the first one B
-      const BvhTri& b = tris_in[first + 1];
-      c[1] = b.v1;
-      c[2] = t.v1;
-      c[3] = t.v2;
-      q.prim_flags |= kQuadSwapped;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { q.q0[k] = c[0][k]; q.q1[k] = c[1][k]; q.q2[k] = c[2][k]; q.q3[k] = c[3][k]; }
+    quad_corners(q, t, tris_in[first + 1], role[first] == 1, role[first] == 5);
     quads_out[j] = q;
   }
   node_lo[(n - 1) + j] = lo_in[leaf];   // leaf j's box lives at slot (n-1)+j, inner node i's at slot i
@@ -370,8 +347,8 @@ __global__ void __launch_bounds__(256) k_level_up(int n, int level, const int* _
     const int s0 = c.x >= 0 ? c.x : (n - 1) + ~c.x, s1 = c.y >= 0 ? c.y : (n - 1) + ~c.y;
     const float4 l0 = node_lo[s0], l1 = node_lo[s1];
     const float4 h0 = node_hi[s0], h1 = node_hi[s1];
-    node_lo[node] = make_float4(fminf(l0.x, l1.x), fminf(l0.y, l1.y), fminf(l0.z, l1.z), 0.0f);
-    node_hi[node] = make_float4(fmaxf(h0.x, h1.x), fmaxf(h0.y, h1.y), fmaxf(h0.z, h1.z), 0.0f);
+    node_lo[node] = union_lo(l0, l1);
+    node_hi[node] = union_hi(h0, h1);
   }
   counts[node] = 1 + (c.x >= 0 ? counts[c.x] : 0) + (c.y >= 0 ? counts[c.y] : 0);
 }
@@ -525,12 +502,11 @@ __global__ void __launch_bounds__(256) k_dfs_ids(int n, const int2* __restrict__
 
 // Quantisation grid from the root box: kBvhGridMax (32 767) cells per axis, stretched by 2^-16 so the top plane stays below it.  15 bits:
 // the tracer turns a coordinate into the float 32768 + q with one byte permute (device/intersect.h box_key).
-constexpr float kGridReach = 1.9073486e-6f;   // 2^-19
 __global__ void k_grid_params(const float4* __restrict__ node_lo, const float4* __restrict__ node_hi, BvhGrid* __restrict__ grid) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const float lo[3] = {node_lo[0].x, node_lo[0].y, node_lo[0].z}, hi[3] = {node_hi[0].x, node_hi[0].y, node_hi[0].z};
   // the grid reaches kGridReach of the largest coordinate past the bounds on every side, so that the margin the boxes get at
-  // quantisation (grid_margin below) has cells to be counted in: across the thin side of a flat scene the grid is then all margin
+  // quantisation (grid_margin, build_common.h) has cells to be counted in: across the thin side of a flat scene the grid is then all margin
   float largest = 0.0f;
   for (int k = 0; k < 3; ++k) largest = fmaxf(largest, fmaxf(fabsf(lo[k]), fabsf(hi[k])));
   const float reach = kGridReach * largest;
@@ -543,30 +519,8 @@ __global__ void k_grid_params(const float4* __restrict__ node_lo, const float4* 
     grid->inv_cell[k] = 1.0f / cell;
   }
 }
-
-// grid coordinate of a world coordinate; the SAME expression maps the ray origin in the tracer
-__device__ __forceinline__ float to_grid(float x, float lo, float inv_cell) { return (x - lo) * inv_cell; }
-// `margin`: cells every box grows by on that axis beyond the 1/16 (grid_margin below)
-__device__ __forceinline__ uint32_t quant_lo(float x, float lo, float inv_cell, float margin) {
-  // 1/16 cell of slack covers the rounding of to_grid() at grid coordinates up to 32767 (ulp 2^-9)
-  const float g = floorf(to_grid(x, lo, inv_cell) - 0.0625f - margin);
-  return (uint32_t)fminf(fmaxf(g, 0.0f), (float)kBvhGridMax);
-}
-__device__ __forceinline__ uint32_t quant_hi(float x, float lo, float inv_cell, float margin) {
-  const float g = ceilf(to_grid(x, lo, inv_cell) + 0.0625f + margin);
-  return (uint32_t)fminf(fmaxf(g, 0.0f), (float)kBvhGridMax);
-}
-// The tracer leaves a box out when its entry distance lies behind the hit it already has, so a box's entry must not round past the
-// distance of a triangle inside it: the plane distance (an fma in grid space) and the triangle's t (sheared coordinates) each carry a
-// few ulps of the coordinates involved.  Where a cell is a fair fraction of the scene the 1/16 above is that margin; across the thin
-// side of a FLAT scene (a floor plan: every box of no thickness, cells of 1e-13 units, the builders' relative pad nothing near
-// coordinate 0) it is not, and exact ties between coincident triangles went to whichever was met first (tools/gpu_fuzz_parity.py,
-// seed 61907).  So every box also grows by 2^-19 of the largest coordinate of the grid's bounds, whatever that is in cells
-// (k_grid_params lets the grid reach that far past the bounds).
-__device__ __forceinline__ void grid_margin(const BvhGrid& g, float* margin) {
-  float largest = 0.0f;
-  for (int k = 0; k < 3; ++k) largest = fmaxf(largest, fmaxf(fabsf(g.lo[k]), fabsf(g.lo[k] + (float)kBvhGridMax * g.cell[k])));
-  for (int k = 0; k < 3; ++k) margin[k] = fminf((kGridReach * largest) * g.inv_cell[k], 65536.0f);
+hipError_t launch_grid_params(hipStream_t st, const float4* root_lo, const float4* root_hi, BvhGrid* grid) {
+  return launch(k_grid_params, dim3(1), dim3(64), st, root_lo, root_hi, grid);
 }
 
 // ---- 4-wide collapse.  A BVH4 node starts from the two children of a binary node and keeps opening the inner child
@@ -667,7 +621,7 @@ __global__ void __launch_bounds__(256) k_emit_nodes4(int n, const int2* __restri
     const float4 l = node_lo[box], h = node_hi[box];
     const uint32_t q[6] = {quant_lo(l.x, g.lo[0], g.inv_cell[0], gm[0]), quant_lo(l.y, g.lo[1], g.inv_cell[1], gm[1]), quant_lo(l.z, g.lo[2], g.inv_cell[2], gm[2]),
                            quant_hi(h.x, g.lo[0], g.inv_cell[0], gm[0]), quant_hi(h.y, g.lo[1], g.inv_cell[1], gm[1]), quant_hi(h.z, g.lo[2], g.inv_cell[2], gm[2])};
-    nd.w[3 * k] = q[0] | (q[3] << 16);       // one word per axis: lo | hi << 16
+    nd.w[3 * k] = q[0] | (q[3] << 16);       // one word per axis: lo | hi << 16 (build_common.h quant_box)
     nd.w[3 * k + 1] = q[1] | (q[4] << 16);
     nd.w[3 * k + 2] = q[2] | (q[5] << 16);
     // inner: its number among the BVH4 nodes; leaf: ~(first slot of the leaf in bvh_tris), or ~(leaf number) when the tracer reads
@@ -698,9 +652,7 @@ __global__ void __launch_bounds__(256) k_emit_nodes8(int n, const int2* __restri
     }
     const int box = ch >= 0 ? ch : (n - 1) + ~ch;
     const float4 l = node_lo[box], h = node_hi[box];
-    nd.w[3 * k] = quant_lo(l.x, g.lo[0], g.inv_cell[0], gm[0]) | (quant_hi(h.x, g.lo[0], g.inv_cell[0], gm[0]) << 16);
-    nd.w[3 * k + 1] = quant_lo(l.y, g.lo[1], g.inv_cell[1], gm[1]) | (quant_hi(h.y, g.lo[1], g.inv_cell[1], gm[1]) << 16);
-    nd.w[3 * k + 2] = quant_lo(l.z, g.lo[2], g.inv_cell[2], gm[2]) | (quant_hi(h.z, g.lo[2], g.inv_cell[2], gm[2]) << 16);
+    quant_box(l, h, g, gm, &nd.w[3 * k]);
     nd.w[24 + k] = (uint32_t)(ch >= 0 ? (int)pos[new_id[ch]] : ch);
   }
   nodes[pos[new_id[i]]] = nd;

@@ -560,6 +560,17 @@ bool Renderer::update_transforms(const glz_transform* t, uint32_t n, Error& err)
   return group_.forward([=](Renderer& p, Error& e) { return p.update_transforms(t, n, e); }, err);
 }
 
+// Deforms the meshes: like update_transforms, on the scene object, with a restart, and followed by every other device's replica.
+bool Renderer::update_vertices(const glz_vertex* v, uint32_t first, uint32_t n, int mode, Error& err) {
+  if (!update_scene([&] { return scene_->update_vertices(v, first, n, mode, err); }, err)) return false;
+  return group_.forward([=](Renderer& p, Error& e) { return p.update_vertices(v, first, n, mode, e); }, err);
+}
+
+bool Renderer::geometry_update_info(glz_geometry_update_info& out, Error& err) {
+  if (!scene_) return err.fail(GLZ_E_ARG, "renderer has no scene");
+  return wait_idle(err) && scene_->geometry_update_info(out, err);
+}
+
 // raytracer.rs:328-356.  The reference rebuilds descriptors, pipeline and SBT and leaves the accumulation alone; here the
 // kernels read the texture array through the scene struct of every launch, so re-uploading it is all there is to do.
 bool Renderer::refresh_binded_textures(const glz_texture* t, uint32_t nt, Error& err) {

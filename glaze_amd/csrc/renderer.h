@@ -29,6 +29,8 @@ class Renderer {
   bool update_materials_and_lights(const glz_material* m, uint32_t nm, const glz_light* l, uint32_t nl, const glz_texture* t, uint32_t nt, Error& err);
   bool refresh_binded_textures(const glz_texture* t, uint32_t nt, Error& err);
   bool update_transforms(const glz_transform* t, uint32_t n, Error& err);   // Scene::update_transforms; restarts accumulation
+  bool update_vertices(const glz_vertex* v, uint32_t first, uint32_t n, int mode, Error& err);   // Scene::update_vertices; restarts accumulation
+  bool geometry_update_info(glz_geometry_update_info& out, Error& err);   // Scene::geometry_update_info, idle first (it may make the refit plan); accumulation goes on
   bool wait_idle(Error& err);
   uint32_t steps_per_sample() const { return cfg_.integrator == GLZ_DIRECT ? 1u : cfg_.pt_steps; }
 

@@ -252,4 +252,28 @@ bool Scene::update_transforms(const glz_transform* transforms, uint32_t n, Error
   return accel_.rebuild(sources(), err);
 }
 
+bool Scene::geometry_update_info(glz_geometry_update_info& out, Error& err) {
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  Composed at_exit{*this};
+  return accel_.geometry_update(sources(), out, err);
+}
+
+bool Scene::update_vertices(const glz_vertex* vertices, uint32_t first, uint32_t n, int mode, Error& err) {
+  if (!vertices || n == 0 || (uint64_t)first + n > data.vertices.size())
+    return err.fail(GLZ_E_ARG, "update_vertices: null vertices, none, or a range past the scene's vertex count");
+  if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return err.fail(GLZ_E_ARG, "update_vertices: unknown mode");
+  // (valid_geometry, which creation runs, looks at index ranges and references alone: no position is refused there, so none is here)
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  hipStream_t st = instance->stream;
+  Composed at_exit{*this};
+  if (mode == GLZ_GEOMETRY_REFIT && !accel_.prepare_refit(sources(), err)) return false;   // needs the vertices the structure was built from
+  StreamTimer timer;
+  if (!timer.start(st, err)) return false;
+  std::copy(vertices, vertices + n, data.vertices.begin() + first);
+  if (!hip_ok(hipMemcpyAsync(geometry_.vertices.ptr + 2 * (size_t)first, data.vertices.data() + first, sizeof(glz_vertex) * n, hipMemcpyHostToDevice, st), "upload vertices", err) ||
+      !hip_ok(launch_derivatives(st, geometry_.vertices.ptr, geometry_.indices.ptr, (uint32_t)(geometry_.derivatives.count / 3), geometry_.derivatives.ptr), "derivatives kernel", err))
+    return false;
+  return accel_.update_geometry(sources(), mode, first, n, timer, err);
+}
+
 }  // namespace glz

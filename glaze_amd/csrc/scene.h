@@ -57,6 +57,11 @@ class Scene {
   // ratio and shape the scene was created with, and equals a scene created with these transforms (Accel::rebuild).  Lights, sky,
   // materials and textures are left alone.
   bool update_transforms(const glz_transform* transforms, uint32_t n, Error& err);
+  // New vertices (positions, normals, texture coordinates) for [first, first + n) of the vertex buffer; indices and everything else stay.
+  // The derivatives are computed again and the structure follows by Accel::update_geometry in `mode` (GLZ_GEOMETRY_*); either way the
+  // scene traces and renders as one created with the new vertices does.  Refused arguments (GLZ_E_ARG) leave the scene untouched.
+  bool update_vertices(const glz_vertex* vertices, uint32_t first, uint32_t n, int mode, Error& err);
+  bool geometry_update_info(glz_geometry_update_info& out, Error& err);   // Accel::geometry_update
   // Instance boxes of a two-level scene under its current transforms (host rule, or the device kernel); false with an empty result
   // for a flattened scene.  budget: kExactBoxBudget for the scene's own.
   bool instance_boxes(bool on_device, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err);

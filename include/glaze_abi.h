@@ -278,8 +278,8 @@ typedef struct glz_scene_info {
   uint64_t n_world_triangles;                /* after instancing (BVH primitives)       */
   uint32_t n_instances, n_materials, n_lights /* lights_no, scene.rs:1549 */, n_rt_lights, n_textures;
   uint32_t bvh_nodes, bvh_depth;
-  float bvh_sah_cost;
-  float build_ms;                            /* hierarchy build time on the device (whichever builder) */
+  float bvh_sah_cost;                        /* of the last BUILD: a refit (glz_renderer_update_vertices) keeps the topology and leaves this figure, bvh_depth, bvh_nodes* and as_bytes alone */
+  float build_ms;                            /* hierarchy build time on the device (whichever builder); after update_vertices the update's stream time */
   float bounds_min[3], bounds_max[3];
   float bvh_grid_lo[3], bvh_grid_cell[3];    /* quantisation grid of the BVH node boxes: world = lo + q * cell */
   uint32_t as_levels;                        /* 1 = one hierarchy over all instanced triangles, 2 = TLAS over per-mesh BLAS */
@@ -320,6 +320,30 @@ int glz_renderer_update_materials_and_lights(glz_renderer*, const glz_material* 
  * its meshes' hierarchies and rebuilds only the top level.  Non-finite or singular transforms are taken as creation takes them.
  * GLZ_E_ARG (nothing changes): null transforms, a different count. */
 int glz_renderer_update_transforms(glz_renderer*, const glz_transform* transforms, uint32_t n_transforms);
+/* Build-defined (the reference has nothing like it): deforming meshes.  Replaces vertices [first_vertex, first_vertex + n_vertices) of
+ * the scene's vertex buffer: positions, normals, texture coordinates.  Indices, meshes, instances, transforms, materials, lights and
+ * textures stay.  Waits for the renderer to go idle; restarts accumulation; reaches every device of set_devices; acts on the SCENE
+ * object, so every renderer sharing the scene sees the change (as with update_transforms).  Afterwards hits and renders equal, bit for
+ * bit, those of a scene created with the new vertices, in both modes:
+ *   GLZ_GEOMETRY_REFIT    the hierarchy keeps its topology; leaf records, boxes and the quantisation grid are refitted on the device (a
+ *                         two-level scene refits the meshes whose indices reach into the range and rebuilds its top level);
+ *   GLZ_GEOMETRY_REBUILD  the builder runs again, with the options and the shape the scene was created with.
+ * A refitted tree traces the slower the further the mesh has moved from the shape it was built for: glz_geometry_update_info gives the
+ * figure to decide on a rebuild by (the library never rebuilds on its own).  After a refit glz_scene_info's bounds_* and bvh_grid_* are
+ * the new ones and build_ms is the update's stream time; bvh_sah_cost, bvh_depth, bvh_nodes* and as_bytes are those of the last build.
+ * GLZ_E_ARG (the scene is untouched): null vertices, n_vertices == 0, a range past the vertex count, an unknown mode.  (Creation checks
+ * index ranges and references, never positions: there is no position it would refuse, and none is refused here.) */
+#define GLZ_GEOMETRY_REFIT   0   /* keep the topology, refit boxes and records (default) */
+#define GLZ_GEOMETRY_REBUILD 1   /* run the builder again, with the options and shape the scene was created with */
+int glz_renderer_update_vertices(glz_renderer*, const glz_vertex* vertices, uint32_t first_vertex, uint32_t n_vertices, int mode);
+typedef struct glz_geometry_update_info {
+  uint32_t mode;            /* what the last update_vertices did */
+  uint32_t meshes_touched;  /* two-level scenes: meshes whose hierarchy was refitted / rebuilt; flattened: 1 */
+  float    update_ms;       /* device-event time on the stream: upload to last kernel */
+  float    box_area;        /* sum of the surface areas of all child boxes of the 4-wide nodes (two levels: of the meshes' nodes) after the update (float, reported only: the sum's order is not fixed) */
+  float    box_area_built;  /* the same sum for the structure as the builder left it (taken on the first refit after a build, before the new vertices go in; after a rebuild, of the new structure) */
+} glz_geometry_update_info;
+int glz_renderer_geometry_update_info(glz_renderer*, glz_geometry_update_info* out);   /* GLZ_E_ARG before any update */
 /* raytracer.rs:328-356: the texture array changed under the same materials and lights (the reference re-binds the
  * textures it shares with the realtime viewer); accumulation is NOT restarted, like the reference. */
 int glz_renderer_refresh_binded_textures(glz_renderer*, const glz_texture* textures, uint32_t n_textures);
@@ -657,6 +681,8 @@ int64_t glz_debug_read_bvh(glz_scene*, void* nodes_out, int64_t cap_nodes, void*
 /* The same hierarchy as 128-byte 8-wide nodes (what the tracer of a small tile share walks; glz_scene_info::bvh_nodes8 of them, flattened
  * builds only): child k's box words at [3k .. 3k+2], its link at [24 + k], leaf links name the first triangle slot as above. */
 int64_t glz_debug_read_bvh8(glz_scene*, void* nodes_out, int64_t cap_nodes);
+/* The 64-byte per-leaf records the tracers read, as they are on the device (returns their count; a two-level scene's are its meshes' concatenated) */
+int64_t glz_debug_read_leaf_records(glz_scene*, void* out, int64_t cap_records);
 
 /* 192-byte TlasInstance records of a two-level scene in the top level's leaf order (returns the byte count; 0 for a flattened scene) */
 int64_t glz_debug_read_tlas_instances(glz_scene*, void* out, int64_t cap_bytes);
