@@ -155,6 +155,19 @@ def _transform_array(transforms):
     return t
 
 
+def _vertex_array(vertices):
+    """(n, 8) float32 of an (n, 8) array, a VERTEX_DTYPE array (SceneDesc.vertices as it is) or an abi.Vertex array"""
+    if isinstance(vertices, C.Array) and vertices._type_ is abi.Vertex:
+        v = np.frombuffer(vertices, np.float32).reshape(-1, 8)
+    elif getattr(vertices, "dtype", None) == VERTEX_DTYPE:
+        v = np.ascontiguousarray(vertices).view(np.float32).reshape(-1, 8)
+    else:
+        v = np.ascontiguousarray(vertices, np.float32)
+    if v.ndim != 2 or v.shape[1] != 8:
+        raise ValueError("vertices must be an (n, 8) array (position, normal, texture coordinate), got shape %s" % (v.shape,))
+    return v
+
+
 def host_instance_boxes(desc, budget=0):
     """The top level's instance boxes by the host rule on a SceneDesc, without a device ((n, 4) float32 lo, hi; one per instance that
     names an existing mesh).  A mesh's box is the min / max of its vertices here.  budget 0 = the library's exact-box budget."""
@@ -685,14 +698,7 @@ class RayTraceRenderer:
         abi.Vertex array, written over the scene's vertices [first, first + n).  mode 'refit' keeps the hierarchy's topology and refits
         it on the device, 'rebuild' runs the builder again; either way the scene then equals one created with the new vertices (every
         renderer sharing it sees the change) and accumulation restarts."""
-        if isinstance(vertices, C.Array) and vertices._type_ is abi.Vertex:
-            v = np.frombuffer(vertices, np.float32).reshape(-1, 8)
-        elif getattr(vertices, "dtype", None) == VERTEX_DTYPE:      # SceneDesc.vertices as it is
-            v = np.ascontiguousarray(vertices).view(np.float32).reshape(-1, 8)
-        else:
-            v = np.ascontiguousarray(vertices, np.float32)
-        if v.ndim != 2 or v.shape[1] != 8:
-            raise ValueError("vertices must be an (n, 8) array (position, normal, texture coordinate), got shape %s" % (v.shape,))
+        v = _vertex_array(vertices)
         abi.check(abi.lib().glz_renderer_update_vertices(self._h, _ptr(v), int(first), v.shape[0], self._GEOMETRY_MODES.get(mode, mode)))
 
     def geometry_update_info(self):
@@ -832,36 +838,60 @@ class RayTraceRenderer:
         abi.check(abi.lib().glz_renderer_read_despeckled(self._h, _ptr(out), _ptr(img) if want_rgba8 else None))
         return (out, img) if want_rgba8 else out
 
-    def read_motion(self, prev_camera, prev_transforms=None):
+    def _previous_state(self, prev_camera, prev_transforms, prev_vertices, first_vertex):
+        """abi.PreviousState and the arrays it points into (keep them alive as long as the state is used)"""
+        t = None if prev_transforms is None else _transform_array(prev_transforms)
+        v = None if prev_vertices is None else _vertex_array(prev_vertices)
+        state = abi.PreviousState(C.cast(C.byref(prev_camera), C.c_void_p), None if t is None else _ptr(t), 0 if t is None else t.shape[0],
+                                  None if v is None else _ptr(v), int(first_vertex), 0 if v is None else v.shape[0])
+        return state, (prev_camera, t, v)
+
+    def read_motion(self, prev_camera, prev_transforms=None, prev_vertices=None, first_vertex=0):
         """The motion plane (include/glaze_abi.h holds the specification): H x W x 4 float32, per pixel (where the first hit of the centre
-        ray was on screen under prev_camera and prev_transforms, minus the pixel's own centre; its distance from the previous eye; the
-        hit's instance bits).  prev_transforms: (n, 16) float32 as update_transforms takes them, None = the instances did not move.
-        Accumulation goes on."""
+        ray was on screen under prev_camera, prev_transforms and prev_vertices, minus the pixel's own centre; its distance from the previous
+        eye; the hit's instance bits).  prev_transforms: (n, 16) float32 as update_transforms takes them, None = the instances did not move.
+        prev_vertices: what the scene's vertices [first_vertex, first_vertex + n) held in the previous frame, in any form update_vertices
+        takes, None = the meshes did not deform.  Accumulation goes on."""
         out = np.zeros((self.height, self.width, 4), np.float32)
+        if prev_vertices is not None:
+            state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
+            abi.check(abi.lib().glz_renderer_read_motion_from(self._h, C.cast(C.byref(state), C.c_void_p), _ptr(out)))
+            return out
         t = None if prev_transforms is None else _transform_array(prev_transforms)
         abi.check(abi.lib().glz_renderer_read_motion(self._h, C.cast(C.byref(prev_camera), C.c_void_p), None if t is None else _ptr(t), 0 if t is None else t.shape[0],
                                                      _ptr(out)))
         return out
 
-    def debug_motion_timing(self, prev_camera, prev_transforms=None):
-        """read_motion's pass without the read-back: the device-event time of k_motion alone, in milliseconds"""
-        t = None if prev_transforms is None else _transform_array(prev_transforms)
+    def debug_motion_timing(self, prev_camera, prev_transforms=None, prev_vertices=None, first_vertex=0):
+        """read_motion's pass without the read-back: the device-event time of k_motion alone (with prev_vertices: of k_motion_deform), in
+        milliseconds"""
         ms = C.c_float(0.0)
+        if prev_vertices is not None:
+            state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
+            abi.check(abi.lib().glz_debug_motion_timing_from(self._h, C.cast(C.byref(state), C.c_void_p), C.cast(C.byref(ms), C.c_void_p)))
+            return ms.value
+        t = None if prev_transforms is None else _transform_array(prev_transforms)
         abi.check(abi.lib().glz_debug_motion_timing(self._h, C.cast(C.byref(prev_camera), C.c_void_p), None if t is None else _ptr(t), 0 if t is None else t.shape[0],
                                                     C.cast(C.byref(ms), C.c_void_p)))
         return ms.value
 
-    def reproject(self, prev_camera, prev_color, prev_aov0, prev_aov1, prev_transforms=None, **params):
+    def reproject(self, prev_camera, prev_color, prev_aov0, prev_aov1, prev_transforms=None, prev_vertices=None, first_vertex=0, **params):
         """The previous frame's colour carried to this frame's pixels with disocclusion rejection: H x W x 4 float32 (rgb, confidence
         0 .. 1).  prev_color: any H x W x 4 image of the previous frame; prev_aov0 / prev_aov1: read_aov(0) / read_aov(1) of the previous
-        state in first-hit mode; params: glz_reproject_params (depth_tolerance).  Accumulation goes on."""
+        state in first-hit mode; prev_transforms, prev_vertices, first_vertex: as read_motion takes them; params: glz_reproject_params
+        (depth_tolerance).  Accumulation goes on."""
         shape = (self.height, self.width, 4)
         c, a0, a1 = (np.ascontiguousarray(f, np.float32) for f in (prev_color, prev_aov0, prev_aov1))
         if c.shape != shape or a0.shape != shape or a1.shape != shape:
             raise ValueError("prev_color, prev_aov0 and prev_aov1 must be H x W x 4 of the renderer's size")
         out = np.zeros(shape, np.float32)
-        t = None if prev_transforms is None else _transform_array(prev_transforms)
         p = abi.ReprojectParams(**params)
+        if prev_vertices is not None:
+            state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
+            abi.check(abi.lib().glz_renderer_reproject_from(self._h, C.cast(C.byref(state), C.c_void_p), _ptr(c), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p),
+                                                            _ptr(out)))
+            return out
+        t = None if prev_transforms is None else _transform_array(prev_transforms)
         abi.check(abi.lib().glz_renderer_reproject(self._h, C.cast(C.byref(prev_camera), C.c_void_p), None if t is None else _ptr(t), 0 if t is None else t.shape[0],
                                                    _ptr(c), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out)))
         return out

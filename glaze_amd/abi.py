@@ -149,6 +149,12 @@ class ReprojectParams(C.Structure):
         super().__init__(**dict(self.DEFAULTS, **kw))
 
 
+class PreviousState(C.Structure):
+    """glz_previous_state: what glz_renderer_read_motion_from / glz_renderer_reproject_from take for the previous frame"""
+    _fields_ = [("camera", C.c_void_p), ("transforms", C.c_void_p), ("n_transforms", C.c_uint32), ("vertices", C.c_void_p),
+                ("first_vertex", C.c_uint32), ("n_vertices", C.c_uint32)]
+
+
 AOV_NORMAL_DEPTH, AOV_ALBEDO_INSTANCE = 0, 1
 GUIDE_FIRST_HIT, GUIDE_THROUGH_SPECULAR, GUIDE_MAX_BOUNCES = 0, 1, 8
 DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_POWER_LOG2 = 8, 31
@@ -270,6 +276,9 @@ PROTOTYPES = {
     "glz_renderer_read_despeckled": (C.c_int, [_P, _P, _P]),
     "glz_renderer_read_motion": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "glz_renderer_reproject": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "glz_renderer_read_motion_from": (C.c_int, [_P, _P, _P]),
+    "glz_renderer_reproject_from": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "glz_debug_motion_timing_from": (C.c_int, [_P, _P, _P]),
     "glz_host_project_constants": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "glz_host_project_points": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P]),
     "glz_host_reproject": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P]),

@@ -429,7 +429,14 @@ int glz_renderer_read_motion(glz_renderer* h, const glz_camera* prev_camera, con
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!prev_camera || !out) return fail(GLZ_E_ARG, "the previous camera or the output is null");
   if (prev_camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
-  GLZ_RET(h->r->post().read_motion(prev_camera, prev_transforms, n_prev_transforms, out, e));
+  GLZ_RET(h->r->post().read_motion(glz_previous_state{prev_camera, prev_transforms, n_prev_transforms, nullptr, 0, 0}, out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_read_motion_from(glz_renderer* h, const glz_previous_state* prev, float* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!prev || !prev->camera || !out) return fail(GLZ_E_ARG, "the previous state, its camera or the output is null");
+  if (prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
+  GLZ_RET(h->r->post().read_motion(*prev, out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_reproject(glz_renderer* h, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms, const float* prev_color,
@@ -437,7 +444,15 @@ int glz_renderer_reproject(glz_renderer* h, const glz_camera* prev_camera, const
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!prev_camera || !prev_color || !prev_aov0 || !prev_aov1 || !out) return fail(GLZ_E_ARG, "the previous camera, a previous frame or the output is null");
   if (prev_camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
-  GLZ_RET(h->r->post().reproject(prev_camera, prev_transforms, n_prev_transforms, prev_color, prev_aov0, prev_aov1, params, out, e));
+  GLZ_RET(h->r->post().reproject(glz_previous_state{prev_camera, prev_transforms, n_prev_transforms, nullptr, 0, 0}, prev_color, prev_aov0, prev_aov1, params, out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_reproject_from(glz_renderer* h, const glz_previous_state* prev, const float* prev_color, const float* prev_aov0, const float* prev_aov1,
+                                const glz_reproject_params* params, float* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!prev || !prev->camera || !prev_color || !prev_aov0 || !prev_aov1 || !out) return fail(GLZ_E_ARG, "the previous state, its camera, a previous frame or the output is null");
+  if (prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
+  GLZ_RET(h->r->post().reproject(*prev, prev_color, prev_aov0, prev_aov1, params, out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_launch_constants(glz_renderer* h, uint32_t launch, uint32_t* seed, float off[2]) {

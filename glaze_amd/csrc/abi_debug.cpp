@@ -101,7 +101,14 @@ int glz_debug_motion_timing(glz_renderer* h, const glz_camera* prev_camera, cons
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!prev_camera || !kernel_ms_out || prev_camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "bad argument");
   *kernel_ms_out = 0.0f;
-  GLZ_RET(h->r->post().time_motion(prev_camera, prev_transforms, n_prev_transforms, kernel_ms_out, e));
+  GLZ_RET(h->r->post().time_motion(glz_previous_state{prev_camera, prev_transforms, n_prev_transforms, nullptr, 0, 0}, kernel_ms_out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_motion_timing_from(glz_renderer* h, const glz_previous_state* prev, float* kernel_ms_out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!prev || !prev->camera || !kernel_ms_out || prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "bad argument");
+  *kernel_ms_out = 0.0f;
+  GLZ_RET(h->r->post().time_motion(*prev, kernel_ms_out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_debug_guide_chain(glz_renderer* h, uint32_t segment, float* origins3, float* dirs3, uint8_t* alive) {

@@ -21,11 +21,13 @@ __device__ __forceinline__ ShadeRecord load_shade_record(const DeviceScene& S, u
   const float4* rec = S.shade_tris + 8u * (size_t)leaf;
   return ShadeRecord{rec[0], rec[1], rec[2], rec[3], rec[4], rec[5], rec[6], rec[7]};
 }
-// the object-space point of the hit `hr` = (t, u, v, leaf)
-__device__ __forceinline__ vec3 hit_point(const ShadeRecord& r, float4 hr) {
+// the point of the hit `hr` = (t, u, v, leaf) on the triangle (a, b, c), the corners in index-buffer order (.w is not read)
+__device__ __forceinline__ vec3 hit_point(float4 a, float4 b, float4 c, float4 hr) {
   const float b0 = 1.0f - hr.y - hr.z, b1 = hr.y, b2 = hr.z;
-  return (mk3(r.va0.x, r.va0.y, r.va0.z) * b0 + mk3(r.vb0.x, r.vb0.y, r.vb0.z) * b1) + mk3(r.vc0.x, r.vc0.y, r.vc0.z) * b2;
+  return (mk3(a.x, a.y, a.z) * b0 + mk3(b.x, b.y, b.z) * b1) + mk3(c.x, c.y, c.z) * b2;
 }
+// the object-space point of the hit, from the record's positions
+__device__ __forceinline__ vec3 hit_point(const ShadeRecord& r, float4 hr) { return hit_point(r.va0, r.vb0, r.vc0, hr); }
 // Material and transform of the hit.  In two-level scenes the record is per OBJECT triangle and both are the instance's: `inst_of()`
 // gives its index and is called in those scenes only.  FLAG: xf carries in bit 31 that the transform is an exact identity (a flat scene's
 // record has the bit, S.xf_identity is read for an instance); without, xf is the plain index and nothing more is read.

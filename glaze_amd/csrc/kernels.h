@@ -228,10 +228,12 @@ hipError_t launch_despeckle(hipStream_t st, uint32_t w, uint32_t h, const glz_de
                             const float4* aov0, const float4* aov1, float4* ping, float4* out, hipEvent_t* despeckle_marks = nullptr);
 // Motion and reprojection (reproject.h).  launch_motion: after launch_first_hit on the same stream and with the same `a`, BEFORE the
 // attribute kernel or the guide chain (the chain reuses `hit` / `inst`); prev_o2w: one column-major 4x4 per transform of the scene, 64 B
-// apart, or null = the scene's own; motion: width * height float4.  launch_reproject: all frames are device memory, w * h float4 each, out
-// may not alias an input; marks (may be null): two events around the kernel.
+// apart, or null = the scene's own; motion: width * height float4; prev_vertices: null (k_motion), or the previous contents of the scene's
+// vertices [first_vertex, first_vertex + n_vertices), two float4 each as the scene stores them, the range inside the scene's vertex count
+// (k_motion_deform: the caller has checked the range, the kernel indexes by it).  launch_reproject: all frames are device memory, w * h
+// float4 each, out may not alias an input; marks (may be null): two events around the kernel.
 hipError_t launch_motion(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, const float4* prev_o2w, const post::ProjectConstants& prev,
-                         float4* motion);
+                         float4* motion, const float4* prev_vertices = nullptr, uint32_t first_vertex = 0, uint32_t n_vertices = 0);
 hipError_t launch_reproject(hipStream_t st, uint32_t w, uint32_t h, const glz_reproject_params& params, const float4* motion, const float4* prev_color,
                             const float4* prev_aov0, const float4* prev_aov1, float4* out, hipEvent_t* marks = nullptr);
 hipError_t launch_project_points(hipStream_t st, const post::ProjectConstants& C, uint32_t w, uint32_t h, const float* points3, uint32_t n, float* out3);

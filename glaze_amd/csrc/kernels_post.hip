@@ -328,28 +328,74 @@ __global__ void __launch_bounds__(kBlock) k_despeckle(uint32_t w, uint32_t h, ui
 //                128-byte line), 64 B of the previous object -> world matrix (the caller's, 64 B apart, or the scene's own, the first half
 //                of its 128-byte TransformPair), one float4 out.  Record, point and transform index are hit_vertex.h's; nothing is skipped
 //                for a transform flagged identity: the previous one need not be.
+//   k_motion_deform  k_motion for meshes that deformed (glz_previous_state::vertices): the object-space point comes from the PREVIOUS
+//                positions of the hit triangle's vertices, which no record holds, so the kernel walks to them: the hit record and the
+//                instance, then the leaf's primitive number (4 B of its BvhTri) and the RTInstance (16 B) together, then the three indices
+//                and the 64 B of the previous matrix together, then three position float4s -- from the caller's array for an index inside
+//                [first, first + count), from the scene's own vertices otherwise: the base pointer is selected, the load is one and
+//                unconditional.  Four dependent levels, nothing in a level waits for another of the same level; the shading record is not
+//                read.  Instance and transform are what k_motion takes: a flat scene's record carries the transform id of the leaf's instance.
+//                Both kernels are motion_pixel, so the arithmetic behind the point is one text.  No LDS, no scratch, no loop.
 //   k_reproject  k_atrous's layout.  A wave's taps sit at p + motion with nearly equal motion, so they fall in a few lines; every load is
 //                requested before the first is used.  No LDS, no scratch, no loop with a data-dependent trip count.
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kBlock) k_motion(const DeviceScene S, uint32_t w, uint32_t h, const float4* __restrict__ hit, const uint32_t* __restrict__ inst,
-                                                   const float4* __restrict__ prev_o2w, const post::ProjectConstants C, float4* __restrict__ out) {
+struct PrevVertices {
+  const float4* v;         // device: the caller's glz_vertex array as it is, two float4 per vertex, the position in the first
+  uint32_t first, count;   // the scene's vertices [first, first + count)
+};
+template <bool DEFORM>
+__device__ __forceinline__ void motion_pixel(const DeviceScene& S, uint32_t w, uint32_t h, const float4* __restrict__ hit, const uint32_t* __restrict__ inst,
+                                             const float4* __restrict__ prev_o2w, const PrevVertices& V, const post::ProjectConstants& C, float4* __restrict__ out) {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   if (p >= w * h) return;
   const float4 hr = hit[p];
+  uint32_t hit_inst = 0;
+  if (DEFORM) {   // requested beside the record, not behind the miss test: the walk starts from both (a miss's is read and dropped)
+    hit_inst = inst[p];
+    asm volatile("" : "+v"(hit_inst));   // (no instruction: it keeps the compiler from sinking the load behind the branch, where it would wait alone)
+  }
   const uint32_t leaf = __float_as_uint(hr.w);
   if (leaf == 0xFFFFFFFFu) {
     out[p] = make_float4(0.0f, 0.0f, INFINITY, __uint_as_float(0xFFFFFFFFu));
     return;
   }
-  const uint32_t hit_inst = inst[p];
-  const ShadeRecord rec = load_shade_record(S, leaf);
-  const uint32_t xf = hit_ids<false>(S, rec, [&]() { return hit_inst; }).xf;
-  const vec3 point = hit_point(rec, hr);
-  const float4* xq = prev_o2w ? prev_o2w + 4u * (size_t)xf : reinterpret_cast<const float4*>(&S.transforms[xf]);
-  const float4 m0 = xq[0], m1 = xq[1], m2 = xq[2], m3 = xq[3];
+  if (!DEFORM) hit_inst = inst[p];
+  uint32_t xf;
+  vec3 point;
+  float4 m0, m1, m2, m3;
+  if (DEFORM) {
+    const uint32_t prim = S.bvh_tris[leaf].prim_flags & kTriPrimMask;
+    const RTInstance in = S.instances[hit_inst];   // flat: the leaf's own instance; two levels: the leaf is the mesh's, whose indices the instance names
+    const uint32_t* ix = S.indices + in.index_offset + 3u * (size_t)prim;
+    const uint32_t i0 = ix[0], i1 = ix[1], i2 = ix[2];
+    xf = in.transform_id;
+    const float4* xq = prev_o2w ? prev_o2w + 4u * (size_t)xf : reinterpret_cast<const float4*>(&S.transforms[xf]);
+    m0 = xq[0], m1 = xq[1], m2 = xq[2], m3 = xq[3];
+    const auto position = [&](uint32_t i) {   // (i - first wraps for i < first: not below count)
+      const bool previous = i - V.first < V.count;
+      return (previous ? V.v : S.vertices)[2u * (size_t)(previous ? i - V.first : i)];
+    };
+    const float4 a = position(i0), b = position(i1), c = position(i2);
+    point = hit_point(a, b, c, hr);
+  } else {
+    const ShadeRecord rec = load_shade_record(S, leaf);
+    xf = hit_ids<false>(S, rec, [&]() { return hit_inst; }).xf;
+    point = hit_point(rec, hr);
+    const float4* xq = prev_o2w ? prev_o2w + 4u * (size_t)xf : reinterpret_cast<const float4*>(&S.transforms[xf]);
+    m0 = xq[0], m1 = xq[1], m2 = xq[2], m3 = xq[3];
+  }
   const float o2w[16] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w, m3.x, m3.y, m3.z, m3.w};
   const vec3 prev = xform_point(o2w, point);
   out[p] = post::motion_value(C, w, h, p % w, p / w, prev.x, prev.y, prev.z, __uint_as_float(hit_inst));
+}
+__global__ void __launch_bounds__(kBlock) k_motion(const DeviceScene S, uint32_t w, uint32_t h, const float4* __restrict__ hit, const uint32_t* __restrict__ inst,
+                                                   const float4* __restrict__ prev_o2w, const post::ProjectConstants C, float4* __restrict__ out) {
+  motion_pixel<false>(S, w, h, hit, inst, prev_o2w, PrevVertices{nullptr, 0u, 0u}, C, out);
+}
+__global__ void __launch_bounds__(kBlock) k_motion_deform(const DeviceScene S, uint32_t w, uint32_t h, const float4* __restrict__ hit, const uint32_t* __restrict__ inst,
+                                                          const float4* __restrict__ prev_o2w, const PrevVertices V, const post::ProjectConstants C,
+                                                          float4* __restrict__ out) {
+  motion_pixel<true>(S, w, h, hit, inst, prev_o2w, V, C, out);
 }
 __global__ void __launch_bounds__(kBlock) k_reproject(uint32_t w, uint32_t h, float tolerance, const float4* __restrict__ motion, const float4* __restrict__ color,
                                                       const float4* __restrict__ aov0, const float4* __restrict__ aov1, float4* __restrict__ out) {
@@ -453,8 +499,11 @@ hipError_t launch_despeckle(hipStream_t st, uint32_t w, uint32_t h, const glz_de
   return hipGetLastError();
 }
 hipError_t launch_motion(hipStream_t st, const LaunchArgs& a, const float4* hit, const uint32_t* inst, const float4* prev_o2w, const post::ProjectConstants& prev,
-                         float4* motion) {
-  return launch_per_item(st, k_motion, a.map.width * a.map.height, a.scene, a.map.width, a.map.height, hit, inst, prev_o2w, prev, motion);
+                         float4* motion, const float4* prev_vertices, uint32_t first_vertex, uint32_t n_vertices) {
+  if (!prev_vertices) return launch_per_item(st, k_motion, a.map.width * a.map.height, a.scene, a.map.width, a.map.height, hit, inst, prev_o2w, prev, motion);
+  if (n_vertices == 0) return hipErrorInvalidValue;
+  return launch_per_item(st, k_motion_deform, a.map.width * a.map.height, a.scene, a.map.width, a.map.height, hit, inst, prev_o2w,
+                         PrevVertices{prev_vertices, first_vertex, n_vertices}, prev, motion);
 }
 hipError_t launch_reproject(hipStream_t st, uint32_t w, uint32_t h, const glz_reproject_params& P, const float4* motion, const float4* prev_color,
                             const float4* prev_aov0, const float4* prev_aov1, float4* out, hipEvent_t* marks) {

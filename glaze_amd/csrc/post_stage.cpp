@@ -72,7 +72,7 @@ bool PostStage::first_hit_pass(const FirstHitRequest& req, Error& err) {
   if (req.motion) {
     const MotionStep& m = *req.motion;
     if (m.marks) (void)hipEventRecord(m.marks[0], st);
-    if (!hip_ok(launch_motion(st, a, fh_hit_.ptr, fh_inst_.ptr, m.prev_o2w, m.prev, m.out), "k_motion", err)) return false;
+    if (!hip_ok(launch_motion(st, a, fh_hit_.ptr, fh_inst_.ptr, m.prev_o2w, m.prev, m.out, m.prev_vertices, m.first_vertex, m.n_vertices), "k_motion", err)) return false;
     if (m.marks) (void)hipEventRecord(m.marks[1], st);
   }
   if (chain) {
@@ -171,12 +171,17 @@ const float4* PostStage::filtered(const float4* frame, bool filter, hipEvent_t* 
   return hip_ok(launched, filter ? "k_atrous" : "k_despeckle", err) ? dn_out_.ptr : nullptr;
 }
 
-// the checks of read_motion and reproject, the upload of the caller's matrices, then the first-hit pass with k_motion in it
-bool PostStage::motion_pass(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, DeviceBuffer<float4>& prev_o2w,
-                            DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks) {
+// the checks of read_motion and reproject, the upload of the caller's matrices and vertices, then the first-hit pass with k_motion in it
+bool PostStage::motion_pass(const glz_previous_state& prev, PrevBuffers& uploaded, DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks) {
+  const glz_camera* prev_camera = prev.camera;
+  const glz_transform* prev_transforms = prev.transforms;
+  const uint32_t n_prev = prev.n_transforms;
   if (!prev_camera) return bad_argument(err, "motion: the previous camera is null");
   if (prev_transforms && n_prev != r_.scene()->data.transforms.size())
     return bad_argument(err, "motion: the previous transforms must be as many as the scene's (instances index transforms)");
+  if (prev.vertices && prev.n_vertices == 0) return bad_argument(err, "motion: previous vertices given, but none of them (n_vertices is 0)");
+  if (prev.vertices && (uint64_t)prev.first_vertex + prev.n_vertices > r_.scene()->data.vertices.size())
+    return bad_argument(err, "motion: the range of the previous vertices reaches past the scene's vertex count");
   if (!hip_ok(hipSetDevice(r_.instance()->device), "hipSetDevice", err)) return false;
   MotionStep step;
   host::project_constants(*prev_camera, r_.width(), r_.height(), step.prev.world2camera, step.prev.camera2screen);
@@ -184,8 +189,18 @@ bool PostStage::motion_pass(const glz_camera* prev_camera, const glz_transform* 
   step.prev_o2w = nullptr;
   if (prev_transforms && n_prev > 0) {
     static_assert(sizeof(glz_transform) == 4 * sizeof(float4), "one previous matrix is four float4");
-    if (!hip_ok(prev_o2w.upload(reinterpret_cast<const float4*>(prev_transforms), 4 * (size_t)n_prev, r_.instance()->stream), "upload previous transforms", err)) return false;
-    step.prev_o2w = prev_o2w.ptr;
+    if (!hip_ok(uploaded.o2w.upload(reinterpret_cast<const float4*>(prev_transforms), 4 * (size_t)n_prev, r_.instance()->stream), "upload previous transforms", err)) return false;
+    step.prev_o2w = uploaded.o2w.ptr;
+  }
+  step.prev_vertices = nullptr;
+  step.first_vertex = step.n_vertices = 0;
+  if (prev.vertices) {   // as they are: the layout of the scene's own vertices, which the kernel reads for the indices outside the range
+    static_assert(sizeof(glz_vertex) == 2 * sizeof(float4), "one vertex is two float4, the position in the first");
+    if (!hip_ok(uploaded.vertices.upload(reinterpret_cast<const float4*>(prev.vertices), 2 * (size_t)prev.n_vertices, r_.instance()->stream), "upload previous vertices", err))
+      return false;
+    step.prev_vertices = uploaded.vertices.ptr;
+    step.first_vertex = prev.first_vertex;
+    step.n_vertices = prev.n_vertices;
   }
   if (!hip_ok(motion.alloc((size_t)r_.width() * r_.height()), "alloc motion plane", err)) return false;
   step.out = motion.ptr;
@@ -195,28 +210,31 @@ bool PostStage::motion_pass(const glz_camera* prev_camera, const glz_transform* 
   return first_hit_pass(pass, err);
 }
 
-bool PostStage::read_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* out, Error& err) {
-  DeviceBuffer<float4> prev_o2w, motion;
-  if (!motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err)) return false;
+bool PostStage::read_motion(const glz_previous_state& prev, float* out, Error& err) {
+  PrevBuffers uploaded;
+  DeviceBuffer<float4> motion;
+  if (!motion_pass(prev, uploaded, motion, err)) return false;
   return r_.frame_to_host(motion.ptr, out, "read motion", err);
 }
 
-bool PostStage::time_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* kernel_ms, Error& err) {
+bool PostStage::time_motion(const glz_previous_state& prev, float* kernel_ms, Error& err) {
   if (!hip_ok(hipSetDevice(r_.instance()->device), "hipSetDevice", err)) return false;
   Events<2> t;
-  DeviceBuffer<float4> prev_o2w, motion;
-  if (!t.create(err) || !motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err, t.ev)) return false;
+  PrevBuffers uploaded;
+  DeviceBuffer<float4> motion;
+  if (!t.create(err) || !motion_pass(prev, uploaded, motion, err, t.ev)) return false;
   if (!hip_ok(hipStreamSynchronize(r_.instance()->stream), "time_motion", err)) return false;
   (void)hipEventElapsedTime(kernel_ms, t.ev[0], t.ev[1]);
   return true;
 }
 
-bool PostStage::reproject(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, const float* prev_color, const float* prev_aov0,
-                          const float* prev_aov1, const glz_reproject_params* params, float* out, Error& err) {
+bool PostStage::reproject(const glz_previous_state& prev, const float* prev_color, const float* prev_aov0, const float* prev_aov1, const glz_reproject_params* params,
+                          float* out, Error& err) {
   const glz_reproject_params P = params ? *params : post::reproject_defaults();
   if (!post::reproject_params_valid(P)) return bad_argument(err, post::kReprojectParamsMessage);
-  DeviceBuffer<float4> prev_o2w, motion, color, plane0, plane1, result;
-  if (!motion_pass(prev_camera, prev_transforms, n_prev, prev_o2w, motion, err)) return false;
+  PrevBuffers uploaded;
+  DeviceBuffer<float4> motion, color, plane0, plane1, result;
+  if (!motion_pass(prev, uploaded, motion, err)) return false;
   const uint32_t w = r_.width(), h = r_.height();
   const size_t n = (size_t)w * h;
   hipStream_t st = r_.instance()->stream;

@@ -29,11 +29,12 @@ class PostStage {
   // kernels, 2 + iterations around the filter's; such a timed run never includes the rejection.
   const float4* filtered(const float4* frame, bool filter, hipEvent_t* marks, Error& err);
   // motion vectors and history reprojection (glz_reproject_params; reproject.h): the first-hit trace and k_motion against the caller's
-  // previous camera and transforms (null = the scene's own), then, for reproject, k_reproject on the three uploaded previous frames
-  bool read_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* out, Error& err);
-  bool time_motion(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, float* kernel_ms, Error& err);   // k_motion alone, device events
-  bool reproject(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, const float* prev_color, const float* prev_aov0,
-                 const float* prev_aov1, const glz_reproject_params* params, float* out, Error& err);
+  // previous state -- camera, transforms (null = the scene's own) and vertices (null = the meshes did not deform; else k_motion_deform on the
+  // uploaded array) -- then, for reproject, k_reproject on the three uploaded previous frames
+  bool read_motion(const glz_previous_state& prev, float* out, Error& err);
+  bool time_motion(const glz_previous_state& prev, float* kernel_ms, Error& err);   // k_motion / k_motion_deform alone, device events
+  bool reproject(const glz_previous_state& prev, const float* prev_color, const float* prev_aov0, const float* prev_aov1, const glz_reproject_params* params, float* out,
+                 Error& err);
   bool camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err);   // camera_ray() of every pixel, on the device
   // which surface the feature buffers describe (GLZ_GUIDE_*, glaze_abi.h holds the specification); accumulation goes on
   bool set_guide_mode(int mode, uint32_t max_bounces, Error& err);
@@ -46,6 +47,8 @@ class PostStage {
   struct MotionStep {
     post::ProjectConstants prev;
     const float4* prev_o2w;   // device, or null = the scene's own
+    const float4* prev_vertices;            // device, or null = the meshes did not deform: the previous contents of the scene's vertices
+    uint32_t first_vertex, n_vertices;      //   [first_vertex, first_vertex + n_vertices), two float4 each
     float4* out;              // device
     hipEvent_t* marks;        // null, or two events recorded around k_motion
   };
@@ -59,8 +62,11 @@ class PostStage {
   // In GLZ_GUIDE_THROUGH_SPECULAR the chain's kernels take the attribute kernel's place (launch_guide_chain).
   bool first_hit_pass(const FirstHitRequest& req, Error& err);
   void post_args(LaunchArgs& a) const;
-  bool motion_pass(const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev, DeviceBuffer<float4>& prev_o2w, DeviceBuffer<float4>& motion,
-                   Error& err, hipEvent_t* marks = nullptr);
+  // what a motion pass uploads of the caller's previous state: owned by the call and released with it
+  struct PrevBuffers {
+    DeviceBuffer<float4> o2w, vertices;
+  };
+  bool motion_pass(const glz_previous_state& prev, PrevBuffers& uploaded, DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks = nullptr);
   GuideLists guide_lists() const { return GuideLists{{guide_o_[0].ptr, guide_o_[1].ptr}, {guide_d_[0].ptr, guide_d_[1].ptr}, guide_count_.ptr}; }
 
   const Renderer& r_;

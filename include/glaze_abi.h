@@ -548,6 +548,14 @@ int glz_renderer_read_despeckled(glz_renderer*, float* rgba32f_out, uint8_t* rgb
  *     (fx, fy, z') = project_point(previous camera, P')
  *     plane = (fx - (float(px) + 0.5), fy - (float(py) + 0.5), z', the first hit's instance bits)
  *     a miss: (0, 0, +inf, 0xFFFFFFFF);   an invalid projection: (0, 0, +inf, instance bits)
+ *     With previous vertices (glz_previous_state::vertices, glz_renderer_read_motion_from): let (i0, i1, i2) be the hit triangle's three
+ *       entries of the index buffer, in index-buffer order -- the order of the shading record and of the barycentrics.
+ *       vk' = the position of vertices[ik - first_vertex] if first_vertex <= ik < first_vertex + n_vertices, else the current position of
+ *       vertex ik
+ *       P_obj' = (v0'*b0 + v1'*u) + v2'*v per component, the same expression in the same order as P_obj
+ *       P' = prev_o2w[transform id] applied to P_obj'
+ *       Only positions are read: normals and texture coordinates of the array are ignored.  The instance bits, the miss rule and the
+ *       invalid rule do not change.
  *   THE REPROJECTION RULE (glz_renderer_reproject, glz_host_reproject), per pixel p, from the motion plane m and three PREVIOUS frames:
  *     the colour c (any RGBA32F image), aov0 = (normal, depth) and aov1 = (albedo, instance bits), both from GLZ_GUIDE_FIRST_HIT:
  *     z' = m.z not finite: out = (0, 0, 0, 0).  Otherwise
@@ -574,6 +582,24 @@ int glz_renderer_read_motion(glz_renderer*, const glz_camera* prev_camera, const
 /* The first-hit trace, the motion plane, then the rule on the three uploaded frames. */
 int glz_renderer_reproject(glz_renderer*, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms,
                            const float* prev_color, const float* prev_aov0, const float* prev_aov1, const glz_reproject_params* params_or_null, float* out);
+/* The same two calls for a scene whose meshes deform (glz_renderer_update_vertices): the previous state with the previous VERTICES in it,
+ * which the caller keeps like the previous camera and transforms -- nothing is kept here between calls.  The two calls above are the case
+ * vertices == NULL, and with it these give their planes bit for bit.  The array is uploaded for the call and released with it; only its
+ * positions are read.  GLZ_E_ARG, before anything is launched and with nothing changed: a null renderer, state, camera or output; a
+ * non-NULL transforms whose count is not the scene's; non-NULL vertices with n_vertices == 0 or with a range that reaches past the
+ * scene's vertex count (with NULL vertices, first_vertex and n_vertices are ignored, as n_transforms is with NULL transforms); for
+ * glz_renderer_reproject_from the frame and parameter checks of glz_renderer_reproject. */
+typedef struct glz_previous_state {
+  const glz_camera*    camera;         /* required */
+  const glz_transform* transforms;     /* NULL = the instances did not move (the scene's own); else n_transforms = the scene's count */
+  uint32_t             n_transforms;
+  const glz_vertex*    vertices;       /* NULL = the meshes did not deform; else the PREVIOUS contents of the scene's vertices */
+  uint32_t             first_vertex;   /*   [first_vertex, first_vertex + n_vertices), exactly the range update_vertices takes */
+  uint32_t             n_vertices;
+} glz_previous_state;
+int glz_renderer_read_motion_from(glz_renderer*, const glz_previous_state*, float* out);
+int glz_renderer_reproject_from(glz_renderer*, const glz_previous_state*, const float* prev_color, const float* prev_aov0,
+                                const float* prev_aov1, const glz_reproject_params* params_or_null, float* out);
 
 /* Multi-GPU (one process per GPU): this renderer owns the 64x64-pixel tiles t with
  * t % world == rank; other pixels stay zero.  The exchange of the HDR accumulator itself is done
@@ -705,6 +731,8 @@ int glz_debug_reproject(glz_instance*, uint32_t w, uint32_t h, const float* moti
                         const glz_reproject_params* params_or_null, float* out, float* kernel_ms_out);
 /* glz_renderer_read_motion's pass without the read-back: the device-event time of k_motion alone, in milliseconds */
 int glz_debug_motion_timing(glz_renderer*, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms, float* kernel_ms_out);
+/* the same for glz_renderer_read_motion_from: k_motion_deform alone when the state has vertices */
+int glz_debug_motion_timing_from(glz_renderer*, const glz_previous_state*, float* kernel_ms_out);
 int glz_debug_tonemap(glz_instance*, const float* rgba32f, uint64_t n_pixels, uint8_t* rgba8_out);
 /* The kernels' texture sampler on n coordinates uv2[2i], uv2[2i+1] of a scene texture, RGBA out: level 0 (texture2d) when
  * footprint4 is NULL, else the level of detail of footprint4[4i..4i+3] = (lod_base, du, dv, taps in 1..16) (texture2d_lod, after

@@ -6,7 +6,8 @@ renderer's own device-event statistics.  Then the guide modes: the first-hit pas
 chain of through_specular at caps 1 .. 8 on the atrium, which has no specular material -- every list is empty, so the slope over the cap
 is the cost of two empty launches -- and on tests/golden/mattest.glaze at 1024 x 1024, where half the frame is Glass: the time every
 bounce adds next to the number of rays alive in it.  Last, k_motion and k_reproject alone (glz_debug_motion_timing, glz_debug_reproject's
-device events) for a camera that moved about 0.6 m and turned, next to their byte floors.  Run from the repository root on the GPU; writes nothing but its output."""
+device events) for a camera that moved about 0.6 m and turned, next to their byte floors, and k_motion_deform (the same hook with previous
+vertices) next to k_motion and to its own floor.  Run from the repository root on the GPU; writes nothing but its output."""
 import os
 import statistics
 import sys
@@ -134,6 +135,23 @@ n_tris = r.scene.info().n_as_triangles
 lo, hi = W * H * 36 / 6.3e12 * 1e6, (W * H * 36 + n_tris * 128) / 6.3e12 * 1e6
 print("k_motion: %.1f us (%.1f %% of the pixels hit) = %.1f x the %.1f us floor of its per-pixel streams (36 B), %.1f x the %.1f us with every one of the "
       "scene's %d shading records read once" % (k_motion, 100 * hits, k_motion / lo, lo, k_motion / hi, hi, n_tris))
+# the deforming variant (k_motion_deform): every vertex of the scene handed over as its previous one, a little displaced.  It reads no shading
+# record; what it gathers instead is shared by the pixels of a triangle as the record is: the leaf's primitive word (4 B of a 48-byte BvhTri)
+# and three indices (12 B) per triangle, and the caller's vertices as they were uploaded, 32 B each for the 16 B of the position
+info = r.scene.info()
+before = desc.vertices.copy()
+before["vv"] += 0.01
+for _ in range(8):
+    r.debug_motion_timing(prev_cam, prev_vertices=before)
+k_deform = statistics.median(r.debug_motion_timing(prev_cam, prev_vertices=before) for _ in range(REPS)) * 1e3
+hi_deform = (W * H * 36 + n_tris * 16 + info.n_vertices * 32) / 6.3e12 * 1e6
+print("k_motion_deform: %.1f us = %.2f x k_motion, %.1f x the %.1f us floor of the per-pixel streams (36 B), %.1f x the %.1f us with the primitive word and the indices of "
+      "every triangle and every one of the %d uploaded 32-byte vertices read once" % (k_deform, k_deform / k_motion, k_deform / lo, lo, k_deform / hi_deform, hi_deform,
+                                                                                     info.n_vertices))
+t = time.time()
+for _ in range(16):
+    r.read_motion(prev_cam, prev_vertices=before)
+print("read_motion() with previous vertices end to end, %d vertices uploaded and the frame read back: %.2f ms" % (info.n_vertices, (time.time() - t) / 16 * 1e3))
 r.update_camera(prev_cam)
 prev0, prev1 = r.read_aov(0), r.read_aov(1)
 r.update_camera(desc.camera)

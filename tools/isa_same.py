@@ -7,7 +7,8 @@ holds it (code that moved to another file) -- and the two disassemblies are comp
 followed, for a kernel, by the code object's figures in both builds (as tools/isa_meta.sh prints them): VGPRs, VGPR spills, scratch
 bytes, LDS bytes.  What does not count as a difference is what moves with the position of the code and not with the code: the address /
 encoding comments, the literals of the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64 (the pc-relative distance to a function that is
-called, not inlined), and the padding behind a symbol's last s_endpgm.  Exit status 1 when a symbol differs or is missing.
+called, not inlined), and the padding behind a symbol's last s_endpgm.  Exit status 1 when a symbol differs or is missing.  A symbol
+that only NEW has is listed as `new` with its figures and does not count.
 (The .o is a fat binary: llvm-objdump --offloading extracts the device ELF first, as in tools/isa_dump.sh.)
 """
 import glob
@@ -106,6 +107,11 @@ def main():
                     text += '  FIGURES DIFFER'
                     bad += 1
             print(text)
+    for obj, syms in new.items():   # what NEW has and OLD has not, with a kernel's figures: reported, not counted
+        fresh = [s for s in syms if not any(s in o for o in old.values())]
+        for sym, name in zip(fresh, run(filt, *fresh).splitlines() if filt and fresh else fresh):
+            fig = syms[sym][1]
+            print('%-8s%s  [- -> %s]' % ('new', re.sub(r'\(.*', '', name), obj) + ('' if fig is None else '  ' + '  '.join('%s -/%s' % (label, fig.get(key, '-')) for label, key in FIGURES)))
     print('%d symbols of %s compared with %s: %s' % (len(names), sys.argv[1], sys.argv[2], 'all same' if not bad else '%d not the same' % bad))
     return 1 if bad else 0
 
