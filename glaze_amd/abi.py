@@ -294,6 +294,7 @@ PROTOTYPES = {
     "glz_renderer_set_guide_mode": (C.c_int, [_P, C.c_int, C.c_uint32]),
     "glz_renderer_guide_mode": (C.c_int, [_P, _P]),
     "glz_debug_guide_chain": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
+    "glz_host_traversal_offsets_fit": (C.c_int, [C.c_uint64] * 6),
 }
 
 _LIB = None

@@ -635,6 +635,10 @@ int64_t glz_host_mip_level(const glz_texture* t, uint32_t level, uint8_t* out, i
   return (int64_t)m.pixels.size();
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_host_traversal_offsets_fit(uint64_t n_nodes, uint64_t n_nodes8, uint64_t n_leaves, uint64_t n_instances, uint64_t grid_lanes, uint64_t overflow_depth) {
+  const char* what = traversal_offsets_exceeded(TraversalSizes{n_nodes, n_nodes8, n_leaves, n_instances, grid_lanes, overflow_depth});
+  return what ? fail(GLZ_E_INVALID_DATA, what) : GLZ_OK;
+}
 int glz_host_srgb8_thresholds(float thresholds_out[256]) {
   if (!thresholds_out) return fail(GLZ_E_ARG, "output is null");
   host::srgb8_thresholds(thresholds_out);

@@ -36,6 +36,29 @@ static std::vector<uint32_t> instance_transforms(const std::vector<RTInstance>& 
   return out;
 }
 
+const char* traversal_offsets_exceeded(const TraversalSizes& s) {
+  constexpr uint64_t kLimit = 1ull << 32;   // first byte offset that 32 bits do not hold
+  auto reaches = [](uint64_t n, uint64_t record) { return n >= (kLimit + record - 1) / record; };   // n * record >= 2^32, without the product
+  if (reaches(s.n_nodes, sizeof(BvhNode4))) return "the hierarchy's 4-wide nodes take 2^32 bytes or more (the tracers address them with 32-bit byte offsets)";
+  if (reaches(s.n_nodes8, sizeof(BvhNode8))) return "the hierarchy's 8-wide nodes take 2^32 bytes or more (the tracers address them with 32-bit byte offsets)";
+  if (reaches(s.n_leaves, sizeof(BvhQuad))) return "the hierarchy's leaf records take 2^32 bytes or more (the tracers address them with 32-bit byte offsets)";
+  if (reaches(s.n_instances, sizeof(TlasInstance))) return "the instance records take 2^32 bytes or more (the tracers address them with 32-bit byte offsets)";
+  constexpr uint64_t kWords = kLimit / sizeof(uint32_t);   // (each factor below it first: the product cannot wrap)
+  if (s.grid_lanes >= kWords || s.overflow_depth >= kWords || s.grid_lanes * s.overflow_depth >= kWords)
+    return "the traversal stacks' spill area takes 2^32 bytes or more (the hierarchy is too deep for 32-bit byte offsets)";
+  return nullptr;
+}
+
+// the structure as built against traversal_offsets_exceeded, with the largest persistent grid the current device is given
+bool Accel::offsets_fit(Error& err) const {
+  int dev = 0, cus = 256;   // (launch_geometry.h resident_blocks: the same query, the same default)
+  hipDeviceProp_t prop;
+  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+  const TraversalSizes sizes{d_nodes_.count, d_nodes8_.count, d_quads_.count, d_tlas_instances_.count, (uint64_t)cus * kPersistentBlocksPerCuMax * kTraceBlock, stack_overflow_depth};
+  const char* what = traversal_offsets_exceeded(sizes);
+  return what ? err.fail(GLZ_E_INVALID_DATA, what) : true;
+}
+
 void Accel::describe(DeviceScene& dev) const {
   dev.bvh_nodes = d_nodes_.ptr;
   dev.bvh_top = d_top_.ptr;
@@ -238,7 +261,7 @@ bool Accel::assemble_top_level(const Sources& s, const float4* d_lo, const float
   timer.stop(st);
   if (!hip_ok(hipStreamSynchronize(st), "top level", err)) return false;
   finish_two_level(s, top, timer.ms());
-  return true;
+  return offsets_fit(err);
 }
 
 // The TlasInstance records in the top level's leaf order (`order`: the top level's leaves, world_id = instance), and the transform
@@ -369,6 +392,7 @@ bool Accel::build_bvh(const Sources& s, Error& err) {
   const uint32_t stack_bound = std::max(3u * out.depth, 7u * out.depth8) + 1u;   // (an 8-wide visit pushes up to seven)
   stack_overflow_depth = stack_bound > (uint32_t)kTraversalLdsStack ? stack_bound - kTraversalLdsStack + 1 : 1;
   if (n_nodes >= (uint32_t)kBvhTopFlag) return err.fail(GLZ_E_UNSUPPORTED, "more than 2^30 BVH nodes");
+  if (!offsets_fit(err)) return false;
   // top levels of the tree for the tracers' LDS staging
   if (!d_top_.ptr && !hip_ok(d_top_.alloc(kBvhTopNodes), "alloc BVH top table", err)) return false;
   if (!hip_ok(launch_top_table(st, d_nodes_.ptr, n_nodes, d_top_.ptr), "k_top_table", err)) return false;

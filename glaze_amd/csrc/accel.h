@@ -122,6 +122,7 @@ class Accel {
   RefitTarget refit_target(const Sources& s, size_t plan) const;
   bool make_plan(hipStream_t st, const RefitTarget& t, uint32_t n_leaves, RefitPlan& p, Error& err);
   bool refit(hipStream_t st, const Sources& s, const RefitTarget& t, RefitPlan& p, bool write, RefitResult& out, Error& err);
+  bool offsets_fit(Error& err) const;   // kernels.h traversal_offsets_exceeded for what has been built: GLZ_E_INVALID_DATA
   bool build_bvh(const Sources& s, Error& err);
   bool build_two_level(const Sources& s, Error& err);
   bool assemble_top_level(const Sources& s, const float4* d_lo, const float4* d_hi, std::vector<float4>& h_lo, std::vector<float4>& h_hi,

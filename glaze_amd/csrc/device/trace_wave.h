@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "device/intersect.h"
+#include "device/sort4.h"
 #include "device/tuning.h"
 #include "device/types.h"
 #include "kernels.h"
@@ -30,20 +31,33 @@ constexpr int kStolen = 0x7FFFFFFE;
 // (tools/gpu_sections.py, round 4: ~1 000 of ~2 400 clocks on an otherwise idle chip).  The staged top of the tree had the same
 // problem in round 2 (LdsNodePtr).
 typedef __attribute__((address_space(3))) int* LdsIntPtr;
+// Record `index` of a table in memory, addressed as the table's (wave-uniform) base plus a 32-bit BYTE offset per lane: the load
+// is global_load_dwordx4 v, vOffset, s[base:base+1] behind one v_lshlrev_b32, where `table + index` with a signed index makes the address
+// in 64 bits per lane (v_mov 0, v_lshlrev_b64, v_lshl_add_u64).  No table of the hierarchy reaches 2^32 bytes: the host refuses such a
+// scene (kernels.h traversal_offsets_exceeded) -- the links alone, 30 bits of node or leaf number, would allow sixteen times that.
+template <class T>
+__device__ __forceinline__ const T* record_at(const T* table, uint32_t index) {
+  return reinterpret_cast<const T*>(reinterpret_cast<const char*>(table) + index * (uint32_t)sizeof(T));
+}
+// this lane's slot of the grid's spill area (a lane traverses one ray or subtree at a time)
+__device__ __forceinline__ uint32_t lane_slot() { return (blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 64u + (threadIdx.x & 63u); }
 template <int kLevels>
 struct StackT {
   LdsIntPtr lds;        // &s_stack[threadIdx.x]
-  uint32_t* spill;      // overflow words of this lane
+  char* spill;          // the grid's overflow area (wave-uniform) ...
+  uint32_t spill_off;   // ... and the byte offset of this lane's words in it (the whole area is shorter than 2^32 bytes: traversal_offsets_exceeded)
   int sp;
-  __device__ __forceinline__ StackT(int* lds_column, uint32_t* spill_words, int sp0) : lds((LdsIntPtr)lds_column), spill(spill_words), sp(sp0) {}
+  __device__ __forceinline__ StackT(int* lds_column, uint32_t* spill_area, uint32_t spill_depth, int sp0)
+      : lds((LdsIntPtr)lds_column), spill(reinterpret_cast<char*>(spill_area)), spill_off(lane_slot() * spill_depth * 4u), sp(sp0) {}
+  __device__ __forceinline__ uint32_t* spilt(int level) const { return reinterpret_cast<uint32_t*>(spill + (spill_off + ((uint32_t)(level - kLevels) << 2))); }
   __device__ __forceinline__ void push(int v) {
-    if (sp < kLevels) lds[sp * kBlock] = v; else spill[sp - kLevels] = (uint32_t)v;
+    if (sp < kLevels) lds[sp * kBlock] = v; else *spilt(sp) = (uint32_t)v;
     ++sp;
   }
   __device__ __forceinline__ int pop() {
     --sp;
     int v;
-    if (__builtin_expect(sp < kLevels, 1)) v = lds[sp * kBlock]; else v = (int)spill[sp - kLevels];   // two loads of two address spaces: not to be merged
+    if (__builtin_expect(sp < kLevels, 1)) v = lds[sp * kBlock]; else v = (int)*spilt(sp);   // two loads of two address spaces: not to be merged
     return v;
   }
   // Hand-overs take the OLDEST live entry of a stack (the lowest level, aux_sb) and move that mark up by one, so the stolen entries are
@@ -131,12 +145,6 @@ __device__ __forceinline__ void rotate_priority(uint32_t turn) {
 // the link of the child a sort key names, out of the wave's link scratch (`base` = LDS byte address of this lane's word of child 0, bits 8..9 zero)
 __device__ __forceinline__ int sorted_link(uint32_t base, uint32_t key) {
   return *(LdsIntPtr)(uintptr_t)((key & kKeyChildMask) | base);
-}
-template <bool DESCENDING = false>   // (DESCENDING: a pass of any-hit rays, box_key<kKeysFarFirst>)
-__device__ __forceinline__ void sort2(uint32_t& a, uint32_t& b) {
-  const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-  a = DESCENDING ? hi : lo;
-  b = DESCENDING ? lo : hi;
 }
 
 // The staged nodes are read through a pointer that keeps its LDS address space: with a generic pointer the compiler
@@ -254,19 +262,19 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
   float tmin = 0.0f, tmax = 0.0f;
   HitRecord best{0.0f, 0.0f, 0.0f, kNone};
   uint32_t best_id = kNone;
-  // the spill area is indexed by the physical lane slot of the grid (a lane traverses one ray or subtree at a time)
-  StackT<kLevels> st{lds_col, spill + ((size_t)(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 64u + (uint32_t)lane) * spill_depth, 0};
+  // the spill area is indexed by the physical lane slot of the grid (lane_slot)
+  StackT<kLevels> st{lds_col, spill, spill_depth, 0};
   // PREFETCH: the node `pf_cur` as loaded (or on its way)
   u32x4 pf0 = {0u, 0u, 0u, 0u}, pf1 = pf0, pf2 = pf0, pf3 = pf0, pf4 = pf0, pf5 = pf0, pf6 = pf0, pf7 = pf0;
   int pf_cur = -1;
   auto prefetch_node = [&]() {
     if (PREFETCH && WIDE8 && cur >= 0 && cur < kStolen) {
-      const u32x4* np = reinterpret_cast<const u32x4*>(nodes8 + cur);
+      const u32x4* np = reinterpret_cast<const u32x4*>(record_at(nodes8, (uint32_t)cur));
       pf0 = np[0]; pf1 = np[1]; pf2 = np[2]; pf3 = np[3]; pf4 = np[4]; pf5 = np[5]; pf6 = np[6]; pf7 = np[7];
       pf_cur = cur;
     } else
     if (PREFETCH && !WIDE8 && cur >= 0 && !(cur & kBvhTopFlag)) {   // a node of the table in memory (staged nodes, kRayDone and kStolen carry bit 30)
-      const u32x4* np = reinterpret_cast<const u32x4*>(nodes + cur);
+      const u32x4* np = reinterpret_cast<const u32x4*>(record_at(nodes, (uint32_t)cur));
       pf0 = np[0]; pf1 = np[1]; pf2 = np[2]; pf3 = np[3];
       pf_cur = cur;
     }
@@ -439,7 +447,7 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
           if (pf_cur != cur) prefetch_node();
           w0 = pf0; w1 = pf1; w2 = pf2; w3 = pf3; w4 = pf4; w5 = pf5; w6 = pf6; w7 = pf7;
         } else {
-          const u32x4* np = reinterpret_cast<const u32x4*>(nodes8 + cur);
+          const u32x4* np = reinterpret_cast<const u32x4*>(record_at(nodes8, (uint32_t)cur));
           w0 = np[0]; w1 = np[1]; w2 = np[2]; w3 = np[3]; w4 = np[4]; w5 = np[5]; w6 = np[6]; w7 = np[7];
         }
         if (COUNT) tally.nodes += 1;
@@ -491,7 +499,7 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
           if (pf_cur != cur) prefetch_node();   // (the ray has just started, or its stack was popped by someone who could not know)
           w0 = pf0; w1 = pf1; w2 = pf2; w3 = pf3;
         } else {
-          const u32x4* np = reinterpret_cast<const u32x4*>(nodes + cur);
+          const u32x4* np = reinterpret_cast<const u32x4*>(record_at(nodes, (uint32_t)cur));
           w0 = np[0]; w1 = np[1]; w2 = np[2]; w3 = np[3];
           // (A fifth 16-byte load from the node's own line costs 2.4 % of the kernel, 0.580 -> 0.594 ms: a 48-byte node format --
           // 8-bit boxes relative to a per-node origin -- would buy about that and pay ~12 VALU instructions per visit for it.)
@@ -509,7 +517,10 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
         uint32_t k0 = box_key<false, ORDER>(w0.x, w0.y, w0.z, w3.x, 0u, sel, ig, cg, cg, tmin, bound, flip), k1 = box_key<false, ORDER>(w0.w, w1.x, w1.y, w3.y, kKeyChild, sel, ig, cg, cg, tmin, bound, flip);
         uint32_t k2 = box_key<false, ORDER>(w1.z, w1.w, w2.x, w3.z, 2u * kKeyChild, sel, ig, cg, cg, tmin, bound, flip), k3 = box_key<false, ORDER>(w2.y, w2.z, w2.w, w3.w, 3u * kKeyChild, sel, ig, cg, cg, tmin, bound, flip);
         constexpr bool DESC = ORDER == kKeysFarFirst;
-        sort2<DESC>(k0, k1); sort2<DESC>(k2, k3); sort2<DESC>(k0, k2); sort2<DESC>(k1, k3); sort2<DESC>(k1, k2);
+        // (seven instructions, device/sort4.h.  The five-exchange network this replaces cost ten; both leave the keys' VALUES in order, so they
+        // agree wherever the keys differ -- hit children always do, by their child bits -- and several miss markers, equal, end up together at
+        // the far end either way: nothing downstream tells one miss marker from another.)
+        sort4<DESC>(k0, k1, k2, k3);
         // The links go through LDS: picking one of four registers by a per-lane index costs 6 VALU instructions (the
         // kernel's bottleneck), an LDS read at a computed address 2 (k_trace 0.714 -> 0.691 ms).  The scratch is laid out
         // [child][lane] so that every access of a wave instruction has bank = lane % 32 (the [lane][child] layout with one
@@ -593,7 +604,7 @@ __device__ __forceinline__ void trace_wave(const DeviceScene& S, Source& src, Si
       // A leaf is one 64-byte record (types.h BvhQuad): one triangle or two that share an edge, tested together (ray_quad).  The
       // candidates are then taken in slot order, the order the 48-byte records were walked in (the alpha test's fetches are counted).
       const uint32_t leaf = (uint32_t)~cur;
-      const float4* qp = reinterpret_cast<const float4*>(S.bvh_quads + leaf);
+      const float4* qp = reinterpret_cast<const float4*>(record_at(S.bvh_quads, leaf));
       const float4 r0 = qp[0], r1 = qp[1], r2 = qp[2], r3 = qp[3];
       const uint32_t id0 = __float_as_uint(r0.w), qflags = __float_as_uint(r2.w), slot0 = __float_as_uint(r3.w);
       const bool pair = (qflags & kTriHasPartner) != 0u;

@@ -52,7 +52,7 @@ __device__ __forceinline__ void trace_wave_tl(const DeviceScene& S, Source& src,
   SlabSel sel{kSlabSelLo, kSlabSelLo, kSlabSelLo};
   float tmin = 0.0f, tmax = 0.0f;
   HitRecord best{0.0f, 0.0f, 0.0f, kNone, 0u, kNone};
-  Stack st{lds_col, spill + ((size_t)(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 64u + (uint32_t)lane) * spill_depth, 0};
+  Stack st{lds_col, spill, spill_depth, 0};
   // grid-space ray for grid g from a ray (oo, dd) given in that grid's space; boxes widened by `slack` (a length in that space)
   // plus `cells` cells on every side
   auto set_grid_ray = [&](const float* glo, const float* gcell, const float* ginv, vec3 oo, vec3 dd, float slack, float cells) {
@@ -146,12 +146,12 @@ __device__ __forceinline__ void trace_wave_tl(const DeviceScene& S, Source& src,
           LdsNodePtr np = top_lds + 4 * (cur & 0xFFFF);
           w0 = np[0]; w1 = np[1]; w2 = np[2]; w3 = np[3];
         } else {
-          const u32x4* np = reinterpret_cast<const u32x4*>(nodes + nbase + (uint32_t)cur);
+          const u32x4* np = reinterpret_cast<const u32x4*>(record_at(nodes, nbase + (uint32_t)cur));   // (base plus a 32-bit byte offset: trace_wave.h record_at)
           w0 = np[0]; w1 = np[1]; w2 = np[2]; w3 = np[3];
         }
         uint32_t k0 = box_key(w0.x, w0.y, w0.z, w3.x, 0u, sel, ig, cgn, cgf, tmin, best.t), k1 = box_key(w0.w, w1.x, w1.y, w3.y, kKeyChild, sel, ig, cgn, cgf, tmin, best.t);
         uint32_t k2 = box_key(w1.z, w1.w, w2.x, w3.z, 2u * kKeyChild, sel, ig, cgn, cgf, tmin, best.t), k3 = box_key(w2.y, w2.z, w2.w, w3.w, 3u * kKeyChild, sel, ig, cgn, cgf, tmin, best.t);
-        sort2(k0, k1); sort2(k2, k3); sort2(k0, k2); sort2(k1, k3); sort2(k1, k2);
+        sort4(k0, k1, k2, k3);   // (device/sort4.h; equal keys are miss markers, which nothing tells apart: see trace_wave)
         int* links = link_scratch + lane;
         links[0] = (int)w3.x; links[64] = (int)w3.y; links[128] = (int)w3.z; links[192] = (int)w3.w;
         const uint32_t link_base = (uint32_t)(uintptr_t)(LdsIntPtr)links;   // the wave's area is 1 KB aligned: bits 8..9 are the child's
@@ -179,7 +179,7 @@ __device__ __forceinline__ void trace_wave_tl(const DeviceScene& S, Source& src,
     if (cur < 0) {
       if (cur_inst == kNone) {
         cur_inst = (uint32_t)~cur;
-        const TlasInstance* ti = instances + cur_inst;
+        const TlasInstance* ti = record_at(instances, cur_inst);
         const float4* q = reinterpret_cast<const float4*>(ti->w2o);
         const float4 r0 = q[0], r1 = q[1], r2 = q[2];
         // object-space ray (a point and a vector through the 3 x 4 matrix): only the box tests see it
@@ -193,11 +193,11 @@ __device__ __forceinline__ void trace_wave_tl(const DeviceScene& S, Source& src,
         set_grid_ray(ti->grid.lo, ti->grid.cell, ti->grid.inv_cell, oo, dd, slack, 1.0f);
         cur = 0;   // the mesh's root
       } else {
-        const TlasInstance* ti = instances + cur_inst;
+        const TlasInstance* ti = record_at(instances, cur_inst);
         // The mesh's leaf record (types.h BvhQuad; its hierarchy was built over the mesh under the identity transform, so the
         // vertices are the object-space ones): one 64-byte line for one triangle or two.  The world triangles are exactly what
         // k_world_tris builds -- points through o2w -- four of them for a pair instead of six.
-        const float4* qp = reinterpret_cast<const float4*>(S.bvh_quads + ti->quad_base + (uint32_t)~cur);
+        const float4* qp = reinterpret_cast<const float4*>(record_at(S.bvh_quads, ti->quad_base + (uint32_t)~cur));
         const float4 r0 = qp[0], r1 = qp[1], r2 = qp[2], r3 = qp[3];
         const uint32_t id0 = __float_as_uint(r0.w), qflags = __float_as_uint(r2.w), slot0 = ti->tri_base + __float_as_uint(r3.w);
         const bool pair = (qflags & kTriHasPartner) != 0u;

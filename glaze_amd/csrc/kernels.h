@@ -95,6 +95,16 @@ hipError_t launch_refit_quantise(hipStream_t st, const RefitNodes& n, const BvhG
 // Traversal stack entries each lane keeps in LDS (a near-first 4-wide traversal holds at most three entries per
 // level of the tree; what does not fit spills to a per-lane HBM area).
 constexpr int kTraversalLdsStack = 17;   // 17 levels + the staged top of the tree = 25 920 bytes per block: six blocks per CU (LDS is granted in 1 280-byte granules: 18 levels + the table would take 22 granules and leave room for five)
+constexpr int kPersistentBlocksPerCuMax = 8;   // the most blocks per CU a persistent tracer's grid is given (launch_geometry.h resident_blocks)
+
+// The tracers fetch nodes, leaf records, instance records and spilt stack words at a wave-uniform base plus a 32-bit BYTE offset per
+// lane (device/trace_wave.h record_at, StackT), so each of these must be shorter than 2^32 bytes: 4-wide nodes and leaf records of 64
+// bytes, 8-wide nodes of 128, instance records of 192, and the spill area of the largest persistent grid, overflow_depth words a lane.
+// Null when all of them fit, else the message that says which does not.  (The largest scene built so far, 21 M triangles, is a tenth of it.)
+struct TraversalSizes {
+  uint64_t n_nodes, n_nodes8, n_leaves, n_instances, grid_lanes, overflow_depth;
+};
+const char* traversal_offsets_exceeded(const TraversalSizes& sizes);   // accel.cpp
 
 // ---- rendering ------------------------------------------------------------------------------------
 // Per-pixel wavefront state, indexed by the LOCAL pixel id `lid` (tile-major, one wave = one 8x8 block):

@@ -20,16 +20,16 @@ static inline hipError_t launch_per_item(hipStream_t st, Kernel kernel, uint32_t
 }
 
 // Blocks of `kernel` (kTraceBlock threads, `dyn_lds` bytes of dynamic LDS) that are resident at once on the current device: CUs x
-// blocks per CU from the occupancy query (`fallback` when it fails), at most 8 and at most `cap` per CU.
+// blocks per CU from the occupancy query (`fallback` when it fails), at most kPersistentBlocksPerCuMax and at most `cap` per CU.
 template <class Kernel>
-static inline uint32_t resident_blocks(Kernel kernel, size_t dyn_lds, int fallback, int cap = 8) {
+static inline uint32_t resident_blocks(Kernel kernel, size_t dyn_lds, int fallback, int cap = kPersistentBlocksPerCuMax) {
   int dev = 0, cus = 256, per_cu = 0;
   if (hipGetDevice(&dev) == hipSuccess) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
   }
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)kTraceBlock, dyn_lds) != hipSuccess || per_cu < 1) per_cu = fallback;
-  return (uint32_t)cus * (uint32_t)std::max(1, std::min({per_cu, 8, cap}));
+  return (uint32_t)cus * (uint32_t)std::max(1, std::min({per_cu, kPersistentBlocksPerCuMax, cap}));
 }
 
 // for every kernel built on trace_wave / trace_wave_tl (kernels_render.hip, kernels_post.hip, kernels_debug.hip)

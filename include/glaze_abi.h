@@ -244,7 +244,11 @@ void* glz_instance_stream(const glz_instance*);
  *   GLZ_BVH_LBVH     Karras 2012 on the GPU: fastest build (3 ms for 262 k triangles, 33 ms for 21 M)
  *   GLZ_BVH_PLOC     parallel locally-ordered clustering on the GPU (Meister & Bittner 2018): the LBVH's quality here
  *   GLZ_BVH_SAH_HOST the SAH builder's reference implementation on the host cores: the same tree node for node, 3-24 x
- *                    slower (tests compare the two) */
+ *                    slower (tests compare the two)
+ * Size limit, whichever builder: the kernels address the hierarchy with 32-bit byte offsets, so scene creation (and every later
+ * rebuild) fails with GLZ_E_INVALID_DATA when a table would reach 2^32 bytes -- 2^26 4-wide nodes or leaf records (64 bytes each), 2^25
+ * 8-wide nodes (128), 2^32 / 192 instance records, or a traversal-stack spill area (lanes of the largest persistent grid x words a
+ * lane spills, which grows with the hierarchy's depth) of 2^30 words.  A 21 M triangle scene is at a tenth of the nearest of these. */
 #define GLZ_BVH_LBVH 0
 #define GLZ_BVH_PLOC 1
 #define GLZ_BVH_SAH 2
@@ -798,6 +802,11 @@ int glz_host_chain_owner(uint32_t width, uint32_t height, uint32_t rank, uint32_
 /* the 8-bit sRGB quantiser of read_rgba8 / draw (the reference's R8G8B8A8_SRGB blit, raytracer.rs:576-584): c encodes to
  * #{k in 1..255 : c >= thresholds_out[k]}; thresholds_out[0] = 0 */
 int glz_host_srgb8_thresholds(float thresholds_out[256]);
+/* the size check of scene creation (glz_instance_set_bvh_builder: "Size limit") on counts given by the caller, nothing built or
+ * allocated: 4-wide nodes, 8-wide nodes, leaf records, instance records, lanes of the largest persistent grid, spilt stack words per
+ * lane.  GLZ_OK when every table stays below 2^32 bytes, else GLZ_E_INVALID_DATA with the message scene creation fails with. */
+int glz_host_traversal_offsets_fit(uint64_t n_nodes, uint64_t n_nodes8, uint64_t n_leaves, uint64_t n_instances, uint64_t grid_lanes,
+                                   uint64_t overflow_depth);
 /* one level of the mip chain the library generates for a texture that brings only level 0 (mipchain.h: LINEAR-blit rule); returns the
  * byte count of that level (0 past the last), writes up to cap bytes */
 int64_t glz_host_mip_level(const glz_texture* texture, uint32_t level, uint8_t* out, int64_t cap, uint32_t* width, uint32_t* height);
