@@ -114,8 +114,12 @@ struct ClosestSink {
 // w += 1.0f sticks at 2^24 too); k_finalize (kernels_render.hip) makes result and the count from it whenever somebody looks.
 // accumulate_retired: a shadow ray's end (k_trace, k_path).  An occluded ray has nothing to add: four bytes say that the pixel updated, the
 // accumulator is not read.  `cum` = cumulative[lid] as read by the caller (only its xyz are used, and only by an unoccluded ray).
-// accumulate_shaded: the shading code's update.  What it adds is finite but for a rare sample, so one path for both (the sum is re-stored
-// unchanged): a branch here is a branch in shade_pixel.
+// accumulate_shaded: the shading code's update.  `add` false -- a hit without a light sample, whose contribution is exactly (+0, +0, +0),
+// or a non-finite sample, which adds nothing -- marks the pixel like an occluded ray does: four bytes, the accumulator is not read.
+// That leaves the bits the read-modify-write left, sum + (+0.0) == sum, unless a component of the sum is -0.0.  None ever is:
+// the sums start at +0.0 (Renderer::reset_buffers fills the array with zero bytes for every new frame), a round-to-nearest sum is -0.0 only when
+// both operands are, so by induction over the additions here and in accumulate_retired no sum becomes -0.0 whatever is added;
+// k_finalize writes .w only, and DeviceGroup's gather / scatter paths (k_export, k_pack_tiles) read the array and never write it.
 __device__ __forceinline__ float update_mark(uint32_t ordinal) { return -(float)(ordinal < (1u << 24) ? ordinal : (1u << 24)); }
 __device__ __forceinline__ void accumulate_retired(const LaunchArgs& A, uint32_t lid, vec3 c, bool add, float mark, float4 cum) {
   if (add) A.st.cumulative[lid] = make_float4(cum.x + c.x, cum.y + c.y, cum.z + c.z, mark);
@@ -123,8 +127,12 @@ __device__ __forceinline__ void accumulate_retired(const LaunchArgs& A, uint32_t
 }
 __device__ __forceinline__ void accumulate_shaded(const LaunchArgs& A, uint32_t lid, vec3 c, bool add, bool update, float mark) {
   if (!update) return;
-  const float4 cum = A.st.cumulative[lid];
-  A.st.cumulative[lid] = make_float4(add ? cum.x + c.x : cum.x, add ? cum.y + c.y : cum.y, add ? cum.z + c.z : cum.z, mark);
+  if (add) {
+    const float4 cum = A.st.cumulative[lid];
+    A.st.cumulative[lid] = make_float4(cum.x + c.x, cum.y + c.y, cum.z + c.z, mark);
+  } else {
+    A.st.cumulative[lid].w = mark;
+  }
 }
 
 // Shadow-ray queue: 8 sub-queues ("shards"), shard = blockIdx % 8.  Blocks b and b+8 are observed to land on

@@ -36,6 +36,7 @@ struct SharedQueue {   // k_shade: the rank's sharded queue in HBM, drained by t
 #endif
 struct DirectState {
   const LaunchArgs& A;
+  static constexpr bool kDeferSkyTexel = false;   // (sample_light: k_path has no registers for the fetch code a second time)
   __device__ __forceinline__ void stamp(int) {}
   __device__ __forceinline__ void ray_o(uint32_t lid, float4 v) { A.st.ray_o[lid] = v; }
   __device__ __forceinline__ void ray_d(uint32_t lid, float4 v) { A.st.ray_d[lid] = v; }
@@ -54,6 +55,7 @@ struct StagedState {
 #else
   __device__ __forceinline__ void stamp(int) {}
 #endif
+  static constexpr bool kDeferSkyTexel = true;
   float4 ro, rd, im[4];
   uint32_t mask = 0;   // 1: ro, 2: rd, 4: im
   __device__ __forceinline__ void ray_o(uint32_t, float4 v) { ro = v; mask |= 1u; }
@@ -190,7 +192,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
     xi.x = rand01(rng); xi.y = rand01(rng); xi.z = rand01(rng);
     LightSample ls;
     ls.pdf = 0.0f;
-    sample_light(S, li, point, xi, F.scene_radius, ls);
+    sample_light<State::kDeferSkyTexel>(S, li, point, xi, F.scene_radius, ls);
     GLZ_SHADE_STAMP(2);   // light sample
     vec3 c = mk3(0.0f, 0.0f, 0.0f);
     uint32_t flags = kFlagUpdate;
@@ -204,7 +206,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
         // weight_light = (1 or 0) * |cos| / pdf; radiance = value*emission*weight*lights_no*importance
         const float w_vis = 1.0f * (fabsf(dot3(ls.wiW, ns)) / ls.pdf);
         const float nl = (float)F.lights_no;
-        const Spec emission = light_emission(ls);
+        const Spec emission = light_emission<State::kDeferSkyTexel>(S, ls);
         const Spec importance = load_importance();
         imp_lum = spec_luminance(importance);
         have_lum = true;
@@ -235,7 +237,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
       A.st.sh_d[slot] = make_float4(sh_dir.x, sh_dir.y, sh_dir.z, __uint_as_float(lid));
       A.st.contrib[slot] = make_float4(c.x, c.y, c.z, __uint_as_float(flags));
     } else {
-      out.accumulate(lid, c, true, true, F.update_mark);
+      out.accumulate(lid, c, false, true, F.update_mark);   // c is (+0, +0, +0) here: the pixel is marked, its sum neither read nor written (accumulate_shaded)
     }
     spec_flag = 0.0f;
   } else {

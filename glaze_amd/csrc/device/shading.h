@@ -647,11 +647,13 @@ struct LightSample {
   vec3 wiW;
   float pdf;
   float distance;
-  uint32_t kind;    // RTLight::shader of the light
+  uint32_t kind;    // RTLight::shader of the light; kLightSampleEmpty: a sky sample without a direction (pdf 0), which has no texel either
   const RTLight* light;
   float k;          // omni, area: squared distance / intensity
-  vec3 rgb;         // area: the emitter's diffuse_mul; sky: texel * intensity
+  vec3 rgb;         // area: the emitter's diffuse_mul; sky, counting pass only: texel * intensity
+  vec2 uv;          // sky: where light_emission fetches the texel -- about half of the sky samples end with a BSDF pdf of 0 and never ask for it
 };
+constexpr uint32_t kLightSampleEmpty = 0xFFFFFFFFu;
 
 GLZ_D float sq_dist(vec3 a, vec3 b) {
   return ((a.x - b.x) * (a.x - b.x) + (a.y - b.y) * (a.y - b.y)) + (a.z - b.z) * (a.z - b.z);
@@ -680,6 +682,9 @@ GLZ_D float sample_cdf(float xi, int size, Fetch fetch, uint32_t& offset_out) {
   return ((float)off + du) / (float)size;
 }
 
+// DEFER_SKY_TEXEL: the sky map's texel is fetched by light_emission (same template argument), for the samples that are used, instead of
+// here.  k_path passes false: its launch loop sits at 128 registers and the fetch code a second time cost it three spilled ones.
+template <bool DEFER_SKY_TEXEL = true>
 GLZ_D void sample_light(const DeviceScene& S, uint32_t light_index, vec3 p, vec3 xi, float scene_radius, LightSample& out) {
   const RTLight* L = &S.lights[light_index];
   const uint32_t kind = L->shader;
@@ -690,6 +695,7 @@ GLZ_D void sample_light(const DeviceScene& S, uint32_t light_index, vec3 p, vec3
   out.light = L;
   out.k = 1.0f;
   out.rgb = mk3(0.0f, 0.0f, 0.0f);
+  out.uv = vec2{0.0f, 0.0f};
   if (kind == kLightOmni) {   // light_omni_sample_visible.rcall:14-25
     vec3 lp = mk3(L->pos[0], L->pos[1], L->pos[2]);
     out.wiW = normalize3(lp - p);
@@ -727,15 +733,20 @@ GLZ_D void sample_light(const DeviceScene& S, uint32_t light_index, vec3 p, vec3
     return;
   }
   // Sky: light_sky_sample_visible.rcall:100-135
-  uint32_t row, col;
+  uint32_t row;
   const float* marg = S.sky_marginal;
   const float* cdf = S.sky_cdf;   // (k_shade: in LDS -- the search is ten dependent reads; the two values read once below come from memory)
   float v = sample_cdf(xi.y, (int)S.sky_header.marginal_cdf_count, [&](int i) { return cdf[i]; }, row);
   float v_pdf = marg[S.sky_header.marginal_cdf_count + row] / S.sky_header.marginal_integral;
   // The conditional lookups hand integer texel coordinates to a normalised REPEAT/NEAREST sampler: every
   // fetch lands on texel (0,0) of the image (Q3).
+  // sample_cdf over that constant, written out: the search ends at `size` when cdf00 <= xi and at 0 otherwise, cur == next == cdf00,
+  // so next - cur > 0 never holds and du stays xi - cdf00
   const float cdf00 = S.sky_cond_cdf[0];
-  float u = sample_cdf(xi.x, (int)S.sky_header.conditional_cdf_count, [&](int) { return cdf00; }, col);
+  const int cond_size = (int)S.sky_header.conditional_cdf_count;
+  int cond_off = (cond_size > 0 && cdf00 <= xi.x ? cond_size : 0) - 1;
+  cond_off = cond_off < 0 ? 0 : (cond_off > cond_size - 2 ? cond_size - 2 : cond_off);
+  float u = ((float)cond_off + (xi.x - cdf00)) / (float)cond_size;
   float u_pdf = S.sky_cond_values[0] / marg[S.sky_header.conditional_integral_offset + row];
   float pdf = u_pdf * v_pdf;
   float theta = v * kPi;
@@ -746,14 +757,19 @@ GLZ_D void sample_light(const DeviceScene& S, uint32_t light_index, vec3 p, vec3
     out.pdf = pdf / (2.0f * kPi * kPi * sint);
     out.wiW = normalize3(xform_dir(S.sky.obj2world, mk3(sint * cosp, sint * sinp, cost)));
     out.distance = 2.0f * scene_radius + 1.0f;
-    out.rgb = texture_rgb(S, S.sky.tex_id, vec2{u, v}) * S.sky.intensity;
+    out.uv = vec2{u, v};
+    // the counting pass fetches here, used or not: its fetch counts are those of the oracle's walk
+    if (!DEFER_SKY_TEXEL || S.tex_counter) out.rgb = texture_rgb(S, S.sky.tex_id, out.uv) * S.sky.intensity;
   } else {
     out.pdf = 0.0f;
+    out.kind = kLightSampleEmpty;
   }
 }
 
-// the spectrum a light sample carries (the `emission` the *_sample_visible callables return)
-GLZ_D Spec light_emission(const LightSample& ls) {
+// the spectrum a light sample carries (the `emission` the *_sample_visible callables return); a sky sample's texel is fetched here, for
+// the samples that are used (the operations sample_light ran on it, in their order)
+template <bool DEFER_SKY_TEXEL = true>
+GLZ_D Spec light_emission(const DeviceScene& S, const LightSample& ls) {
   Spec e;
   if (ls.kind == kLightOmni) {
     GLZ_BINS e.w[i] = ls.light->color.w[i] / ls.k;
@@ -762,7 +778,8 @@ GLZ_D Spec light_emission(const LightSample& ls) {
   } else if (ls.kind == kLightArea) {
     e = spec_div(from_surface_color(ls.rgb), ls.k);
   } else {
-    e = from_illuminant_color(ls.rgb);
+    // (an empty sample's rgb is the zero sample_light left)
+    e = from_illuminant_color(!DEFER_SKY_TEXEL || S.tex_counter || ls.kind == kLightSampleEmpty ? ls.rgb : texture_rgb(S, S.sky.tex_id, ls.uv) * S.sky.intensity);
   }
   return e;
 }

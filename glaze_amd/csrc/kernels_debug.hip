@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(kBlock) k_debug_light_sample(DeviceScene S, ui
   ls.pdf = 0.0f;
   ls.distance = 0.0f;
   sample_light(S, light, mk3(pos3[3 * t], pos3[3 * t + 1], pos3[3 * t + 2]), mk3(rand3[3 * t], rand3[3 * t + 1], rand3[3 * t + 2]), scene_radius, ls);
-  const Spec e = light_emission(ls);
+  const Spec e = light_emission(S, ls);
   wi3[3 * t] = ls.wiW.x; wi3[3 * t + 1] = ls.wiW.y; wi3[3 * t + 2] = ls.wiW.z;
   dist[t] = ls.distance;
   pdf[t] = ls.pdf;
