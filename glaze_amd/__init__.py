@@ -24,7 +24,7 @@ from .abi import GlazeError
 from .scene_desc import VERTEX_DTYPE, SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
 
 __all__ = ["parse", "converted_file", "ParsedScene", "RayTraceInstance", "RayTraceScene", "RayTraceRenderer", "Integrator",
-           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points",
+           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points", "host_skin",
            "host_project_constants"]
 
 
@@ -244,6 +244,30 @@ def host_reproject(motion, prev_color, prev_aov0, prev_aov1, **params):
     out = np.zeros_like(m)
     p = abi.ReprojectParams(**params)
     abi.check(abi.lib().glz_host_reproject(m.shape[1], m.shape[0], _ptr(m), _ptr(c), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out)))
+    return out
+
+
+def _skin_arrays(joints, weights):
+    j = np.ascontiguousarray(joints)
+    if j.ndim != 2 or j.shape[1] != 4 or j.dtype.kind not in "iu" or (j.size and (j.min() < 0 or j.max() > 0xFFFF)):
+        raise ValueError("joints must be an (n, 4) integer array of bone indices below 65536")
+    w = np.ascontiguousarray(weights, np.float32)
+    if w.shape != j.shape:
+        raise ValueError("weights must be (n, 4), one per joint")
+    return np.ascontiguousarray(j, np.uint16), w
+
+
+def host_skin(bind, joints, weights, bones):
+    """glz_host_skin: the skinning rule (include/glaze_abi.h holds the specification) on the host, no device, the reference of k_skin.
+    bind: n vertices in any form update_vertices takes; joints: (n, 4) integers; weights: (n, 4) float32; bones: (n_bones, 16) float32,
+    column-major.  Returns the posed vertices, (n, 8) float32."""
+    v = _vertex_array(bind)
+    j, w = _skin_arrays(joints, weights)
+    b = _transform_array(bones)
+    if j.shape[0] != v.shape[0]:
+        raise ValueError("joints and weights must have one row per vertex")
+    out = np.zeros_like(v)
+    abi.check(abi.lib().glz_host_skin(_ptr(v), _ptr(j), _ptr(w), v.shape[0], _ptr(b), b.shape[0], _ptr(out)))
     return out
 
 
@@ -701,6 +725,44 @@ class RayTraceRenderer:
         v = _vertex_array(vertices)
         abi.check(abi.lib().glz_renderer_update_vertices(self._h, _ptr(v), int(first), v.shape[0], self._GEOMETRY_MODES.get(mode, mode)))
 
+    def add_skin(self, first, joints, weights, n_bones):
+        """A skin over the scene's vertices [first, first + n): joints (n, 4) integers below n_bones, weights (n, 4) float32.  The bind pose
+        is what the scene's vertices hold there now.  Returns the skin's id; the skin is the scene's (every renderer sharing it sees it)."""
+        j, w = _skin_arrays(joints, weights)
+        skin = abi.Skin(int(first), j.shape[0], _ptr(j), _ptr(w), int(n_bones))
+        return abi.check(abi.lib().glz_renderer_add_skin(self._h, C.cast(C.byref(skin), C.c_void_p)))
+
+    def remove_skin(self, skin):
+        """Frees a skin; the vertices stay as they are."""
+        abi.check(abi.lib().glz_renderer_remove_skin(self._h, int(skin)))
+
+    @staticmethod
+    def _pose_array(poses):
+        """abi.Pose array of {skin id: (n_bones, 16) bones} and the arrays it points into"""
+        keep = [_transform_array(b) for b in poses.values()]
+        arr = (abi.Pose * max(1, len(poses)))(*[abi.Pose(int(k), _ptr(b), b.shape[0]) for k, b in zip(poses.keys(), keep)])
+        return arr, keep
+
+    def pose(self, poses, mode="refit"):
+        """Poses skins on the device: poses is {skin id: (n_bones, 16) float32 bone matrices, column-major, joint_now x inverse_bind in the
+        mesh's object space}.  Every named skin is written from its bind pose and the structure follows once, as update_vertices does in
+        `mode`; accumulation restarts."""
+        arr, keep = self._pose_array(poses)
+        abi.check(abi.lib().glz_renderer_pose_skins(self._h, C.cast(arr, C.c_void_p), len(poses), self._GEOMETRY_MODES.get(mode, mode)))
+
+    def debug_skin_timing(self, skin, bones, reps=20):
+        """k_skin alone on one skin, into a scratch buffer (the scene is untouched): milliseconds per launch, device events around reps launches"""
+        arr, keep = self._pose_array({skin: bones})
+        ms = C.c_float(0.0)
+        abi.check(abi.lib().glz_debug_skin_timing(self._h, C.cast(arr, C.c_void_p), int(reps), C.cast(C.byref(ms), C.c_void_p)))
+        return ms.value
+
+    def read_vertices(self, first, n):
+        """The scene's current vertices [first, first + n) as the device holds them: (n, 8) float32"""
+        out = np.zeros((int(n), 8), np.float32)
+        abi.check(abi.lib().glz_renderer_read_vertices(self._h, int(first), int(n), _ptr(out)))
+        return out
+
     def geometry_update_info(self):
         """glz_geometry_update_info of the scene's last update_vertices: mode, meshes_touched, update_ms and the box-area figures whose
         ratio box_area / box_area_built says how far a refitted tree has degraded.  Raises GlazeError before any update."""
@@ -846,13 +908,19 @@ class RayTraceRenderer:
                                   None if v is None else _ptr(v), int(first_vertex), 0 if v is None else v.shape[0])
         return state, (prev_camera, t, v)
 
-    def read_motion(self, prev_camera, prev_transforms=None, prev_vertices=None, first_vertex=0):
+    def read_motion(self, prev_camera, prev_transforms=None, prev_vertices=None, first_vertex=0, prev_poses=None):
         """The motion plane (include/glaze_abi.h holds the specification): H x W x 4 float32, per pixel (where the first hit of the centre
         ray was on screen under prev_camera, prev_transforms and prev_vertices, minus the pixel's own centre; its distance from the previous
         eye; the hit's instance bits).  prev_transforms: (n, 16) float32 as update_transforms takes them, None = the instances did not move.
         prev_vertices: what the scene's vertices [first_vertex, first_vertex + n) held in the previous frame, in any form update_vertices
-        takes, None = the meshes did not deform.  Accumulation goes on."""
+        takes, None = the meshes did not deform.  prev_poses: {skin id: bones} as pose() takes them, the PREVIOUS frame's -- the previous
+        vertices are then made on the device (prev_vertices must be None).  Accumulation goes on."""
         out = np.zeros((self.height, self.width, 4), np.float32)
+        if prev_poses is not None:
+            state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
+            arr, keep_bones = self._pose_array(prev_poses)
+            abi.check(abi.lib().glz_renderer_read_motion_posed(self._h, C.cast(C.byref(state), C.c_void_p), C.cast(arr, C.c_void_p), len(prev_poses), _ptr(out)))
+            return out
         if prev_vertices is not None:
             state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
             abi.check(abi.lib().glz_renderer_read_motion_from(self._h, C.cast(C.byref(state), C.c_void_p), _ptr(out)))
@@ -875,10 +943,10 @@ class RayTraceRenderer:
                                                     C.cast(C.byref(ms), C.c_void_p)))
         return ms.value
 
-    def reproject(self, prev_camera, prev_color, prev_aov0, prev_aov1, prev_transforms=None, prev_vertices=None, first_vertex=0, **params):
+    def reproject(self, prev_camera, prev_color, prev_aov0, prev_aov1, prev_transforms=None, prev_vertices=None, first_vertex=0, prev_poses=None, **params):
         """The previous frame's colour carried to this frame's pixels with disocclusion rejection: H x W x 4 float32 (rgb, confidence
         0 .. 1).  prev_color: any H x W x 4 image of the previous frame; prev_aov0 / prev_aov1: read_aov(0) / read_aov(1) of the previous
-        state in first-hit mode; prev_transforms, prev_vertices, first_vertex: as read_motion takes them; params: glz_reproject_params
+        state in first-hit mode; prev_transforms, prev_vertices, first_vertex, prev_poses: as read_motion takes them; params: glz_reproject_params
         (depth_tolerance).  Accumulation goes on."""
         shape = (self.height, self.width, 4)
         c, a0, a1 = (np.ascontiguousarray(f, np.float32) for f in (prev_color, prev_aov0, prev_aov1))
@@ -886,6 +954,12 @@ class RayTraceRenderer:
             raise ValueError("prev_color, prev_aov0 and prev_aov1 must be H x W x 4 of the renderer's size")
         out = np.zeros(shape, np.float32)
         p = abi.ReprojectParams(**params)
+        if prev_poses is not None:
+            state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
+            arr, keep_bones = self._pose_array(prev_poses)
+            abi.check(abi.lib().glz_renderer_reproject_posed(self._h, C.cast(C.byref(state), C.c_void_p), C.cast(arr, C.c_void_p), len(prev_poses), _ptr(c), _ptr(a0),
+                                                             _ptr(a1), C.cast(C.byref(p), C.c_void_p), _ptr(out)))
+            return out
         if prev_vertices is not None:
             state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
             abi.check(abi.lib().glz_renderer_reproject_from(self._h, C.cast(C.byref(state), C.c_void_p), _ptr(c), _ptr(a0), _ptr(a1), C.cast(C.byref(p), C.c_void_p),

@@ -155,6 +155,16 @@ class PreviousState(C.Structure):
                 ("first_vertex", C.c_uint32), ("n_vertices", C.c_uint32)]
 
 
+class Skin(C.Structure):
+    """glz_skin"""
+    _fields_ = [("first_vertex", C.c_uint32), ("n_vertices", C.c_uint32), ("joints", C.c_void_p), ("weights", C.c_void_p), ("n_bones", C.c_uint32)]
+
+
+class Pose(C.Structure):
+    """glz_pose"""
+    _fields_ = [("skin", C.c_int), ("bones", C.c_void_p), ("n_bones", C.c_uint32)]
+
+
 AOV_NORMAL_DEPTH, AOV_ALBEDO_INSTANCE = 0, 1
 GUIDE_FIRST_HIT, GUIDE_THROUGH_SPECULAR, GUIDE_MAX_BOUNCES = 0, 1, 8
 DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_POWER_LOG2 = 8, 31
@@ -207,6 +217,13 @@ PROTOTYPES = {
     "glz_renderer_update_transforms": (C.c_int, [_P, _P, C.c_uint32]),
     "glz_renderer_update_vertices": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int]),
     "glz_renderer_geometry_update_info": (C.c_int, [_P, _P]),
+    "glz_renderer_add_skin": (C.c_int, [_P, _P]),
+    "glz_renderer_remove_skin": (C.c_int, [_P, C.c_int]),
+    "glz_renderer_pose_skins": (C.c_int, [_P, _P, C.c_uint32, C.c_int]),
+    "glz_renderer_read_vertices": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "glz_renderer_read_motion_posed": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    "glz_renderer_reproject_posed": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "glz_host_skin": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, _P]),
     "glz_debug_read_leaf_records": (C.c_int64, [_P, _P, C.c_int64]),
     "glz_debug_read_tlas_instances": (C.c_int64, [_P, _P, C.c_int64]),
     "glz_debug_instance_boxes": (C.c_int64, [_P, C.c_int, C.c_uint64, _P, _P]),
@@ -279,6 +296,7 @@ PROTOTYPES = {
     "glz_renderer_read_motion_from": (C.c_int, [_P, _P, _P]),
     "glz_renderer_reproject_from": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "glz_debug_motion_timing_from": (C.c_int, [_P, _P, _P]),
+    "glz_debug_skin_timing": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "glz_host_project_constants": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     "glz_host_project_points": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P]),
     "glz_host_reproject": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P]),

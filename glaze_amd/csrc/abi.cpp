@@ -354,6 +354,38 @@ int glz_renderer_geometry_update_info(glz_renderer* h, glz_geometry_update_info*
   GLZ_RET(h->r->geometry_update_info(*out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_renderer_add_skin(glz_renderer* h, const glz_skin* skin) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!skin) return fail(GLZ_E_ARG, "add_skin: the skin is null");
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  const int id = h->r->add_skin(*skin, e);
+  if (id < 0) return fail(e);
+  return id;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_remove_skin(glz_renderer* h, int skin) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  GLZ_RET(h->r->remove_skin(skin, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_pose_skins(glz_renderer* h, const glz_pose* poses, uint32_t n, int mode) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  // (checked here as well as in the scene: a refused call must not make the renderer drain and restart)
+  uint32_t first = 0, count = 0;
+  if (!h->r->scene()->posed_span(poses, n, "pose_skins", first, count, e)) return fail(e);
+  if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return fail(GLZ_E_ARG, "pose_skins: unknown mode");
+  GLZ_RET(h->r->pose_skins(poses, n, mode, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_read_vertices(glz_renderer* h, uint32_t first, uint32_t n, glz_vertex* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  if (!out || !n || (uint64_t)first + n > h->r->scene()->data.vertices.size()) return fail(GLZ_E_ARG, "read_vertices: null output, none, or a range past the scene's vertex count");
+  GLZ_RET(h->r->read_vertices(first, n, out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_refresh_binded_textures(glz_renderer* h, const glz_texture* t, uint32_t nt) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!t || !nt) return fail(GLZ_E_ARG, "null array");
@@ -453,6 +485,21 @@ int glz_renderer_reproject_from(glz_renderer* h, const glz_previous_state* prev,
   if (!prev || !prev->camera || !prev_color || !prev_aov0 || !prev_aov1 || !out) return fail(GLZ_E_ARG, "the previous state, its camera, a previous frame or the output is null");
   if (prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
   GLZ_RET(h->r->post().reproject(*prev, prev_color, prev_aov0, prev_aov1, params, out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_read_motion_posed(glz_renderer* h, const glz_previous_state* prev, const glz_pose* poses, uint32_t n_poses, float* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!prev || !prev->camera || !out) return fail(GLZ_E_ARG, "the previous state, its camera or the output is null");
+  if (prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
+  GLZ_RET(h->r->post().read_motion(*prev, out, e, PrevPoses{poses, n_poses, true}));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_reproject_posed(glz_renderer* h, const glz_previous_state* prev, const glz_pose* poses, uint32_t n_poses, const float* prev_color, const float* prev_aov0,
+                                 const float* prev_aov1, const glz_reproject_params* params, float* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!prev || !prev->camera || !prev_color || !prev_aov0 || !prev_aov1 || !out) return fail(GLZ_E_ARG, "the previous state, its camera, a previous frame or the output is null");
+  if (prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
+  GLZ_RET(h->r->post().reproject(*prev, prev_color, prev_aov0, prev_aov1, params, out, e, PrevPoses{poses, n_poses, true}));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_launch_constants(glz_renderer* h, uint32_t launch, uint32_t* seed, float off[2]) {

@@ -8,6 +8,7 @@
 #include "abi_internal.h"
 #include "denoise.h"
 #include "reproject.h"
+#include "skin.h"
 #include "mipchain.h"
 #include "rccl_dl.h"
 #include "tile_map.h"
@@ -109,6 +110,13 @@ int glz_debug_motion_timing_from(glz_renderer* h, const glz_previous_state* prev
   if (!prev || !prev->camera || !kernel_ms_out || prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "bad argument");
   *kernel_ms_out = 0.0f;
   GLZ_RET(h->r->post().time_motion(*prev, kernel_ms_out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_skin_timing(glz_renderer* h, const glz_pose* pose, uint32_t reps, float* kernel_ms_out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!pose || !kernel_ms_out || !h->r->scene()) return fail(GLZ_E_ARG, "bad argument");
+  *kernel_ms_out = 0.0f;
+  GLZ_RET(h->r->wait_idle(e) && h->r->scene()->time_skin(*pose, reps, kernel_ms_out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_debug_guide_chain(glz_renderer* h, uint32_t segment, float* origins3, float* dirs3, uint8_t* alive) {
@@ -411,6 +419,17 @@ int glz_debug_project_points(glz_instance* inst, const glz_camera* camera, uint3
   if (st != 0) return st < 0 ? st : GLZ_OK;
   return debug_call(inst->i.get(), "debug project points", "k_project_points",
                     [&](DebugCall& c) { return launch_project_points(c.st, C, w, h, c.in(points3, n * 3), (uint32_t)n, c.out(out3, n * 3)); });
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_host_skin(const glz_vertex* bind, const uint16_t* joints, const float* weights, uint64_t n, const glz_transform* bones, uint32_t n_bones, glz_vertex* out) {
+  GLZ_GUARD_BEGIN
+  if (n_bones == 0 || !bones) return fail(GLZ_E_ARG, "host_skin: no bones");
+  if (n == 0) return GLZ_OK;
+  if (!bind || !joints || !weights || !out) return fail(GLZ_E_ARG, "host_skin: null argument");
+  for (uint64_t i = 0; i < 4 * n; ++i)
+    if (joints[i] >= n_bones) return fail(GLZ_E_ARG, "host_skin: a joint names a bone past n_bones");
+  post::host_skin(bind, joints, weights, (size_t)n, bones, n_bones, out);
+  return GLZ_OK;
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_host_reproject(uint32_t w, uint32_t h, const float* motion, const float* color, const float* aov0, const float* aov1, const glz_reproject_params* p, float* out) {

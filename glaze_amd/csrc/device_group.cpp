@@ -97,8 +97,10 @@ struct DeviceGroup::Peer {
   std::shared_ptr<Scene> replica_of(const Scene& src, const Instance& src_inst, Error& e) {
     inst->copy_build_options(src_inst);
     if (src.info.as_levels) inst->as_levels = (int)src.info.as_levels;
-    SceneData copy = src.data;
-    return std::shared_ptr<Scene>(Scene::create(inst.get(), std::move(copy), e));
+    SceneData copy = src.data;   // (current: change_scene / build have asked src.host_data() on the root's thread)
+    std::shared_ptr<Scene> replica(Scene::create(inst.get(), std::move(copy), e));
+    if (replica && !replica->copy_skins(src, e)) replica.reset();
+    return replica;
   }
   ~Peer() {
     worker.stop();
@@ -297,6 +299,7 @@ bool DeviceGroup::build(const Plan& plan, Error& err) {
   exchange_ = plan.exchange;
   // instance + scene replica (upload, BVH build) + renderer for the tiles t % n == i, on every peer's own thread
   const Renderer* root = &root_;
+  if (!root_.scene()->host_data(err)) return false;   // the replicas are created from the host copy: its vertices as the device has them
   const Scene* src = root_.scene();
   const Instance* src_inst = src->instance ? src->instance : root_.instance();
   const uint32_t w = root_.width(), h = root_.height(), world = (uint32_t)n;

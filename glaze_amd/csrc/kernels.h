@@ -248,6 +248,14 @@ hipError_t launch_reproject(hipStream_t st, uint32_t w, uint32_t h, const glz_re
                             const float4* prev_aov0, const float4* prev_aov1, float4* out, hipEvent_t* marks = nullptr);
 hipError_t launch_project_points(hipStream_t st, const post::ProjectConstants& C, uint32_t w, uint32_t h, const float* points3, uint32_t n, float* out3);
 
+// ---- skinning (kernels_skin.hip; skin.h holds the rule) ----
+// out[2 * i], out[2 * i + 1] = vertex i of `bind` under its four joints and weights, i < n.  bind: two float4 a vertex; joints: four uint16
+// a vertex as one uint2; weights: one float4 a vertex; bones: three float4 rows a bone (post::pack_bone), every joint below n_bones (the
+// caller has checked: the kernel indexes by them); out: n vertices of device memory that overlap no input.  The bone table is staged in LDS
+// when n_bones <= kSkinLdsBones, else read from memory.
+constexpr uint32_t kSkinLdsBones = 256;   // 12 KB of a block's LDS
+hipError_t launch_skin(hipStream_t st, const float4* bind, const uint2* joints, const float4* weights, uint32_t n, const float4* bones, uint32_t n_bones, float4* out);
+
 // debug / parity hooks
 hipError_t launch_debug_closest(hipStream_t st, const DeviceScene& scene, const float* origins, const float* dirs, uint32_t n, float tmin,
                                 float* t, uint32_t* tri, uint32_t* inst, float* u, float* v, uint32_t* overflow, uint32_t overflow_depth);

@@ -172,7 +172,7 @@ const float4* PostStage::filtered(const float4* frame, bool filter, hipEvent_t* 
 }
 
 // the checks of read_motion and reproject, the upload of the caller's matrices and vertices, then the first-hit pass with k_motion in it
-bool PostStage::motion_pass(const glz_previous_state& prev, PrevBuffers& uploaded, DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks) {
+bool PostStage::motion_pass(const glz_previous_state& prev, PrevBuffers& uploaded, DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks, const PrevPoses& posed) {
   const glz_camera* prev_camera = prev.camera;
   const glz_transform* prev_transforms = prev.transforms;
   const uint32_t n_prev = prev.n_transforms;
@@ -182,6 +182,11 @@ bool PostStage::motion_pass(const glz_previous_state& prev, PrevBuffers& uploade
   if (prev.vertices && prev.n_vertices == 0) return bad_argument(err, "motion: previous vertices given, but none of them (n_vertices is 0)");
   if (prev.vertices && (uint64_t)prev.first_vertex + prev.n_vertices > r_.scene()->data.vertices.size())
     return bad_argument(err, "motion: the range of the previous vertices reaches past the scene's vertex count");
+  uint32_t posed_first = 0, posed_count = 0;
+  if (posed.given) {
+    if (prev.vertices) return bad_argument(err, "motion: a posed previous state brings no vertices of its own (vertices must be null)");
+    if (!r_.scene()->posed_span(posed.poses, posed.n, "motion", posed_first, posed_count, err)) return false;
+  }
   if (!hip_ok(hipSetDevice(r_.instance()->device), "hipSetDevice", err)) return false;
   MotionStep step;
   host::project_constants(*prev_camera, r_.width(), r_.height(), step.prev.world2camera, step.prev.camera2screen);
@@ -202,6 +207,21 @@ bool PostStage::motion_pass(const glz_previous_state& prev, PrevBuffers& uploade
     step.first_vertex = prev.first_vertex;
     step.n_vertices = prev.n_vertices;
   }
+  if (posed.given) {   // the same buffer, filled on the device: the current vertices of the span, then every skin as its previous bones pose it
+    hipStream_t st = r_.instance()->stream;
+    const Scene& scene = *r_.scene();
+    if (!hip_ok(uploaded.vertices.alloc(2 * (size_t)posed_count), "alloc previous vertices", err) ||
+        !hip_ok(hipMemcpyAsync(uploaded.vertices.ptr, scene.dev.vertices + 2 * (size_t)posed_first, sizeof(float4) * 2 * (size_t)posed_count, hipMemcpyDeviceToDevice, st),
+                "copy current vertices", err))
+      return false;
+    uploaded.bones = std::vector<DeviceBuffer<float4>>(posed.n);
+    uploaded.packed.assign(posed.n, {});
+    for (uint32_t i = 0; i < posed.n; ++i)
+      if (!scene.skin_into(posed.poses[i], uploaded.vertices.ptr, posed_first, uploaded.packed[i], uploaded.bones[i], st, err)) return false;
+    step.prev_vertices = uploaded.vertices.ptr;
+    step.first_vertex = posed_first;
+    step.n_vertices = posed_count;
+  }
   if (!hip_ok(motion.alloc((size_t)r_.width() * r_.height()), "alloc motion plane", err)) return false;
   step.out = motion.ptr;
   step.marks = marks;
@@ -210,10 +230,10 @@ bool PostStage::motion_pass(const glz_previous_state& prev, PrevBuffers& uploade
   return first_hit_pass(pass, err);
 }
 
-bool PostStage::read_motion(const glz_previous_state& prev, float* out, Error& err) {
+bool PostStage::read_motion(const glz_previous_state& prev, float* out, Error& err, const PrevPoses& posed) {
   PrevBuffers uploaded;
   DeviceBuffer<float4> motion;
-  if (!motion_pass(prev, uploaded, motion, err)) return false;
+  if (!motion_pass(prev, uploaded, motion, err, nullptr, posed)) return false;
   return r_.frame_to_host(motion.ptr, out, "read motion", err);
 }
 
@@ -229,12 +249,12 @@ bool PostStage::time_motion(const glz_previous_state& prev, float* kernel_ms, Er
 }
 
 bool PostStage::reproject(const glz_previous_state& prev, const float* prev_color, const float* prev_aov0, const float* prev_aov1, const glz_reproject_params* params,
-                          float* out, Error& err) {
+                          float* out, Error& err, const PrevPoses& posed) {
   const glz_reproject_params P = params ? *params : post::reproject_defaults();
   if (!post::reproject_params_valid(P)) return bad_argument(err, post::kReprojectParamsMessage);
   PrevBuffers uploaded;
   DeviceBuffer<float4> motion, color, plane0, plane1, result;
-  if (!motion_pass(prev, uploaded, motion, err)) return false;
+  if (!motion_pass(prev, uploaded, motion, err, nullptr, posed)) return false;
   const uint32_t w = r_.width(), h = r_.height();
   const size_t n = (size_t)w * h;
   hipStream_t st = r_.instance()->stream;

@@ -11,6 +11,15 @@ namespace glz {
 
 class Renderer;
 
+// Previous vertices made on the device (glz_renderer_read_motion_posed / reproject_posed): the skins as the PREVIOUS bones pose them.  The
+// buffer k_motion_deform reads then holds the span from the lowest to the highest posed vertex: the scene's current vertices copied
+// device to device (so a gap between skins holds current values), then k_skin of every named skin with these bones.
+struct PrevPoses {
+  const glz_pose* poses = nullptr;
+  uint32_t n = 0;
+  bool given = false;   // a *_posed call: the state must bring no vertices, and the poses are checked as pose_skins checks them
+};
+
 class PostStage {
  public:
   explicit PostStage(const Renderer& r) : r_(r) {}
@@ -31,10 +40,10 @@ class PostStage {
   // motion vectors and history reprojection (glz_reproject_params; reproject.h): the first-hit trace and k_motion against the caller's
   // previous state -- camera, transforms (null = the scene's own) and vertices (null = the meshes did not deform; else k_motion_deform on the
   // uploaded array) -- then, for reproject, k_reproject on the three uploaded previous frames
-  bool read_motion(const glz_previous_state& prev, float* out, Error& err);
+  bool read_motion(const glz_previous_state& prev, float* out, Error& err, const PrevPoses& posed = {});
   bool time_motion(const glz_previous_state& prev, float* kernel_ms, Error& err);   // k_motion / k_motion_deform alone, device events
   bool reproject(const glz_previous_state& prev, const float* prev_color, const float* prev_aov0, const float* prev_aov1, const glz_reproject_params* params, float* out,
-                 Error& err);
+                 Error& err, const PrevPoses& posed = {});
   bool camera_rays(float off_x, float off_y, float* origins3, float* dirs3, Error& err);   // camera_ray() of every pixel, on the device
   // which surface the feature buffers describe (GLZ_GUIDE_*, glaze_abi.h holds the specification); accumulation goes on
   bool set_guide_mode(int mode, uint32_t max_bounces, Error& err);
@@ -64,9 +73,12 @@ class PostStage {
   void post_args(LaunchArgs& a) const;
   // what a motion pass uploads of the caller's previous state: owned by the call and released with it
   struct PrevBuffers {
+    std::vector<std::vector<float4>> packed;     // the host arrays the bone tables are copied from (first, so released last: after the buffers' hipFree has waited)
     DeviceBuffer<float4> o2w, vertices;
+    std::vector<DeviceBuffer<float4>> bones;     // one table per previous pose
   };
-  bool motion_pass(const glz_previous_state& prev, PrevBuffers& uploaded, DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks = nullptr);
+  bool motion_pass(const glz_previous_state& prev, PrevBuffers& uploaded, DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks = nullptr,
+                   const PrevPoses& posed = {});
   GuideLists guide_lists() const { return GuideLists{{guide_o_[0].ptr, guide_o_[1].ptr}, {guide_d_[0].ptr, guide_d_[1].ptr}, guide_count_.ptr}; }
 
   const Renderer& r_;

@@ -529,7 +529,7 @@ bool Renderer::change_scene(std::shared_ptr<Scene> scene, Error& err) {
   if (!resize([&] {
         scene_ = scene;
         cfg_.exposure = scene->data.meta.exposure;
-      }, err) || !group_.change_scene(*scene, scene->instance ? *scene->instance : *inst_, err))
+      }, err) || (!group_.empty() && !scene->host_data(err)) || !group_.change_scene(*scene, scene->instance ? *scene->instance : *inst_, err))
     return false;
   return update_camera(scene->data.camera, err);   // raytracer.rs:246-247
 }
@@ -564,6 +564,32 @@ bool Renderer::update_transforms(const glz_transform* t, uint32_t n, Error& err)
 bool Renderer::update_vertices(const glz_vertex* v, uint32_t first, uint32_t n, int mode, Error& err) {
   if (!update_scene([&] { return scene_->update_vertices(v, first, n, mode, err); }, err)) return false;
   return group_.forward([=](Renderer& p, Error& e) { return p.update_vertices(v, first, n, mode, e); }, err);
+}
+
+// Skins are the scene's: added, removed and posed on the scene object and on every other device's replica, which gives the same ids.
+int Renderer::add_skin(const glz_skin& skin, Error& err) {
+  if (!wait_idle(err)) return -1;
+  const int id = scene_->add_skin(skin, err);
+  if (id < 0) return -1;
+  const glz_skin k = skin;
+  const bool followed = group_.forward([=](Renderer& p, Error& e) {
+    const int got = p.add_skin(k, e);
+    if (got >= 0 && got != id) e.fail(GLZ_E_DEVICE, "add_skin: a replica gave another skin id");
+    return got == id;
+  }, err);
+  if (!followed) return -1;
+  return id;
+}
+bool Renderer::remove_skin(int id, Error& err) {
+  if (!wait_idle(err) || !scene_->remove_skin(id, err)) return false;
+  return group_.forward([=](Renderer& p, Error& e) { return p.remove_skin(id, e); }, err);
+}
+bool Renderer::pose_skins(const glz_pose* poses, uint32_t n, int mode, Error& err) {
+  if (!update_scene([&] { return scene_->pose_skins(poses, n, mode, err); }, err)) return false;
+  return group_.forward([=](Renderer& p, Error& e) { return p.pose_skins(poses, n, mode, e); }, err);
+}
+bool Renderer::read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& err) {
+  return wait_idle(err) && scene_->read_vertices(first, n, out, err);
 }
 
 bool Renderer::geometry_update_info(glz_geometry_update_info& out, Error& err) {

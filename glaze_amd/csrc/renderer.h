@@ -30,6 +30,10 @@ class Renderer {
   bool refresh_binded_textures(const glz_texture* t, uint32_t nt, Error& err);
   bool update_transforms(const glz_transform* t, uint32_t n, Error& err);   // Scene::update_transforms; restarts accumulation
   bool update_vertices(const glz_vertex* v, uint32_t first, uint32_t n, int mode, Error& err);   // Scene::update_vertices; restarts accumulation
+  int add_skin(const glz_skin& skin, Error& err);       // Scene::add_skin here and on every replica; the id, or -1
+  bool remove_skin(int id, Error& err);
+  bool pose_skins(const glz_pose* poses, uint32_t n, int mode, Error& err);   // Scene::pose_skins; restarts accumulation, like update_vertices
+  bool read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& err);   // idle first, then the scene's vertices as the device holds them
   bool geometry_update_info(glz_geometry_update_info& out, Error& err);   // Scene::geometry_update_info, idle first (it may make the refit plan); accumulation goes on
   bool wait_idle(Error& err);
   uint32_t steps_per_sample() const { return cfg_.integrator == GLZ_DIRECT ? 1u : cfg_.pt_steps; }

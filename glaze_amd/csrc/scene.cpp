@@ -7,6 +7,7 @@
 
 #include "host_math.h"
 #include "mipchain.h"
+#include "skin.h"
 
 namespace glz {
 
@@ -199,6 +200,7 @@ bool Scene::update_materials_and_lights(const glz_material* mats, uint32_t n_mat
   }
   for (uint32_t i = 0; i < n_lights; ++i)
     if (lights[i].ltype == GLZ_LIGHT_SKY && lights[i].resource_id >= nt) return err.fail(GLZ_E_INVALID_DATA, "sky light references a missing texture");
+  if (!mirror_for_accel(err)) return false;
   hipStream_t st = instance->stream;
   Composed at_exit{*this};
   if (textures) {
@@ -229,6 +231,11 @@ bool Scene::refresh_textures(const glz_texture* textures, uint32_t n, Error& err
 }
 
 bool Scene::instance_boxes(bool on_device, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err) {
+  if (!mirror_for_accel(err)) {
+    lo.clear();
+    hi.clear();
+    return false;
+  }
   if (!on_device || !accel_.two_level()) return accel_.instance_boxes(sources(), false, budget, lo, hi, err);
   if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) {
     lo.clear();
@@ -242,7 +249,7 @@ bool Scene::instance_boxes(bool on_device, uint64_t budget, std::vector<float4>&
 bool Scene::update_transforms(const glz_transform* transforms, uint32_t n, Error& err) {
   if (!transforms || n != data.transforms.size())
     return err.fail(GLZ_E_ARG, "update_transforms: the transform count must not change (instances index transforms)");
-  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err) || !mirror_for_accel(err)) return false;
   data.transforms.assign(transforms, transforms + n);
   const std::vector<TransformPair> xf = transform_pairs(data.transforms);
   if (!hip_ok(hipMemcpyAsync(geometry_.transforms.ptr, xf.data(), sizeof(TransformPair) * n, hipMemcpyHostToDevice, instance->stream), "upload transforms", err) ||
@@ -264,6 +271,7 @@ bool Scene::update_vertices(const glz_vertex* vertices, uint32_t first, uint32_t
   if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return err.fail(GLZ_E_ARG, "update_vertices: unknown mode");
   // (valid_geometry, which creation runs, looks at index ranges and references alone: no position is refused there, so none is here)
   if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  if (!mirror_for_accel(err)) return false;   // (before the new ones go into it: a span read back later would be the device's all the same)
   hipStream_t st = instance->stream;
   Composed at_exit{*this};
   if (mode == GLZ_GEOMETRY_REFIT && !accel_.prepare_refit(sources(), err)) return false;   // needs the vertices the structure was built from
@@ -274,6 +282,163 @@ bool Scene::update_vertices(const glz_vertex* vertices, uint32_t first, uint32_t
       !hip_ok(launch_derivatives(st, geometry_.vertices.ptr, geometry_.indices.ptr, (uint32_t)(geometry_.derivatives.count / 3), geometry_.derivatives.ptr), "derivatives kernel", err))
     return false;
   return accel_.update_geometry(sources(), mode, first, n, timer, err);
+}
+
+// ---- skinned meshes ----
+
+const SceneData* Scene::host_data(Error& err) {
+  if (stale_count_ == 0) return &data;
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err) ||
+      !hip_ok(hipMemcpyAsync(data.vertices.data() + stale_first_, geometry_.vertices.ptr + 2 * (size_t)stale_first_, sizeof(glz_vertex) * stale_count_, hipMemcpyDeviceToHost,
+                             instance->stream), "read posed vertices", err) ||
+      !hip_ok(hipStreamSynchronize(instance->stream), "read posed vertices", err))
+    return nullptr;
+  stale_count_ = 0;
+  return &data;
+}
+
+bool Scene::read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& err) {
+  if (!out || n == 0 || (uint64_t)first + n > data.vertices.size())
+    return err.fail(GLZ_E_ARG, "read_vertices: null output, none, or a range past the scene's vertex count");
+  return hip_ok(hipSetDevice(instance->device), "hipSetDevice", err) &&
+         hip_ok(hipMemcpyAsync(out, geometry_.vertices.ptr + 2 * (size_t)first, sizeof(glz_vertex) * n, hipMemcpyDeviceToHost, instance->stream), "read vertices", err) &&
+         hip_ok(hipStreamSynchronize(instance->stream), "read vertices", err);
+}
+
+// the device half of add_skin and copy_skins: every buffer of the skin, or none of it
+int Scene::install_skin(int id, uint32_t first, std::vector<glz_vertex>&& bind, std::vector<uint16_t>&& joints, std::vector<float>&& weights, uint32_t n_bones,
+                        const float4* device_bind, Error& err) {
+  hipStream_t st = instance->stream;
+  Skin s;
+  s.first = first;
+  s.n = (uint32_t)bind.size();
+  s.n_bones = n_bones;
+  s.h_bind = std::move(bind);
+  s.h_joints = std::move(joints);
+  s.h_weights = std::move(weights);
+  static_assert(sizeof(uint2) == 4 * sizeof(uint16_t) && sizeof(glz_vertex) == 2 * sizeof(float4), "four joints are one uint2, a vertex two float4");
+  // the bind pose: device to device from the scene's own vertices (add_skin), or from the host copy (a replica on another device)
+  hipError_t bound = device_bind ? s.bind.alloc(2 * (size_t)s.n) : s.bind.upload(reinterpret_cast<const float4*>(s.h_bind.data()), 2 * (size_t)s.n, st);
+  if (bound == hipSuccess && device_bind) bound = hipMemcpyAsync(s.bind.ptr, device_bind, sizeof(float4) * 2 * (size_t)s.n, hipMemcpyDeviceToDevice, st);
+  if (!hip_ok(bound, "bind pose", err) ||
+      !hip_ok(s.joints.upload(reinterpret_cast<const uint2*>(s.h_joints.data()), s.n, st), "upload joints", err) ||
+      !hip_ok(s.weights.upload(reinterpret_cast<const float4*>(s.h_weights.data()), s.n, st), "upload weights", err) ||
+      !hip_ok(s.bones.alloc((size_t)post::kSkinBoneRows * n_bones), "alloc bones", err) || !hip_ok(hipStreamSynchronize(st), "add_skin", err))
+    return -1;
+  skins_.emplace(id, std::move(s));
+  return id;
+}
+
+int Scene::add_skin(const glz_skin& k, Error& err) {
+  auto refuse = [&](const char* why) {
+    err.fail(GLZ_E_ARG, why);
+    return -1;
+  };
+  if (!k.joints || !k.weights) return refuse("add_skin: joints or weights is null");
+  if (k.n_vertices == 0 || (uint64_t)k.first_vertex + k.n_vertices > data.vertices.size()) return refuse("add_skin: no vertices, or a range past the scene's vertex count");
+  if (k.n_bones == 0 || k.n_bones > 65536u) return refuse("add_skin: n_bones must be 1 .. 65536 (joints are 16 bits)");
+  for (size_t i = 0; i < 4 * (size_t)k.n_vertices; ++i)
+    if (k.joints[i] >= k.n_bones) return refuse("add_skin: a joint names a bone past n_bones");
+  for (const auto& kv : skins_)
+    if (k.first_vertex < (uint64_t)kv.second.first + kv.second.n && kv.second.first < (uint64_t)k.first_vertex + k.n_vertices)
+      return refuse("add_skin: the range overlaps an existing skin");
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return -1;
+  // the bind pose is what the device holds now (the mirror may be behind it); the host copy of it is for replicas made later
+  std::vector<glz_vertex> bind(k.n_vertices);
+  if (!read_vertices(k.first_vertex, k.n_vertices, bind.data(), err)) return -1;
+  const int id = install_skin(next_skin_, k.first_vertex, std::move(bind), std::vector<uint16_t>(k.joints, k.joints + 4 * (size_t)k.n_vertices),
+                              std::vector<float>(k.weights, k.weights + 4 * (size_t)k.n_vertices), k.n_bones, geometry_.vertices.ptr + 2 * (size_t)k.first_vertex, err);
+  if (id >= 0) ++next_skin_;
+  return id;
+}
+
+bool Scene::remove_skin(int id, Error& err) {
+  if (skins_.erase(id) == 0) return err.fail(GLZ_E_ARG, "remove_skin: no such skin");
+  return true;
+}
+
+bool Scene::copy_skins(const Scene& src, Error& err) {
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  for (const auto& kv : src.skins_) {
+    const Skin& s = kv.second;
+    if (install_skin(kv.first, s.first, std::vector<glz_vertex>(s.h_bind), std::vector<uint16_t>(s.h_joints), std::vector<float>(s.h_weights), s.n_bones, nullptr, err) < 0) return false;
+  }
+  next_skin_ = src.next_skin_;
+  return true;
+}
+
+bool Scene::posed_span(const glz_pose* poses, uint32_t n_poses, const char* who, uint32_t& first, uint32_t& count, Error& err) const {
+  auto refuse = [&](const char* why) { return err.fail(GLZ_E_ARG, std::string(who) + ": " + why); };
+  if (!poses || n_poses == 0) return refuse("poses is null or empty");
+  uint64_t lo = ~0ull, hi = 0;
+  for (uint32_t i = 0; i < n_poses; ++i) {
+    const auto it = skins_.find(poses[i].skin);
+    if (it == skins_.end()) return refuse("no such skin");
+    if (!poses[i].bones) return refuse("a pose's bones are null");
+    if (poses[i].n_bones != it->second.n_bones) return refuse("a pose's bone count is not its skin's");
+    for (uint32_t k = 0; k < i; ++k)
+      if (poses[k].skin == poses[i].skin) return refuse("a skin is named twice");
+    lo = std::min<uint64_t>(lo, it->second.first);
+    hi = std::max<uint64_t>(hi, (uint64_t)it->second.first + it->second.n);
+  }
+  first = (uint32_t)lo;
+  count = (uint32_t)(hi - lo);
+  return true;
+}
+
+bool Scene::skin_into(const glz_pose& pose, float4* span, uint32_t span_first, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const {
+  const Skin& s = skins_.at(pose.skin);
+  packed.resize((size_t)post::kSkinBoneRows * s.n_bones);
+  for (uint32_t b = 0; b < s.n_bones; ++b) post::pack_bone(pose.bones[b], packed.data() + (size_t)post::kSkinBoneRows * b);
+  if (bones.ptr == nullptr || bones.count != packed.size()) {
+    if (!hip_ok(bones.alloc(packed.size()), "alloc bones", err)) return false;
+  }
+  return hip_ok(hipMemcpyAsync(bones.ptr, packed.data(), sizeof(float4) * packed.size(), hipMemcpyHostToDevice, st), "upload bones", err) &&
+         hip_ok(launch_skin(st, s.bind.ptr, s.joints.ptr, s.weights.ptr, s.n, bones.ptr, s.n_bones, span + 2 * (size_t)(s.first - span_first)), "k_skin", err);
+}
+
+bool Scene::time_skin(const glz_pose& pose, uint32_t reps, float* kernel_ms, Error& err) const {
+  uint32_t first = 0, count = 0;
+  if (!kernel_ms || reps == 0) return err.fail(GLZ_E_ARG, "skin timing: null output or no repeats");
+  if (!posed_span(&pose, 1, "skin timing", first, count, err)) return false;
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  hipStream_t st = instance->stream;
+  std::vector<float4> packed;
+  DeviceBuffer<float4> bones, out;
+  Events<2> t;
+  if (!hip_ok(out.alloc(2 * (size_t)count), "alloc", err) || !t.create(err) || !skin_into(pose, out.ptr, first, packed, bones, st, err)) return false;
+  (void)hipEventRecord(t.ev[0], st);
+  for (uint32_t i = 0; i < reps; ++i)
+    if (!skin_into(pose, out.ptr, first, packed, bones, st, err)) return false;
+  (void)hipEventRecord(t.ev[1], st);
+  if (!hip_ok(hipStreamSynchronize(st), "skin timing", err)) return false;
+  (void)hipEventElapsedTime(kernel_ms, t.ev[0], t.ev[1]);
+  *kernel_ms /= (float)reps;
+  return true;
+}
+
+bool Scene::pose_skins(const glz_pose* poses, uint32_t n_poses, int mode, Error& err) {
+  uint32_t first = 0, count = 0;
+  if (!posed_span(poses, n_poses, "pose_skins", first, count, err)) return false;
+  if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return err.fail(GLZ_E_ARG, "pose_skins: unknown mode");
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  hipStream_t st = instance->stream;
+  Composed at_exit{*this};
+  if (mode == GLZ_GEOMETRY_REFIT && !accel_.prepare_refit(sources(), err)) return false;   // needs the vertices the structure was built from
+  StreamTimer timer;
+  if (!timer.start(st, err)) return false;
+  // whatever happens from here on, the device's vertices may differ from the mirror's over the span (joined with a span still pending)
+  const uint64_t lo = stale_count_ ? std::min(stale_first_, first) : first;
+  const uint64_t hi = stale_count_ ? std::max<uint64_t>((uint64_t)stale_first_ + stale_count_, (uint64_t)first + count) : (uint64_t)first + count;
+  stale_first_ = (uint32_t)lo;
+  stale_count_ = (uint32_t)(hi - lo);
+  std::vector<std::vector<float4>> packed(n_poses);   // (they outlive the copies: update_geometry waits for the stream)
+  for (uint32_t i = 0; i < n_poses; ++i)
+    if (!skin_into(poses[i], geometry_.vertices.ptr, 0, packed[i], skins_.at(poses[i].skin).bones, st, err)) return false;
+  if (!hip_ok(launch_derivatives(st, geometry_.vertices.ptr, geometry_.indices.ptr, (uint32_t)(geometry_.derivatives.count / 3), geometry_.derivatives.ptr), "derivatives kernel", err))
+    return false;
+  if (!mirror_for_accel(err)) return false;   // two levels: the top level is rebuilt from the meshes' points
+  return accel_.update_geometry(sources(), mode, first, count, timer, err);
 }
 
 }  // namespace glz

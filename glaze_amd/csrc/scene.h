@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -62,6 +63,32 @@ class Scene {
   // scene traces and renders as one created with the new vertices does.  Refused arguments (GLZ_E_ARG) leave the scene untouched.
   bool update_vertices(const glz_vertex* vertices, uint32_t first, uint32_t n, int mode, Error& err);
   bool geometry_update_info(glz_geometry_update_info& out, Error& err);   // Accel::geometry_update
+  // ---- skinned meshes (skin.h holds the rule, kernels_skin.hip the kernel) ----
+  // A skin over the vertices [first_vertex, first_vertex + n_vertices): its bind pose is what the DEVICE holds there now (copied device to
+  // device into a buffer the skin owns), joints and weights are uploaded once.  Returns the skin's id (>= 0), or -1 with the error set;
+  // GLZ_E_ARG (nothing changes): see glz_renderer_add_skin.  Skins are the scene's, as the vertices are; ids count up and are never reused,
+  // so the replicas of a scene, told the same calls in the same order, give the same ids.
+  int add_skin(const glz_skin& skin, Error& err);
+  bool remove_skin(int id, Error& err);   // the vertices stay as they are
+  // Poses skins (each named once, with the bone count it was added with) and updates the structure once: bones up, k_skin per skin from its
+  // bind pose into the vertex buffer, then what update_vertices does after its upload, over the span from the lowest to the highest posed
+  // vertex.  The host mirror (data.vertices) is NOT written: the span is marked stale and read back when a reader asks (host_data()).
+  bool pose_skins(const glz_pose* poses, uint32_t n_poses, int mode, Error& err);
+  // The checks of a set of poses (null, none, unknown id, an id twice, another bone count) and the span [first, first + count) they cover
+  bool posed_span(const glz_pose* poses, uint32_t n_poses, const char* who, uint32_t& first, uint32_t& count, Error& err) const;
+  // What motion_pass fills its previous-vertex buffer with: k_skin of one (checked) pose into `span`, which holds the vertices from
+  // span_first on; the packed bones go up through `bones`, which must live until the stream has run the kernel, as must `packed`.
+  bool skin_into(const glz_pose& pose, float4* span, uint32_t span_first, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const;
+  bool read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& err);   // as the device holds them
+  // k_skin of one (checked) pose alone, into a scratch buffer (the scene is untouched): device-event time of `reps` launches after one
+  // that is not timed, divided by reps (glz_debug_skin_timing)
+  bool time_skin(const glz_pose& pose, uint32_t reps, float* kernel_ms, Error& err) const;
+  // The host copy with its vertices current.  `data` itself may be behind the device after pose_skins (never in its counts, transforms,
+  // indices, materials or lights); everything that reads the CONTENTS of data.vertices goes through here, which reads the stale span back
+  // (that span, no more) the first time it is asked after a pose.
+  const SceneData* host_data(Error& err);
+  // everything that makes `src`'s skins, on this scene (a replica on another device): same ids, same bind poses
+  bool copy_skins(const Scene& src, Error& err);
   // Instance boxes of a two-level scene under its current transforms (host rule, or the device kernel); false with an empty result
   // for a flattened scene.  budget: kExactBoxBudget for the scene's own.
   bool instance_boxes(bool on_device, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err);
@@ -86,6 +113,23 @@ class Scene {
   void compose();
   bool upload_geometry(Error& err);
   Accel::Sources sources() const { return Accel::Sources{instance->stream, data, geometry_, tables_, textures_}; }
+  // before sources() goes to a call of accel_ that may read the mirror's vertices: a two-level scene's instance boxes come from them
+  bool mirror_for_accel(Error& err) { return !accel_.two_level() || host_data(err) != nullptr; }
+
+  struct Skin {
+    uint32_t first = 0, n = 0, n_bones = 0;
+    DeviceBuffer<float4> bind, weights, bones;   // 2 a vertex; 1 a vertex; post::kSkinBoneRows a bone
+    DeviceBuffer<uint2> joints;                  // four uint16 a vertex
+    // host copies, for the replicas on other devices that are created later (DeviceGroup)
+    std::vector<glz_vertex> h_bind;
+    std::vector<uint16_t> h_joints;
+    std::vector<float> h_weights;
+  };
+  int install_skin(int id, uint32_t first, std::vector<glz_vertex>&& bind, std::vector<uint16_t>&& joints, std::vector<float>&& weights, uint32_t n_bones,
+                   const float4* device_bind, Error& err);
+  std::map<int, Skin> skins_;
+  int next_skin_ = 0;
+  uint32_t stale_first_ = 0, stale_count_ = 0;   // the span of data.vertices that is behind the device (count 0: none)
 
   Geometry geometry_;
   Textures textures_;

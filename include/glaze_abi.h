@@ -348,6 +348,55 @@ typedef struct glz_geometry_update_info {
   float    box_area_built;  /* the same sum for the structure as the builder left it (taken on the first refit after a build, before the new vertices go in; after a rebuild, of the new structure) */
 } glz_geometry_update_info;
 int glz_renderer_geometry_update_info(glz_renderer*, glz_geometry_update_info* out);   /* GLZ_E_ARG before any update */
+/* Build-defined: skinned meshes -- linear-blend skinning on the device, so that a posed character costs a few matrices over the bus a frame
+ * instead of its vertices.
+ *
+ *   THE SKINNING RULE (glz_renderer_pose_skins, glz_host_skin; one definition, glaze_amd/csrc/skin.h, compiled for host and device; the
+ *   tests hold both sides to this text bit for bit).  float32 throughout, only + and x, no contraction into fused multiply-adds, the
+ *   operations in exactly this order.  A vertex has bind position p, bind normal n, texture coordinate t, joints j0..j3 and weights w0..w3;
+ *   the bone matrices B[k] are glz_transform, column-major (element [r][c] is m[4 * c + r]); only the upper 3 x 4 is read, the fourth row
+ *   is ignored.  For row r in 0..2 and column c in 0..3:
+ *     M[r][c] = ((w0 * B[j0][r][c] + w1 * B[j1][r][c]) + w2 * B[j2][r][c]) + w3 * B[j3][r][c]
+ *     p'[r]   = ((M[r][0] * p.x + M[r][1] * p.y) + M[r][2] * p.z) + M[r][3]
+ *     n'[r]   =  (M[r][0] * n.x + M[r][1] * n.y) + M[r][2] * n.z
+ *     t'      = t
+ *   No term is skipped for a zero weight (0 x inf is NaN here too).  Weights are used as given and are not normalised.  The normal goes
+ *   through M's 3 x 3 and is not renormalised (shading normalises the normal it interpolates): that is exact only for rigid bones.  Bones
+ *   act in the mesh's OBJECT space, where the vertex buffer lives; the caller supplies joint_now x inverse_bind per bone -- the library
+ *   knows nothing of a skeleton hierarchy.
+ *
+ * glz_renderer_add_skin: a skin over the vertices [first_vertex, first_vertex + n_vertices).  Its bind pose is what the scene's vertices
+ * hold in that range at the moment of the call (copied on the device into a buffer the skin owns); joints (4 per vertex) and weights (4
+ * per vertex) are uploaded once.  Returns the skin's id (>= 0).  Skins belong to the SCENE object, as the vertices do: every renderer
+ * sharing the scene sees them, and every device of set_devices gets them.  GLZ_E_ARG (nothing changes): a null pointer, n_vertices == 0, a
+ * range past the vertex count, n_bones == 0 (or above 65536), a joint >= n_bones, a range that overlaps an existing skin.
+ * glz_renderer_remove_skin frees a skin; the vertices stay as they are.  GLZ_E_ARG: no such skin. */
+typedef struct glz_skin {
+  uint32_t        first_vertex;
+  uint32_t        n_vertices;
+  const uint16_t* joints;    /* 4 * n_vertices, each < n_bones */
+  const float*    weights;   /* 4 * n_vertices */
+  uint32_t        n_bones;
+} glz_skin;
+int glz_renderer_add_skin(glz_renderer*, const glz_skin*);
+int glz_renderer_remove_skin(glz_renderer*, int skin);
+/* Poses one or more skins and updates the structure ONCE: the bones of every named skin go up, the rule runs per skin from its bind pose
+ * into the scene's vertices, then the derivatives and the structure follow as in glz_renderer_update_vertices (`mode`: GLZ_GEOMETRY_*),
+ * over the span from the lowest to the highest posed vertex.  Everything update_vertices promises holds: idle first, accumulation
+ * restarts, every device of set_devices follows, glz_renderer_geometry_update_info describes it (update_ms: bone upload to last kernel),
+ * and afterwards hits and renders equal, bit for bit, those of a scene created with the vertices glz_host_skin gives.  A later
+ * update_vertices over a skinned range is allowed: it overwrites the current vertices, the bind pose stays, the next pose overwrites them
+ * again.  GLZ_E_ARG (the scene is untouched): a null pointer or n_poses == 0, an unknown skin, the same skin named twice, null bones,
+ * n_bones different from the skin's, an unknown mode. */
+typedef struct glz_pose {
+  int                  skin;
+  const glz_transform* bones;   /* n_bones matrices: joint_now x inverse_bind, object space */
+  uint32_t             n_bones; /* the skin's */
+} glz_pose;
+int glz_renderer_pose_skins(glz_renderer*, const glz_pose* poses, uint32_t n_poses, int mode);
+/* The scene's current vertices [first_vertex, first_vertex + n_vertices) as the device holds them (idle first).  GLZ_E_ARG: null output,
+ * n_vertices == 0, a range past the vertex count. */
+int glz_renderer_read_vertices(glz_renderer*, uint32_t first_vertex, uint32_t n_vertices, glz_vertex* out);
 /* raytracer.rs:328-356: the texture array changed under the same materials and lights (the reference re-binds the
  * textures it shares with the realtime viewer); accumulation is NOT restarted, like the reference. */
 int glz_renderer_refresh_binded_textures(glz_renderer*, const glz_texture* textures, uint32_t n_textures);
@@ -604,6 +653,15 @@ typedef struct glz_previous_state {
 int glz_renderer_read_motion_from(glz_renderer*, const glz_previous_state*, float* out);
 int glz_renderer_reproject_from(glz_renderer*, const glz_previous_state*, const float* prev_color, const float* prev_aov0,
                                 const float* prev_aov1, const glz_reproject_params* params_or_null, float* out);
+/* The same for a scene whose meshes are POSED (glz_renderer_pose_skins): the previous vertices never visit the host.  The state's
+ * vertices must be NULL; the buffer the motion kernel reads is filled on the device instead -- the span from the lowest to the highest
+ * vertex of the named skins is copied from the scene's current vertices (a gap between skins holds current values), then the skinning
+ * rule runs with the PREVIOUS bones, once per skin.  The planes equal, bit for bit, those of read_motion_from / reproject_from given the
+ * vertices glz_host_skin makes of the previous bones over that span.  GLZ_E_ARG (nothing launched, nothing changed): the checks of
+ * read_motion_from / reproject_from, non-NULL state->vertices, and the pose checks of glz_renderer_pose_skins. */
+int glz_renderer_read_motion_posed(glz_renderer*, const glz_previous_state*, const glz_pose* prev_poses, uint32_t n_prev_poses, float* out);
+int glz_renderer_reproject_posed(glz_renderer*, const glz_previous_state*, const glz_pose* prev_poses, uint32_t n_prev_poses, const float* prev_color,
+                                 const float* prev_aov0, const float* prev_aov1, const glz_reproject_params* params_or_null, float* out);
 
 /* Multi-GPU (one process per GPU): this renderer owns the 64x64-pixel tiles t with
  * t % world == rank; other pixels stay zero.  The exchange of the HDR accumulator itself is done
@@ -737,6 +795,9 @@ int glz_debug_reproject(glz_instance*, uint32_t w, uint32_t h, const float* moti
 int glz_debug_motion_timing(glz_renderer*, const glz_camera* prev_camera, const glz_transform* prev_transforms, uint32_t n_prev_transforms, float* kernel_ms_out);
 /* the same for glz_renderer_read_motion_from: k_motion_deform alone when the state has vertices */
 int glz_debug_motion_timing_from(glz_renderer*, const glz_previous_state*, float* kernel_ms_out);
+/* k_skin alone on one skin of the scene, into a scratch buffer (the scene is untouched): the device-event time of `reps` launches after
+ * one that is not timed, divided by reps.  The pose is checked as glz_renderer_pose_skins checks it. */
+int glz_debug_skin_timing(glz_renderer*, const glz_pose* pose, uint32_t reps, float* kernel_ms_out);
 int glz_debug_tonemap(glz_instance*, const float* rgba32f, uint64_t n_pixels, uint8_t* rgba8_out);
 /* The kernels' texture sampler on n coordinates uv2[2i], uv2[2i+1] of a scene texture, RGBA out: level 0 (texture2d) when
  * footprint4 is NULL, else the level of detail of footprint4[4i..4i+3] = (lod_base, du, dv, taps in 1..16) (texture2d_lod, after
@@ -830,6 +891,11 @@ int glz_host_project_points(const glz_camera* camera, uint32_t width, uint32_t h
 int glz_host_reproject(uint32_t w, uint32_t h, const float* motion, const float* prev_color, const float* prev_aov0, const float* prev_aov1,
                        const glz_reproject_params* params_or_null, float* out);
 int64_t glz_host_instance_boxes(const glz_scene_desc* desc, uint64_t budget, float* lo4, float* hi4);
+/* THE SKINNING RULE (glz_renderer_add_skin) on host arrays, no device: the reference k_skin is compared with bit for bit.  bind / out: n
+ * vertices (out may be bind itself); joints, weights: 4 per vertex; bones: n_bones matrices.  GLZ_E_ARG: a null pointer with n > 0,
+ * n_bones == 0, a joint >= n_bones. */
+int glz_host_skin(const glz_vertex* bind, const uint16_t* joints, const float* weights, uint64_t n, const glz_transform* bones, uint32_t n_bones,
+                  glz_vertex* out);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // AddressSanitizer / UBSan run of the host-only parts of libglaze_hip (the GPU parts cannot run under sanitizers on
-// this pool): .glaze reader and writer with their own xz / PNG / JPEG codecs, the OBJ converter, the host SAH builder and the host
-// rule of the instance boxes.
+// this pool): .glaze reader and writer with their own xz / PNG / JPEG codecs, the OBJ converter, the host SAH builder, the host
+// rule of the instance boxes and the skinning reference.
 // Built and run by tools/sanitize/run.sh; exits non-zero on the first failure (the sanitizers abort on their findings).
 #include <cmath>
 #include <cstdio>
@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "parser.h"
 #include "serializer.h"
+#include "skin.h"
 
 using namespace glz;
 
@@ -250,6 +251,22 @@ int main(int argc, char** argv) {
     std::vector<float4> lo, hi;
     Error e2;
     REQUIRE(!host_instance_boxes_of(bad, kExactBoxBudget, lo, hi, e2) && e2.code == GLZ_E_INVALID_DATA);
+  }
+  // 8. the skinning reference (skin_host.cpp) on the fixture's vertices: every joint at the table's ends, `out` aliasing `bind`, one vertex, none
+  {
+    const uint32_t n_bones = 5;
+    std::vector<glz_transform> bones(n_bones, identity_transform());
+    for (uint32_t b = 0; b < n_bones; ++b) bones[b].m[12] = (float)b;
+    std::vector<glz_vertex> bind = sd.vertices, out(bind.size());
+    std::vector<uint16_t> joints(4 * bind.size());
+    std::vector<float> weights(4 * bind.size(), 0.25f);
+    for (size_t i = 0; i < joints.size(); ++i) joints[i] = (uint16_t)((i % 2) ? n_bones - 1 : 0);
+    post::host_skin(bind.data(), joints.data(), weights.data(), bind.size(), bones.data(), n_bones, out.data());
+    for (size_t i = 0; i < bind.size(); i += 997) REQUIRE(out[i].vv[0] == bind[i].vv[0] + 2.0f && out[i].vv[1] == bind[i].vv[1] && out[i].vt[0] == bind[i].vt[0]);
+    post::host_skin(bind.data(), joints.data(), weights.data(), bind.size(), bones.data(), n_bones, bind.data());   // in place
+    REQUIRE(bind[0].vv[0] == out[0].vv[0] && bind.back().vv[0] == out.back().vv[0]);
+    post::host_skin(out.data() + out.size() - 1, joints.data(), weights.data(), 1, bones.data(), n_bones, out.data() + out.size() - 1);
+    post::host_skin(nullptr, nullptr, nullptr, 0, bones.data(), n_bones, nullptr);
   }
   printf("host sanitize: ok\n");
   return 0;
