@@ -313,6 +313,7 @@ PROTOTYPES = {
     "glz_renderer_guide_mode": (C.c_int, [_P, _P]),
     "glz_debug_guide_chain": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
     "glz_host_traversal_offsets_fit": (C.c_int, [C.c_uint64] * 6),
+    "glz_host_sky_row_pairs": (C.c_int, [_P, _P, C.c_uint64, _P]),
 }
 
 _LIB = None

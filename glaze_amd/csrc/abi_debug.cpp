@@ -663,6 +663,11 @@ int glz_host_srgb8_thresholds(float thresholds_out[256]) {
   host::srgb8_thresholds(thresholds_out);
   return GLZ_OK;
 }
+int glz_host_sky_row_pairs(const float* marginal_values, const float* conditional_integrals, uint64_t n, float* pairs_out) {
+  if (n != 0 && (!marginal_values || !conditional_integrals || !pairs_out)) return fail(GLZ_E_ARG, "glz_host_sky_row_pairs: null array");
+  sky_row_pairs(marginal_values, conditional_integrals, (size_t)n, pairs_out);
+  return GLZ_OK;
+}
 
 }  // extern "C"
 

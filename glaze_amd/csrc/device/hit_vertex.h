@@ -56,7 +56,7 @@ __device__ __forceinline__ HitVertex load_hit_vertex(const DeviceScene& S, float
   v.uv = vec2{(r.va1.z * b0 + r.vb1.z * b1) + r.vc1.z * b2, (r.va1.w * b0 + r.vb1.w * b1) + r.vc1.w * b2};
   v.ng = mk3(r.dn.x, r.dn.y, r.dn.z), v.dpdu = mk3(r.du.x, r.du.y, r.du.z);
   v.ns = (mk3(r.va0.w, r.va1.x, r.va1.y) * b0 + mk3(r.vb0.w, r.vb1.x, r.vb1.y) * b1) + mk3(r.vc0.w, r.vc1.x, r.vc1.y) * b2;
-  v.mat = load_material(&S.materials[ids.material_id]);
+  v.mat = load_material(S, ids.material_id);
   v.xf_bits = ids.xf;
   return v;
 }

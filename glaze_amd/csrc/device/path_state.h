@@ -33,6 +33,18 @@ __device__ __forceinline__ PixelId pixel_of(const TileMap& m, uint32_t lid) {
   p.active = lid < m.n_local_pixels && p.x < m.width && p.y < m.height;
   return p;
 }
+// pixel_of(m, block * 256 + p) for p < 256: the 256 pixels share a tile, so the tile's place in the frame -- the division -- is computed
+// from the block number alone, once per wave on the scalar unit, whichever pixel of the block a thread then turns to
+__device__ __forceinline__ PixelId pixel_of_block(const TileMap& m, uint32_t block, uint32_t p) {
+  const uint32_t gtile = (block >> 4) * m.world + m.rank;
+  const uint32_t tx = gtile % m.tiles_x, ty = gtile / m.tiles_x;
+  const uint32_t lane = p & 63u, sub = (block & 15u) * 4u + (p >> 6);
+  PixelId px;
+  px.x = tx * 64u + (sub & 7u) * 8u + (lane & 7u);
+  px.y = ty * 64u + (sub >> 3) * 8u + (lane >> 3);
+  px.active = block * 256u + p < m.n_local_pixels && px.x < m.width && px.y < m.height;
+  return px;
+}
 
 // ---------------------------------------------------------------------------------------------
 // closest-hit phase of k_trace: path_trace.rgen:143-169

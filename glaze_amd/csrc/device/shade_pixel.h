@@ -34,6 +34,12 @@ struct SharedQueue {   // k_shade: the rank's sharded queue in HBM, drained by t
 #else
 #define GLZ_SHADE_STAMP(k) do { } while (0)
 #endif
+__device__ __forceinline__ uint32_t pixel_rng(const FrameData& F, PixelId px) {
+  return pcg(__float_as_uint((float)F.seed) ^ pcg(__float_as_uint((float)px.x) ^ pcg(__float_as_uint((float)px.y))));
+}
+__device__ __forceinline__ uint32_t light_pick(const FrameData& F, uint32_t& rng) {
+  return (uint32_t)gl_min(rand01(rng) * (float)F.lights_no, (float)(F.lights_no - 1u));
+}
 struct DirectState {
   const LaunchArgs& A;
   static constexpr bool kDeferSkyTexel = false;   // (sample_light: k_path has no registers for the fetch code a second time)
@@ -42,6 +48,10 @@ struct DirectState {
   __device__ __forceinline__ void ray_d(uint32_t lid, float4 v) { A.st.ray_d[lid] = v; }
   __device__ __forceinline__ void imp(int q, uint32_t lid, float4 v) { A.st.imp[q][lid] = v; }
   __device__ __forceinline__ float4 read_imp(int q, uint32_t lid) const { return A.st.imp[q][lid]; }
+  __device__ __forceinline__ float4 reset_origin(uint32_t, float4 ro) const { return ro; }   // (the caller read the whole of ray_o, a line per wave)
+  // the pixel's RNG at the start of the launch (path_trace.rgen:143, Q11) and the light pick of direct_light() (:84-117), made here
+  __device__ __forceinline__ uint32_t seed_rng(const FrameData& F, PixelId px) const { return pixel_rng(F, px); }
+  __device__ __forceinline__ uint32_t pick_light(const FrameData& F, uint32_t& rng) const { return light_pick(F, rng); }
   __device__ __forceinline__ void accumulate(uint32_t lid, vec3 c, bool add, bool update, float mark) { accumulate_shaded(A, lid, c, add && isfinite(c.x + c.y + c.z), update, mark); }
 };
 struct StagedState {
@@ -71,6 +81,17 @@ struct StagedState {
     const u32x4 v = lds_imp[q * kShadeBlockPixels];
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
   }
+  // The origin an ended path restarts from when the camera ray is not made here (no FrameData::pregen): the only reader of ray_o.xyz in
+  // k_shade, so the only place that loads it -- the bounce, ray_o.w, reaches shade_pixel through LDS from the prologue's read in pixel order.
+  __device__ __forceinline__ float4 reset_origin(uint32_t lid, float4) const { return A->st.ray_o[lid]; }
+  // k_shade's prologue made both for the sort key (the hash of the seed: eight v_mul_lo_u32 with the pick) and left them in LDS for the
+  // thread at the pixel's sorted slot: {the RNG state, the light index}.  The state is the one the draws of shade_pixel_body continue
+  // from -- after the pick where the material takes one, the seed's hash where it does not -- so the sequence is DirectState's.
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  typedef const __attribute__((address_space(3))) u32x2* LdsPickPtr;
+  LdsPickPtr lds_pick = nullptr;   // &s_pick[pixel's index in the block]
+  __device__ __forceinline__ uint32_t seed_rng(const FrameData&, PixelId) const { return (*lds_pick).x; }
+  __device__ __forceinline__ uint32_t pick_light(const FrameData&, uint32_t&) const { return (*lds_pick).y; }
   __device__ __forceinline__ void accumulate(uint32_t lid, vec3 cc, bool add, bool update, float mark) { accumulate_shaded(*A, lid, cc, add && isfinite(cc.x + cc.y + cc.z), update, mark); }
 };
 // Returns 0 when the pixel's next path state has been written (or, with the direct-light integrator, is not needed), 1 / 2 when the path
@@ -179,7 +200,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
   finish_hit_vertex<true>(S, hv, fp);
   const vec3 point = hv.point, ns = hv.ns;
   // ---- raygen continues (path_trace.rgen:180-237) ----
-  uint32_t rng = pcg(__float_as_uint((float)F.seed) ^ pcg(__float_as_uint((float)px.x) ^ pcg(__float_as_uint((float)px.y))));   // :143, Q11
+  uint32_t rng = out.seed_rng(F, px);   // :143, Q11
   const SurfacePoint P = hit_surface_point(S, hv, direction, fp);
   GLZ_SHADE_STAMP(1);   // normal map, transform, frame, the material's textures
   float spec_flag;
@@ -187,7 +208,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
   bool have_lum = false;
   if (mat.is_specular == 0) {
     // direct_light(), :84-117
-    const uint32_t li = (uint32_t)gl_min(rand01(rng) * (float)F.lights_no, (float)(F.lights_no - 1u));
+    const uint32_t li = out.pick_light(F, rng);
     vec3 xi;
     xi.x = rand01(rng); xi.y = rand01(rng); xi.z = rand01(rng);
     LightSample ls;
@@ -299,36 +320,41 @@ __device__ __forceinline__ void shade_pixel(const LaunchArgs& A, const DeviceSce
       out.ray_o(lid, make_float4(co.x, co.y, co.z, __uint_as_float(kPregenBounceBits)));
       out.ray_d(lid, make_float4(cd.x, cd.y, cd.z, end_w));
     } else {
-      out.ray_o(lid, make_float4(ro.x, ro.y, ro.z, 0.0f));
+      const float4 o = out.reset_origin(lid, ro);
+      out.ray_o(lid, make_float4(o.x, o.y, o.z, 0.0f));
       if (ended == 2) out.ray_d(lid, make_float4(rd.x, rd.y, rd.z, end_w));
     }
   }
 }
 
-// The scene tables every hit walks through -- [RTMaterial x n_materials | RTLight x n_rt_lights | TexDesc x n_textures] -- as k_shade and
-// k_path stage them in LDS when they fit.  The two capacities differ: k_shade's pool also holds the pixels' importance and the sky's
+// The scene tables every hit walks through -- [MatCompact x n_materials | MetalSpectra x n_metal_spectra | RTLight x n_rt_lights |
+// TexDesc x n_textures] -- as k_shade and k_path stage them in LDS when they fit.  The materials' metal spectra (128 of an RTMaterial's
+// 208 bytes) are there once per distinct pair, not once per material.  The two capacities differ: k_shade's pool also holds the pixels' importance and the sky's
 // marginal cdf, so its table area is the smaller; k_path takes its copy from dynamic LDS, which it asks for only when the tables fit,
 // so a scene with small tables buys residency.
-constexpr uint32_t kShadeLdsTableBytes = 8192;   // k_shade (38 materials; larger tables are read from memory)
-constexpr uint32_t kPathTableBytes = 16384;      // k_path (78 materials alone would fill it)
-static_assert(sizeof(RTMaterial) % 16 == 0 && sizeof(RTLight) % 16 == 0 && sizeof(TexDesc) % 16 == 0, "the tables are copied in 16-byte pieces");
+constexpr uint32_t kShadeLdsTableBytes = 8192;   // k_shade (about 90 materials of one metal; larger tables are read from memory)
+constexpr uint32_t kPathTableBytes = 16384;      // k_path (about 190 materials)
+static_assert(sizeof(MatCompact) % 16 == 0 && sizeof(MetalSpectra) % 16 == 0 && sizeof(RTLight) % 16 == 0 && sizeof(TexDesc) % 16 == 0, "the tables are copied in 16-byte pieces");
 struct SceneTables {
-  uint32_t qm, ql, qt;   // the three tables' sizes in 16-byte pieces
+  uint32_t qm, qs, ql, qt;   // the four tables' sizes in 16-byte pieces
   __host__ __device__ explicit SceneTables(const DeviceScene& s)
-      : qm(s.n_materials * (uint32_t)(sizeof(RTMaterial) / 16)), ql(s.n_rt_lights * (uint32_t)(sizeof(RTLight) / 16)), qt(s.n_textures * (uint32_t)(sizeof(TexDesc) / 16)) {}
-  __host__ __device__ uint32_t bytes() const { return (qm + ql + qt) * 16u; }
+      : qm(s.n_materials * (uint32_t)(sizeof(MatCompact) / 16)), qs(s.n_metal_spectra * (uint32_t)(sizeof(MetalSpectra) / 16)), ql(s.n_rt_lights * (uint32_t)(sizeof(RTLight) / 16)), qt(s.n_textures * (uint32_t)(sizeof(TexDesc) / 16)) {}
+  __host__ __device__ uint32_t bytes() const { return (qm + qs + ql + qt) * 16u; }
   // the cooperative copy by a block of `block` threads (the caller's barrier ends it) ...
   __device__ __forceinline__ void stage(const DeviceScene& s, uint4* dst, uint32_t block) const {
-    const uint4* gm = reinterpret_cast<const uint4*>(s.materials);
+    const uint4* gm = reinterpret_cast<const uint4*>(s.mat_compact);
+    const uint4* gs = reinterpret_cast<const uint4*>(s.metal_spectra);
     const uint4* gl = reinterpret_cast<const uint4*>(s.lights);
     const uint4* gt = reinterpret_cast<const uint4*>(s.tex_desc);
-    for (uint32_t i = threadIdx.x; i < qm + ql + qt; i += block) dst[i] = i < qm ? gm[i] : (i < qm + ql ? gl[i - qm] : gt[i - qm - ql]);
+    const uint32_t es = qm + qs, el = es + ql;
+    for (uint32_t i = threadIdx.x; i < el + qt; i += block) dst[i] = i < qm ? gm[i] : (i < es ? gs[i - qm] : (i < el ? gl[i - es] : gt[i - el]));
   }
-  // ... and the three table pointers of S onto the copy
+  // ... and the four table pointers of S onto the copy
   __device__ __forceinline__ void use(DeviceScene& S, const uint4* copy) const {
-    S.materials = reinterpret_cast<const RTMaterial*>(copy);
-    S.lights = reinterpret_cast<const RTLight*>(copy + qm);
-    S.tex_desc = reinterpret_cast<const TexDesc*>(copy + qm + ql);
+    S.mat_compact = reinterpret_cast<const MatCompact*>(copy);
+    S.metal_spectra = reinterpret_cast<const MetalSpectra*>(copy + qm);
+    S.lights = reinterpret_cast<const RTLight*>(copy + qm + qs);
+    S.tex_desc = reinterpret_cast<const TexDesc*>(copy + qm + qs + ql);
   }
 };
 

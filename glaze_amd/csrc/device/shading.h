@@ -367,24 +367,24 @@ GLZ_D vec2 anisotropic_alpha(float a, float anis) { return vec2{a * (1.0f + anis
 // BSDFs.  One switch on RTMaterial::bsdf_index replaces the SBT callable dispatch
 // (executeCallableEXT(material.bsdf_index [+1]), path_trace.rgen:103, :218).
 // ---------------------------------------------------------------------------------------------
-// The scalar part of an RTMaterial, fetched with four dwordx4 loads (bytes 0..15 and 160..207 of the 208-byte record)
-// instead of one load per field; the two 64-byte metal spectra stay in memory and are read only by conductor lobes.
+// The scalar part of a material, fetched from its MatCompact record with four 16-byte loads (the record without emissive_col) instead of
+// one load per field; the two 64-byte metal spectra are read only by conductor lobes, from the table of the scene's distinct pairs.
 struct MatScalars {
   float diffuse_mul[3];
   uint32_t diffuse, roughness, metalness, opacity, normal, bsdf_index;
   float roughness_mul, metalness_mul, anisotropy, ior_dielectric;
   uint32_t is_specular;
-  const RTMaterial* spectra;   // metal_ior / metal_fresnel
+  const MetalSpectra* spectra;   // metal_ior / metal_fresnel
 };
-GLZ_D MatScalars load_material(const RTMaterial* m) {
-  const float4* q = reinterpret_cast<const float4*>(m);
-  const float4 a = q[0], b = q[10], c = q[11], d = q[12];
+GLZ_D MatScalars load_material(const DeviceScene& S, uint32_t id) {
+  const float4* q = reinterpret_cast<const float4*>(&S.mat_compact[id]);
+  const float4 a = q[0], b = q[2], c = q[3], d = q[4];
   MatScalars r;
   r.diffuse_mul[0] = a.x; r.diffuse_mul[1] = a.y; r.diffuse_mul[2] = a.z;
   r.diffuse = __float_as_uint(b.x); r.roughness = __float_as_uint(b.y); r.metalness = __float_as_uint(b.z); r.opacity = __float_as_uint(b.w);
   r.normal = __float_as_uint(c.x); r.bsdf_index = __float_as_uint(c.y); r.roughness_mul = c.z; r.metalness_mul = c.w;
   r.anisotropy = d.x; r.ior_dielectric = d.y; r.is_specular = __float_as_uint(d.z);
-  r.spectra = m;
+  r.spectra = &S.metal_spectra[__float_as_uint(a.w)];
   return r;
 }
 
@@ -466,7 +466,7 @@ GLZ_D float bsdf_eval(const DeviceScene& S, const SurfacePoint& P, vec3 wiW, flo
   if (kind == kBsdfMetal) {   // mat_metal_value.rcall:19-44
     vec3 wh = normalize3(wo + wi);
     if (!(wo.z * wi.z > 0.0f)) return 0.0f;
-    Spec F = fresnel_conductor(dot3(wi, wh), m.spectra->metal_ior, m.spectra->metal_fresnel);
+    Spec F = fresnel_conductor(dot3(wi, wh), m.spectra->ior, m.spectra->fresnel);
     vec2 a = anisotropic_alpha(P.rough_tex * m.roughness_mul, m.anisotropy);
     float d = ggx_d(wh, a);
     float g = ggx_g(wo, wi, a);
@@ -510,7 +510,7 @@ GLZ_D float bsdf_eval(const DeviceScene& S, const SurfacePoint& P, vec3 wiW, flo
     dielectric_etas(m, wo.z, etai, etat);
     Lobe L = reflect_lobe(wo, wi, wh, a);
     float fd = fresnel_dielectric(L.costi, etai, etat);
-    Spec fc = fresnel_conductor(L.costi, m.spectra->metal_ior, m.spectra->metal_fresnel);
+    Spec fc = fresnel_conductor(L.costi, m.spectra->ior, m.spectra->fresnel);
     float term = L.d * L.g / (4.0f * L.cwo * L.cwi);
     GLZ_BINS value.w[i] = gl_mix(fd, fc.w[i], metalness) * term;
     return check_nan(same * 0.5f * L.pdf);
@@ -542,7 +542,7 @@ GLZ_D float bsdf_sample(const DeviceScene& S, const SurfacePoint& P, vec3 xi, Sp
     return fabsf(wi.z) * kInvPi;
   }
   if (kind == kBsdfMirror) {   // mat_mirror_sample_value.rcall:16-34
-    Spec F = fresnel_conductor(wo.z, m.spectra->metal_ior, m.spectra->metal_fresnel);
+    Spec F = fresnel_conductor(wo.z, m.spectra->ior, m.spectra->fresnel);
     wiW = normalize3(to_world(mk3(-wo.x, -wo.y, wo.z), P.frame));
     value = spec_div(F, fabsf(wo.z));
     return 1.0f;
@@ -576,7 +576,7 @@ GLZ_D float bsdf_sample(const DeviceScene& S, const SurfacePoint& P, vec3 xi, Sp
     float d = ggx_d(wh, a);
     float g = ggx_g(wo, wi, a);
     float gp = ggx_pdf(d, a, wo, wh);
-    Spec F = fresnel_conductor(dot3(wi, wh), m.spectra->metal_ior, m.spectra->metal_fresnel);
+    Spec F = fresnel_conductor(dot3(wi, wh), m.spectra->ior, m.spectra->fresnel);
     float term = d * g / (4.0f * fabsf(wo.z) * fabsf(wi.z));
     float pdf = gp / (4.0f * dot3(wo, wh));
     value = spec_scale(F, term);
@@ -625,7 +625,7 @@ GLZ_D float bsdf_sample(const DeviceScene& S, const SurfacePoint& P, vec3 xi, Sp
     wi = -normalize3(gl_reflect(wo, wh));
     Lobe L = reflect_lobe(wo, wi, wh, a);
     float fd = fresnel_dielectric(L.costi, etai, etat);
-    Spec fc = fresnel_conductor(L.costi, m.spectra->metal_ior, m.spectra->metal_fresnel);
+    Spec fc = fresnel_conductor(L.costi, m.spectra->ior, m.spectra->fresnel);
     float term = L.d * L.g / (4.0f * L.cwo * L.cwi);
     GLZ_BINS value.w[i] = gl_mix(fd, fc.w[i], metalness) * term;
     pdf = check_nan(0.5f * L.pdf);
@@ -726,7 +726,7 @@ GLZ_D void sample_light(const DeviceScene& S, uint32_t light_index, vec3 p, vec3
     out.wiW = normalize3(p - rp);   // points away from the light (Q2)
     float d2 = sq_dist(rp, p);
     out.distance = sqrtf(d2);
-    const RTMaterial* m = &S.materials[in.material_id];
+    const MatCompact* m = &S.mat_compact[in.material_id];
     out.rgb = mk3(m->diffuse_mul[0], m->diffuse_mul[1], m->diffuse_mul[2]);
     out.k = d2 / L->intensity;
     out.pdf = (1.0f / (float)ntri) * (1.0f / area);
@@ -734,20 +734,20 @@ GLZ_D void sample_light(const DeviceScene& S, uint32_t light_index, vec3 p, vec3
   }
   // Sky: light_sky_sample_visible.rcall:100-135
   uint32_t row;
-  const float* marg = S.sky_marginal;
-  const float* cdf = S.sky_cdf;   // (k_shade: in LDS -- the search is ten dependent reads; the two values read once below come from memory)
+  const float* cdf = S.sky_cdf;   // (k_shade: in LDS -- the search is ten dependent reads; the row's two values read once below come from memory, in one load)
   float v = sample_cdf(xi.y, (int)S.sky_header.marginal_cdf_count, [&](int i) { return cdf[i]; }, row);
-  float v_pdf = marg[S.sky_header.marginal_cdf_count + row] / S.sky_header.marginal_integral;
+  const float2 of_row = S.sky_rows[row];   // (sky_marginal[marginal_cdf_count + row], sky_marginal[conditional_integral_offset + row])
+  float v_pdf = of_row.x / S.sky_header.marginal_integral;
   // The conditional lookups hand integer texel coordinates to a normalised REPEAT/NEAREST sampler: every
   // fetch lands on texel (0,0) of the image (Q3).
   // sample_cdf over that constant, written out: the search ends at `size` when cdf00 <= xi and at 0 otherwise, cur == next == cdf00,
   // so next - cur > 0 never holds and du stays xi - cdf00
-  const float cdf00 = S.sky_cond_cdf[0];
+  const float cdf00 = S.sky_header.cond_cdf00;   // sky_cond_cdf[0], from the kernel arguments
   const int cond_size = (int)S.sky_header.conditional_cdf_count;
   int cond_off = (cond_size > 0 && cdf00 <= xi.x ? cond_size : 0) - 1;
   cond_off = cond_off < 0 ? 0 : (cond_off > cond_size - 2 ? cond_size - 2 : cond_off);
   float u = ((float)cond_off + (xi.x - cdf00)) / (float)cond_size;
-  float u_pdf = S.sky_cond_values[0] / marg[S.sky_header.conditional_integral_offset + row];
+  float u_pdf = S.sky_header.cond_value00 / of_row.y;   // sky_cond_values[0]
   float pdf = u_pdf * v_pdf;
   float theta = v * kPi;
   float sint = glz_sinf(theta);

@@ -68,6 +68,47 @@ struct alignas(16) RTMaterial {
   uint32_t is_emissive;
 };
 static_assert(sizeof(RTMaterial) == 208, "RTMaterial is 208 bytes");
+// The two spectra of an RTMaterial on their own: there are as many different pairs in a scene as it uses metals (29 at the most,
+// include/glz_tables.h; most scenes use one), whatever the number of materials.
+struct alignas(16) MetalSpectra {
+  Spectrum16 ior;       // RTMaterial::metal_ior
+  Spectrum16 fresnel;   // RTMaterial::metal_fresnel
+};
+static_assert(sizeof(MetalSpectra) == 128, "MetalSpectra is 8 x 16 bytes");
+// What the shading kernels read of a material at every hit: the RTMaterial without its two metal spectra (bytes 0..31 and 160..207 of
+// the record, field for field), and in place of diffuse_mul's unread fourth component the index of the material's spectra in the table
+// of the scene's DISTINCT pairs (DeviceScene::metal_spectra).  Both are derived arrays, rebuilt with the RTMaterial array
+// (ShadingTables::build_materials); k_shade and k_path stage THESE tables in LDS.  The spectra are 128 of an RTMaterial's 208 bytes and
+// only conductor lobes read them; left in the RTMaterial array in memory they cost those lobes sixteen 16-byte loads per pixel
+// (measured: EXPERIMENTS.md).
+struct alignas(16) MatCompact {
+  float diffuse_mul[3];
+  uint32_t spectra;
+  float emissive_col[4];
+  uint32_t diffuse;
+  uint32_t roughness;
+  uint32_t metalness;
+  uint32_t opacity;
+  uint32_t normal;
+  uint32_t bsdf_index;
+  float roughness_mul;
+  float metalness_mul;
+  float anisotropy;
+  float ior_dielectric;
+  uint32_t is_specular;
+  uint32_t is_emissive;
+};
+static_assert(sizeof(MatCompact) == 80, "MatCompact is 5 x 16 bytes");
+inline MatCompact compact_material(const RTMaterial& m, uint32_t spectra) {
+  MatCompact c;
+  for (int i = 0; i < 3; ++i) c.diffuse_mul[i] = m.diffuse_mul[i];
+  for (int i = 0; i < 4; ++i) c.emissive_col[i] = m.emissive_col[i];
+  c.spectra = spectra;
+  c.diffuse = m.diffuse; c.roughness = m.roughness; c.metalness = m.metalness; c.opacity = m.opacity;
+  c.normal = m.normal; c.bsdf_index = m.bsdf_index; c.roughness_mul = m.roughness_mul; c.metalness_mul = m.metalness_mul;
+  c.anisotropy = m.anisotropy; c.ior_dielectric = m.ior_dielectric; c.is_specular = m.is_specular; c.is_emissive = m.is_emissive;
+  return c;
+}
 
 // raytrace_structures.rs:66-76
 struct alignas(16) RTLight {
@@ -212,6 +253,10 @@ struct SkyHeader {
   uint32_t conditional_integral_offset;
   uint32_t conditional_cdf_count;
   float marginal_integral;
+  // Not in the reference's buffer: the two words of the conditional tables every sky sample reads -- sky_cond_cdf[0] and sky_cond_values[0],
+  // the texel (0, 0) all conditional lookups land on (Q3) -- copied here when the tables are built, so that they travel in the kernel arguments
+  float cond_cdf00;
+  float cond_value00;
 };
 
 // Everything the kernels need about a scene (device pointers).
@@ -219,7 +264,9 @@ struct DeviceScene {
   const float4* vertices;          // 2 x float4 per vertex (VertexPacked, raytrace_commons.glsl:11-14)
   const uint32_t* indices;
   const RTInstance* instances;
-  const RTMaterial* materials;
+  const RTMaterial* materials;     // the whole records, in memory: alpha tests, the hierarchy build, the debug readers
+  const MatCompact* mat_compact;   // the same materials without the spectra: what shading reads at every hit (k_shade, k_path: their LDS copy)
+  const MetalSpectra* metal_spectra;   // the distinct spectra pairs of `materials`, MatCompact::spectra indexes them (conductor lobes; staged with mat_compact)
   const RTLight* lights;
   const TransformPair* transforms;
   const float4* derivatives;       // 3 x float4 per object triangle (normal, dpdu, dpdv)
@@ -255,12 +302,14 @@ struct DeviceScene {
   uint32_t n_world_tris;
   uint32_t n_textures;
   uint32_t n_materials;            // RTMaterial records
+  uint32_t n_metal_spectra;        // MetalSpectra records
   uint32_t n_rt_lights;            // RTLight records (area lights expand to one per instance)
   // sky
   RTSky sky;
   SkyHeader sky_header;
   const float* sky_marginal;       // cdf (H+1) | values (H) | conditional integrals (H)
   const float* sky_cdf;            // the H + 1 cdf entries the row search walks: sky_marginal, or k_shade's LDS copy of them
+  const float2* sky_rows;          // per row (marginal value, conditional integral): the two entries of sky_marginal a sample reads once its row is found, side by side
   const float* sky_cond_values;    // W x H
   const float* sky_cond_cdf;       // (W+1) x H
   // counting builds only (null otherwise; the host never sets it): the THREAD's tallies {texture fetches that read memory, their texel

@@ -122,7 +122,7 @@ __device__ __forceinline__ SurfacePoint debug_surface_point(const DeviceScene& S
   P.frame.s = frame9 ? mk3(frame9[0], frame9[1], frame9[2]) : mk3(1.0f, 0.0f, 0.0f);
   P.frame.t = frame9 ? mk3(frame9[3], frame9[4], frame9[5]) : mk3(0.0f, 1.0f, 0.0f);
   P.frame.n = frame9 ? mk3(frame9[6], frame9[7], frame9[8]) : mk3(0.0f, 0.0f, 1.0f);
-  P.mat = load_material(&S.materials[material]);
+  P.mat = load_material(S, material);
   fetch_material_textures(S, P, TexFootprint{kNoLod, 0.0f, 0.0f, 1u});
   return P;
 }

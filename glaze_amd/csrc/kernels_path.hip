@@ -131,7 +131,8 @@ __device__ __forceinline__ uint32_t path_shade(uint32_t g, uint32_t n_groups, ui
   DeviceScene S = A.scene;
   S.tex_counter = nullptr;   // k_path is never a counting pass: the checks fold away
   S.srgb_lut = S_lds.srgb_lut;
-  S.materials = S_lds.materials;
+  S.mat_compact = S_lds.mat_compact;
+  S.metal_spectra = S_lds.metal_spectra;
   S.lights = S_lds.lights;
   S.tex_desc = S_lds.tex_desc;
   const FrameData F = launch_frame(A, *(const PathBatch*)(reread_kernarg() + kPathBatchOffset), L);

@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   // The kernel is bound by the memory system's random-access rate (16 extra scattered loads per pixel cost +27 %, 200 extra
   // VALU instructions nothing; 1 / 2 / 3 / 4 waves per SIMD take 0.76 / 0.45 / 0.36 / 0.35 ms), so the two small tables every texture fetch /
   // sky sample walks are staged in LDS once per block: the sRGB decode LUT (12 lookups per bilinear fetch) and the sky marginal CDF (an 11-step dependent search).
-  __shared__ float s_lut[256];
+  __shared__ alignas(16) float s_lut[256];
   // One pool: [the importance the block's 256 pixels arrived with, 4 x 4 KB, read in whole lines by the prologue | the sky's marginal cdf |
   // the scene tables] while the block shades; after its last barrier the first 24 KB are the staging area of the state the pixels leave
   // (StagedState): 6 x 16 bytes per pixel, written where the pixel lives instead of where its thread sat.
@@ -71,10 +71,16 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   __shared__ uint32_t s_bin[kShadeWavesPerBlock * 64];   // [wave][key] counts, then start offsets
   __shared__ uint16_t s_perm[kShadeBlock];
   __shared__ float4 s_hit[kShadeBlock];   // hit records read by the regrouping prologue, handed to the thread that shades the pixel
+  __shared__ float s_bounce[kShadeBlock];   // ray_o.w, the same way: all k_shade reads of ray_o unless a path restarts without pregen (StagedState::reset_origin)
+  __shared__ uint2 s_pick[kShadeBlock];     // what the prologue computed for the sort key and shade_pixel needs again: {RNG state, light index} (StagedState::lds_pick)
+  static_assert(kShadeBlock == 256, "pixel_of_block");
   const uint32_t n_sky = A.scene.sky_header.marginal_cdf_count;
-  if (threadIdx.x < 256u) s_lut[threadIdx.x] = A.scene.srgb_lut[threadIdx.x];
+  // both copies in 16-byte pieces, as the tables: the block pays per request, and these are a quarter of the 4-byte ones (the LUT is one
+  // wave's load instead of four waves', a sky of 1 024 rows two loads per thread instead of five).  The cdf's last piece reads up to three
+  // floats past it -- marginal values, which follow it in the same array (3 H + 1 floats; the pieces cover at most H + 4 of them, and exactly 4 when H = 1).
+  if (threadIdx.x < 64u) reinterpret_cast<float4*>(s_lut)[threadIdx.x] = reinterpret_cast<const float4*>(A.scene.srgb_lut)[threadIdx.x];
   if (SKY)
-    for (uint32_t i = threadIdx.x; i < n_sky; i += kShadeBlock) s_sky[i] = A.scene.sky_marginal[i];
+    for (uint32_t i = threadIdx.x; i < (n_sky + 3u) / 4u; i += kShadeBlock) s_pool[kShadeBlock * 4 + i] = reinterpret_cast<const uint4*>(A.scene.sky_marginal)[i];
   s_bin[threadIdx.x] = 0;
   const SceneTables tables(A.scene);
   if (TABLES) tables.stage(A.scene, s_tables, kShadeBlock);
@@ -85,10 +91,12 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   S.tex_counter = COUNT ? tex_tally : nullptr;
   S.srgb_lut = s_lut;
   S.sky_cdf = SKY ? s_sky : in_memory(S.sky_cdf);
+  S.sky_rows = in_memory(S.sky_rows);
   if (TABLES) {
     tables.use(S, s_tables);
   } else {
-    S.materials = in_memory(S.materials);
+    S.mat_compact = in_memory(S.mat_compact);
+    S.metal_spectra = in_memory(S.metal_spectra);
     S.lights = in_memory(S.lights);
     S.tex_desc = in_memory(S.tex_desc);
   }
@@ -103,22 +111,24 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   uint32_t key = 63u;   // pixels outside the image sort last
   {
     const uint32_t lid0 = blockIdx.x * kShadeBlock + threadIdx.x;
-    const PixelId px0 = pixel_of(A.map, lid0);
+    const PixelId px0 = pixel_of_block(A.map, blockIdx.x, threadIdx.x);
     if (px0.active) {
       const float4 h0 = A.st.hit[lid0];
 #pragma unroll
       for (int q = 0; q < 4; ++q) s_imp[q * kShadeBlock + threadIdx.x] = *reinterpret_cast<const uint4*>(&A.st.imp[q][lid0]);   // whole lines, pixel order (a fresh path's is never read)
       s_hit[threadIdx.x] = h0;   // the thread at this pixel's sorted slot reads it back after the barriers below: one dependent global load less
+      s_bounce[threadIdx.x] = A.st.ray_o[lid0].w;   // (4 of the 16 bytes, in pixel order; the sorted thread asked for all 16, scattered)
       const uint32_t leaf0 = __float_as_uint(h0.w);
       key = 0u;
       if (leaf0 != 0xFFFFFFFFu) {
-        const RTMaterial* m0 = &S.materials[S.two_level ? S.instances[A.st.hit_inst[lid0]].material_id : __float_as_uint(S.shade_tris[8u * (size_t)leaf0 + 6u].w)];
-        uint32_t light = 4u;
-        if (m0->is_specular == 0 && F.lights_no != 0u) {
-          uint32_t rng0 = pcg(__float_as_uint((float)F.seed) ^ pcg(__float_as_uint((float)px0.x) ^ pcg(__float_as_uint((float)px0.y))));
-          const uint32_t li0 = (uint32_t)gl_min(rand01(rng0) * (float)F.lights_no, (float)(F.lights_no - 1u));
-          light = S.lights[li0].shader;
+        const MatCompact* m0 = &S.mat_compact[S.two_level ? S.instances[A.st.hit_inst[lid0]].material_id : __float_as_uint(S.shade_tris[8u * (size_t)leaf0 + 6u].w)];
+        // the draws shade_pixel_body starts with (DirectState::seed_rng / pick_light), made once: here, for the key, and handed on
+        uint32_t light = 4u, rng0 = pixel_rng(F, px0), li0 = 0u;
+        if (m0->is_specular == 0) {
+          li0 = light_pick(F, rng0);
+          if (F.lights_no != 0u) light = S.lights[li0].shader;
         }
+        s_pick[threadIdx.x] = make_uint2(rng0, li0);
         key = 1u + (m0->bsdf_index < 6u ? m0->bsdf_index : 5u) * 5u + (light < 4u ? light : 4u);
       }
     }
@@ -175,15 +185,16 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   // (Handing the next k_trace the pixels in this regrouped order -- one more word per pixel -- does nothing for the traversal, 0.588 ->
   // 0.591 ms; sorted per block by the octant of the new direction, camera rays last, 0.590 -> 0.573 ms, less than the sort and the
   // indirection cost.)
-  const PixelId px = pixel_of(A.map, lid);
+  const PixelId px = pixel_of_block(A.map, blockIdx.x, s_perm[threadIdx.x]);
   StagedState staged;
   if (px.active) {
-    const float4 ro = A.st.ray_o[lid], rd = A.st.ray_d[lid], hr = s_hit[s_perm[threadIdx.x]];
+    const float4 ro = make_float4(0.0f, 0.0f, 0.0f, s_bounce[s_perm[threadIdx.x]]), rd = A.st.ray_d[lid], hr = s_hit[s_perm[threadIdx.x]];
     // (see reread_kernarg: without it the regrouping prologue's view of the arguments stays in SGPRs through the shading code)
     const LaunchArgs& A2 = *(const LaunchArgs*)reread_kernarg();
     SharedQueue queue{A2};
     staged.A = &A2;
     staged.lds_imp = (LdsNodePtr)(reinterpret_cast<u32x4*>(s_imp) + s_perm[threadIdx.x]);
+    staged.lds_pick = (StagedState::LdsPickPtr)(reinterpret_cast<StagedState::u32x2*>(s_pick) + s_perm[threadIdx.x]);
 #ifdef GLZ_SECTION_TIMES
     staged.sec_last = __builtin_amdgcn_s_memtime();
 #endif

@@ -3,6 +3,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <utility>
 
 #include "host_math.h"
 #include "instance_boxes.h"
@@ -51,8 +52,40 @@ bool ShadingTables::build_materials(hipStream_t st, const std::vector<glz_materi
     r.is_emissive = m.has_emissive ? 1u : 0u;
     h_materials.push_back(r);
   }
-  if (!hip_ok(d_materials_.upload(h_materials.data(), h_materials.size(), st), "upload materials", err)) return false;
-  return hip_ok(hipStreamSynchronize(st), "materials upload", err);
+  // the tables the shading kernels read at every hit, derived from the records just made (device/types.h): MatCompact, and the spectra
+  // on their own, each distinct pair once
+  h_mat_compact.clear();
+  h_metal_spectra.clear();
+  for (const RTMaterial& r : h_materials) {
+    MetalSpectra sp;
+    sp.ior = r.metal_ior;
+    sp.fresnel = r.metal_fresnel;
+    size_t slot = 0;
+    while (slot < h_metal_spectra.size() && memcmp(&h_metal_spectra[slot], &sp, sizeof(sp)) != 0) ++slot;
+    if (slot == h_metal_spectra.size()) h_metal_spectra.push_back(sp);
+    h_mat_compact.push_back(compact_material(r, (uint32_t)slot));
+  }
+  // The three device arrays belong together (MatCompact::spectra indexes the spectra table, both mirror the RTMaterial array): they are
+  // uploaded into new buffers and take the old ones' place only when all three are there, so a failed upload leaves the device with the
+  // consistent set it had.
+  DeviceBuffer<RTMaterial> materials_new;
+  DeviceBuffer<MetalSpectra> spectra_new;
+  DeviceBuffer<MatCompact> compact_new;
+  if (!hip_ok(materials_new.upload(h_materials.data(), h_materials.size(), st), "upload materials", err)) return false;
+  if (!hip_ok(spectra_new.upload(h_metal_spectra.data(), h_metal_spectra.size(), st), "upload metal spectra", err)) return false;
+  if (!hip_ok(compact_new.upload(h_mat_compact.data(), h_mat_compact.size(), st), "upload compact materials", err)) return false;
+  if (!hip_ok(hipStreamSynchronize(st), "materials upload", err)) return false;
+  d_materials_ = std::move(materials_new);
+  d_metal_spectra_ = std::move(spectra_new);
+  d_mat_compact_ = std::move(compact_new);
+  return true;
+}
+
+void sky_row_pairs(const float* marginal_values, const float* conditional_integrals, size_t n, float* pairs_out) {
+  for (size_t y = 0; y < n; ++y) {
+    pairs_out[2 * y] = marginal_values[y];
+    pairs_out[2 * y + 1] = conditional_integrals[y];
+  }
 }
 
 bool ShadingTables::has_non_opaque() const {
@@ -153,6 +186,13 @@ bool ShadingTables::build_lights_and_sky(hipStream_t st, const SceneData& data, 
     h_sky_marginal = marginal_cdf;
     h_sky_marginal.insert(h_sky_marginal.end(), integrals.begin(), integrals.end());   // marginal values
     h_sky_marginal.insert(h_sky_marginal.end(), integrals.begin(), integrals.end());   // conditional integrals
+    // what a sample reads besides the row search, where it costs no scattered load: the conditional tables' first words in the header
+    // (the kernel arguments), the row's two entries of h_sky_marginal as one pair
+    h_sky_header.cond_cdf00 = cond_cdf.empty() ? 0.0f : cond_cdf[0];
+    h_sky_header.cond_value00 = values.empty() ? 0.0f : values[0];
+    h_sky_rows.resize(2 * (size_t)H);
+    sky_row_pairs(h_sky_marginal.data() + h_sky_header.marginal_cdf_count, h_sky_marginal.data() + h_sky_header.conditional_integral_offset, H, h_sky_rows.data());
+    if (!hip_ok(d_sky_rows_.upload(reinterpret_cast<const float2*>(h_sky_rows.data()), H, st), "upload sky rows", err)) return false;
     if (!hip_ok(d_sky_marginal_.upload(h_sky_marginal.data(), h_sky_marginal.size(), st), "upload sky marginal", err)) return false;
     if (!hip_ok(d_sky_cond_values_.upload(values.data(), values.size(), st), "upload sky values", err)) return false;
     if (!hip_ok(d_sky_cond_cdf_.upload(cond_cdf.data(), cond_cdf.size(), st), "upload sky cdf", err)) return false;
@@ -166,6 +206,9 @@ bool ShadingTables::build_lights_and_sky(hipStream_t st, const SceneData& data, 
 
 void ShadingTables::describe(DeviceScene& dev) const {
   dev.materials = d_materials_.ptr;
+  dev.mat_compact = d_mat_compact_.ptr;
+  dev.metal_spectra = d_metal_spectra_.ptr;
+  dev.n_metal_spectra = (uint32_t)d_metal_spectra_.count;
   dev.n_materials = (uint32_t)d_materials_.count;
   dev.has_non_opaque = has_non_opaque() ? 1u : 0u;
   dev.lights = d_lights_.ptr;
@@ -174,6 +217,7 @@ void ShadingTables::describe(DeviceScene& dev) const {
   dev.sky_header = h_sky_header;
   dev.sky_marginal = d_sky_marginal_.ptr;
   dev.sky_cdf = d_sky_marginal_.ptr;   // (k_shade points its copy at an LDS copy of the same entries)
+  dev.sky_rows = d_sky_rows_.ptr;
   dev.sky_cond_values = d_sky_cond_values_.ptr;
   dev.sky_cond_cdf = d_sky_cond_cdf_.ptr;
   dev.sky_w = sky_w_;

@@ -863,6 +863,9 @@ int glz_host_chain_owner(uint32_t width, uint32_t height, uint32_t rank, uint32_
 /* the 8-bit sRGB quantiser of read_rgba8 / draw (the reference's R8G8B8A8_SRGB blit, raytracer.rs:576-584): c encodes to
  * #{k in 1..255 : c >= thresholds_out[k]}; thresholds_out[0] = 0 */
 int glz_host_srgb8_thresholds(float thresholds_out[256]);
+/* the per-row table a sky sample reads once its row is found, as scene creation builds it from the sky's marginal values and conditional
+ * integrals (n rows each): pairs_out[2 y] = marginal_values[y], pairs_out[2 y + 1] = conditional_integrals[y] -- the same floats, interleaved */
+int glz_host_sky_row_pairs(const float* marginal_values, const float* conditional_integrals, uint64_t n, float* pairs_out);
 /* the size check of scene creation (glz_instance_set_bvh_builder: "Size limit") on counts given by the caller, nothing built or
  * allocated: 4-wide nodes, 8-wide nodes, leaf records, instance records, lanes of the largest persistent grid, spilt stack words per
  * lane.  GLZ_OK when every table stays below 2^32 bytes, else GLZ_E_INVALID_DATA with the message scene creation fails with. */
