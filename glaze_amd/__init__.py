@@ -24,7 +24,7 @@ from .abi import GlazeError
 from .scene_desc import VERTEX_DTYPE, SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
 
 __all__ = ["parse", "converted_file", "ParsedScene", "RayTraceInstance", "RayTraceScene", "RayTraceRenderer", "Integrator",
-           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points", "host_skin",
+           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points", "host_skin", "host_morph",
            "host_project_constants"]
 
 
@@ -268,6 +268,42 @@ def host_skin(bind, joints, weights, bones):
         raise ValueError("joints and weights must have one row per vertex")
     out = np.zeros_like(v)
     abi.check(abi.lib().glz_host_skin(_ptr(v), _ptr(j), _ptr(w), v.shape[0], _ptr(b), b.shape[0], _ptr(out)))
+    return out
+
+
+def _morph_targets(targets, n_vertices):
+    """(abi.MorphTarget array, the arrays it points into) of a list of (indices | None, d_position, d_normal)"""
+    keep, rows = [], []
+    for t in targets:
+        if len(t) != 3:
+            raise ValueError("a target is (indices or None, d_position, d_normal)")
+        dp, dn = (np.ascontiguousarray(d, np.float32).reshape(-1, 3) for d in t[1:])
+        if t[0] is None:
+            idx, n = None, int(n_vertices)
+        else:
+            raw = np.ascontiguousarray(t[0])
+            if raw.ndim != 1 or (raw.size and (raw.dtype.kind not in "iu" or raw.min() < 0 or raw.max() > 0xFFFFFFFF)):
+                raise ValueError("a target's indices must be a 1-d array of vertex indices")
+            idx = np.ascontiguousarray(raw, np.uint32)
+            n = idx.shape[0]
+        if dp.shape != (n, 3) or dn.shape != (n, 3):
+            raise ValueError("d_position and d_normal must be (n, 3), one row per entry (per vertex for a dense target)")
+        keep += [idx, dp, dn]
+        rows.append(abi.MorphTarget(None if idx is None else _ptr(idx), _ptr(dp), _ptr(dn), n))
+    return (abi.MorphTarget * max(1, len(rows)))(*rows), keep
+
+
+def host_morph(base, targets, weights):
+    """glz_host_morph: the morph rule (include/glaze_abi.h holds the specification) on the host, no device, the reference of k_morph.
+    base: n vertices in any form update_vertices takes; targets: a list of (indices | None, d_position, d_normal), indices relative to
+    base, strictly ascending, None = dense; weights: one float32 a target.  Returns the morphed vertices, (n, 8) float32."""
+    v = _vertex_array(base)
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w.shape[0] != len(targets):
+        raise ValueError("weights must have one entry per target")
+    arr, keep = _morph_targets(targets, v.shape[0])
+    out = v.copy()
+    abi.check(abi.lib().glz_host_morph(_ptr(v), v.shape[0], C.cast(arr, C.c_void_p), len(targets), _ptr(w), _ptr(out)))
     return out
 
 
@@ -730,7 +766,9 @@ class RayTraceRenderer:
         is what the scene's vertices hold there now.  Returns the skin's id; the skin is the scene's (every renderer sharing it sees it)."""
         j, w = _skin_arrays(joints, weights)
         skin = abi.Skin(int(first), j.shape[0], _ptr(j), _ptr(w), int(n_bones))
-        return abi.check(abi.lib().glz_renderer_add_skin(self._h, C.cast(C.byref(skin), C.c_void_p)))
+        skin_id = abi.check(abi.lib().glz_renderer_add_skin(self._h, C.cast(C.byref(skin), C.c_void_p)))
+        self.__dict__.setdefault("_skin_sizes", {})[skin_id] = j.shape[0]   # (add_morph(skin=...) takes its vertex count from here)
+        return skin_id
 
     def remove_skin(self, skin):
         """Frees a skin; the vertices stay as they are."""
@@ -756,6 +794,51 @@ class RayTraceRenderer:
         ms = C.c_float(0.0)
         abi.check(abi.lib().glz_debug_skin_timing(self._h, C.cast(arr, C.c_void_p), int(reps), C.cast(C.byref(ms), C.c_void_p)))
         return ms.value
+
+    def add_morph(self, first, targets, skin=None, n_vertices=None):
+        """Morph targets over the scene's vertices [first, first + n): targets is a list of (indices | None, d_position, d_normal), indices
+        relative to `first`, strictly ascending, None = a dense target.  skin=None: free-standing, the base is what the scene's vertices
+        hold there now, and n is n_vertices (or, with a dense target in the list, its length); skin=id: attached to that skin -- the base
+        is the skin's bind pose, `first` must be the skin's and n is the skin's.  Returns the morph's id."""
+        if n_vertices is None and skin is not None:
+            n_vertices = self.__dict__.get("_skin_sizes", {}).get(int(skin))
+        if n_vertices is None:
+            dense = [np.asarray(t[1]).reshape(-1, 3).shape[0] for t in targets if t[0] is None]
+            if not dense:
+                raise ValueError("n_vertices is needed when no target is dense")
+            n_vertices = dense[0]
+        arr, keep = _morph_targets(targets, n_vertices)
+        m = abi.Morph(int(first), int(n_vertices), C.cast(arr, C.c_void_p), len(targets), -1 if skin is None else int(skin))
+        return abi.check(abi.lib().glz_renderer_add_morph(self._h, C.cast(C.byref(m), C.c_void_p)))
+
+    def remove_morph(self, morph):
+        """Frees a morph; the vertices stay as they are."""
+        abi.check(abi.lib().glz_renderer_remove_morph(self._h, int(morph)))
+
+    @classmethod
+    def _animation(cls, morphs, poses):
+        """abi.Animation of {morph id: weights} and {skin id: bones}, and what it points into"""
+        morphs, poses = morphs or {}, poses or {}
+        ws = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in morphs.values()]
+        marr = (abi.MorphWeights * max(1, len(morphs)))(*[abi.MorphWeights(int(k), _ptr(w), w.shape[0]) for k, w in zip(morphs.keys(), ws)])
+        parr, bones = cls._pose_array(poses)
+        a = abi.Animation(C.cast(marr, C.c_void_p) if morphs else None, len(morphs), C.cast(parr, C.c_void_p) if poses else None, len(poses))
+        return a, (ws, marr, parr, bones)
+
+    def animate(self, morphs=None, poses=None, mode="refit"):
+        """Morphs and poses in one update of the structure: morphs is {morph id: weights, one float32 a target}, poses {skin id: bones} as
+        pose() takes them.  A free-standing morph is blended from its base; a skin whose morph is named too is morphed, then skinned, in
+        one kernel; an attached morph must come with its skin's pose.  Nothing is kept between calls: every call starts from the bases."""
+        a, keep = self._animation(morphs, poses)
+        abi.check(abi.lib().glz_renderer_animate(self._h, C.cast(C.byref(a), C.c_void_p), self._GEOMETRY_MODES.get(mode, mode)))
+
+    def debug_morph_timing(self, morphs, poses=None, reps=20):
+        """k_morph on one morph (morphs={id: weights}), or k_morph_skin on an attached morph with its skin's pose, alone into a scratch
+        buffer (the scene is untouched): (milliseconds per launch, the bytes one launch moves)"""
+        a, keep = self._animation(morphs, poses)
+        ms, nbytes = C.c_float(0.0), C.c_uint64(0)
+        abi.check(abi.lib().glz_debug_morph_timing(self._h, C.cast(C.byref(a), C.c_void_p), int(reps), C.cast(C.byref(ms), C.c_void_p), C.cast(C.byref(nbytes), C.c_void_p)))
+        return ms.value, nbytes.value
 
     def read_vertices(self, first, n):
         """The scene's current vertices [first, first + n) as the device holds them: (n, 8) float32"""
@@ -908,14 +991,20 @@ class RayTraceRenderer:
                                   None if v is None else _ptr(v), int(first_vertex), 0 if v is None else v.shape[0])
         return state, (prev_camera, t, v)
 
-    def read_motion(self, prev_camera, prev_transforms=None, prev_vertices=None, first_vertex=0, prev_poses=None):
+    def read_motion(self, prev_camera, prev_transforms=None, prev_vertices=None, first_vertex=0, prev_poses=None, prev_morphs=None):
         """The motion plane (include/glaze_abi.h holds the specification): H x W x 4 float32, per pixel (where the first hit of the centre
         ray was on screen under prev_camera, prev_transforms and prev_vertices, minus the pixel's own centre; its distance from the previous
         eye; the hit's instance bits).  prev_transforms: (n, 16) float32 as update_transforms takes them, None = the instances did not move.
         prev_vertices: what the scene's vertices [first_vertex, first_vertex + n) held in the previous frame, in any form update_vertices
         takes, None = the meshes did not deform.  prev_poses: {skin id: bones} as pose() takes them, the PREVIOUS frame's -- the previous
-        vertices are then made on the device (prev_vertices must be None).  Accumulation goes on."""
+        vertices are then made on the device (prev_vertices must be None).  prev_morphs: {morph id: weights} as animate() takes them, the
+        PREVIOUS frame's, with prev_poses as animate() would need them.  Accumulation goes on."""
         out = np.zeros((self.height, self.width, 4), np.float32)
+        if prev_morphs is not None:
+            state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
+            a, keep_animation = self._animation(prev_morphs, prev_poses)
+            abi.check(abi.lib().glz_renderer_read_motion_animated(self._h, C.cast(C.byref(state), C.c_void_p), C.cast(C.byref(a), C.c_void_p), _ptr(out)))
+            return out
         if prev_poses is not None:
             state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
             arr, keep_bones = self._pose_array(prev_poses)
@@ -943,10 +1032,10 @@ class RayTraceRenderer:
                                                     C.cast(C.byref(ms), C.c_void_p)))
         return ms.value
 
-    def reproject(self, prev_camera, prev_color, prev_aov0, prev_aov1, prev_transforms=None, prev_vertices=None, first_vertex=0, prev_poses=None, **params):
+    def reproject(self, prev_camera, prev_color, prev_aov0, prev_aov1, prev_transforms=None, prev_vertices=None, first_vertex=0, prev_poses=None, prev_morphs=None, **params):
         """The previous frame's colour carried to this frame's pixels with disocclusion rejection: H x W x 4 float32 (rgb, confidence
         0 .. 1).  prev_color: any H x W x 4 image of the previous frame; prev_aov0 / prev_aov1: read_aov(0) / read_aov(1) of the previous
-        state in first-hit mode; prev_transforms, prev_vertices, first_vertex, prev_poses: as read_motion takes them; params: glz_reproject_params
+        state in first-hit mode; prev_transforms, prev_vertices, first_vertex, prev_poses, prev_morphs: as read_motion takes them; params: glz_reproject_params
         (depth_tolerance).  Accumulation goes on."""
         shape = (self.height, self.width, 4)
         c, a0, a1 = (np.ascontiguousarray(f, np.float32) for f in (prev_color, prev_aov0, prev_aov1))
@@ -954,6 +1043,12 @@ class RayTraceRenderer:
             raise ValueError("prev_color, prev_aov0 and prev_aov1 must be H x W x 4 of the renderer's size")
         out = np.zeros(shape, np.float32)
         p = abi.ReprojectParams(**params)
+        if prev_morphs is not None:
+            state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
+            a, keep_animation = self._animation(prev_morphs, prev_poses)
+            abi.check(abi.lib().glz_renderer_reproject_animated(self._h, C.cast(C.byref(state), C.c_void_p), C.cast(C.byref(a), C.c_void_p), _ptr(c), _ptr(a0), _ptr(a1),
+                                                                C.cast(C.byref(p), C.c_void_p), _ptr(out)))
+            return out
         if prev_poses is not None:
             state, keep = self._previous_state(prev_camera, prev_transforms, prev_vertices, first_vertex)
             arr, keep_bones = self._pose_array(prev_poses)

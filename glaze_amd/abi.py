@@ -165,6 +165,27 @@ class Pose(C.Structure):
     _fields_ = [("skin", C.c_int), ("bones", C.c_void_p), ("n_bones", C.c_uint32)]
 
 
+class MorphTarget(C.Structure):
+    """glz_morph_target"""
+    _fields_ = [("vertices", C.c_void_p), ("d_position", C.c_void_p), ("d_normal", C.c_void_p), ("n", C.c_uint32)]
+
+
+class Morph(C.Structure):
+    """glz_morph"""
+    _fields_ = [("first_vertex", C.c_uint32), ("n_vertices", C.c_uint32), ("targets", C.c_void_p), ("n_targets", C.c_uint32), ("skin", C.c_int)]
+
+
+class MorphWeights(C.Structure):
+    """glz_morph_weights"""
+    _fields_ = [("morph", C.c_int), ("weights", C.c_void_p), ("n_targets", C.c_uint32)]
+
+
+class Animation(C.Structure):
+    """glz_animation"""
+    _fields_ = [("morphs", C.c_void_p), ("n_morphs", C.c_uint32), ("poses", C.c_void_p), ("n_poses", C.c_uint32)]
+
+
+MORPH_LDS_TARGETS = 1024   # kMorphLdsTargets (csrc/kernels.h): the morph kernels stage the weight table in LDS up to this many targets
 AOV_NORMAL_DEPTH, AOV_ALBEDO_INSTANCE = 0, 1
 GUIDE_FIRST_HIT, GUIDE_THROUGH_SPECULAR, GUIDE_MAX_BOUNCES = 0, 1, 8
 DENOISE_MAX_ITERATIONS, DENOISE_MAX_NORMAL_POWER_LOG2 = 8, 31
@@ -224,6 +245,13 @@ PROTOTYPES = {
     "glz_renderer_read_motion_posed": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "glz_renderer_reproject_posed": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "glz_host_skin": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, _P]),
+    "glz_renderer_add_morph": (C.c_int, [_P, _P]),
+    "glz_renderer_remove_morph": (C.c_int, [_P, C.c_int]),
+    "glz_renderer_animate": (C.c_int, [_P, _P, C.c_int]),
+    "glz_renderer_read_motion_animated": (C.c_int, [_P, _P, _P, _P]),
+    "glz_renderer_reproject_animated": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "glz_host_morph": (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, _P]),
+    "glz_debug_morph_timing": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
     "glz_debug_read_leaf_records": (C.c_int64, [_P, _P, C.c_int64]),
     "glz_debug_read_tlas_instances": (C.c_int64, [_P, _P, C.c_int64]),
     "glz_debug_instance_boxes": (C.c_int64, [_P, C.c_int, C.c_uint64, _P, _P]),

@@ -379,6 +379,31 @@ int glz_renderer_pose_skins(glz_renderer* h, const glz_pose* poses, uint32_t n, 
   GLZ_RET(h->r->pose_skins(poses, n, mode, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_renderer_add_morph(glz_renderer* h, const glz_morph* morph) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!morph) return fail(GLZ_E_ARG, "add_morph: the morph is null");
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  const int id = h->r->add_morph(*morph, e);
+  if (id < 0) return fail(e);
+  return id;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_remove_morph(glz_renderer* h, int morph) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  GLZ_RET(h->r->remove_morph(morph, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_animate(glz_renderer* h, const glz_animation* anim, int mode) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  // (checked here as well as in the scene: a refused call must not make the renderer drain and restart)
+  uint32_t first = 0, count = 0;
+  if (!h->r->scene()->animated_span(anim, "animate", first, count, e)) return fail(e);
+  if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return fail(GLZ_E_ARG, "animate: unknown mode");
+  GLZ_RET(h->r->animate(*anim, mode, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_read_vertices(glz_renderer* h, uint32_t first, uint32_t n, glz_vertex* out) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
@@ -500,6 +525,30 @@ int glz_renderer_reproject_posed(glz_renderer* h, const glz_previous_state* prev
   if (!prev || !prev->camera || !prev_color || !prev_aov0 || !prev_aov1 || !out) return fail(GLZ_E_ARG, "the previous state, its camera, a previous frame or the output is null");
   if (prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
   GLZ_RET(h->r->post().reproject(*prev, prev_color, prev_aov0, prev_aov1, params, out, e, PrevPoses{poses, n_poses, true}));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+static PrevPoses previous_animation(const glz_animation& a) {
+  PrevPoses p{a.poses, a.n_poses, true};
+  p.morphs = a.morphs;
+  p.n_morphs = a.n_morphs;
+  p.animated = true;
+  return p;
+}
+int glz_renderer_read_motion_animated(glz_renderer* h, const glz_previous_state* prev, const glz_animation* anim, float* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!prev || !prev->camera || !out) return fail(GLZ_E_ARG, "the previous state, its camera or the output is null");
+  if (prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
+  if (!anim) return fail(GLZ_E_ARG, "motion: the animation is null");
+  GLZ_RET(h->r->post().read_motion(*prev, out, e, previous_animation(*anim)));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_reproject_animated(glz_renderer* h, const glz_previous_state* prev, const glz_animation* anim, const float* prev_color, const float* prev_aov0,
+                                    const float* prev_aov1, const glz_reproject_params* params, float* out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!prev || !prev->camera || !prev_color || !prev_aov0 || !prev_aov1 || !out) return fail(GLZ_E_ARG, "the previous state, its camera, a previous frame or the output is null");
+  if (prev->camera->type > GLZ_CAMERA_ORTHOGRAPHIC) return fail(GLZ_E_ARG, "unknown camera type");
+  if (!anim) return fail(GLZ_E_ARG, "motion: the animation is null");
+  GLZ_RET(h->r->post().reproject(*prev, prev_color, prev_aov0, prev_aov1, params, out, e, previous_animation(*anim)));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_renderer_launch_constants(glz_renderer* h, uint32_t launch, uint32_t* seed, float off[2]) {

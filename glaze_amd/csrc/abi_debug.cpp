@@ -9,6 +9,7 @@
 #include "denoise.h"
 #include "reproject.h"
 #include "skin.h"
+#include "morph.h"
 #include "mipchain.h"
 #include "rccl_dl.h"
 #include "tile_map.h"
@@ -117,6 +118,13 @@ int glz_debug_skin_timing(glz_renderer* h, const glz_pose* pose, uint32_t reps, 
   if (!pose || !kernel_ms_out || !h->r->scene()) return fail(GLZ_E_ARG, "bad argument");
   *kernel_ms_out = 0.0f;
   GLZ_RET(h->r->wait_idle(e) && h->r->scene()->time_skin(*pose, reps, kernel_ms_out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_morph_timing(glz_renderer* h, const glz_animation* one, uint32_t reps, float* kernel_ms_out, uint64_t* bytes_out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!one || !kernel_ms_out || !h->r->scene()) return fail(GLZ_E_ARG, "bad argument");
+  *kernel_ms_out = 0.0f;
+  GLZ_RET(h->r->wait_idle(e) && h->r->scene()->time_morph(*one, reps, kernel_ms_out, bytes_out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_debug_guide_chain(glz_renderer* h, uint32_t segment, float* origins3, float* dirs3, uint8_t* alive) {
@@ -429,6 +437,19 @@ int glz_host_skin(const glz_vertex* bind, const uint16_t* joints, const float* w
   for (uint64_t i = 0; i < 4 * n; ++i)
     if (joints[i] >= n_bones) return fail(GLZ_E_ARG, "host_skin: a joint names a bone past n_bones");
   post::host_skin(bind, joints, weights, (size_t)n, bones, n_bones, out);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_host_morph(const glz_vertex* base, uint64_t n, const glz_morph_target* targets, uint32_t n_targets, const float* weights, glz_vertex* out) {
+  GLZ_GUARD_BEGIN
+  if (n_targets == 0 || n_targets > post::kMorphMaxTargets) return fail(GLZ_E_ARG, "host_morph: n_targets must be 1 .. 65536");
+  if (n == 0) return GLZ_OK;
+  if (!base || !targets || !weights || !out) return fail(GLZ_E_ARG, "host_morph: null argument");
+  if (n > 0xFFFFFFFFull) return fail(GLZ_E_ARG, "host_morph: more vertices than a morph can have");
+  post::MorphLayout layout;
+  std::string why;
+  if (!post::pack_morph((uint32_t)n, targets, n_targets, layout, why)) return fail(GLZ_E_ARG, ("host_morph: " + why).c_str());
+  post::host_morph(base, layout, weights, out);
   return GLZ_OK;
   GLZ_GUARD_END(GLZ_E_IO)
 }

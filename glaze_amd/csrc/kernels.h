@@ -256,6 +256,24 @@ hipError_t launch_project_points(hipStream_t st, const post::ProjectConstants& C
 constexpr uint32_t kSkinLdsBones = 256;   // 12 KB of a block's LDS
 hipError_t launch_skin(hipStream_t st, const float4* bind, const uint2* joints, const float4* weights, uint32_t n, const float4* bones, uint32_t n_bones, float4* out);
 
+// ---- morph targets (kernels_morph.hip; morph.h holds the rule and the layout) ----
+// What a morph's kernels read: post::MorphLayout on the device, and the base of its n vertices (two float4 a vertex).  Every row's count is
+// at most its slice's width and every entry's target below n_targets (pack_morph made them so: the kernels index by them).
+struct MorphArgs {
+  const float4* base;
+  const uint32_t* counts;
+  const uint2* slices;
+  const float4* entries;
+  uint32_t n;
+  const float* weights;   // n_targets of them, staged in LDS when n_targets <= kMorphLdsTargets, else read from memory
+  uint32_t n_targets;
+};
+constexpr uint32_t kMorphLdsTargets = 1024;   // 4 KB of a block's LDS
+// out[2 * i], out[2 * i + 1] = vertex i of the base under the morph rule, i < n; out: n vertices of device memory that overlap no input
+hipError_t launch_morph(hipStream_t st, const MorphArgs& m, float4* out);
+// the same, then the skinning rule on the morphed vertex (launch_skin's arguments), one store: the base is the skin's bind pose
+hipError_t launch_morph_skin(hipStream_t st, const MorphArgs& m, const uint2* joints, const float4* skin_weights, const float4* bones, uint32_t n_bones, float4* out);
+
 // debug / parity hooks
 hipError_t launch_debug_closest(hipStream_t st, const DeviceScene& scene, const float* origins, const float* dirs, uint32_t n, float tmin,
                                 float* t, uint32_t* tri, uint32_t* inst, float* u, float* v, uint32_t* overflow, uint32_t overflow_depth);

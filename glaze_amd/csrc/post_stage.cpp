@@ -185,7 +185,10 @@ bool PostStage::motion_pass(const glz_previous_state& prev, PrevBuffers& uploade
   uint32_t posed_first = 0, posed_count = 0;
   if (posed.given) {
     if (prev.vertices) return bad_argument(err, "motion: a posed previous state brings no vertices of its own (vertices must be null)");
-    if (!r_.scene()->posed_span(posed.poses, posed.n, "motion", posed_first, posed_count, err)) return false;
+    const glz_animation previous = posed.animation();
+    if (posed.animated ? !r_.scene()->animated_span(&previous, "motion", posed_first, posed_count, err)
+                       : !r_.scene()->posed_span(posed.poses, posed.n, "motion", posed_first, posed_count, err))
+      return false;
   }
   if (!hip_ok(hipSetDevice(r_.instance()->device), "hipSetDevice", err)) return false;
   MotionStep step;
@@ -207,17 +210,14 @@ bool PostStage::motion_pass(const glz_previous_state& prev, PrevBuffers& uploade
     step.first_vertex = prev.first_vertex;
     step.n_vertices = prev.n_vertices;
   }
-  if (posed.given) {   // the same buffer, filled on the device: the current vertices of the span, then every skin as its previous bones pose it
+  if (posed.given) {   // the same buffer, filled on the device: the current vertices of the span, then every morph and skin as its previous weights and bones make it
     hipStream_t st = r_.instance()->stream;
     const Scene& scene = *r_.scene();
     if (!hip_ok(uploaded.vertices.alloc(2 * (size_t)posed_count), "alloc previous vertices", err) ||
         !hip_ok(hipMemcpyAsync(uploaded.vertices.ptr, scene.dev.vertices + 2 * (size_t)posed_first, sizeof(float4) * 2 * (size_t)posed_count, hipMemcpyDeviceToDevice, st),
                 "copy current vertices", err))
       return false;
-    uploaded.bones = std::vector<DeviceBuffer<float4>>(posed.n);
-    uploaded.packed.assign(posed.n, {});
-    for (uint32_t i = 0; i < posed.n; ++i)
-      if (!scene.skin_into(posed.poses[i], uploaded.vertices.ptr, posed_first, uploaded.packed[i], uploaded.bones[i], st, err)) return false;
+    if (!scene.animate_into(posed.animation(), uploaded.vertices.ptr, posed_first, uploaded.animation, st, err)) return false;
     step.prev_vertices = uploaded.vertices.ptr;
     step.first_vertex = posed_first;
     step.n_vertices = posed_count;

@@ -11,13 +11,18 @@ namespace glz {
 
 class Renderer;
 
-// Previous vertices made on the device (glz_renderer_read_motion_posed / reproject_posed): the skins as the PREVIOUS bones pose them.  The
+// Previous vertices made on the device (glz_renderer_read_motion_posed / reproject_posed, *_animated): the skins as the PREVIOUS bones pose them.  The
 // buffer k_motion_deform reads then holds the span from the lowest to the highest posed vertex: the scene's current vertices copied
 // device to device (so a gap between skins holds current values), then k_skin of every named skin with these bones.
 struct PrevPoses {
   const glz_pose* poses = nullptr;
   uint32_t n = 0;
-  bool given = false;   // a *_posed call: the state must bring no vertices, and the poses are checked as pose_skins checks them
+  bool given = false;   // a *_posed / *_animated call: the state must bring no vertices, and the poses are checked as pose_skins checks them
+  // *_animated: the previous morph weights as well, and the whole checked and run as glz_renderer_animate does (Scene::animate_into)
+  const glz_morph_weights* morphs = nullptr;
+  uint32_t n_morphs = 0;
+  bool animated = false;
+  glz_animation animation() const { return glz_animation{morphs, n_morphs, poses, n}; }
 };
 
 class PostStage {
@@ -73,9 +78,8 @@ class PostStage {
   void post_args(LaunchArgs& a) const;
   // what a motion pass uploads of the caller's previous state: owned by the call and released with it
   struct PrevBuffers {
-    std::vector<std::vector<float4>> packed;     // the host arrays the bone tables are copied from (first, so released last: after the buffers' hipFree has waited)
+    Scene::AnimationUploads animation;           // the bone and weight tables of the previous poses and morphs (its host arrays first, so released last)
     DeviceBuffer<float4> o2w, vertices;
-    std::vector<DeviceBuffer<float4>> bones;     // one table per previous pose
   };
   bool motion_pass(const glz_previous_state& prev, PrevBuffers& uploaded, DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks = nullptr,
                    const PrevPoses& posed = {});

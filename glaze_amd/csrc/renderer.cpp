@@ -588,6 +588,29 @@ bool Renderer::pose_skins(const glz_pose* poses, uint32_t n, int mode, Error& er
   if (!update_scene([&] { return scene_->pose_skins(poses, n, mode, err); }, err)) return false;
   return group_.forward([=](Renderer& p, Error& e) { return p.pose_skins(poses, n, mode, e); }, err);
 }
+// Morphs are the scene's, as skins are.
+int Renderer::add_morph(const glz_morph& morph, Error& err) {
+  if (!wait_idle(err)) return -1;
+  const int id = scene_->add_morph(morph, err);
+  if (id < 0) return -1;
+  const glz_morph m = morph;
+  const bool followed = group_.forward([=](Renderer& p, Error& e) {
+    const int got = p.add_morph(m, e);
+    if (got >= 0 && got != id) e.fail(GLZ_E_DEVICE, "add_morph: a replica gave another morph id");
+    return got == id;
+  }, err);
+  if (!followed) return -1;
+  return id;
+}
+bool Renderer::remove_morph(int id, Error& err) {
+  if (!wait_idle(err) || !scene_->remove_morph(id, err)) return false;
+  return group_.forward([=](Renderer& p, Error& e) { return p.remove_morph(id, e); }, err);
+}
+bool Renderer::animate(const glz_animation& anim, int mode, Error& err) {
+  if (!update_scene([&] { return scene_->animate(anim, mode, err); }, err)) return false;
+  const glz_animation a = anim;
+  return group_.forward([=](Renderer& p, Error& e) { return p.animate(a, mode, e); }, err);
+}
 bool Renderer::read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& err) {
   return wait_idle(err) && scene_->read_vertices(first, n, out, err);
 }

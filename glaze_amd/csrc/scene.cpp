@@ -323,7 +323,7 @@ int Scene::install_skin(int id, uint32_t first, std::vector<glz_vertex>&& bind, 
   if (!hip_ok(bound, "bind pose", err) ||
       !hip_ok(s.joints.upload(reinterpret_cast<const uint2*>(s.h_joints.data()), s.n, st), "upload joints", err) ||
       !hip_ok(s.weights.upload(reinterpret_cast<const float4*>(s.h_weights.data()), s.n, st), "upload weights", err) ||
-      !hip_ok(s.bones.alloc((size_t)post::kSkinBoneRows * n_bones), "alloc bones", err) || !hip_ok(hipStreamSynchronize(st), "add_skin", err))
+      !hip_ok(hipStreamSynchronize(st), "add_skin", err))
     return -1;
   skins_.emplace(id, std::move(s));
   return id;
@@ -342,6 +342,9 @@ int Scene::add_skin(const glz_skin& k, Error& err) {
   for (const auto& kv : skins_)
     if (k.first_vertex < (uint64_t)kv.second.first + kv.second.n && kv.second.first < (uint64_t)k.first_vertex + k.n_vertices)
       return refuse("add_skin: the range overlaps an existing skin");
+  for (const auto& kv : morphs_)
+    if (kv.second.skin < 0 && k.first_vertex < (uint64_t)kv.second.first + kv.second.n && kv.second.first < (uint64_t)k.first_vertex + k.n_vertices)
+      return refuse("add_skin: the range overlaps a free-standing morph");
   if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return -1;
   // the bind pose is what the device holds now (the mirror may be behind it); the host copy of it is for replicas made later
   std::vector<glz_vertex> bind(k.n_vertices);
@@ -353,7 +356,10 @@ int Scene::add_skin(const glz_skin& k, Error& err) {
 }
 
 bool Scene::remove_skin(int id, Error& err) {
-  if (skins_.erase(id) == 0) return err.fail(GLZ_E_ARG, "remove_skin: no such skin");
+  const auto it = skins_.find(id);
+  if (it == skins_.end()) return err.fail(GLZ_E_ARG, "remove_skin: no such skin");
+  if (it->second.morph >= 0) return err.fail(GLZ_E_ARG, "remove_skin: the skin still carries a morph (remove_morph first)");
+  skins_.erase(it);
   return true;
 }
 
@@ -386,14 +392,19 @@ bool Scene::posed_span(const glz_pose* poses, uint32_t n_poses, const char* who,
   return true;
 }
 
-bool Scene::skin_into(const glz_pose& pose, float4* span, uint32_t span_first, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const {
+bool Scene::upload_bones(const glz_pose& pose, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const {
   const Skin& s = skins_.at(pose.skin);
   packed.resize((size_t)post::kSkinBoneRows * s.n_bones);
   for (uint32_t b = 0; b < s.n_bones; ++b) post::pack_bone(pose.bones[b], packed.data() + (size_t)post::kSkinBoneRows * b);
   if (bones.ptr == nullptr || bones.count != packed.size()) {
     if (!hip_ok(bones.alloc(packed.size()), "alloc bones", err)) return false;
   }
-  return hip_ok(hipMemcpyAsync(bones.ptr, packed.data(), sizeof(float4) * packed.size(), hipMemcpyHostToDevice, st), "upload bones", err) &&
+  return hip_ok(hipMemcpyAsync(bones.ptr, packed.data(), sizeof(float4) * packed.size(), hipMemcpyHostToDevice, st), "upload bones", err);
+}
+
+bool Scene::skin_into(const glz_pose& pose, float4* span, uint32_t span_first, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const {
+  const Skin& s = skins_.at(pose.skin);
+  return upload_bones(pose, packed, bones, st, err) &&
          hip_ok(launch_skin(st, s.bind.ptr, s.joints.ptr, s.weights.ptr, s.n, bones.ptr, s.n_bones, span + 2 * (size_t)(s.first - span_first)), "k_skin", err);
 }
 
@@ -418,9 +429,203 @@ bool Scene::time_skin(const glz_pose& pose, uint32_t reps, float* kernel_ms, Err
 }
 
 bool Scene::pose_skins(const glz_pose* poses, uint32_t n_poses, int mode, Error& err) {
+  return run_animation(glz_animation{nullptr, 0, poses, n_poses}, mode, "pose_skins", err);
+}
+
+// ---- morph targets ----
+
+int Scene::install_morph(int id, uint32_t first, int skin, std::vector<glz_vertex>&& base, post::MorphLayout&& layout, const float4* device_base, Error& err) {
+  hipStream_t st = instance->stream;
+  Morph m;
+  m.first = first;
+  m.n = layout.n_vertices;
+  m.n_targets = layout.n_targets;
+  m.n_entries = layout.n_entries;
+  m.skin = skin;
+  m.h_base = std::move(base);
+  m.layout = std::move(layout);
+  hipError_t based = hipSuccess;
+  if (skin < 0) {   // its own base: device to device from the scene's vertices (add_morph), or from the host copy (a replica on another device)
+    based = device_base ? m.base.alloc(2 * (size_t)m.n) : m.base.upload(reinterpret_cast<const float4*>(m.h_base.data()), 2 * (size_t)m.n, st);
+    if (based == hipSuccess && device_base) based = hipMemcpyAsync(m.base.ptr, device_base, sizeof(float4) * 2 * (size_t)m.n, hipMemcpyDeviceToDevice, st);
+  }
+  if (!hip_ok(based, "morph base", err) || !hip_ok(m.counts.upload(m.layout.counts.data(), m.layout.counts.size(), st), "upload morph counts", err) ||
+      !hip_ok(m.slices.upload(m.layout.slices.data(), m.layout.slices.size(), st), "upload morph slices", err) ||
+      !hip_ok(m.entries.upload(m.layout.entries.data(), m.layout.entries.size(), st), "upload morph entries", err) || !hip_ok(hipStreamSynchronize(st), "add_morph", err))
+    return -1;
+  if (skin >= 0) skins_.at(skin).morph = id;
+  morphs_.emplace(id, std::move(m));
+  return id;
+}
+
+int Scene::add_morph(const glz_morph& g, Error& err) {
+  auto refuse = [&](const std::string& why) {
+    err.fail(GLZ_E_ARG, "add_morph: " + why);
+    return -1;
+  };
+  if (g.n_vertices == 0 || (uint64_t)g.first_vertex + g.n_vertices > data.vertices.size()) return refuse("no vertices, or a range past the scene's vertex count");
+  const uint64_t lo = g.first_vertex, hi = lo + g.n_vertices;
+  if (g.skin >= 0) {
+    const auto it = skins_.find(g.skin);
+    if (it == skins_.end()) return refuse("no such skin");
+    if (it->second.morph >= 0) return refuse("the skin already carries a morph");
+    if (it->second.first != g.first_vertex || it->second.n != g.n_vertices) return refuse("an attached morph's range must be exactly its skin's");
+  } else {
+    if (g.skin != -1) return refuse("skin must be a skin's id, or -1");
+    for (const auto& kv : skins_)
+      if (lo < (uint64_t)kv.second.first + kv.second.n && kv.second.first < hi) return refuse("the range overlaps a skin");
+    for (const auto& kv : morphs_)
+      if (lo < (uint64_t)kv.second.first + kv.second.n && kv.second.first < hi) return refuse("the range overlaps an existing morph");
+  }
+  post::MorphLayout layout;
+  std::string why;
+  if (!post::pack_morph(g.n_vertices, g.targets, g.n_targets, layout, why)) return refuse(why);
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return -1;
+  std::vector<glz_vertex> base;
+  if (g.skin < 0) {   // the base is what the device holds now; the host copy of it is for replicas made later
+    base.resize(g.n_vertices);
+    if (!read_vertices(g.first_vertex, g.n_vertices, base.data(), err)) return -1;
+  }
+  const int id = install_morph(next_morph_, g.first_vertex, g.skin, std::move(base), std::move(layout), geometry_.vertices.ptr + 2 * (size_t)g.first_vertex, err);
+  if (id >= 0) ++next_morph_;
+  return id;
+}
+
+bool Scene::remove_morph(int id, Error& err) {
+  const auto it = morphs_.find(id);
+  if (it == morphs_.end()) return err.fail(GLZ_E_ARG, "remove_morph: no such morph");
+  if (it->second.skin >= 0) skins_.at(it->second.skin).morph = -1;
+  morphs_.erase(it);
+  return true;
+}
+
+bool Scene::copy_morphs(const Scene& src, Error& err) {
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  for (const auto& kv : src.morphs_) {
+    const Morph& m = kv.second;
+    if (install_morph(kv.first, m.first, m.skin, std::vector<glz_vertex>(m.h_base), post::MorphLayout(m.layout), nullptr, err) < 0) return false;
+  }
+  next_morph_ = src.next_morph_;
+  return true;
+}
+
+bool Scene::animated_span(const glz_animation* anim, const char* who, uint32_t& first, uint32_t& count, Error& err) const {
+  auto refuse = [&](const char* why) { return err.fail(GLZ_E_ARG, std::string(who) + ": " + why); };
+  if (!anim) return refuse("the animation is null");
+  if (anim->n_morphs == 0) return posed_span(anim->poses, anim->n_poses, who, first, count, err);
+  if (!anim->morphs) return refuse("morphs is null");
+  uint64_t lo = ~0ull, hi = 0;
+  if (anim->n_poses) {
+    if (!posed_span(anim->poses, anim->n_poses, who, first, count, err)) return false;
+    lo = first;
+    hi = (uint64_t)first + count;
+  }
+  for (uint32_t i = 0; i < anim->n_morphs; ++i) {
+    const glz_morph_weights& w = anim->morphs[i];
+    const auto it = morphs_.find(w.morph);
+    if (it == morphs_.end()) return refuse("no such morph");
+    if (!w.weights) return refuse("a morph's weights are null");
+    if (w.n_targets != it->second.n_targets) return refuse("a morph's target count is not its morph's");
+    for (uint32_t k = 0; k < i; ++k)
+      if (anim->morphs[k].morph == w.morph) return refuse("a morph is named twice");
+    if (it->second.skin >= 0) {   // no bones are kept between calls: the skin's pose must come with it
+      bool posed = false;
+      for (uint32_t k = 0; k < anim->n_poses; ++k) posed = posed || anim->poses[k].skin == it->second.skin;
+      if (!posed) return refuse("an attached morph is named without its skin's pose");
+    }
+    lo = std::min<uint64_t>(lo, it->second.first);
+    hi = std::max<uint64_t>(hi, (uint64_t)it->second.first + it->second.n);
+  }
+  first = (uint32_t)lo;
+  count = (uint32_t)(hi - lo);
+  return true;
+}
+
+MorphArgs Scene::morph_args(const Morph& m, const float* weights) const {
+  return MorphArgs{m.skin >= 0 ? skins_.at(m.skin).bind.ptr : m.base.ptr, m.counts.ptr, m.slices.ptr, m.entries.ptr, m.n, weights, m.n_targets};
+}
+
+static bool upload_morph_weights(const glz_morph_weights& w, DeviceBuffer<float>& buffer, hipStream_t st, Error& err) {
+  if (buffer.ptr == nullptr || buffer.count != w.n_targets) {
+    if (!hip_ok(buffer.alloc(w.n_targets), "alloc morph weights", err)) return false;
+  }
+  return hip_ok(hipMemcpyAsync(buffer.ptr, w.weights, sizeof(float) * w.n_targets, hipMemcpyHostToDevice, st), "upload morph weights", err);
+}
+
+bool Scene::animate_into(const glz_animation& anim, float4* span, uint32_t span_first, AnimationUploads& up, hipStream_t st, Error& err) const {
+  up.packed.resize(anim.n_poses);
+  up.bones.resize(anim.n_poses);
+  up.weights.resize(anim.n_morphs);
+  for (uint32_t i = 0; i < anim.n_morphs; ++i) {
+    const Morph& m = morphs_.at(anim.morphs[i].morph);
+    if (!upload_morph_weights(anim.morphs[i], up.weights[i], st, err)) return false;
+    if (m.skin < 0 && !hip_ok(launch_morph(st, morph_args(m, up.weights[i].ptr), span + 2 * (size_t)(m.first - span_first)), "k_morph", err)) return false;
+  }
+  for (uint32_t i = 0; i < anim.n_poses; ++i) {
+    const glz_pose& pose = anim.poses[i];
+    const Skin& s = skins_.at(pose.skin);
+    uint32_t named = anim.n_morphs;   // where the skin's morph is named, if it is
+    for (uint32_t k = 0; k < anim.n_morphs && s.morph >= 0; ++k)
+      if (anim.morphs[k].morph == s.morph) named = k;
+    if (named == anim.n_morphs) {
+      if (!skin_into(pose, span, span_first, up.packed[i], up.bones[i], st, err)) return false;
+      continue;
+    }
+    if (!upload_bones(pose, up.packed[i], up.bones[i], st, err) ||
+        !hip_ok(launch_morph_skin(st, morph_args(morphs_.at(s.morph), up.weights[named].ptr), s.joints.ptr, s.weights.ptr, up.bones[i].ptr, s.n_bones,
+                                  span + 2 * (size_t)(s.first - span_first)), "k_morph_skin", err))
+      return false;
+  }
+  return true;
+}
+
+bool Scene::time_morph(const glz_animation& one, uint32_t reps, float* kernel_ms, uint64_t* bytes, Error& err) const {
+  auto refuse = [&](const char* why) { return err.fail(GLZ_E_ARG, std::string("morph timing: ") + why); };
+  if (!kernel_ms || reps == 0) return refuse("null output or no repeats");
+  if (!one.morphs || one.n_morphs != 1 || one.n_poses > 1) return refuse("one morph, alone or with its skin's pose");
+  const bool fused = one.n_poses == 1;
+  const glz_morph_weights& w = one.morphs[0];
   uint32_t first = 0, count = 0;
-  if (!posed_span(poses, n_poses, "pose_skins", first, count, err)) return false;
-  if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return err.fail(GLZ_E_ARG, "pose_skins: unknown mode");
+  if (fused && !animated_span(&one, "morph timing", first, count, err)) return false;
+  const auto it = morphs_.find(w.morph);
+  if (it == morphs_.end() || !w.weights || w.n_targets != it->second.n_targets) return refuse("no such morph, null weights, or a target count that is not the morph's");
+  const Morph& m = it->second;
+  if (fused && m.skin != one.poses[0].skin) return refuse("the pose is not of the morph's skin");
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  hipStream_t st = instance->stream;
+  std::vector<float4> packed;
+  DeviceBuffer<float4> bones, out;
+  DeviceBuffer<float> weights;
+  Events<2> t;
+  if (!hip_ok(out.alloc(2 * (size_t)m.n), "alloc", err) || !t.create(err)) return false;
+  auto once = [&] {
+    if (!upload_morph_weights(w, weights, st, err)) return false;
+    if (!fused) return hip_ok(launch_morph(st, morph_args(m, weights.ptr), out.ptr), "k_morph", err);
+    const Skin& s = skins_.at(m.skin);
+    return upload_bones(one.poses[0], packed, bones, st, err) &&
+           hip_ok(launch_morph_skin(st, morph_args(m, weights.ptr), s.joints.ptr, s.weights.ptr, bones.ptr, s.n_bones, out.ptr), "k_morph_skin", err);
+  };
+  if (!once()) return false;
+  (void)hipEventRecord(t.ev[0], st);
+  for (uint32_t i = 0; i < reps; ++i)
+    if (!once()) return false;
+  (void)hipEventRecord(t.ev[1], st);
+  if (!hip_ok(hipStreamSynchronize(st), "morph timing", err)) return false;
+  (void)hipEventElapsedTime(kernel_ms, t.ev[0], t.ev[1]);
+  *kernel_ms /= (float)reps;
+  if (bytes) {
+    *bytes = (uint64_t)m.n * (32 + 32 + 4) + (uint64_t)m.layout.slices.size() * 8 + m.n_entries * 32 + (uint64_t)m.n_targets * 4;
+    if (fused) *bytes += (uint64_t)m.n * (8 + 16) + (uint64_t)skins_.at(m.skin).n_bones * 48;
+  }
+  return true;
+}
+
+bool Scene::animate(const glz_animation& anim, int mode, Error& err) { return run_animation(anim, mode, "animate", err); }
+
+bool Scene::run_animation(const glz_animation& anim, int mode, const char* who, Error& err) {
+  uint32_t first = 0, count = 0;
+  if (!animated_span(&anim, who, first, count, err)) return false;
+  if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return err.fail(GLZ_E_ARG, std::string(who) + ": unknown mode");
   if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
   hipStream_t st = instance->stream;
   Composed at_exit{*this};
@@ -432,9 +637,8 @@ bool Scene::pose_skins(const glz_pose* poses, uint32_t n_poses, int mode, Error&
   const uint64_t hi = stale_count_ ? std::max<uint64_t>((uint64_t)stale_first_ + stale_count_, (uint64_t)first + count) : (uint64_t)first + count;
   stale_first_ = (uint32_t)lo;
   stale_count_ = (uint32_t)(hi - lo);
-  std::vector<std::vector<float4>> packed(n_poses);   // (they outlive the copies: update_geometry waits for the stream)
-  for (uint32_t i = 0; i < n_poses; ++i)
-    if (!skin_into(poses[i], geometry_.vertices.ptr, 0, packed[i], skins_.at(poses[i].skin).bones, st, err)) return false;
+  // (the uploads outlive the copies: update_geometry waits for the stream; the buffers are the scene's, reused while the calls name as much)
+  if (!animate_into(anim, geometry_.vertices.ptr, 0, uploads_, st, err)) return false;
   if (!hip_ok(launch_derivatives(st, geometry_.vertices.ptr, geometry_.indices.ptr, (uint32_t)(geometry_.derivatives.count / 3), geometry_.derivatives.ptr), "derivatives kernel", err))
     return false;
   if (!mirror_for_accel(err)) return false;   // two levels: the top level is rebuilt from the meshes' points

@@ -15,6 +15,7 @@
 #include "hip_util.h"
 #include "instance_boxes.h"
 #include "kernels.h"
+#include "morph.h"
 #include "parser.h"
 #include "shading_tables.h"
 #include "textures.h"
@@ -89,6 +90,33 @@ class Scene {
   const SceneData* host_data(Error& err);
   // everything that makes `src`'s skins, on this scene (a replica on another device): same ids, same bind poses
   bool copy_skins(const Scene& src, Error& err);
+  // ---- morph targets (morph.h holds the rule and the layout, kernels_morph.hip the kernels) ----
+  // A morph over [first_vertex, first_vertex + n_vertices): the targets are checked and transposed into the layout (post::pack_morph) and
+  // uploaded once.  Free-standing (skin == -1): its base is what the DEVICE holds in the range now, copied into a buffer the morph owns;
+  // attached: its base is the skin's bind buffer.  Returns the id (>= 0, counting up, never reused), or -1 with the error set; GLZ_E_ARG
+  // (nothing changes): see glz_renderer_add_morph.
+  int add_morph(const glz_morph& morph, Error& err);
+  bool remove_morph(int id, Error& err);   // the vertices stay as they are
+  // Morphs and poses in one update of the structure (glz_renderer_animate): each named free-standing morph by k_morph from its base, each
+  // named skin by k_skin, or by k_morph_skin where its morph is named too, into the vertex buffer; then what pose_skins does after its
+  // kernels, over the span from the lowest to the highest vertex written.  pose_skins is this with no morph named.
+  bool animate(const glz_animation& anim, int mode, Error& err);
+  // The checks of an animation (glz_renderer_animate lists them; the poses' are posed_span's) and the span it writes
+  bool animated_span(const glz_animation* anim, const char* who, uint32_t& first, uint32_t& count, Error& err) const;
+  // What an animation's kernels need uploaded per call: owned by whoever runs them, alive until the stream has run them
+  struct AnimationUploads {
+    std::vector<std::vector<float4>> packed;   // the host arrays the bone tables are copied from (first, so released last)
+    std::vector<DeviceBuffer<float4>> bones;   // one table per pose
+    std::vector<DeviceBuffer<float>> weights;  // one table per named morph
+  };
+  // Every kernel of one (checked) animation into `span`, which holds the vertices from span_first on: the scene's vertex buffer
+  // (animate), or motion_pass's previous-vertex buffer
+  bool animate_into(const glz_animation& anim, float4* span, uint32_t span_first, AnimationUploads& up, hipStream_t st, Error& err) const;
+  // One of the morph kernels alone, into a scratch buffer (glz_debug_morph_timing): timed as time_skin times k_skin; *bytes: what one
+  // launch moves, by the layout's own count
+  bool time_morph(const glz_animation& one, uint32_t reps, float* kernel_ms, uint64_t* bytes, Error& err) const;
+  // everything that makes `src`'s morphs, on this scene (a replica on another device), after copy_skins: same ids, same bases
+  bool copy_morphs(const Scene& src, Error& err);
   // Instance boxes of a two-level scene under its current transforms (host rule, or the device kernel); false with an empty result
   // for a flattened scene.  budget: kExactBoxBudget for the scene's own.
   bool instance_boxes(bool on_device, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err);
@@ -118,13 +146,33 @@ class Scene {
 
   struct Skin {
     uint32_t first = 0, n = 0, n_bones = 0;
-    DeviceBuffer<float4> bind, weights, bones;   // 2 a vertex; 1 a vertex; post::kSkinBoneRows a bone
+    DeviceBuffer<float4> bind, weights;          // 2 a vertex; 1 a vertex
     DeviceBuffer<uint2> joints;                  // four uint16 a vertex
     // host copies, for the replicas on other devices that are created later (DeviceGroup)
     std::vector<glz_vertex> h_bind;
     std::vector<uint16_t> h_joints;
     std::vector<float> h_weights;
+    int morph = -1;   // the attached morph's id
   };
+  struct Morph {
+    uint32_t first = 0, n = 0, n_targets = 0;
+    int skin = -1;                         // -1: free-standing, base is its own; else the skin whose bind buffer is the base
+    uint64_t n_entries = 0;
+    DeviceBuffer<float4> base, entries;    // 2 a vertex (free-standing only); the layout's
+    DeviceBuffer<uint32_t> counts;
+    DeviceBuffer<uint2> slices;
+    // host copies, for the replicas on other devices that are created later (DeviceGroup)
+    std::vector<glz_vertex> h_base;
+    post::MorphLayout layout;
+  };
+  int install_morph(int id, uint32_t first, int skin, std::vector<glz_vertex>&& base, post::MorphLayout&& layout, const float4* device_base, Error& err);
+  MorphArgs morph_args(const Morph& m, const float* weights) const;
+  // the bones of a (checked) pose, packed and on their way up through `bones` (post::kSkinBoneRows float4 a bone)
+  bool upload_bones(const glz_pose& pose, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const;
+  bool run_animation(const glz_animation& anim, int mode, const char* who, Error& err);   // pose_skins and animate
+  AnimationUploads uploads_;   // what the scene's own animate / pose_skins calls send up
+  std::map<int, Morph> morphs_;
+  int next_morph_ = 0;
   int install_skin(int id, uint32_t first, std::vector<glz_vertex>&& bind, std::vector<uint16_t>&& joints, std::vector<float>&& weights, uint32_t n_bones,
                    const float4* device_bind, Error& err);
   std::map<int, Skin> skins_;

@@ -397,6 +397,70 @@ int glz_renderer_pose_skins(glz_renderer*, const glz_pose* poses, uint32_t n_pos
 /* The scene's current vertices [first_vertex, first_vertex + n_vertices) as the device holds them (idle first).  GLZ_E_ARG: null output,
  * n_vertices == 0, a range past the vertex count. */
 int glz_renderer_read_vertices(glz_renderer*, uint32_t first_vertex, uint32_t n_vertices, glz_vertex* out);
+/* Build-defined: morph targets (blend shapes) -- applied on the device, ahead of the skin, so that a morphed character costs a few weights
+ * over the bus a frame instead of its vertices.
+ *
+ *   THE MORPH RULE (glz_renderer_animate, glz_host_morph; one definition, glaze_amd/csrc/morph.h, compiled for host and device; the tests
+ *   hold both sides to this text bit for bit).  A morph covers the vertices [first_vertex, first_vertex + n_vertices) and has n_targets
+ *   targets, 1 .. 65536.  Target t is a list of entries (v, dp[3], dn[3]): v is a vertex index relative to first_vertex, STRICTLY
+ *   ASCENDING within the target, so a target touches a vertex at most once.  A target given without an index list (vertices == NULL) is
+ *   dense: entry e is vertex e, and there are n_vertices of them.  d_normal is required; a caller without normal deltas passes zeros.
+ *   For a vertex with base position p, base normal n and texture coordinate t, let t1 < t2 < ... < tk be the targets that have an entry
+ *   for it, with weights w[ti] and deltas dp_i, dn_i.  Per component, in float32, with no contraction into fused multiply-adds, and in
+ *   exactly this order:
+ *     p' = ((…((p + w[t1] * dp_1) + w[t2] * dp_2) …) + w[tk] * dp_k)
+ *     n' = ((…((n + w[t1] * dn_1) + w[t2] * dn_2) …) + w[tk] * dn_k)
+ *     t' = t
+ *   No term is skipped for a zero weight (0 x inf is NaN here too, and -0 + 0 x d is +0).  Weights are used as given; the normal is not
+ *   renormalised.  A vertex no target touches comes out with the bits it went in with.
+ *   COMPOSITION WITH A SKIN: the morphed vertex is the BIND vertex THE SKINNING RULE then sees; the result equals
+ *   glz_host_skin(glz_host_morph(bind, ...), ...) bit for bit.
+ *
+ * glz_renderer_add_morph returns the morph's id (>= 0).  The targets are transposed once, on the host, into the layout the kernels read
+ * and uploaded; the caller's arrays are not kept.  A FREE-STANDING morph (skin == -1) owns a copy of its base, made on the device from
+ * what the scene's vertices hold in the range at the moment of the call; its range may overlap no other morph and no skin.  An ATTACHED
+ * morph (skin >= 0) has exactly its skin's range, its base IS the skin's bind pose (no copy), and a skin carries at most one;
+ * glz_renderer_remove_skin of a skin that still carries a morph is refused (GLZ_E_ARG).  Morphs belong to the SCENE object, as skins do:
+ * ids count up and are never reused, and every device of set_devices gets them.  GLZ_E_ARG (nothing changes): a null pointer,
+ * n_vertices == 0, a range past the vertex count, n_targets out of 1 .. 65536, an entry index >= n_vertices, indices not strictly
+ * ascending, a dense target whose n != n_vertices, null deltas where n > 0 (a target with n == 0 is allowed), an overlap (free-standing),
+ * an unknown skin, a skin that already has a morph, or a range that is not the skin's (attached).
+ * glz_renderer_remove_morph frees a morph; the vertices stay as they are.  GLZ_E_ARG: no such morph. */
+typedef struct glz_morph_target {
+  const uint32_t* vertices;     /* n indices relative to the morph's first vertex, strictly ascending; NULL: dense */
+  const float*    d_position;   /* 3 * n */
+  const float*    d_normal;     /* 3 * n */
+  uint32_t        n;
+} glz_morph_target;
+typedef struct glz_morph {
+  uint32_t                first_vertex, n_vertices;
+  const glz_morph_target* targets;
+  uint32_t                n_targets;
+  int                     skin;   /* -1: free-standing */
+} glz_morph;
+int glz_renderer_add_morph(glz_renderer*, const glz_morph*);
+int glz_renderer_remove_morph(glz_renderer*, int morph);
+/* Morphs and poses in one call, and the structure updated ONCE, over the span from the lowest to the highest vertex written.  A named
+ * free-standing morph is blended from its base into the scene's vertices; a named skin whose morph is not named is posed as
+ * glz_renderer_pose_skins poses it (from its unmorphed bind pose); a named skin whose morph is also named goes through the fused kernel:
+ * THE MORPH RULE, then THE SKINNING RULE, the vertex never in memory in between.  With n_morphs == 0 it is glz_renderer_pose_skins, and
+ * everything that promises holds: idle first, accumulation restarts, every device follows, glz_renderer_geometry_update_info describes it,
+ * hits and renders equal those of a scene created with the vertices the host references give.  The library keeps no weights and no bones
+ * between calls: every call starts from the bases.  GLZ_E_ARG (the scene is untouched): a null animation, or nothing named; an unknown
+ * morph, or a morph named twice; null weights; n_targets not the morph's; an attached morph named without its skin's pose; the pose
+ * checks of glz_renderer_pose_skins; an unknown mode.  glz_renderer_pose_skins itself knows nothing of morphs. */
+typedef struct glz_morph_weights {
+  int          morph;
+  const float* weights;     /* n_targets */
+  uint32_t     n_targets;   /* the morph's */
+} glz_morph_weights;
+typedef struct glz_animation {
+  const glz_morph_weights* morphs;
+  uint32_t                 n_morphs;
+  const glz_pose*          poses;
+  uint32_t                 n_poses;
+} glz_animation;
+int glz_renderer_animate(glz_renderer*, const glz_animation*, int mode);
 /* raytracer.rs:328-356: the texture array changed under the same materials and lights (the reference re-binds the
  * textures it shares with the realtime viewer); accumulation is NOT restarted, like the reference. */
 int glz_renderer_refresh_binded_textures(glz_renderer*, const glz_texture* textures, uint32_t n_textures);
@@ -662,6 +726,14 @@ int glz_renderer_reproject_from(glz_renderer*, const glz_previous_state*, const 
 int glz_renderer_read_motion_posed(glz_renderer*, const glz_previous_state*, const glz_pose* prev_poses, uint32_t n_prev_poses, float* out);
 int glz_renderer_reproject_posed(glz_renderer*, const glz_previous_state*, const glz_pose* prev_poses, uint32_t n_prev_poses, const float* prev_color,
                                  const float* prev_aov0, const float* prev_aov1, const glz_reproject_params* params_or_null, float* out);
+/* The same for a scene that is ANIMATED (glz_renderer_animate): state->vertices must be NULL; the previous-vertex buffer is the current
+ * vertices of the span copied device to device, then every named morph and skin run with the PREVIOUS weights and bones, as
+ * glz_renderer_animate runs them.  The planes equal, bit for bit, those of read_motion_from / reproject_from given the vertices the host
+ * references make of the previous animation over that span.  GLZ_E_ARG (nothing launched, nothing changed): the checks of
+ * read_motion_from / reproject_from, non-NULL state->vertices, and the animation checks of glz_renderer_animate. */
+int glz_renderer_read_motion_animated(glz_renderer*, const glz_previous_state*, const glz_animation* prev, float* out);
+int glz_renderer_reproject_animated(glz_renderer*, const glz_previous_state*, const glz_animation* prev, const float* prev_color, const float* prev_aov0,
+                                    const float* prev_aov1, const glz_reproject_params* params_or_null, float* out);
 
 /* Multi-GPU (one process per GPU): this renderer owns the 64x64-pixel tiles t with
  * t % world == rank; other pixels stay zero.  The exchange of the HDR accumulator itself is done
@@ -798,6 +870,11 @@ int glz_debug_motion_timing_from(glz_renderer*, const glz_previous_state*, float
 /* k_skin alone on one skin of the scene, into a scratch buffer (the scene is untouched): the device-event time of `reps` launches after
  * one that is not timed, divided by reps.  The pose is checked as glz_renderer_pose_skins checks it. */
 int glz_debug_skin_timing(glz_renderer*, const glz_pose* pose, uint32_t reps, float* kernel_ms_out);
+/* The morph kernels alone, into a scratch buffer (the scene is untouched), timed as glz_debug_skin_timing times k_skin.  `one` names one
+ * morph and no pose -- k_morph on it, from the skin's bind pose if it is attached -- or one attached morph and its skin's pose --
+ * k_morph_skin.  bytes_out (may be NULL): the bytes one launch moves by the layout's own count -- per vertex 32 in, 32 out and 4 of row
+ * length, 8 a slice, 32 an entry that is not padding, 4 a target; fused, also 24 a vertex of joints and weights and 48 a bone. */
+int glz_debug_morph_timing(glz_renderer*, const glz_animation* one, uint32_t reps, float* kernel_ms_out, uint64_t* bytes_out);
 int glz_debug_tonemap(glz_instance*, const float* rgba32f, uint64_t n_pixels, uint8_t* rgba8_out);
 /* The kernels' texture sampler on n coordinates uv2[2i], uv2[2i+1] of a scene texture, RGBA out: level 0 (texture2d) when
  * footprint4 is NULL, else the level of detail of footprint4[4i..4i+3] = (lod_base, du, dv, taps in 1..16) (texture2d_lod, after
@@ -899,6 +976,11 @@ int64_t glz_host_instance_boxes(const glz_scene_desc* desc, uint64_t budget, flo
  * n_bones == 0, a joint >= n_bones. */
 int glz_host_skin(const glz_vertex* bind, const uint16_t* joints, const float* weights, uint64_t n, const glz_transform* bones, uint32_t n_bones,
                   glz_vertex* out);
+/* THE MORPH RULE (glz_renderer_add_morph) on host arrays, no device: the reference k_morph is compared with bit for bit; it runs through
+ * the same layout packer as glz_renderer_add_morph.  base / out: n vertices (out may be base itself); targets, n_targets: as glz_morph
+ * has them, over n vertices; weights: n_targets.  GLZ_E_ARG: a null pointer with n > 0, and what glz_renderer_add_morph refuses of a
+ * morph's targets. */
+int glz_host_morph(const glz_vertex* base, uint64_t n, const glz_morph_target* targets, uint32_t n_targets, const float* weights, glz_vertex* out);
 
 #ifdef __cplusplus
 }

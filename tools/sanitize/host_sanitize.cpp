@@ -1,6 +1,6 @@
 // AddressSanitizer / UBSan run of the host-only parts of libglaze_hip (the GPU parts cannot run under sanitizers on
 // this pool): .glaze reader and writer with their own xz / PNG / JPEG codecs, the OBJ converter, the host SAH builder, the host
-// rule of the instance boxes and the skinning reference.
+// rule of the instance boxes, the skinning reference, and the morph reference with its layout packer.
 // Built and run by tools/sanitize/run.sh; exits non-zero on the first failure (the sanitizers abort on their findings).
 #include <cmath>
 #include <cstdio>
@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "parser.h"
 #include "serializer.h"
+#include "morph.h"
 #include "skin.h"
 
 using namespace glz;
@@ -267,6 +268,34 @@ int main(int argc, char** argv) {
     REQUIRE(bind[0].vv[0] == out[0].vv[0] && bind.back().vv[0] == out.back().vv[0]);
     post::host_skin(out.data() + out.size() - 1, joints.data(), weights.data(), 1, bones.data(), n_bones, out.data() + out.size() - 1);
     post::host_skin(nullptr, nullptr, nullptr, 0, bones.data(), n_bones, nullptr);
+  }
+  // 9. the morph reference and the layout packer (morph_host.cpp): one vertex, no vertices, 65 vertices with a slice that is wholly empty
+  // and another whose only entry is its last lane's, a target with n == 0, a dense target, `out` aliasing `base`, and refused targets
+  {
+    auto run = [&](uint32_t n, const std::vector<glz_morph_target>& targets, const std::vector<float>& weights, glz_vertex* base, glz_vertex* out) {
+      post::MorphLayout layout;
+      std::string why;
+      if (!post::pack_morph(n, targets.data(), (uint32_t)targets.size(), layout, why)) return false;
+      post::host_morph(base, layout, weights.data(), out);
+      return true;
+    };
+    std::vector<float> d(3 * 65, 0.5f);
+    std::vector<glz_vertex> base(sd.vertices.begin(), sd.vertices.begin() + 65), out(65);
+    const uint32_t one[] = {0}, last_lanes[] = {63}, up[] = {3, 7, 63}, twice[] = {3, 3}, past[] = {65};
+    const std::vector<float> w = {2.0f, -1.0f, 4.0f};
+    REQUIRE(run(1, {{one, d.data(), d.data(), 1}}, w, base.data(), out.data()) && out[0].vv[0] == base[0].vv[0] + 1.0f && out[0].vt[0] == base[0].vt[0]);
+    REQUIRE(run(1, {{nullptr, d.data(), d.data(), 1}, {nullptr, nullptr, nullptr, 0}}, w, base.data(), out.data()) && out[0].vn[2] == base[0].vn[2] + 1.0f);
+    REQUIRE(run(0, {{nullptr, nullptr, nullptr, 0}}, w, nullptr, nullptr));                       // no vertices
+    // 65 vertices: slice 0 holds lane 63 alone (and rows 3 and 7 of another target), slice 1 -- vertex 64 -- is empty
+    REQUIRE(run(65, {{last_lanes, d.data(), d.data(), 1}, {nullptr, nullptr, nullptr, 0}, {up, d.data(), d.data(), 3}}, w, base.data(), out.data()));
+    REQUIRE(out[63].vv[1] == (base[63].vv[1] + 1.0f) + 2.0f && out[3].vv[1] == base[3].vv[1] + 2.0f && out[64].vv[0] == base[64].vv[0] && out[0].vn[1] == base[0].vn[1]);
+    REQUIRE(run(65, {{last_lanes, d.data(), d.data(), 1}}, w, base.data(), out.data()) && out[62].vv[0] == base[62].vv[0]);   // an empty slice next to one entry
+    const std::vector<glz_vertex> morphed = out;
+    REQUIRE(run(65, {{last_lanes, d.data(), d.data(), 1}}, w, base.data(), base.data()) && base[63].vv[2] == morphed[63].vv[2] && base[64].vv[2] == morphed[64].vv[2]);   // in place
+    std::vector<glz_vertex> scratch(65);
+    REQUIRE(!run(65, {{twice, d.data(), d.data(), 2}}, w, base.data(), scratch.data()) && !run(65, {{past, d.data(), d.data(), 1}}, w, base.data(), scratch.data()));
+    REQUIRE(!run(65, {{nullptr, d.data(), d.data(), 64}}, w, base.data(), scratch.data()) && !run(65, {{up, nullptr, d.data(), 3}}, w, base.data(), scratch.data()));
+    REQUIRE(!run(65, {}, w, base.data(), scratch.data()));
   }
   printf("host sanitize: ok\n");
   return 0;
