@@ -584,6 +584,11 @@ class RayTraceScene:
                                                  _ptr(value), _ptr(pdf)))
         return value, pdf
 
+    def debug_set_spectra(self, material_id, ior, ior2abs2):
+        """metal spectra of the caller's (16 bins each) for one material, for debug_bsdf_value / debug_bsdf_sample (glz_debug_scene_set_spectra)"""
+        n, a = np.ascontiguousarray(ior, np.float32).reshape(16), np.ascontiguousarray(ior2abs2, np.float32).reshape(16)
+        abi.check(abi.lib().glz_debug_scene_set_spectra(self._h, material_id, _ptr(n), _ptr(a)))
+
     def debug_bsdf_sample(self, material_id, wo, rand3, uv=(0.5, 0.5), frame=None):
         wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
         r = np.ascontiguousarray(rand3, np.float32).reshape(-1, 3)

@@ -296,7 +296,8 @@ PROTOTYPES = {
     "glz_debug_sample_texture": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint64, _P]),
     "glz_debug_detmath": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_uint64]),
     "glz_debug_color_to_spec": (C.c_int, [_P, C.c_int, _P, C.c_uint64, _P]),
-    "glz_debug_bsdf_value": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64, _P, _P]),
+    "glz_debug_scene_set_spectra": (C.c_int, [_P, C.c_uint32, _P, _P]),
+    "glz_debug_bsdf_value": (C.c_int,[_P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64, _P, _P]),
     "glz_debug_bsdf_sample": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P, _P, _P]),
     "glz_debug_light_sample": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint64, C.c_float, _P, _P, _P, _P]),
     "glz_debug_read_texture_level": (C.c_int64, [_P, C.c_uint32, C.c_uint32, _P, C.c_int64, _P, _P]),
@@ -342,6 +343,8 @@ PROTOTYPES = {
     "glz_debug_guide_chain": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
     "glz_host_traversal_offsets_fit": (C.c_int, [C.c_uint64] * 6),
     "glz_host_sky_row_pairs": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "glz_host_conductor_finite": (C.c_int, [_P, _P, _P]),
+    "glz_host_metal_spectra": (C.c_int, [C.c_uint32, _P, _P]),
 }
 
 _LIB = None

@@ -567,6 +567,13 @@ int glz_debug_bsdf_sample(glz_scene* h, uint32_t material_id, const float* wo3, 
   });
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_debug_scene_set_spectra(glz_scene* h, uint32_t material_id, const float ior[16], const float ior2abs2[16]) {
+  GLZ_GUARD_BEGIN
+  if (!h || !h->s || !ior || !ior2abs2) return fail(GLZ_E_ARG, "null argument");
+  Error e;
+  GLZ_RET(h->s->debug_set_spectra(material_id, ior, ior2abs2, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_debug_light_sample(glz_scene* h, uint32_t light_index, const float* pos3, const float* rand3, uint64_t n, float scene_radius, float* wi3,
                            float* dist, float* pdf, float* emission16) {
   GLZ_GUARD_BEGIN
@@ -687,6 +694,15 @@ int glz_host_srgb8_thresholds(float thresholds_out[256]) {
 int glz_host_sky_row_pairs(const float* marginal_values, const float* conditional_integrals, uint64_t n, float* pairs_out) {
   if (n != 0 && (!marginal_values || !conditional_integrals || !pairs_out)) return fail(GLZ_E_ARG, "glz_host_sky_row_pairs: null array");
   sky_row_pairs(marginal_values, conditional_integrals, (size_t)n, pairs_out);
+  return GLZ_OK;
+}
+int glz_host_conductor_finite(const float ior[16], const float ior2abs2[16], int* flag_out) {
+  if (!ior || !ior2abs2 || !flag_out) return fail(GLZ_E_ARG, "glz_host_conductor_finite: null argument");
+  *flag_out = conductor_finite(ior, ior2abs2) ? 1 : 0;
+  return GLZ_OK;
+}
+int glz_host_metal_spectra(uint32_t metal, float ior_out[16], float ior2abs2_out[16]) {
+  if (!ior_out || !ior2abs2_out || !metal_spectra(metal, ior_out, ior2abs2_out)) return fail(GLZ_E_ARG, "glz_host_metal_spectra: no such metal, or a null output");
   return GLZ_OK;
 }
 

@@ -374,7 +374,7 @@ struct MatScalars {
   uint32_t diffuse, roughness, metalness, opacity, normal, bsdf_index;
   float roughness_mul, metalness_mul, anisotropy, ior_dielectric;
   uint32_t is_specular;
-  const MetalSpectra* spectra;   // metal_ior / metal_fresnel
+  uint32_t spectra;   // MatCompact::spectra: the index of the pair (material_spectra) | kSpectraConductorFinite
 };
 GLZ_D MatScalars load_material(const DeviceScene& S, uint32_t id) {
   const float4* q = reinterpret_cast<const float4*>(&S.mat_compact[id]);
@@ -384,9 +384,11 @@ GLZ_D MatScalars load_material(const DeviceScene& S, uint32_t id) {
   r.diffuse = __float_as_uint(b.x); r.roughness = __float_as_uint(b.y); r.metalness = __float_as_uint(b.z); r.opacity = __float_as_uint(b.w);
   r.normal = __float_as_uint(c.x); r.bsdf_index = __float_as_uint(c.y); r.roughness_mul = c.z; r.metalness_mul = c.w;
   r.anisotropy = d.x; r.ior_dielectric = d.y; r.is_specular = __float_as_uint(d.z);
-  r.spectra = &S.metal_spectra[__float_as_uint(a.w)];
+  r.spectra = __float_as_uint(a.w);
   return r;
 }
+// metal_ior / metal_fresnel of a material
+GLZ_D const MetalSpectra& material_spectra(const DeviceScene& S, const MatScalars& m) { return S.metal_spectra[m.spectra & ~kSpectraConductorFinite]; }
 
 struct SurfacePoint {
   vec3 woW;
@@ -452,6 +454,23 @@ GLZ_D void fetch_material_textures(const DeviceScene& S, SurfacePoint& P, const 
 }
 GLZ_D vec3 diffuse_tint(const DeviceScene&, const SurfacePoint& P) { return P.tint; }
 
+// The Uber specular lobe's value, mix(fd, fc, metalness) * term per bin (mat_uber_value.rcall:49-52, mat_uber_sample_value.rcall the same).
+// Where the metalness is zero the conductor term fc is multiplied by zero, and the product is a zero of either sign as long as fc is finite:
+// fd * (1 - 0) + (+-0) has fd's bits (fd is 1 or a sum of squares halved, never -0; a NaN stays that NaN).  fc is finite in every bin when
+// the pair is conductor_finite (shading_tables.h) and |c| <= 2 -- a NaN cosine fails the comparison.  Such a lane evaluates the same
+// expression with +0 for fc, once for all bins, and never reads the spectra; every other lane does what it always did.  The ordinary
+// non-metallic material (metalness_mul = 0, or a metalness map's black texel) is such a lane: the conductor term is 32 floats from LDS and
+// 16 x 2 correctly rounded divisions, at both call sites.
+GLZ_D void uber_specular_value(const DeviceScene& S, const MatScalars& m, float c, float fd, float metalness, float term, Spec& value) {
+  if ((m.spectra & kSpectraConductorFinite) != 0u && metalness == 0.0f && fabsf(c) <= 2.0f) {
+    const float v = gl_mix(fd, 0.0f, metalness) * term;
+    GLZ_BINS value.w[i] = v;
+    return;
+  }
+  const Spec fc = fresnel_conductor(c, material_spectra(S, m).ior, material_spectra(S, m).fresnel);
+  GLZ_BINS value.w[i] = gl_mix(fd, fc.w[i], metalness) * term;
+}
+
 // BSDF evaluation for next-event estimation; returns the pdf (0 = no contribution).
 GLZ_D float bsdf_eval(const DeviceScene& S, const SurfacePoint& P, vec3 wiW, float xi, Spec& value) {
   const MatScalars& m = P.mat;
@@ -466,7 +485,7 @@ GLZ_D float bsdf_eval(const DeviceScene& S, const SurfacePoint& P, vec3 wiW, flo
   if (kind == kBsdfMetal) {   // mat_metal_value.rcall:19-44
     vec3 wh = normalize3(wo + wi);
     if (!(wo.z * wi.z > 0.0f)) return 0.0f;
-    Spec F = fresnel_conductor(dot3(wi, wh), m.spectra->ior, m.spectra->fresnel);
+    Spec F = fresnel_conductor(dot3(wi, wh), material_spectra(S, m).ior, material_spectra(S, m).fresnel);
     vec2 a = anisotropic_alpha(P.rough_tex * m.roughness_mul, m.anisotropy);
     float d = ggx_d(wh, a);
     float g = ggx_g(wo, wi, a);
@@ -510,9 +529,8 @@ GLZ_D float bsdf_eval(const DeviceScene& S, const SurfacePoint& P, vec3 wiW, flo
     dielectric_etas(m, wo.z, etai, etat);
     Lobe L = reflect_lobe(wo, wi, wh, a);
     float fd = fresnel_dielectric(L.costi, etai, etat);
-    Spec fc = fresnel_conductor(L.costi, m.spectra->ior, m.spectra->fresnel);
     float term = L.d * L.g / (4.0f * L.cwo * L.cwi);
-    GLZ_BINS value.w[i] = gl_mix(fd, fc.w[i], metalness) * term;
+    uber_specular_value(S, m, L.costi, fd, metalness, term, value);
     return check_nan(same * 0.5f * L.pdf);
   }
   value = from_surface_color(diffuse_tint(S, P) * oren_nayar(roughness, wo, wi));
@@ -542,7 +560,7 @@ GLZ_D float bsdf_sample(const DeviceScene& S, const SurfacePoint& P, vec3 xi, Sp
     return fabsf(wi.z) * kInvPi;
   }
   if (kind == kBsdfMirror) {   // mat_mirror_sample_value.rcall:16-34
-    Spec F = fresnel_conductor(wo.z, m.spectra->ior, m.spectra->fresnel);
+    Spec F = fresnel_conductor(wo.z, material_spectra(S, m).ior, material_spectra(S, m).fresnel);
     wiW = normalize3(to_world(mk3(-wo.x, -wo.y, wo.z), P.frame));
     value = spec_div(F, fabsf(wo.z));
     return 1.0f;
@@ -576,7 +594,7 @@ GLZ_D float bsdf_sample(const DeviceScene& S, const SurfacePoint& P, vec3 xi, Sp
     float d = ggx_d(wh, a);
     float g = ggx_g(wo, wi, a);
     float gp = ggx_pdf(d, a, wo, wh);
-    Spec F = fresnel_conductor(dot3(wi, wh), m.spectra->ior, m.spectra->fresnel);
+    Spec F = fresnel_conductor(dot3(wi, wh), material_spectra(S, m).ior, material_spectra(S, m).fresnel);
     float term = d * g / (4.0f * fabsf(wo.z) * fabsf(wi.z));
     float pdf = gp / (4.0f * dot3(wo, wh));
     value = spec_scale(F, term);
@@ -625,9 +643,8 @@ GLZ_D float bsdf_sample(const DeviceScene& S, const SurfacePoint& P, vec3 xi, Sp
     wi = -normalize3(gl_reflect(wo, wh));
     Lobe L = reflect_lobe(wo, wi, wh, a);
     float fd = fresnel_dielectric(L.costi, etai, etat);
-    Spec fc = fresnel_conductor(L.costi, m.spectra->ior, m.spectra->fresnel);
     float term = L.d * L.g / (4.0f * L.cwo * L.cwi);
-    GLZ_BINS value.w[i] = gl_mix(fd, fc.w[i], metalness) * term;
+    uber_specular_value(S, m, L.costi, fd, metalness, term, value);
     pdf = check_nan(0.5f * L.pdf);
   } else {
     wi = cosine_hemisphere(xi.x, xi.y, wo.z);

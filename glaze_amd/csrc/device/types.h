@@ -81,9 +81,12 @@ static_assert(sizeof(MetalSpectra) == 128, "MetalSpectra is 8 x 16 bytes");
 // (ShadingTables::build_materials); k_shade and k_path stage THESE tables in LDS.  The spectra are 128 of an RTMaterial's 208 bytes and
 // only conductor lobes read them; left in the RTMaterial array in memory they cost those lobes sixteen 16-byte loads per pixel
 // (measured: EXPERIMENTS.md).
+// The top bit of the index word says that the pair is `conductor_finite` (shading_tables.h): fresnel_conductor of these spectra is finite
+// in every bin for every cosine |c| <= 2, which lets the Uber lobe drop the term where a zero metalness multiplies it.
+constexpr uint32_t kSpectraConductorFinite = 0x80000000u;
 struct alignas(16) MatCompact {
   float diffuse_mul[3];
-  uint32_t spectra;
+  uint32_t spectra;   // index | kSpectraConductorFinite
   float emissive_col[4];
   uint32_t diffuse;
   uint32_t roughness;

@@ -222,6 +222,12 @@ bool Scene::update_materials_and_lights(const glz_material* mats, uint32_t n_mat
   return hip_ok(hipStreamSynchronize(st), "update_materials_and_lights", err);
 }
 
+bool Scene::debug_set_spectra(uint32_t material, const float* ior, const float* ior2abs2, Error& err) {
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  Composed at_exit{*this};
+  return tables_.debug_set_spectra(instance->stream, material, ior, ior2abs2, err);
+}
+
 // refresh_binded_textures (raytracer.rs:328-356): the texture array changed under the same materials and lights
 bool Scene::refresh_textures(const glz_texture* textures, uint32_t n, Error& err) {
   const size_t nm = data.materials.size();

@@ -55,6 +55,8 @@ class Scene {
   bool update_materials_and_lights(const glz_material* mats, uint32_t n_mats, const glz_light* lights, uint32_t n_lights,
                                    const glz_texture* textures, uint32_t n_textures, Error& err);
   bool refresh_textures(const glz_texture* textures, uint32_t n, Error& err);   // refresh_binded_textures, raytracer.rs:328-356
+  // glz_debug_scene_set_spectra: metal spectra of the caller's for one material, for the debug BSDF hooks (ShadingTables::debug_set_spectra)
+  bool debug_set_spectra(uint32_t material, const float* ior, const float* ior2abs2, Error& err);
   // New object -> world transforms, as many as the scene has (instances index them).  The structure is rebuilt with the builder, pair
   // ratio and shape the scene was created with, and equals a scene created with these transforms (Accel::rebuild).  Lights, sky,
   // materials and textures are left alone.

@@ -22,6 +22,34 @@ static uint32_t sbt_callable_index(uint8_t mtype) {   // materials/material.rs:2
   }
 }
 
+bool metal_spectra(uint32_t metal, float* ior_out, float* ior2abs2_out) {
+  if (metal >= GLZ_METAL_COUNT) return false;
+  for (int i = 0; i < 16; ++i) {
+    const float n = GLZ_METAL_N[metal][i], k = GLZ_METAL_K[metal][i];
+    ior_out[i] = n;
+    ior2abs2_out[i] = (n * n) + (k * k);
+  }
+  return true;
+}
+
+bool conductor_finite(const float* ior, const float* ior2abs2) {
+  const double big = 1152921504606846976.0;   // 2^60
+  for (int i = 0; i < 16; ++i) {
+    const double n = ior[i], a = ior2abs2[i];
+    if (!std::isfinite(n) || !std::isfinite(a) || std::fabs(n) > big || std::fabs(a) > big) return false;
+    const double need = (std::fabs(a) + 4.0 * std::fabs(n) + 5.0) / 1024.0;
+    // a + 2nc + c^2 on [-2, 2]: the ends, and the vertex c = -n where it lies inside
+    double lo = std::fmin(a + 4.0 * n + 4.0, a - 4.0 * n + 4.0);
+    if (std::fabs(n) <= 2.0) lo = std::fmin(lo, a - n * n);
+    if (!(lo >= need)) return false;
+    // a c^2 + 2nc + 1: the ends, and the vertex c = -n / a (for a < 0 the maximum, which lowers nothing)
+    lo = std::fmin(4.0 * a + 4.0 * n + 1.0, 4.0 * a - 4.0 * n + 1.0);
+    if (a != 0.0 && std::fabs(n) <= 2.0 * std::fabs(a)) lo = std::fmin(lo, 1.0 - n * n / a);
+    if (!(lo >= need)) return false;
+  }
+  return true;
+}
+
 // load_raytrace_materials_to_gpu (scene.rs:1821-1860)
 bool ShadingTables::build_materials(hipStream_t st, const std::vector<glz_material>& materials, Error& err) {
   h_materials.clear();
@@ -32,12 +60,7 @@ bool ShadingTables::build_materials(hipStream_t st, const std::vector<glz_materi
       r.emissive_col[i] = m.has_emissive ? (float)m.emissive_col[i] / 255.0f : 0.0f;
     }
     r.diffuse_mul[3] = r.emissive_col[3] = 1.0f;
-    const unsigned metal = m.metal < GLZ_METAL_COUNT ? m.metal : 0;
-    for (int i = 0; i < 16; ++i) {
-      const float n = GLZ_METAL_N[metal][i], k = GLZ_METAL_K[metal][i];
-      r.metal_ior.w[i] = n;
-      r.metal_fresnel.w[i] = (n * n) + (k * k);
-    }
+    metal_spectra(m.metal < GLZ_METAL_COUNT ? m.metal : 0, r.metal_ior.w, r.metal_fresnel.w);
     r.diffuse = m.diffuse;
     r.roughness = m.roughness;
     r.metalness = m.metalness;
@@ -52,18 +75,33 @@ bool ShadingTables::build_materials(hipStream_t st, const std::vector<glz_materi
     r.is_emissive = m.has_emissive ? 1u : 0u;
     h_materials.push_back(r);
   }
+  return upload_materials(st, err);
+}
+
+bool ShadingTables::debug_set_spectra(hipStream_t st, uint32_t material, const float* ior, const float* ior2abs2, Error& err) {
+  if (material >= h_materials.size()) return err.fail(GLZ_E_ARG, "no such material");
+  memcpy(h_materials[material].metal_ior.w, ior, 64);
+  memcpy(h_materials[material].metal_fresnel.w, ior2abs2, 64);
+  return upload_materials(st, err);
+}
+
+bool ShadingTables::upload_materials(hipStream_t st, Error& err) {
   // the tables the shading kernels read at every hit, derived from the records just made (device/types.h): MatCompact, and the spectra
-  // on their own, each distinct pair once
+  // on their own, each distinct pair once; a material's index word says whether its pair is conductor_finite
   h_mat_compact.clear();
   h_metal_spectra.clear();
+  std::vector<uint32_t> finite;   // per distinct pair: kSpectraConductorFinite or 0
   for (const RTMaterial& r : h_materials) {
     MetalSpectra sp;
     sp.ior = r.metal_ior;
     sp.fresnel = r.metal_fresnel;
     size_t slot = 0;
     while (slot < h_metal_spectra.size() && memcmp(&h_metal_spectra[slot], &sp, sizeof(sp)) != 0) ++slot;
-    if (slot == h_metal_spectra.size()) h_metal_spectra.push_back(sp);
-    h_mat_compact.push_back(compact_material(r, (uint32_t)slot));
+    if (slot == h_metal_spectra.size()) {
+      h_metal_spectra.push_back(sp);
+      finite.push_back(conductor_finite(sp.ior.w, sp.fresnel.w) ? kSpectraConductorFinite : 0u);
+    }
+    h_mat_compact.push_back(compact_material(r, (uint32_t)slot | finite[slot]));
   }
   // The three device arrays belong together (MatCompact::spectra indexes the spectra table, both mirror the RTMaterial array): they are
   // uploaded into new buffers and take the old ones' place only when all three are there, so a failed upload leaves the device with the

@@ -14,9 +14,23 @@ namespace glz {
 // (glz_host_sky_row_pairs exposes it).
 void sky_row_pairs(const float* marginal_values, const float* conditional_integrals, size_t n, float* pairs_out);
 
+// Whether fresnel_conductor (device/shading.h) of a spectra pair -- n = ior, a = ior2abs2, 16 bins each -- is finite in every bin for
+// every cosine |c| <= 2, so that its product with a zero metalness is a zero (kSpectraConductorFinite; glz_host_conductor_finite exposes
+// it).  In double precision, per bin: n and a finite and at most 2^60 in magnitude, and the exact minima over |c| <= 2 of the routine's two
+// denominators, a + 2nc + c^2 and a c^2 + 2nc + 1 (quadratics in c: the vertex and the two ends), at least 2^-10 M with
+// M = |a| + 4|n| + 5.  4 M bounds every term, numerator and denominator (|c| <= 2: |a c^2| <= 4|a|); the float evaluation of a
+// denominator is off by a few ulp of that, some 2^-19 M, five hundred times less than the margin, so the float denominators are normal and
+// non-zero and the quotients stay below 2^12.  A condition, not a tuned value.  A NaN or infinite entry fails it.
+bool conductor_finite(const float* ior, const float* ior2abs2);
+// The pair of built-in metal `metal` (include/glz_tables.h) as a material record carries it: n, and n^2 + k^2 in float; false past the table
+bool metal_spectra(uint32_t metal, float* ior_out, float* ior2abs2_out);
+
 class ShadingTables {
  public:
   bool build_materials(hipStream_t st, const std::vector<glz_material>& materials, Error& err);
+  // glz_debug_scene_set_spectra: gives one material's record spectra no built-in metal has and derives the tables again, flag included;
+  // the next build_materials puts the material's own metal back
+  bool debug_set_spectra(hipStream_t st, uint32_t material, const float* ior, const float* ior2abs2, Error& err);
   // n_instances: the instances the device got (an area light names one of them)
   bool build_lights_and_sky(hipStream_t st, const SceneData& data, size_t n_instances, Error& err);
   void forget_sky_distribution() { sky_distribution_tex_ = 0xFFFFFFFFu; }   // the sky map's texels may have changed: rebuilt by the next build
@@ -37,6 +51,7 @@ class ShadingTables {
   uint32_t lights_no = 0;   // lights.len() after reorder_lights (scene.rs:1549)
 
  private:
+  bool upload_materials(hipStream_t st, Error& err);   // h_mat_compact and h_metal_spectra from h_materials, then the three device arrays
   DeviceBuffer<RTMaterial> d_materials_;
   DeviceBuffer<MatCompact> d_mat_compact_;
   DeviceBuffer<MetalSpectra> d_metal_spectra_;

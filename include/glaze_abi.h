@@ -896,6 +896,11 @@ int glz_debug_bsdf_sample(glz_scene*, uint32_t material_id, const float* wo3, co
                           uint64_t n, float* wi3_out, float* value16_out, float* pdf_out);
 int glz_debug_light_sample(glz_scene*, uint32_t light_index, const float* pos3, const float* rand3, uint64_t n, float scene_radius,
                            float* wi3_out, float* dist_out, float* pdf_out, float* emission16_out);
+/* For the two BSDF hooks above: gives one material's record metal spectra of the caller's (ior = n, ior2abs2 = n^2 + k^2, 16 bins each; any
+ * floats, NaN and zeros included -- pairs no built-in metal has), and derives the shading tables again as a material update does, the
+ * glz_host_conductor_finite flag included.  For a scene no renderer is rendering; the next glz_renderer_update_materials_and_lights puts
+ * the material's own metal back.  A material id out of range is GLZ_E_ARG. */
+int glz_debug_scene_set_spectra(glz_scene*, uint32_t material_id, const float ior[16], const float ior2abs2[16]);
 
 /* The device filter of glz_denoise_params on host arrays (w*h*4 floats each, row-major): upload, kernels, read back.  params NULL = defaults. */
 int glz_debug_denoise(glz_instance*, uint32_t w, uint32_t h, const float* result, const float* aov0, const float* aov1,
@@ -943,6 +948,14 @@ int glz_host_srgb8_thresholds(float thresholds_out[256]);
 /* the per-row table a sky sample reads once its row is found, as scene creation builds it from the sky's marginal values and conditional
  * integrals (n rows each): pairs_out[2 y] = marginal_values[y], pairs_out[2 y + 1] = conditional_integrals[y] -- the same floats, interleaved */
 int glz_host_sky_row_pairs(const float* marginal_values, const float* conditional_integrals, uint64_t n, float* pairs_out);
+/* the flag scene creation and material updates give a pair of metal spectra (ior = n, ior2abs2 = n^2 + k^2, 16 bins each): *flag_out = 1
+ * when the conductor Fresnel term of the pair is finite in every bin for every cosine |c| <= 2 -- both are finite and at most 2^60 in
+ * magnitude, and the minima over |c| <= 2 of a + 2nc + c^2 and of a c^2 + 2nc + 1 are at least 2^-10 (|a| + 4|n| + 5), in double
+ * precision -- else 0.  An Uber hit of a flagged pair whose metalness is zero and whose cosine is within |c| <= 2 skips the term: its
+ * product with the metalness is a zero, and the result has the same bits. */
+int glz_host_conductor_finite(const float ior[16], const float ior2abs2[16], int* flag_out);
+/* the pair of built-in metal `metal` (glz_material::metal, below GLZ_METAL_COUNT of glz_tables.h) as a material's record carries it */
+int glz_host_metal_spectra(uint32_t metal, float ior_out[16], float ior2abs2_out[16]);
 /* the size check of scene creation (glz_instance_set_bvh_builder: "Size limit") on counts given by the caller, nothing built or
  * allocated: 4-wide nodes, 8-wide nodes, leaf records, instance records, lanes of the largest persistent grid, spilt stack words per
  * lane.  GLZ_OK when every table stays below 2^32 bytes, else GLZ_E_INVALID_DATA with the message scene creation fails with. */
