@@ -21,10 +21,10 @@ import numpy as np
 
 from . import abi
 from .abi import GlazeError
-from .scene_desc import VERTEX_DTYPE, SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
+from .scene_desc import MESH_DTYPE, VERTEX_DTYPE, SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
 
 __all__ = ["parse", "converted_file", "ParsedScene", "RayTraceInstance", "RayTraceScene", "RayTraceRenderer", "Integrator",
-           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points", "host_skin", "host_morph",
+           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points", "host_skin", "host_morph", "host_vertex_normals", "host_weld_groups",
            "host_project_constants"]
 
 
@@ -304,6 +304,40 @@ def host_morph(base, targets, weights):
     arr, keep = _morph_targets(targets, v.shape[0])
     out = v.copy()
     abi.check(abi.lib().glz_host_morph(_ptr(v), v.shape[0], C.cast(arr, C.c_void_p), len(targets), _ptr(w), _ptr(out)))
+    return out
+
+
+def _group_array(groups, n):
+    """n uint32 labels, or None"""
+    if groups is None:
+        return None
+    raw = np.ascontiguousarray(groups)
+    if raw.shape != (int(n),) or raw.dtype.kind not in "iu" or (raw.size and (raw.min() < 0 or raw.max() > 0xFFFFFFFF)):
+        raise ValueError("groups must be one label per vertex of the range")
+    return np.ascontiguousarray(raw, np.uint32)
+
+
+def host_vertex_normals(vertices, indices, meshes, first, n, groups=None):
+    """glz_host_vertex_normals: the normal rule (include/glaze_abi.h holds the specification) on the host, no device, the reference of
+    k_face_vectors and k_vertex_normals.  vertices: a scene's whole vertex array in any form update_vertices takes; indices: its uint32
+    index array; meshes: its MESH_DTYPE array; [first, first + n): the set's range; groups: n labels below n, or None.  Returns the
+    range's vertices with the rule's normals, (n, 8) float32."""
+    v = _vertex_array(vertices)
+    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+    m = np.ascontiguousarray(meshes, MESH_DTYPE).reshape(-1)
+    g = _group_array(groups, n)
+    out = np.zeros((int(n), 8), np.float32)
+    abi.check(abi.lib().glz_host_vertex_normals(_ptr(v), v.shape[0], _ptr(idx), idx.shape[0], _ptr(m), m.shape[0], int(first), int(n),
+                                                None if g is None else _ptr(g), _ptr(out)))
+    return out
+
+
+def host_weld_groups(vertices):
+    """glz_host_weld_groups: one uint32 label per vertex, the lowest index whose position and normal words are bit-equal to its own --
+    what add_normals(groups=...) takes to keep a seam of duplicated vertices smooth."""
+    v = _vertex_array(vertices)
+    out = np.zeros(v.shape[0], np.uint32)
+    abi.check(abi.lib().glz_host_weld_groups(_ptr(v), v.shape[0], _ptr(out)))
     return out
 
 
@@ -844,6 +878,30 @@ class RayTraceRenderer:
         ms, nbytes = C.c_float(0.0), C.c_uint64(0)
         abi.check(abi.lib().glz_debug_morph_timing(self._h, C.cast(C.byref(a), C.c_void_p), int(reps), C.cast(C.byref(ms), C.c_void_p), C.cast(C.byref(nbytes), C.c_void_p)))
         return ms.value, nbytes.value
+
+    def add_normals(self, first, n_vertices, groups=None):
+        """A normal set over the scene's vertices [first, first + n_vertices): from now on their normals are the normal rule
+        (include/glaze_abi.h) of the positions the device holds, made again after every update_vertices, pose and animate that reaches
+        them -- in place of the normals those calls write.  groups: n_vertices labels below n_vertices (equal labels share one normal),
+        None = every vertex on its own, "weld" = host_weld_groups of what read_vertices gives for the range.  Returns the set's id."""
+        if isinstance(groups, str):
+            if groups != "weld":
+                raise ValueError("groups must be labels, None or 'weld'")
+            groups = host_weld_groups(self.read_vertices(first, n_vertices))
+        g = _group_array(groups, n_vertices)
+        s = abi.Normals(int(first), int(n_vertices), None if g is None else _ptr(g))
+        return abi.check(abi.lib().glz_renderer_add_normals(self._h, C.cast(C.byref(s), C.c_void_p)))
+
+    def remove_normals(self, normals):
+        """Frees a normal set; the vertices stay as they are."""
+        abi.check(abi.lib().glz_renderer_remove_normals(self._h, int(normals)))
+
+    def debug_normals_timing(self, normals, reps=20):
+        """k_face_vectors and k_vertex_normals of one set, each alone into scratch (the scene is untouched): ((milliseconds per launch of
+        the face kernel, of the vertex kernel), (the bytes one launch of each moves))"""
+        ms, nbytes = (C.c_float * 2)(), (C.c_uint64 * 2)()
+        abi.check(abi.lib().glz_debug_normals_timing(self._h, int(normals), int(reps), C.cast(ms, C.c_void_p), C.cast(nbytes, C.c_void_p)))
+        return (ms[0], ms[1]), (nbytes[0], nbytes[1])
 
     def read_vertices(self, first, n):
         """The scene's current vertices [first, first + n) as the device holds them: (n, 8) float32"""

@@ -185,6 +185,11 @@ class Animation(C.Structure):
     _fields_ = [("morphs", C.c_void_p), ("n_morphs", C.c_uint32), ("poses", C.c_void_p), ("n_poses", C.c_uint32)]
 
 
+class Normals(C.Structure):
+    """glz_normals"""
+    _fields_ = [("first_vertex", C.c_uint32), ("n_vertices", C.c_uint32), ("groups", C.c_void_p)]
+
+
 MORPH_LDS_TARGETS = 1024   # kMorphLdsTargets (csrc/kernels.h): the morph kernels stage the weight table in LDS up to this many targets
 AOV_NORMAL_DEPTH, AOV_ALBEDO_INSTANCE = 0, 1
 GUIDE_FIRST_HIT, GUIDE_THROUGH_SPECULAR, GUIDE_MAX_BOUNCES = 0, 1, 8
@@ -252,6 +257,11 @@ PROTOTYPES = {
     "glz_renderer_reproject_animated": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "glz_host_morph": (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, _P]),
     "glz_debug_morph_timing": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    "glz_renderer_add_normals": (C.c_int, [_P, _P]),
+    "glz_renderer_remove_normals": (C.c_int, [_P, C.c_int]),
+    "glz_host_vertex_normals": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    "glz_host_weld_groups": (C.c_int, [_P, C.c_uint64, _P]),
+    "glz_debug_normals_timing": (C.c_int, [_P, C.c_int, C.c_uint32, _P, _P]),
     "glz_debug_read_leaf_records": (C.c_int64, [_P, _P, C.c_int64]),
     "glz_debug_read_tlas_instances": (C.c_int64, [_P, _P, C.c_int64]),
     "glz_debug_instance_boxes": (C.c_int64, [_P, C.c_int, C.c_uint64, _P, _P]),

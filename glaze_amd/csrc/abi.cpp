@@ -404,6 +404,21 @@ int glz_renderer_animate(glz_renderer* h, const glz_animation* anim, int mode) {
   GLZ_RET(h->r->animate(*anim, mode, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_renderer_add_normals(glz_renderer* h, const glz_normals* set) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!set) return fail(GLZ_E_ARG, "add_normals: the set is null");
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  const int id = h->r->add_normals(*set, e);
+  if (id < 0) return fail(e);
+  return id;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_remove_normals(glz_renderer* h, int id) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  GLZ_RET(h->r->remove_normals(id, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_read_vertices(glz_renderer* h, uint32_t first, uint32_t n, glz_vertex* out) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");

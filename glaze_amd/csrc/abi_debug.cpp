@@ -10,6 +10,7 @@
 #include "reproject.h"
 #include "skin.h"
 #include "morph.h"
+#include "normals.h"
 #include "mipchain.h"
 #include "rccl_dl.h"
 #include "tile_map.h"
@@ -125,6 +126,13 @@ int glz_debug_morph_timing(glz_renderer* h, const glz_animation* one, uint32_t r
   if (!one || !kernel_ms_out || !h->r->scene()) return fail(GLZ_E_ARG, "bad argument");
   *kernel_ms_out = 0.0f;
   GLZ_RET(h->r->wait_idle(e) && h->r->scene()->time_morph(*one, reps, kernel_ms_out, bytes_out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_normals_timing(glz_renderer* h, int id, uint32_t reps, float ms_out[2], uint64_t bytes_out[2]) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!ms_out || !h->r->scene()) return fail(GLZ_E_ARG, "bad argument");
+  ms_out[0] = ms_out[1] = 0.0f;
+  GLZ_RET(h->r->wait_idle(e) && h->r->scene()->time_normals(id, reps, ms_out, bytes_out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_debug_guide_chain(glz_renderer* h, uint32_t segment, float* origins3, float* dirs3, uint8_t* alive) {
@@ -450,6 +458,26 @@ int glz_host_morph(const glz_vertex* base, uint64_t n, const glz_morph_target* t
   std::string why;
   if (!post::pack_morph((uint32_t)n, targets, n_targets, layout, why)) return fail(GLZ_E_ARG, ("host_morph: " + why).c_str());
   post::host_morph(base, layout, weights, out);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_host_vertex_normals(const glz_vertex* vertices, uint64_t n_vertices, const uint32_t* indices, uint64_t n_indices, const glz_mesh* meshes, uint64_t n_meshes,
+                            uint32_t first_vertex, uint32_t n, const uint32_t* groups, glz_vertex* out) {
+  GLZ_GUARD_BEGIN
+  if (!vertices || !out) return fail(GLZ_E_ARG, "host_vertex_normals: null argument");
+  post::NormalLayout layout;
+  std::string why;
+  if (!post::pack_normals(indices, n_indices, meshes, n_meshes, n_vertices, first_vertex, n, groups, layout, why)) return fail(GLZ_E_ARG, ("host_vertex_normals: " + why).c_str());
+  post::host_vertex_normals(vertices, layout, out);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_host_weld_groups(const glz_vertex* vertices, uint64_t n, uint32_t* groups_out) {
+  GLZ_GUARD_BEGIN
+  if (n == 0) return GLZ_OK;
+  if (!vertices || !groups_out) return fail(GLZ_E_ARG, "host_weld_groups: null argument");
+  if (n > 0xFFFFFFFFull) return fail(GLZ_E_ARG, "host_weld_groups: more vertices than a label can name");
+  post::host_weld_groups(vertices, (uint32_t)n, groups_out);
   return GLZ_OK;
   GLZ_GUARD_END(GLZ_E_IO)
 }

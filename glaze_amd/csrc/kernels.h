@@ -274,6 +274,23 @@ hipError_t launch_morph(hipStream_t st, const MorphArgs& m, float4* out);
 // the same, then the skinning rule on the morphed vertex (launch_skin's arguments), one store: the base is the skin's bind pose
 hipError_t launch_morph_skin(hipStream_t st, const MorphArgs& m, const uint2* joints, const float4* skin_weights, const float4* bones, uint32_t n_bones, float4* out);
 
+// ---- vertex normals from deformed positions (kernels_normals.hip; normals.h holds the rule and the layout) ----
+// What a normal set's kernels read: post::NormalLayout on the device.  Every face's three indices are below the scene's vertex count,
+// every row entry below n_faces and every row's count at most its slice's width (pack_normals made them so: the kernels index by them).
+struct NormalArgs {
+  const uint32_t* faces;    // 3 a face: indices into the scene's vertex buffer
+  uint32_t n_faces;
+  const uint32_t* counts;   // one a vertex of the set
+  const uint2* slices;
+  const uint32_t* rows;
+  uint32_t n;               // the set's vertices
+};
+// face_vectors[f] = the face vector of face f from `vertices`, the scene's WHOLE vertex buffer (two float4 a vertex), f < n_faces
+hipError_t launch_face_vectors(hipStream_t st, const float4* vertices, const NormalArgs& a, float4* face_vectors);
+// out[2 * i], out[2 * i + 1] = in[2 * i], in[2 * i + 1] with the normal words the rule gives vertex i of the set, i < n, where its row is
+// not empty (nothing is stored elsewhere); in: the set's first vertex; out may be `in` itself
+hipError_t launch_vertex_normals(hipStream_t st, const float4* in, const NormalArgs& a, const float4* face_vectors, float4* out);
+
 // debug / parity hooks
 hipError_t launch_debug_closest(hipStream_t st, const DeviceScene& scene, const float* origins, const float* dirs, uint32_t n, float tmin,
                                 float* t, uint32_t* tri, uint32_t* inst, float* u, float* v, uint32_t* overflow, uint32_t overflow_depth);

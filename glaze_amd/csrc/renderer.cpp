@@ -611,6 +611,23 @@ bool Renderer::animate(const glz_animation& anim, int mode, Error& err) {
   const glz_animation a = anim;
   return group_.forward([=](Renderer& p, Error& e) { return p.animate(a, mode, e); }, err);
 }
+// Normal sets are the scene's, as skins and morphs are; adding one changes the vertices' normals, so it is an update of the scene too.
+int Renderer::add_normals(const glz_normals& set, Error& err) {
+  int id = -1;
+  if (!update_scene([&] { return (id = scene_->add_normals(set, err)) >= 0; }, err)) return -1;
+  const glz_normals s = set;
+  const bool followed = group_.forward([=](Renderer& p, Error& e) {
+    const int got = p.add_normals(s, e);
+    if (got >= 0 && got != id) e.fail(GLZ_E_DEVICE, "add_normals: a replica gave another id");
+    return got == id;
+  }, err);
+  if (!followed) return -1;
+  return id;
+}
+bool Renderer::remove_normals(int id, Error& err) {
+  if (!wait_idle(err) || !scene_->remove_normals(id, err)) return false;
+  return group_.forward([=](Renderer& p, Error& e) { return p.remove_normals(id, e); }, err);
+}
 bool Renderer::read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& err) {
   return wait_idle(err) && scene_->read_vertices(first, n, out, err);
 }

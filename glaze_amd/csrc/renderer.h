@@ -36,6 +36,8 @@ class Renderer {
   int add_morph(const glz_morph& morph, Error& err);    // Scene::add_morph here and on every replica; the id, or -1
   bool remove_morph(int id, Error& err);
   bool animate(const glz_animation& anim, int mode, Error& err);   // Scene::animate; restarts accumulation, like pose_skins
+  int add_normals(const glz_normals& set, Error& err);  // Scene::add_normals here and on every replica; restarts accumulation; the id, or -1
+  bool remove_normals(int id, Error& err);
   bool read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& err);   // idle first, then the scene's vertices as the device holds them
   bool geometry_update_info(glz_geometry_update_info& out, Error& err);   // Scene::geometry_update_info, idle first (it may make the refit plan); accumulation goes on
   bool wait_idle(Error& err);

@@ -284,8 +284,12 @@ bool Scene::update_vertices(const glz_vertex* vertices, uint32_t first, uint32_t
   StreamTimer timer;
   if (!timer.start(st, err)) return false;
   std::copy(vertices, vertices + n, data.vertices.begin() + first);
-  if (!hip_ok(hipMemcpyAsync(geometry_.vertices.ptr + 2 * (size_t)first, data.vertices.data() + first, sizeof(glz_vertex) * n, hipMemcpyHostToDevice, st), "upload vertices", err) ||
-      !hip_ok(launch_derivatives(st, geometry_.vertices.ptr, geometry_.indices.ptr, (uint32_t)(geometry_.derivatives.count / 3), geometry_.derivatives.ptr), "derivatives kernel", err))
+  if (!hip_ok(hipMemcpyAsync(geometry_.vertices.ptr + 2 * (size_t)first, data.vertices.data() + first, sizeof(glz_vertex) * n, hipMemcpyHostToDevice, st), "upload vertices", err))
+    return false;
+  // the normal sets the new positions reach: their normals are the device's to make (the mirror's positions stay current: the instance
+  // boxes of a two-level scene read nothing else of it)
+  if (!run_normals(first, n, st, err)) return false;
+  if (!hip_ok(launch_derivatives(st, geometry_.vertices.ptr, geometry_.indices.ptr, (uint32_t)(geometry_.derivatives.count / 3), geometry_.derivatives.ptr), "derivatives kernel", err))
     return false;
   return accel_.update_geometry(sources(), mode, first, n, timer, err);
 }
@@ -626,6 +630,143 @@ bool Scene::time_morph(const glz_animation& one, uint32_t reps, float* kernel_ms
   return true;
 }
 
+// ---- vertex normals from deformed positions ----
+
+void Scene::mark_stale(uint32_t first, uint32_t count) {
+  const uint64_t lo = stale_count_ ? std::min(stale_first_, first) : first;
+  const uint64_t hi = stale_count_ ? std::max<uint64_t>((uint64_t)stale_first_ + stale_count_, (uint64_t)first + count) : (uint64_t)first + count;
+  stale_first_ = (uint32_t)lo;
+  stale_count_ = (uint32_t)(hi - lo);
+}
+
+NormalArgs Scene::normal_args(const NormalSet& s) {
+  return NormalArgs{s.faces.ptr, s.layout.n_faces, s.counts.ptr, s.slices.ptr, s.rows.ptr, s.layout.n_vertices};
+}
+
+// the device half of add_normals and copy_normals: every buffer of the set, or none of it
+int Scene::install_normals(int id, post::NormalLayout&& layout, Error& err) {
+  hipStream_t st = instance->stream;
+  NormalSet s;
+  s.layout = std::move(layout);
+  if (!hip_ok(s.faces.upload(s.layout.faces.data(), s.layout.faces.size(), st), "upload normal faces", err) ||
+      !hip_ok(s.counts.upload(s.layout.counts.data(), s.layout.counts.size(), st), "upload normal counts", err) ||
+      !hip_ok(s.slices.upload(s.layout.slices.data(), s.layout.slices.size(), st), "upload normal slices", err) ||
+      !hip_ok(s.rows.upload(s.layout.rows.data(), s.layout.rows.size(), st), "upload normal rows", err) ||
+      !hip_ok(s.face_vectors.alloc(std::max<size_t>(s.layout.n_faces, 1)), "alloc face vectors", err) || !hip_ok(hipStreamSynchronize(st), "add_normals", err))
+    return -1;
+  normals_.emplace(id, std::move(s));
+  return id;
+}
+
+int Scene::add_normals(const glz_normals& g, Error& err) {
+  auto refuse = [&](const std::string& why) {
+    err.fail(GLZ_E_ARG, "add_normals: " + why);
+    return -1;
+  };
+  if (g.n_vertices == 0 || (uint64_t)g.first_vertex + g.n_vertices > data.vertices.size()) return refuse("no vertices, or a range past the scene's vertex count");
+  for (const auto& kv : normals_)
+    if (g.first_vertex < (uint64_t)kv.second.layout.first + kv.second.layout.n_vertices && kv.second.layout.first < (uint64_t)g.first_vertex + g.n_vertices)
+      return refuse("the range overlaps an existing normal set");
+  post::NormalLayout layout;
+  std::string why;
+  if (!post::pack_normals(data.indices.data(), data.indices.size(), data.meshes.data(), data.meshes.size(), data.vertices.size(), g.first_vertex, g.n_vertices, g.groups,
+                          layout, why))
+    return refuse(why);
+  // from here on it is update_vertices(REFIT) over the set's range, with the two kernels where the upload is
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err) || !mirror_for_accel(err)) return -1;
+  hipStream_t st = instance->stream;
+  Composed at_exit{*this};
+  if (!accel_.prepare_refit(sources(), err)) return -1;
+  StreamTimer timer;
+  if (!timer.start(st, err)) return -1;
+  const int id = install_normals(next_normals_, std::move(layout), err);
+  if (id < 0) return -1;
+  ++next_normals_;
+  const NormalSet& s = normals_.at(id);
+  mark_stale(g.first_vertex, g.n_vertices);
+  float4* range = geometry_.vertices.ptr + 2 * (size_t)g.first_vertex;
+  if (!hip_ok(launch_face_vectors(st, geometry_.vertices.ptr, normal_args(s), s.face_vectors.ptr), "k_face_vectors", err) ||
+      !hip_ok(launch_vertex_normals(st, range, normal_args(s), s.face_vectors.ptr, range), "k_vertex_normals", err) ||
+      !hip_ok(launch_derivatives(st, geometry_.vertices.ptr, geometry_.indices.ptr, (uint32_t)(geometry_.derivatives.count / 3), geometry_.derivatives.ptr), "derivatives kernel", err) ||
+      !accel_.update_geometry(sources(), GLZ_GEOMETRY_REFIT, g.first_vertex, g.n_vertices, timer, err)) {   // (the mirror's positions are current)
+    normals_.erase(id);
+    return -1;
+  }
+  return id;
+}
+
+bool Scene::remove_normals(int id, Error& err) {
+  if (normals_.erase(id) == 0) return err.fail(GLZ_E_ARG, "remove_normals: no such normal set");
+  return true;
+}
+
+bool Scene::copy_normals(const Scene& src, Error& err) {
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  for (const auto& kv : src.normals_)
+    if (install_normals(kv.first, post::NormalLayout(kv.second.layout), err) < 0) return false;
+  next_normals_ = src.next_normals_;
+  return true;
+}
+
+bool Scene::run_normals(uint32_t& first, uint32_t& count, hipStream_t st, Error& err) {
+  uint64_t lo = first, hi = (uint64_t)first + count;
+  const uint64_t written_lo = lo, written_hi = hi;
+  bool any = false;
+  for (const auto& kv : normals_) {
+    const NormalSet& s = kv.second;
+    // (the rule is a function of positions alone: the whole set again, and what did not change comes out with the bits it had)
+    if (s.layout.n_faces == 0 || s.layout.reach_lo >= written_hi || s.layout.reach_hi < written_lo) continue;
+    float4* range = geometry_.vertices.ptr + 2 * (size_t)s.layout.first;
+    if (!hip_ok(launch_face_vectors(st, geometry_.vertices.ptr, normal_args(s), s.face_vectors.ptr), "k_face_vectors", err) ||
+        !hip_ok(launch_vertex_normals(st, range, normal_args(s), s.face_vectors.ptr, range), "k_vertex_normals", err))
+      return false;
+    lo = std::min<uint64_t>(lo, s.layout.first);
+    hi = std::max<uint64_t>(hi, (uint64_t)s.layout.first + s.layout.n_vertices);
+    any = true;
+  }
+  if (!any) return true;
+  first = (uint32_t)lo;
+  count = (uint32_t)(hi - lo);
+  mark_stale(first, count);
+  return true;
+}
+
+bool Scene::time_normals(int id, uint32_t reps, float ms[2], uint64_t bytes[2], Error& err) const {
+  const auto it = normals_.find(id);
+  if (!ms || reps == 0 || it == normals_.end()) return err.fail(GLZ_E_ARG, "normals timing: null output, no repeats, or no such normal set");
+  const NormalSet& s = it->second;
+  if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
+  hipStream_t st = instance->stream;
+  DeviceBuffer<float4> face_vectors, out;
+  Events<3> t;
+  const float4* range = geometry_.vertices.ptr + 2 * (size_t)s.layout.first;
+  if (!hip_ok(face_vectors.alloc(std::max<size_t>(s.layout.n_faces, 1)), "alloc", err) || !hip_ok(out.alloc(2 * (size_t)s.layout.n_vertices), "alloc", err) || !t.create(err) ||
+      !hip_ok(hipMemcpyAsync(out.ptr, range, sizeof(float4) * 2 * (size_t)s.layout.n_vertices, hipMemcpyDeviceToDevice, st), "copy vertices", err))
+    return false;
+  auto faces = [&] { return hip_ok(launch_face_vectors(st, geometry_.vertices.ptr, normal_args(s), face_vectors.ptr), "k_face_vectors", err); };
+  auto vertices = [&] { return hip_ok(launch_vertex_normals(st, range, normal_args(s), face_vectors.ptr, out.ptr), "k_vertex_normals", err); };
+  if (!faces() || !vertices()) return false;
+  (void)hipEventRecord(t.ev[0], st);
+  for (uint32_t i = 0; i < reps; ++i)
+    if (!faces()) return false;
+  (void)hipEventRecord(t.ev[1], st);
+  for (uint32_t i = 0; i < reps; ++i)
+    if (!vertices()) return false;
+  (void)hipEventRecord(t.ev[2], st);
+  if (!hip_ok(hipStreamSynchronize(st), "normals timing", err)) return false;
+  (void)hipEventElapsedTime(&ms[0], t.ev[0], t.ev[1]);
+  (void)hipEventElapsedTime(&ms[1], t.ev[1], t.ev[2]);
+  ms[0] /= (float)reps;
+  ms[1] /= (float)reps;
+  if (bytes) {
+    uint64_t with_faces = 0;
+    for (uint32_t c : s.layout.counts) with_faces += c != 0;
+    bytes[0] = (uint64_t)s.layout.n_faces * (12 + 3 * 16 + 16);
+    bytes[1] = (uint64_t)s.layout.n_vertices * 4 + (uint64_t)s.layout.slices.size() * 8 + s.layout.n_entries * (4 + 16) + with_faces * (32 + 12);
+  }
+  return true;
+}
+
 bool Scene::animate(const glz_animation& anim, int mode, Error& err) { return run_animation(anim, mode, "animate", err); }
 
 bool Scene::run_animation(const glz_animation& anim, int mode, const char* who, Error& err) {
@@ -639,12 +780,10 @@ bool Scene::run_animation(const glz_animation& anim, int mode, const char* who, 
   StreamTimer timer;
   if (!timer.start(st, err)) return false;
   // whatever happens from here on, the device's vertices may differ from the mirror's over the span (joined with a span still pending)
-  const uint64_t lo = stale_count_ ? std::min(stale_first_, first) : first;
-  const uint64_t hi = stale_count_ ? std::max<uint64_t>((uint64_t)stale_first_ + stale_count_, (uint64_t)first + count) : (uint64_t)first + count;
-  stale_first_ = (uint32_t)lo;
-  stale_count_ = (uint32_t)(hi - lo);
+  mark_stale(first, count);
   // (the uploads outlive the copies: update_geometry waits for the stream; the buffers are the scene's, reused while the calls name as much)
   if (!animate_into(anim, geometry_.vertices.ptr, 0, uploads_, st, err)) return false;
+  if (!run_normals(first, count, st, err)) return false;   // the normal sets the written span reaches; the span grows by their ranges
   if (!hip_ok(launch_derivatives(st, geometry_.vertices.ptr, geometry_.indices.ptr, (uint32_t)(geometry_.derivatives.count / 3), geometry_.derivatives.ptr), "derivatives kernel", err))
     return false;
   if (!mirror_for_accel(err)) return false;   // two levels: the top level is rebuilt from the meshes' points

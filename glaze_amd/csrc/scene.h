@@ -16,6 +16,7 @@
 #include "instance_boxes.h"
 #include "kernels.h"
 #include "morph.h"
+#include "normals.h"
 #include "parser.h"
 #include "shading_tables.h"
 #include "textures.h"
@@ -119,6 +120,20 @@ class Scene {
   bool time_morph(const glz_animation& one, uint32_t reps, float* kernel_ms, uint64_t* bytes, Error& err) const;
   // everything that makes `src`'s morphs, on this scene (a replica on another device), after copy_skins: same ids, same bases
   bool copy_morphs(const Scene& src, Error& err);
+  // ---- vertex normals from deformed positions (normals.h holds the rule and the layout, kernels_normals.hip the kernels) ----
+  // A normal set over [first_vertex, first_vertex + n_vertices): the face list and the rows are made once (post::pack_normals) and
+  // uploaded; the rule runs once, and the scene then does what update_vertices(REFIT) does after its upload over the set's range.  From
+  // then on update_vertices, pose_skins and animate run the set's two kernels after their own writes and before the derivatives whenever
+  // the span they wrote overlaps the set's reach (the lowest to the highest corner of its faces).  Returns the id (>= 0, counting up,
+  // never reused), or -1 with the error set; GLZ_E_ARG (nothing changes): see glz_renderer_add_normals.
+  int add_normals(const glz_normals& set, Error& err);
+  bool remove_normals(int id, Error& err);   // the vertices stay as they are
+  // Each of the two kernels of one set alone, `reps` times after one launch that is not timed: k_face_vectors into a scratch buffer of
+  // face vectors, k_vertex_normals from it into a scratch copy of the set's vertices (the scene is untouched).  ms / bytes: [0] the
+  // face kernel, [1] the vertex kernel; bytes by the layout's own count (glz_debug_normals_timing)
+  bool time_normals(int id, uint32_t reps, float ms[2], uint64_t bytes[2], Error& err) const;
+  // everything that makes `src`'s normal sets, on this scene (a replica on another device, made of src's current vertices): same ids
+  bool copy_normals(const Scene& src, Error& err);
   // Instance boxes of a two-level scene under its current transforms (host rule, or the device kernel); false with an empty result
   // for a flattened scene.  budget: kExactBoxBudget for the scene's own.
   bool instance_boxes(bool on_device, uint64_t budget, std::vector<float4>& lo, std::vector<float4>& hi, Error& err);
@@ -175,6 +190,20 @@ class Scene {
   AnimationUploads uploads_;   // what the scene's own animate / pose_skins calls send up
   std::map<int, Morph> morphs_;
   int next_morph_ = 0;
+  struct NormalSet {
+    post::NormalLayout layout;               // (kept whole on the host for the replicas on other devices that are created later)
+    DeviceBuffer<uint32_t> faces, counts, rows;
+    DeviceBuffer<uint2> slices;
+    DeviceBuffer<float4> face_vectors;       // one a face: k_face_vectors writes it, k_vertex_normals reads it
+  };
+  int install_normals(int id, post::NormalLayout&& layout, Error& err);
+  static NormalArgs normal_args(const NormalSet& s);
+  // The two kernels of every set whose reach overlaps the written span [first, first + count), on `st`; first / count come back as the
+  // union of the span and those sets' ranges: what the structure's update and the host mirror have to know as changed
+  bool run_normals(uint32_t& first, uint32_t& count, hipStream_t st, Error& err);
+  void mark_stale(uint32_t first, uint32_t count);   // joins a span with the one of data.vertices that is already behind the device
+  std::map<int, NormalSet> normals_;
+  int next_normals_ = 0;
   int install_skin(int id, uint32_t first, std::vector<glz_vertex>&& bind, std::vector<uint16_t>&& joints, std::vector<float>&& weights, uint32_t n_bones,
                    const float4* device_bind, Error& err);
   std::map<int, Skin> skins_;

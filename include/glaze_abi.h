@@ -461,6 +461,56 @@ typedef struct glz_animation {
   uint32_t                 n_poses;
 } glz_animation;
 int glz_renderer_animate(glz_renderer*, const glz_animation*, int mode);
+/* Build-defined: shading normals recomputed on the device from the positions it holds -- after a pose, a morph or new positions from the
+ * caller -- so that a deformed surface is shaded with the normals of the shape it has now.  Opt-in per vertex range: without a normal set
+ * nothing changes.
+ *
+ *   THE NORMAL RULE (glz_renderer_add_normals, glz_host_vertex_normals; one definition, glaze_amd/csrc/normals.h, compiled for host and
+ *   device; the tests hold both sides to this text bit for bit).  float32 throughout, no contraction into fused multiply-adds; only
+ *   + - x, one sqrtf and one 1.0f / x, both correctly rounded.  A NORMAL SET covers the vertices [first_vertex, first_vertex + n_vertices).
+ *   TRIANGLES: mesh m of the scene's mesh array, in array order, has the triangles k < index_count / 3 with corners
+ *   indices[index_offset + 3k + c]; triangles are ordered by (m, k).  Mesh index ranges need not be disjoint: two meshes over the same
+ *   indices contribute their triangles twice, and nothing is done about it.  The set's FACES are the triangles with at least one corner
+ *   in the range, in that order.
+ *   FACE VECTOR of a face with corner positions p0, p1, p2, read from the current vertex buffer (corners outside the range are read and
+ *   never written):
+ *     a = p1 - p0, b = p2 - p0 (per component)
+ *     F = (a.y*b.z - a.z*b.y,  a.z*b.x - a.x*b.z,  a.x*b.y - a.y*b.x)
+ *   Area weighting: the face's own length is its weight.
+ *   GROUPS: `groups` is optional, n_vertices uint32 each < n_vertices; vertices with equal values form one group, NULL = every vertex is
+ *   its own group.  All members of a group receive the same normal: a UV seam (positions duplicated, texture coordinates not) stays
+ *   smooth, and a hard edge stays hard where the caller puts the duplicates in different groups.
+ *   VERTEX NORMAL: let F_1 .. F_k be the faces with at least one corner in the vertex's group, each taken once, in ascending face order.
+ *     S = ((...((0 + F_1) + F_2) ...) + F_k)      per component, starting from +0
+ *     d = (S.x*S.x + S.y*S.y) + S.z*S.z
+ *     if d > 0 and d < +inf:  inv = 1.0f / sqrtf(d);  n' = (S.x*inv, S.y*inv, S.z*inv)
+ *     else:                   n' = S
+ *   A vertex whose group has no face keeps its normal bits.  Position and texture coordinate are never touched.  NaN and infinity go
+ *   through as the arithmetic says.
+ *
+ * glz_renderer_add_normals returns the set's id (>= 0).  The face list and a row of face numbers per vertex are made once, on the host,
+ * and uploaded; the caller's groups are not kept.  The rule then runs once, and the scene does what
+ * glz_renderer_update_vertices(GLZ_GEOMETRY_REFIT) does after its upload, over the set's range: idle first, accumulation restarts, every
+ * device follows.  FROM THEN ON the set's normals on the device are THE NORMAL RULE of the device's current positions: every
+ * glz_renderer_update_vertices, glz_renderer_pose_skins and glz_renderer_animate whose written span overlaps the set's REACH (the lowest to
+ * the highest vertex index of any corner of its faces) runs the rule over the whole set after its own writes and before the derivatives
+ * and the one update of the structure, whose span is the union of the written span and the recomputed sets' ranges;
+ * glz_geometry_update_info.update_ms includes the rule's kernels.  An update outside every reach runs nothing more than it did.
+ * WARNING: a set over a skinned or morphed range REPLACES the normal THE SKINNING RULE transforms or THE MORPH RULE blends (and the
+ * normals glz_renderer_update_vertices is given) in that range: the scene then equals one created with
+ * glz_host_vertex_normals(glz_host_skin(...)), not with glz_host_skin(...) alone.  The previous-vertex buffers of read_motion* /
+ * reproject* need positions only and are not touched by the rule.
+ * Sets belong to the SCENE object, as skins and morphs do: ids count up and are never reused, every device of set_devices gets them, and a
+ * set may overlap skins and morphs freely -- but no other set.  GLZ_E_ARG (nothing changes): a null pointer, n_vertices == 0, a range past
+ * the vertex count, a group label >= n_vertices, a range overlapping another set.
+ * glz_renderer_remove_normals frees a set; the vertices stay as they are, and later updates write what they wrote before the set was
+ * there.  GLZ_E_ARG: no such set. */
+typedef struct glz_normals {
+  uint32_t        first_vertex, n_vertices;
+  const uint32_t* groups;   /* n_vertices labels, each < n_vertices; NULL: every vertex is its own group */
+} glz_normals;
+int glz_renderer_add_normals(glz_renderer*, const glz_normals*);
+int glz_renderer_remove_normals(glz_renderer*, int id);
 /* raytracer.rs:328-356: the texture array changed under the same materials and lights (the reference re-binds the
  * textures it shares with the realtime viewer); accumulation is NOT restarted, like the reference. */
 int glz_renderer_refresh_binded_textures(glz_renderer*, const glz_texture* textures, uint32_t n_textures);
@@ -875,6 +925,11 @@ int glz_debug_skin_timing(glz_renderer*, const glz_pose* pose, uint32_t reps, fl
  * k_morph_skin.  bytes_out (may be NULL): the bytes one launch moves by the layout's own count -- per vertex 32 in, 32 out and 4 of row
  * length, 8 a slice, 32 an entry that is not padding, 4 a target; fused, also 24 a vertex of joints and weights and 48 a bone. */
 int glz_debug_morph_timing(glz_renderer*, const glz_animation* one, uint32_t reps, float* kernel_ms_out, uint64_t* bytes_out);
+/* The two kernels of one normal set alone, timed as glz_debug_skin_timing times k_skin: k_face_vectors into a scratch buffer of face
+ * vectors, then k_vertex_normals from it into a scratch copy of the set's vertices (the scene is untouched).  ms_out[0] / bytes_out[0]: the
+ * face kernel, [1]: the vertex kernel.  bytes_out (may be NULL): per face 12 of indices, 3 x 16 gathered, 16 out; per vertex 4 of row
+ * length, 4 + 16 a row entry that is not padding, 8 a slice, and 32 in + 12 out for a vertex that has a face. */
+int glz_debug_normals_timing(glz_renderer*, int id, uint32_t reps, float ms_out[2], uint64_t bytes_out[2]);
 int glz_debug_tonemap(glz_instance*, const float* rgba32f, uint64_t n_pixels, uint8_t* rgba8_out);
 /* The kernels' texture sampler on n coordinates uv2[2i], uv2[2i+1] of a scene texture, RGBA out: level 0 (texture2d) when
  * footprint4 is NULL, else the level of detail of footprint4[4i..4i+3] = (lod_base, du, dv, taps in 1..16) (texture2d_lod, after
@@ -994,6 +1049,17 @@ int glz_host_skin(const glz_vertex* bind, const uint16_t* joints, const float* w
  * has them, over n vertices; weights: n_targets.  GLZ_E_ARG: a null pointer with n > 0, and what glz_renderer_add_morph refuses of a
  * morph's targets. */
 int glz_host_morph(const glz_vertex* base, uint64_t n, const glz_morph_target* targets, uint32_t n_targets, const float* weights, glz_vertex* out);
+/* THE NORMAL RULE (glz_renderer_add_normals) on host arrays, no device: the reference k_face_vectors and k_vertex_normals are compared
+ * with bit for bit; it runs through the same layout packer as glz_renderer_add_normals.  vertices, indices, meshes: a scene's, whole;
+ * first_vertex, n, groups_or_null: as glz_normals has them; out: n vertices, the range's own with the rule's normals (out may be
+ * vertices + first_vertex itself).  GLZ_E_ARG: a null pointer, what glz_renderer_add_normals refuses of a set, a mesh whose index range
+ * is past n_indices, an index >= n_vertices. */
+int glz_host_vertex_normals(const glz_vertex* vertices, uint64_t n_vertices, const uint32_t* indices, uint64_t n_indices, const glz_mesh* meshes, uint64_t n_meshes,
+                            uint32_t first_vertex, uint32_t n, const uint32_t* groups_or_null, glz_vertex* out);
+/* Group labels for glz_normals.groups by welding: groups_out[i] = the lowest index j of the n vertices whose three position words and
+ * three normal words are bit-equal to i's (so -0 is not +0).  A convenience for callers: the library itself never welds.  GLZ_E_ARG: a
+ * null pointer with n > 0, n > 2^32 - 1. */
+int glz_host_weld_groups(const glz_vertex* vertices, uint64_t n, uint32_t* groups_out);
 
 #ifdef __cplusplus
 }
