@@ -353,6 +353,9 @@ PROTOTYPES = {
     "glz_debug_guide_chain": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
     "glz_host_traversal_offsets_fit": (C.c_int, [C.c_uint64] * 6),
     "glz_host_sky_row_pairs": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "glz_host_sky_bracket_table": (C.c_int, [_P, C.c_uint64, _P]),
+    "glz_host_sky_cdf_search": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint64, _P, _P]),
+    "glz_host_texel_wrap": (C.c_int, [_P, C.c_uint64, C.c_int32, _P]),
     "glz_host_conductor_finite": (C.c_int, [_P, _P, _P]),
     "glz_host_metal_spectra": (C.c_int, [C.c_uint32, _P, _P]),
 }

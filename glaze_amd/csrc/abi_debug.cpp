@@ -724,6 +724,29 @@ int glz_host_sky_row_pairs(const float* marginal_values, const float* conditiona
   sky_row_pairs(marginal_values, conditional_integrals, (size_t)n, pairs_out);
   return GLZ_OK;
 }
+int glz_host_sky_bracket_table(const float* cdf, uint64_t size, uint16_t* table_out) {
+  if (!table_out || (size != 0 && !cdf) || size > 0xFFFFFFFFull) return fail(GLZ_E_ARG, "glz_host_sky_bracket_table: null array, or a cdf of 2^32 entries");
+  sky_bracket_table(cdf, (uint32_t)size, table_out);
+  return GLZ_OK;
+}
+int glz_host_sky_cdf_search(const float* cdf, uint64_t size, const uint16_t* bracket_or_null, const float* xi, uint64_t n, float* sample_out, uint32_t* offset_out) {
+  if (size < 2 || size > 0x7FFFFFFFull || !cdf) return fail(GLZ_E_ARG, "glz_host_sky_cdf_search: a cdf has two entries at least");
+  if (n != 0 && (!xi || !sample_out || !offset_out)) return fail(GLZ_E_ARG, "glz_host_sky_cdf_search: null array");
+  if (bracket_or_null && bracket_or_null[0] != kSkyBracketFallback)   // a table of another cdf must not walk the search out of this one
+    for (uint32_t b = 0; b <= kSkyBracketBuckets; ++b)
+      if (bracket_or_null[b] > size || (b != 0 && bracket_or_null[b] < bracket_or_null[b - 1])) return fail(GLZ_E_ARG, "glz_host_sky_cdf_search: the bracket table does not fit the cdf");
+  for (uint64_t i = 0; i < n; ++i) sample_out[i] = sky_cdf_search(cdf, (uint32_t)size, xi[i], bracket_or_null, &offset_out[i]);
+  return GLZ_OK;
+}
+int glz_host_texel_wrap(const int32_t* i, uint64_t count, int32_t n, int32_t* index_out) {
+  if (n <= 0 || (count != 0 && (!i || !index_out))) return fail(GLZ_E_ARG, "glz_host_texel_wrap: a size below 1, or a null array");
+  const bool pow2 = (n & (n - 1)) == 0;
+  for (uint64_t k = 0; k < count; ++k) {
+    const int32_t r = i[k] % n;
+    index_out[k] = pow2 ? (i[k] & (n - 1)) : (r < 0 ? r + n : r);
+  }
+  return GLZ_OK;
+}
 int glz_host_conductor_finite(const float ior[16], const float ior2abs2[16], int* flag_out) {
   if (!ior || !ior2abs2 || !flag_out) return fail(GLZ_E_ARG, "glz_host_conductor_finite: null argument");
   *flag_out = conductor_finite(ior, ior2abs2) ? 1 : 0;

@@ -61,11 +61,12 @@ __device__ __forceinline__ HitVertex load_hit_vertex(const DeviceScene& S, float
   return v;
 }
 // The normal map at the footprint `fp`, then object -> world.  POINTS: `point` and `dpdu` are transformed too (a caller that goes on
-// along the path needs them; the normals always are).
-template <bool POINTS>
+// along the path needs them; the normals always are).  SHORT: the sampler's short forms (device/shading.h, texel_address); the post stage
+// passes false and keeps the code it had.
+template <bool POINTS, bool SHORT = true>
 __device__ __forceinline__ void finish_hit_vertex(const DeviceScene& S, HitVertex& v, const TexFootprint& fp) {
   if (v.mat.normal != 0) {
-    const vec4 tx = texture2d_lod(S, v.mat.normal, v.uv.x, v.uv.y, fp);
+    const vec4 tx = texture2d_lod<SHORT>(S, v.mat.normal, v.uv.x, v.uv.y, fp);
     Frame old;
     old.s = normalize3(v.dpdu);
     old.n = v.ns;
@@ -89,13 +90,14 @@ __device__ __forceinline__ void finish_hit_vertex(const DeviceScene& S, HitVerte
   }
 }
 // The surface point the BSDFs work on at the finished vertex, reached along `direction`: frame, material, the material's textures at `fp`.
+template <bool SHORT = true>
 __device__ __forceinline__ SurfacePoint hit_surface_point(const DeviceScene& S, const HitVertex& v, vec3 direction, const TexFootprint& fp) {
   SurfacePoint P;
   P.woW = -direction;
   P.uv = v.uv;
   P.frame = make_frame(v.dpdu, v.ns);
   P.mat = v.mat;
-  fetch_material_textures(S, P, fp);
+  fetch_material_textures<SHORT>(S, P, fp);
   return P;
 }
 }  // namespace glz

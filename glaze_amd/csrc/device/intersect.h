@@ -210,7 +210,7 @@ __device__ __forceinline__ bool alpha_test(const DeviceScene& S, uint32_t leaf, 
   const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
   const float tu = (r0.x * w + r0.z * u) + r1.x * v, tv = (r0.y * w + r0.w * u) + r1.y * v;
   const TexDesc t{__float_as_uint(r1.z), __float_as_uint(r1.w), __float_as_uint(r2.x), __float_as_uint(r2.y)};
-  return !(bilinear_level(S, t, S.tex_pool, tu, tv).x < 0.5f);
+  return !(bilinear_level<false>(S, t, S.tex_pool, tu, tv).x < 0.5f);   // (<false>: device/shading.h, texel_address)
 }
 
 // the same for a two-level scene: the shading record is per OBJECT triangle, the material is the instance's
@@ -220,7 +220,7 @@ __device__ __forceinline__ bool alpha_test_instance(const DeviceScene& S, uint32
   const uint32_t material_id = S.instances[instance].material_id;
   const float w = 1.0f - u - v;
   const float tu = (a.z * w + b.z * u) + c.z * v, tv = (a.w * w + b.w * u) + c.w * v;
-  return !(texture_r(S, S.materials[material_id].opacity, vec2{tu, tv}) < 0.5f);
+  return !(texture_r<false>(S, S.materials[material_id].opacity, vec2{tu, tv}) < 0.5f);
 }
 
 struct HitRecord {

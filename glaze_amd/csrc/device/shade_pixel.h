@@ -43,7 +43,12 @@ __device__ __forceinline__ uint32_t light_pick(const FrameData& F, uint32_t& rng
 struct DirectState {
   const LaunchArgs& A;
   static constexpr bool kDeferSkyTexel = false;   // (sample_light: k_path has no registers for the fetch code a second time)
+  static constexpr bool kHandLambert = false;     // (nor for sixteen more between the evaluation and the sample)
   __device__ __forceinline__ void stamp(int) {}
+  // the bracket table of S.sky_cdf (sample_cdf), where the cdf is: in memory, behind it
+  __device__ __forceinline__ const uint16_t* sky_bracket(const DeviceScene& S) const {
+    return reinterpret_cast<const uint16_t*>(S.sky_marginal + sky_bracket_offset(S.sky_header.marginal_cdf_count));
+  }
   __device__ __forceinline__ void ray_o(uint32_t lid, float4 v) { A.st.ray_o[lid] = v; }
   __device__ __forceinline__ void ray_d(uint32_t lid, float4 v) { A.st.ray_d[lid] = v; }
   __device__ __forceinline__ void imp(int q, uint32_t lid, float4 v) { A.st.imp[q][lid] = v; }
@@ -66,6 +71,10 @@ struct StagedState {
   __device__ __forceinline__ void stamp(int) {}
 #endif
   static constexpr bool kDeferSkyTexel = true;
+  static constexpr bool kHandLambert = true;
+  // the bracket table of the sky's marginal cdf, staged next to it in LDS; null where the cdf stays in memory (a sky too tall for LDS: the full search)
+  const uint16_t* lds_sky_bracket = nullptr;
+  __device__ __forceinline__ const uint16_t* sky_bracket(const DeviceScene&) const { return lds_sky_bracket; }
   float4 ro, rd, im[4];
   uint32_t mask = 0;   // 1: ro, 2: rd, 4: im
   __device__ __forceinline__ void ray_o(uint32_t, float4 v) { ro = v; mask |= 1u; }
@@ -204,8 +213,10 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
   const SurfacePoint P = hit_surface_point(S, hv, direction, fp);
   GLZ_SHADE_STAMP(1);   // normal map, transform, frame, the material's textures
   float spec_flag;
-  float imp_lum = 0.0f;      // luminance of the importance, taken when the light-sampling block reads it: the roulette needs nothing else of it
-  bool have_lum = false;
+  // A Lambert hit's value is the same spectrum in the evaluation and in the sample, from_surface_color(tint / pi): where the evaluation
+  // ran, State::kHandLambert hands what it made to bsdf_sample (alive across the radiance and the roulette only)
+  Spec lambert_value = spec_set(0.0f);
+  bool have_lambert = false;
   if (mat.is_specular == 0) {
     // direct_light(), :84-117
     const uint32_t li = out.pick_light(F, rng);
@@ -213,7 +224,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
     xi.x = rand01(rng); xi.y = rand01(rng); xi.z = rand01(rng);
     LightSample ls;
     ls.pdf = 0.0f;
-    sample_light<State::kDeferSkyTexel>(S, li, point, xi, F.scene_radius, ls);
+    sample_light<State::kDeferSkyTexel>(S, li, point, xi, F.scene_radius, ls, out.sky_bracket(S));
     GLZ_SHADE_STAMP(2);   // light sample
     vec3 c = mk3(0.0f, 0.0f, 0.0f);
     uint32_t flags = kFlagUpdate;
@@ -223,14 +234,16 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
       const float xi_b = rand01(rng);
       Spec value = spec_set(0.0f);
       const float bpdf = bsdf_eval(S, P, ls.wiW, xi_b, value);
+      if (State::kHandLambert && mat.bsdf_index == kBsdfLambert) {
+        lambert_value = value;
+        have_lambert = true;
+      }
       if (bpdf > 0.0f) {
         // weight_light = (1 or 0) * |cos| / pdf; radiance = value*emission*weight*lights_no*importance
         const float w_vis = 1.0f * (fabsf(dot3(ls.wiW, ns)) / ls.pdf);
         const float nl = (float)F.lights_no;
         const Spec emission = light_emission<State::kDeferSkyTexel>(S, ls);
         const Spec importance = load_importance();
-        imp_lum = spec_luminance(importance);
-        have_lum = true;
         Spec rad;
         GLZ_BINS {
           const float rl = value.w[i] * emission.w[i];
@@ -243,12 +256,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
         sh_tmax = ls.distance - 1e-3f;
       }
     }
-    if (!(flags & kFlagShadow)) {
-      // no light sample: the reference adds rgb(0 * lights_no * importance), zero or (non-finite importance) a NaN that adds nothing
-      const Spec importance = load_importance();
-      imp_lum = spec_luminance(importance);
-      have_lum = true;
-    }
+    // (no light sample: the reference adds rgb(0 * lights_no * importance), zero or (non-finite importance) a NaN that adds nothing)
     // shadow-ray queue (consumed by the next launch's k_trace); pixels without a shadow ray are accumulated right here
     const bool push = (flags & kFlagShadow) != 0;
     GLZ_SHADE_STAMP(3);   // BSDF evaluation, radiance, importance read
@@ -269,7 +277,9 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
   // Russian roulette (:197-210)
   float rr_scale = 1.0f;   // importance * 1.0f is importance, bit for bit: the paths that skip the roulette multiply by it too
   if (bounce > (float)(F.pt_steps / 2u)) {
-    const float kill = gl_max(0.05f, 1.0f - (have_lum ? imp_lum : spec_luminance(load_importance())));
+    // the luminance of the importance is made here, by the bounces that play: taken where the light-sampling block read the importance, on
+    // both sides of its branch, every hit made it and only these read it (the importance is in LDS in k_shade: the second read is cheap)
+    const float kill = gl_max(0.05f, 1.0f - spec_luminance(load_importance()));
     if (rand01(rng) < kill) {
       end_w = spec_flag;
       return 2;
@@ -280,7 +290,7 @@ __device__ __forceinline__ int shade_pixel_body(const LaunchArgs& A, const Devic
   xi.x = rand01(rng); xi.y = rand01(rng); xi.z = rand01(rng);
   Spec value = spec_set(0.0f);
   vec3 wiW = mk3(0.0f, 0.0f, 0.0f);
-  const float pdf = bsdf_sample(S, P, xi, value, wiW);   // :212-218
+  const float pdf = bsdf_sample(S, P, xi, value, wiW, &lambert_value, State::kHandLambert && have_lambert);   // :212-218
   if (pdf == 0.0f) {
     end_w = spec_flag;
     return 2;

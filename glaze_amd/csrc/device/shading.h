@@ -95,13 +95,24 @@ GLZ_D vec4 decode_texel(const DeviceScene& S, uint32_t format, uint32_t bits) {
   if (format == GLZ_TEX_RGBA_SRGB) return vec4{S.srgb_lut[r], S.srgb_lut[g], S.srgb_lut[b], (float)a / 255.0f};
   return vec4{(float)r / 255.0f, (float)g / 255.0f, (float)b / 255.0f, (float)a / 255.0f};
 }
+// (tile row x tiles per row: tiles_x has the 24 bits `format` leaves it and Textures::upload admits no texture of 2^24 tile rows, so a
+// 24-bit multiply gives the product's 32 bits -- one v_mad_u32_u24 with the tile column instead of a 32-bit v_mul_lo_u32 and an add)
+// SHORT (here and in the fetch functions below): the sampler of the shading code -- this multiply, and bilinear_level's wrap of a
+// power-of-two size.  The tracers' alpha test passes false and keeps the code it had: same texels, and k_trace is not to change by a register.
+template <bool SHORT = true>
 GLZ_D uint32_t texel_address(const TexDesc& t, uint32_t format, uint32_t ux, uint32_t uy) {
   const uint32_t tiles_x = t.format >> 8;
-  if (format == GLZ_TEX_GRAY) return t.offset + ((uy >> 3) * tiles_x + (ux >> 4)) * 128u + (uy & 7u) * 16u + (ux & 15u);
-  return t.offset + (((uy >> 2) * tiles_x + (ux >> 3)) * 32u + (uy & 3u) * 8u + (ux & 7u)) * 4u;
+  if constexpr (SHORT) {
+    if (format == GLZ_TEX_GRAY) return t.offset + ((uint32_t)__umul24(uy >> 3, tiles_x) + (ux >> 4)) * 128u + (uy & 7u) * 16u + (ux & 15u);
+    return t.offset + (((uint32_t)__umul24(uy >> 2, tiles_x) + (ux >> 3)) * 32u + (uy & 3u) * 8u + (ux & 7u)) * 4u;
+  } else {
+    if (format == GLZ_TEX_GRAY) return t.offset + ((uy >> 3) * tiles_x + (ux >> 4)) * 128u + (uy & 7u) * 16u + (ux & 15u);
+    return t.offset + (((uy >> 2) * tiles_x + (ux >> 3)) * 32u + (uy & 3u) * 8u + (ux & 7u)) * 4u;
+  }
 }
+template <bool SHORT = true>
 GLZ_D uint32_t load_texel(const uint8_t* __restrict__ pool, const TexDesc& t, uint32_t format, uint32_t ux, uint32_t uy) {
-  const uint32_t addr = texel_address(t, format, ux, uy);
+  const uint32_t addr = texel_address<SHORT>(t, format, ux, uy);
   return format == GLZ_TEX_GRAY ? (uint32_t)pool[addr] : *reinterpret_cast<const uint32_t*>(pool + addr);
 }
 GLZ_D int wrap_coord(int i, int n) {
@@ -128,6 +139,7 @@ GLZ_D float lerp_ab(float a, float b, float t) { return a + (b - a) * t; }
 // bilinear, REPEAT fetch from ONE level: `t` describes it, `pool` holds its texels.  Texel centres at (i + 0.5) / width; the texel
 // index is floor(u * width - 0.5) wrapped into [0, width).  Inside (-2^23, 2^23) it goes through int (the hot path); outside, where
 // glz_floorf returns the coordinate itself and the weight is 0, it is wrapped exactly by wrap_coord_far, never converted to int.
+template <bool SHORT = true>
 GLZ_D vec4 bilinear_level(const DeviceScene& S, const TexDesc& t, const uint8_t* __restrict__ pool, float u, float v) {
   const uint32_t format = t.format & 0x7Fu;
   float fu = u * (float)t.width - 0.5f, fv = v * (float)t.height - 0.5f;
@@ -141,19 +153,27 @@ GLZ_D vec4 bilinear_level(const DeviceScene& S, const TexDesc& t, const uint8_t*
       S.tex_counter[0] += 1ull;
       S.tex_counter[1] += format == GLZ_TEX_GRAY ? 4ull : 16ull;
     }
-    const int x0 = fabsf(iu) < 8388608.0f ? wrap_coord((int)iu, (int)t.width) : wrap_coord_far(iu, (int)t.width);
-    const int y0 = fabsf(iv) < 8388608.0f ? wrap_coord((int)iv, (int)t.height) : wrap_coord_far(iv, (int)t.height);
+    int x0, y0;
+    if (SHORT && (((t.width & (t.width - 1u)) | (t.height & (t.height - 1u))) == 0u) && fabsf(iu) < 8388608.0f && fabsf(iv) < 8388608.0f) {
+      // both sizes a power of two (nearly every texture there is): in two's complement i & (n - 1) is the non-negative remainder wrap_coord
+      // returns, for any int i -- one v_and_b32 where i % n with a run-time n is some two dozen instructions (no SIMD divides integers)
+      x0 = (int)iu & (int)(t.width - 1u);
+      y0 = (int)iv & (int)(t.height - 1u);
+    } else {
+      x0 = fabsf(iu) < 8388608.0f ? wrap_coord((int)iu, (int)t.width) : wrap_coord_far(iu, (int)t.width);
+      y0 = fabsf(iv) < 8388608.0f ? wrap_coord((int)iv, (int)t.height) : wrap_coord_far(iv, (int)t.height);
+    }
     const int x1 = x0 + 1 == (int)t.width ? 0 : x0 + 1, y1 = y0 + 1 == (int)t.height ? 0 : y0 + 1;
     if (format != GLZ_TEX_GRAY && x1 == x0 + 1 && (x0 & 7) != 7) {
       // the two texels of a row are neighbours inside one tile row: one 8-byte load per row
-      const uint2 r0 = *reinterpret_cast<const uint2*>(pool + texel_address(t, format, (uint32_t)x0, (uint32_t)y0));
-      const uint2 r1 = *reinterpret_cast<const uint2*>(pool + texel_address(t, format, (uint32_t)x0, (uint32_t)y1));
+      const uint2 r0 = *reinterpret_cast<const uint2*>(pool + texel_address<SHORT>(t, format, (uint32_t)x0, (uint32_t)y0));
+      const uint2 r1 = *reinterpret_cast<const uint2*>(pool + texel_address<SHORT>(t, format, (uint32_t)x0, (uint32_t)y1));
       ta = r0.x; tb = r0.y; tc = r1.x; tdx = r1.y;
     } else {
-      ta = load_texel(pool, t, format, (uint32_t)x0, (uint32_t)y0);
-      tb = load_texel(pool, t, format, (uint32_t)x1, (uint32_t)y0);
-      tc = load_texel(pool, t, format, (uint32_t)x0, (uint32_t)y1);
-      tdx = load_texel(pool, t, format, (uint32_t)x1, (uint32_t)y1);
+      ta = load_texel<SHORT>(pool, t, format, (uint32_t)x0, (uint32_t)y0);
+      tb = load_texel<SHORT>(pool, t, format, (uint32_t)x1, (uint32_t)y0);
+      tc = load_texel<SHORT>(pool, t, format, (uint32_t)x0, (uint32_t)y1);
+      tdx = load_texel<SHORT>(pool, t, format, (uint32_t)x1, (uint32_t)y1);
     }
   }
   const vec4 a = decode_texel(S, format, ta), b = decode_texel(S, format, tb), c = decode_texel(S, format, tc), d = decode_texel(S, format, tdx);
@@ -164,10 +184,11 @@ GLZ_D vec4 bilinear_level(const DeviceScene& S, const TexDesc& t, const uint8_t*
   r.w = lerp_ab(lerp_ab(a.w, b.w, ax), lerp_ab(c.w, d.w, ax), ay);
   return r;
 }
+template <bool SHORT = true>
 GLZ_D vec4 texture2d(const DeviceScene& S, uint32_t id, float u, float v) {
   // one dwordx4 for the whole descriptor
   const uint4 td = reinterpret_cast<const uint4*>(S.tex_desc)[id];
-  return bilinear_level(S, TexDesc{td.x, td.y, td.z, td.w}, S.tex_pool, u, v);
+  return bilinear_level<SHORT>(S, TexDesc{td.x, td.y, td.z, td.w}, S.tex_pool, u, v);
 }
 // Texture level of detail (build-defined, FrameData::lod_mode; the reference's ray-tracing stages sample level 0).  `lod_base` is
 // the texture-independent part of the ray-cone level, 0.5 log2(uv area / world area * cone width^2 / cos^2); the texture adds
@@ -177,6 +198,7 @@ GLZ_D vec4 texture2d(const DeviceScene& S, uint32_t id, float u, float v) {
 // around (u, v), averaged -- what the anisotropy of the reference's sampler does in its raster viewer.
 constexpr float kNoLod = -1e30f;
 struct TexFootprint { float lod_base; float du, dv; uint32_t taps; };
+template <bool SHORT = true>
 GLZ_D vec4 texture2d_lod(const DeviceScene& S, uint32_t id, float u, float v, const TexFootprint& fp) {
   const uint4 td = reinterpret_cast<const uint4*>(S.tex_desc)[id];
   const TexDesc t0{td.x, td.y, td.z, td.w};
@@ -215,7 +237,7 @@ GLZ_D vec4 texture2d_lod(const DeviceScene& S, uint32_t id, float u, float v, co
       uu = u + s * fp.du;
       vv = v + s * fp.dv;
     }
-    const vec4 r = bilinear_level(S, t, pool, uu, vv);
+    const vec4 r = bilinear_level<SHORT>(S, t, pool, uu, vv);
     if (upper == 0u) {
       cur = r;
     } else {
@@ -239,7 +261,8 @@ GLZ_D vec3 texture_rgb(const DeviceScene& S, uint32_t id, vec2 uv) {
   vec4 t = texture2d(S, id, uv.x, uv.y);
   return mk3(t.x, t.y, t.z);
 }
-GLZ_D float texture_r(const DeviceScene& S, uint32_t id, vec2 uv) { return texture2d(S, id, uv.x, uv.y).x; }
+template <bool SHORT = true>
+GLZ_D float texture_r(const DeviceScene& S, uint32_t id, vec2 uv) { return texture2d<SHORT>(S, id, uv.x, uv.y).x; }
 
 // ---------------------------------------------------------------------------------------------
 // Shading frame (shading_space.glsl)
@@ -441,16 +464,17 @@ GLZ_D float oren_nayar(float roughness, vec3 wo, vec3 wi) {
   return kInvPi * (A + B * maxcos * sinalpha * tanbeta);
 }
 
+template <bool SHORT = true>   // (texel_address: false in the post stage, whose kernels keep the sampler they had)
 GLZ_D void fetch_material_textures(const DeviceScene& S, SurfacePoint& P, const TexFootprint& fp) {
   const uint32_t kind = P.mat.bsdf_index;
   P.tint = mk3(0.0f, 0.0f, 0.0f);
   P.rough_tex = P.metal_tex = 0.0f;
   if (kind == kBsdfLambert || kind == kBsdfUber) {
-    const vec4 tx = texture2d_lod(S, P.mat.diffuse, P.uv.x, P.uv.y, fp);
+    const vec4 tx = texture2d_lod<SHORT>(S, P.mat.diffuse, P.uv.x, P.uv.y, fp);
     P.tint = mk3(tx.x, tx.y, tx.z) * mk3(P.mat.diffuse_mul[0], P.mat.diffuse_mul[1], P.mat.diffuse_mul[2]);
   }
-  if (kind == kBsdfMetal || kind == kBsdfFrosted || kind == kBsdfUber) P.rough_tex = texture2d_lod(S, P.mat.roughness, P.uv.x, P.uv.y, fp).x;
-  if (kind == kBsdfUber) P.metal_tex = texture2d_lod(S, P.mat.metalness, P.uv.x, P.uv.y, fp).x;
+  if (kind == kBsdfMetal || kind == kBsdfFrosted || kind == kBsdfUber) P.rough_tex = texture2d_lod<SHORT>(S, P.mat.roughness, P.uv.x, P.uv.y, fp).x;
+  if (kind == kBsdfUber) P.metal_tex = texture2d_lod<SHORT>(S, P.mat.metalness, P.uv.x, P.uv.y, fp).x;
 }
 GLZ_D vec3 diffuse_tint(const DeviceScene&, const SurfacePoint& P) { return P.tint; }
 
@@ -549,14 +573,20 @@ GLZ_D vec3 cosine_hemisphere(float rx, float ry, float woz) {   // mat_lambert_s
 }
 
 // BSDF sampling for the path continuation; returns the pdf (0 = terminate the path).
-GLZ_D float bsdf_sample(const DeviceScene& S, const SurfacePoint& P, vec3 xi, Spec& value, vec3& wiW) {
+// `lambert_value` (have_lambert false: none): the value bsdf_eval gave this very hit when it is Lambert -- from_surface_color(tint / pi) of the same
+// tint, the same bits -- handed over by a caller that ran the evaluation; the conversion (some 50 instructions and eight loads of basis
+// rows) is then not made a second time.  The flag travels next to the pointer on purpose: the pointer always names the caller's spectrum
+// and is read only under the flag.  As one nullable pointer (`have ? &spectrum : nullptr`) the caller's spectrum has its address taken
+// under a select, stays in memory, and every k_shade instantiation gets 68 bytes of scratch.
+GLZ_D float bsdf_sample(const DeviceScene& S, const SurfacePoint& P, vec3 xi, Spec& value, vec3& wiW, const Spec* lambert_value = nullptr, bool have_lambert = false) {
   const MatScalars& m = P.mat;
   const uint32_t kind = m.bsdf_index;
   const vec3 wo = to_local(P.woW, P.frame);
   if (kind == kBsdfLambert) {   // mat_lambert_sample_value.rcall:31-41
     vec3 wi = cosine_hemisphere(xi.x, xi.y, wo.z);
     wiW = normalize3(to_world(wi, P.frame));
-    value = from_surface_color(diffuse_tint(S, P) * kInvPi);
+    if (have_lambert) value = *lambert_value;
+    else value = from_surface_color(diffuse_tint(S, P) * kInvPi);
     return fabsf(wi.z) * kInvPi;
   }
   if (kind == kBsdfMirror) {   // mat_mirror_sample_value.rcall:16-34
@@ -678,9 +708,23 @@ GLZ_D float sq_dist(vec3 a, vec3 b) {
 
 // Piecewise-constant CDF lookup used by both sky searches.  `fetch(i)` returns cdf[i].
 // (sample_marginal / sample_conditional, light_sky_sample_visible.rcall:31-98)
+// `bracket` (null: none): the cdf's bracket table (device/types.h, sky_bracket_table).  The search is the upper bound of xi -- the first
+// entry above it -- and in a monotone cdf that index lies in [bracket[b], bracket[b + 1]] for xi in [b, b + 1) / kSkyBracketBuckets: the
+// entries before bracket[b] are <= b / B <= xi, the entry at bracket[b + 1] is above (b + 1) / B > xi.  The same loop over that range ends
+// on the same index after three or four dependent reads instead of eleven (1 025 entries); `off`, the two reads behind it and the result
+// are the full search's.  xi outside [0, 1), a NaN xi and a fall-back table (kSkyBracketFallback: the builder found the cdf not monotone,
+// where the index does depend on the path) take the full search.  (b is exact: xi * 256 only moves the exponent, below 256.)
 template <class Fetch>
-GLZ_D float sample_cdf(float xi, int size, Fetch fetch, uint32_t& offset_out) {
+GLZ_D float sample_cdf(float xi, int size, Fetch fetch, uint32_t& offset_out, const uint16_t* bracket = nullptr) {
   int first = 0, len = size;
+  if (bracket != nullptr && xi >= 0.0f && xi < 1.0f) {
+    const int b = (int)(xi * (float)kSkyBracketBuckets);
+    const int lo = (int)bracket[b], hi = (int)bracket[b + 1];
+    if (lo != (int)kSkyBracketFallback) {
+      first = lo;
+      len = hi - lo;
+    }
+  }
   while (len > 0) {
     int half = len >> 1, middle = first + half;
     if (fetch(middle) <= xi) {
@@ -702,7 +746,7 @@ GLZ_D float sample_cdf(float xi, int size, Fetch fetch, uint32_t& offset_out) {
 // DEFER_SKY_TEXEL: the sky map's texel is fetched by light_emission (same template argument), for the samples that are used, instead of
 // here.  k_path passes false: its launch loop sits at 128 registers and the fetch code a second time cost it three spilled ones.
 template <bool DEFER_SKY_TEXEL = true>
-GLZ_D void sample_light(const DeviceScene& S, uint32_t light_index, vec3 p, vec3 xi, float scene_radius, LightSample& out) {
+GLZ_D void sample_light(const DeviceScene& S, uint32_t light_index, vec3 p, vec3 xi, float scene_radius, LightSample& out, const uint16_t* sky_bracket = nullptr) {
   const RTLight* L = &S.lights[light_index];
   const uint32_t kind = L->shader;
   if (S.tex_counter) {   // counting pass
@@ -751,8 +795,8 @@ GLZ_D void sample_light(const DeviceScene& S, uint32_t light_index, vec3 p, vec3
   }
   // Sky: light_sky_sample_visible.rcall:100-135
   uint32_t row;
-  const float* cdf = S.sky_cdf;   // (k_shade: in LDS -- the search is ten dependent reads; the row's two values read once below come from memory, in one load)
-  float v = sample_cdf(xi.y, (int)S.sky_header.marginal_cdf_count, [&](int i) { return cdf[i]; }, row);
+  const float* cdf = S.sky_cdf;   // (k_shade: in LDS -- the search is eleven dependent reads over 1 025 entries, three or four inside a bracket; the row's two values read once below come from memory, in one load)
+  float v = sample_cdf(xi.y, (int)S.sky_header.marginal_cdf_count, [&](int i) { return cdf[i]; }, row, sky_bracket);   // (sky_bracket: S.sky_cdf's table, where the caller has it at hand)
   const float2 of_row = S.sky_rows[row];   // (sky_marginal[marginal_cdf_count + row], sky_marginal[conditional_integral_offset + row])
   float v_pdf = of_row.x / S.sky_header.marginal_integral;
   // The conditional lookups hand integer texel coordinates to a normalised REPEAT/NEAREST sampler: every

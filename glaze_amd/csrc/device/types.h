@@ -262,6 +262,19 @@ struct SkyHeader {
   float cond_value00;
 };
 
+// The bracket table of the sky's row search (shading_tables.h: sky_bracket_table; device/shading.h: sample_cdf): kSkyBracketBuckets + 1
+// entries of 16 bits, entry b the full search's `first` for xi = b / kSkyBracketBuckets.  It follows the 3 H + 1 floats of
+// DeviceScene::sky_marginal in the same buffer, at the next multiple of four floats (it is staged in 16-byte pieces), padded to whole pieces.
+constexpr uint32_t kSkyLdsFloats = 1088;   // the cdf entries k_shade (and the light-sample hook) stage in LDS: skies of up to 1 087 rows
+constexpr uint32_t kSkyBracketBuckets = 256;
+constexpr uint32_t kSkyBracketFallback = 0xFFFFu;   // every entry of the table of a cdf that is not monotone, or too long for 16 bits: the search takes all of it
+constexpr uint32_t kSkyBracketFloats = ((kSkyBracketBuckets + 1u) * 2u + 15u) / 16u * 4u;   // the table's 16-byte pieces, in floats
+inline
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+uint32_t sky_bracket_offset(uint32_t marginal_cdf_count) { return marginal_cdf_count == 0u ? 0u : (3u * (marginal_cdf_count - 1u) + 1u + 3u) / 4u * 4u; }   // in floats
+
 // Everything the kernels need about a scene (device pointers).
 struct DeviceScene {
   const float4* vertices;          // 2 x float4 per vertex (VertexPacked, raytrace_commons.glsl:11-14)

@@ -150,10 +150,24 @@ __global__ void __launch_bounds__(kBlock) k_debug_bsdf_sample(DeviceScene S, uin
   wi3[3 * t] = wi.x; wi3[3 * t + 1] = wi.y; wi3[3 * t + 2] = wi.z;
   GLZ_BINS value16[16 * t + i] = value.w[i];
 }
-// (the sky's row search reads the marginal cdf from memory here, S.sky_cdf as the host set it; k_shade's LDS copy is the render tests' to cover)
+// SKY_LDS: the sky's marginal cdf fits kSkyLdsFloats and the row search reads it, and its bracket table, from a copy in LDS made the way
+// k_shade makes its own; otherwise the search reads the cdf from memory (S.sky_cdf as the host set it), all of it, as k_shade's does for a
+// sky that tall.
+template <bool SKY_LDS>
 __global__ void __launch_bounds__(kBlock) k_debug_light_sample(DeviceScene S, uint32_t light, const float* __restrict__ pos3, const float* __restrict__ rand3,
                                                                uint32_t n, float scene_radius, float* __restrict__ wi3, float* __restrict__ dist,
                                                                float* __restrict__ pdf, float* __restrict__ emission16) {
+  __shared__ uint4 s_sky[SKY_LDS ? kSkyLdsFloats / 4 + kSkyBracketFloats / 4 : 1];
+  const uint16_t* bracket = nullptr;
+  if (SKY_LDS) {
+    static_assert(kSkyBracketFloats / 4 <= kBlock, "the bracket table is copied one piece per thread");
+    const uint32_t n_sky = S.sky_header.marginal_cdf_count;   // (at most kSkyLdsFloats: launch_debug_light_sample)
+    for (uint32_t i = threadIdx.x; i < (n_sky + 3u) / 4u; i += kBlock) s_sky[i] = reinterpret_cast<const uint4*>(S.sky_marginal)[i];
+    if (threadIdx.x < kSkyBracketFloats / 4) s_sky[kSkyLdsFloats / 4 + threadIdx.x] = reinterpret_cast<const uint4*>(S.sky_marginal)[sky_bracket_offset(n_sky) / 4u + threadIdx.x];
+    __syncthreads();
+    S.sky_cdf = reinterpret_cast<const float*>(s_sky);
+    bracket = reinterpret_cast<const uint16_t*>(s_sky + kSkyLdsFloats / 4);
+  }
   const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
   if (t >= n) return;
   S.tex_counter = nullptr;
@@ -161,7 +175,7 @@ __global__ void __launch_bounds__(kBlock) k_debug_light_sample(DeviceScene S, ui
   ls.wiW = mk3(0.0f, 0.0f, 0.0f);
   ls.pdf = 0.0f;
   ls.distance = 0.0f;
-  sample_light(S, light, mk3(pos3[3 * t], pos3[3 * t + 1], pos3[3 * t + 2]), mk3(rand3[3 * t], rand3[3 * t + 1], rand3[3 * t + 2]), scene_radius, ls);
+  sample_light(S, light, mk3(pos3[3 * t], pos3[3 * t + 1], pos3[3 * t + 2]), mk3(rand3[3 * t], rand3[3 * t + 1], rand3[3 * t + 2]), scene_radius, ls, bracket);
   const Spec e = light_emission(S, ls);
   wi3[3 * t] = ls.wiW.x; wi3[3 * t + 1] = ls.wiW.y; wi3[3 * t + 2] = ls.wiW.z;
   dist[t] = ls.distance;
@@ -202,6 +216,8 @@ hipError_t launch_debug_bsdf_sample(hipStream_t st, const DeviceScene& scene, ui
 }
 hipError_t launch_debug_light_sample(hipStream_t st, const DeviceScene& scene, uint32_t light, const float* pos3, const float* rand3, uint32_t n,
                                      float scene_radius, float* wi3, float* dist, float* pdf, float* emission16) {
-  return launch_per_item(st, k_debug_light_sample, n, scene, light, pos3, rand3, n, scene_radius, wi3, dist, pdf, emission16);
+  const bool sky_lds = scene.sky_marginal != nullptr && scene.sky_header.marginal_cdf_count > 1u && scene.sky_header.marginal_cdf_count <= kSkyLdsFloats;
+  return sky_lds ? launch_per_item(st, k_debug_light_sample<true>, n, scene, light, pos3, rand3, n, scene_radius, wi3, dist, pdf, emission16)
+                 : launch_per_item(st, k_debug_light_sample<false>, n, scene, light, pos3, rand3, n, scene_radius, wi3, dist, pdf, emission16);
 }
 }  // namespace glz

@@ -74,7 +74,7 @@ template <bool CHAIN>
 __device__ __forceinline__ GuideVertex guide_vertex(const DeviceScene& S, float4 hr, uint32_t hit_inst, vec3 direction) {
   const TexFootprint fp{kNoLod, 0.0f, 0.0f, 1u};
   HitVertex hv = load_hit_vertex(S, hr, [&]() { return hit_inst; });
-  finish_hit_vertex<CHAIN>(S, hv, fp);
+  finish_hit_vertex<CHAIN, false>(S, hv, fp);   // (false, here and below: the sampler without the shading kernels' short forms, device/shading.h texel_address)
   const MatScalars& mat = hv.mat;
   GuideVertex v;
   v.n = normalize3(hv.ns);
@@ -82,14 +82,14 @@ __device__ __forceinline__ GuideVertex guide_vertex(const DeviceScene& S, float4
   if (!(post::finite1(v.n.x) && post::finite1(v.n.y) && post::finite1(v.n.z))) v.n = mk3(0.0f, 0.0f, 0.0f);   // a zero-length ns normalises to NaN
   v.albedo = mk3(1.0f, 1.0f, 1.0f);
   if (mat.bsdf_index == kBsdfLambert || mat.bsdf_index == kBsdfUber) {
-    const vec4 tx = texture2d_lod(S, mat.diffuse, hv.uv.x, hv.uv.y, fp);
+    const vec4 tx = texture2d_lod<false>(S, mat.diffuse, hv.uv.x, hv.uv.y, fp);
     v.albedo = mk3(tx.x, tx.y, tx.z) * mk3(mat.diffuse_mul[0], mat.diffuse_mul[1], mat.diffuse_mul[2]);
   }
   v.go_on = false;
   v.point = hv.point;
   v.wiW = mk3(0.0f, 0.0f, 0.0f);
   if (CHAIN && mat.is_specular != 0) {
-    const SurfacePoint P = hit_surface_point(S, hv, direction, fp);
+    const SurfacePoint P = hit_surface_point<false>(S, hv, direction, fp);
     Spec value = spec_set(0.0f);
     const float pdf = bsdf_sample(S, P, mk3(0.0f, 0.0f, 0x1.fffffep-1f), value, v.wiW);
     v.go_on = pdf != 0.0f && post::finite1(v.wiW.x) && post::finite1(v.wiW.y) && post::finite1(v.wiW.z);

@@ -24,7 +24,7 @@ using namespace dev;
 // k_shade: path_trace.rgen:170-237 minus the two traceRayEXT calls, raytrace_hit.rchit:30-71
 // ---------------------------------------------------------------------------------------------
 // the sky's marginal cdf (H + 1 floats) is staged in LDS when it fits (the values and row integrals next to it are read once per sample, from memory: staging all 3 H + 1 floats was 12 of the 19 KB a block copies before it starts)
-constexpr uint32_t kSkyLdsFloats = 1088;   // (skies of up to 1 087 rows; a taller one is searched in memory)
+// (kSkyLdsFloats, device/types.h: skies of up to 1 087 rows; a taller one is searched in memory)
 
 // (GLZ_SHADE_WAVES = 4, device/tuning.h: 128 VGPRs, 4 of them spilled, since the light's spectrum is made after the BSDF evaluation and the
 // importance is read where it is used (natural demand 152 -> 132): 0.357 -> 0.348 ms; at three waves the same code takes 0.363 ms.)
@@ -60,11 +60,14 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   // One pool: [the importance the block's 256 pixels arrived with, 4 x 4 KB, read in whole lines by the prologue | the sky's marginal cdf |
   // the scene tables] while the block shades; after its last barrier the first 24 KB are the staging area of the state the pixels leave
   // (StagedState): 6 x 16 bytes per pixel, written where the pixel lives instead of where its thread sat.
-  __shared__ uint4 s_pool[kShadeBlock * 4 + kSkyLdsFloats / 4 + kShadeLdsTableBytes / 16];
+  // (the cdf's bracket table right behind it, 33 pieces: the row search starts inside the bracket of its xi, sample_cdf)
+  __shared__ uint4 s_pool[kShadeBlock * 4 + kSkyLdsFloats / 4 + kSkyBracketFloats / 4 + kShadeLdsTableBytes / 16];
   uint4* s_imp = s_pool;
   float* s_sky = reinterpret_cast<float*>(s_pool + kShadeBlock * 4);
-  uint4* s_tables = s_pool + kShadeBlock * 4 + kSkyLdsFloats / 4;
-  static_assert(6u * kShadeBlock <= kShadeBlock * 4 + kSkyLdsFloats / 4 + kShadeLdsTableBytes / 16, "the staging area of the path state fits the pool");
+  uint4* s_bracket = s_pool + kShadeBlock * 4 + kSkyLdsFloats / 4;
+  uint4* s_tables = s_bracket + kSkyBracketFloats / 4;
+  static_assert(6u * kShadeBlock <= kShadeBlock * 4 + kSkyLdsFloats / 4 + kSkyBracketFloats / 4 + kShadeLdsTableBytes / 16, "the staging area of the path state fits the pool");
+  static_assert(kSkyBracketFloats / 4 <= kShadeBlock, "the bracket table is copied one piece per thread");
   // The small scene tables every hit walks through one after the other -- shading record -> RTMaterial -> texture descriptor
   // -> texels, light pick -> RTLight -- are staged in LDS when they fit: each lookup that stays on chip takes a dependent
   // memory round trip (1-2 us under load, the kernel's bound) off the hit's critical path.
@@ -79,8 +82,10 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
   // wave's load instead of four waves', a sky of 1 024 rows two loads per thread instead of five).  The cdf's last piece reads up to three
   // floats past it -- marginal values, which follow it in the same array (3 H + 1 floats; the pieces cover at most H + 4 of them, and exactly 4 when H = 1).
   if (threadIdx.x < 64u) reinterpret_cast<float4*>(s_lut)[threadIdx.x] = reinterpret_cast<const float4*>(A.scene.srgb_lut)[threadIdx.x];
-  if (SKY)
+  if (SKY) {
     for (uint32_t i = threadIdx.x; i < (n_sky + 3u) / 4u; i += kShadeBlock) s_pool[kShadeBlock * 4 + i] = reinterpret_cast<const uint4*>(A.scene.sky_marginal)[i];
+    if (threadIdx.x < kSkyBracketFloats / 4) s_bracket[threadIdx.x] = reinterpret_cast<const uint4*>(A.scene.sky_marginal)[sky_bracket_offset(n_sky) / 4u + threadIdx.x];
+  }
   s_bin[threadIdx.x] = 0;
   const SceneTables tables(A.scene);
   if (TABLES) tables.stage(A.scene, s_tables, kShadeBlock);
@@ -194,6 +199,7 @@ __global__ void __launch_bounds__(kShadeBlock, GLZ_SHADE_WAVES) k_shade(const La
     SharedQueue queue{A2};
     staged.A = &A2;
     staged.lds_imp = (LdsNodePtr)(reinterpret_cast<u32x4*>(s_imp) + s_perm[threadIdx.x]);
+    staged.lds_sky_bracket = SKY ? reinterpret_cast<const uint16_t*>(s_bracket) : nullptr;
     staged.lds_pick = (StagedState::LdsPickPtr)(reinterpret_cast<StagedState::u32x2*>(s_pick) + s_perm[threadIdx.x]);
 #ifdef GLZ_SECTION_TIMES
     staged.sec_last = __builtin_amdgcn_s_memtime();

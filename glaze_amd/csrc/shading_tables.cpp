@@ -126,6 +126,59 @@ void sky_row_pairs(const float* marginal_values, const float* conditional_integr
   }
 }
 
+float sky_cdf_search(const float* cdf, uint32_t size_u, float xi, const uint16_t* bracket, uint32_t* offset_out) {
+  const int size = (int)size_u;
+  int first = 0, len = size;
+  if (bracket != nullptr && xi >= 0.0f && xi < 1.0f) {
+    const int b = (int)(xi * (float)kSkyBracketBuckets);
+    const int lo = (int)bracket[b], hi = (int)bracket[b + 1];
+    if (lo != (int)kSkyBracketFallback) {
+      first = lo;
+      len = hi - lo;
+    }
+  }
+  while (len > 0) {
+    const int half = len >> 1, middle = first + half;
+    if (cdf[middle] <= xi) {
+      first = middle + 1;
+      len -= half + 1;
+    } else {
+      len = half;
+    }
+  }
+  int off = first - 1;
+  off = off < 0 ? 0 : (off > size - 2 ? size - 2 : off);
+  const float cur = cdf[off], next = cdf[off + 1];
+  float du = xi - cur;
+  if (next - cur > 0.0f) du /= next - cur;
+  *offset_out = (uint32_t)off;
+  return ((float)off + du) / (float)size;
+}
+
+void sky_bracket_table(const float* cdf, uint32_t size, uint16_t* table_out) {
+  bool monotone = size < kSkyBracketFallback;
+  for (uint32_t i = 0; monotone && i + 1 < size; ++i) monotone = cdf[i + 1] >= cdf[i];   // (a NaN fails it)
+  if (monotone && size != 0u) monotone = cdf[0] == cdf[0];   // (a cdf of one entry that is a NaN)
+  for (uint32_t b = 0; b <= kSkyBracketBuckets; ++b) {
+    if (!monotone) {
+      table_out[b] = (uint16_t)kSkyBracketFallback;
+      continue;
+    }
+    const float xi = (float)b / (float)kSkyBracketBuckets;
+    int first = 0, len = (int)size;   // the full search's bisection
+    while (len > 0) {
+      const int half = len >> 1, middle = first + half;
+      if (cdf[middle] <= xi) {
+        first = middle + 1;
+        len -= half + 1;
+      } else {
+        len = half;
+      }
+    }
+    table_out[b] = (uint16_t)first;
+  }
+}
+
 bool ShadingTables::has_non_opaque() const {
   for (const RTMaterial& m : h_materials)
     if (m.opacity != 0u) return true;
@@ -231,7 +284,13 @@ bool ShadingTables::build_lights_and_sky(hipStream_t st, const SceneData& data, 
     h_sky_rows.resize(2 * (size_t)H);
     sky_row_pairs(h_sky_marginal.data() + h_sky_header.marginal_cdf_count, h_sky_marginal.data() + h_sky_header.conditional_integral_offset, H, h_sky_rows.data());
     if (!hip_ok(d_sky_rows_.upload(reinterpret_cast<const float2*>(h_sky_rows.data()), H, st), "upload sky rows", err)) return false;
-    if (!hip_ok(d_sky_marginal_.upload(h_sky_marginal.data(), h_sky_marginal.size(), st), "upload sky marginal", err)) return false;
+    // the marginal cdf's bracket table travels behind the three arrays, in the same buffer (sky_bracket_offset: whole 16-byte pieces)
+    h_sky_bracket.assign(kSkyBracketFloats * 2u, 0);
+    sky_bracket_table(h_sky_marginal.data(), h_sky_header.marginal_cdf_count, h_sky_bracket.data());
+    std::vector<float> with_bracket(sky_bracket_offset(h_sky_header.marginal_cdf_count) + kSkyBracketFloats, 0.0f);
+    memcpy(with_bracket.data(), h_sky_marginal.data(), h_sky_marginal.size() * sizeof(float));
+    memcpy(with_bracket.data() + sky_bracket_offset(h_sky_header.marginal_cdf_count), h_sky_bracket.data(), h_sky_bracket.size() * sizeof(uint16_t));
+    if (!hip_ok(d_sky_marginal_.upload(with_bracket.data(), with_bracket.size(), st), "upload sky marginal", err)) return false;
     if (!hip_ok(d_sky_cond_values_.upload(values.data(), values.size(), st), "upload sky values", err)) return false;
     if (!hip_ok(d_sky_cond_cdf_.upload(cond_cdf.data(), cond_cdf.size(), st), "upload sky cdf", err)) return false;
     if (!hip_ok(hipStreamSynchronize(st), "sky upload", err)) return false;

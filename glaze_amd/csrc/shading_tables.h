@@ -14,6 +14,16 @@ namespace glz {
 // (glz_host_sky_row_pairs exposes it).
 void sky_row_pairs(const float* marginal_values, const float* conditional_integrals, size_t n, float* pairs_out);
 
+// The search of a piecewise-constant cdf of `size` entries as the kernels run it (device/shading.h: sample_cdf, the sky's row search):
+// the upper bound of xi by bisection, the clamped offset and the position inside its step.  `bracket` null: the full search; otherwise
+// it starts inside the bracket of xi wherever the device's does.  Returns the sample, *offset_out the row.
+float sky_cdf_search(const float* cdf, uint32_t size, float xi, const uint16_t* bracket, uint32_t* offset_out);
+// The bracket table of a cdf (device/types.h: kSkyBracketBuckets + 1 entries): entry b is where the full search's bisection ends for
+// xi = b / kSkyBracketBuckets.  In a monotone cdf the search of any xi in [b, b + 1) / kSkyBracketBuckets ends inside [entry b, entry b + 1].
+// A cdf with a descent or a NaN anywhere (there the end depends on the path the bisection takes), or of more entries than 16 bits count,
+// gets the fall-back table: kSkyBracketFallback in every entry.  (glz_host_sky_bracket_table / glz_host_sky_cdf_search expose the two.)
+void sky_bracket_table(const float* cdf, uint32_t size, uint16_t* table_out);
+
 // Whether fresnel_conductor (device/shading.h) of a spectra pair -- n = ior, a = ior2abs2, 16 bins each -- is finite in every bin for
 // every cosine |c| <= 2, so that its product with a zero metalness is a zero (kSpectraConductorFinite; glz_host_conductor_finite exposes
 // it).  In double precision, per bin: n and a finite and at most 2^60 in magnitude, and the exact minima over |c| <= 2 of the routine's two
@@ -46,6 +56,7 @@ class ShadingTables {
   std::vector<RTLight> h_lights;
   std::vector<float> h_sky_marginal;
   std::vector<float> h_sky_rows;   // per row (marginal value, conditional integral), sky_row_pairs of h_sky_marginal's two last parts
+  std::vector<uint16_t> h_sky_bracket;   // sky_bracket_table of the marginal cdf; on the device behind h_sky_marginal's floats (sky_bracket_offset)
   SkyHeader h_sky_header{};
   RTSky h_sky{};
   uint32_t lights_no = 0;   // lights.len() after reorder_lights (scene.rs:1549)

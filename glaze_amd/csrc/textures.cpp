@@ -58,6 +58,8 @@ bool Textures::upload(hipStream_t st, const std::vector<TextureData>& textures, 
       return err.fail(GLZ_E_INVALID_DATA, "texture has inconsistent dimensions");
     const Tiling tiling(t.info.format, t.info.width, t.info.height);
     if (pool.size() + tiling.bytes() > 0xFFFFFFFFull || tiling.tiles_x >= (1u << 24)) return err.fail(GLZ_E_UNSUPPORTED, "texture pool larger than 4 GiB");
+    // texel_address multiplies the tile row by tiles_x with a 24-bit multiply (2^24 tile rows are a strip of 2^26 texel rows or more)
+    if (tiling.tiles_y >= (1u << 24)) return err.fail(GLZ_E_UNSUPPORTED, "texture of 2^24 tile rows or more");
     if (t.info.width == 1 && t.info.height == 1) {
       // the texel travels in the descriptor (device/shading.h kTexInline): materials' default maps cost no texel load
       uint32_t bits = 0;

@@ -1003,6 +1003,17 @@ int glz_host_srgb8_thresholds(float thresholds_out[256]);
 /* the per-row table a sky sample reads once its row is found, as scene creation builds it from the sky's marginal values and conditional
  * integrals (n rows each): pairs_out[2 y] = marginal_values[y], pairs_out[2 y + 1] = conditional_integrals[y] -- the same floats, interleaved */
 int glz_host_sky_row_pairs(const float* marginal_values, const float* conditional_integrals, uint64_t n, float* pairs_out);
+/* the bracket table scene creation makes of the sky's marginal cdf (`size` entries) for the kernels' row search: 257 entries, entry b the
+ * index at which the full search's bisection ends for xi = b / 256; 0xFFFF in every entry (the fall-back table: searches take the whole
+ * cdf) when the cdf has a descent or a NaN, or 65 535 entries or more */
+int glz_host_sky_bracket_table(const float* cdf, uint64_t size, uint16_t* table_out);
+/* the kernels' row search on the host, for n values xi: the full bisection (bracket_or_null null) or the one that starts inside the
+ * bracket of xi (a table of glz_host_sky_bracket_table for this cdf; GLZ_E_ARG for one that leaves it); xi outside [0, 1), a NaN and the
+ * fall-back table take the full search.  sample_out[i] = (row + position inside the row's step) / size, offset_out[i] = the row */
+int glz_host_sky_cdf_search(const float* cdf, uint64_t size, const uint16_t* bracket_or_null, const float* xi, uint64_t n, float* sample_out, uint32_t* offset_out);
+/* the texel index the sampler gives integer coordinate i in a REPEAT texture of n >= 1 texels: the non-negative remainder, taken as
+ * i & (n - 1) when n is a power of two and through i % n otherwise, as the kernels do */
+int glz_host_texel_wrap(const int32_t* i, uint64_t count, int32_t n, int32_t* index_out);
 /* the flag scene creation and material updates give a pair of metal spectra (ior = n, ior2abs2 = n^2 + k^2, 16 bins each): *flag_out = 1
  * when the conductor Fresnel term of the pair is finite in every bin for every cosine |c| <= 2 -- both are finite and at most 2^60 in
  * magnitude, and the minima over |c| <= 2 of a + 2nc + c^2 and of a c^2 + 2nc + 1 are at least 2^-10 (|a| + 4|n| + 5), in double
