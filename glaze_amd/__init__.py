@@ -24,7 +24,7 @@ from .abi import GlazeError
 from .scene_desc import MESH_DTYPE, VERTEX_DTYPE, SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
 
 __all__ = ["parse", "converted_file", "ParsedScene", "RayTraceInstance", "RayTraceScene", "RayTraceRenderer", "Integrator",
-           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points", "host_skin", "host_morph", "host_vertex_normals", "host_weld_groups",
+           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points", "host_skin", "host_bone_dual_quats", "host_morph", "host_vertex_normals", "host_weld_groups",
            "host_project_constants"]
 
 
@@ -257,17 +257,37 @@ def _skin_arrays(joints, weights):
     return np.ascontiguousarray(j, np.uint16), w
 
 
-def host_skin(bind, joints, weights, bones):
+_SKIN_BLENDS = {"linear": abi.SKIN_LINEAR, "dual_quaternion": abi.SKIN_DUAL_QUATERNION}
+
+
+def _skin_blend(blend):
+    if blend not in _SKIN_BLENDS:
+        raise ValueError("blend must be 'linear' or 'dual_quaternion'")
+    return _SKIN_BLENDS[blend]
+
+
+def host_skin(bind, joints, weights, bones, blend="linear"):
     """glz_host_skin: the skinning rule (include/glaze_abi.h holds the specification) on the host, no device, the reference of k_skin.
     bind: n vertices in any form update_vertices takes; joints: (n, 4) integers; weights: (n, 4) float32; bones: (n_bones, 16) float32,
-    column-major.  Returns the posed vertices, (n, 8) float32."""
+    column-major.  blend="dual_quaternion": glz_host_skin_dq, the dual-quaternion rule, the reference of k_skin_dq.  Returns the posed
+    vertices, (n, 8) float32."""
+    fn = abi.lib().glz_host_skin_dq if _skin_blend(blend) == abi.SKIN_DUAL_QUATERNION else abi.lib().glz_host_skin
     v = _vertex_array(bind)
     j, w = _skin_arrays(joints, weights)
     b = _transform_array(bones)
     if j.shape[0] != v.shape[0]:
         raise ValueError("joints and weights must have one row per vertex")
     out = np.zeros_like(v)
-    abi.check(abi.lib().glz_host_skin(_ptr(v), _ptr(j), _ptr(w), v.shape[0], _ptr(b), b.shape[0], _ptr(out)))
+    abi.check(fn(_ptr(v), _ptr(j), _ptr(w), v.shape[0], _ptr(b), b.shape[0], _ptr(out)))
+    return out
+
+
+def host_bone_dual_quats(bones):
+    """glz_host_bone_dual_quats: the bone conversion of the dual-quaternion rule, (n_bones, 16) float32 matrices -> (n_bones, 8) float32,
+    the unit quaternion (x, y, z, w) and the dual part (dx, dy, dz, dw) a bone, as the kernels of that mode read them."""
+    b = _transform_array(bones)
+    out = np.zeros((b.shape[0], 8), np.float32)
+    abi.check(abi.lib().glz_host_bone_dual_quats(_ptr(b), b.shape[0], _ptr(out)))
     return out
 
 
@@ -800,14 +820,28 @@ class RayTraceRenderer:
         v = _vertex_array(vertices)
         abi.check(abi.lib().glz_renderer_update_vertices(self._h, _ptr(v), int(first), v.shape[0], self._GEOMETRY_MODES.get(mode, mode)))
 
-    def add_skin(self, first, joints, weights, n_bones):
+    def add_skin(self, first, joints, weights, n_bones, blend="linear"):
         """A skin over the scene's vertices [first, first + n): joints (n, 4) integers below n_bones, weights (n, 4) float32.  The bind pose
-        is what the scene's vertices hold there now.  Returns the skin's id; the skin is the scene's (every renderer sharing it sees it)."""
+        is what the scene's vertices hold there now.  blend: 'linear' or 'dual_quaternion', as set_skin_blend takes it.  Returns the
+        skin's id; the skin is the scene's (every renderer sharing it sees it)."""
+        mode = _skin_blend(blend)
         j, w = _skin_arrays(joints, weights)
         skin = abi.Skin(int(first), j.shape[0], _ptr(j), _ptr(w), int(n_bones))
         skin_id = abi.check(abi.lib().glz_renderer_add_skin(self._h, C.cast(C.byref(skin), C.c_void_p)))
         self.__dict__.setdefault("_skin_sizes", {})[skin_id] = j.shape[0]   # (add_morph(skin=...) takes its vertex count from here)
+        if mode != abi.SKIN_LINEAR:
+            abi.check(abi.lib().glz_renderer_set_skin_blend(self._h, skin_id, mode))
         return skin_id
+
+    def set_skin_blend(self, skin, blend):
+        """How a skin blends its bones from its next pose on: 'linear' (linear-blend skinning, the default) or 'dual_quaternion' (the
+        blend is a rigid motion per vertex: joints keep their volume under twist and bend, normals stay exact).  Writes no vertex."""
+        abi.check(abi.lib().glz_renderer_set_skin_blend(self._h, int(skin), _skin_blend(blend)))
+
+    def skin_blend(self, skin):
+        """'linear' or 'dual_quaternion'"""
+        mode = abi.check(abi.lib().glz_renderer_skin_blend(self._h, int(skin)))
+        return next(k for k, v in _SKIN_BLENDS.items() if v == mode)
 
     def remove_skin(self, skin):
         """Frees a skin; the vertices stay as they are."""

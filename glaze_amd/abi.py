@@ -94,6 +94,7 @@ class SceneInfo(C.Structure):
 
 
 GEOMETRY_REFIT, GEOMETRY_REBUILD = 0, 1
+SKIN_LINEAR, SKIN_DUAL_QUATERNION = 0, 1
 
 
 class GeometryUpdateInfo(C.Structure):
@@ -250,6 +251,10 @@ PROTOTYPES = {
     "glz_renderer_read_motion_posed": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "glz_renderer_reproject_posed": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "glz_host_skin": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, _P]),
+    "glz_renderer_set_skin_blend": (C.c_int, [_P, C.c_int, C.c_int]),
+    "glz_renderer_skin_blend": (C.c_int, [_P, C.c_int]),
+    "glz_host_skin_dq": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, _P]),
+    "glz_host_bone_dual_quats": (C.c_int, [_P, C.c_uint32, _P]),
     "glz_renderer_add_morph": (C.c_int, [_P, _P]),
     "glz_renderer_remove_morph": (C.c_int, [_P, C.c_int]),
     "glz_renderer_animate": (C.c_int, [_P, _P, C.c_int]),

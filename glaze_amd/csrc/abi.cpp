@@ -369,6 +369,20 @@ int glz_renderer_remove_skin(glz_renderer* h, int skin) {
   GLZ_RET(h->r->remove_skin(skin, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_renderer_set_skin_blend(glz_renderer* h, int skin, int blend) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  GLZ_RET(h->r->set_skin_blend(skin, blend, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_skin_blend(glz_renderer* h, int skin) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  const int blend = h->r->scene()->skin_blend(skin, e);
+  if (blend < 0) return fail(e);
+  return blend;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_pose_skins(glz_renderer* h, const glz_pose* poses, uint32_t n, int mode) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");

@@ -448,6 +448,29 @@ int glz_host_skin(const glz_vertex* bind, const uint16_t* joints, const float* w
   return GLZ_OK;
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_host_skin_dq(const glz_vertex* bind, const uint16_t* joints, const float* weights, uint64_t n, const glz_transform* bones, uint32_t n_bones, glz_vertex* out) {
+  GLZ_GUARD_BEGIN
+  if (n_bones == 0 || !bones) return fail(GLZ_E_ARG, "host_skin_dq: no bones");
+  if (n == 0) return GLZ_OK;
+  if (!bind || !joints || !weights || !out) return fail(GLZ_E_ARG, "host_skin_dq: null argument");
+  for (uint64_t i = 0; i < 4 * n; ++i)
+    if (joints[i] >= n_bones) return fail(GLZ_E_ARG, "host_skin_dq: a joint names a bone past n_bones");
+  post::host_skin_dq(bind, joints, weights, (size_t)n, bones, n_bones, out);
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_host_bone_dual_quats(const glz_transform* bones, uint32_t n, float* out8) {
+  GLZ_GUARD_BEGIN
+  if (n == 0) return GLZ_OK;
+  if (!bones || !out8) return fail(GLZ_E_ARG, "host_bone_dual_quats: null argument");
+  for (uint32_t b = 0; b < n; ++b) {
+    float4 rows[post::kSkinDqBoneRows];
+    post::pack_bone_dq(bones[b], rows);
+    memcpy(out8 + 8 * (size_t)b, rows, sizeof rows);
+  }
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_host_morph(const glz_vertex* base, uint64_t n, const glz_morph_target* targets, uint32_t n_targets, const float* weights, glz_vertex* out) {
   GLZ_GUARD_BEGIN
   if (n_targets == 0 || n_targets > post::kMorphMaxTargets) return fail(GLZ_E_ARG, "host_morph: n_targets must be 1 .. 65536");

@@ -255,6 +255,8 @@ hipError_t launch_project_points(hipStream_t st, const post::ProjectConstants& C
 // when n_bones <= kSkinLdsBones, else read from memory.
 constexpr uint32_t kSkinLdsBones = 256;   // 12 KB of a block's LDS
 hipError_t launch_skin(hipStream_t st, const float4* bind, const uint2* joints, const float4* weights, uint32_t n, const float4* bones, uint32_t n_bones, float4* out);
+// the same under the dual-quaternion rule (k_skin_dq); bones: two float4 a bone (post::pack_bone_dq), 8 KB of LDS at kSkinLdsBones
+hipError_t launch_skin_dq(hipStream_t st, const float4* bind, const uint2* joints, const float4* weights, uint32_t n, const float4* bones, uint32_t n_bones, float4* out);
 
 // ---- morph targets (kernels_morph.hip; morph.h holds the rule and the layout) ----
 // What a morph's kernels read: post::MorphLayout on the device, and the base of its n vertices (two float4 a vertex).  Every row's count is
@@ -273,6 +275,8 @@ constexpr uint32_t kMorphLdsTargets = 1024;   // 4 KB of a block's LDS
 hipError_t launch_morph(hipStream_t st, const MorphArgs& m, float4* out);
 // the same, then the skinning rule on the morphed vertex (launch_skin's arguments), one store: the base is the skin's bind pose
 hipError_t launch_morph_skin(hipStream_t st, const MorphArgs& m, const uint2* joints, const float4* skin_weights, const float4* bones, uint32_t n_bones, float4* out);
+// the same with the dual-quaternion rule on the morphed vertex (launch_skin_dq's arguments; k_morph_skin_dq)
+hipError_t launch_morph_skin_dq(hipStream_t st, const MorphArgs& m, const uint2* joints, const float4* skin_weights, const float4* bones, uint32_t n_bones, float4* out);
 
 // ---- vertex normals from deformed positions (kernels_normals.hip; normals.h holds the rule and the layout) ----
 // What a normal set's kernels read: post::NormalLayout on the device.  Every face's three indices are below the scene's vertex count,

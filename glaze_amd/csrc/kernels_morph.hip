@@ -15,7 +15,8 @@
 //
 // STAGED: the weight table (one float a target) fits kMorphLdsTargets and is copied to LDS, whose reads (ds_read_b32) stay off the
 // vector-memory path; otherwise the weights are read from memory (global_load_dword).  k_morph_skin stages the bone table by k_skin's own
-// rule, independently: four instantiations.  One instantiation per address space, chosen at launch: no access is FLAT.
+// rule, independently: four instantiations, and four more of k_morph_skin_dq for skins in dual-quaternion mode.  One instantiation per
+// address space, chosen at launch: no access is FLAT.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -92,6 +93,34 @@ __global__ void __launch_bounds__(kMorphBlock) k_morph_skin(const float4* __rest
   }
 }
 
+// k_morph_skin for a skin in dual-quaternion mode: the same morph walk, then skin_vertex_dq on the registers, one store.  The bone table is
+// two float4 a bone (post::pack_bone_dq), staged by k_skin_dq's rule.
+template <bool STAGED, bool BONES_STAGED>
+__global__ void __launch_bounds__(kMorphBlock) k_morph_skin_dq(const float4* __restrict__ bind, const uint32_t* __restrict__ counts, const uint2* __restrict__ slices,
+                                                               const float4* __restrict__ entries, uint32_t n, const float* __restrict__ weights, uint32_t n_targets,
+                                                               const uint2* __restrict__ joints, const float4* __restrict__ skin_weights,
+                                                               const float4* __restrict__ bones, uint32_t n_bones, float4* __restrict__ out) {
+  __shared__ float s_weights[STAGED ? kMorphLdsTargets : 1];
+  __shared__ float4 s_bones[BONES_STAGED ? kSkinLdsBones * post::kSkinDqBoneRows : 1];
+  if (STAGED)
+    for (uint32_t k = threadIdx.x; k < n_targets; k += kMorphBlock) s_weights[k] = weights[k];
+  if (BONES_STAGED)
+    for (uint32_t k = threadIdx.x; k < post::kSkinDqBoneRows * n_bones; k += kMorphBlock) s_bones[k] = bones[k];
+  if (STAGED || BONES_STAGED) __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * kMorphBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kMorphBlock) {
+    float4 v0 = bind[2 * i], v1 = bind[2 * i + 1];
+    const uint2 jj = joints[i];
+    const float4 w = skin_weights[i];
+    if (STAGED) morph_row(i, counts, slices, entries, static_cast<const float*>(s_weights), v0, v1);
+    else morph_row(i, counts, slices, entries, in_memory(weights), v0, v1);
+    const uint32_t j[4] = {jj.x & 0xFFFFu, jj.x >> 16, jj.y & 0xFFFFu, jj.y >> 16};
+    if (BONES_STAGED) post::skin_vertex_dq(static_cast<const float4*>(s_bones), j, w, v0, v1);
+    else post::skin_vertex_dq(in_memory(bones), j, w, v0, v1);
+    out[2 * i] = v0;
+    out[2 * i + 1] = v1;
+  }
+}
+
 static uint32_t morph_blocks(uint32_t n) { return (uint32_t)std::min<uint64_t>(((uint64_t)n + kMorphBlock - 1) / kMorphBlock, kMorphMaxBlocks); }
 
 hipError_t launch_morph(hipStream_t st, const MorphArgs& m, float4* out) {
@@ -115,6 +144,22 @@ hipError_t launch_morph_skin(hipStream_t st, const MorphArgs& m, const uint2* jo
   if (m.n == 0) return hipSuccess;
   if (m.n_targets <= kMorphLdsTargets) launch_morph_skin_as<true>(st, m, joints, skin_weights, bones, n_bones, out);
   else launch_morph_skin_as<false>(st, m, joints, skin_weights, bones, n_bones, out);
+  return hipGetLastError();
+}
+
+template <bool STAGED>
+static void launch_morph_skin_dq_as(hipStream_t st, const MorphArgs& m, const uint2* joints, const float4* skin_weights, const float4* bones, uint32_t n_bones, float4* out) {
+  const dim3 grid(morph_blocks(m.n)), block(kMorphBlock);
+  if (n_bones <= kSkinLdsBones)
+    hipLaunchKernelGGL((k_morph_skin_dq<STAGED, true>), grid, block, 0, st, m.base, m.counts, m.slices, m.entries, m.n, m.weights, m.n_targets, joints, skin_weights, bones, n_bones, out);
+  else
+    hipLaunchKernelGGL((k_morph_skin_dq<STAGED, false>), grid, block, 0, st, m.base, m.counts, m.slices, m.entries, m.n, m.weights, m.n_targets, joints, skin_weights, bones, n_bones, out);
+}
+
+hipError_t launch_morph_skin_dq(hipStream_t st, const MorphArgs& m, const uint2* joints, const float4* skin_weights, const float4* bones, uint32_t n_bones, float4* out) {
+  if (m.n == 0) return hipSuccess;
+  if (m.n_targets <= kMorphLdsTargets) launch_morph_skin_dq_as<true>(st, m, joints, skin_weights, bones, n_bones, out);
+  else launch_morph_skin_dq_as<false>(st, m, joints, skin_weights, bones, n_bones, out);
   return hipGetLastError();
 }
 

@@ -584,6 +584,11 @@ bool Renderer::remove_skin(int id, Error& err) {
   if (!wait_idle(err) || !scene_->remove_skin(id, err)) return false;
   return group_.forward([=](Renderer& p, Error& e) { return p.remove_skin(id, e); }, err);
 }
+// host state alone (the next pose reads it): nothing to wait for, nothing restarts
+bool Renderer::set_skin_blend(int id, int blend, Error& err) {
+  if (!scene_->set_skin_blend(id, blend, err)) return false;
+  return group_.forward([=](Renderer& p, Error& e) { return p.set_skin_blend(id, blend, e); }, err);
+}
 bool Renderer::pose_skins(const glz_pose* poses, uint32_t n, int mode, Error& err) {
   if (!update_scene([&] { return scene_->pose_skins(poses, n, mode, err); }, err)) return false;
   return group_.forward([=](Renderer& p, Error& e) { return p.pose_skins(poses, n, mode, e); }, err);

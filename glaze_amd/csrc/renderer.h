@@ -32,6 +32,7 @@ class Renderer {
   bool update_vertices(const glz_vertex* v, uint32_t first, uint32_t n, int mode, Error& err);   // Scene::update_vertices; restarts accumulation
   int add_skin(const glz_skin& skin, Error& err);       // Scene::add_skin here and on every replica; the id, or -1
   bool remove_skin(int id, Error& err);
+  bool set_skin_blend(int id, int blend, Error& err);   // Scene::set_skin_blend here and on every replica
   bool pose_skins(const glz_pose* poses, uint32_t n, int mode, Error& err);   // Scene::pose_skins; restarts accumulation, like update_vertices
   int add_morph(const glz_morph& morph, Error& err);    // Scene::add_morph here and on every replica; the id, or -1
   bool remove_morph(int id, Error& err);

@@ -317,12 +317,13 @@ bool Scene::read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& er
 
 // the device half of add_skin and copy_skins: every buffer of the skin, or none of it
 int Scene::install_skin(int id, uint32_t first, std::vector<glz_vertex>&& bind, std::vector<uint16_t>&& joints, std::vector<float>&& weights, uint32_t n_bones,
-                        const float4* device_bind, Error& err) {
+                        int blend, const float4* device_bind, Error& err) {
   hipStream_t st = instance->stream;
   Skin s;
   s.first = first;
   s.n = (uint32_t)bind.size();
   s.n_bones = n_bones;
+  s.blend = blend;
   s.h_bind = std::move(bind);
   s.h_joints = std::move(joints);
   s.h_weights = std::move(weights);
@@ -360,7 +361,8 @@ int Scene::add_skin(const glz_skin& k, Error& err) {
   std::vector<glz_vertex> bind(k.n_vertices);
   if (!read_vertices(k.first_vertex, k.n_vertices, bind.data(), err)) return -1;
   const int id = install_skin(next_skin_, k.first_vertex, std::move(bind), std::vector<uint16_t>(k.joints, k.joints + 4 * (size_t)k.n_vertices),
-                              std::vector<float>(k.weights, k.weights + 4 * (size_t)k.n_vertices), k.n_bones, geometry_.vertices.ptr + 2 * (size_t)k.first_vertex, err);
+                              std::vector<float>(k.weights, k.weights + 4 * (size_t)k.n_vertices), k.n_bones, GLZ_SKIN_LINEAR,
+                              geometry_.vertices.ptr + 2 * (size_t)k.first_vertex, err);
   if (id >= 0) ++next_skin_;
   return id;
 }
@@ -373,11 +375,29 @@ bool Scene::remove_skin(int id, Error& err) {
   return true;
 }
 
+bool Scene::set_skin_blend(int id, int blend, Error& err) {
+  const auto it = skins_.find(id);
+  if (it == skins_.end()) return err.fail(GLZ_E_ARG, "set_skin_blend: no such skin");
+  if (blend != GLZ_SKIN_LINEAR && blend != GLZ_SKIN_DUAL_QUATERNION) return err.fail(GLZ_E_ARG, "set_skin_blend: unknown blend mode");
+  it->second.blend = blend;   // no bones are kept between calls: the next pose packs its bones for this mode
+  return true;
+}
+
+int Scene::skin_blend(int id, Error& err) const {
+  const auto it = skins_.find(id);
+  if (it == skins_.end()) {
+    err.fail(GLZ_E_ARG, "skin_blend: no such skin");
+    return -1;
+  }
+  return it->second.blend;
+}
+
 bool Scene::copy_skins(const Scene& src, Error& err) {
   if (!hip_ok(hipSetDevice(instance->device), "hipSetDevice", err)) return false;
   for (const auto& kv : src.skins_) {
     const Skin& s = kv.second;
-    if (install_skin(kv.first, s.first, std::vector<glz_vertex>(s.h_bind), std::vector<uint16_t>(s.h_joints), std::vector<float>(s.h_weights), s.n_bones, nullptr, err) < 0) return false;
+    if (install_skin(kv.first, s.first, std::vector<glz_vertex>(s.h_bind), std::vector<uint16_t>(s.h_joints), std::vector<float>(s.h_weights), s.n_bones, s.blend, nullptr, err) < 0)
+      return false;
   }
   next_skin_ = src.next_skin_;
   return true;
@@ -404,8 +424,12 @@ bool Scene::posed_span(const glz_pose* poses, uint32_t n_poses, const char* who,
 
 bool Scene::upload_bones(const glz_pose& pose, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const {
   const Skin& s = skins_.at(pose.skin);
-  packed.resize((size_t)post::kSkinBoneRows * s.n_bones);
-  for (uint32_t b = 0; b < s.n_bones; ++b) post::pack_bone(pose.bones[b], packed.data() + (size_t)post::kSkinBoneRows * b);
+  const uint32_t rows = post::bone_rows(s.blend);
+  packed.resize((size_t)rows * s.n_bones);
+  for (uint32_t b = 0; b < s.n_bones; ++b) {
+    if (s.blend == GLZ_SKIN_DUAL_QUATERNION) post::pack_bone_dq(pose.bones[b], packed.data() + (size_t)rows * b);
+    else post::pack_bone(pose.bones[b], packed.data() + (size_t)rows * b);
+  }
   if (bones.ptr == nullptr || bones.count != packed.size()) {
     if (!hip_ok(bones.alloc(packed.size()), "alloc bones", err)) return false;
   }
@@ -414,8 +438,10 @@ bool Scene::upload_bones(const glz_pose& pose, std::vector<float4>& packed, Devi
 
 bool Scene::skin_into(const glz_pose& pose, float4* span, uint32_t span_first, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const {
   const Skin& s = skins_.at(pose.skin);
+  const auto launch = s.blend == GLZ_SKIN_DUAL_QUATERNION ? launch_skin_dq : launch_skin;
   return upload_bones(pose, packed, bones, st, err) &&
-         hip_ok(launch_skin(st, s.bind.ptr, s.joints.ptr, s.weights.ptr, s.n, bones.ptr, s.n_bones, span + 2 * (size_t)(s.first - span_first)), "k_skin", err);
+         hip_ok(launch(st, s.bind.ptr, s.joints.ptr, s.weights.ptr, s.n, bones.ptr, s.n_bones, span + 2 * (size_t)(s.first - span_first)),
+                s.blend == GLZ_SKIN_DUAL_QUATERNION ? "k_skin_dq" : "k_skin", err);
 }
 
 bool Scene::time_skin(const glz_pose& pose, uint32_t reps, float* kernel_ms, Error& err) const {
@@ -581,9 +607,10 @@ bool Scene::animate_into(const glz_animation& anim, float4* span, uint32_t span_
       if (!skin_into(pose, span, span_first, up.packed[i], up.bones[i], st, err)) return false;
       continue;
     }
+    const auto launch = s.blend == GLZ_SKIN_DUAL_QUATERNION ? launch_morph_skin_dq : launch_morph_skin;
     if (!upload_bones(pose, up.packed[i], up.bones[i], st, err) ||
-        !hip_ok(launch_morph_skin(st, morph_args(morphs_.at(s.morph), up.weights[named].ptr), s.joints.ptr, s.weights.ptr, up.bones[i].ptr, s.n_bones,
-                                  span + 2 * (size_t)(s.first - span_first)), "k_morph_skin", err))
+        !hip_ok(launch(st, morph_args(morphs_.at(s.morph), up.weights[named].ptr), s.joints.ptr, s.weights.ptr, up.bones[i].ptr, s.n_bones,
+                       span + 2 * (size_t)(s.first - span_first)), s.blend == GLZ_SKIN_DUAL_QUATERNION ? "k_morph_skin_dq" : "k_morph_skin", err))
       return false;
   }
   return true;
@@ -612,8 +639,10 @@ bool Scene::time_morph(const glz_animation& one, uint32_t reps, float* kernel_ms
     if (!upload_morph_weights(w, weights, st, err)) return false;
     if (!fused) return hip_ok(launch_morph(st, morph_args(m, weights.ptr), out.ptr), "k_morph", err);
     const Skin& s = skins_.at(m.skin);
+    const auto launch = s.blend == GLZ_SKIN_DUAL_QUATERNION ? launch_morph_skin_dq : launch_morph_skin;
     return upload_bones(one.poses[0], packed, bones, st, err) &&
-           hip_ok(launch_morph_skin(st, morph_args(m, weights.ptr), s.joints.ptr, s.weights.ptr, bones.ptr, s.n_bones, out.ptr), "k_morph_skin", err);
+           hip_ok(launch(st, morph_args(m, weights.ptr), s.joints.ptr, s.weights.ptr, bones.ptr, s.n_bones, out.ptr),
+                  s.blend == GLZ_SKIN_DUAL_QUATERNION ? "k_morph_skin_dq" : "k_morph_skin", err);
   };
   if (!once()) return false;
   (void)hipEventRecord(t.ev[0], st);
@@ -625,7 +654,7 @@ bool Scene::time_morph(const glz_animation& one, uint32_t reps, float* kernel_ms
   *kernel_ms /= (float)reps;
   if (bytes) {
     *bytes = (uint64_t)m.n * (32 + 32 + 4) + (uint64_t)m.layout.slices.size() * 8 + m.n_entries * 32 + (uint64_t)m.n_targets * 4;
-    if (fused) *bytes += (uint64_t)m.n * (8 + 16) + (uint64_t)skins_.at(m.skin).n_bones * 48;
+    if (fused) *bytes += (uint64_t)m.n * (8 + 16) + (uint64_t)skins_.at(m.skin).n_bones * sizeof(float4) * post::bone_rows(skins_.at(m.skin).blend);
   }
   return true;
 }

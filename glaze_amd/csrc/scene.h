@@ -74,13 +74,18 @@ class Scene {
   // so the replicas of a scene, told the same calls in the same order, give the same ids.
   int add_skin(const glz_skin& skin, Error& err);
   bool remove_skin(int id, Error& err);   // the vertices stay as they are
+  // A skin's blend mode (GLZ_SKIN_*; a new skin is GLZ_SKIN_LINEAR).  Setting it writes no vertex: no bones are kept between calls, so the
+  // next pose, animation or previous-pose pass packs its bones for the mode and runs the mode's kernel.  GLZ_E_ARG (nothing changes): no
+  // such skin, an unknown mode; skin_blend returns -1 then.
+  bool set_skin_blend(int id, int blend, Error& err);
+  int skin_blend(int id, Error& err) const;
   // Poses skins (each named once, with the bone count it was added with) and updates the structure once: bones up, k_skin per skin from its
   // bind pose into the vertex buffer, then what update_vertices does after its upload, over the span from the lowest to the highest posed
   // vertex.  The host mirror (data.vertices) is NOT written: the span is marked stale and read back when a reader asks (host_data()).
   bool pose_skins(const glz_pose* poses, uint32_t n_poses, int mode, Error& err);
   // The checks of a set of poses (null, none, unknown id, an id twice, another bone count) and the span [first, first + count) they cover
   bool posed_span(const glz_pose* poses, uint32_t n_poses, const char* who, uint32_t& first, uint32_t& count, Error& err) const;
-  // What motion_pass fills its previous-vertex buffer with: k_skin of one (checked) pose into `span`, which holds the vertices from
+  // What motion_pass fills its previous-vertex buffer with: k_skin (k_skin_dq for a skin in that mode) of one (checked) pose into `span`, which holds the vertices from
   // span_first on; the packed bones go up through `bones`, which must live until the stream has run the kernel, as must `packed`.
   bool skin_into(const glz_pose& pose, float4* span, uint32_t span_first, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const;
   bool read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& err);   // as the device holds them
@@ -91,7 +96,7 @@ class Scene {
   // indices, materials or lights); everything that reads the CONTENTS of data.vertices goes through here, which reads the stale span back
   // (that span, no more) the first time it is asked after a pose.
   const SceneData* host_data(Error& err);
-  // everything that makes `src`'s skins, on this scene (a replica on another device): same ids, same bind poses
+  // everything that makes `src`'s skins, on this scene (a replica on another device): same ids, same bind poses, same blend modes
   bool copy_skins(const Scene& src, Error& err);
   // ---- morph targets (morph.h holds the rule and the layout, kernels_morph.hip the kernels) ----
   // A morph over [first_vertex, first_vertex + n_vertices): the targets are checked and transposed into the layout (post::pack_morph) and
@@ -163,6 +168,7 @@ class Scene {
 
   struct Skin {
     uint32_t first = 0, n = 0, n_bones = 0;
+    int blend = GLZ_SKIN_LINEAR;                 // GLZ_SKIN_*: which rule, bone table and kernel a pose of it uses
     DeviceBuffer<float4> bind, weights;          // 2 a vertex; 1 a vertex
     DeviceBuffer<uint2> joints;                  // four uint16 a vertex
     // host copies, for the replicas on other devices that are created later (DeviceGroup)
@@ -184,7 +190,7 @@ class Scene {
   };
   int install_morph(int id, uint32_t first, int skin, std::vector<glz_vertex>&& base, post::MorphLayout&& layout, const float4* device_base, Error& err);
   MorphArgs morph_args(const Morph& m, const float* weights) const;
-  // the bones of a (checked) pose, packed and on their way up through `bones` (post::kSkinBoneRows float4 a bone)
+  // the bones of a (checked) pose, packed for its skin's blend mode and on their way up through `bones` (post::bone_rows float4 a bone)
   bool upload_bones(const glz_pose& pose, std::vector<float4>& packed, DeviceBuffer<float4>& bones, hipStream_t st, Error& err) const;
   bool run_animation(const glz_animation& anim, int mode, const char* who, Error& err);   // pose_skins and animate
   AnimationUploads uploads_;   // what the scene's own animate / pose_skins calls send up
@@ -205,7 +211,7 @@ class Scene {
   std::map<int, NormalSet> normals_;
   int next_normals_ = 0;
   int install_skin(int id, uint32_t first, std::vector<glz_vertex>&& bind, std::vector<uint16_t>&& joints, std::vector<float>&& weights, uint32_t n_bones,
-                   const float4* device_bind, Error& err);
+                   int blend, const float4* device_bind, Error& err);
   std::map<int, Skin> skins_;
   int next_skin_ = 0;
   uint32_t stale_first_ = 0, stale_count_ = 0;   // the span of data.vertices that is behind the device (count 0: none)

@@ -5,7 +5,14 @@
 // The normal goes through the blended matrix's 3 x 3 as it is -- not through its inverse transpose, and it is not renormalised (shading
 // normalises the normal it interpolates).  That is EXACT ONLY FOR RIGID BONES (rotation + translation) blended with weights that sum to 1;
 // under scale, shear or other weights the normal is the blended matrix's image of the bind normal, no more.
+//
+// Dual-quaternion blending (GLZ_SKIN_DUAL_QUATERNION; "THE DUAL-QUATERNION RULE" in include/glaze_abi.h) is the second rule of this file,
+// a per-skin mode next to the linear one and held to the same discipline: one definition for host and device, float32, + - *, one sqrtf
+// and one 1.0f / x, both correctly rounded on either side (normals.h normalises the same way).  The blend of unit dual quaternions,
+// normalised, IS a rigid motion, so the normal it gives is exact wherever the bones are rigid, whatever the weights.
 #pragma once
+#include <math.h>
+
 #include "denoise.h"
 
 namespace glz {
@@ -47,7 +54,48 @@ GLZ_POST_FN void skin_vertex(Rows bones, const uint32_t j[4], float4 w, float4& 
   v1 = make_float4(n[1], n[2], v1.z, v1.w);
 }
 
+// ---- dual-quaternion blending ----
+// A bone as the kernels of this mode read it: the unit quaternion of the matrix's 3 x 3 (x, y, z, w), then the dual part (dx, dy, dz, dw)
+// that carries the translation, 32 bytes.  pack_bone_dq (skin_host.cpp, host only, once per bone per pose: it feeds the device upload and
+// the host reference alike) makes it in float64 by the rule's bone conversion and rounds to float32 at the end.
+constexpr uint32_t kSkinDqBoneRows = 2;
+void pack_bone_dq(const glz_transform& b, float4 rows[kSkinDqBoneRows]);
+// float4 a bone of the table a skin's kernels read, by its blend mode (GLZ_SKIN_*)
+inline uint32_t bone_rows(int blend) { return blend == GLZ_SKIN_DUAL_QUATERNION ? kSkinDqBoneRows : kSkinBoneRows; }
+
+// One vertex, the arguments of skin_vertex; bones: kSkinDqBoneRows float4 per bone.  The pivot of the sign step is joint 0 whatever its
+// weight; no term is skipped for a zero weight; a blend of squared length 0 is not special-cased (1 / sqrt(0) is inf, the vertex comes out
+// non-finite).
+template <class Rows>
+GLZ_POST_FN void skin_vertex_dq(Rows bones, const uint32_t j[4], float4 w, float4& v0, float4& v1) {
+  const float4 q0 = bones[kSkinDqBoneRows * j[0]], q1 = bones[kSkinDqBoneRows * j[1]], q2 = bones[kSkinDqBoneRows * j[2]], q3 = bones[kSkinDqBoneRows * j[3]];
+  const float4 d0 = bones[kSkinDqBoneRows * j[0] + 1], d1 = bones[kSkinDqBoneRows * j[1] + 1], d2 = bones[kSkinDqBoneRows * j[2] + 1],
+               d3 = bones[kSkinDqBoneRows * j[3] + 1];
+  // signs: a bone on the other hemisphere from the pivot's enters with its weight negated (dot < 0: -0, +0 and NaN keep the weight)
+  const float dot1 = ((q0.x * q1.x + q0.y * q1.y) + q0.z * q1.z) + q0.w * q1.w;
+  const float dot2 = ((q0.x * q2.x + q0.y * q2.y) + q0.z * q2.z) + q0.w * q2.w;
+  const float dot3 = ((q0.x * q3.x + q0.y * q3.y) + q0.z * q3.z) + q0.w * q3.w;
+  const float4 c = make_float4(w.x, dot1 < 0.0f ? -w.y : w.y, dot2 < 0.0f ? -w.z : w.z, dot3 < 0.0f ? -w.w : w.w);
+  const float4 R = blend_row(c, q0, q1, q2, q3), D = blend_row(c, d0, d1, d2, d3);
+  const float nn = ((R.x * R.x + R.y * R.y) + R.z * R.z) + R.w * R.w;
+  const float inv = 1.0f / sqrtf(nn);
+  const float rx = R.x * inv, ry = R.y * inv, rz = R.z * inv, rw = R.w * inv;
+  const float dx = D.x * inv, dy = D.y * inv, dz = D.z * inv, dw = D.w * inv;
+  const float tx = 2.0f * (((rw * dx - dw * rx) + ry * dz) - rz * dy);
+  const float ty = 2.0f * (((rw * dy - dw * ry) + rz * dx) - rx * dz);
+  const float tz = 2.0f * (((rw * dz - dw * rz) + rx * dy) - ry * dx);
+  const float px = v0.x, py = v0.y, pz = v0.z, nx = v0.w, ny = v1.x, nz = v1.y;
+  // rot(v) = v + 2 r_v x (r_v x v + r_w v)
+  const float pax = (ry * pz - rz * py) + rw * px, pay = (rz * px - rx * pz) + rw * py, paz = (rx * py - ry * px) + rw * pz;
+  const float pbx = ry * paz - rz * pay, pby = rz * pax - rx * paz, pbz = rx * pay - ry * pax;
+  const float nax = (ry * nz - rz * ny) + rw * nx, nay = (rz * nx - rx * nz) + rw * ny, naz = (rx * ny - ry * nx) + rw * nz;
+  const float nbx = ry * naz - rz * nay, nby = rz * nax - rx * naz, nbz = rx * nay - ry * nax;
+  v0 = make_float4((px + 2.0f * pbx) + tx, (py + 2.0f * pby) + ty, (pz + 2.0f * pbz) + tz, nx + 2.0f * nbx);
+  v1 = make_float4(ny + 2.0f * nby, nz + 2.0f * nbz, v1.z, v1.w);
+}
+
 // the reference on host arrays (skin_host.cpp): n vertices, 4 joints and 4 weights each, every joint below n_bones; out may be `bind` itself
+void host_skin_dq(const glz_vertex* bind, const uint16_t* joints, const float* weights, size_t n, const glz_transform* bones, uint32_t n_bones, glz_vertex* out);
 void host_skin(const glz_vertex* bind, const uint16_t* joints, const float* weights, size_t n, const glz_transform* bones, uint32_t n_bones, glz_vertex* out);
 
 }  // namespace post

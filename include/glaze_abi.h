@@ -365,6 +365,42 @@ int glz_renderer_geometry_update_info(glz_renderer*, glz_geometry_update_info* o
  *   act in the mesh's OBJECT space, where the vertex buffer lives; the caller supplies joint_now x inverse_bind per bone -- the library
  *   knows nothing of a skeleton hierarchy.
  *
+ *   THE DUAL-QUATERNION RULE (a skin set to GLZ_SKIN_DUAL_QUATERNION; glz_host_skin_dq, glz_host_bone_dual_quats; one definition,
+ *   glaze_amd/csrc/skin.h and skin_host.cpp, the per-vertex part compiled for host and device; the tests hold both sides to this text bit
+ *   for bit).  The caller's side does not change: a pose still carries glz_transform matrices, joint_now x inverse_bind in object space.
+ *   Linear blending of two rigid bones is not rigid (a half-turn twist at weights 1/2 : 1/2 collapses to a line); the normalised blend of
+ *   their unit dual quaternions is, so positions keep their distance to the joint and the normal is exact, for rigid bones.
+ *
+ *   BONE CONVERSION, on the host only, once per bone per pose, for the device upload and the host reference alike: float64 throughout,
+ *   the operations in exactly this order, rounded to float32 at the end.  mRC is element m[4 * C + R]; only the upper 3 x 4 is read.
+ *     tr = (m00 + m11) + m22
+ *     if tr > 0:                        s = 2 * sqrt(tr + 1);                   w = s / 4;           x = (m21 - m12) / s;  y = (m02 - m20) / s;  z = (m10 - m01) / s
+ *     else if m00 > m11 and m00 > m22:  s = 2 * sqrt(((1 + m00) - m11) - m22);  w = (m21 - m12) / s;  x = s / 4;           y = (m01 + m10) / s;  z = (m02 + m20) / s
+ *     else if m11 > m22:                s = 2 * sqrt(((1 + m11) - m00) - m22);  w = (m02 - m20) / s;  x = (m01 + m10) / s;  y = s / 4;           z = (m12 + m21) / s
+ *     else:                             s = 2 * sqrt(((1 + m22) - m00) - m11);  w = (m10 - m01) / s;  x = (m02 + m20) / s;  y = (m12 + m21) / s;  z = s / 4
+ *     len = sqrt(((x * x + y * y) + z * z) + w * w);   x = x / len;  y = y / len;  z = z / len;  w = w / len
+ *     (tx, ty, tz) = (m03, m13, m23)
+ *     dx = 0.5 * ((tx * w + ty * z) - tz * y)
+ *     dy = 0.5 * ((ty * w + tz * x) - tx * z)
+ *     dz = 0.5 * ((tz * w + tx * y) - ty * x)
+ *     dw = -(0.5 * ((tx * x + ty * y) + tz * z))
+ *   A comparison with a NaN is false (such a matrix takes the last branch).  A uniform scale drops out in the division by len; the 3 x 3
+ *   is otherwise used as given: a matrix that is no rotation gives this text's image of it and no more.  Nothing is checked.  A bone as
+ *   the kernels read it is two float4, q = (x, y, z, w) then d = (dx, dy, dz, dw): 32 bytes against the skinning rule's 48.
+ *
+ *   PER VERTEX: float32 throughout, + - x, one square root and one division (both correctly rounded), no contraction into fused
+ *   multiply-adds, the operations in exactly this order.  q_k, d_k are the two parts of bone j_k, k in 0..3.
+ *     1. signs     c0 = w0;  for k in 1..3:  dot_k = ((q0.x * qk.x + q0.y * qk.y) + q0.z * qk.z) + q0.w * qk.w;  c_k = -w_k if dot_k < 0 else w_k
+ *     2. blend     R.e = ((c0 * q0.e + c1 * q1.e) + c2 * q2.e) + c3 * q3.e   and   D.e = the same sum over d_k,   e in x, y, z, w
+ *     3. normalise nn = ((R.x * R.x + R.y * R.y) + R.z * R.z) + R.w * R.w;   inv = 1 / sqrt(nn);   r = R * inv;   d = D * inv
+ *     4. translate T.x = 2 * (((r.w * d.x - d.w * r.x) + r.y * d.z) - r.z * d.y)      (T.y, T.z: x -> y -> z -> x in every subscript but w)
+ *     5. rotate    a.x = (r.y * v.z - r.z * v.y) + r.w * v.x;   b.x = r.y * a.z - r.z * a.y;   rot(v).x = v.x + 2 * b.x     (y, z: cyclic)
+ *     6. result    p' = rot(p) + T;   n' = rot(n);   t' = t
+ *   The pivot of the sign step is j0 whatever its weight; a dot of -0, +0 or NaN keeps the weight's sign.  No term is skipped for a zero
+ *   weight.  Weights are used as given and are NOT normalised (step 3 removes their common factor).  nn == 0 is NOT special-cased: 1 /
+ *   sqrt(0) is infinite and the vertex comes out non-finite, on both sides alike.  The normal is not renormalised: r is a unit quaternion
+ *   up to rounding, so |n'| = |n| up to rounding, and a skin in this mode needs no normal set for what its bones do.
+ *
  * glz_renderer_add_skin: a skin over the vertices [first_vertex, first_vertex + n_vertices).  Its bind pose is what the scene's vertices
  * hold in that range at the moment of the call (copied on the device into a buffer the skin owns); joints (4 per vertex) and weights (4
  * per vertex) are uploaded once.  Returns the skin's id (>= 0).  Skins belong to the SCENE object, as the vertices do: every renderer
@@ -380,6 +416,16 @@ typedef struct glz_skin {
 } glz_skin;
 int glz_renderer_add_skin(glz_renderer*, const glz_skin*);
 int glz_renderer_remove_skin(glz_renderer*, int skin);
+/* A skin's blend mode: which of the two rules above poses it.  A new skin is GLZ_SKIN_LINEAR, which is exactly what a skin was before the
+ * mode existed.  Setting the mode writes no vertex and restarts nothing: the library keeps no bones between calls, so the next
+ * glz_renderer_pose_skins / glz_renderer_animate, and the previous-pose passes of read_motion_posed / reproject_posed and their _animated
+ * forms, convert their bones for the mode and run its kernel (k_skin_dq; k_morph_skin_dq where the skin's morph is named too).  Every
+ * device of set_devices follows, and a device attached later gets the mode with the skin.  glz_renderer_skin_blend returns the mode.
+ * GLZ_E_ARG (nothing changes): an unknown skin, an unknown mode. */
+#define GLZ_SKIN_LINEAR          0   /* THE SKINNING RULE (default) */
+#define GLZ_SKIN_DUAL_QUATERNION 1   /* THE DUAL-QUATERNION RULE */
+int glz_renderer_set_skin_blend(glz_renderer*, int skin, int blend);
+int glz_renderer_skin_blend(glz_renderer*, int skin);
 /* Poses one or more skins and updates the structure ONCE: the bones of every named skin go up, the rule runs per skin from its bind pose
  * into the scene's vertices, then the derivatives and the structure follow as in glz_renderer_update_vertices (`mode`: GLZ_GEOMETRY_*),
  * over the span from the lowest to the highest posed vertex.  Everything update_vertices promises holds: idle first, accumulation
@@ -414,7 +460,8 @@ int glz_renderer_read_vertices(glz_renderer*, uint32_t first_vertex, uint32_t n_
  *   No term is skipped for a zero weight (0 x inf is NaN here too, and -0 + 0 x d is +0).  Weights are used as given; the normal is not
  *   renormalised.  A vertex no target touches comes out with the bits it went in with.
  *   COMPOSITION WITH A SKIN: the morphed vertex is the BIND vertex THE SKINNING RULE then sees; the result equals
- *   glz_host_skin(glz_host_morph(bind, ...), ...) bit for bit.
+ *   glz_host_skin(glz_host_morph(bind, ...), ...) bit for bit -- glz_host_skin_dq(glz_host_morph(bind, ...), ...) for a skin in
+ *   GLZ_SKIN_DUAL_QUATERNION mode, whose fused kernel applies THE DUAL-QUATERNION RULE instead.
  *
  * glz_renderer_add_morph returns the morph's id (>= 0).  The targets are transposed once, on the host, into the layout the kernels read
  * and uploaded; the caller's arrays are not kept.  A FREE-STANDING morph (skin == -1) owns a copy of its base, made on the device from
@@ -918,7 +965,8 @@ int glz_debug_motion_timing(glz_renderer*, const glz_camera* prev_camera, const 
 /* the same for glz_renderer_read_motion_from: k_motion_deform alone when the state has vertices */
 int glz_debug_motion_timing_from(glz_renderer*, const glz_previous_state*, float* kernel_ms_out);
 /* k_skin alone on one skin of the scene, into a scratch buffer (the scene is untouched): the device-event time of `reps` launches after
- * one that is not timed, divided by reps.  The pose is checked as glz_renderer_pose_skins checks it. */
+ * one that is not timed, divided by reps.  The pose is checked as glz_renderer_pose_skins checks it.  A skin in
+ * GLZ_SKIN_DUAL_QUATERNION mode is timed with its own kernel, k_skin_dq (and k_morph_skin_dq below, at 32 bytes a bone). */
 int glz_debug_skin_timing(glz_renderer*, const glz_pose* pose, uint32_t reps, float* kernel_ms_out);
 /* The morph kernels alone, into a scratch buffer (the scene is untouched), timed as glz_debug_skin_timing times k_skin.  `one` names one
  * morph and no pose -- k_morph on it, from the skin's bind pose if it is attached -- or one attached morph and its skin's pose --
@@ -1055,6 +1103,12 @@ int64_t glz_host_instance_boxes(const glz_scene_desc* desc, uint64_t budget, flo
  * n_bones == 0, a joint >= n_bones. */
 int glz_host_skin(const glz_vertex* bind, const uint16_t* joints, const float* weights, uint64_t n, const glz_transform* bones, uint32_t n_bones,
                   glz_vertex* out);
+/* THE DUAL-QUATERNION RULE on host arrays, no device: the reference k_skin_dq is compared with bit for bit.  glz_host_skin_dq: the
+ * arguments and the refusals of glz_host_skin.  glz_host_bone_dual_quats: the rule's bone conversion alone, n matrices -> 8 floats a
+ * bone, (x, y, z, w) then (dx, dy, dz, dw); GLZ_E_ARG: a null pointer with n > 0. */
+int glz_host_skin_dq(const glz_vertex* bind, const uint16_t* joints, const float* weights, uint64_t n, const glz_transform* bones, uint32_t n_bones,
+                     glz_vertex* out);
+int glz_host_bone_dual_quats(const glz_transform* bones, uint32_t n, float* out8);
 /* THE MORPH RULE (glz_renderer_add_morph) on host arrays, no device: the reference k_morph is compared with bit for bit; it runs through
  * the same layout packer as glz_renderer_add_morph.  base / out: n vertices (out may be base itself); targets, n_targets: as glz_morph
  * has them, over n vertices; weights: n_targets.  GLZ_E_ARG: a null pointer with n > 0, and what glz_renderer_add_morph refuses of a

@@ -15,7 +15,7 @@ touch a random tenth of the vertices, so a row holds five entries on average and
                   vertices, timed the same way in the same run (glz_debug_skin_timing), 88 bytes a vertex; its spread between repeats is
                   what a difference has to exceed to mean anything.
   k_morph_skin    the fused kernel on the 8 dense targets attached to that skin, against k_morph (from the skin's bind pose) plus k_skin
-                  timed separately.
+                  timed separately; and k_morph_skin_dq, the same with the skin set to dual-quaternion mode, turn by turn with it.
   animate         median wall time around animate() of the free-standing morph, against update_vertices() fed the vertices glz_host_morph
                   made of the same weights BEFORE the clock starts, alternating call by call; and the update_ms of both.
 
@@ -107,13 +107,22 @@ def measure(emit, inst, name, desc, kinds, args):
     targets = kept["8 dense"]
     w = rng.normal(size=len(targets)).astype(np.float32)
     morph = r.add_morph(0, targets, skin=skin)
-    skin_ms, morph_ms, fused_ms = [], [], []
-    fused_bytes = 0
-    for _ in range(args.repeats):                                                                 # the three take turns
+    skin_ms, morph_ms, fused_ms, fused_dq_ms = [], [], [], []
+    fused_bytes = fused_dq_bytes = 0
+    for _ in range(args.repeats):                                                                 # the four take turns
         skin_ms.append(r.debug_skin_timing(skin, bones, reps=20))
         morph_ms.append(r.debug_morph_timing({morph: w}, reps=20)[0])
         t, fused_bytes = r.debug_morph_timing({morph: w}, {skin: bones}, reps=20)
         fused_ms.append(t)
+        r.set_skin_blend(skin, "dual_quaternion")                                                 # the same skin in the other mode: k_morph_skin_dq
+        t, fused_dq_bytes = r.debug_morph_timing({morph: w}, {skin: bones}, reps=20)
+        fused_dq_ms.append(t)
+        r.set_skin_blend(skin, "linear")
+    r.set_skin_blend(skin, "dual_quaternion")
+    r.animate(morphs={morph: w}, poses={skin: bones})
+    want = glaze_amd.host_skin(glaze_amd.host_morph(base, targets, w), joints, sw, bones, blend="dual_quaternion")
+    same_dq = bool(np.array_equal(r.read_vertices(0, n).view(np.uint32), want.view(np.uint32)))
+    r.set_skin_blend(skin, "linear")
     r.animate(morphs={morph: w}, poses={skin: bones})
     want = glaze_amd.host_skin(glaze_amd.host_morph(base, targets, w), joints, sw, bones)
     same = bool(np.array_equal(r.read_vertices(0, n).view(np.uint32), want.view(np.uint32)))
@@ -124,8 +133,13 @@ def measure(emit, inst, name, desc, kinds, args):
     fused = {"scene": name, "what": "k_morph_skin, 8 dense", "k_morph_skin_ms": kf, "k_morph_ms": km, "k_skin_ms": ks, "k_morph_skin_bytes": fused_bytes,
              "k_morph_skin_TB_per_s": fused_bytes / (kf["median"] * 1e-3) / 1e12, "fused_over_separate": kf["median"] / (km["median"] + ks["median"]),
              "animated_equals_host_skin_of_host_morph": same}
+    kd = spread(fused_dq_ms)
+    fused_dq = {"scene": name, "what": "k_morph_skin_dq, 8 dense", "k_morph_skin_dq_ms": kd, "k_morph_skin_dq_bytes": fused_dq_bytes,
+                "k_morph_skin_dq_TB_per_s": fused_dq_bytes / (kd["median"] * 1e-3) / 1e12, "dq_over_linear": kd["median"] / kf["median"],
+                "animated_equals_host_skin_dq_of_host_morph": same_dq}
     emit(json.dumps(yard))
     emit(json.dumps(fused))
+    emit(json.dumps(fused_dq))
     emit("")
     emit("%s, %d vertices" % (name, n))
     emit("")
@@ -137,6 +151,8 @@ def measure(emit, inst, name, desc, kinds, args):
     emit("| k_skin (yardstick) | %.4f / %.4f / %.4f | %d | %.2f (%.2f .. %.2f) |" % (ks["min"], ks["median"], ks["max"], yard["k_skin_bytes"], yard["k_skin_TB_per_s"],
                                                                                      *yard["k_skin_TB_per_s_spread"]))
     emit("| k_morph_skin, 8 dense | %.4f / %.4f / %.4f | %d | %.2f |" % (kf["min"], kf["median"], kf["max"], fused_bytes, fused["k_morph_skin_TB_per_s"]))
+    emit("| k_morph_skin_dq, 8 dense (against k_morph_skin %.2f) | %.4f / %.4f / %.4f | %d | %.2f |" % (fused_dq["dq_over_linear"], kd["min"], kd["median"], kd["max"],
+                                                                                                     fused_dq_bytes, fused_dq["k_morph_skin_dq_TB_per_s"]))
     emit("| k_morph from the bind pose + k_skin, separately | %.4f + %.4f = %.4f (fused / separate %.2f) | | |" % (km["median"], ks["median"], km["median"] + ks["median"],
                                                                                                                 fused["fused_over_separate"]))
     emit("")

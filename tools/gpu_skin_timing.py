@@ -1,18 +1,20 @@
 """What posing a skinned mesh on the device costs (RayTraceRenderer.pose) against what there was before: skinning on the host and
 update_vertices with the posed vertices -- the same scene, the same vertices, the same process.
 
-    python tools/gpu_skin_timing.py [--scenes small large forest] [--forest-n 1000] [--reps 7] [--bones 64]
+    python tools/gpu_skin_timing.py [--scenes small large forest] [--forest-n 1000] [--reps 7] [--bones 64] [--kernel-repeats 5]
 
 Scenes: the atrium at its small detail (262 k triangles) and at 7.2 M triangles, every vertex skinned (flattened); forest_scene(n) in two
 levels with the column mesh skinned (its vertex range alone).  The skeleton is a chain of `--bones` bones along the scene's longest axis,
 each vertex under the two bones nearest to it (convex weights, the other two influences zero); two poses alternate, small rotations
-about the chain's axis.  Per scene, in mode refit:
+about the chain's axis.  Per scene, in mode refit, once with the skin in linear mode and once in dual-quaternion mode (set_skin_blend; the
+update_vertices side is then fed what glz_host_skin_dq makes), both in the same process:
 
   pose            median wall time around pose() (bones over the bus, k_skin, derivatives, refit), and the median update_ms of it;
   update_vertices median wall time around update_vertices() fed the vertices glz_host_skin made of the same bones BEFORE the clock starts
                   (the host's skinning time is given on its own and is in neither figure), and the median update_ms of it;
   k_skin          the kernel alone (glz_debug_skin_timing: device events around 20 launches), and its algorithmic bytes -- 88 a vertex:
-                  32 bind + 8 joints + 16 weights in, 32 out -- over that time.
+                  32 bind + 8 joints + 16 weights in, 32 out -- over that time; k_skin_dq, which moves the same bytes, turn by turn with
+                  it: --kernel-repeats measurements each, the median and the lowest and highest.
 
 Both paths end in a wait for the stream, so the wall times are whole calls.  The two alternate call by call, so that what else the host
 does falls on both.  After the timed calls the posed vertices are read back and compared with the host's, bit for bit.  One JSON line per
@@ -69,6 +71,7 @@ def main():
     ap.add_argument("--forest-n", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--bones", type=int, default=64)
+    ap.add_argument("--kernel-repeats", type=int, default=5)
     args = ap.parse_args()
     inst = glaze_amd.RayTraceInstance.new()
     cases = []
@@ -94,45 +97,57 @@ def main():
         bind = desc.vertices[first:first + count]
         joints, weights, axis, centre = chain(bind, args.bones)
         poses = [twist(args.bones, axis, centre, a) for a in (0.05, -0.05)]
-        t0 = time.perf_counter()
-        posed = [glaze_amd.host_skin(bind, joints, weights, b) for b in poses]
-        host_ms = (time.perf_counter() - t0) * 1e3 / len(poses)
         skin = r.add_skin(first, joints, weights, args.bones)
-        r.update_vertices(posed[1], first=first)                                                  # the first refit makes the plan: not timed
-        r.pose({skin: poses[0]})
-        wall = {"pose": [], "update": []}
-        stream = {"pose": [], "update": []}
-        for i in range(2 * args.reps):
-            k = (i // 2) % 2
+        row = {"scene": name, "levels": levels, "vertices_skinned": count, "bones": args.bones, "k_skin_bytes": BYTES_PER_VERTEX * count}
+        for blend, tag in (("linear", ""), ("dual_quaternion", "dq_")):
+            r.set_skin_blend(skin, blend)
             t0 = time.perf_counter()
-            if i % 2 == 0:
-                r.pose({skin: poses[k]})
-            else:
-                r.update_vertices(posed[1 - k], first=first)
-            which = "pose" if i % 2 == 0 else "update"
-            wall[which].append((time.perf_counter() - t0) * 1e3)
-            stream[which].append(float(scene.info().build_ms))                                    # = glz_geometry_update_info::update_ms
-        r.pose({skin: poses[0]})
-        same = bool(np.array_equal(r.read_vertices(first, count).view(np.uint32), posed[0].view(np.uint32)))
-        kernel_ms = r.debug_skin_timing(skin, poses[1], reps=20)
-        row = {"scene": name, "levels": levels, "vertices_skinned": count, "bones": args.bones,
-               "pose_wall_ms": statistics.median(wall["pose"]), "pose_wall_min_max_ms": [min(wall["pose"]), max(wall["pose"])],
-               "pose_update_ms": statistics.median(stream["pose"]),
-               "update_vertices_wall_ms": statistics.median(wall["update"]), "update_vertices_wall_min_max_ms": [min(wall["update"]), max(wall["update"])],
-               "update_vertices_update_ms": statistics.median(stream["update"]),
-               "host_skin_ms": host_ms, "k_skin_ms": kernel_ms, "k_skin_bytes": BYTES_PER_VERTEX * count,
-               "k_skin_TB_per_s": BYTES_PER_VERTEX * count / (kernel_ms * 1e-3) / 1e12 if kernel_ms > 0 else float("nan"),
-               "posed_equals_host_skin": same}
-        row["wall_ratio"] = row["pose_wall_ms"] / row["update_vertices_wall_ms"]
+            posed = [glaze_amd.host_skin(bind, joints, weights, b, blend=blend) for b in poses]
+            row[tag + "host_skin_ms"] = (time.perf_counter() - t0) * 1e3 / len(poses)
+            r.update_vertices(posed[1], first=first)                                              # the first refit makes the plan: not timed
+            r.pose({skin: poses[0]})
+            wall = {"pose": [], "update": []}
+            stream = {"pose": [], "update": []}
+            for i in range(2 * args.reps):
+                k = (i // 2) % 2
+                t0 = time.perf_counter()
+                if i % 2 == 0:
+                    r.pose({skin: poses[k]})
+                else:
+                    r.update_vertices(posed[1 - k], first=first)
+                which = "pose" if i % 2 == 0 else "update"
+                wall[which].append((time.perf_counter() - t0) * 1e3)
+                stream[which].append(float(scene.info().build_ms))                                # = glz_geometry_update_info::update_ms
+            r.pose({skin: poses[0]})
+            row[tag + "posed_equals_host_skin"] = bool(np.array_equal(r.read_vertices(first, count).view(np.uint32), posed[0].view(np.uint32)))
+            row.update({tag + "pose_wall_ms": statistics.median(wall["pose"]), tag + "pose_wall_min_max_ms": [min(wall["pose"]), max(wall["pose"])],
+                        tag + "pose_update_ms": statistics.median(stream["pose"]),
+                        tag + "update_vertices_wall_ms": statistics.median(wall["update"]),
+                        tag + "update_vertices_wall_min_max_ms": [min(wall["update"]), max(wall["update"])],
+                        tag + "update_vertices_update_ms": statistics.median(stream["update"])})
+            row[tag + "wall_ratio"] = row[tag + "pose_wall_ms"] / row[tag + "update_vertices_wall_ms"]
+        # the two kernels alone, turn by turn in one process: 20 launches between device events, --kernel-repeats times each, medians
+        kernel = {"linear": [], "dual_quaternion": []}
+        for _ in range(args.kernel_repeats):
+            for blend in kernel:
+                r.set_skin_blend(skin, blend)
+                kernel[blend].append(r.debug_skin_timing(skin, poses[1], reps=20))
+        for blend, tag in (("linear", "k_skin"), ("dual_quaternion", "k_skin_dq")):
+            ms = statistics.median(kernel[blend])
+            row.update({tag + "_ms": ms, tag + "_min_max_ms": [min(kernel[blend]), max(kernel[blend])],
+                        tag + "_TB_per_s": BYTES_PER_VERTEX * count / (ms * 1e-3) / 1e12 if ms > 0 else float("nan")})
+        row["k_skin_dq_over_k_skin"] = row["k_skin_dq_ms"] / row["k_skin_ms"]
         print(json.dumps(row), flush=True)
         rows.append(row)
         del r, scene
-    print("| scene | shape | vertices skinned | pose: wall (ms) | update_ms | update_vertices: wall (ms) | update_ms | pose / update_vertices (wall) | host skinning, not in either (ms) | k_skin (ms) | 88 B a vertex over it (TB/s) | bits equal |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
+    print("| scene | shape | vertices skinned | blend | pose: wall (ms) | update_ms | update_vertices: wall (ms) | update_ms | pose / update_vertices (wall) | host skinning, not in either (ms) | kernel (ms, median) | min - max | 88 B a vertex over it (TB/s) | against k_skin | bits equal |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
     for w in rows:
-        print("| %s | %s | %d | %.3f | %.3f | %.3f | %.3f | %.2f | %.1f | %.4f | %.2f | %s |" % (
-            w["scene"], w["levels"], w["vertices_skinned"], w["pose_wall_ms"], w["pose_update_ms"], w["update_vertices_wall_ms"], w["update_vertices_update_ms"],
-            w["wall_ratio"], w["host_skin_ms"], w["k_skin_ms"], w["k_skin_TB_per_s"], "yes" if w["posed_equals_host_skin"] else "NO"))
+        for blend, tag, k in (("linear", "", "k_skin"), ("dual quaternion", "dq_", "k_skin_dq")):
+            print("| %s | %s | %d | %s | %.3f | %.3f | %.3f | %.3f | %.2f | %.1f | %.4f | %.4f - %.4f | %.2f | %.2f | %s |" % (
+                w["scene"], w["levels"], w["vertices_skinned"], blend, w[tag + "pose_wall_ms"], w[tag + "pose_update_ms"], w[tag + "update_vertices_wall_ms"],
+                w[tag + "update_vertices_update_ms"], w[tag + "wall_ratio"], w[tag + "host_skin_ms"], w[k + "_ms"], w[k + "_min_max_ms"][0], w[k + "_min_max_ms"][1],
+                w[k + "_TB_per_s"], w[k + "_ms"] / w["k_skin_ms"], "yes" if w[tag + "posed_equals_host_skin"] else "NO"))
 
 
 if __name__ == "__main__":
