@@ -267,9 +267,9 @@ def _skin_blend(blend):
 
 
 def host_skin(bind, joints, weights, bones, blend="linear"):
-    """glz_host_skin: the skinning rule (include/glaze_abi.h holds the specification) on the host, no device, the reference of k_skin.
+    """glz_host_skin: the skinning rule (include/glaze_abi.h holds the specification) on the host, no device, the reference of k_skin (the skin step of k_deform under the linear rule).
     bind: n vertices in any form update_vertices takes; joints: (n, 4) integers; weights: (n, 4) float32; bones: (n_bones, 16) float32,
-    column-major.  blend="dual_quaternion": glz_host_skin_dq, the dual-quaternion rule, the reference of k_skin_dq.  Returns the posed
+    column-major.  blend="dual_quaternion": glz_host_skin_dq, the dual-quaternion rule, the reference of k_skin_dq (the same step under that rule).  Returns the posed
     vertices, (n, 8) float32."""
     fn = abi.lib().glz_host_skin_dq if _skin_blend(blend) == abi.SKIN_DUAL_QUATERNION else abi.lib().glz_host_skin
     v = _vertex_array(bind)
@@ -314,7 +314,7 @@ def _morph_targets(targets, n_vertices):
 
 
 def host_morph(base, targets, weights):
-    """glz_host_morph: the morph rule (include/glaze_abi.h holds the specification) on the host, no device, the reference of k_morph.
+    """glz_host_morph: the morph rule (include/glaze_abi.h holds the specification) on the host, no device, the reference of k_morph (the morph step of k_deform).
     base: n vertices in any form update_vertices takes; targets: a list of (indices | None, d_position, d_normal), indices relative to
     base, strictly ascending, None = dense; weights: one float32 a target.  Returns the morphed vertices, (n, 8) float32."""
     v = _vertex_array(base)
@@ -862,7 +862,7 @@ class RayTraceRenderer:
         abi.check(abi.lib().glz_renderer_pose_skins(self._h, C.cast(arr, C.c_void_p), len(poses), self._GEOMETRY_MODES.get(mode, mode)))
 
     def debug_skin_timing(self, skin, bones, reps=20):
-        """k_skin alone on one skin, into a scratch buffer (the scene is untouched): milliseconds per launch, device events around reps launches"""
+        """k_skin (k_deform with the skin step alone; k_skin_dq for a skin in that mode) alone on one skin, into a scratch buffer (the scene is untouched): milliseconds per launch, device events around reps launches"""
         arr, keep = self._pose_array({skin: bones})
         ms = C.c_float(0.0)
         abi.check(abi.lib().glz_debug_skin_timing(self._h, C.cast(arr, C.c_void_p), int(reps), C.cast(C.byref(ms), C.c_void_p)))
@@ -906,8 +906,9 @@ class RayTraceRenderer:
         abi.check(abi.lib().glz_renderer_animate(self._h, C.cast(C.byref(a), C.c_void_p), self._GEOMETRY_MODES.get(mode, mode)))
 
     def debug_morph_timing(self, morphs, poses=None, reps=20):
-        """k_morph on one morph (morphs={id: weights}), or k_morph_skin on an attached morph with its skin's pose, alone into a scratch
-        buffer (the scene is untouched): (milliseconds per launch, the bytes one launch moves)"""
+        """k_morph (k_deform with the morph step alone) on one morph (morphs={id: weights}), or k_morph_skin (both steps) on an attached
+        morph with its skin's pose, alone into a scratch buffer (the scene is untouched): (milliseconds per launch, the bytes one
+        launch moves)"""
         a, keep = self._animation(morphs, poses)
         ms, nbytes = C.c_float(0.0), C.c_uint64(0)
         abi.check(abi.lib().glz_debug_morph_timing(self._h, C.cast(C.byref(a), C.c_void_p), int(reps), C.cast(C.byref(ms), C.c_void_p), C.cast(C.byref(nbytes), C.c_void_p)))

@@ -388,7 +388,8 @@ int glz_renderer_pose_skins(glz_renderer* h, const glz_pose* poses, uint32_t n, 
   if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
   // (checked here as well as in the scene: a refused call must not make the renderer drain and restart)
   uint32_t first = 0, count = 0;
-  if (!h->r->scene()->posed_span(poses, n, "pose_skins", first, count, e)) return fail(e);
+  const glz_animation posed{nullptr, 0, poses, n};
+  if (!h->r->scene()->animated_span(&posed, "pose_skins", first, count, e)) return fail(e);
   if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return fail(GLZ_E_ARG, "pose_skins: unknown mode");
   GLZ_RET(h->r->pose_skins(poses, n, mode, e));
   GLZ_GUARD_END(GLZ_E_IO)
@@ -560,7 +561,6 @@ static PrevPoses previous_animation(const glz_animation& a) {
   PrevPoses p{a.poses, a.n_poses, true};
   p.morphs = a.morphs;
   p.n_morphs = a.n_morphs;
-  p.animated = true;
   return p;
 }
 int glz_renderer_read_motion_animated(glz_renderer* h, const glz_previous_state* prev, const glz_animation* anim, float* out) {

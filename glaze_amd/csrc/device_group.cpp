@@ -99,7 +99,7 @@ struct DeviceGroup::Peer {
     if (src.info.as_levels) inst->as_levels = (int)src.info.as_levels;
     SceneData copy = src.data;   // (current: change_scene / build have asked src.host_data() on the root's thread)
     std::shared_ptr<Scene> replica(Scene::create(inst.get(), std::move(copy), e));
-    if (replica && (!replica->copy_skins(src, e) || !replica->copy_morphs(src, e) || !replica->copy_normals(src, e))) replica.reset();
+    if (replica && !replica->copy_deformers(src, e)) replica.reset();
     return replica;
   }
   ~Peer() {

@@ -248,19 +248,22 @@ hipError_t launch_reproject(hipStream_t st, uint32_t w, uint32_t h, const glz_re
                             const float4* prev_aov0, const float4* prev_aov1, float4* out, hipEvent_t* marks = nullptr);
 hipError_t launch_project_points(hipStream_t st, const post::ProjectConstants& C, uint32_t w, uint32_t h, const float* points3, uint32_t n, float* out3);
 
-// ---- skinning (kernels_skin.hip; skin.h holds the rule) ----
-// out[2 * i], out[2 * i + 1] = vertex i of `bind` under its four joints and weights, i < n.  bind: two float4 a vertex; joints: four uint16
-// a vertex as one uint2; weights: one float4 a vertex; bones: three float4 rows a bone (post::pack_bone), every joint below n_bones (the
-// caller has checked: the kernel indexes by them); out: n vertices of device memory that overlap no input.  The bone table is staged in LDS
-// when n_bones <= kSkinLdsBones, else read from memory.
-constexpr uint32_t kSkinLdsBones = 256;   // 12 KB of a block's LDS
-hipError_t launch_skin(hipStream_t st, const float4* bind, const uint2* joints, const float4* weights, uint32_t n, const float4* bones, uint32_t n_bones, float4* out);
-// the same under the dual-quaternion rule (k_skin_dq); bones: two float4 a bone (post::pack_bone_dq), 8 KB of LDS at kSkinLdsBones
-hipError_t launch_skin_dq(hipStream_t st, const float4* bind, const uint2* joints, const float4* weights, uint32_t n, const float4* bones, uint32_t n_bones, float4* out);
-
-// ---- morph targets (kernels_morph.hip; morph.h holds the rule and the layout) ----
-// What a morph's kernels read: post::MorphLayout on the device, and the base of its n vertices (two float4 a vertex).  Every row's count is
-// at most its slice's width and every entry's target below n_targets (pack_morph made them so: the kernels index by them).
+// ---- vertex deformers: morph targets, then skinning (kernels_deform.hip; morph.h and skin.h hold the rules and the layouts) ----
+// What the skin step reads.  bind: two float4 a vertex; joints: four uint16 a vertex as one uint2; weights: one float4 a vertex; bones:
+// post::bone_rows(blend) float4 a bone (post::pack_bone: three rows; post::pack_bone_dq: two), every joint below n_bones (the caller has
+// checked: the kernel indexes by them).  The bone table is staged in LDS when n_bones <= kSkinLdsBones, else read from memory.
+struct SkinArgs {
+  const float4* bind;
+  const uint2* joints;
+  const float4* weights;
+  uint32_t n;
+  const float4* bones;
+  uint32_t n_bones;
+  int blend;   // GLZ_SKIN_*: the linear rule (k_skin) or the dual-quaternion rule (k_skin_dq)
+};
+constexpr uint32_t kSkinLdsBones = 256;   // 12 KB of a block's LDS under the linear rule, 8 KB under the dual-quaternion rule
+// What the morph step reads: post::MorphLayout on the device, and the base of its n vertices (two float4 a vertex).  Every row's count is
+// at most its slice's width and every entry's target below n_targets (pack_morph made them so: the kernel indexes by them).
 struct MorphArgs {
   const float4* base;
   const uint32_t* counts;
@@ -271,12 +274,11 @@ struct MorphArgs {
   uint32_t n_targets;
 };
 constexpr uint32_t kMorphLdsTargets = 1024;   // 4 KB of a block's LDS
-// out[2 * i], out[2 * i + 1] = vertex i of the base under the morph rule, i < n; out: n vertices of device memory that overlap no input
-hipError_t launch_morph(hipStream_t st, const MorphArgs& m, float4* out);
-// the same, then the skinning rule on the morphed vertex (launch_skin's arguments), one store: the base is the skin's bind pose
-hipError_t launch_morph_skin(hipStream_t st, const MorphArgs& m, const uint2* joints, const float4* skin_weights, const float4* bones, uint32_t n_bones, float4* out);
-// the same with the dual-quaternion rule on the morphed vertex (launch_skin_dq's arguments; k_morph_skin_dq)
-hipError_t launch_morph_skin_dq(hipStream_t st, const MorphArgs& m, const uint2* joints, const float4* skin_weights, const float4* bones, uint32_t n_bones, float4* out);
+// out[2 * i], out[2 * i + 1] = vertex i, i < n, of the morph's base under the morph rule (skin null: k_morph), of the skin's bind pose under
+// its skinning rule (morph null: k_skin, k_skin_dq), or of the base -- the skin's bind pose -- under the morph rule and then the skinning
+// rule, one store (k_morph_skin, k_morph_skin_dq; n is the morph's).  out: n vertices of device memory that overlap no input.  Nothing is
+// launched for no vertices; both null is hipErrorInvalidValue.
+hipError_t launch_deform(hipStream_t st, const MorphArgs* morph, const SkinArgs* skin, float4* out);
 
 // ---- vertex normals from deformed positions (kernels_normals.hip; normals.h holds the rule and the layout) ----
 // What a normal set's kernels read: post::NormalLayout on the device.  Every face's three indices are below the scene's vertex count,

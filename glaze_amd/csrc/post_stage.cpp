@@ -186,9 +186,7 @@ bool PostStage::motion_pass(const glz_previous_state& prev, PrevBuffers& uploade
   if (posed.given) {
     if (prev.vertices) return bad_argument(err, "motion: a posed previous state brings no vertices of its own (vertices must be null)");
     const glz_animation previous = posed.animation();
-    if (posed.animated ? !r_.scene()->animated_span(&previous, "motion", posed_first, posed_count, err)
-                       : !r_.scene()->posed_span(posed.poses, posed.n, "motion", posed_first, posed_count, err))
-      return false;
+    if (!r_.scene()->animated_span(&previous, "motion", posed_first, posed_count, err)) return false;
   }
   if (!hip_ok(hipSetDevice(r_.instance()->device), "hipSetDevice", err)) return false;
   MotionStep step;

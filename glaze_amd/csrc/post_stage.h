@@ -21,7 +21,6 @@ struct PrevPoses {
   // *_animated: the previous morph weights as well, and the whole checked and run as glz_renderer_animate does (Scene::animate_into)
   const glz_morph_weights* morphs = nullptr;
   uint32_t n_morphs = 0;
-  bool animated = false;
   glz_animation animation() const { return glz_animation{morphs, n_morphs, poses, n}; }
 };
 
@@ -78,7 +77,7 @@ class PostStage {
   void post_args(LaunchArgs& a) const;
   // what a motion pass uploads of the caller's previous state: owned by the call and released with it
   struct PrevBuffers {
-    Scene::AnimationUploads animation;           // the bone and weight tables of the previous poses and morphs (its host arrays first, so released last)
+    Deformers::AnimationUploads animation;           // the bone and weight tables of the previous poses and morphs (its host arrays first, so released last)
     DeviceBuffer<float4> o2w, vertices;
   };
   bool motion_pass(const glz_previous_state& prev, PrevBuffers& uploaded, DeviceBuffer<float4>& motion, Error& err, hipEvent_t* marks = nullptr,

@@ -197,7 +197,7 @@ def test_fused_kernel_equals_skin_of_morph(instance, n_targets, n_bones):
 
 @pytest.mark.parametrize("attached", [False, True])
 def test_slices_without_padding_equal_the_host_reference(instance, attached):
-    """only dense targets: every row is as long as its slice is wide, which the kernels run without a lane mask (kernels_morph.hip);
+    """only dense targets: every row is as long as its slice is wide, which the kernels run without a lane mask (kernels_deform.hip);
     at 65 and 257 vertices the last slice holds one lane, at 63 none is full"""
     desc = sheet_scene()
     v0 = as_rows(desc.vertices)

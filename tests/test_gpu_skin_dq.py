@@ -11,6 +11,7 @@ import glaze_amd
 from glaze_amd import abi
 from glaze_amd.scene_desc import make_camera
 
+import test_gpu_morph as gm
 from test_gpu_morph import LDS_TARGETS, same_bits
 from test_gpu_motion import FOVX, moved_camera
 from test_gpu_skin import (FIRST_A, FIRST_B, LDS_BONES, N_A, N_B, N_SHEET, as_rows, as_vertices, bend, hinge, loopback, random_bones, renderer,  # noqa: F401
@@ -265,3 +266,34 @@ def test_non_finite_bones_reach_the_vertices_the_host_says(instance):
     assert (~np.isfinite(got[rest])).any()
     whole = r.read_vertices(0, len(v0))
     assert same_bits(whole[:first], v0[:first]) and same_bits(whole[first + n:], v0[first + n:])
+
+
+# ---- 8: two rules in one call -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("blend_b,blend_c", [(DQ, "linear"), ("linear", DQ)])
+def test_one_call_runs_each_skin_by_its_own_rule(instance, blend_b, blend_c):
+    """a free-standing morph, a morphed skin (B) and a plain skin (C) named in one animate (three_parts of test_gpu_morph.py), the two skins
+    in different modes: every part is the host morph followed by the host skin of its own skin's mode, and the gaps keep their bits"""
+    desc = sheet_scene()
+    v0 = as_rows(desc.vertices)
+    _, r = renderer(instance, desc)
+    (ma, ta), (sb, jb, swb, mb, tb), (sc, jc, swc) = gm.three_parts(r, desc.vertices)
+    r.set_skin_blend(sb, blend_b)
+    r.set_skin_blend(sc, blend_c)
+    wa, wb = np.array([1.0, -0.5], np.float32), np.array([0.5, 1.5, 3.0], np.float32)
+    bones_b, bones_c = np.stack([hinge(0.3, lift=0.05), hinge(0.8)]), bend(-0.6)
+    r.animate(morphs={mb: wb, ma: wa}, poses={sc: bones_c, sb: bones_b})
+
+    def host(rule_b, rule_c):
+        v = gm.host_morphed(desc.vertices, gm.FIRST_A, gm.N_A, ta, wa)
+        v = host_posed(gm.host_morphed(v, gm.FIRST_B, gm.N_B, tb, wb), gm.FIRST_B, jb, swb, bones_b, blend=rule_b)
+        return as_rows(host_posed(v, gm.FIRST_C, jc, swc, bones_c, blend=rule_c))
+
+    want, swapped = host(blend_b, blend_c), host(blend_c, blend_b)
+    part_b, part_c = slice(gm.FIRST_B, gm.FIRST_B + gm.N_B), slice(gm.FIRST_C, gm.FIRST_C + gm.N_C)
+    assert not np.array_equal(want[part_b], swapped[part_b]) and not np.array_equal(want[part_c], swapped[part_c])   # (either rule swapped would show)
+    got = r.read_vertices(0, len(v0))
+    same_finite_bits(got, want)
+    for gap in (slice(0, gm.FIRST_A), slice(gm.FIRST_A + gm.N_A, gm.FIRST_B), slice(gm.FIRST_B + gm.N_B, gm.FIRST_C)):
+        assert same_bits(got[gap], v0[gap])
+    for part in (slice(gm.FIRST_A, gm.FIRST_A + gm.N_A), part_b, part_c):
+        assert not np.array_equal(got[part, :6], v0[part, :6])

@@ -20,6 +20,10 @@ touch a random tenth of the vertices, so a row holds five entries on average and
                   made of the same weights BEFORE the clock starts, alternating call by call; and the update_ms of both.
 
 After the timed calls the vertices are read back and compared with the host's, bit for bit.  One JSON line per measurement, then a table.
+
+The kernel names in the text, the table rows and the JSON keys -- k_skin, k_skin_dq, k_morph, k_morph_skin, k_morph_skin_dq -- name the RULE
+a launch runs: each is a set of instantiations of one template, k_deform (kernels_deform.hip), and was a kernel of its own in earlier
+result files, which therefore compare key for key.
 """
 import argparse
 import json

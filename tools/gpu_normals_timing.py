@@ -19,6 +19,10 @@ like it, sits at the launch floor) and at 7.2 M triangles, which is where a rate
                   update_vertices with the result: what a caller with positions alone pays today.
 
 After the timed calls the vertices are read back and compared with the host's, bit for bit.  One JSON line per measurement, then a table.
+
+The kernel names in the text, the table rows and the JSON keys -- k_skin, k_skin_dq, k_morph, k_morph_skin, k_morph_skin_dq -- name the RULE
+a launch runs: each is a set of instantiations of one template, k_deform (kernels_deform.hip), and was a kernel of its own in earlier
+result files, which therefore compare key for key.
 """
 import argparse
 import json

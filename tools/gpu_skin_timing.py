@@ -19,6 +19,10 @@ update_vertices side is then fed what glz_host_skin_dq makes), both in the same 
 Both paths end in a wait for the stream, so the wall times are whole calls.  The two alternate call by call, so that what else the host
 does falls on both.  After the timed calls the posed vertices are read back and compared with the host's, bit for bit.  One JSON line per
 scene, then a markdown table.
+
+The kernel names in the text, the table rows and the JSON keys -- k_skin, k_skin_dq, k_morph, k_morph_skin, k_morph_skin_dq -- name the RULE
+a launch runs: each is a set of instantiations of one template, k_deform (kernels_deform.hip), and was a kernel of its own in earlier
+result files, which therefore compare key for key.
 """
 import argparse
 import json

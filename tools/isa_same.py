@@ -9,6 +9,11 @@ bytes, LDS bytes.  What does not count as a difference is what moves with the po
 encoding comments, the literals of the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64 (the pc-relative distance to a function that is
 called, not inlined), and the padding behind a symbol's last s_endpgm.  Exit status 1 when a symbol differs or is missing.  A symbol
 that only NEW has is listed as `new` with its figures and does not count.
+With --pair 'OLD NAME=NEW NAME' (demangled kernel names without their arguments, any number of times) nothing else is compared: each
+OLD kernel is held against the NEW kernel of another name that replaces it -- `same` (the same instructions in the same order),
+`operands` (the same mnemonics in the same order; some operand differs, as a kernel argument's offset does when the argument list
+changed), `reordered` (the same number of instructions and the same multiset of mnemonics), or `differs` -- with both instruction counts and
+the figures, SGPRs included.  Exit status 1 when a pair differs, a figure differs or a name is not found.
 (The .o is a fat binary: llvm-objdump --offloading extracts the device ELF first, as in tools/isa_dump.sh.)
 """
 import glob
@@ -83,10 +88,37 @@ def load(directory):
     return build
 
 
+def pairs(old, new, wanted, filt):
+    """The --pair mode: kernels of OLD against the kernels of NEW that replace them under another name."""
+    def by_name(build):
+        syms = [(s, v) for o in build.values() for s, v in o.items() if v[1] is not None]
+        return {re.sub(r'\(.*', '', n).replace('void ', ''): v for (s, v), n in zip(syms, run(filt, *[s for s, _ in syms]).splitlines())}
+    old, new, bad = by_name(old), by_name(new), 0
+    figures = FIGURES + [('sgpr', '.sgpr_count')]
+    for pair in wanted:
+        a, b = (x.strip() for x in pair.split('='))
+        if a not in old or b not in new:
+            print('%-10s%s = %s' % ('not found', a, b))
+            bad += 1
+            continue
+        (code, fig), (code2, fig2) = old[a], new[b]
+        m, m2 = [i.split()[0] for i in code], [i.split()[0] for i in code2]
+        verdict = 'same' if code == code2 else 'operands' if m == m2 else 'reordered' if sorted(m) == sorted(m2) else 'differs'
+        differ = any(fig.get(key) != fig2.get(key) for _, key in figures)
+        bad += verdict == 'differs' or differ
+        print('%-10s%s = %s  instructions %d/%d  %s%s' % (verdict, a, b, len(code), len(code2), '  '.join('%s %s/%s' % (label, fig.get(key, '-'), fig2.get(key, '-')) for label, key in figures),
+                                                       '  FIGURES DIFFER' if differ else ''))
+    print('%d pairs: %s' % (len(wanted), 'none differs' if not bad else '%d not' % bad))
+    return 1 if bad else 0
+
+
 def main():
-    if len(sys.argv) != 3:
+    wanted = [sys.argv[i + 1] for i, a in enumerate(sys.argv[:-1]) if a == '--pair']
+    if len(sys.argv) != 3 + 2 * len(wanted) or '--pair' in sys.argv[1:3]:
         sys.exit(__doc__)
     old, new = load(sys.argv[1]), load(sys.argv[2])
+    if wanted:
+        return pairs(old, new, wanted, shutil.which('llvm-cxxfilt', path=LLVM) or shutil.which('c++filt'))
     names = [s for syms in old.values() for s in syms]
     filt = shutil.which('llvm-cxxfilt', path=LLVM) or shutil.which('c++filt')   # readable names where a demangler is at hand
     plain = dict(zip(names, run(filt, *names).splitlines() if filt and names else names))
