@@ -24,7 +24,7 @@ from .abi import GlazeError
 from .scene_desc import MESH_DTYPE, VERTEX_DTYPE, SceneDesc, make_camera, make_light, make_material, make_meta  # noqa: F401
 
 __all__ = ["parse", "converted_file", "ParsedScene", "RayTraceInstance", "RayTraceScene", "RayTraceRenderer", "Integrator",
-           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points", "host_skin", "host_bone_dual_quats", "host_morph", "host_vertex_normals", "host_weld_groups",
+           "GlazeError", "SceneDesc", "host_denoise", "host_despeckle", "host_reproject", "host_project_points", "host_skin", "host_bone_dual_quats", "host_clip_bones", "host_morph", "host_vertex_normals", "host_weld_groups",
            "host_project_constants"]
 
 
@@ -289,6 +289,52 @@ def host_bone_dual_quats(bones):
     out = np.zeros((b.shape[0], 8), np.float32)
     abi.check(abi.lib().glz_host_bone_dual_quats(_ptr(b), b.shape[0], _ptr(out)))
     return out
+
+
+_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0)
+
+
+def _skeleton_struct(skin, parents, inverse_bind, root):
+    """(abi.Skeleton, the arrays it points into) of parents (n_bones integers, -1 a root), inverse_bind (n_bones, 16) and root (16, or None)"""
+    raw = np.ascontiguousarray(parents)
+    if raw.ndim != 1 or raw.dtype.kind not in "iu" or (raw.size and (raw.min() < -0x80000000 or raw.max() > 0x7FFFFFFF)):
+        raise ValueError("parents must be a 1-d array of bone indices, -1 for a root")
+    p = np.ascontiguousarray(raw, np.int32)
+    ib = _transform_array(inverse_bind)
+    if ib.shape[0] != p.shape[0]:
+        raise ValueError("inverse_bind must have one matrix per bone")
+    r = _IDENTITY if root is None else tuple(float(x) for x in np.asarray(root, np.float32).reshape(16))
+    return abi.Skeleton(int(skin), p.shape[0], _ptr(p), _ptr(ib), (C.c_float * 16)(*r)), (p, ib)
+
+
+def _clip_struct(skeleton, n_bones, times, translations, rotations, scales, morph_weights):
+    """(abi.Clip, the arrays it points into) of times (n_keys,), translations (n_keys, n_bones, 3), rotations (n_keys, n_bones, 4) as
+    (x, y, z, w), scales (n_keys, n_bones, 3) or None, morph_weights (n_keys, n_targets) or None"""
+    t = np.ascontiguousarray(times, np.float32).reshape(-1)
+    nk = t.shape[0]
+    tr = np.ascontiguousarray(translations, np.float32)
+    ro = np.ascontiguousarray(rotations, np.float32)
+    sc = None if scales is None else np.ascontiguousarray(scales, np.float32)
+    if tr.shape != (nk, n_bones, 3) or ro.shape != (nk, n_bones, 4) or (sc is not None and sc.shape != (nk, n_bones, 3)):
+        raise ValueError("translations and scales must be (n_keys, n_bones, 3), rotations (n_keys, n_bones, 4)")
+    mw = None if morph_weights is None else np.ascontiguousarray(morph_weights, np.float32)
+    if mw is not None and (mw.ndim != 2 or mw.shape[0] != nk):
+        raise ValueError("morph_weights must be (n_keys, n_targets)")
+    clip = abi.Clip(int(skeleton), nk, _ptr(t), _ptr(tr), _ptr(ro), None if sc is None else _ptr(sc), None if mw is None else _ptr(mw), 0 if mw is None else mw.shape[1])
+    return clip, (t, tr, ro, sc, mw)
+
+
+def host_clip_bones(parents, inverse_bind, times, translations, rotations, time, scales=None, morph_weights=None, root=None):
+    """glz_host_clip_bones: the clip rule (include/glaze_abi.h holds the specification) on the host, no device, the reference of
+    k_clip_bones.  parents, inverse_bind, root: as add_skeleton takes them; times, translations, rotations, scales, morph_weights: as
+    add_clip takes them.  Returns the (n_bones, 16) float32 bone matrices pose() takes -- or, for a clip with a weight track, (bones,
+    the (n_targets,) float32 lerped weights)."""
+    sk, keep = _skeleton_struct(-1, parents, inverse_bind, root)
+    clip, keep2 = _clip_struct(-1, sk.n_bones, times, translations, rotations, scales, morph_weights)
+    bones = np.zeros((sk.n_bones, 16), np.float32)
+    weights = np.zeros(clip.n_targets, np.float32) if clip.morph_weights else None
+    abi.check(abi.lib().glz_host_clip_bones(C.cast(C.byref(sk), C.c_void_p), C.cast(C.byref(clip), C.c_void_p), float(time), _ptr(bones), None if weights is None else _ptr(weights)))
+    return bones if weights is None else (bones, weights)
 
 
 def _morph_targets(targets, n_vertices):
@@ -913,6 +959,63 @@ class RayTraceRenderer:
         ms, nbytes = C.c_float(0.0), C.c_uint64(0)
         abi.check(abi.lib().glz_debug_morph_timing(self._h, C.cast(C.byref(a), C.c_void_p), int(reps), C.cast(C.byref(ms), C.c_void_p), C.cast(C.byref(nbytes), C.c_void_p)))
         return ms.value, nbytes.value
+
+    def add_skeleton(self, skin, parents, inverse_bind, root=None):
+        """A skeleton on a skin: parents (n_bones integers, -1 a root, else below the bone's own index), inverse_bind (n_bones, 16) float32,
+        column-major, and root (16 floats; None: the identity), the matrix roots are multiplied under.  n_bones must be the skin's, and a
+        skin has at most one skeleton.  Returns the skeleton's id; the skeleton is the scene's, as the skin is."""
+        sk, keep = _skeleton_struct(skin, parents, inverse_bind, root)
+        sid = abi.check(abi.lib().glz_renderer_add_skeleton(self._h, C.cast(C.byref(sk), C.c_void_p)))
+        self.__dict__.setdefault("_skeleton_bones", {})[sid] = sk.n_bones   # (add_clip checks its arrays' shapes against it)
+        return sid
+
+    def remove_skeleton(self, skeleton):
+        """Frees a skeleton and its clips; the vertices stay as they are."""
+        abi.check(abi.lib().glz_renderer_remove_skeleton(self._h, int(skeleton)))
+
+    def add_clip(self, skeleton, times, translations, rotations, scales=None, morph_weights=None):
+        """A keyframed clip on a skeleton, uploaded once: times (n_keys,) strictly ascending, translations (n_keys, n_bones, 3), rotations
+        (n_keys, n_bones, 4) as (x, y, z, w), scales (n_keys, n_bones, 3) or None (every scale 1), morph_weights (n_keys, n_targets) or
+        None -- allowed when the skeleton's skin carries an attached morph with that many targets.  Returns the clip's id."""
+        n_bones = self.__dict__.get("_skeleton_bones", {}).get(int(skeleton))
+        if n_bones is None:
+            n_bones = np.asarray(translations).shape[1] if np.asarray(translations).ndim == 3 else 0
+        clip, keep = _clip_struct(skeleton, n_bones, times, translations, rotations, scales, morph_weights)
+        return abi.check(abi.lib().glz_renderer_add_clip(self._h, C.cast(C.byref(clip), C.c_void_p)))
+
+    def remove_clip(self, clip):
+        """Frees a clip."""
+        abi.check(abi.lib().glz_renderer_remove_clip(self._h, int(clip)))
+
+    @staticmethod
+    def _play_array(plays):
+        """abi.Play array of a list of (clip id, time)"""
+        plays = list(plays)
+        return (abi.Play * max(1, len(plays)))(*[abi.Play(int(c), float(t)) for c, t in plays]), len(plays)
+
+    def play(self, plays, mode="refit"):
+        """Plays clips on the device: plays is a list of (clip id, time), at most one clip a skeleton.  One kernel makes every named
+        skeleton's bone table (and morph weight table) from the clips' keys, each skin is then written from its bind pose, and the
+        structure follows once, as pose() and animate() do in `mode`; accumulation restarts.  No bone crosses the bus."""
+        arr, n = self._play_array(plays)
+        abi.check(abi.lib().glz_renderer_play(self._h, C.cast(arr, C.c_void_p), n, self._GEOMETRY_MODES.get(mode, mode)))
+
+    def debug_clip_bones(self, clip, time, n_bones, blend="linear", n_targets=0):
+        """k_clip_bones alone for one play, no vertex written: the bone table as the device holds it, (n_bones, 12) float32 (three rows
+        a bone) for a skin whose blend is 'linear', (n_bones, 8) for 'dual_quaternion' -- `blend` must be the skin's -- and, with
+        n_targets > 0 (a clip with a weight track), (table, the (n_targets,) weight table)."""
+        arr, _ = self._play_array([(clip, time)])
+        rows = np.zeros((int(n_bones), 4 * (2 if _skin_blend(blend) == abi.SKIN_DUAL_QUATERNION else 3)), np.float32)
+        weights = np.zeros(int(n_targets), np.float32) if n_targets else None
+        abi.check(abi.lib().glz_debug_clip_bones(self._h, C.cast(arr, C.c_void_p), _ptr(rows), None if weights is None else _ptr(weights)))
+        return rows if weights is None else (rows, weights)
+
+    def debug_clip_timing(self, plays, reps=20):
+        """k_clip_bones alone, one launch for all of plays (the scene is untouched): milliseconds per launch, device events around reps launches"""
+        arr, n = self._play_array(plays)
+        ms = C.c_float(0.0)
+        abi.check(abi.lib().glz_debug_clip_timing(self._h, C.cast(arr, C.c_void_p), n, int(reps), C.cast(C.byref(ms), C.c_void_p)))
+        return ms.value
 
     def add_normals(self, first, n_vertices, groups=None):
         """A normal set over the scene's vertices [first, first + n_vertices): from now on their normals are the normal rule

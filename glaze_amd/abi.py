@@ -186,6 +186,22 @@ class Animation(C.Structure):
     _fields_ = [("morphs", C.c_void_p), ("n_morphs", C.c_uint32), ("poses", C.c_void_p), ("n_poses", C.c_uint32)]
 
 
+class Skeleton(C.Structure):
+    """glz_skeleton"""
+    _fields_ = [("skin", C.c_int), ("n_bones", C.c_uint32), ("parents", C.c_void_p), ("inverse_bind", C.c_void_p), ("root", C.c_float * 16)]
+
+
+class Clip(C.Structure):
+    """glz_clip"""
+    _fields_ = [("skeleton", C.c_int), ("n_keys", C.c_uint32), ("times", C.c_void_p), ("translations", C.c_void_p), ("rotations", C.c_void_p),
+                ("scales", C.c_void_p), ("morph_weights", C.c_void_p), ("n_targets", C.c_uint32)]
+
+
+class Play(C.Structure):
+    """glz_play"""
+    _fields_ = [("clip", C.c_int), ("time", C.c_float)]
+
+
 class Normals(C.Structure):
     """glz_normals"""
     _fields_ = [("first_vertex", C.c_uint32), ("n_vertices", C.c_uint32), ("groups", C.c_void_p)]
@@ -262,6 +278,14 @@ PROTOTYPES = {
     "glz_renderer_reproject_animated": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "glz_host_morph": (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, _P]),
     "glz_debug_morph_timing": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    "glz_renderer_add_skeleton": (C.c_int, [_P, _P]),
+    "glz_renderer_remove_skeleton": (C.c_int, [_P, C.c_int]),
+    "glz_renderer_add_clip": (C.c_int, [_P, _P]),
+    "glz_renderer_remove_clip": (C.c_int, [_P, C.c_int]),
+    "glz_renderer_play": (C.c_int, [_P, _P, C.c_uint32, C.c_int]),
+    "glz_host_clip_bones": (C.c_int, [_P, _P, C.c_float, _P, _P]),
+    "glz_debug_clip_bones": (C.c_int, [_P, _P, _P, _P]),
+    "glz_debug_clip_timing": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
     "glz_renderer_add_normals": (C.c_int, [_P, _P]),
     "glz_renderer_remove_normals": (C.c_int, [_P, C.c_int]),
     "glz_host_vertex_normals": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),

@@ -419,6 +419,46 @@ int glz_renderer_animate(glz_renderer* h, const glz_animation* anim, int mode) {
   GLZ_RET(h->r->animate(*anim, mode, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
+int glz_renderer_add_skeleton(glz_renderer* h, const glz_skeleton* skeleton) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!skeleton) return fail(GLZ_E_ARG, "add_skeleton: the skeleton is null");
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  const int id = h->r->add_skeleton(*skeleton, e);
+  if (id < 0) return fail(e);
+  return id;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_remove_skeleton(glz_renderer* h, int skeleton) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  GLZ_RET(h->r->remove_skeleton(skeleton, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_add_clip(glz_renderer* h, const glz_clip* clip) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!clip) return fail(GLZ_E_ARG, "add_clip: the clip is null");
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  const int id = h->r->add_clip(*clip, e);
+  if (id < 0) return fail(e);
+  return id;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_remove_clip(glz_renderer* h, int clip) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  GLZ_RET(h->r->remove_clip(clip, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_renderer_play(glz_renderer* h, const glz_play* plays, uint32_t n, int mode) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!h->r->scene()) return fail(GLZ_E_ARG, "renderer has no scene");
+  // (checked here as well as in the scene: a refused call must not make the renderer drain and restart)
+  uint32_t first = 0, count = 0;
+  if (!h->r->scene()->played_span(plays, n, "play", first, count, e)) return fail(e);
+  if (mode != GLZ_GEOMETRY_REFIT && mode != GLZ_GEOMETRY_REBUILD) return fail(GLZ_E_ARG, "play: unknown mode");
+  GLZ_RET(h->r->play(plays, n, mode, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
 int glz_renderer_add_normals(glz_renderer* h, const glz_normals* set) {
   GLZ_GUARD_BEGIN GLZ_R(h);
   if (!set) return fail(GLZ_E_ARG, "add_normals: the set is null");

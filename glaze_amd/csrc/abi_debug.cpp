@@ -1,6 +1,7 @@
 // The test hooks of the extern "C" surface (include/glaze_abi.h): the glz_debug_* entry points, which read a scene's device structures
 // back or run one kernel on arrays the caller gives, and the glz_host_* ones, which expose host logic that needs no device.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -9,6 +10,7 @@
 #include "denoise.h"
 #include "reproject.h"
 #include "skin.h"
+#include "clip.h"
 #include "morph.h"
 #include "normals.h"
 #include "mipchain.h"
@@ -119,6 +121,19 @@ int glz_debug_skin_timing(glz_renderer* h, const glz_pose* pose, uint32_t reps, 
   if (!pose || !kernel_ms_out || !h->r->scene()) return fail(GLZ_E_ARG, "bad argument");
   *kernel_ms_out = 0.0f;
   GLZ_RET(h->r->wait_idle(e) && h->r->scene()->time_skin(*pose, reps, kernel_ms_out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_clip_bones(glz_renderer* h, const glz_play* play, float* rows_out, float* weights_out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!play || !rows_out || !h->r->scene()) return fail(GLZ_E_ARG, "bad argument");
+  GLZ_RET(h->r->wait_idle(e) && h->r->scene()->clip_bones(*play, rows_out, weights_out, e));
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_debug_clip_timing(glz_renderer* h, const glz_play* plays, uint32_t n_plays, uint32_t reps, float* kernel_ms_out) {
+  GLZ_GUARD_BEGIN GLZ_R(h);
+  if (!plays || !kernel_ms_out || !h->r->scene()) return fail(GLZ_E_ARG, "bad argument");
+  *kernel_ms_out = 0.0f;
+  GLZ_RET(h->r->wait_idle(e) && h->r->scene()->time_clip(plays, n_plays, reps, kernel_ms_out, e));
   GLZ_GUARD_END(GLZ_E_IO)
 }
 int glz_debug_morph_timing(glz_renderer* h, const glz_animation* one, uint32_t reps, float* kernel_ms_out, uint64_t* bytes_out) {
@@ -468,6 +483,17 @@ int glz_host_bone_dual_quats(const glz_transform* bones, uint32_t n, float* out8
     post::pack_bone_dq(bones[b], rows);
     memcpy(out8 + 8 * (size_t)b, rows, sizeof rows);
   }
+  return GLZ_OK;
+  GLZ_GUARD_END(GLZ_E_IO)
+}
+int glz_host_clip_bones(const glz_skeleton_desc* skeleton, const glz_clip_desc* clip, float time, glz_transform* bones_out, float* weights_out) {
+  GLZ_GUARD_BEGIN
+  if (!skeleton || !clip || !bones_out) return fail(GLZ_E_ARG, "host_clip_bones: null argument");
+  std::string why;
+  if (!post::clip_check_skeleton(skeleton->parents, skeleton->inverse_bind, skeleton->n_bones, why) || !post::clip_check_keys(*clip, why))
+    return fail(GLZ_E_ARG, ("host_clip_bones: " + why).c_str());
+  if (!std::isfinite(time)) return fail(GLZ_E_ARG, "host_clip_bones: the time is not finite");
+  post::host_clip_bones(*skeleton, *clip, time, bones_out, weights_out);
   return GLZ_OK;
   GLZ_GUARD_END(GLZ_E_IO)
 }

@@ -1,7 +1,8 @@
-// Skins, morph targets and normal sets of a scene on the device: their records, their checks and their launches.
+// Skins, morph targets, normal sets, skeletons and clips of a scene on the device: their records, their checks and their launches.
 #include "deformers.h"
 
 #include <algorithm>
+#include <cmath>
 #include <functional>
 #include <string>
 
@@ -103,6 +104,7 @@ bool Deformers::remove_skin(int id, Error& err) {
   const auto it = skins_.find(id);
   if (it == skins_.end()) return err.fail(GLZ_E_ARG, "remove_skin: no such skin");
   if (it->second.h.morph >= 0) return err.fail(GLZ_E_ARG, "remove_skin: the skin still carries a morph (remove_morph first)");
+  if (it->second.h.skeleton >= 0) return err.fail(GLZ_E_ARG, "remove_skin: the skin still has a skeleton (remove_skeleton first)");
   skins_.erase(it);
   return true;
 }
@@ -173,7 +175,12 @@ int Deformers::add_morph(const Sources& s, const glz_morph& g, Error& err) {
 bool Deformers::remove_morph(int id, Error& err) {
   const auto it = morphs_.find(id);
   if (it == morphs_.end()) return err.fail(GLZ_E_ARG, "remove_morph: no such morph");
-  if (it->second.h.skin >= 0) skins_.at(it->second.h.skin).h.morph = -1;
+  if (it->second.h.skin >= 0) {
+    for (const auto& kv : clips_)   // (a clip's weight track feeds the fused kernel of this morph)
+      if (!kv.second.h.morph_weights.empty() && skeletons_.at(kv.second.h.skeleton).h.skin == it->second.h.skin)
+        return err.fail(GLZ_E_ARG, "remove_morph: a clip's weight track still drives the morph (remove_clip first)");
+    skins_.at(it->second.h.skin).h.morph = -1;
+  }
   morphs_.erase(it);
   return true;
 }
@@ -221,15 +228,6 @@ bool Deformers::animated_span(const glz_animation* anim, const char* who, uint32
 
 bool Deformers::deform(const Morph* morph, const float* weights, const glz_pose* pose, std::vector<float4>* packed, DeviceBuffer<float4>* bones, float4* span,
                        uint32_t span_first, hipStream_t st, Error& err) const {
-  MorphArgs m{};
-  SkinArgs k{};
-  const char* rule = "k_morph";   // which rule ran, for an error's text
-  uint32_t first = 0;
-  if (morph) {
-    const post::MorphLayout& l = morph->h.layout;
-    m = MorphArgs{morph->h.skin >= 0 ? skins_.at(morph->h.skin).bind.ptr : morph->base.ptr, morph->counts.ptr, morph->slices.ptr, morph->entries.ptr, l.n_vertices, weights, l.n_targets};
-    first = morph->h.first;
-  }
   if (pose) {   // the bones, packed for the skin's blend mode (post::bone_rows float4 a bone), on their way up
     const Skin& s = skins_.at(pose->skin);
     const bool dq = s.h.blend == GLZ_SKIN_DUAL_QUATERNION;
@@ -243,11 +241,28 @@ bool Deformers::deform(const Morph* morph, const float* weights, const glz_pose*
       if (!hip_ok(bones->alloc(packed->size()), "alloc bones", err)) return false;
     }
     if (!hip_ok(hipMemcpyAsync(bones->ptr, packed->data(), sizeof(float4) * packed->size(), hipMemcpyHostToDevice, st), "upload bones", err)) return false;
-    k = SkinArgs{s.bind.ptr, s.joints.ptr, s.weights.ptr, s.h.n, bones->ptr, s.h.n_bones, s.h.blend};
-    rule = dq ? (morph ? "k_morph_skin_dq" : "k_skin_dq") : (morph ? "k_morph_skin" : "k_skin");
-    first = s.h.first;
   }
-  return hip_ok(launch_deform(st, morph ? &m : nullptr, pose ? &k : nullptr, span + 2 * (size_t)(first - span_first)), rule, err);
+  return deform_tables(morph, weights, pose ? &skins_.at(pose->skin) : nullptr, pose ? bones->ptr : nullptr, span, span_first, st, err);
+}
+
+bool Deformers::deform_tables(const Morph* morph, const float* weights, const Skin* skin, const float4* bones, float4* span, uint32_t span_first, hipStream_t st,
+                              Error& err) const {
+  MorphArgs m{};
+  SkinArgs k{};
+  const char* rule = "k_morph";   // which rule ran, for an error's text
+  uint32_t first = 0;
+  if (morph) {
+    const post::MorphLayout& l = morph->h.layout;
+    m = MorphArgs{morph->h.skin >= 0 ? skins_.at(morph->h.skin).bind.ptr : morph->base.ptr, morph->counts.ptr, morph->slices.ptr, morph->entries.ptr, l.n_vertices, weights, l.n_targets};
+    first = morph->h.first;
+  }
+  if (skin) {
+    const bool dq = skin->h.blend == GLZ_SKIN_DUAL_QUATERNION;
+    k = SkinArgs{skin->bind.ptr, skin->joints.ptr, skin->weights.ptr, skin->h.n, bones, skin->h.n_bones, skin->h.blend};
+    rule = dq ? (morph ? "k_morph_skin_dq" : "k_skin_dq") : (morph ? "k_morph_skin" : "k_skin");
+    first = skin->h.first;
+  }
+  return hip_ok(launch_deform(st, morph ? &m : nullptr, skin ? &k : nullptr, span + 2 * (size_t)(first - span_first)), rule, err);
 }
 
 bool Deformers::animate_into(const glz_animation& anim, float4* span, uint32_t span_first, AnimationUploads& up, hipStream_t st, Error& err) const {
@@ -269,6 +284,173 @@ bool Deformers::animate_into(const glz_animation& anim, float4* span, uint32_t s
       return false;
   }
   return true;
+}
+
+// ---- skeletons and clips ----
+
+int Deformers::install_skeleton(const Sources& s, int id, SkeletonHost&& h, Error& err) {
+  Skeleton k;
+  k.h = std::move(h);
+  const size_t n = k.h.n_bones;
+  if (!hip_ok(k.parents.upload(k.h.parents.data(), n, s.stream), "upload parents", err) ||
+      !hip_ok(k.level_bones.upload(k.h.level_bones.data(), k.h.level_bones.size(), s.stream), "upload levels", err) ||
+      !hip_ok(k.level_offsets.upload(k.h.level_offsets.data(), k.h.level_offsets.size(), s.stream), "upload levels", err) ||
+      !hip_ok(k.inverse_bind.upload(k.h.inverse_bind.data(), k.h.inverse_bind.size(), s.stream), "upload inverse bind", err) ||
+      !hip_ok(k.world.alloc(post::kSkinBoneRows * n), "alloc world table", err) ||
+      !hip_ok(k.bones.alloc(std::max(post::kSkinBoneRows, post::kSkinDqBoneRows) * n), "alloc bone table", err) || !hip_ok(hipStreamSynchronize(s.stream), "add_skeleton", err))
+    return -1;
+  skins_.at(k.h.skin).h.skeleton = id;
+  skeletons_.emplace(id, std::move(k));
+  return id;
+}
+
+int Deformers::add_skeleton(const Sources& s, const glz_skeleton& g, Error& err) {
+  auto refuse = [&](const std::string& why) {
+    err.fail(GLZ_E_ARG, "add_skeleton: " + why);
+    return -1;
+  };
+  const auto it = skins_.find(g.skin);
+  if (it == skins_.end()) return refuse("no such skin");
+  if (it->second.h.skeleton >= 0) return refuse("the skin already has a skeleton");
+  if (g.n_bones != it->second.h.n_bones) return refuse("n_bones is not the skin's");
+  std::string why;
+  if (!post::clip_check_skeleton(g.parents, g.inverse_bind, g.n_bones, why)) return refuse(why);
+  if (!hip_ok(hipSetDevice(s.device), "hipSetDevice", err)) return -1;
+  SkeletonHost h;
+  h.skin = g.skin;
+  h.n_bones = g.n_bones;
+  h.parents.assign(g.parents, g.parents + g.n_bones);
+  h.inverse_bind.resize(post::kSkinBoneRows * ((size_t)g.n_bones + 1));
+  for (uint32_t b = 0; b <= g.n_bones; ++b) {
+    const post::Affine a = post::affine_of(b < g.n_bones ? g.inverse_bind[b] : g.root);
+    std::copy(a.r, a.r + post::kSkinBoneRows, h.inverse_bind.begin() + post::kSkinBoneRows * (size_t)b);
+  }
+  post::clip_levels(g.parents, g.n_bones, h.level_bones, h.level_offsets);
+  const int id = install_skeleton(s, next_skeleton_, std::move(h), err);
+  if (id >= 0) ++next_skeleton_;
+  return id;
+}
+
+bool Deformers::remove_skeleton(int id, Error& err) {
+  const auto it = skeletons_.find(id);
+  if (it == skeletons_.end()) return err.fail(GLZ_E_ARG, "remove_skeleton: no such skeleton");
+  for (auto c = clips_.begin(); c != clips_.end();) c = c->second.h.skeleton == id ? clips_.erase(c) : std::next(c);
+  skins_.at(it->second.h.skin).h.skeleton = -1;
+  skeletons_.erase(it);
+  return true;
+}
+
+int Deformers::install_clip(const Sources& s, int id, ClipHost&& h, Error& err) {
+  Clip c;
+  c.h = std::move(h);
+  const Skeleton& k = skeletons_.at(c.h.skeleton);
+  const bool scaled = !c.h.scales.empty(), tracked = !c.h.morph_weights.empty();
+  if (!hip_ok(c.translations.upload(c.h.translations.data(), c.h.translations.size(), s.stream), "upload clip translations", err) ||
+      !hip_ok(c.rotations.upload(c.h.rotations.data(), c.h.rotations.size(), s.stream), "upload clip rotations", err) ||
+      (scaled && !hip_ok(c.scales.upload(c.h.scales.data(), c.h.scales.size(), s.stream), "upload clip scales", err)) ||
+      (tracked && (!hip_ok(c.morph_weights.upload(c.h.morph_weights.data(), c.h.morph_weights.size(), s.stream), "upload clip morph weights", err) ||
+                   !hip_ok(c.weights.alloc(c.h.n_targets), "alloc clip weight table", err))))
+    return -1;
+  const ClipArgs args{c.translations.ptr, c.rotations.ptr, c.scales.ptr, c.morph_weights.ptr, k.parents.ptr, k.level_bones.ptr, k.level_offsets.ptr, k.inverse_bind.ptr,
+                      k.world.ptr,        k.bones.ptr,     c.weights.ptr, k.h.n_bones, (uint32_t)k.h.level_offsets.size() - 1, c.h.n_targets};
+  if (!hip_ok(c.args.upload(&args, 1, s.stream), "upload clip", err) || !hip_ok(hipStreamSynchronize(s.stream), "add_clip", err)) return -1;
+  clips_.emplace(id, std::move(c));
+  return id;
+}
+
+int Deformers::add_clip(const Sources& s, const glz_clip& g, Error& err) {
+  auto refuse = [&](const std::string& why) {
+    err.fail(GLZ_E_ARG, "add_clip: " + why);
+    return -1;
+  };
+  const auto it = skeletons_.find(g.skeleton);
+  if (it == skeletons_.end()) return refuse("no such skeleton");
+  std::string why;
+  if (!post::clip_check_keys(g, why)) return refuse(why);
+  if (g.morph_weights) {
+    const int morph = skins_.at(it->second.h.skin).h.morph;
+    if (morph < 0) return refuse("a weight track needs an attached morph on the skeleton's skin");
+    if (g.n_targets != morphs_.at(morph).h.layout.n_targets) return refuse("the weight track's target count is not the morph's");
+  }
+  if (!hip_ok(hipSetDevice(s.device), "hipSetDevice", err)) return -1;
+  const size_t per_key = (size_t)g.n_keys * it->second.h.n_bones;
+  ClipHost h;
+  h.skeleton = g.skeleton;
+  h.n_keys = g.n_keys;
+  h.n_targets = g.n_targets;
+  h.times.assign(g.times, g.times + g.n_keys);
+  h.translations.assign(g.translations, g.translations + 3 * per_key);
+  h.rotations.assign(g.rotations, g.rotations + 4 * per_key);
+  if (g.scales) h.scales.assign(g.scales, g.scales + 3 * per_key);
+  if (g.morph_weights) h.morph_weights.assign(g.morph_weights, g.morph_weights + (size_t)g.n_keys * g.n_targets);
+  const int id = install_clip(s, next_clip_, std::move(h), err);
+  if (id >= 0) ++next_clip_;
+  return id;
+}
+
+bool Deformers::remove_clip(int id, Error& err) {
+  if (clips_.erase(id) == 0) return err.fail(GLZ_E_ARG, "remove_clip: no such clip");
+  return true;
+}
+
+bool Deformers::played_span(const glz_play* plays, uint32_t n, const char* who, uint32_t& first, uint32_t& count, Error& err) const {
+  auto refuse = [&](const char* why) { return err.fail(GLZ_E_ARG, std::string(who) + ": " + why); };
+  if (!plays || n == 0) return refuse("plays is null or empty");
+  uint64_t lo = ~0ull, hi = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const auto it = clips_.find(plays[i].clip);
+    if (it == clips_.end()) return refuse("no such clip");
+    if (!std::isfinite(plays[i].time)) return refuse("a time is not finite");
+    for (uint32_t k = 0; k < i; ++k)
+      if (clips_.at(plays[k].clip).h.skeleton == it->second.h.skeleton) return refuse("two plays name clips of the same skeleton");
+    const SkinHost& skin = skins_.at(skeletons_.at(it->second.h.skeleton).h.skin).h;
+    lo = std::min<uint64_t>(lo, skin.first);
+    hi = std::max<uint64_t>(hi, (uint64_t)skin.first + skin.n);
+  }
+  first = (uint32_t)lo;
+  count = (uint32_t)(hi - lo);
+  return true;
+}
+
+bool Deformers::upload_plays(const glz_play* plays, uint32_t n, PlayUploads& up, hipStream_t st, Error& err) const {
+  up.records.resize(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const Clip& c = clips_.at(plays[i].clip);
+    const post::ClipKey key = post::clip_key(c.h.times.data(), c.h.n_keys, plays[i].time);
+    up.records[i] = ClipPlay{c.args.ptr, key.k0, key.k1, key.u, skins_.at(skeletons_.at(c.h.skeleton).h.skin).h.blend};
+  }
+  if (up.table.ptr == nullptr || up.table.count != n) {
+    if (!hip_ok(up.table.alloc(n), "alloc plays", err)) return false;
+  }
+  return hip_ok(hipMemcpyAsync(up.table.ptr, up.records.data(), sizeof(ClipPlay) * n, hipMemcpyHostToDevice, st), "upload plays", err);
+}
+
+bool Deformers::play_into(const glz_play* plays, uint32_t n, float4* span, uint32_t span_first, PlayUploads& up, hipStream_t st, Error& err) const {
+  if (!upload_plays(plays, n, up, st, err) || !hip_ok(launch_clip_bones(st, up.table.ptr, n), "k_clip_bones", err)) return false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const Clip& c = clips_.at(plays[i].clip);
+    const Skeleton& k = skeletons_.at(c.h.skeleton);
+    const Skin& skin = skins_.at(k.h.skin);
+    const bool fused = c.weights.ptr != nullptr;   // (add_clip and remove_morph see to it that the morph is there)
+    if (!deform_tables(fused ? &morphs_.at(skin.h.morph) : nullptr, c.weights.ptr, &skin, k.bones.ptr, span, span_first, st, err)) return false;
+  }
+  return true;
+}
+
+bool Deformers::clip_bones(const Sources& s, const glz_play& play, float* rows_out, float* weights_out, Error& err) const {
+  uint32_t first = 0, count = 0;
+  if (!rows_out) return err.fail(GLZ_E_ARG, "clip bones: null output");
+  if (!played_span(&play, 1, "clip bones", first, count, err) || !hip_ok(hipSetDevice(s.device), "hipSetDevice", err)) return false;
+  const Clip& c = clips_.at(play.clip);
+  const Skeleton& k = skeletons_.at(c.h.skeleton);
+  PlayUploads up;
+  if (!upload_plays(&play, 1, up, s.stream, err) || !hip_ok(launch_clip_bones(s.stream, up.table.ptr, 1), "k_clip_bones", err)) return false;
+  const size_t rows = (size_t)post::bone_rows(skins_.at(k.h.skin).h.blend) * k.h.n_bones;
+  if (!hip_ok(hipMemcpyAsync(rows_out, k.bones.ptr, sizeof(float4) * rows, hipMemcpyDeviceToHost, s.stream), "read bone table", err)) return false;
+  if (weights_out && c.weights.ptr &&
+      !hip_ok(hipMemcpyAsync(weights_out, c.weights.ptr, sizeof(float) * c.h.n_targets, hipMemcpyDeviceToHost, s.stream), "read weight table", err))
+    return false;
+  return hip_ok(hipStreamSynchronize(s.stream), "clip bones", err);
 }
 
 // ---- vertex normals from deformed positions ----
@@ -337,13 +519,19 @@ bool Deformers::copy_from(const Sources& s, const Deformers& src, Error& err) {
   if (!hip_ok(hipSetDevice(s.device), "hipSetDevice", err)) return false;
   for (const auto& kv : src.skins_) {
     SkinHost h = kv.second.h;
-    h.morph = -1;   // (its morph attaches itself below)
+    h.morph = h.skeleton = -1;   // (its morph and its skeleton attach themselves below)
     if (install_skin(s, kv.first, std::move(h), true, err) < 0) return false;
   }
   for (const auto& kv : src.morphs_)
     if (install_morph(s, kv.first, MorphHost(kv.second.h), true, err) < 0) return false;
   for (const auto& kv : src.normals_)
     if (install_normals(s, kv.first, post::NormalLayout(kv.second.layout), err) < 0) return false;
+  for (const auto& kv : src.skeletons_)
+    if (install_skeleton(s, kv.first, SkeletonHost(kv.second.h), err) < 0) return false;
+  for (const auto& kv : src.clips_)
+    if (install_clip(s, kv.first, ClipHost(kv.second.h), err) < 0) return false;
+  next_skeleton_ = src.next_skeleton_;
+  next_clip_ = src.next_clip_;
   next_skin_ = src.next_skin_;
   next_morph_ = src.next_morph_;
   next_normals_ = src.next_normals_;
@@ -362,6 +550,15 @@ bool Deformers::time_skin(const Sources& s, const glz_pose& pose, uint32_t reps,
   DeviceBuffer<float4> bones, out;
   if (!hip_ok(out.alloc(2 * (size_t)count), "alloc", err)) return false;
   return time_launches(s.stream, reps, "skin timing", {[&] { return deform(nullptr, nullptr, &pose, &packed, &bones, out.ptr, first, s.stream, err); }}, kernel_ms, err);
+}
+
+bool Deformers::time_clip(const Sources& s, const glz_play* plays, uint32_t n, uint32_t reps, float* kernel_ms, Error& err) const {
+  uint32_t first = 0, count = 0;
+  if (!kernel_ms || reps == 0) return err.fail(GLZ_E_ARG, "clip timing: null output or no repeats");
+  if (!played_span(plays, n, "clip timing", first, count, err) || !hip_ok(hipSetDevice(s.device), "hipSetDevice", err)) return false;
+  PlayUploads up;
+  if (!upload_plays(plays, n, up, s.stream, err)) return false;
+  return time_launches(s.stream, reps, "clip timing", {[&] { return hip_ok(launch_clip_bones(s.stream, up.table.ptr, n), "k_clip_bones", err); }}, kernel_ms, err);
 }
 
 bool Deformers::time_morph(const Sources& s, const glz_animation& one, uint32_t reps, float* kernel_ms, uint64_t* bytes, Error& err) const {

@@ -280,6 +280,37 @@ constexpr uint32_t kMorphLdsTargets = 1024;   // 4 KB of a block's LDS
 // launched for no vertices; both null is hipErrorInvalidValue.
 hipError_t launch_deform(hipStream_t st, const MorphArgs* morph, const SkinArgs* skin, float4* out);
 
+// ---- skeletons and clips: the bone and weight tables the deformers read, made from keyframes (kernels_clip.hip; clip.h holds the rule) ----
+// One clip with its skeleton, as it lies on the device from add_clip on.  Keys: key after key, bone after bone within a key (translations
+// and scales 3 floats a bone, rotations 4; scales null: every scale is 1), morph_weights n_targets a key (null: no weight track).
+// Skeleton: parents (-1, or below the bone's own index), the level table (clip_levels: level l is level_bones[level_offsets[l] ..
+// level_offsets[l + 1]), every entry below n_bones), inverse_bind as three rows a bone with root's three rows behind the last bone's.
+// What the kernel writes: world (three rows a bone, scratch), bones (the skin's table: at least 3 * n_bones float4) and weights (n_targets).
+struct ClipArgs {
+  const float* translations;
+  const float* rotations;
+  const float* scales;
+  const float* morph_weights;
+  const int32_t* parents;
+  const uint32_t* level_bones;
+  const uint32_t* level_offsets;
+  const float4* inverse_bind;
+  float4* world;
+  float4* bones;
+  float* weights;
+  uint32_t n_bones, n_levels, n_targets;
+};
+// One play of a call: which clip, the two keys (both below the clip's key count) and the second's weight, and the skin's blend mode now
+struct ClipPlay {
+  const ClipArgs* clip;
+  uint32_t k0, k1;
+  float u;
+  int blend;   // GLZ_SKIN_*: which layout the bone table gets
+};
+// One block a play: clip.bones and clip.weights of every play, by THE CLIP RULE.  plays: n_plays of them on the device; no two name
+// clips that share a world or bone table.  Nothing is launched for no plays.
+hipError_t launch_clip_bones(hipStream_t st, const ClipPlay* plays, uint32_t n_plays);
+
 // ---- vertex normals from deformed positions (kernels_normals.hip; normals.h holds the rule and the layout) ----
 // What a normal set's kernels read: post::NormalLayout on the device.  Every face's three indices are below the scene's vertex count,
 // every row entry below n_faces and every row's count at most its slice's width (pack_normals made them so: the kernels index by them).

@@ -616,6 +616,45 @@ bool Renderer::animate(const glz_animation& anim, int mode, Error& err) {
   const glz_animation a = anim;
   return group_.forward([=](Renderer& p, Error& e) { return p.animate(a, mode, e); }, err);
 }
+// Skeletons and clips are the scene's, as skins are.
+int Renderer::add_skeleton(const glz_skeleton& skeleton, Error& err) {
+  if (!wait_idle(err)) return -1;
+  const int id = scene_->add_skeleton(skeleton, err);
+  if (id < 0) return -1;
+  const glz_skeleton k = skeleton;
+  const bool followed = group_.forward([=](Renderer& p, Error& e) {
+    const int got = p.add_skeleton(k, e);
+    if (got >= 0 && got != id) e.fail(GLZ_E_DEVICE, "add_skeleton: a replica gave another skeleton id");
+    return got == id;
+  }, err);
+  if (!followed) return -1;
+  return id;
+}
+bool Renderer::remove_skeleton(int id, Error& err) {
+  if (!wait_idle(err) || !scene_->remove_skeleton(id, err)) return false;
+  return group_.forward([=](Renderer& p, Error& e) { return p.remove_skeleton(id, e); }, err);
+}
+int Renderer::add_clip(const glz_clip& clip, Error& err) {
+  if (!wait_idle(err)) return -1;
+  const int id = scene_->add_clip(clip, err);
+  if (id < 0) return -1;
+  const glz_clip c = clip;
+  const bool followed = group_.forward([=](Renderer& p, Error& e) {
+    const int got = p.add_clip(c, e);
+    if (got >= 0 && got != id) e.fail(GLZ_E_DEVICE, "add_clip: a replica gave another clip id");
+    return got == id;
+  }, err);
+  if (!followed) return -1;
+  return id;
+}
+bool Renderer::remove_clip(int id, Error& err) {
+  if (!wait_idle(err) || !scene_->remove_clip(id, err)) return false;
+  return group_.forward([=](Renderer& p, Error& e) { return p.remove_clip(id, e); }, err);
+}
+bool Renderer::play(const glz_play* plays, uint32_t n, int mode, Error& err) {
+  if (!update_scene([&] { return scene_->play(plays, n, mode, err); }, err)) return false;
+  return group_.forward([=](Renderer& p, Error& e) { return p.play(plays, n, mode, e); }, err);
+}
 // Normal sets are the scene's, as skins and morphs are; adding one changes the vertices' normals, so it is an update of the scene too.
 int Renderer::add_normals(const glz_normals& set, Error& err) {
   int id = -1;

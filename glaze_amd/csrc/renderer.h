@@ -37,6 +37,12 @@ class Renderer {
   int add_morph(const glz_morph& morph, Error& err);    // Scene::add_morph here and on every replica; the id, or -1
   bool remove_morph(int id, Error& err);
   bool animate(const glz_animation& anim, int mode, Error& err);   // Scene::animate; restarts accumulation, like pose_skins
+  // skeletons and clips are the scene's, as skins are: here and on every replica; the id, or -1
+  int add_skeleton(const glz_skeleton& skeleton, Error& err);
+  bool remove_skeleton(int id, Error& err);
+  int add_clip(const glz_clip& clip, Error& err);
+  bool remove_clip(int id, Error& err);
+  bool play(const glz_play* plays, uint32_t n, int mode, Error& err);   // Scene::play; restarts accumulation, like animate
   int add_normals(const glz_normals& set, Error& err);  // Scene::add_normals here and on every replica; restarts accumulation; the id, or -1
   bool remove_normals(int id, Error& err);
   bool read_vertices(uint32_t first, uint32_t n, glz_vertex* out, Error& err);   // idle first, then the scene's vertices as the device holds them

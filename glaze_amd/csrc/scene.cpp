@@ -314,6 +314,16 @@ bool Scene::run_animation(const glz_animation& anim, int mode, const char* who, 
   }, err);
 }
 
+bool Scene::play(const glz_play* plays, uint32_t n, int mode, Error& err) {
+  uint32_t first = 0, count = 0;
+  if (!deformers_.played_span(plays, n, "play", first, count, err)) return false;
+  // as run_animation: the mirror comes up to date after the derivatives, and the span is stale from the first kernel on
+  return update_geometry("play", mode, false, -1, first, count, [&](hipStream_t) {
+    mark_stale(first, count);
+    return deformers_.play(deformer_sources(), plays, n, err);   // (the table outlives its copy: Accel::update_geometry waits for the stream)
+  }, err);
+}
+
 int Scene::add_normals(const glz_normals& g, Error& err) {
   post::NormalLayout layout;
   if (!deformers_.pack_normals(deformer_sources(), g, layout, err)) return -1;

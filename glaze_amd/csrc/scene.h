@@ -73,6 +73,15 @@ class Scene {
   int add_morph(const glz_morph& morph, Error& err) { return deformers_.add_morph(deformer_sources(), morph, err); }
   bool remove_morph(int id, Error& err) { return deformers_.remove_morph(id, err); }
   bool remove_normals(int id, Error& err) { return deformers_.remove_normals(id, err); }
+  int add_skeleton(const glz_skeleton& skeleton, Error& err) { return deformers_.add_skeleton(deformer_sources(), skeleton, err); }
+  bool remove_skeleton(int id, Error& err) { return deformers_.remove_skeleton(id, err); }
+  int add_clip(const glz_clip& clip, Error& err) { return deformers_.add_clip(deformer_sources(), clip, err); }
+  bool remove_clip(int id, Error& err) { return deformers_.remove_clip(id, err); }
+  bool played_span(const glz_play* plays, uint32_t n, const char* who, uint32_t& first, uint32_t& count, Error& err) const {
+    return deformers_.played_span(plays, n, who, first, count, err);
+  }
+  bool clip_bones(const glz_play& play, float* rows_out, float* weights_out, Error& err) const { return deformers_.clip_bones(deformer_sources(), play, rows_out, weights_out, err); }
+  bool time_clip(const glz_play* plays, uint32_t n, uint32_t reps, float* kernel_ms, Error& err) const { return deformers_.time_clip(deformer_sources(), plays, n, reps, kernel_ms, err); }
   bool animated_span(const glz_animation* anim, const char* who, uint32_t& first, uint32_t& count, Error& err) const {
     return deformers_.animated_span(anim, who, first, count, err);
   }
@@ -92,6 +101,9 @@ class Scene {
   bool animate(const glz_animation& anim, int mode, Error& err) { return run_animation(anim, mode, "animate", err); }
   // animate with no morph named
   bool pose_skins(const glz_pose* poses, uint32_t n_poses, int mode, Error& err) { return run_animation(glz_animation{nullptr, 0, poses, n_poses}, mode, "pose_skins", err); }
+  // Clips played in one update of the structure (glz_renderer_play): k_clip_bones and the skins' kernels into the vertex buffer
+  // (Deformers::play_into), then the same tail as animate, over the span from the lowest to the highest vertex written.
+  bool play(const glz_play* plays, uint32_t n, int mode, Error& err);
   // A normal set (Deformers::pack_normals, install_normals): the rule runs once, and the scene then does what update_vertices(REFIT) does
   // after its upload over the set's range.  From then on update_vertices, pose_skins and animate run the set's two kernels after their own
   // writes and before the derivatives whenever the span they wrote overlaps the set's reach.  The id, or -1 with the error set.
@@ -129,7 +141,7 @@ class Scene {
   bool mirror_for_accel(Error& err) { return !accel_.two_level() || host_data(err) != nullptr; }
 
   Deformers::Sources deformer_sources() const { return Deformers::Sources{instance->device, instance->stream, geometry_.vertices.ptr, data}; }
-  // What update_vertices, run_animation and add_normals share.  The beginning: the mode's check, the device, the mirror where
+  // What update_vertices, run_animation, play and add_normals share.  The beginning: the mode's check, the device, the mirror where
   // `mirror_first` says so, compose() on every way out, the refit's preparation and the timer.  Then `write(stream)`, the caller's own
   // step, which puts new vertices on the device.  The tail: the normal sets the written span [first, first + count) reaches (or the set
   // `only` alone, if it is not negative by then), the derivatives, the mirror where it did not come first, and the structure's update over the span as the sets widened it.

@@ -56,10 +56,62 @@ GLZ_POST_FN void skin_vertex(Rows bones, const uint32_t j[4], float4 w, float4& 
 
 // ---- dual-quaternion blending ----
 // A bone as the kernels of this mode read it: the unit quaternion of the matrix's 3 x 3 (x, y, z, w), then the dual part (dx, dy, dz, dw)
-// that carries the translation, 32 bytes.  pack_bone_dq (skin_host.cpp, host only, once per bone per pose: it feeds the device upload and
-// the host reference alike) makes it in float64 by the rule's bone conversion and rounds to float32 at the end.
+// that carries the translation, 32 bytes.  pack_bone_dq (once per bone per pose: it feeds the device upload and the host reference
+// alike) makes it in float64 by the rule's bone conversion and rounds to float32 at the end.
 constexpr uint32_t kSkinDqBoneRows = 2;
-void pack_bone_dq(const glz_transform& b, float4 rows[kSkinDqBoneRows]);
+// The bone conversion of THE DUAL-QUATERNION RULE, of a matrix given as pack_bone's three rows: float64 throughout, the operations in
+// the specification's order, rounded to float32 at the end.  Shepperd's branches pick the largest of w, x, y, z to divide by; a
+// comparison with a NaN is false, so such a matrix takes the last branch.  Nothing is checked: a matrix that is no rotation gives the
+// rule's image of it.  One definition for the host (pack_bone_dq) and for the device, where k_clip_bones makes a played skin's table
+// (float64 sqrt and / are correctly rounded on both sides).
+GLZ_POST_FN void bone_dual_quat(const float4 m[kSkinBoneRows], float4 rows[2]) {
+  const double m00 = (double)m[0].x, m01 = (double)m[0].y, m02 = (double)m[0].z, m10 = (double)m[1].x, m11 = (double)m[1].y, m12 = (double)m[1].z, m20 = (double)m[2].x,
+               m21 = (double)m[2].y, m22 = (double)m[2].z;
+  const double tr = (m00 + m11) + m22;
+  double x, y, z, w;
+  if (tr > 0.0) {
+    const double s = 2.0 * sqrt(tr + 1.0);
+    w = s / 4.0;
+    x = (m21 - m12) / s;
+    y = (m02 - m20) / s;
+    z = (m10 - m01) / s;
+  } else if (m00 > m11 && m00 > m22) {
+    const double s = 2.0 * sqrt(((1.0 + m00) - m11) - m22);
+    w = (m21 - m12) / s;
+    x = s / 4.0;
+    y = (m01 + m10) / s;
+    z = (m02 + m20) / s;
+  } else if (m11 > m22) {
+    const double s = 2.0 * sqrt(((1.0 + m11) - m00) - m22);
+    w = (m02 - m20) / s;
+    x = (m01 + m10) / s;
+    y = s / 4.0;
+    z = (m12 + m21) / s;
+  } else {
+    const double s = 2.0 * sqrt(((1.0 + m22) - m00) - m11);
+    w = (m10 - m01) / s;
+    x = (m02 + m20) / s;
+    y = (m12 + m21) / s;
+    z = s / 4.0;
+  }
+  const double len = sqrt(((x * x + y * y) + z * z) + w * w);   // a uniform scale drops out here
+  x = x / len;
+  y = y / len;
+  z = z / len;
+  w = w / len;
+  const double tx = (double)m[0].w, ty = (double)m[1].w, tz = (double)m[2].w;
+  const double dx = 0.5 * ((tx * w + ty * z) - tz * y);
+  const double dy = 0.5 * ((ty * w + tz * x) - tx * z);
+  const double dz = 0.5 * ((tz * w + tx * y) - ty * x);
+  const double dw = -0.5 * ((tx * x + ty * y) + tz * z);
+  rows[0] = make_float4((float)x, (float)y, (float)z, (float)w);
+  rows[1] = make_float4((float)dx, (float)dy, (float)dz, (float)dw);
+}
+inline void pack_bone_dq(const glz_transform& b, float4 rows[kSkinDqBoneRows]) {
+  float4 m[kSkinBoneRows];
+  pack_bone(b, m);
+  bone_dual_quat(m, rows);
+}
 // float4 a bone of the table a skin's kernels read, by its blend mode (GLZ_SKIN_*)
 inline uint32_t bone_rows(int blend) { return blend == GLZ_SKIN_DUAL_QUATERNION ? kSkinDqBoneRows : kSkinBoneRows; }
 

@@ -362,8 +362,8 @@ int glz_renderer_geometry_update_info(glz_renderer*, glz_geometry_update_info* o
  *     t'      = t
  *   No term is skipped for a zero weight (0 x inf is NaN here too).  Weights are used as given and are not normalised.  The normal goes
  *   through M's 3 x 3 and is not renormalised (shading normalises the normal it interpolates): that is exact only for rigid bones.  Bones
- *   act in the mesh's OBJECT space, where the vertex buffer lives; the caller supplies joint_now x inverse_bind per bone -- the library
- *   knows nothing of a skeleton hierarchy.
+ *   act in the mesh's OBJECT space, where the vertex buffer lives; the caller supplies joint_now x inverse_bind per bone -- or gives the
+ *   skin a skeleton and plays clips on it (glz_renderer_play, THE CLIP RULE), and the device makes these matrices itself.
  *
  *   THE DUAL-QUATERNION RULE (a skin set to GLZ_SKIN_DUAL_QUATERNION; glz_host_skin_dq, glz_host_bone_dual_quats; one definition,
  *   glaze_amd/csrc/skin.h and skin_host.cpp, the per-vertex part compiled for host and device; the tests hold both sides to this text bit
@@ -508,6 +508,89 @@ typedef struct glz_animation {
   uint32_t                 n_poses;
 } glz_animation;
 int glz_renderer_animate(glz_renderer*, const glz_animation*, int mode);
+/* Build-defined: skeletons and clips -- the bone tables (and morph weight tables) of playing characters made ON THE DEVICE from keyframes
+ * uploaded once, so that a frame of a playing crowd sends one small record per character and no bone crosses the bus.
+ *
+ *   THE CLIP RULE (glz_renderer_play, glz_host_clip_bones; one definition, glaze_amd/csrc/clip.h, compiled for host and device; the tests
+ *   hold both sides to this text bit for bit).  float32 throughout, + - x, one 1 / sqrt per bone (both operations correctly rounded), no
+ *   contraction into fused multiply-adds, the operations in exactly this order.  A skeleton has n_bones bones; parents[b] is -1 for a root,
+ *   else below b.  A clip has n_keys keys at times[k], strictly ascending; key k holds, per bone, a translation (3), a rotation (x, y, z,
+ *   w; used as given, not normalised) and a scale (3), and optionally one weight per morph target.  Matrices are 3 x 4, [r][c].
+ *     1. key choice (on the host, in float32, for the reference and the device alike; the kernel receives the triple, never t):
+ *          t <= times[0]:     (k0, k1, u) = (0, 0, 0)
+ *          t >= times[last]:  (k0, k1, u) = (last, last, 0)
+ *          else:              k0 = the largest k with times[k] <= t;  k1 = k0 + 1;  u = (t - times[k0]) / (times[k1] - times[k0])
+ *     2. lerp(a, b) = a + u * (b - a)  per component, for translation, scale and morph weights.  No term is skipped: with k0 == k1 a finite
+ *        value comes back as it is, an infinity becomes NaN.
+ *     3. rotation, a normalised lerp with a hemisphere step: a, b the rotations of keys k0, k1
+ *          dot = ((a.x * b.x + a.y * b.y) + a.z * b.z) + a.w * b.w;   b enters negated if dot < 0 (a dot of -0, +0 or NaN keeps it)
+ *          Q = lerp(a, +-b);   nn = ((Q.x * Q.x + Q.y * Q.y) + Q.z * Q.z) + Q.w * Q.w;   inv = 1 / sqrt(nn);   q = Q * inv
+ *        nn == 0 is NOT special-cased.
+ *     4. local matrix from (t, q, s), with xx = q.x * q.x, xy = q.x * q.y, ... wz = q.w * q.z:
+ *          R00 = 1 - 2 * (yy + zz)   R01 = 2 * (xy - wz)       R02 = 2 * (xz + wy)
+ *          R10 = 2 * (xy + wz)       R11 = 1 - 2 * (xx + zz)   R12 = 2 * (yz - wx)
+ *          R20 = 2 * (xz - wy)       R21 = 2 * (yz + wx)       R22 = 1 - 2 * (xx + yy)
+ *          L[r][c] = R[r][c] * s[c]  (c in 0..2; without a scale track s = 1 and the product is still formed),   L[r][3] = t[r]
+ *     5. affine product C = A o B:
+ *          C[r][c] = (A[r][0] * B[0][c] + A[r][1] * B[1][c]) + A[r][2] * B[2][c]                      c in 0..2
+ *          C[r][3] = ((A[r][0] * B[0][3] + A[r][1] * B[1][3]) + A[r][2] * B[2][3]) + A[r][3]
+ *     6. hierarchy:  W[b] = root o L[b] for a root, else W[parents[b]] o L[b] -- the product always runs down the chain and is never
+ *        regrouped, so the order bones are evaluated in does not reach the bits.   The bone is B[b] = W[b] o inverse_bind[b].
+ *     7. table: for a linear skin the three rows of B[b] (what glz_renderer_pose_skins uploads for that matrix); for a skin in
+ *        GLZ_SKIN_DUAL_QUATERNION mode the BONE CONVERSION above applied to B[b] -- float64, in that text's order, rounded to float32 at
+ *        the end -- which the device computes with the same definition the host does.
+ *   CONSEQUENCE: glz_renderer_play(clip, t) leaves the vertices glz_renderer_pose_skins leaves when given glz_host_clip_bones(..., t), bit
+ *   for bit, in either blend mode; with a weight track, those glz_renderer_animate leaves when given those bones and the lerped weights.
+ *   Interpolation is nlerp, not slerp: keys are expected to be dense enough.  Keys are uniform across bones, as in a baked clip.
+ *
+ * glz_renderer_add_skeleton returns the skeleton's id (>= 0; ids count up and are never reused).  Skeletons and clips belong to the SCENE
+ * object, as skins do, and every device of set_devices gets them under the same ids.  The level table (bones grouped by depth) is made
+ * on the host; it, parents, inverse_bind and root are uploaded once, and the skeleton's world and bone tables are allocated on the
+ * device (the bone table for the larger blend mode, so glz_renderer_set_skin_blend reallocates nothing).  Only the upper 3 x 4 of
+ * inverse_bind and root is read; root is what roots are multiplied under, so the skin's object space may differ from the skeleton's.
+ * GLZ_E_ARG (nothing changes): a null pointer, an unknown skin, n_bones not the skin's, a skin that already has a skeleton, a parent
+ * that is neither -1 nor below its bone.  glz_renderer_remove_skeleton frees it AND its clips; glz_renderer_remove_skin of a skin that
+ * still has a skeleton is refused (GLZ_E_ARG), and so is glz_renderer_remove_morph of a morph that a clip's weight track still drives.
+ * glz_renderer_add_clip returns the clip's id (>= 0, counting up, never reused); the clip is uploaded once.  scales == NULL: every scale
+ * is 1.  morph_weights (n_keys x n_targets) is allowed only when the skeleton's skin carries an attached morph with n_targets targets;
+ * NULL (with n_targets 0): the clip does not drive the morph.  GLZ_E_ARG (nothing changes): a null pointer, an unknown skeleton,
+ * n_keys == 0, times not finite or not strictly ascending, null translations or rotations, a weight track without such a morph or with
+ * another target count.  glz_renderer_remove_clip frees a clip. */
+typedef struct glz_skeleton {
+  int                  skin;           /* ignored by glz_host_clip_bones */
+  uint32_t             n_bones;        /* the skin's */
+  const int32_t*       parents;        /* n_bones: -1 a root, else < the bone's own index */
+  const glz_transform* inverse_bind;   /* n_bones */
+  glz_transform        root;
+} glz_skeleton;
+typedef struct glz_clip {
+  int          skeleton;        /* ignored by glz_host_clip_bones */
+  uint32_t     n_keys;          /* >= 1 */
+  const float* times;           /* n_keys, finite, strictly ascending */
+  const float* translations;    /* n_keys x n_bones x 3 */
+  const float* rotations;       /* n_keys x n_bones x 4: (x, y, z, w) */
+  const float* scales;          /* n_keys x n_bones x 3, or NULL */
+  const float* morph_weights;   /* n_keys x n_targets, or NULL */
+  uint32_t     n_targets;
+} glz_clip;
+int glz_renderer_add_skeleton(glz_renderer*, const glz_skeleton*);
+int glz_renderer_remove_skeleton(glz_renderer*, int skeleton);
+int glz_renderer_add_clip(glz_renderer*, const glz_clip*);
+int glz_renderer_remove_clip(glz_renderer*, int clip);
+/* Plays clips and updates the structure ONCE.  One launch of k_clip_bones makes the bone table of every named clip's skeleton, in its
+ * skin's blend layout, and the weight table of every clip that has a weight track; then each skin is deformed from its bind pose by the
+ * kernel glz_renderer_animate would use -- the fused morph kernel where the clip has a weight track -- reading those tables where they
+ * are.  The only upload is one small table for the whole call: per play the clip, (k0, k1, u) and the blend mode.  Everything
+ * glz_renderer_animate promises holds: idle first, accumulation restarts, the structure is updated once (`mode`: GLZ_GEOMETRY_*) over the
+ * span from the lowest to the highest vertex written, every device of set_devices follows, normal sets whose reach overlaps the span
+ * run afterwards, glz_renderer_geometry_update_info describes it.  Nothing is kept between calls: every call starts from the bind pose.
+ * glz_renderer_pose_skins and glz_renderer_animate keep working on a skin that has a skeleton.  GLZ_E_ARG (the scene is untouched): a
+ * null pointer or n_plays == 0, an unknown clip, two plays whose clips belong to the same skeleton, a non-finite time, an unknown mode. */
+typedef struct glz_play {
+  int   clip;
+  float time;
+} glz_play;
+int glz_renderer_play(glz_renderer*, const glz_play* plays, uint32_t n_plays, int mode);
 /* Build-defined: shading normals recomputed on the device from the positions it holds -- after a pose, a morph or new positions from the
  * caller -- so that a deformed surface is shaded with the normals of the shape it has now.  Opt-in per vertex range: without a normal set
  * nothing changes.
@@ -968,6 +1051,14 @@ int glz_debug_motion_timing_from(glz_renderer*, const glz_previous_state*, float
  * one that is not timed, divided by reps.  The pose is checked as glz_renderer_pose_skins checks it.  A skin in
  * GLZ_SKIN_DUAL_QUATERNION mode is timed with its own kernel, k_skin_dq (and k_morph_skin_dq below, at 32 bytes a bone). */
 int glz_debug_skin_timing(glz_renderer*, const glz_pose* pose, uint32_t reps, float* kernel_ms_out);
+/* k_clip_bones alone for ONE play (checked as glz_renderer_play checks it): the bone table as the device holds it afterwards, in the
+ * skin's current blend layout -- rows_out: 3 x n_bones float4 for a linear skin (row after row of each bone), 2 x n_bones in
+ * GLZ_SKIN_DUAL_QUATERNION mode -- and, for a clip with a weight track, its n_targets weights (weights_out may be NULL).  No vertex is
+ * written: with it, a failing vertex test says which stage failed. */
+int glz_debug_clip_bones(glz_renderer*, const glz_play* play, float* rows_out, float* weights_out);
+/* k_clip_bones alone, one launch for all the plays, timed as glz_debug_skin_timing times k_skin; the plays are checked as
+ * glz_renderer_play checks them, the table of (clip, k0, k1, u) goes up once, outside the timed span. */
+int glz_debug_clip_timing(glz_renderer*, const glz_play* plays, uint32_t n_plays, uint32_t reps, float* kernel_ms_out);
 /* The morph kernels alone, into a scratch buffer (the scene is untouched), timed as glz_debug_skin_timing times k_skin.  `one` names one
  * morph and no pose -- k_morph on it, from the skin's bind pose if it is attached -- or one attached morph and its skin's pose --
  * k_morph_skin.  bytes_out (may be NULL): the bytes one launch moves by the layout's own count -- per vertex 32 in, 32 out and 4 of row
@@ -1109,6 +1200,15 @@ int glz_host_skin(const glz_vertex* bind, const uint16_t* joints, const float* w
 int glz_host_skin_dq(const glz_vertex* bind, const uint16_t* joints, const float* weights, uint64_t n, const glz_transform* bones, uint32_t n_bones,
                      glz_vertex* out);
 int glz_host_bone_dual_quats(const glz_transform* bones, uint32_t n, float* out8);
+/* THE CLIP RULE on host arrays, no device: the reference k_clip_bones is compared with bit for bit.  The structs of
+ * glz_renderer_add_skeleton / glz_renderer_add_clip, their `skin` / `skeleton` ids ignored and n_bones the skeleton's own.  bones_out:
+ * n_bones matrices B[b], column-major, with the fourth row (0, 0, 0, 1) -- what glz_renderer_pose_skins takes.  weights_out: the
+ * clip's n_targets lerped weights; may be NULL, and is not written for a clip without a weight track.  GLZ_E_ARG: a null pointer,
+ * n_bones == 0, a parent that is neither -1 nor below its bone, n_keys == 0, times not finite or not strictly ascending, null
+ * translations or rotations, a weight track with n_targets == 0, a non-finite time. */
+typedef glz_skeleton glz_skeleton_desc;
+typedef glz_clip glz_clip_desc;
+int glz_host_clip_bones(const glz_skeleton_desc* skeleton, const glz_clip_desc* clip, float time, glz_transform* bones_out, float* weights_out);
 /* THE MORPH RULE (glz_renderer_add_morph) on host arrays, no device: the reference k_morph is compared with bit for bit; it runs through
  * the same layout packer as glz_renderer_add_morph.  base / out: n vertices (out may be base itself); targets, n_targets: as glz_morph
  * has them, over n vertices; weights: n_targets.  GLZ_E_ARG: a null pointer with n > 0, and what glz_renderer_add_morph refuses of a
