@@ -182,7 +182,9 @@ struct ShadowSource {
   uint32_t cap;
   uint32_t lid;            // per-lane: owning pixel and contribution of the ray in flight
   float4 contrib;
+  uint32_t base = 0u;      // wave-uniform: ray i of a call is queue ray base + i (k_trace: the first ray of a chunk drawn from the pool; 0 everywhere else)
   __device__ __forceinline__ bool load(uint32_t i, vec3& o, vec3& d, float& tmin, float& tmax) {
+    i += base;
     uint32_t shard = 0;
 #pragma unroll
     for (uint32_t k = 1; k < kQueueShards; ++k) shard += i >= start[k] ? 1u : 0u;
@@ -210,5 +212,12 @@ struct ShadowSink {
 // every tracing kernel clears the counters of the queue set the k_shade that follows fills (shade_set)
 __device__ __forceinline__ void clear_next_queue_set(const LaunchArgs& A) {
   if (blockIdx.x == 0 && threadIdx.x < kQueueShards) A.st.queue_count[A.shade_set * kQueueSetWords + threadIdx.x * kCounterStride] = 0;
+}
+// k_trace, both the product's and the counting one: with them the head of that set's shadow-group pool (kernels.h pool_head_word) -- the
+// k_trace that drains the set in the next launch draws from it, this one draws from the other set's.  The other tracers need not: which
+// tracer runs a chain's launches only changes with a reallocation, which restarts (Renderer::reset_buffers clears both heads), or with
+// the work counters, which swap k_trace for its own counting instantiation.
+__device__ __forceinline__ void clear_next_pool_head(const LaunchArgs& A) {
+  if (blockIdx.x == 0 && threadIdx.x == kQueueShards) A.st.queue_count[pool_head_word(A.shade_set)] = 0;
 }
 }  // namespace glz

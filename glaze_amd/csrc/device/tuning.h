@@ -6,9 +6,12 @@
 //   switch                 default  what
 //   ---------------------  -------  ----------------------------------------------------------------------------------------------
 //   GLZ_TRACE_WAVES           6     waves per SIMD k_trace is compiled for (80 VGPRs)
-//   GLZ_TRACE_SPLIT_NUM / _DEN  8 / 10  k_trace: with more groups than waves, waves take groups of ONE kind (closest-hit or shadow); the shadow waves' share relative to the shadow groups' share
-//                                   (9 / 10 while shadow rays walked nearest first.  Far first, 5 / 6 / 7 / 8 / 9 over 10: the atrium 0.700 / 0.675 / 0.677 / 0.688 / 0.696 ms per launch, but
-//                                   mattest.glaze, whose shadow rays are mostly unoccluded and no cheaper than before, 0.401 at 7 against 0.389 / 0.388 at 8 / 9: 8 is the smallest value that costs it nothing)
+//   GLZ_TRACE_SPLIT_NUM / _DEN  6 / 10  k_trace: with more groups than waves, waves take groups of ONE kind (closest-hit or shadow); the shadow waves' share relative to the shadow groups' share
+//                                   (9 / 10 while shadow rays walked nearest first, 8 / 10 after.  With the plan of device/trace_split.h, 5 / 6 / 7 / 8 over 10: the atrium 0.647 / 0.623 / 0.622 / 0.630 ms
+//                                   per launch, mattest.glaze 0.370 / 0.370 / 0.386 / 0.372: 6 is the best that costs mattest nothing; profiles/shadow_pool_sweep.txt)
+//   GLZ_TRACE_POOL_NUM / _DEN   0 / 1   k_trace: the fraction of the shadow groups left undealt, for whichever wave finishes its fixed share first to draw (0: none, everything is dealt).
+//                                   1/8, 1/4, 1/2 at every static share: the atrium +1 ... +7 %, a drawn chunk drains on its own (EXPERIMENTS.md, "A pool of shadow groups")
+//   GLZ_TRACE_POOL_CHUNK        2       k_trace: groups a wave draws from the pool at a time (1 / 2 / 4: 4 costs mattest.glaze 5 - 17 %, its last chunks end the kernel late)
 //   GLZ_ANY_FAR_FIRST         1     any-hit (shadow) rays enter the child with the LARGEST entry distance and keep the nearest for last (trace_wave); 0: nearest first, as closest-hit rays
 //   GLZ_COUNT_ANY_FAR_FIRST   0     tools only: the counting kernels walk any-hit rays in the product's order too (tools/gpu_diag.py); off, their counts are the oracle's walk
 //   GLZ_TRACE_PREFETCH        0     k_trace: the next node's loads issued as soon as the node is known (as k_path does; wants 16 more registers)
@@ -33,10 +36,19 @@
 #define GLZ_TRACE_WAVES 6
 #endif
 #ifndef GLZ_TRACE_SPLIT_NUM
-#define GLZ_TRACE_SPLIT_NUM 8
+#define GLZ_TRACE_SPLIT_NUM 6
 #endif
 #ifndef GLZ_TRACE_SPLIT_DEN
 #define GLZ_TRACE_SPLIT_DEN 10
+#endif
+#ifndef GLZ_TRACE_POOL_NUM
+#define GLZ_TRACE_POOL_NUM 0
+#endif
+#ifndef GLZ_TRACE_POOL_DEN
+#define GLZ_TRACE_POOL_DEN 1
+#endif
+#ifndef GLZ_TRACE_POOL_CHUNK
+#define GLZ_TRACE_POOL_CHUNK 2
 #endif
 #ifndef GLZ_ANY_FAR_FIRST
 #define GLZ_ANY_FAR_FIRST 1

@@ -5,6 +5,7 @@
 
 #include <vector>
 
+#include "device/trace_split.h"
 #include "device/types.h"
 #include "glaze_abi.h"
 #include "device_buffer.h"
@@ -160,6 +161,7 @@ struct LaunchArgs {
   uint32_t do_closest, do_shadow;
   uint32_t shade_set;        // which of the two shadow-queue counter sets this launch's k_shade fills (the other one is drained)
   float shadow_mark;         // FrameData::update_mark of the launch that queued the shadow rays
+  TraceSplitTuning split;    // k_trace: how the waves divide the two kinds of group (device/trace_split.h; the defaults of device/tuning.h unless GLAZE_TRACE_SPLIT says otherwise)
 };
 // The launches one k_path call runs (kernels_path.hip): what differs between launches, by value in the kernel arguments (12 bytes a
 // launch next to the 880 of LaunchArgs: 192 launches stay inside the 4 KB the arguments may take).  Long batches matter: the kernel
@@ -176,6 +178,10 @@ struct PathBatch {
 };
 constexpr uint32_t kTraceBlock = 256;          // threads per block of the render kernels (4 waves)
 constexpr uint32_t kQueueSetWords = 8 * 32;   // 8 shard counters, 128 bytes apart
+// PathState::queue_count: the two counter sets, then per set the head of its shadow-group pool (device/trace_split.h), each on a 128-byte line of its own
+constexpr uint32_t kPoolHeadStride = 32;
+constexpr uint32_t kQueueCountWords = 2 * kQueueSetWords + 2 * kPoolHeadStride;
+constexpr uint32_t pool_head_word(uint32_t set) { return 2 * kQueueSetWords + set * kPoolHeadStride; }
 
 // persistent grid of k_trace / k_trace_tl / (wide8) k_trace8 (device must be current); wide8: the walk over the 8-wide nodes, flattened scenes without work counters
 uint32_t trace_grid_blocks(uint32_t n_local_pixels, bool counting, bool two_level, bool wide8 = false);

@@ -277,6 +277,7 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE_WAVES) k_trace(const LaunchA
   int* aux = wave_aux(s_aux, threadIdx.x >> 6);
   int* links = wave_links(s_aux, threadIdx.x >> 6);
   clear_next_queue_set(A);
+  clear_next_pool_head(A);
   // counting build: the alpha tests' texture fetches are tallied through a copy of the scene that points at this thread's registers
   unsigned long long tex_tally[4] = {0ull, 0ull, 0ull, 0ull};
   DeviceScene counted_scene;
@@ -285,60 +286,82 @@ __global__ void __launch_bounds__(kBlock, GLZ_TRACE_WAVES) k_trace(const LaunchA
     counted_scene.tex_counter = tex_tally;
   }
   const DeviceScene& TS = COUNT ? counted_scene : A.scene;
-  // Waves that specialise: with more 64-ray groups than waves, a share of the waves -- GLZ_TRACE_SPLIT_NUM / _DEN (device/tuning.h)
-  // of the shadow groups' share of all groups, spread evenly over the grid wave by wave -- takes only shadow groups and the others only
-  // closest-hit groups: a wave then drains ONCE, at the end of the kernel, instead of once per kind, and a CU holds waves of both kinds at
-  // all times.  With fewer groups than waves every group gets a wave of its own either way.  The counting kernels keep the two passes per wave.
-  uint32_t split_closest = A.do_closest, split_shadow = A.do_shadow, split_wave_c = wave_index(), split_waves_c = wave_count(), split_wave_s = 0, split_waves_s = 0;
-  bool split = false;
+  // Waves that specialise: with more 64-ray groups than waves, a share of the waves, spread evenly over the grid wave by wave, takes only
+  // shadow groups and the others only closest-hit groups: a CU holds waves of both kinds at all times.  With fewer groups than waves every
+  // group gets a wave of its own either way.  The counting kernels keep the two passes per wave.
+  // The division is device/trace_split.h's (one definition for host and device): the shadow waves' number, which waves they are, the shadow
+  // rays [0, n_static) that are dealt to them, and the POOL [n_static, n_sh): chunks of whole groups that a wave of EITHER kind draws, one
+  // returning atomic add per chunk, once its fixed share is done -- whichever kind of wave finishes first takes what is left, so neither
+  // kind's fixed share has to be guessed right for every scene.  A wave that draws drains a second time, when it would otherwise be idle.
+  // (Measured, that drain costs more than the idle time it fills: the default pool share is 0, everything is dealt -- device/tuning.h.)
+  // Everything that steers the loops below is wave-uniform and said to be so (v_readfirstlane; see trace_wave on why the compiler must know).
+  const auto uniform = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+  const uint32_t* counts = A.st.queue_count + (A.shade_set ^ 1u) * kQueueSetWords;
+  const uint32_t closest_groups = A.do_closest ? (A.map.n_local_pixels + 63u) / 64u : 0u;
+  uint32_t split_closest = A.do_closest, split_wave_c = wave_index(), split_waves_c = wave_count();
+  // the shadow side's first trip: when the waves do not specialise, the shadow groups are dealt out starting at the wave after the one that
+  // received the last closest-hit group: with fewer groups than waves (a small tile share per GPU) every group of either kind gets a
+  // wave of its own, with more the per-wave totals stay level
+  uint32_t sh_trip = A.do_shadow, sh_total = 0xFFFFFFFFu /* all of them: set below */, sh_waves = wave_count(), sh_wave = (wave_index() + sh_waves - closest_groups % sh_waves) % sh_waves, sh_base = 0u;
+  TraceSplit plan{0u, 0u, 0u, 0u, 0u};
   if (!COUNT && A.do_closest && A.do_shadow) {
-    const uint32_t* counts0 = A.st.queue_count + (A.shade_set ^ 1u) * kQueueSetWords;
     uint32_t n_sh = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < kQueueShards; ++k) n_sh += counts0[k * kCounterStride];
-    const uint32_t gc = (A.map.n_local_pixels + 63u) / 64u, gs = (n_sh + 63u) / 64u, nw = wave_count();
-    if (gc + gs > nw && gs > 0u) {
-      split = true;
-      uint32_t ws = (uint32_t)(((unsigned long long)nw * gs * GLZ_TRACE_SPLIT_NUM) / ((unsigned long long)gc * GLZ_TRACE_SPLIT_DEN + (unsigned long long)gs * GLZ_TRACE_SPLIT_NUM));
-      ws = ws < 1u ? 1u : (ws > nw - 1u ? nw - 1u : ws);
-      const uint32_t w = wave_index();
-      const uint32_t s_before = (uint32_t)(((unsigned long long)w * ws) / nw), s_after = (uint32_t)(((unsigned long long)(w + 1u) * ws) / nw);
-      const bool is_shadow = s_after > s_before;   // the same in all lanes of a wave
-      split_closest = is_shadow ? 0u : 1u;
-      split_shadow = is_shadow ? 1u : 0u;
-      split_wave_c = w - s_before;    // this wave's number among the closest-hit waves ...
-      split_waves_c = nw - ws;
-      split_wave_s = s_before;        // ... or among the shadow waves
-      split_waves_s = ws;
+    for (uint32_t k = 0; k < kQueueShards; ++k) n_sh += counts[k * kCounterStride];
+    plan = trace_split_plan(closest_groups, uniform(n_sh), wave_count(), A.split);
+    if (plan.split) {
+      const TraceWaveRole role = trace_split_role(plan, wave_index(), wave_count());   // the same in all lanes of a wave
+      split_closest = role.is_shadow ? 0u : 1u;
+      split_wave_c = role.index;    // this wave's number among the closest-hit waves (unused by a shadow wave)
+      split_waves_c = wave_count() - plan.ws;
+      sh_trip = role.is_shadow;     // the static sequence: shadow waves only
+      sh_total = plan.n_static;
+      sh_wave = role.index;         // ... or among the shadow waves
+      sh_waves = plan.ws;
     }
   }
+  // what of the plan the shadow side needs behind the closest-hit pass: the pool's first ray, the chunk size, the number of chunks
+  const TraceSplit pool{plan.split, 0u, uniform(plan.n_static), uniform(plan.chunk_groups), uniform(plan.n_chunks)};
+  split_closest = uniform(split_closest);
   if (split_closest) {
     TraceTally tally;
     ClosestSource src{A, A.frame, tally, 0u};
     ClosestSink sink{A};
-    trace_wave<false, COUNT, false, GLZ_TRACE_PREFETCH != 0, false, ALPHA>(TS, src, sink, &s_stack[threadIdx.x], aux, links, (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, A.map.n_local_pixels, split_wave_c,
-                                                         split_waves_c, tally);
+    trace_wave<false, COUNT, false, GLZ_TRACE_PREFETCH != 0, false, ALPHA>(TS, src, sink, &s_stack[threadIdx.x], aux, links, (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, A.map.n_local_pixels, uniform(split_wave_c),
+                                                         uniform(split_waves_c), tally);
     if (COUNT) flush_counters(A.counters, false, tally);
   }
   GLZ_WAVE_STAMP(1);
-  if (split_shadow) {
+  if (A.do_shadow) {
     // prefix sums of the eight shard counts (final: the k_shade that filled them has completed)
-    const uint32_t* counts = A.st.queue_count + (A.shade_set ^ 1u) * kQueueSetWords;
     uint32_t start[kQueueShards + 1];
     start[0] = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < kQueueShards; ++k) start[k + 1] = start[k] + counts[k * kCounterStride];
+    for (uint32_t k = 0; k < kQueueShards; ++k) start[k + 1] = uniform(start[k] + counts[k * kCounterStride]);
+    const uint32_t n_sh = start[kQueueShards];
+    if (!pool.split) sh_total = n_sh;
     TraceTally tally;
     ShadowSource src{A, start, queue_capacity(A.map.n_local_pixels), 0u, make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
     ShadowSink sink{A, src};
-    // When the waves do not specialise, the shadow groups are dealt out starting at the wave after the one that received the last
-    // closest-hit group: with fewer groups than waves (a small tile share per GPU) every group of either kind gets a wave of its own,
-    // with more the per-wave totals stay level.
-    uint32_t n_waves = wave_count();
-    const uint32_t closest_groups = A.do_closest ? (A.map.n_local_pixels + 63u) / 64u : 0u;
-    uint32_t wave = (wave_index() + n_waves - closest_groups % n_waves) % n_waves;
-    if (split) { wave = split_wave_s; n_waves = split_waves_s; }
-    trace_wave<true, COUNT, false, GLZ_TRACE_PREFETCH != 0, false, ALPHA>(TS, src, sink, &s_stack[threadIdx.x], aux, links, (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, start[kQueueShards], wave, n_waves, tally);
+    // ONE trace_wave in the kernel's code: the first trip is the static sequence, every later trip a chunk drawn from the pool.  Bounded: the
+    // head only grows, so a wave draws at most n_chunks + 1 times, and nothing waits for another wave.
+    sh_trip = uniform(sh_trip); sh_total = uniform(sh_total); sh_wave = uniform(sh_wave); sh_waves = uniform(sh_waves);
+    for (;;) {
+      if (!sh_trip) {
+        if (pool.n_chunks == 0u) break;
+        uint32_t c = 0u;
+        if ((threadIdx.x & 63u) == 0u) c = atomicAdd(A.st.queue_count + pool_head_word(A.shade_set ^ 1u), 1u);
+        c = uniform(c);   // lane 0's
+        if (c >= pool.n_chunks) break;
+        sh_base = uniform(trace_split_chunk_first(pool, c));
+        sh_total = uniform(trace_split_chunk_rays(pool, c, n_sh));   // the last chunk is short
+        sh_wave = 0u;
+        sh_waves = 1u;
+      }
+      sh_trip = 0u;
+      src.base = sh_base;
+      trace_wave<true, COUNT, false, GLZ_TRACE_PREFETCH != 0, false, ALPHA>(TS, src, sink, &s_stack[threadIdx.x], aux, links, (LdsNodePtr)s_top, A.st.overflow, A.st.overflow_depth, sh_total, sh_wave, sh_waves, tally);
+    }
     if (COUNT) flush_counters(A.counters, true, tally);
   }
   if (COUNT) flush_tex_tallies(A.counters->trace_tex, tex_tally);

@@ -3,8 +3,11 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+
+#include "device/tuning.h"
 
 namespace glz {
 
@@ -140,7 +143,7 @@ bool Renderer::allocate(Error& err) {
     c->grid_path = path_mode_ ? path_grid_blocks(m.n_local_pixels, scene_->dev) : 0u;
     // traversal spill: one slot of `od` entries per lane of the largest of the persistent grids
     if (!hip_ok(c->overflow.alloc((size_t)std::max(std::max(std::max(c->grid, c->grid_counting), c->grid_path), c->grid8) * kTraceBlock * od), "alloc traversal spill", err)) return false;
-    if (!hip_ok(c->queue_count.alloc(2 * kQueueSetWords), "alloc queue counters", err)) return false;
+    if (!hip_ok(c->queue_count.alloc(kQueueCountWords), "alloc queue counters", err)) return false;
     if (!hip_ok(c->path_cost.alloc(8 + n / 64 + 1), "alloc path costs", err)) return false;
     if (!hip_ok(hipMemsetAsync(c->path_cost.ptr, 0, sizeof(uint32_t) * (8 + n / 64 + 1), c->stream), "clear path costs", err)) return false;
     chains_.push_back(std::move(c));
@@ -169,7 +172,7 @@ bool Renderer::reset_buffers(Error& err) {
     DeviceBuffer<float4>* zero[] = {&c.ray_o, &c.ray_d, &c.imp[0], &c.imp[1], &c.imp[2], &c.imp[3], &c.cumulative, &c.result, &c.contrib};
     for (auto* b : zero)
       if (bytes && !hip_ok(hipMemsetAsync(b->ptr, 0, bytes, c.stream), "clear path state", err)) return false;
-    if (!hip_ok(hipMemsetAsync(c.queue_count.ptr, 0, sizeof(uint32_t) * 2 * kQueueSetWords, c.stream), "clear queue counters", err)) return false;
+    if (!hip_ok(hipMemsetAsync(c.queue_count.ptr, 0, sizeof(uint32_t) * kQueueCountWords, c.stream), "clear queue counters", err)) return false;
     c.shadow_pending = false;   // queued shadow rays of the abandoned frame are dropped with it
     c.trace_ms = c.shade_ms = c.flush_ms = c.path_ms = 0;
     for (auto& s : c.pending_events) c.free_events.push_back(s);
@@ -209,6 +212,19 @@ void Renderer::fill_args(const Chain& c, LaunchArgs& a) const {
   a.do_closest = a.do_shadow = 0;
   a.shade_set = c.pending_set ^ 1u;
   a.shadow_mark = c.pending_mark;
+  a.split = cfg_.trace_split;
+}
+
+// The defaults of device/tuning.h, or GLAZE_TRACE_SPLIT="<static num>/<den>,<pool num>/<den>,<chunk groups>" (tuning and tests: one
+// library serves every setting; the images do not depend on it).  A value that does not parse leaves the defaults.
+TraceSplitTuning trace_split_from_env() {
+  TraceSplitTuning t{GLZ_TRACE_SPLIT_NUM, GLZ_TRACE_SPLIT_DEN, GLZ_TRACE_POOL_NUM, GLZ_TRACE_POOL_DEN, GLZ_TRACE_POOL_CHUNK};
+  unsigned v[5];
+  const char* s = getenv("GLAZE_TRACE_SPLIT");
+  if (s && sscanf(s, "%u/%u,%u/%u,%u", &v[0], &v[1], &v[2], &v[3], &v[4]) == 5 && v[0] >= 1 && v[1] >= 1 && v[3] >= 1 && v[2] <= v[3] && v[4] >= 1 &&
+      v[0] <= 65535 && v[1] <= 65535 && v[3] <= 65535 && v[4] <= 65535)
+    t = TraceSplitTuning{v[0], v[1], v[2], v[3], v[4]};
+  return t;
 }
 
 void Renderer::resolve_events(Chain& c) {

@@ -16,6 +16,8 @@
 
 namespace glz {
 
+TraceSplitTuning trace_split_from_env();   // renderer.cpp
+
 class Renderer {
  public:
   static Renderer* create(Instance* inst, std::shared_ptr<Scene> scene /* may be null: empty scene */, uint32_t w, uint32_t h, Error& err);
@@ -151,6 +153,7 @@ class Renderer {
     int node_width = getenv("GLAZE_NODE_WIDTH") ? atoi(getenv("GLAZE_NODE_WIDTH")) : 0;   // set_node_width
     bool counting = false;
     bool profile_kernels = true;
+    TraceSplitTuning trace_split = trace_split_from_env();   // LaunchArgs::split of every launch: read once, here
   } cfg_;
   host::SeedStream rng_;
   host::WorkScheduler sched_;

@@ -9,6 +9,7 @@ FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -I. -I../../include
 /opt/rocm/bin/hipcc $FLAGS "$@" ${RENDER_FLAGS--mllvm -disable-machine-licm -fno-slp-vectorize} -c kernels_render.hip -o build_var/kr_$NAME.o &
 /opt/rocm/bin/hipcc $FLAGS "$@" ${PATH_FLAGS--mllvm -disable-machine-licm -fno-slp-vectorize} -c kernels_path.hip -o build_var/kp_$NAME.o &
 wait
-/opt/rocm/bin/hipcc -shared -fPIC -o ../../variants/libglaze_hip_$NAME.so build/abi.o build/abi_debug.o build/parser.o build/serializer.o build/converter.o build/scene.o build/instance_boxes.o build/textures.o build/shading_tables.o build/accel.o build/renderer.o build/post_stage.o build/device_group.o build/denoise_host.o build/bvh_sah.o build/xz_dec.o build/xz_enc.o build/png_dec.o build/png_enc.o build/jpeg.o build/kernels_build.o build/kernels_build_sah.o build/kernels_records.o build/kernels_tlas.o build/kernels_post.o build/kernels_debug.o build_var/kr_$NAME.o build_var/kp_$NAME.o -lz -lpthread -ldl
+# every object of the in-tree build (make) but the two that were just compiled
+/opt/rocm/bin/hipcc -shared -fPIC -o ../../variants/libglaze_hip_$NAME.so $(ls build/*.o | grep -v -e build/kernels_render.o -e build/kernels_path.o) build_var/kr_$NAME.o build_var/kp_$NAME.o -lz -lpthread -ldl
 rm -f build_var/kr_$NAME.o build_var/kp_$NAME.o   # (the snapshot gpurun sends would carry them)
 echo built variants/libglaze_hip_$NAME.so

@@ -1,4 +1,8 @@
-"""When the waves of one k_trace finish (variant built with -DGLZ_WAVE_TIMES): share of the frame WORLD, one chain."""
+"""When the waves of one k_trace finish (variant built with -DGLZ_WAVE_TIMES): share of the frame WORLD, one chain.
+SCENE=atrium (1920 x 1080, the bench workload) or mattest (tests/golden/mattest.glaze at 1024 x 1024), depth 8.  With LAUNCHES=2 the kernel
+looked at also traces the shadow rays of the launch before, and where its waves specialise the two kinds are told apart -- a shadow wave
+has no closest-hit pass, its second stamp follows its first within the kernel's prologue -- and listed each on its own: when the first, the median and the last
+wave of the kind end, as fractions of the kernel's duration, and the wave-slot time left idle between a wave's end and the kernel's."""
 import ctypes, os, sys
 import numpy as np
 sys.path.insert(0, ".")
@@ -6,8 +10,12 @@ import glaze_amd
 from glaze_amd.scenes import atrium_scene
 lib = ctypes.CDLL(os.environ["GLAZE_HIP_LIB"])
 inst = glaze_amd.RayTraceInstance.new()
-scene = glaze_amd.RayTraceScene.from_desc(inst, atrium_scene())
-r = glaze_amd.RayTraceRenderer.new(inst, scene, 1920, 1080)
+if os.environ.get("SCENE", "atrium") == "mattest":
+    scene = glaze_amd.RayTraceScene.new(inst, glaze_amd.parse(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "mattest.glaze")))
+    r = glaze_amd.RayTraceRenderer.new(inst, scene, 1024, 1024)
+else:
+    scene = glaze_amd.RayTraceScene.from_desc(inst, atrium_scene())
+    r = glaze_amd.RayTraceRenderer.new(inst, scene, 1920, 1080)
 r.set_depth(8)
 r.enable_counters(False, False)
 for world in [int(w) for w in os.environ.get("WORLDS", "8,1").split(",")]:
@@ -25,6 +33,16 @@ for world in [int(w) for w in os.environ.get("WORLDS", "8,1").split(",")]:
         end = np.sort(us[:, 2])
         print("world %d rep %d: %d waves, start spread %.1f us, closest done p50/p90/p99/max %.1f/%.1f/%.1f/%.1f us, end p10/p50/p75/p90/p95/p99/max %.1f/%.1f/%.1f/%.1f/%.1f/%.1f/%.1f us" % (
             world, rep, len(t), us[:, 0].max(), *np.percentile(us[:, 1], [50, 90, 99, 100]), *np.percentile(end, [10, 50, 75, 90, 95, 99, 100])), flush=True)
+        # the two kinds of wave of a kernel whose waves specialise (kernels_render.hip k_trace): ends as fractions of the kernel, idle wave-slot time
+        length = us[:, 2].max()
+        shadow = (us[:, 1] - us[:, 0]) < 20.0   # the prologue (staged tree top, the plan) takes a few us, a closest-hit pass of several groups hundreds
+        if shadow.any() and not shadow.all():
+            idle = length - us[:, 2]
+            for name, sel in (("closest-hit", ~shadow), ("shadow", shadow)):
+                e = us[sel, 2] / length
+                print("   %-11s %5d waves: first / median / last end at %.3f / %.3f / %.3f of the kernel's %.1f us; idle after their ends %.2f %% of all wave-slot time" % (
+                    name, int(sel.sum()), e.min(), np.median(e), e.max(), length, 100.0 * idle[sel].sum() / (length * len(us))), flush=True)
+            print("   idle wave-slot time between a wave's end and the kernel's: %.2f %% of all" % (100.0 * idle.sum() / (length * len(us))), flush=True)
         # what sharing work inside a block (4 consecutive waves) could reach at best: the slowest block's mean against the slowest wave
         work = (us[:, 2] - us[:, 0])
         nb = len(work) // 4
